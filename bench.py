@@ -10,8 +10,11 @@ replicated front end + propagate, builds the Jacobians / nullspace / gate / comp
 feature shard, and the per-rank information blocks [A|b] are exchanged with ONE all-gather (RCCL)
 per frame, enqueued by the library on the handle's filter stream (rvio_hip_frame_sharded_dev: one
 C-ABI call per frame); the same frames are processed by the whole group => "scaling": "strong".
-Every frame index goes through FrameSet.args, which refuses anything outside the resident sequence;
-secondary legs fail soft ({"error": ...}) — tests/test_gpu_bench.py runs the driver's own command.
+Every frame index goes through FrameSet.args, which refuses anything outside the resident sequence.
+
+A plain run sets up, warms up, times the steps and prints the headline.  --full adds the secondary legs (CPU baselines and parity,
+stage and pose latencies, roofline, host buffers, multi-stream and batched modes, the sharded side modes); they fail soft
+({"error": ...}) — tests/test_gpu_bench.py runs both forms.  --dump-outputs DIR writes what the timed path left behind.
 
 Prints ONE JSON line on rank 0.
 """
@@ -35,18 +38,52 @@ PARITY_FRAMES = 141   # frames of the free-running device-vs-CPU comparison
 ROOFLINE_FRAMES = 141  # frames the stage latencies and the roofline candidates are measured after (fixed: independent of --steps)
 PEAK_F64_ = 78.6      # TFLOP/s FP64 (vector == matrix), public MI355X spec
 CPU_WARM, CPU_TIMED = 50, 300   # the CPU baseline is p50 / p95 over >= 300 frames after 50 warm-up frames
+# Rendering costs ~50 ms of host time per frame, so the resident sequence is bounded: it ends one period of the synthetic trajectory after
+# its start-up ramp (rates are multiples of 0.1 rad/s: 20 pi s = 1256.6 frames at 20 Hz), and longer runs go round that period again.
+# At the seam the camera moves 0.032 s worth of the trajectory instead of 0.05 s; every frame before the seam is what it always was.
+LOOP_FIRST = 41     # frame index of t = 4.0 s, where the ramp ends
+LOOP_LEN = 1257
 
 
-def build_inputs(cfg, n_frames, seed=0):
-    """Render the sequence on the host (untimed): frames, IMU batches, detector corner lists."""
-    seq = synth.SynthSequence(cfg, duration=(K0 + n_frames + 3) / 20.0, seed=seed)
+def resident_frames(n_frames):
+    return min(n_frames, LOOP_FIRST + LOOP_LEN)
+
+
+def loop_frame(i):
+    """resident frame that step i of the run (seed frame = 0) hands over"""
+    return i if i < LOOP_FIRST + LOOP_LEN else LOOP_FIRST + (i - LOOP_FIRST) % LOOP_LEN
+
+
+def _render(cfg, duration, seed, ks):
+    seq = synth.SynthSequence(cfg, duration=duration, seed=seed)
+    return [seq.render(k) for k in ks]
+
+
+def render_workers(n_frames):
+    """worker processes for build_inputs: up to 16, one per 32 frames, within the CPUs this process may use"""
+    return min(16, len(os.sched_getaffinity(0)), n_frames // 32)
+
+
+def build_inputs(cfg, n_frames, seed=0, workers=1):
+    """Render the sequence on the host (untimed): frames, IMU batches, detector corner lists.  A frame is a pure function of its index, so
+    with workers > 1 the frames are rendered by that many worker processes (fresh interpreters, not forks): the same bytes, a fraction of
+    the wait.  Spawned workers import the caller's __main__ script again, so only a caller whose top level is guarded may ask for them."""
+    duration = (K0 + n_frames + 3) / 20.0
+    seq = synth.SynthSequence(cfg, duration=duration, seed=seed)
     F = cfg.n_features
     imgs = np.zeros((n_frames, cfg.height, cfg.width), np.uint8)
+    if workers > 1:
+        import concurrent.futures
+        import multiprocessing
+        parts = [[int(K0 + 1 + i) for i in p] for p in np.array_split(np.arange(n_frames), workers)]
+        with concurrent.futures.ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("spawn")) as ex:
+            imgs[:] = [img for part in ex.map(_render, [cfg] * workers, [duration] * workers, [seed] * workers, parts) for img in part]
     imus, cands = [], []
     mmax = 0
     for i in range(n_frames):
         k = K0 + 1 + i
-        imgs[i] = seq.render(k)
+        if workers <= 1:
+            imgs[i] = seq.render(k)
         xy, vis = seq.project(k, noise=False)
         cand, _ = seq.candidates(k, xy, vis)
         imu = seq.imu_between(k)
@@ -162,7 +199,24 @@ def main():
     ap.add_argument("--no-defined-load", action="store_true", help="skip the batched filter at SURVEY 8d's defined load (profiling passes of the natural-flow leg)")
     ap.add_argument("--streams", type=int, default=8, help="independent filter instances for the aggregate-throughput leg")
     ap.add_argument("--stream-threads", type=int, default=1, help="host threads issuing the launches of the aggregate-throughput leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs (the options above: CPU baselines, parity, latencies, roofline, other modes and batch sizes); "
+                         "without it the run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path left after its last step (state, covariance, pose, tracker points, frame counters) as DIR/<name>.npy")
     args = ap.parse_args()
+
+    # Tracker.EnableEqualizer: 1 in the stock config (config/rvio_euroc.yaml): CLAHE runs on every frame
+    cfg = abi.config_named(args.config, enable_equalizer=0 if args.no_equalizer else 1)
+    K, W = args.steps, args.warmup
+    if K < 1 or W < 0:
+        raise SystemExit("--steps >= 1 and --warmup >= 0")
+    n_frames = 1 + W + K   # first image (seed) + warmup + timed
+    n_res = resident_frames(n_frames)
+    seq, imgs, imu_arr, imu_cnt, cand_arr, cand_cnt = build_inputs(cfg, n_res, workers=render_workers(n_res))   # (before the GPU is touched)
+    if not args.host_corners:
+        # stock behaviour: FeatureDetector::DetectWithSubPix runs inside the library (NULL corner list), also in the CPU baseline
+        cand_arr, cand_cnt = None, np.zeros_like(cand_cnt)
 
     import torch
     import torch.distributed as dist
@@ -184,17 +238,6 @@ def main():
         os.environ.setdefault("RANK", "0")
         os.environ.setdefault("WORLD_SIZE", "1")
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-
-    # Tracker.EnableEqualizer: 1 in the stock config (config/rvio_euroc.yaml): CLAHE runs on every frame
-    cfg = abi.config_named(args.config, enable_equalizer=0 if args.no_equalizer else 1)
-    K, W = args.steps, args.warmup
-    if K < 1 or W < 0:
-        raise SystemExit("--steps >= 1 and --warmup >= 0")
-    n_frames = 1 + W + K   # first image (seed) + warmup + timed
-    seq, imgs, imu_arr, imu_cnt, cand_arr, cand_cnt = build_inputs(cfg, n_frames)
-    if not args.host_corners:
-        # stock behaviour: FeatureDetector::DetectWithSubPix runs inside the library (NULL corner list), also in the CPU baseline
-        cand_arr, cand_cnt = None, np.zeros_like(cand_cnt)
 
     h = hip.RvioHip(cfg, device=local_rank)
     stream = torch.cuda.ExternalStream(h.stream(), device=torch.device("cuda", local_rank))
@@ -236,7 +279,7 @@ def main():
     frame = make_frame(h, fs, gathered)
 
     for i in range(1 + W):
-        frame(i)
+        frame(loop_frame(i))
     h.sync()
     torch.cuda.synchronize()
     if sharded:      # RCCL may have printed its version banner through C stdio: push it out now, the JSON line must come last
@@ -249,7 +292,7 @@ def main():
     with torch.cuda.stream(stream):
         ev0.record()
     for i in range(1 + W, n_frames):
-        frame(i)
+        frame(loop_frame(i))
     t_enq = time.perf_counter() - t0          # host time to enqueue the K frames (launch-rate bound if close to the total)
     with torch.cuda.stream(stream):
         ev1.record()
@@ -266,6 +309,13 @@ def main():
     gpu_ms = ev0.elapsed_time(ev1)
     info = h.frame_info()
     x_gpu, P_gpu = h.get_state()
+    if args.dump_outputs and rank == 0:
+        pos, quat = h.pose()
+        xy, ids = h.get_points()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("state", x_gpu), ("covariance", P_gpu), ("pose_p", pos), ("pose_q", quat), ("tracker_points", xy), ("tracker_ids", ids),
+                        ("frame_info", [info[k] for k in sorted(info)])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, np.float32 if name == "tracker_points" else np.float64))
     h.close()      # (the first live handle of a process owns private hardware queues: every secondary leg below measures a handle of its own)
 
     out = {
@@ -299,20 +349,20 @@ def main():
                 long_in = (pi, pa, pc, pca, pcc) if args.host_corners else (pi, pa, pc, None, np.zeros_like(pcc))
         return long_in
 
-    if sharded and not args.no_streams:
+    if args.full and sharded and not args.no_streams:
         def side_modes():
             # beside the sharded figure: every rank ALSO runs the same K frames as an independent camera stream on its own handle (N cameras
             # on N GPUs, no collective) — the weak-scaling counterpart of `value`, reported in its own object
             h2 = hip.RvioHip(cfg, device=local_rank)
             h2.initialize(wi, ai, ni)
             for i in range(1 + W):
-                h2.frame_dev(*fs.args(i))
+                h2.frame_dev(*fs.args(loop_frame(i)))
             h2.sync()
             if world > 1:
                 dist.barrier()
             t0 = time.perf_counter()
             for i in range(1 + W, n_frames):
-                h2.frame_dev(*fs.args(i))
+                h2.frame_dev(*fs.args(loop_frame(i)))
             h2.sync()
             if world > 1:
                 dist.barrier()
@@ -386,12 +436,12 @@ def main():
                 out["independent_streams"] = {"error": repr(e)[:300]}
             if args.config != "E":
                 safe_leg(out, "sharded_cfgE", lambda: (sharded_cfg_e(), out["sharded_cfgE"])[1])
-    if rank == 0 and world == 1 and not args.no_streams:
+    if args.full and rank == 0 and world == 1 and not args.no_streams:
         # (first of the extra legs: a process normally owns ONE handle.  HIP multiplexes its streams onto 4 hardware queues in creation
         # order; a handle created after dozens of other streams — the later legs — can find two of its three streams on one queue and
         # loses their overlap: 2.3 k instead of 4.1 k frames/s were measured for this leg when it ran last)
-        safe_leg(out, "host_buffers", host_buffer_leg, cfg, fs, wi, ai, ni, 1 + W)
-    if rank == 0 and not args.no_latency:
+        safe_leg(out, "host_buffers", host_buffer_leg, cfg, fs, wi, ai, ni, 1 + W, n_frames)
+    if args.full and rank == 0 and not args.no_latency:
         # (also at N>1: the per-kernel roofline is a property of one GPU; the other ranks wait in the barrier below)
         x_single = None
         try:
@@ -424,9 +474,9 @@ def main():
         out.pop("x_at_cpu_frames", None)
     if world > 1:
         dist.barrier()
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_streams:
-            safe_leg(out, "multi_stream", multi_stream, cfg, fs, wi, ai, ni, 1 + W, streams=args.streams, threads=args.stream_threads)
+            safe_leg(out, "multi_stream", multi_stream, cfg, fs, wi, ai, ni, 1 + W, streams=args.streams, threads=args.stream_threads, n_frames=n_frames)
         if not args.no_latency:
             safe_leg(out, "update_at_load", update_at_load_leg, cfg, torch, name=args.config)
         if args.batch_streams:
@@ -831,13 +881,13 @@ def batched_at_load_leg(cfg, torch, sizes, name="B", reps=10):
             "peak_tflops_fp64": PEAK_F64, "sizes": res}
 
 
-def multi_stream(cfg, fs, wi, ai, ni, n_warm, streams=8, threads=1):
+def multi_stream(cfg, fs, wi, ai, ni, n_warm, streams=8, threads=1, n_frames=None):
     """Aggregate throughput of `streams` independent filter instances (own handle, own HIP streams) fed the same resident
     frames: kernels of different instances overlap on the 256 CUs.  `threads` host threads issue the launches (each drives
-    streams/threads instances; the C-ABI calls release the GIL)."""
+    streams/threads instances; the C-ABI calls release the GIL).  n_frames (default fs.n) steps, going round the loop like the timed run."""
     import threading
     from rvio_amd import hip
-    n_frames = fs.n
+    n_frames = fs.n if n_frames is None else n_frames
     n_warm = max(0, min(n_warm, n_frames - 1))
     hs = [hip.RvioHip(cfg) for _ in range(streams)]
     for h in hs:
@@ -845,7 +895,7 @@ def multi_stream(cfg, fs, wi, ai, ni, n_warm, streams=8, threads=1):
 
     def run(mine, lo, hi):
         for i in range(lo, hi):
-            a = fs.args(i)
+            a = fs.args(loop_frame(i))
             for h in mine:
                 h.frame_dev(*a)
         for h in mine:
@@ -871,20 +921,20 @@ def multi_stream(cfg, fs, wi, ai, ni, n_warm, streams=8, threads=1):
             "note": "independent handles (3 streams each) issued from one host thread onto HIP's 4 hardware queues: superseded by batch handles (batched_streams)"}
 
 
-def host_buffer_leg(cfg, fs, wi, ai, ni, n_warm):
+def host_buffer_leg(cfg, fs, wi, ai, ni, n_warm, n_frames=None):
     """PCIe-inclusive rate: the same frames handed over as HOST buffers (rvio_hip_frame: image + IMU + corners copied H2D on
-    the tracker stream every frame).  Reported beside `value`, never as `value`."""
+    the tracker stream every frame).  Reported beside `value`, never as `value`.  n_frames (default fs.n) steps, going round the loop."""
     from rvio_amd import hip
     h = hip.RvioHip(cfg)
     h.initialize(wi, ai, ni)
-    n = fs.n
+    n = fs.n if n_frames is None else n_frames
     n_warm = max(0, min(n_warm, n - 1))
     for i in range(n_warm):
-        h.frame(*fs.host(i))
+        h.frame(*fs.host(loop_frame(i)))
     h.sync()
     t0 = time.perf_counter()
     for i in range(n_warm, n):
-        h.frame(*fs.host(i))
+        h.frame(*fs.host(loop_frame(i)))
     h.sync()
     el = time.perf_counter() - t0
     h.close()

@@ -118,6 +118,47 @@ def test_a_failing_secondary_leg_becomes_an_error_object():
     assert out["value"] == 1.0 and "leg died" in out["pose_latency_unpipelined"]["error"]
 
 
+def test_long_runs_go_round_one_period_of_the_trajectory():
+    """past the resident sequence the steps replay its last trajectory period; at the seam the camera moves forward by less than a step"""
+    n_res = bench.resident_frames(10 ** 6)
+    assert bench.resident_frames(300) == 300 and [bench.loop_frame(i) for i in range(n_res)] == list(range(n_res))
+    for i in range(n_res, n_res + 3 * bench.LOOP_LEN):
+        assert bench.LOOP_FIRST <= bench.loop_frame(i) < n_res and bench.loop_frame(i) == bench.loop_frame(i - bench.LOOP_LEN)
+    seq = bench.synth.SynthSequence(bench.abi.config_named("B"), duration=(bench.K0 + n_res + 3) / 20.0)
+
+    def move(a, b):
+        (Ra, pa), (Rb, pb) = (seq.pose(seq.frame_time(bench.K0 + 1 + i)) for i in (a, b))
+        return np.array([np.linalg.norm(pb - pa), np.linalg.norm(Rb - Ra)])
+    assert float(bench.synth._ramp(seq.frame_time(bench.K0 + 1 + bench.LOOP_FIRST))) == 1.0
+    seam, step = move(n_res - 1, bench.LOOP_FIRST), move(n_res - 2, n_res - 1)
+    assert np.all(seam <= 0.7 * step) and np.all(seam >= 0.5 * step), (seam, step)
+
+
+def test_legs_longer_than_the_resident_sequence_go_round_its_loop(monkeypatch):
+    """--full's host-buffer and multi-stream legs run as many steps as the timed run, past the resident sequence through loop_frame"""
+    from rvio_amd import hip
+    monkeypatch.setattr(hip, "RvioHip", FakeHandle)
+    cfg = bench.abi.config_named("B")
+    n_res = bench.resident_frames(10 ** 6)
+    n_frames = n_res + bench.LOOP_LEN + 7
+    FakeHandle.fs, FakeHandle.seen = bench.FrameSet.fake(cfg, n_res), []
+    r = bench.host_buffer_leg(cfg, FakeHandle.fs, None, None, 0, 6, n_frames)
+    assert len(FakeHandle.seen) == n_frames and r["value"] > 0
+    FakeHandle.seen = []
+    r = bench.multi_stream(cfg, FakeHandle.fs, None, None, 0, 6, streams=2, n_frames=n_frames)
+    assert sorted(FakeHandle.seen) == sorted([bench.loop_frame(i) for i in range(n_frames)] * 2) and r["frames_per_stream"] == n_frames - 6
+
+
+def test_parallel_rendering_gives_the_same_frames():
+    """workers > 1 (only bench.main asks for them): the same bytes as rendering in order"""
+    cfg = bench.abi.config_named("B")
+    n = 70
+    imgs = bench.build_inputs(cfg, n, workers=2)[1]
+    seq = bench.synth.SynthSequence(cfg, duration=(bench.K0 + n + 3) / 20.0)
+    for i in (0, 33, n - 1):
+        assert np.array_equal(imgs[i], seq.render(bench.K0 + 1 + i)), i
+
+
 def test_batch_size_entries():
     """--batch entries: plain counts and "instances x handles" """
     assert bench.parse_batch_size("2048") == (2048, 1) and bench.parse_batch_size(256) == (256, 1)

@@ -14,7 +14,7 @@ for C in $CFGS; do
   python tools/pmc_traffic.py $F $W --json $OUT/pmc_traffic_cfg$C.json > $OUT/pmc_traffic_cfg$C.md 2>&1
   cp $OUT/pmc_traffic_cfg$C.json profiles/r03_pmc_traffic_cfg$C.json
   rm -rf $OUT/pmc_${C}_FETCH_SIZE $OUT/pmc_${C}_WRITE_SIZE
-  timeout 260 python bench.py --config $C --steps 60 --warmup 20 --batch '' --batch-streams '' --no-streams > $OUT/bench_cfg$C.json 2> /dev/null
+  timeout 260 python bench.py --config $C --steps 60 --warmup 20 --full --batch '' --batch-streams '' --no-streams > $OUT/bench_cfg$C.json 2> /dev/null
   python - <<EOF
 import json
 try:
