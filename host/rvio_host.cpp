@@ -157,7 +157,33 @@ System::System(const Settings& s, int device) : s_(s) {
 System::~System() {
     delete static_cast<std::ofstream*>(f_pose_);
     delete static_cast<std::ofstream*>(f_time_);
+    delete static_cast<std::ofstream*>(f_lm_);
     if (h_) rvio_hip_destroy(h_);
+}
+
+bool System::record_landmarks_to(const std::string& path) {
+    if (!h_) return false;
+    auto* f = new std::ofstream(path, std::ofstream::out);
+    if (!*f) { delete f; err_ = "cannot write " + path; return false; }
+    if (rvio_hip_set_landmarks(h_, 1) != RVIO_OK) { delete f; err_ = rvio_hip_last_error(h_); return false; }
+    delete static_cast<std::ofstream*>(f_lm_);
+    f_lm_ = f;
+    const int Fu = (s_.cfg.n_features + 1) / 2;
+    lm_feat_.assign(Fu, 0); lm_pr_.assign((size_t)3 * Fu, 0.0); lm_pw_.assign((size_t)3 * Fu, 0.0);
+    lm_last_ = -1;
+    return true;
+}
+
+// behind a filtered frame: the cloud of the frame's update, if it had one (the stamp is new)
+int System::write_landmarks(double t) {
+    int32_t n = 0, frame = -1;
+    if (rvio_hip_get_landmarks(h_, &n, &frame, lm_feat_.data(), lm_pr_.data(), lm_pw_.data()) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+    if (frame < 0 || frame == lm_last_) return 0;
+    lm_last_ = frame;
+    auto& f = *static_cast<std::ofstream*>(f_lm_);
+    f << format_landmarks(t, frame, n, lm_feat_.data(), lm_pw_.data(), lm_pr_.data());
+    f.flush();
+    return 0;
 }
 
 bool System::record_to(const std::string& dir, bool force) {
@@ -231,6 +257,7 @@ int System::MonoVIO(PoseLine* pose) {
             pose->t = image.t;
             if (rvio_hip_get_pose(h_, pose->p, pose->q) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
         }
+        if (f_lm_ && write_landmarks(image.t) < 0) return -1;
         return 1;
     }
     // INI.RecordOutputs: the same body stage by stage with the host waiting behind each, t1 / t2 / t3 taken where upstream takes them
@@ -252,6 +279,7 @@ int System::MonoVIO(PoseLine* pose) {
     auto& ft = *static_cast<std::ofstream*>(f_time_);
     fp << format_pose(pl); fp.flush();
     ft << format_time_cost(n_img_, t2 - t1, t3 - t2); ft.flush();
+    if (f_lm_ && write_landmarks(image.t) < 0) return -1;
     if (pose) *pose = pl;
     return 1;
 }
@@ -266,6 +294,17 @@ std::string format_pose(const PoseLine& p) {
     char buf[512];
     std::snprintf(buf, sizeof buf, "%.19g %.19g %.19g %.19g %.19g %.19g %.19g %.19g\n", p.t, p.p[0], p.p[1], p.p[2], p.q[0], p.q[1], p.q[2], p.q[3]);
     return buf;
+}
+
+std::string format_landmarks(double t, int frame, int n, const int32_t* feat, const double* p_world, const double* p_r) {
+    std::string out;
+    char buf[512];
+    for (int i = 0; i < n; ++i) {
+        const double *w = p_world + 3 * i, *r = p_r + 3 * i;
+        std::snprintf(buf, sizeof buf, "%.19g %d %d %.19g %.19g %.19g %.19g %.19g %.19g\n", t, frame, (int)feat[i], w[0], w[1], w[2], r[0], r[1], r[2]);
+        out += buf;
+    }
+    return out;
 }
 
 // ------------------------------------------------------------------ images

@@ -83,6 +83,10 @@ public:
     // waiting behind each — so that the two spans of time_cost.dat (System.cc:254-260,367: t2-t1 and t3-t2, milliseconds) mean what they
     // mean there; without it the frame is one pipelined rvio_hip_frame call.  No-op unless the settings ask for it (or `force`).
     bool record_to(const std::string& dir, bool force = false);
+    // Updater::update's landmark cloud (Updater.cc:78-87,430-448,458: what the reference publishes on /rvio/landmarks): enables it on the
+    // handle (rvio_hip_set_landmarks) and appends the cloud to `path` behind every frame whose update stamp is new — one line per point,
+    // format_landmarks.  The settings file has no key for it.
+    bool record_landmarks_to(const std::string& path);
     // the handle's sticky device-side flags (rvio_frame_info.reserved[0]: 1 singular pivot, 2 a track dropped, 4 a stage counter timed out,
     // 8 a non-positive gate pivot; 0 = none) — waits for everything in flight, so a replay reads it once at its end.  -1: the query failed.
     int device_flags();
@@ -102,6 +106,11 @@ private:
     bool rec_ = false;
     void* f_pose_ = nullptr;      // std::ofstream* (kept out of the header)
     void* f_time_ = nullptr;
+    void* f_lm_ = nullptr;        // std::ofstream* of record_landmarks_to
+    int lm_last_ = -1;            // frame stamp of the last cloud written
+    std::vector<int32_t> lm_feat_;
+    std::vector<double> lm_pr_, lm_pw_;
+    int write_landmarks(double t);
 };
 
 // 8-bit PNG (non-interlaced; gray, RGB or RGBA: channels in file order = RGB) or binary PGM / PPM (P5 / P6, maxval 255)
@@ -115,6 +124,8 @@ struct AslDataset {
 bool read_asl(const std::string& root, AslDataset* out, std::string* err);
 
 std::string format_pose(const PoseLine& p);               // one line of stamped_pose_ests.dat, setprecision(19)
+// the points of one cloud (rvio_hip_get_landmarks), one line each: t frame feat xw yw zw xr yr zr (world frame, then {Rk} as published), %.19g
+std::string format_landmarks(double t, int frame, int n, const int32_t* feat, const double* p_world, const double* p_r);
 std::string format_time_cost(int n_img, double track_ms, double filter_ms);   // one line of time_cost.dat (System.cc:376-378)
 
 }  // namespace rvio

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 5   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at) */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -302,6 +302,27 @@ int rvio_hip_frame_sharded_dev(rvio_hip* h, const uint8_t* d_img, int stride, co
 int rvio_hip_get_update_diag(rvio_hip* h, int32_t* n_feat, int32_t* accepted, double* gamma,
                              int32_t* ndof, double* pfinv /* n_feat x 3 */);
 
+/* --- landmark cloud ---------------------------------------------------------- */
+/* Updater::update's landmark cloud (Updater.cc:78-87,430-448,458). Off by default; takes effect from the next update enqueued;
+ * on a batch handle for every instance.  The first enable drains the handle and allocates the cloud's buffers; with the cloud off a
+ * handle launches what it launched before.  One cloud per update call, also when the update itself is then skipped (<= 2 accepted
+ * features) and when it is empty; frames without an update leave the last cloud in place. */
+int rvio_hip_set_landmarks(rvio_hip* h, int enable);
+/* The cloud of the most recent update: n points, frame = nImageCountAfterInit when that update was issued (-1: none since create /
+ * rvio_hip_initialize), feat[i] = index in that frame's hand-over list (ascending), p_r = points in {Rk} as published, p_world =
+ * R(qG)^T (p_r - pG) with the updated state. Buffers hold ceil(n_features/2) entries; any pointer may be NULL. Synchronises like
+ * the other getters. RVIO_ERR_STATE if the cloud was never enabled. Batch handle: instance 0 (_at: any instance; RVIO_ERR_INVALID
+ * out of range).  rvio_hip_initialize clears the cloud (n = 0, frame = -1) and keeps the enable flag.
+ * A point is a feature that passed the chi^2 gate (Updater.cc:422) with rho > 0 (Updater.cc:430): rank-truncated type-'1' features
+ * are in it, a feature accepted with rho = 0 is not.  p_r = R_k (R_ic e / rho + t_ic) + t_k, (R_k, t_k) the end of the feature's
+ * relative-pose chain in xk1k (Updater.cc:114-131).
+ * Feature-sharded handles (rvio_hip_update_local / _global, rvio_hip_frame_sharded_dev): the cloud is what THIS rank's per-feature
+ * stage accepted — the features f with f % world == rank, except for an update handed at most 24 features (the literal path,
+ * csrc/literal.h LIT_FEATS), where every rank builds every feature and so holds the whole cloud.  `feat` lets a caller merge the
+ * ranks' clouds; p_world is the same on every rank (the updated state is replicated).  The all-gather payload carries no cloud. */
+int rvio_hip_get_landmarks(rvio_hip* h, int32_t* n, int32_t* frame, int32_t* feat, double* p_r, double* p_world);
+int rvio_hip_get_landmarks_at(rvio_hip* h, int instance, int32_t* n, int32_t* frame, int32_t* feat, double* p_r, double* p_world);
+
 /* pyramid level of the most recent image (u8 w*h, int16 (dx,dy) w*h*2) and the raw KLT output
  * (vFeatsTracked + its undistorted-normalised form) of the last track() call */
 int rvio_hip_debug_pyramid(rvio_hip* h, int level, int32_t* w, int32_t* hgt, uint8_t* img, int16_t* dxy);
@@ -311,7 +332,10 @@ int rvio_hip_debug_tracked(rvio_hip* h, int n, float* xy, float* un_xy);
  * which: 0 = solve kernel, 1 = KLT kernel (the current image matched back onto the previous one from the current feature positions),
  * 2 = per-feature Jacobian/nullspace/gate kernel, 3 = reduction of the per-feature information shares (+ rank truncation),
  * 4 = U/G/P1 strips, 5 = Joseph-form kernel (4, 5: the two-launch forms), 6 = cornerSubPix on the last corner list,
- * 7 = U/G/P1 + Joseph form as this handle launches them for an update (one instance, 6n <= 60: one fused kernel). */
+ * 7 = U/G/P1 + Joseph form as this handle launches them for an update (one instance, 6n <= 60: one fused kernel),
+ * 8 = the per-feature kernel with propagate fused in, as the pipelined frame launches it, 9 = the detector's selection kernel,
+ * 10 = the landmark cloud kernel on the hand-over table and per-feature results of the last update (into buffers of its own: the
+ * cloud rvio_hip_get_landmarks returns is left alone; RVIO_ERR_UNSUPPORTED unless the cloud was enabled). */
 int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us);
 /* Test hook against results that depend on LEFT-OVER state (scratch in HBM, LDS contents, stale hand-over entries).  Drains every stream of
  * the handle, then: what & 1 fills the filter's scratch and the spare state / covariance buffer with 0xff bytes (NaN); & 2 rewrites the LDS

@@ -22,6 +22,7 @@
 #include "solve6.hip"
 #include "solve7.hip"
 #include "solve9.hip"   // round 5: the solve as blocked SPD factorisations on the matrix cores (one instance; every window up to 6n = 192)
+#include "landmarks.hip"   // Updater::update's landmark cloud (rvio_hip_set_landmarks)
 #ifndef S9_BATCH
 #define S9_BATCH (ab_env("RVIO_S9_BATCH") != nullptr)   // A/B timing: batch handles at 6n <= 64 through solve9_kernel<1, 4> instead of gemm_T + solve6
 #endif
@@ -177,6 +178,11 @@ struct rvio_hip {
     int* cand_scratch = nullptr;
     rvio_frame_info* d_info = nullptr;
     double* d_pose = nullptr;
+    // landmark cloud of the last update (landmark_kernel): allocated on the first rvio_hip_set_landmarks(1), outside the filter slab (a handle
+    // that never enables it keeps its memory layout); one cloud per instance, lm.bs bytes apart
+    bool lm_on = false;
+    int lm_frame = -1;       // nImageCountAfterInit when the update behind the cloud was enqueued, -1: none since create / initialize
+    LmOut lm = {nullptr, nullptr, nullptr, nullptr, 0};
 };
 
 // ---------------------------------------------------------------- environment surface of the SHIPPING library: two variables.
@@ -790,6 +796,7 @@ int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n
     for (int i = 18; i < 21; ++i) D(i, n_imu * dt * std::pow(c.sigma_wg, 2));
     for (int i = 21; i < 24; ++i) D(i, n_imu * dt * std::pow(c.sigma_wa, 2));
     h->img_count = 0;
+    h->lm_frame = -1;   // no cloud since initialisation (the enable flag stays)
     // a (re-)initialised filter starts with an empty window: the tracker starts over too (mbIsTheFirstImage, Tracker.cc:88), or its
     // histories would be longer than the window they refer to
     if (h->front_end) {
@@ -1083,6 +1090,26 @@ static void launch_ug_final(rvio_hip* h, int n, const double* Ab, double* Pn, bo
     }
 }
 
+// Updater::update's landmark cloud behind the update just enqueued (h->cur already toggled): one workgroup per instance, a lane per feature slot
+static void launch_landmarks(rvio_hip* h, int n, const LmOut& out) {
+    const int T = std::min(LM_MAX_T, 64 * ((h->dc.Fu + 63) / 64));
+    hipLaunchKernelGGL(landmark_kernel, dim3(1, 1, h->batch), dim3(T), 0, h->stream, h->dc, n, (const double*)h->x[h->cur ^ 1], (const double*)h->x[h->cur],
+                       (const int*)h->t.n_feat, (const unsigned char*)h->t.types, (const int*)h->t.len, (const int*)h->acc, (const double*)h->pfinv,
+                       h->slab_bytes, h->bin, out);
+}
+// the cloud buffers of every instance in one allocation (count | feat[Fu] | p_r[Fu][3] | p_w[Fu][3], 256-byte aligned parts)
+static int lm_alloc(rvio_hip* h, LmOut* out) {
+    const size_t Fu = (size_t)h->dc.Fu;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_feat = 256, o_pr = o_feat + up(sizeof(int) * Fu), o_pw = o_pr + up(sizeof(double) * 3 * Fu), bs = o_pw + up(sizeof(double) * 3 * Fu);
+    char* p = nullptr;
+    HIPCHK(h, hipMalloc((void**)&p, bs * h->batch));
+    h->allocs.push_back(p);
+    HIPCHK(h, hipMemsetAsync(p, 0, bs * h->batch, h->stream));
+    *out = LmOut{(int*)p, (int*)(p + o_feat), (double*)(p + o_pr), (double*)(p + o_pw), bs};
+    return RVIO_OK;
+}
+
 // combined: d_blocks is the handle's own block, already turned into [A|b] by gram_reduce_kernel (unsharded update)
 static int update_global_dev(rvio_hip* h, const double* d_blocks, int world, bool combined) {
     const DevCfg& d = h->dc;
@@ -1113,6 +1140,11 @@ static int update_global_dev(rvio_hip* h, const double* d_blocks, int world, boo
     launch_ug_final(h, n, Ab, Pn, true, true);
     HIPCHK(h, hipGetLastError());
     h->cur ^= 1;
+    if (h->lm_on) {   // the cloud: x[cur] is xk1k1 now, x[cur ^ 1] still xk1k (every update form writes the other buffer; augcomp_kernel2 rewrites it next)
+        launch_landmarks(h, n, h->lm);
+        HIPCHK(h, hipGetLastError());
+        h->lm_frame = h->img_count;
+    }
     return RVIO_OK;
 }
 
@@ -1162,6 +1194,44 @@ int rvio_hip_get_update_diag(rvio_hip* h, int32_t* n_feat, int32_t* accepted, do
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RVIO_OK;
+}
+
+// ------------------------------------------------------------------ landmark cloud (Updater.cc:78-87,430-448,458)
+int rvio_hip_set_landmarks(rvio_hip* h, int enable) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (enable && !h->lm.count) {   // first enable: the buffers are allocated with nothing in flight
+        { const int rc = drain_all(h); if (rc != RVIO_OK) return rc; }
+        { const int rc = lm_alloc(h, &h->lm); if (rc != RVIO_OK) return rc; }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    h->lm_on = enable != 0;
+    return RVIO_OK;
+}
+int rvio_hip_get_landmarks_at(rvio_hip* h, int instance, int32_t* n, int32_t* frame, int32_t* feat, double* p_r, double* p_world) {
+    if (!h || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
+    if (!h->lm.count) { h->err = "the landmark cloud was never enabled (rvio_hip_set_landmarks)"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    SYNC_FRONT(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t o = (size_t)instance * h->lm.bs;
+    int cnt = 0;
+    if (h->lm_frame >= 0) {
+        HIPCHK(h, hipMemcpyAsync(&cnt, (char*)h->lm.count + o, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        cnt = std::max(0, std::min(cnt, h->dc.Fu));
+    }
+    if (n) *n = cnt;
+    if (frame) *frame = h->lm_frame;
+    if (cnt > 0) {
+        if (feat) HIPCHK(h, hipMemcpyAsync(feat, (char*)h->lm.feat + o, sizeof(int) * cnt, hipMemcpyDeviceToHost, h->stream));
+        if (p_r) HIPCHK(h, hipMemcpyAsync(p_r, (char*)h->lm.p_r + o, sizeof(double) * 3 * cnt, hipMemcpyDeviceToHost, h->stream));
+        if (p_world) HIPCHK(h, hipMemcpyAsync(p_world, (char*)h->lm.p_w + o, sizeof(double) * 3 * cnt, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return RVIO_OK;
+}
+int rvio_hip_get_landmarks(rvio_hip* h, int32_t* n, int32_t* frame, int32_t* feat, double* p_r, double* p_world) {
+    return rvio_hip_get_landmarks_at(h, 0, n, frame, feat, p_r, p_world);
 }
 
 // ------------------------------------------------------------------ S1 + S2
@@ -2075,9 +2145,20 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
         HIPCHK(h, hipMemcpyAsync(bx, h->x[h->cur], sizeof(double) * d.xdmax, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(bP, h->P[h->cur], sizeof(double) * d.dmax * d.dmax, hipMemcpyDeviceToDevice, h->stream));
     }
+    LmOut lmt = {nullptr, nullptr, nullptr, nullptr, 0};
+    if (which == 10) {   // (into buffers of its own: the getter's cloud stays the last update's)
+        if (!h->lm.count) return RVIO_ERR_UNSUPPORTED;
+        const int rc = lm_alloc(h, &lmt);
+        if (rc != RVIO_OK) return rc;
+    }
     HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
     HIPCHK(h, hipEventRecord(e0, h->stream));
     for (int it = 0; it < iters; ++it) {
+        if (which == 10) {
+            // landmark_kernel as the update launches it, on the hand-over table, accept flags and (phi, psi, rho) of the last update; the state
+            // buffers are the ones it reads (behind a whole frame: the composed state and xk1k1 — the same arithmetic)
+            launch_landmarks(h, n, lmt);
+        } else
         if (which == 8) {
             // feat_prop_kernel exactly as the pipelined frame launches it: the per-feature workgroups of the last hand-over table + PreIntegrator::propagate on the
             // IMU batch of the last frame (the caller's device buffer must still be alive) + at 6n <= 96 the Cholesky role
@@ -2140,6 +2221,7 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
     HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
     hipEventDestroy(e0); hipEventDestroy(e1);
     if (bx) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(bx); (void)hipFree(bP); }
+    if (lmt.count) { h->allocs.pop_back(); (void)hipFree(lmt.count); }   // (lm_alloc pushed it last; the event above has drained the stream)
     *avg_us = ms * 1e3f / iters;
     HIPCHK(h, hipGetLastError());
     return RVIO_OK;

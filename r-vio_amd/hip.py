@@ -24,6 +24,7 @@ SYMBOLS = [
     "rvio_hip_debug_time_kernel", "rvio_hip_get_corners", "rvio_hip_frame_begin_dev", "rvio_hip_frame_end",
     "rvio_hip_create_batch", "rvio_hip_batch_size", "rvio_hip_set_state_at", "rvio_hip_get_state_at", "rvio_hip_frame_tracks_dev",
     "rvio_hip_frame_batch_dev", "rvio_hip_get_tracker_points_at", "rvio_hip_frame_sharded_dev", "rvio_hip_debug_poison", "rvio_hip_debug_stall", "rvio_hip_debug_noise", "rvio_hip_debug_kernel_forms",
+    "rvio_hip_set_landmarks", "rvio_hip_get_landmarks", "rvio_hip_get_landmarks_at",
 ]
 
 _LIB = None
@@ -176,6 +177,23 @@ class RvioHip:
         self._ck(self.L.rvio_hip_get_update_diag(self.h, C.byref(nf), _p(acc, ip), _p(gam, dp), _p(ndof, ip), _p(pf, dp)), "update_diag")
         n = nf.value
         return dict(accepted=acc[:n], gamma=gam[:n], ndof=ndof[:n], pfinv=pf[:n])
+
+    # ---- landmark cloud (Updater.cc:78-87,430-448,458)
+    def set_landmarks(self, on=True):
+        """compute Updater::update's landmark cloud behind every update from the next one on (all instances of a batch handle)"""
+        self._ck(self.L.rvio_hip_set_landmarks(self.h, int(bool(on))), "set_landmarks")
+
+    def landmarks_at(self, i):
+        """the cloud of the most recent update of instance i: dict(n, frame, feat, p_r, p_world), arrays cut to n"""
+        n, frame = C.c_int32(0), C.c_int32(0)
+        feat, pr, pw = np.zeros(self.Fu, np.int32), np.zeros((self.Fu, 3)), np.zeros((self.Fu, 3))
+        self._ck(self.L.rvio_hip_get_landmarks_at(self.h, int(i), C.byref(n), C.byref(frame), _p(feat, ip), _p(pr, dp), _p(pw, dp)),
+                 "get_landmarks_at")
+        k = n.value
+        return dict(n=k, frame=frame.value, feat=feat[:k].copy(), p_r=pr[:k].copy(), p_world=pw[:k].copy())
+
+    def landmarks(self):
+        return self.landmarks_at(0)
 
     def augment_compose(self, do_augment=True):
         self._ck(self.L.rvio_hip_augment_compose(self.h, int(do_augment)), "augment_compose")
@@ -359,7 +377,7 @@ class RvioHip:
         return xy, un
 
     def time_kernel(self, which, iters=20):
-        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection (HIP events, handle stream)"""
+        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection, 10 the landmark cloud kernel (HIP events, handle stream)"""
         us = C.c_float(0)
         self._ck(self.L.rvio_hip_debug_time_kernel(self.h, int(which), int(iters), C.byref(us)), "debug_time_kernel")
         return float(us.value)
