@@ -66,9 +66,12 @@ typedef struct rvio_config {
     double T_bc[16];                  /* Camera.T_BC0, ROW-major 4x4 (Updater.cc:46-53) */
     int32_t fisheye;                  /* Camera.Fisheye: cv::fisheye::undistortPoints with D = (k1,k2,p1,p2) (Tracker.cc:116-119) */
     /* Tracker.* */
-    int32_t n_features;               /* Tracker.nFeatures          (Tracker.cc:73)  */
-    int32_t max_track_len;            /* Tracker.nMaxTrackingLength (Tracker.cc:78)  */
-    int32_t min_track_len;            /* Tracker.nMinTrackingLength (Tracker.cc:79)  */
+    int32_t n_features;               /* Tracker.nFeatures          (Tracker.cc:73)  supported: 2 .. 4096 (ceil(n/2) <= 2048 hand-over slots);
+                                         beyond it create returns RVIO_ERR_UNSUPPORTED and rvio_hip_last_error names the limit.  Every count in
+                                         the range is created and launched: book-keeping runs with as many waves as one CU's LDS holds beside
+                                         the kernel's static LDS, and as two launches instead of one above 2850 */
+    int32_t max_track_len;            /* Tracker.nMaxTrackingLength (Tracker.cc:78)  supported: 3 .. 32 */
+    int32_t min_track_len;            /* Tracker.nMinTrackingLength (Tracker.cc:79)  >= 2 */
     float   min_dist;                 /* Tracker.nMinDist           (FeatureDetector.cc:31) */
     float   qual_lvl;                 /* Tracker.nQualLvl           */
     float   block_x, block_y;         /* Tracker.nBlockSizeX/Y, stored as float like upstream (FeatureDetector.h:72-73) */

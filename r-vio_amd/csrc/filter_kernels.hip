@@ -37,14 +37,7 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // One workgroup per feature slot.  Dynamic LDS (doubles):
 //   xcl[7*nmax] pose[(L-1)*24] hrr[L*6] hf[2L*3] lr[(L-1)*18] vh[3*2L] misc[16]
 //   Hx[2L][ldh]  ([Hx | r], row-major)   Tm[rho][ldh]   S[(rho+1)][rho+1]
-__host__ __device__ inline size_t feat_lds_doubles(int max_len, int ldh, bool tm_in_lds) {
-    const int L = max_len, M2 = 2 * L, rho = 2 * L - 2;
-    size_t n = (size_t)7 * (L - 1) + (size_t)(L - 1) * 24 + L * 6 + M2 * 3 + (L - 1) * 18 + 3 * M2 + 16;
-    n += (size_t)M2 * ldh;
-    if (tm_in_lds) n += (size_t)rho * ldh;
-    n += (size_t)(rho + 1) * (rho + 1);
-    return n;
-}
+// (feat_lds_doubles(): launch_plan.h)
 // reciprocal of a positive normal double: hardware estimate + two Newton steps (the IEEE division sequence is three times as long)
 __device__ __forceinline__ double fast_rcp(double v) {
     double y = __builtin_amdgcn_rcp(v);
@@ -865,10 +858,8 @@ __global__ __launch_bounds__(64) void geom4_kernel(DevCfg cfg, int n, const doub
 //
 // block = the payload of one shard: part 0 = S2, part 1 = S1 (each c6 x ldh row-major inside an ldh x ldh square); the spare
 // last row of part 0 carries {n_good, n_rows, rows of type '2', e2 (-1: none), min start column of type '1' (TR_NONE: none)}.
-#define GRAM_MAX_FEATS 2048
 #define TR_NONE 1000000000
-__host__ __device__ inline int trunc_mmax(int max_len) { return 6 * ((max_len + 1) / 2 - 1); }   // largest e2 + 1
-__host__ __device__ inline size_t trunc_lds_doubles(int max_len) { const size_t m = trunc_mmax(max_len); return m * (m | 1) + m + 8; }
+// (GRAM_MAX_FEATS, trunc_mmax(), trunc_lds_doubles(): launch_plan.h)
 
 // data written by other workgroups of the same launch: read it from L2 (agent scope), not through this CU's vector cache
 __device__ __forceinline__ double ld_l2(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1097,10 +1088,7 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(DevCfg cfg, int n, con
 // block, ~0.7 GB per launch at B = 2048 for 29 KB of result per instance.  Thread (r, c) owns element (16 pt + r, 16 qt + c) of EVERY tile,
 // so the additions to one element happen in feature order in one thread: deterministic without a barrier between features.  The sum
 // leaves LDS once, lower triangle mirrored.  A truncation candidate (rare) takes two passes (S2, then S1) and trunc_finish.
-__host__ __device__ inline size_t gram_batch_lds_doubles(int max_len, int ldh) {
-    const size_t a = (size_t)(ldh - 1) * ldh, t = trunc_lds_doubles(max_len);
-    return a > t ? a : t;
-}
+// (LDS: gram_batch_lds_doubles(), launch_plan.h)
 template <int NT>      // row / column tiles of [A|b]: 4 for 6n <= 63, 6 for 6n <= 95
 __global__ __launch_bounds__(256) void gram_reduce_batch_kernel(DevCfg cfg, int n, const double* __restrict__ partial, const int* __restrict__ nrows,
                                                                 const unsigned char* __restrict__ types, const int* __restrict__ lens, double* __restrict__ block,

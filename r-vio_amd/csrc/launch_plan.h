@@ -1,0 +1,236 @@
+// launch_plan.h — the launch geometry of a handle as a function of (max_track_len, n_features, batch): every dynamic-LDS size, the kernel
+// variants and the LDS-or-global decisions that rvio_hip_create / rvio_hip_create_batch derive from a configuration.
+//
+// Plain C++: create_impl (rvio_hip.hip) calls launch_plan() and applies what it returns, and tests/hostemu/plan_emu.cpp compiles THIS text with
+// g++ and sweeps every accepted configuration on the CPU (tests/test_launch_plan.py) — a configuration whose footprint does not fit a CU is
+// found by arithmetic, not by a failed launch.  The one input that is not arithmetic is the STATIC LDS of each kernel, which the compiler
+// decides: create_impl reads it from the loaded code object (hipFuncGetAttributes), the test from the notes of the built library.
+#pragma once
+#include <stddef.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define LP_HD __host__ __device__
+#else
+#define LP_HD
+#endif
+
+#define RVIO_MAX_LEN 32          // max Tracker.nMaxTrackingLength supported (cfg E: 31)
+#define RVIO_MAX_FEATURES 4096   // max Tracker.nFeatures supported: ceil(F / 2) hand-over slots <= GRAM_MAX_FEATS
+#define GRAM_MAX_FEATS 2048      // feature slots of an update (the Gram stage lists them in static LDS)
+#define RVIO_LDS_LIMIT 163840    // LDS of a gfx950 CU (160 KiB): what ONE workgroup may hold, static + dynamic
+#define LIT_FEATS 24             // an update handed more features than this never takes the literal path (M <= LIT_FEATS * rho_max rows)
+#define LIT_RING 32              // stack rows of the literal sweep staged in LDS (two blocks of LIT_RING / 2)
+#ifndef FEAT_T_SMALL
+#define FEAT_T_SMALL 128     // threads of a per-feature workgroup at 6n <= 127 (same-box A/B of 64 against 128 at B = 2048: profiles/r06_feat_threads_ab.txt)
+#endif
+#define LIT_STAMPS 5             // phase stamps of the literal sweep (instrumented build)
+#define LIT_STAMP_OFF 200        // their offset behind the second part of the [A|b] block
+
+// ---------------------------------------------------------------- footprints (doubles) of the kernels' dynamic LDS
+// feat_build_kernel, one workgroup per feature slot:
+//   xcl[7*nmax] pose[(L-1)*24] hrr[L*6] hf[2L*3] lr[(L-1)*18] vh[3*2L] misc[16]
+//   Hx[2L][ldh]  ([Hx | r], row-major)   Tm[rho][ldh]   S[(rho+1)][rho+1]
+LP_HD inline size_t feat_lds_doubles(int max_len, int ldh, bool tm_in_lds) {
+    const int L = max_len, M2 = 2 * L, rho = 2 * L - 2;
+    size_t n = (size_t)7 * (L - 1) + (size_t)(L - 1) * 24 + L * 6 + M2 * 3 + (L - 1) * 18 + 3 * M2 + 16;
+    n += (size_t)M2 * ldh;
+    if (tm_in_lds) n += (size_t)rho * ldh;
+    n += (size_t)(rho + 1) * (rho + 1);
+    return n;
+}
+LP_HD inline int trunc_mmax(int max_len) { return 6 * ((max_len + 1) / 2 - 1); }   // largest e2 + 1
+LP_HD inline size_t trunc_lds_doubles(int max_len) { const size_t m = trunc_mmax(max_len); return m * (m | 1) + m + 8; }
+LP_HD inline size_t gram_batch_lds_doubles(int max_len, int ldh) {
+    const size_t a = (size_t)(ldh - 1) * ldh, t = trunc_lds_doubles(max_len);
+    return a > t ? a : t;
+}
+// state of the literal sweep's array: U (running rows), X[2] (rows in flight between cells, double-buffered), each `tri` doubles: cell n owns
+// columns n..Nc (Nc = the residual), offset n (Nc + 1) - n (n - 1) / 2
+LP_HD inline size_t lit_tri(int c6) { return (size_t)c6 * (c6 + 1) / 2 + c6; }
+// LDS of lit_finish besides the state: ring of stack rows, (c, s) pairs of two steps, the level-to-level hand-over of two steps, row norms, the row map
+LP_HD inline size_t lit_aux_doubles(int ldh, int rho_max) { return (size_t)LIT_RING * ldh + 4 * (size_t)ldh + 2 * 256 + ldh + (size_t)(LIT_FEATS * rho_max + 1) / 2 + 8; }
+LP_HD inline size_t lit_state_doubles(int c6) { return 3 * lit_tri(c6); }
+// a feature's raw block in LDS for the nullspace sweep: 2 max_len rows of [Hx columns + residual | Hf (3)]
+LP_HD inline size_t lit_slab_doubles(int ldh, int rho_max) { return (size_t)(rho_max + 2) * (ldh + 3); }
+// the export buffer: LIT_FEATS blocks of 2 max_len rows x ldh, then the Hf blocks (2 max_len x 3 each)
+// + the projected blocks the nullspace sweep leaves (rho_max rows x ldh each): the raw blocks stay as exported, a second run on the same export
+// (rvio_hip_debug_time_kernel) finds what the first one found
+LP_HD inline size_t lit_rows_doubles(int ldh, int rho_max) { return (size_t)LIT_FEATS * (rho_max + 2) * (ldh + 3) + (size_t)LIT_FEATS * rho_max * ldh; }
+// book-keeping's refill half: tfs[F] + cds[F] float2, cid_t[F] + cid_c[F] short, then one list of F float2 per wave (8-byte aligned) + a spare 16
+LP_HD inline size_t book_lds_bytes(int F, int waves) { return (((size_t)20 * F + 7) & ~(size_t)7) + (size_t)waves * F * 8 + 16; }
+
+// ---------------------------------------------------------------- diagnostics in the unused second part of the [A|b] block (2 ldh^2 doubles)
+// lit_scan_gram leaves the row norms its scan saw at [ldh^2, ldh^2 + Nc), Nc <= 6n = ldh - 1; the instrumented build adds LIT_STAMPS phase stamps at
+// ldh^2 + LIT_STAMP_OFF — where the block has room for them (ldh^2 >= LIT_STAMP_OFF + LIT_STAMPS: every window but max_track_len = 3).
+LP_HD inline size_t lit_norm_off(int ldh) { return (size_t)ldh * ldh; }
+LP_HD inline bool lit_stamp_fits(int ldh) { return (size_t)ldh * ldh + LIT_STAMP_OFF + LIT_STAMPS <= 2 * (size_t)ldh * ldh; }
+LP_HD inline size_t lit_stamp_off(int ldh, int k) { return (size_t)ldh * ldh + LIT_STAMP_OFF + k; }
+// one past the last double the diagnostics write (stamps: the instrumented build)
+LP_HD inline size_t lit_diag_end(int ldh, bool stamps) {
+    size_t e = lit_norm_off(ldh) + (size_t)(ldh - 1);
+    if (stamps && lit_stamp_fits(ldh)) { const size_t s = lit_stamp_off(ldh, LIT_STAMPS - 1) + 1; if (s > e) e = s; }
+    return e;
+}
+
+// ---------------------------------------------------------------- sizes the kernel files fix (bytes): rvio_hip.hip static_asserts each against its definition
+#define LP_S9CHOL4_BYTES 35976       // sizeof(S9CholLds<4, 4>)   (solve9.hip)
+#define LP_S9CHOL6_BYTES 44424       // sizeof(S9CholLds<6, 4>)
+#define LP_S9SMALL_BYTES 160328      // sizeof(S9SmallLds)
+#define LP_PROP3_BYTES 86432         // sizeof(Prop3Lds<16>)      (filter_kernels2.hip)
+#define LP_JB_TL_DOUBLES (12 * 16 * 17)                        // JB_TL_DOUBLES   (filter_kernels.hip)
+#define LP_UGL_BYTES ((2 * 64 * 65 + 88 * 65 + 2 * 16 * 65) * 8)   // UGL_LDS_DOUBLES
+#define LP_FNL_BYTES ((3 * 88 * 65 + 4 * 16 * 17) * 8)             // FNL_LDS_DOUBLES
+#define LP_JL_BYTES ((3 * 60 * 61 + 8 * 16 * 61 + 16) * 8)         // JL_LDS_DOUBLES
+#define LP_GEMM_T_LDS_BYTES (2 * 64 * 65 * 8)                      // gemm_T_lds_kernel's operands
+
+// ---------------------------------------------------------------- the kernels create_impl gives a dynamic-LDS limit
+enum LpKernel {
+    LPK_FEAT_BUILD16, LPK_FEAT_BUILD4, LPK_GRAM_REDUCE, LPK_BLOCK_SUM, LPK_LIT_BATCH, LPK_GEMM_T_LDS, LPK_GRAM_BATCH4, LPK_GRAM_BATCH6, LPK_FEAT_PROP,
+    LPK_BOOKKEEP_B, LPK_RANSAC_BOOK, LPK_SOLVE9_SMALL, LPK_SOLVE6_1, LPK_SOLVE6_2, LPK_SOLVE6_3, LPK_JOSEPH_BATCH, LPK_UG, LPK_UG_LDS, LPK_FINAL_LDS,
+    LPK_JOSEPH_LDS, LPK_COUNT
+};
+// (as c++filt prints them, without return type and arguments: how the test finds each kernel's static LDS in the code object's notes)
+static const char* const kLpKernelName[LPK_COUNT] = {
+    "feat_build_kernel<16>", "feat_build_kernel<4>", "gram_reduce_kernel", "block_sum_kernel", "lit_batch_kernel", "gemm_T_lds_kernel",
+    "gram_reduce_batch_kernel<4>", "gram_reduce_batch_kernel<6>", "feat_prop_kernel", "bookkeep_b_kernel", "ransac_book_kernel", "solve9_small_kernel",
+    "solve6_kernel<1, 8, 8>", "solve6_kernel<2, 12, 8>", "solve6_kernel<2, 16, 8>", "joseph_batch_kernel", "ug_kernel", "ug_lds_kernel", "final_lds_kernel",
+    "joseph_lds_kernel"
+};
+
+// A/B switches of the instrumented build (all off in the shipping library)
+struct LaunchSwitches {
+    bool solve6 = false, solve7 = false, s9_batch = false, batch_solve7 = false, no_joseph_fused = false, no_fused_propagate = false;
+    bool dbg_build = false;      // -DRVIO_DBG_CLOCKS: the register-tableau solve's variants stay selectable
+};
+
+struct LaunchPlan {
+    int rc = 0;                  // 0, or 1: the configuration is not supported (why says which limit)
+    const char* why = nullptr;
+    int Fu = 0, ldh = 0, rho_max = 0;
+    int feat_threads = 256;
+    int n_ic = 2;                // image chains in flight
+    bool chol_queue = false;     // long windows (96 < 6n <= 192, one instance): the queue a second image chain would take runs the Cholesky factor of the clone block
+    size_t trunc_lds = 0, lit_batch_lds = 0, feat_lds = 0, fprop_lds = 0, gram_batch_lds = 0, book_lds = 0, solve5_lds = 0, jb_lds = 0, ug_lds = 0;
+    bool lit_state_global = false, tm_global = false, fuse_ok = false;
+    int book_waves = 4;
+    bool book_fused = false;     // RANSAC + both halves of book-keeping in one launch (ransac_book_kernel) fit one CU; else ransac_book_a_kernel + bookkeep_b_kernel
+    int solve5_variant = 0, solve7_variant = 0, solve9_nt = 0;
+    size_t attr[LPK_COUNT] = {}; // dynamic-LDS limit to set per kernel (0: none)
+};
+
+LP_HD inline size_t lp_max(size_t a, size_t b) { return a > b ? a : b; }
+LP_HD inline size_t lp_min(size_t a, size_t b) { return a < b ? a : b; }
+
+// statics[k]: static LDS (bytes) of kernel k of THIS build
+inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size_t* statics, const LaunchSwitches& sw = LaunchSwitches()) {
+    LaunchPlan p;
+    const int nmax = max_len - 1;
+    p.Fu = (n_features + 1) / 2; p.ldh = 6 * nmax + 1; p.rho_max = 2 * max_len - 2;
+    const size_t ldh = p.ldh, c6m = ldh - 1;
+    const int F = n_features;
+    if (max_len < 3 || max_len > RVIO_MAX_LEN || n_features < 2 || batch < 1) { p.rc = 1; p.why = "invalid configuration"; return p; }
+    if (p.Fu > GRAM_MAX_FEATS) { p.rc = 1; p.why = "Tracker.nFeatures too large: at most 4096 (RVIO_MAX_FEATURES; ceil(F/2) hand-over slots <= 2048 in the Gram stage)"; return p; }
+    // Image chains in flight.  Two (default): with the filter, tracker and side streams that makes FOUR busy queues.  Long windows
+    // (96 < 6n <= 192: the solve in its split form, filter chain >= 250 us): ONE image chain in flight is enough (the chain is ~180 us),
+    // and the queue that frees runs the Cholesky factor of the clone block beside the filter chain.
+    if (batch == 1 && c6m > 96 && c6m <= 192) { p.n_ic = 1; p.chol_queue = true; }
+    p.feat_threads = (p.ldh <= 128) ? FEAT_T_SMALL : 256;
+    p.trunc_lds = trunc_lds_doubles(max_len) * sizeof(double);
+    {   // the literal sweep runs in the workgroup that finishes the reduction (literal.h): its ring / rotation tables always in that launch's LDS, the
+        // array's state too when it fits beside gram_reduce_kernel's static LDS — else, and for batch handles (occupancy), in the slab
+        const size_t aux = lit_aux_doubles(p.ldh, p.rho_max) * sizeof(double), st = lit_state_doubles(p.ldh - 1) * sizeof(double);
+        const size_t slab = lit_slab_doubles(p.ldh, p.rho_max) * sizeof(double);   // (a feature's raw block for the nullspace sweep: at least one must fit)
+        p.lit_state_global = batch > 1 || aux + st > 144 * 1024;
+        p.lit_batch_lds = lp_max(aux, slab);
+        p.trunc_lds = lp_max(p.trunc_lds, lp_max(p.lit_state_global ? aux : aux + st, lp_min((size_t)4, (size_t)(144 * 1024) / slab) * slab));
+    }
+    p.feat_lds = feat_lds_doubles(max_len, p.ldh, true) * sizeof(double);
+    // (a batch handle keeps T in global memory as well: a third less LDS per feature workgroup = 8 instead of 5 resident per CU)
+    if (p.feat_lds > 150 * 1024 || batch > 1) {
+        p.feat_lds = feat_lds_doubles(max_len, p.ldh, false) * sizeof(double);
+        p.tm_global = true;
+    }
+    if (p.feat_lds > 160 * 1024) { p.rc = 1; p.why = "per-feature LDS footprint exceeds 160 KiB"; return p; }
+    p.attr[LPK_FEAT_BUILD16] = p.attr[LPK_FEAT_BUILD4] = p.feat_lds;
+    p.attr[LPK_GRAM_REDUCE] = p.attr[LPK_BLOCK_SUM] = p.trunc_lds;
+    p.attr[LPK_LIT_BATCH] = p.lit_batch_lds;
+    if (batch > 1 && gram_batch_lds_doubles(max_len, p.ldh) * sizeof(double) <= 64 * 1024) {
+        p.gram_batch_lds = gram_batch_lds_doubles(max_len, p.ldh) * sizeof(double);
+        p.attr[LPK_GEMM_T_LDS] = LP_GEMM_T_LDS_BYTES;
+        p.attr[LPK_GRAM_BATCH4] = p.attr[LPK_GRAM_BATCH6] = p.gram_batch_lds;
+    }
+    // propagate rides in the per-feature launch: its workgroup builds no feature, so its buffers (Prop3Lds<16>, 86 KB) and the per-feature footprint
+    // share the launch's dynamic LDS — max of the two, which fits one CU for every window (rounds 2-4: static + dynamic, the SUM: long windows
+    // fell back to 8-sample chunks, cfg E to a propagate launch of its own on the chain)
+    p.fprop_lds = p.feat_lds;
+    // (round 5: + the Cholesky role of solve9 at 6n <= 96 — one more workgroup whose buffers live in the launch's dynamic LDS too)
+    if (batch == 1 && c6m <= 96) p.fprop_lds = lp_max(p.fprop_lds, c6m <= 64 ? (size_t)LP_S9CHOL4_BYTES : (size_t)LP_S9CHOL6_BYTES);
+    p.fprop_lds = lp_max(p.fprop_lds, (size_t)LP_PROP3_BYTES);
+    p.fuse_ok = batch == 1 && !sw.no_fused_propagate && p.fprop_lds + statics[LPK_FEAT_PROP] <= RVIO_LDS_LIMIT;
+    if (p.fuse_ok) p.attr[LPK_FEAT_PROP] = p.fprop_lds;
+    // the refill half of book-keeping walks the ChessGrid one wave per cell with a per-wave list of the cell's points (F float2 each): as many
+    // waves as one CU's LDS holds BESIDE THE KERNEL'S STATIC LDS for one stream (16 at F <= 1001: 20 cells -> two rounds instead of five), 4 for
+    // batch handles (occupancy).  The fused launch (RANSAC + both halves, ransac_book_kernel: ~15 KB static, >= 4 waves — RANSAC's inlier count
+    // needs 256 threads) where that fits; beyond it (F >= 2851) the pair ransac_book_a_kernel + bookkeep_b_kernel, whose refill half has
+    // next to no static LDS and runs with any number of waves.
+    {
+        const int top = batch == 1 ? 16 : 4;
+        for (int nwv = top; nwv >= 4 && !p.book_fused; nwv /= 2)
+            if (book_lds_bytes(F, nwv) + lp_max(statics[LPK_RANSAC_BOOK], statics[LPK_BOOKKEEP_B]) <= RVIO_LDS_LIMIT) { p.book_waves = nwv; p.book_fused = true; }
+        if (!p.book_fused) {
+            p.book_waves = 0;
+            for (int nwv = top; nwv >= 1 && !p.book_waves; nwv /= 2)
+                if (book_lds_bytes(F, nwv) + statics[LPK_BOOKKEEP_B] <= RVIO_LDS_LIMIT) p.book_waves = nwv;
+            if (!p.book_waves) { p.rc = 1; p.why = "Tracker.nFeatures too large for book-keeping's LDS lists (160 KiB per workgroup)"; return p; }
+        }
+        p.book_lds = book_lds_bytes(F, p.book_waves);
+        p.attr[LPK_BOOKKEEP_B] = p.book_lds;
+        if (p.book_fused) p.attr[LPK_RANSAC_BOOK] = p.book_lds;
+    }
+    {   // fully unrolled solve kernel: variants <column chunks, rows per wave> for c6 <= 126
+        int rpw = 0, nch = 0;
+        const int nw = 8;
+        if (c6m <= 60) { p.solve5_variant = 1; nch = 1; rpw = 8; }
+        else if (c6m <= 96) { p.solve5_variant = 2; nch = 2; rpw = 12; }
+        else if (c6m <= 126) { p.solve5_variant = 3; nch = 2; rpw = 16; }
+        p.solve7_variant = (c6m <= 64) ? 1 : (c6m <= 96) ? 2 : (c6m <= 128) ? 3 : (c6m <= 192) ? 4 : 0;
+        if (sw.solve6 && p.solve5_variant) p.solve7_variant = 0;   // A/B timing: the LDS-tableau kernel behind gemm_T_kernel
+        // one instance: the blocked SPD solve (solve9.hip).  Measured on full-load updates (tools/solve9_probe.py, profiles/r05_solve9_probe.txt), solve kernel alone:
+        // 6n = 84: 94.0 us against solve7's 102.6; 120: 173 against 212; 180: 511 against 797.  At 6n <= 96 the Cholesky of the clone block — the part that does
+        // not depend on the measurements — rides as one more workgroup in the per-feature launch (pipelined frame) or in propagate's launch (staged entry
+        // points), off the chain; the solve kernel then starts at Q = A L.  RVIO_SOLVE7=1 (instrumented build) keeps the register-tableau elimination: A/B timing.
+        if ((batch == 1 || (c6m <= 64 && sw.s9_batch)) && c6m <= 192 && !sw.solve7) {
+            p.solve9_nt = (c6m <= 64) ? 4 : (c6m <= 96) ? 6 : (c6m <= 128) ? 8 : 12;
+            if (p.solve9_nt == 4) p.attr[LPK_SOLVE9_SMALL] = LP_S9SMALL_BYTES;
+        }
+        // batch handles: throughput, not latency — solve6 keeps four instances resident per CU (33 KB of LDS against 112 KB) and the
+        // multi-workgroup gemm_T_kernel costs nothing there (measured at B = 2048: 2.67 ms per batched frame against 3.09)
+        // (round 3, measured and NOT adopted: solve7 with T through the L2 scratch instead of LDS — 11 KB of LDS, eight workgroups per CU, no gemm_T
+        // launch — as the batch form at 6n <= 64, RVIO_BATCH_SOLVE7: 2.62 ms per batched frame at B = 2048 against 2.29 with solve6 behind gemm_T)
+        if (batch > 1 && p.solve5_variant && !sw.solve7 && !(p.solve7_variant == 1 && sw.batch_solve7)) p.solve7_variant = 0;
+        if (batch > 1 && p.solve7_variant == 1) p.solve7_variant = 5;
+        // shipping library: the register-tableau solve survives for batch handles beyond solve6's windows only (6n > 126: solve7_kernel<3, 16, 12>)
+        if (!sw.dbg_build && (p.solve7_variant != 4 || p.solve9_nt)) p.solve7_variant = 0;
+        if (p.solve5_variant) {
+            p.solve5_lds = (size_t)(nw * rpw) * (64 * nch + 1) * sizeof(double);
+            p.attr[LPK_SOLVE6_1] = p.attr[LPK_SOLVE6_2] = p.attr[LPK_SOLVE6_3] = lp_max(p.solve5_lds, (size_t)1024);
+        }
+    }
+    const size_t c6t = (c6m + 15) / 16;
+    if (batch >= 128 && c6m <= 60 && !sw.no_joseph_fused) {   // the Joseph form of a batch handle in one kernel, one workgroup per instance
+        const size_t ls = c6m + 1, dmx = 24 + c6m;
+        p.jb_lds = (3 * dmx * ls + lp_max(c6m * ls, (size_t)LP_JB_TL_DOUBLES)) * sizeof(double);
+        if (p.jb_lds + statics[LPK_JOSEPH_BATCH] > RVIO_LDS_LIMIT) p.jb_lds = 0;
+        else p.attr[LPK_JOSEPH_BATCH] = p.jb_lds;
+    }
+    p.ug_lds = 2 * 16 * (c6t * 16 + 1) * sizeof(double);
+    p.attr[LPK_UG] = p.ug_lds;
+    p.attr[LPK_UG_LDS] = LP_UGL_BYTES;
+    p.attr[LPK_FINAL_LDS] = LP_FNL_BYTES;
+    p.attr[LPK_JOSEPH_LDS] = LP_JL_BYTES;
+    if (batch > 1 && !p.solve5_variant && !p.solve7_variant) { p.rc = 1; p.why = "batched filter: clone window too long for the unrolled solve kernel (6n <= 126)"; return p; }
+    // nothing above may ask for more than a CU has: a configuration that would is refused here, by name, not by a failed hipFuncSetAttribute / launch
+    for (int k = 0; k < LPK_COUNT; ++k)
+        if (p.attr[k] && p.attr[k] + statics[k] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
+    return p;
+}

@@ -35,23 +35,9 @@
 
 // (experiments only: rvio_hip_debug_literal_force — every update the literal sweep CAN take (<= LIT_FEATS features, > 2 accepted, tall) takes it)
 __device__ int g_lit_force = 0;
-#define LIT_FEATS 24      // an update handed more features than this never takes the literal path (M <= LIT_FEATS * rho_max rows)
+// (LIT_FEATS, LIT_RING and the footprints lit_tri / lit_aux_doubles / lit_state_doubles / lit_slab_doubles / lit_rows_doubles: launch_plan.h)
 #define LIT_SLACK 0       // "barely tall" (rows - 6n <= LIT_SLACK) as a second trigger: 0 = off — see the header
 #define LIT_SPARE 48      // the gap trigger applies to stacks with few rows to spare only: rows - 6n <= LIT_SPARE (see lit_decide)
-#define LIT_RING 32       // stack rows staged in LDS (two blocks of LIT_RING / 2)
-
-// state of the array: U (running rows), X[2] (rows in flight between cells, double-buffered), each `tri` doubles: cell n owns
-// columns n..Nc (Nc = the residual), offset n (Nc + 1) - n (n - 1) / 2
-__host__ __device__ inline size_t lit_tri(int c6) { return (size_t)c6 * (c6 + 1) / 2 + c6; }
-// LDS of lit_finish besides the state: ring of stack rows, (c, s) pairs of two steps, the level-to-level hand-over of two steps, row norms, the row map
-__host__ __device__ inline size_t lit_aux_doubles(int ldh, int rho_max) { return (size_t)LIT_RING * ldh + 4 * (size_t)ldh + 2 * 256 + ldh + (size_t)(LIT_FEATS * rho_max + 1) / 2 + 8; }
-__host__ __device__ inline size_t lit_state_doubles(int c6) { return 3 * lit_tri(c6); }
-// a feature's raw block in LDS for the nullspace sweep: 2 max_len rows of [Hx columns + residual | Hf (3)]
-__host__ __device__ inline size_t lit_slab_doubles(int ldh, int rho_max) { return (size_t)(rho_max + 2) * (ldh + 3); }
-// the export buffer: LIT_FEATS blocks of 2 max_len rows x ldh, then the Hf blocks (2 max_len x 3 each)
-// + the projected blocks the nullspace sweep leaves (rho_max rows x ldh each): the raw blocks stay as exported, a second run on the same export
-// (rvio_hip_debug_time_kernel) finds what the first one found
-__host__ __device__ inline size_t lit_rows_doubles(int ldh, int rho_max) { return (size_t)LIT_FEATS * (rho_max + 2) * (ldh + 3) + (size_t)LIT_FEATS * rho_max * ldh; }
 __host__ __device__ inline double* lit_proj_of(double* lit_rows, int ldh, int rho_max) { return lit_rows + (size_t)LIT_FEATS * (rho_max + 2) * (ldh + 3); }
 __host__ __device__ inline const double* lit_hf_of(const double* lit_rows, int ldh, int rho_max) { return lit_rows + (size_t)LIT_FEATS * (rho_max + 2) * ldh; }
 
@@ -358,7 +344,7 @@ __device__ __forceinline__ int lit_scan_gram(double* st_, double* nrm, double* A
         while (r < Nc && !(nrm[r] < 1e-4)) ++r;
         *s_rank = r;
     }
-    for (int i = tid; i < Nc; i += T) A[(size_t)ldh * ldh + i] = nrm[i];
+    for (int i = tid; i < Nc; i += T) A[lit_norm_off(ldh) + i] = nrm[i];
     __syncthreads();
     const int nRank = *s_rank;
     for (int e = tid; e < c6 * ldh; e += T) {
@@ -376,8 +362,13 @@ __device__ __forceinline__ int lit_scan_gram(double* st_, double* nrm, double* A
     return nRank;
 }
 
-// phase stamps (100 MHz wall clock) behind the diagnostic row norms in the unused second part of the block: tools/lit_probe.py
-#define LIT_STAMP(k) do { if (threadIdx.x == 0) A[(size_t)cfg.ldh * cfg.ldh + 200 + (k)] = (double)wall_clock64(); } while (0)
+// phase stamps (100 MHz wall clock) behind the diagnostic row norms in the unused second part of the block: tools/lit_probe.py.  Instrumented build
+// only, and only where the block (2 ldh^2 doubles) has room for them (launch_plan.h: lit_stamp_fits — not at max_track_len = 3)
+#ifdef RVIO_DBG_CLOCKS
+#define LIT_STAMP(k) do { if (threadIdx.x == 0 && lit_stamp_fits(cfg.ldh)) A[lit_stamp_off(cfg.ldh, (k))] = (double)wall_clock64(); } while (0)
+#else
+#define LIT_STAMP(k) do { } while (0)
+#endif
 // The two sweeps + scan + [A|b], by one workgroup of 256 threads.  A: the [A|b] block (c6 x ldh row-major inside ldh x ldh; the spare last
 // row = the meta row).  st: lit_state_doubles(c6) doubles (LDS or global — generic pointer), aux: lit_aux_doubles() doubles of LDS.
 // lds_cap: doubles of LDS behind aux that the nullspace sweep may use for its slabs (everything else of this function starts after it).

@@ -13,9 +13,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "launch_plan.h"   // RVIO_MAX_LEN, the LDS footprints and the launch geometry of a configuration (plain C++: also compiled on the host by the tests)
 
 #define RVIO_MAX_IMU 192     // IMU samples per call (= RVIO_HIP_MAX_IMU of the header): RANSAC forms one delta rotation per thread
-#define RVIO_MAX_LEN 32      // max Tracker.nMaxTrackingLength supported (cfg E: 31)
 
 struct DevCfg {
     double gravity, small_angle;

@@ -77,6 +77,7 @@ struct rvio_hip {
     int feat_threads = 64;
     size_t feat_lds = 0, fprop_lds = 0, ug_lds = 0, book_lds = 0, jb_lds = 0;
     int book_waves = 4;
+    bool book_fused = true;      // RANSAC + both halves of book-keeping fit one launch's LDS (launch_plan.h)
     int solve5_variant = 0;      // solve6_kernel (the LDS-tableau solve behind gemm_T_kernel: batch handles): 0 none, 1: <1,8,8>  2: <2,12,8>  3: <2,16,8>
     StageSync* stage_sync = nullptr;   // device-side completion counter of the filter chain (aug) and the value it reaches after the launches so far
     StageSync stage_tgt = {};
@@ -444,6 +445,56 @@ static hipError_t lds_attr(const void* fn, int bytes) {
     if (e == hipSuccess) cur = bytes;
     return e;
 }
+// launch_plan.h's kernels, in LpKernel order; its fixed sizes stand for these definitions
+static_assert(LP_S9CHOL4_BYTES == sizeof(S9CholLds<4, 4>), "launch_plan.h: solve9's LDS structs");
+static_assert(LP_S9CHOL6_BYTES == sizeof(S9CholLds<6, 4>), "launch_plan.h: solve9's LDS structs");
+static_assert(LP_S9SMALL_BYTES == sizeof(S9SmallLds), "launch_plan.h: solve9's LDS structs");
+static_assert(LP_PROP3_BYTES == sizeof(Prop3Lds<16>), "launch_plan.h: propagate's LDS struct");
+static_assert(LP_JB_TL_DOUBLES == JB_TL_DOUBLES && LP_UGL_BYTES == UGL_LDS_DOUBLES * sizeof(double) && LP_FNL_BYTES == FNL_LDS_DOUBLES * sizeof(double) &&
+              LP_JL_BYTES == JL_LDS_DOUBLES * sizeof(double), "launch_plan.h: the Joseph-form kernels' LDS");
+static const void* lp_kernel_fn(int k) {
+    switch (k) {
+        case LPK_FEAT_BUILD16: return (const void*)feat_build_kernel<16>;
+        case LPK_FEAT_BUILD4: return (const void*)feat_build_kernel<4>;
+        case LPK_GRAM_REDUCE: return (const void*)gram_reduce_kernel;
+        case LPK_BLOCK_SUM: return (const void*)block_sum_kernel;
+        case LPK_LIT_BATCH: return (const void*)lit_batch_kernel;
+        case LPK_GEMM_T_LDS: return (const void*)gemm_T_lds_kernel;
+        case LPK_GRAM_BATCH4: return (const void*)gram_reduce_batch_kernel<4>;
+        case LPK_GRAM_BATCH6: return (const void*)gram_reduce_batch_kernel<6>;
+        case LPK_FEAT_PROP: return (const void*)feat_prop_kernel;
+        case LPK_BOOKKEEP_B: return (const void*)bookkeep_b_kernel;
+        case LPK_RANSAC_BOOK: return (const void*)ransac_book_kernel;
+        case LPK_SOLVE9_SMALL: return (const void*)solve9_small_kernel;
+        case LPK_SOLVE6_1: return (const void*)solve6_kernel<1, 8, 8>;
+        case LPK_SOLVE6_2: return (const void*)solve6_kernel<2, 12, 8>;
+        case LPK_SOLVE6_3: return (const void*)solve6_kernel<2, 16, 8>;
+        case LPK_JOSEPH_BATCH: return (const void*)joseph_batch_kernel;
+        case LPK_UG: return (const void*)ug_kernel;
+        case LPK_UG_LDS: return (const void*)ug_lds_kernel;
+        case LPK_FINAL_LDS: return (const void*)final_lds_kernel;
+        case LPK_JOSEPH_LDS: return (const void*)joseph_lds_kernel;
+    }
+    return nullptr;
+}
+// static LDS of those kernels as the loaded code object has it (the compiler's decision: the plan budgets dynamic + static against a CU's 160 KiB)
+static hipError_t static_lds_table(const size_t** out) {
+    static std::mutex mu;
+    static bool have = false;
+    static size_t tab[LPK_COUNT];
+    std::lock_guard<std::mutex> lk(mu);
+    if (!have) {
+        for (int k = 0; k < LPK_COUNT; ++k) {
+            hipFuncAttributes a;
+            const hipError_t e = hipFuncGetAttributes(&a, lp_kernel_fn(k));
+            if (e != hipSuccess) return e;
+            tab[k] = a.sharedSizeBytes;
+        }
+        have = true;
+    }
+    *out = tab;
+    return hipSuccess;
+}
 static int create_impl(const rvio_config* cfg, int device, int batch, bool front_end, rvio_hip** out) {
     if (!cfg || !out) return RVIO_ERR_INVALID;
     *out = nullptr;
@@ -461,6 +512,19 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
     if (d.grid_cols * d.grid_rows < 1) { delete h; return RVIO_ERR_INVALID; }
     *out = h;   // returned even on allocation failure so last_error is readable
     HIPCHK(h, hipSetDevice(device));
+    // launch geometry (launch_plan.h: LDS sizes, kernel variants, what moves from LDS to global memory) — before anything is allocated: a configuration
+    // whose footprint does not fit a CU beside the kernels' static LDS is refused here, not by a failed launch
+    LaunchSwitches sw;
+    sw.solve6 = ab_env("RVIO_SOLVE6") != nullptr; sw.solve7 = ab_env("RVIO_SOLVE7") != nullptr; sw.s9_batch = S9_BATCH;
+    sw.batch_solve7 = ab_env("RVIO_BATCH_SOLVE7") != nullptr; sw.no_joseph_fused = ab_env("RVIO_NO_JOSEPH_FUSED") != nullptr;
+    sw.no_fused_propagate = ab_env("RVIO_NO_FUSED_PROPAGATE") != nullptr;
+#ifdef RVIO_DBG_CLOCKS
+    sw.dbg_build = true;
+#endif
+    const size_t* statics = nullptr;
+    HIPCHK(h, static_lds_table(&statics));
+    const LaunchPlan plan = launch_plan(cfg->max_track_len, cfg->n_features, batch, statics, sw);
+    if (plan.rc) { h->err = plan.why; return RVIO_ERR_UNSUPPORTED; }
     h->private_queues = g_private_queue_handles.fetch_add(1) == 0;
     if (!h->private_queues) g_private_queue_handles.fetch_sub(1);
     HIPCHK(h, make_stream(h, &h->stream));
@@ -470,17 +534,16 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
         HIPCHK(h, make_stream(h, &h->stream_t, true));
         HIPCHK(h, make_stream(h, &h->stream_d, true));
         HIPCHK(h, make_stream(h, &h->stream_c, true));
-        // Image chains in flight.  Two (default): with the filter, tracker and side streams that makes FOUR busy queues.  A third chain on a
+        // Image chains in flight (plan.n_ic).  Two (default): with the filter, tracker and side streams that makes FOUR busy queues.  A third chain on a
         // fifth queue was measured (RVIO_IC=3): the frame period goes from 131 to 180-250 us whatever CUs the front end is kept off — beyond
         // four busy queues the command processor time-slices them.
         // Long windows (96 < 6n <= 192: the solve in its split form, filter chain >= 250 us): ONE image chain in flight is enough (the chain is ~180 us),
         // and the queue that frees runs the Cholesky factor of the clone block beside the filter chain (augment_compose_dev).  A FIFTH queue for it was
         // measured: cfg C 3.2 k frames/s instead of 3.9 k — the command processor time-slices beyond four busy queues.
-        const int c6m_ = 6 * (h->cfg.max_track_len - 1);
-        if (batch == 1 && c6m_ > 96 && c6m_ <= 192) h->n_ic = 1;
+        h->n_ic = plan.n_ic;
         if (const char* e = ab_env("RVIO_IC")) h->n_ic = std::max(1, std::min((int)rvio_hip::kIC, atoi(e)));
         if (h->n_ic > 2) HIPCHK(h, make_stream(h, &h->stream_e, true));
-        if (batch == 1 && c6m_ > 96 && c6m_ <= 192 && h->n_ic == 1) {
+        if (plan.chol_queue && h->n_ic == 1) {
             h->stream_l = h->stream_c;
             HIPCHK(h, hipEventCreateWithFlags(&h->evA, kEvFlags));
             HIPCHK(h, hipEventCreateWithFlags(&h->evL, kEvFlags));
@@ -499,32 +562,11 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
         HIPCHK(h, hipEventCreateWithFlags(&h->evF[b + 2], kEvFlags));
         HIPCHK(h, hipEventCreateWithFlags(&h->evIn[b], kEvFlags));
     }
-    const size_t ldh = d.ldh;
-    // launch geometry (decides two optional slab members)
-    if (d.Fu > GRAM_MAX_FEATS) { h->err = "Tracker.nFeatures too large for the Gram stage (ceil(F/2) <= 2048)"; return RVIO_ERR_UNSUPPORTED; }
-#ifndef FEAT_T_SMALL
-#define FEAT_T_SMALL 128     // threads of a per-feature workgroup at 6n <= 127 (same-box A/B of 64 against 128 at B = 2048: profiles/r06_feat_threads_ab.txt)
-#endif
-    h->feat_threads = (d.ldh <= 128) ? FEAT_T_SMALL : 256;
+    h->feat_threads = plan.feat_threads;
     if (const char* ft = ab_env("RVIO_FEAT_THREADS")) h->feat_threads = atoi(ft);   // A/B timing only (64, 128 or 256)
-    h->trunc_lds = trunc_lds_doubles(d.max_len) * sizeof(double);
-    {   // the literal sweep runs in the workgroup that finishes the reduction (literal.h): its ring / rotation tables always in that launch's LDS, the
-        // array's state too when it fits (gram_reduce_kernel holds ~11 KB of static LDS) — else, and for batch handles (occupancy), in the slab
-        const size_t aux = lit_aux_doubles(d.ldh, d.rho_max) * sizeof(double), st = lit_state_doubles(d.ldh - 1) * sizeof(double);
-        const size_t slab = lit_slab_doubles(d.ldh, d.rho_max) * sizeof(double);   // (a feature's raw block for the nullspace sweep: at least one must fit)
-        h->lit_state_global = batch > 1 || aux + st > 144 * 1024;
-        h->lit_batch_lds = std::max(aux, slab);
-        h->trunc_lds = std::max(h->trunc_lds, std::max(h->lit_state_global ? aux : aux + st, std::min((size_t)4, (size_t)(144 * 1024) / slab) * slab));
-    }
-    h->feat_lds = feat_lds_doubles(d.max_len, d.ldh, true) * sizeof(double);
-    bool need_tm_global = false;
-    // (a batch handle keeps T in global memory as well: a third less LDS per feature workgroup = 8 instead of 5 resident per CU)
-    if (h->feat_lds > 150 * 1024 || batch > 1) {
-        h->feat_lds = feat_lds_doubles(d.max_len, d.ldh, false) * sizeof(double);
-        need_tm_global = true;
-    }
-    if (h->feat_lds > 160 * 1024) { h->err = "per-feature LDS footprint exceeds 160 KiB"; return RVIO_ERR_UNSUPPORTED; }
-    const size_t c6m = ldh - 1;
+    h->trunc_lds = plan.trunc_lds; h->lit_state_global = plan.lit_state_global; h->lit_batch_lds = plan.lit_batch_lds;
+    h->feat_lds = plan.feat_lds;
+    const bool need_tm_global = plan.tm_global;
     if (front_end && cfg->enable_equalizer) {   // CLAHE(3.0, 5x5), Tracker.cc:198-202
         h->cl_tx = 5; h->cl_ty = 5;
         int ew = d.W, eh = d.H;
@@ -567,89 +609,22 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
         HIPCHK(h, hipMemcpy2DAsync(t.first, h->slab_bytes, ones.data(), sizeof(int), sizeof(int), (size_t)batch, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    HIPCHK(h, lds_attr((const void*)feat_build_kernel<16>, (int)h->feat_lds));
-    HIPCHK(h, lds_attr((const void*)feat_build_kernel<4>, (int)h->feat_lds));
-    HIPCHK(h, lds_attr((const void*)gram_reduce_kernel, (int)h->trunc_lds));
-    HIPCHK(h, lds_attr((const void*)block_sum_kernel, (int)h->trunc_lds));
-    HIPCHK(h, lds_attr((const void*)lit_batch_kernel, (int)h->lit_batch_lds));
-    if (batch > 1 && gram_batch_lds_doubles(d.max_len, d.ldh) * sizeof(double) <= 64 * 1024) {
-        h->gram_batch_lds = gram_batch_lds_doubles(d.max_len, d.ldh) * sizeof(double);
-        HIPCHK(h, lds_attr((const void*)gemm_T_lds_kernel, 2 * 64 * 65 * (int)sizeof(double)));
-        HIPCHK(h, lds_attr((const void*)gram_reduce_batch_kernel<4>, (int)h->gram_batch_lds));
-        HIPCHK(h, lds_attr((const void*)gram_reduce_batch_kernel<6>, (int)h->gram_batch_lds));
-    }
-    // propagate rides in the per-feature launch: its workgroup builds no feature, so its buffers (Prop3Lds<16>, 86 KB) and the per-feature footprint
-    // share the launch's dynamic LDS — max of the two, which fits one CU for every window (rounds 2-4: static + dynamic, the SUM: long windows
-    // fell back to 8-sample chunks, cfg E to a propagate launch of its own on the chain)
-    h->fprop_lds = h->feat_lds;
-    // (round 5: + the Cholesky role of solve9 at 6n <= 96 — one more workgroup whose buffers live in the launch's dynamic LDS too)
-    if (batch == 1 && c6m <= 96) h->fprop_lds = std::max(h->fprop_lds, c6m <= 64 ? sizeof(S9CholLds<4, 4>) : sizeof(S9CholLds<6, 4>));
-    h->fprop_lds = std::max(h->fprop_lds, sizeof(Prop3Lds<16>));
-    h->fuse_ok = batch == 1 && !ab_env("RVIO_NO_FUSED_PROPAGATE") && h->fprop_lds <= 160 * 1024;
-    if (h->fuse_ok) HIPCHK(h, lds_attr((const void*)feat_prop_kernel, (int)h->fprop_lds));
-    // the refill half of book-keeping walks the ChessGrid one wave per cell with a per-wave list of the cell's points (F float2 each): as many
-    // waves as the 160 KB of LDS hold for one stream (16 at F <= 800: 20 cells -> two rounds instead of five), 4 for batch handles (occupancy)
-    h->book_waves = 4;
-    if (h->batch == 1) for (int nwv = 16; nwv > 4; nwv /= 2) if ((((size_t)20 * d.F + 7) & ~(size_t)7) + (size_t)nwv * d.F * 8 + 16 <= (size_t)150 * 1024) { h->book_waves = nwv; break; }
-    h->book_lds = (((size_t)20 * d.F + 7) & ~(size_t)7) + (size_t)h->book_waves * d.F * 8 + 16;
-    HIPCHK(h, lds_attr((const void*)bookkeep_b_kernel, (int)h->book_lds));
-    HIPCHK(h, lds_attr((const void*)ransac_book_kernel, (int)h->book_lds));
-    {
-        {   // fully unrolled solve kernel: variants <column chunks, rows per wave> for c6 <= 126
-            int rpw = 0, nch = 0, nw = 8;
-            if (c6m <= 60) { h->solve5_variant = 1; nch = 1; rpw = 8; }
-            else if (c6m <= 96) { h->solve5_variant = 2; nch = 2; rpw = 12; }
-            else if (c6m <= 126) { h->solve5_variant = 3; nch = 2; rpw = 16; }
-            h->solve7_variant = (c6m <= 64) ? 1 : (c6m <= 96) ? 2 : (c6m <= 128) ? 3 : (c6m <= 192) ? 4 : 0;
-            if (ab_env("RVIO_SOLVE6") && h->solve5_variant) h->solve7_variant = 0;   // A/B timing: the LDS-tableau kernel behind gemm_T_kernel
-            // one instance: the blocked SPD solve (solve9.hip).  Measured on full-load updates (tools/solve9_probe.py, profiles/r05_solve9_probe.txt), solve kernel alone:
-            // 6n = 84: 94.0 us against solve7's 102.6; 120: 173 against 212; 180: 511 against 797.  At 6n <= 96 the Cholesky of the clone block — the part that does
-            // not depend on the measurements — rides as one more workgroup in the per-feature launch (pipelined frame) or in propagate's launch (staged entry
-            // points), off the chain; the solve kernel then starts at Q = A L.  RVIO_SOLVE7=1 (instrumented build) keeps the register-tableau elimination: A/B timing.
-            if ((batch == 1 || (c6m <= 64 && S9_BATCH)) && c6m <= 192 && !ab_env("RVIO_SOLVE7")) {
-                h->solve9_nt = (c6m <= 64) ? 4 : (c6m <= 96) ? 6 : (c6m <= 128) ? 8 : 12;
-                DALLOC(h, h->S9scr, S9_SLAB_DOUBLES(h->solve9_nt) * (size_t)batch);
-                if (h->solve9_nt == 4) HIPCHK(h, lds_attr((const void*)solve9_small_kernel, (int)sizeof(S9SmallLds)));
-            }
-            // batch handles: throughput, not latency — solve6 keeps four instances resident per CU (33 KB of LDS against 112 KB) and the
-            // multi-workgroup gemm_T_kernel costs nothing there (measured at B = 2048: 2.67 ms per batched frame against 3.09)
-            // (round 3, measured and NOT adopted: solve7 with T through the L2 scratch instead of LDS — 11 KB of LDS, eight workgroups per CU, no gemm_T
-            // launch — as the batch form at 6n <= 64, RVIO_BATCH_SOLVE7: 2.62 ms per batched frame at B = 2048 against 2.29 with solve6 behind gemm_T)
-            if (batch > 1 && h->solve5_variant && !ab_env("RVIO_SOLVE7") && !(h->solve7_variant == 1 && ab_env("RVIO_BATCH_SOLVE7"))) h->solve7_variant = 0;
-            if (batch > 1 && h->solve7_variant == 1) h->solve7_variant = 5;
+    h->gram_batch_lds = plan.gram_batch_lds;
+    h->fprop_lds = plan.fprop_lds; h->fuse_ok = plan.fuse_ok;
+    h->book_waves = plan.book_waves; h->book_lds = plan.book_lds; h->book_fused = plan.book_fused;
+    h->solve5_variant = plan.solve5_variant; h->solve7_variant = plan.solve7_variant; h->solve9_nt = plan.solve9_nt;
+    h->solve5_lds = plan.solve5_lds; h->jb_lds = plan.jb_lds; h->ug_lds = plan.ug_lds;
+    if (h->solve9_nt) DALLOC(h, h->S9scr, S9_SLAB_DOUBLES(h->solve9_nt) * (size_t)batch);
+    for (int k = 0; k < LPK_COUNT; ++k)
+        if (plan.attr[k]) HIPCHK(h, lds_attr(lp_kernel_fn(k), (int)plan.attr[k]));
 #ifdef RVIO_DBG_CLOCKS
-            if (h->solve7_variant == 1)
-            {
-                HIPCHK(h, lds_attr((const void*)solve7_kernel<1, 16, 4>, (3 * 64 * 65 + 24 * 64) * (int)sizeof(double)));
-                HIPCHK(h, lds_attr((const void*)solve7_kernel<1, 8, 8>, (3 * 64 * 65 + 24 * 64) * (int)sizeof(double)));
-                HIPCHK(h, lds_attr((const void*)solve7_kernel<1, 4, 16>, (3 * 64 * 65 + 24 * 64) * (int)sizeof(double)));
-            }
-#else
-            // shipping library: the register-tableau solve survives for batch handles beyond solve6's windows only (6n > 126: solve7_kernel<3, 16, 12>)
-            if (h->solve7_variant != 4 || h->solve9_nt) h->solve7_variant = 0;
-#endif
-            if (h->solve5_variant) {
-                h->solve5_lds = (size_t)(nw * rpw) * (64 * nch + 1) * sizeof(double);
-                const int lds = (int)std::max(h->solve5_lds, (size_t)1024);
-                HIPCHK(h, lds_attr((const void*)solve6_kernel<1, 8, 8>, lds));
-                HIPCHK(h, lds_attr((const void*)solve6_kernel<2, 12, 8>, lds));
-                HIPCHK(h, lds_attr((const void*)solve6_kernel<2, 16, 8>, lds));
-            }
-        }
-        const size_t c6t = (c6m + 15) / 16;
-        if (batch >= 128 && c6m <= 60 && !ab_env("RVIO_NO_JOSEPH_FUSED")) {   // the Joseph form of a batch handle in one kernel, one workgroup per instance
-            const size_t ls = c6m + 1, dmx = 24 + c6m;
-            h->jb_lds = (3 * dmx * ls + std::max((size_t)c6m * ls, (size_t)JB_TL_DOUBLES)) * sizeof(double);
-            if (h->jb_lds > 160 * 1024) h->jb_lds = 0;
-            else HIPCHK(h, lds_attr((const void*)joseph_batch_kernel, (int)h->jb_lds));
-        }
-        h->ug_lds = 2 * 16 * (c6t * 16 + 1) * sizeof(double);
-        HIPCHK(h, lds_attr((const void*)ug_kernel, (int)h->ug_lds));
-        HIPCHK(h, lds_attr((const void*)ug_lds_kernel, (int)(UGL_LDS_DOUBLES * sizeof(double))));
-        HIPCHK(h, lds_attr((const void*)final_lds_kernel, (int)(FNL_LDS_DOUBLES * sizeof(double))));
-        HIPCHK(h, lds_attr((const void*)joseph_lds_kernel, (int)(JL_LDS_DOUBLES * sizeof(double))));
+    if (h->solve7_variant == 1)
+    {
+        HIPCHK(h, lds_attr((const void*)solve7_kernel<1, 16, 4>, (3 * 64 * 65 + 24 * 64) * (int)sizeof(double)));
+        HIPCHK(h, lds_attr((const void*)solve7_kernel<1, 8, 8>, (3 * 64 * 65 + 24 * 64) * (int)sizeof(double)));
+        HIPCHK(h, lds_attr((const void*)solve7_kernel<1, 4, 16>, (3 * 64 * 65 + 24 * 64) * (int)sizeof(double)));
     }
-    if (batch > 1 && !h->solve5_variant && !h->solve7_variant) { h->err = "batched filter: clone window too long for the unrolled solve kernel (6n <= 126)"; return RVIO_ERR_UNSUPPORTED; }
+#endif
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RVIO_OK;
 }
@@ -1544,7 +1519,7 @@ static int post_klt_dev(rvio_hip* h, const rvio_imu* d_imu, int m, const float* 
             if (h->dev_sync) { hand = &h->stage_sync->handover; h->stage_tgt.handover++; }
             // one stream, device-side counters: RANSAC and both halves of book-keeping are ONE launch (the refill half polls the detector's counter inside it)
             static const bool no_book_fuse = ab_env("RVIO_NO_FUSED_BOOK") != nullptr;   // A/B timing
-            if (fused && h->dev_sync && !no_book_fuse) {
+            if (fused && h->dev_sync && !no_book_fuse && h->book_fused) {
                 const int cix = ab_env("RVIO_DBG_ONE_CORNERS") ? 0 : h->ic;
                 h->gate_pending = true; h->gate_target = h->stage_tgt.handover;
                 hipLaunchKernelGGL(ransac_book_kernel, dim3(1, 1, B), dim3(64 * h->book_waves), h->book_lds, h->tail, h->dc, h->t, d_imu, m, h->rng, bs, h->imu_bs,

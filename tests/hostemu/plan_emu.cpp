@@ -1,0 +1,51 @@
+// plan_emu.cpp — r-vio_amd/csrc/launch_plan.h compiled with g++: the launch geometry create_impl derives from a configuration, evaluated on the
+// CPU for every accepted (max_track_len, n_features, batch).  tests/test_launch_plan.py feeds it the static LDS of each kernel as the built
+// library's code object has it and checks static + dynamic against a CU's LDS.
+#include "../../r-vio_amd/csrc/launch_plan.h"
+#include <string.h>
+
+extern "C" {
+int lp_num_kernels() { return LPK_COUNT; }
+const char* lp_kernel_name(int k) { return (k >= 0 && k < LPK_COUNT) ? kLpKernelName[k] : ""; }
+long lp_lds_limit() { return RVIO_LDS_LIMIT; }
+int lp_max_features() { return RVIO_MAX_FEATURES; }
+int lp_max_len() { return RVIO_MAX_LEN; }
+
+// one configuration.  attr[LPK_COUNT]: dynamic LDS per kernel; info[16]: see below; why: the refusal's text (<= 255 chars).  Returns plan.rc
+int lp_eval(int max_len, int n_features, int batch, const size_t* statics, size_t* attr, long* info, char* why) {
+    const LaunchPlan p = launch_plan(max_len, n_features, batch, statics);
+    for (int k = 0; k < LPK_COUNT; ++k) attr[k] = p.attr[k];
+    info[0] = p.book_waves; info[1] = (long)p.book_lds; info[2] = p.book_fused; info[3] = p.tm_global; info[4] = p.lit_state_global;
+    info[5] = p.solve5_variant; info[6] = p.solve7_variant; info[7] = p.solve9_nt; info[8] = p.n_ic; info[9] = p.feat_threads;
+    info[10] = (long)p.feat_lds; info[11] = (long)p.fprop_lds; info[12] = (long)p.trunc_lds; info[13] = p.fuse_ok; info[14] = (long)p.jb_lds; info[15] = (long)p.gram_batch_lds;
+    why[0] = 0;
+    if (p.why) { strncpy(why, p.why, 255); why[255] = 0; }
+    return p.rc;
+}
+
+// every max_track_len in [ml0, ml1] x every n_features in [f0, f1] at one batch size.  worst[k]: the largest static + dynamic of kernel k over the
+// supported configurations, at worst_cfg[2k] = max_len, worst_cfg[2k + 1] = n_features.  first_bad[3]: {kernel, max_len, n_features} of the first
+// supported configuration with a kernel over the limit.  Returns the number of such (configuration, kernel) pairs; *n_unsupported: refused configurations.
+long lp_sweep(int ml0, int ml1, int f0, int f1, int batch, const size_t* statics, size_t* worst, int* worst_cfg, int* first_bad, long* n_unsupported) {
+    long bad = 0, uns = 0;
+    for (int k = 0; k < LPK_COUNT; ++k) { worst[k] = 0; worst_cfg[2 * k] = worst_cfg[2 * k + 1] = 0; }
+    for (int ml = ml0; ml <= ml1; ++ml)
+        for (int F = f0; F <= f1; ++F) {
+            const LaunchPlan p = launch_plan(ml, F, batch, statics);
+            if (p.rc) { ++uns; continue; }
+            for (int k = 0; k < LPK_COUNT; ++k) {
+                if (!p.attr[k]) continue;
+                const size_t tot = p.attr[k] + statics[k];
+                if (tot > worst[k]) { worst[k] = tot; worst_cfg[2 * k] = ml; worst_cfg[2 * k + 1] = F; }
+                if (tot > RVIO_LDS_LIMIT) { if (!bad) { first_bad[0] = k; first_bad[1] = ml; first_bad[2] = F; } ++bad; }
+            }
+        }
+    *n_unsupported = uns;
+    return bad;
+}
+
+// diagnostics in the [A|b] block: one past the last double written (stamps: the instrumented build), and the block's size
+long lp_diag_end(int max_len, int stamps) { return (long)lit_diag_end(6 * (max_len - 1) + 1, stamps != 0); }
+long lp_block_doubles(int max_len) { const long ldh = 6 * (max_len - 1) + 1; return 2 * ldh * ldh; }
+long lp_book_lds_bytes(int F, int waves) { return (long)book_lds_bytes(F, waves); }
+}

@@ -342,11 +342,14 @@ def sweep_wider(trials=1500):
         yield trial, mode, cfg, n, x, P, ty, ln, me
 
 
-def sweep_few(trials=1500):
+def sweep_few(trials=1500, cfg=None, short_only=False):
     """the stock motion at the 14-clone window (cfg A), 3..15 features per update with random type-'1' lengths — a scene with little texture.
+    cfg: the same recipe at another configuration (any window: tests/test_gpu_windows.py); short_only: stacks made of type-'1' tracks of two
+    and three observations only (the only tracks a window of 2..4 clones can hold besides the full ones).
     Yields (trial, 0, cfg, n, x, P, types, lens, meas)."""
     synth = O.rv.synth
-    cfg = abi.config_named("A", enable_equalizer=0)
+    if cfg is None:
+        cfg = abi.config_named("A", enable_equalizer=0)
     n = cfg.max_track_len - 1
     recs = [r for r in _run(cfg, 4 * n + 30, image=False, seed=3) if (len(r["x1"]) - 26) // 7 == n]
     rng = np.random.default_rng(103)
@@ -355,10 +358,12 @@ def sweep_few(trials=1500):
         x, P = base["x1"].copy(), base["P1"]
         nf = int(rng.integers(3, 16))
         mix = ("half", "all2", "all1")[int(rng.integers(0, 3))]
+        if short_only:
+            mix = "all1"
         ty, ln, me = synth.worst_case_tracks(cfg, x, n_feat=nf, seed=int(rng.integers(1 << 30)), mix=mix)
         for f in range(nf):
-            if ty[f] == ord("1") and rng.uniform() < 0.5:
-                L = int(rng.integers(2, ln[f] + 1))
+            if ty[f] == ord("1") and (short_only or rng.uniform() < 0.5):
+                L = int(rng.integers(2, min(3, ln[f]) + 1)) if short_only else int(rng.integers(2, ln[f] + 1))
                 me[f, :L] = me[f, ln[f] - L: ln[f]].copy()
                 ln[f] = L
         yield trial, 0, cfg, n, x, P, ty, ln, me

@@ -35,7 +35,7 @@ def main():
                      sum(1 for i in ins if i.startswith("v_mfma_f64")), min(8, 512 // max(vg, 1)), int(acc.group(1)) if acc else 0))
     names = demangle([r[0] for r in rows])
     rows = sorted(zip(names, rows), key=lambda x: x[0])
-    lines = ["# r05 — per-kernel resources of the shipping build (device assembly of `hipcc --offload-arch=gfx950 -O3`, `tools/kernel_resources.py`)", "",
+    lines = ["# Per-kernel resources of the shipping build (device assembly of `hipcc --offload-arch=gfx950 -O3`, `tools/kernel_resources.py`)", "",
              "VGPRs = `next_free_vgpr` (arch + accumulation registers of the unified file); waves / SIMD = min(8, 512 / VGPRs); LDS = the static part "
              "(kernels with dynamic LDS get the rest at launch); scratch = bytes per lane.", "",
              "| kernel | VGPRs | SGPRs | static LDS (B) | scratch (B) | instructions | `v_mfma_f64` | waves / SIMD by registers |", "|---|---|---|---|---|---|---|---|"]

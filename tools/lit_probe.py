@@ -1,4 +1,5 @@
-"""Time of the literal path (csrc/literal.h) per update: stacks of the random sweeps that take it, by rows; HIP events around rvio_hip_update_tracked."""
+"""Time of the literal path (csrc/literal.h) per update: stacks of the random sweeps that take it, by rows; HIP events around rvio_hip_update_tracked.
+The phase split needs the instrumented build (-DRVIO_DBG_CLOCKS, loaded through RVIO_HIP_LIB): the shipping library writes no phase stamps."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
