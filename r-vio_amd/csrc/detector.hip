@@ -4,7 +4,8 @@
 // file is included inside the fp-contract(off) region).  s = 1 on the first image, 2 on refills (Tracker.cc:207,350): the
 // first-image flag lives on the device, so the kernels pick s themselves.
 //   mineig_kernel     Sobel 3x3 (scaled) -> products -> 3x3 box (double) -> lambda_min, + image maximum (atomic on an ordered key)
-//   nms_kernel        threshold at max*quality, strict 3x3 local maxima away from the border -> candidate list + per-cell buckets
+//   mineig_nms_kernel the map and its strict 3x3 local maxima away from the border in one pass (the map stays in LDS) -> provisional list;
+//   nms_threshold_kernel: threshold at max*quality -> candidate list + per-cell buckets
 //   greedy_kernel     OpenCV's sequential min-distance selection in descending-strength order, computed as the
 //                     lexicographically-first maximal independent set by priority rounds: a candidate is dropped once a
 //                     STRONGER candidate within the distance is taken, and taken once all of those are dropped; the
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(DET_T) void mineig_kernel(const uint8_t* __restrict
 // threshold does.  So: one workgroup computes the map on its 64 x 16 tile PLUS a one-pixel ring (the neighbours' values, recomputed —
 // the same arithmetic, hence the same bits), keeps it in LDS, appends every local maximum (value != 0) to a provisional list and folds the
 // tile's maximum into the image maximum; nms_threshold_kernel then applies  value > quality x maximum  to that list (a few thousand
-// entries instead of the 361 k-pixel map) and fills the candidate list and the cell buckets exactly as nms_kernel did.  The map itself
+// entries instead of the 361 k-pixel map) and fills the candidate list and the cell buckets exactly as nms_kernel, the second pass of rounds 1-3, did.  The map itself
 // is no longer stored (batch handles of >= 8 instances run the same pass in its strip form, mineig_nms_strip_kernel);
 // rvio_hip_get_corners(eig) recomputes it on demand with mineig_kernel.
 // Arithmetic = mineig_kernel's, in the separable form of round 2's throughput kernel: raw pixels staged once (one byte load per pixel),
@@ -447,7 +448,7 @@ __device__ __forceinline__ void det_geometry(const DetDev& d, float* md, int* ce
 }
 
 // The image-wide threshold on the provisional list (value > quality x maximum: goodFeaturesToTrack's cv::threshold THRESH_TOZERO):
-// the survivors are the candidates; list and cell buckets as nms_kernel filled them (the order inside `cand` is an atomic append, as it was).
+// the survivors are the candidates; list and cell buckets as the second pass of rounds 1-3 filled them (the order inside `cand` is an atomic append, as it was).
 #define NMS_T 256
 __global__ __launch_bounds__(NMS_T) void nms_threshold_kernel(DetDev d, size_t bs) {
     det_shift(d, (size_t)blockIdx.z * bs);
@@ -471,36 +472,6 @@ __global__ __launch_bounds__(NMS_T) void nms_threshold_kernel(DetDev d, size_t b
     }
 }
 
-// The two-pass form of rounds 1-3 (the map through HBM), kept for A/B timing in the instrumented build and for rvio_hip_get_corners(eig)
-#ifdef RVIO_DBG_CLOCKS   // (the two-pass form of rounds 1-3, RVIO_DET_TWO_PASS: instrumented build only)
-__global__ __launch_bounds__(DET_T) void nms_kernel(DetDev d, size_t bs) {
-    det_shift(d, (size_t)blockIdx.z * bs);
-    const int W = d.W, H = d.H;
-    const int x = blockIdx.x * DET_TW + (threadIdx.x & 63), y = blockIdx.y * DET_TH + (threadIdx.x >> 6);
-    if (x < 1 || y < 1 || x >= W - 1 || y >= H - 1) return;
-    const float mx = ord2f(*d.maxkey);
-    const float thr = (float)((double)mx * d.quality);
-    const float* e = d.eig + (size_t)y * W + x;
-    const float v = e[0];
-    if (!(v > thr) || v == 0.f) return;
-    float m = v;
-    m = fmaxf(m, e[-W - 1]); m = fmaxf(m, e[-W]); m = fmaxf(m, e[-W + 1]);
-    m = fmaxf(m, e[-1]);     m = fmaxf(m, e[1]);
-    m = fmaxf(m, e[W - 1]);  m = fmaxf(m, e[W]);  m = fmaxf(m, e[W + 1]);
-    if (v != m) return;
-    float md; int cell, gw, gh;
-    det_geometry(d, &md, &cell, &gw, &gh);
-    const int idx = y * W + x;
-    const unsigned long long key = ((unsigned long long)(unsigned)__float_as_int(v) << 32) | (unsigned)idx;   // v > 0: bits are ordered
-    const int ci = atomicAdd(&d.counters[0], 1);
-    d.cand[ci] = key;
-    const int c = (y / cell) * gw + (x / cell);
-    const size_t slot = (size_t)c * cell * cell + atomicAdd(&d.cell_cnt[c], 1);
-    d.cell_ent[slot] = key;
-    d.cell_ci[slot] = ci;
-}
-#endif
-
 #define NEIGH_T 1024
 #define NEIGH_BLOCKS 8
 #define NEIGH_BLOCKS_WIDE 2     // batch handles (measured at 128 streams: 8 -> 134.5 k frames/s, 4 -> 135.3, 2 -> 136.0, 1 -> 135.9)
@@ -510,7 +481,7 @@ __global__ __launch_bounds__(DET_T) void nms_kernel(DetDev d, size_t bs) {
 // Every candidate collects its STRONGER neighbours within the distance — only those decide its fate: it is dropped when
 // one of them is taken, taken when all of them are dropped.  OpenCV searches the 3x3 grid cells around the candidate.
 // Up to DET_FAST_N candidates every workgroup rebuilds compact cell buckets in its LDS (a few microseconds) and walks
-// them; denser candidate sets walk the global buckets nms_kernel filled.  Lists go to d.nb (global, L2 resident).
+// them; denser candidate sets walk the global buckets nms_threshold_kernel filled.  Lists go to d.nb (global, L2 resident).
 __global__ __launch_bounds__(NEIGH_T) void neigh_kernel(DetDev d, size_t bs) {
     det_shift(d, (size_t)blockIdx.z * bs);
     extern __shared__ __align__(16) unsigned char ndyn[];

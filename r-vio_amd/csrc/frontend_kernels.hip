@@ -55,78 +55,6 @@ __global__ __launch_bounds__(PYR_T) void pyramid_kernel(const uint8_t* __restric
     pyr_phase5(g, tid, s, o);
 }
 
-// The round-1..4 form (a 25-tap gather per output, reflect-101 per tap), kept for A/B timing in the instrumented build only (RVIO_PYR_V1=1)
-#ifdef RVIO_DBG_CLOCKS
-__device__ __forceinline__ int pyr_down_at(const uint8_t* __restrict__ src, int sw, int sx0, int sy0, int w, int h, int x, int y) {
-    // pyrDown pixel (x, y) of the next level from the LDS patch `src` (row stride sw) that holds level pixels [sx0.., sy0..]
-    int xs[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) xs[k] = reflect101(2 * x - 2 + k, w) - sx0;
-    int rows[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const uint8_t* s = src + (reflect101(2 * y - 2 + k, h) - sy0) * sw;
-        rows[k] = s[xs[2]] * 6 + (s[xs[1]] + s[xs[3]]) * 4 + s[xs[0]] + s[xs[4]];
-    }
-    return (rows[0] + rows[4] + (rows[1] + rows[3]) * 4 + rows[2] * 6 + 128) >> 8;
-}
-__global__ __launch_bounds__(PYR_T) void pyramid_kernel_v1(const uint8_t* __restrict__ src, int stride, PyrDev p, int levels, int copy0, size_t src_bs, size_t bs) {
-    src = zoff(src, src_bs); pyr_shift(p, (size_t)blockIdx.z * bs);
-    __shared__ uint8_t L0[85 * 88], L1[41 * 44], L2[19 * 20];
-    const int tid = threadIdx.x;
-    const int X3 = blockIdx.x * 8, Y3 = blockIdx.y * 8;
-    const int w0 = p.w[0], h0 = p.h[0];
-    // level-0 patch [8 X3 - 14, 8 X3 + 70] clipped to the image
-    const int ax = max(8 * X3 - 14, 0), ay = max(8 * Y3 - 14, 0), bx = min(8 * X3 + 70, w0 - 1), by = min(8 * Y3 + 70, h0 - 1);
-    const int pw = bx - ax + 1, ph = by - ay + 1;
-    if (pw <= 0 || ph <= 0) return;
-    for (int e = tid; e < pw * ph; e += PYR_T) { const int yy = e / pw, xx = e - yy * pw; L0[yy * 88 + xx] = src[(size_t)(ay + yy) * stride + ax + xx]; }
-    __syncthreads();
-    if (copy0) {   // this workgroup's 64x64 tile of level 0
-        uint8_t* d0 = (uint8_t*)p.img[0];
-        for (int e = tid; e < 64 * 64; e += PYR_T) {
-            const int x = 8 * X3 + (e & 63), y = 8 * Y3 + (e >> 6);
-            if (x < w0 && y < h0) d0[(size_t)y * w0 + x] = L0[(y - ay) * 88 + (x - ax)];
-        }
-    }
-    if (levels < 2) return;
-    const int w1 = p.w[1], h1 = p.h[1];
-    const int cx = max(4 * X3 - 6, 0), cy = max(4 * Y3 - 6, 0), dx = min(4 * X3 + 34, w1 - 1), dy = min(4 * Y3 + 34, h1 - 1);
-    const int qw = dx - cx + 1, qh = dy - cy + 1;
-    if (qw <= 0 || qh <= 0) return;
-    {
-        uint8_t* d1 = (uint8_t*)p.img[1];
-        for (int e = tid; e < qw * qh; e += PYR_T) {
-            const int yy = e / qw, xx = e - yy * qw, x = cx + xx, y = cy + yy;
-            const int v = pyr_down_at(L0, 88, ax, ay, w0, h0, x, y);
-            L1[yy * 44 + xx] = (uint8_t)v;
-            if (x >= 4 * X3 && x < 4 * X3 + 32 && y >= 4 * Y3 && y < 4 * Y3 + 32) d1[(size_t)y * w1 + x] = (uint8_t)v;
-        }
-    }
-    if (levels < 3) return;
-    __syncthreads();
-    const int w2 = p.w[2], h2 = p.h[2];
-    const int ex = max(2 * X3 - 2, 0), ey = max(2 * Y3 - 2, 0), fx = min(2 * X3 + 16, w2 - 1), fy = min(2 * Y3 + 16, h2 - 1);
-    const int rw = fx - ex + 1, rh = fy - ey + 1;
-    if (rw <= 0 || rh <= 0) return;
-    {
-        uint8_t* d2 = (uint8_t*)p.img[2];
-        for (int e = tid; e < rw * rh; e += PYR_T) {
-            const int yy = e / rw, xx = e - yy * rw, x = ex + xx, y = ey + yy;
-            const int v = pyr_down_at(L1, 44, cx, cy, w1, h1, x, y);
-            L2[yy * 20 + xx] = (uint8_t)v;
-            if (x >= 2 * X3 && x < 2 * X3 + 16 && y >= 2 * Y3 && y < 2 * Y3 + 16) d2[(size_t)y * w2 + x] = (uint8_t)v;
-        }
-    }
-    if (levels < 4) return;
-    __syncthreads();
-    const int w3 = p.w[3], h3 = p.h[3];
-    if (tid < 64) {
-        const int x = X3 + (tid & 7), y = Y3 + (tid >> 3);
-        if (x < w3 && y < h3) ((uint8_t*)p.img[3])[(size_t)y * w3 + x] = (uint8_t)pyr_down_at(L2, 20, ex, ey, w2, h2, x, y);
-    }
-}
-#endif
 
 // calcSharrDeriv of one pyramid level, on demand (rvio_hip_debug_pyramid): un-normalised 3x3 Scharr with reflect-101 neighbours,
 // int16 (dx,dy) packed — the same arithmetic the KLT kernel applies to its staged template patch

@@ -97,12 +97,6 @@ static const char* const kLpKernelName[LPK_COUNT] = {
     "joseph_lds_kernel"
 };
 
-// A/B switches of the instrumented build (all off in the shipping library)
-struct LaunchSwitches {
-    bool solve6 = false, solve7 = false, s9_batch = false, batch_solve7 = false, no_joseph_fused = false, no_fused_propagate = false;
-    bool dbg_build = false;      // -DRVIO_DBG_CLOCKS: the register-tableau solve's variants stay selectable
-};
-
 struct LaunchPlan {
     int rc = 0;                  // 0, or 1: the configuration is not supported (why says which limit)
     const char* why = nullptr;
@@ -122,7 +116,7 @@ LP_HD inline size_t lp_max(size_t a, size_t b) { return a > b ? a : b; }
 LP_HD inline size_t lp_min(size_t a, size_t b) { return a < b ? a : b; }
 
 // statics[k]: static LDS (bytes) of kernel k of THIS build
-inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size_t* statics, const LaunchSwitches& sw = LaunchSwitches()) {
+inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size_t* statics) {
     LaunchPlan p;
     const int nmax = max_len - 1;
     p.Fu = (n_features + 1) / 2; p.ldh = 6 * nmax + 1; p.rho_max = 2 * max_len - 2;
@@ -166,7 +160,7 @@ inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size
     // (round 5: + the Cholesky role of solve9 at 6n <= 96 — one more workgroup whose buffers live in the launch's dynamic LDS too)
     if (batch == 1 && c6m <= 96) p.fprop_lds = lp_max(p.fprop_lds, c6m <= 64 ? (size_t)LP_S9CHOL4_BYTES : (size_t)LP_S9CHOL6_BYTES);
     p.fprop_lds = lp_max(p.fprop_lds, (size_t)LP_PROP3_BYTES);
-    p.fuse_ok = batch == 1 && !sw.no_fused_propagate && p.fprop_lds + statics[LPK_FEAT_PROP] <= RVIO_LDS_LIMIT;
+    p.fuse_ok = batch == 1 && p.fprop_lds + statics[LPK_FEAT_PROP] <= RVIO_LDS_LIMIT;
     if (p.fuse_ok) p.attr[LPK_FEAT_PROP] = p.fprop_lds;
     // the refill half of book-keeping walks the ChessGrid one wave per cell with a per-wave list of the cell's points (F float2 each): as many
     // waves as one CU's LDS holds BESIDE THE KERNEL'S STATIC LDS for one stream (16 at F <= 1001: 20 cells -> two rounds instead of five), 4 for
@@ -187,37 +181,33 @@ inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size
         p.attr[LPK_BOOKKEEP_B] = p.book_lds;
         if (p.book_fused) p.attr[LPK_RANSAC_BOOK] = p.book_lds;
     }
-    {   // fully unrolled solve kernel: variants <column chunks, rows per wave> for c6 <= 126
+    {   // solve6_kernel (the LDS-tableau solve behind gemm_T_kernel): variants <column chunks, rows per wave> for c6 <= 126
         int rpw = 0, nch = 0;
         const int nw = 8;
         if (c6m <= 60) { p.solve5_variant = 1; nch = 1; rpw = 8; }
         else if (c6m <= 96) { p.solve5_variant = 2; nch = 2; rpw = 12; }
         else if (c6m <= 126) { p.solve5_variant = 3; nch = 2; rpw = 16; }
-        p.solve7_variant = (c6m <= 64) ? 1 : (c6m <= 96) ? 2 : (c6m <= 128) ? 3 : (c6m <= 192) ? 4 : 0;
-        if (sw.solve6 && p.solve5_variant) p.solve7_variant = 0;   // A/B timing: the LDS-tableau kernel behind gemm_T_kernel
-        // one instance: the blocked SPD solve (solve9.hip).  Measured on full-load updates (tools/solve9_probe.py, profiles/r05_solve9_probe.txt), solve kernel alone:
-        // 6n = 84: 94.0 us against solve7's 102.6; 120: 173 against 212; 180: 511 against 797.  At 6n <= 96 the Cholesky of the clone block — the part that does
-        // not depend on the measurements — rides as one more workgroup in the per-feature launch (pipelined frame) or in propagate's launch (staged entry
-        // points), off the chain; the solve kernel then starts at Q = A L.  RVIO_SOLVE7=1 (instrumented build) keeps the register-tableau elimination: A/B timing.
-        if ((batch == 1 || (c6m <= 64 && sw.s9_batch)) && c6m <= 192 && !sw.solve7) {
+        // one instance: the blocked SPD solve (solve9.hip).  Measured on full-load updates (tools/solve9_probe.py, profiles/r05_solve9_probe.txt), solve kernel alone,
+        // against the register-tableau elimination of rounds 3-4: 6n = 84: 94.0 us against 102.6; 120: 173 against 212; 180: 511 against 797.  At 6n <= 96 the Cholesky
+        // of the clone block — the part that does not depend on the measurements — rides as one more workgroup in the per-feature launch (pipelined frame) or in
+        // propagate's launch (staged entry points), off the chain; the solve kernel then starts at Q = A L.
+        if (batch == 1 && c6m <= 192) {
             p.solve9_nt = (c6m <= 64) ? 4 : (c6m <= 96) ? 6 : (c6m <= 128) ? 8 : 12;
             if (p.solve9_nt == 4) p.attr[LPK_SOLVE9_SMALL] = LP_S9SMALL_BYTES;
         }
         // batch handles: throughput, not latency — solve6 keeps four instances resident per CU (33 KB of LDS against 112 KB) and the
         // multi-workgroup gemm_T_kernel costs nothing there (measured at B = 2048: 2.67 ms per batched frame against 3.09)
-        // (round 3, measured and NOT adopted: solve7 with T through the L2 scratch instead of LDS — 11 KB of LDS, eight workgroups per CU, no gemm_T
-        // launch — as the batch form at 6n <= 64, RVIO_BATCH_SOLVE7: 2.62 ms per batched frame at B = 2048 against 2.29 with solve6 behind gemm_T)
-        if (batch > 1 && p.solve5_variant && !sw.solve7 && !(p.solve7_variant == 1 && sw.batch_solve7)) p.solve7_variant = 0;
-        if (batch > 1 && p.solve7_variant == 1) p.solve7_variant = 5;
-        // shipping library: the register-tableau solve survives for batch handles beyond solve6's windows only (6n > 126: solve7_kernel<3, 16, 12>)
-        if (!sw.dbg_build && (p.solve7_variant != 4 || p.solve9_nt)) p.solve7_variant = 0;
+        // (round 3, measured and NOT adopted: the register-tableau solve with T through the L2 scratch instead of LDS — 11 KB of LDS, eight workgroups per CU, no
+        // gemm_T launch — as the batch form at 6n <= 64: 2.62 ms per batched frame at B = 2048 against 2.29 with solve6 behind gemm_T)
+        // ... and beyond solve6's windows (126 < 6n <= 192) the register-tableau solve with the T prologue: solve7_kernel<3, 16, 12>
+        if (batch > 1 && !p.solve5_variant && c6m <= 192) p.solve7_variant = 4;
         if (p.solve5_variant) {
             p.solve5_lds = (size_t)(nw * rpw) * (64 * nch + 1) * sizeof(double);
             p.attr[LPK_SOLVE6_1] = p.attr[LPK_SOLVE6_2] = p.attr[LPK_SOLVE6_3] = lp_max(p.solve5_lds, (size_t)1024);
         }
     }
     const size_t c6t = (c6m + 15) / 16;
-    if (batch >= 128 && c6m <= 60 && !sw.no_joseph_fused) {   // the Joseph form of a batch handle in one kernel, one workgroup per instance
+    if (batch >= 128 && c6m <= 60) {   // the Joseph form of a batch handle in one kernel, one workgroup per instance
         const size_t ls = c6m + 1, dmx = 24 + c6m;
         p.jb_lds = (3 * dmx * ls + lp_max(c6m * ls, (size_t)LP_JB_TL_DOUBLES)) * sizeof(double);
         if (p.jb_lds + statics[LPK_JOSEPH_BATCH] > RVIO_LDS_LIMIT) p.jb_lds = 0;

@@ -23,9 +23,6 @@
 #include "solve7.hip"
 #include "solve9.hip"   // round 5: the solve as blocked SPD factorisations on the matrix cores (one instance; every window up to 6n = 192)
 #include "landmarks.hip"   // Updater::update's landmark cloud (rvio_hip_set_landmarks)
-#ifndef S9_BATCH
-#define S9_BATCH (ab_env("RVIO_S9_BATCH") != nullptr)   // A/B timing: batch handles at 6n <= 64 through solve9_kernel<1, 4> instead of gemm_T + solve6
-#endif
 #pragma clang fp contract(off)
 #include "frontend_kernels.hip"
 #include "klt3.hip"
@@ -83,8 +80,8 @@ struct rvio_hip {
     StageSync stage_tgt = {};
     const unsigned long long* klt_wait = nullptr; unsigned long long klt_target = 0;
     unsigned long long* pyr_signal = nullptr;   // pending: the next detector launch on the image chain's queue bumps it   // this frame's klt_kernel3 polls the image chain's pyramid counter
-    int solve7_variant = 0;      // register-tableau solve with the T prologue (solve7.hip): 1: 6n <= 64, 2: <= 96, 3: <= 128, 4: <= 192
-    int solve9_nt = 0;           // solve9_kernel (solve9.hip): tiles per side of the padded clone block (4, 6, 8, 12), 0: not used (batch handles, RVIO_SOLVE7=1)
+    int solve7_variant = 0;      // register-tableau solve with the T prologue (solve7.hip): 4: batch handles at 126 < 6n <= 192, 0: not used
+    int solve9_nt = 0;           // solve9_kernel (solve9.hip): tiles per side of the padded clone block (4, 6, 8, 12), 0: not used (batch handles)
     double* S9scr = nullptr;     // its slab of tiles in L2: 5 NT^2 x 256 doubles (+ the verdict of the Cholesky role)
     bool chol_ready = false;     // the slab holds L, G of the clone block the next solve will see (written by the role workgroup of the per-feature / propagate launch)
     float* eig_map = nullptr;    // W x H min-eigenvalue map of rvio_hip_get_corners(eig): allocated on first use
@@ -108,9 +105,8 @@ struct rvio_hip {
     hipStream_t stream_d = nullptr;               // side stream of the front end: forks from / joins the tracker stream (see build_pyramid_dev)
     hipStream_t stream_c = nullptr;               // CLAHE stream of the run-ahead mode (frame k+1 is equalised while frame k is still being detected)
     hipEvent_t evC[kIC] = {nullptr, nullptr, nullptr};   // equalised image + pyramid of the frame ready, by image chain
-    hipStream_t stream_e = nullptr;               // third image-chain stream (the chain is ~200 us long in situ: two in flight made it a co-bottleneck of the 130 us period)
     int n_ic = 2;                                 // image chains in flight (<= kIC)
-    int ic = 0;                                   // image chain (stream / detector scratch / LUT set) of the call in progress: frame_no % kIC in run-ahead mode, else the parity
+    int ic = 0;                                   // image chain (stream / detector scratch / LUT set) of the call in progress: frame_no % n_ic in run-ahead mode, else the parity
     hipStream_t side = nullptr;                   // stream of pyramid / KLT / RANSAC of the call in progress (stream_d beside the detector, else ts)
     hipEvent_t evD0 = nullptr, evD1 = nullptr;
     uint8_t* hb_img[2] = {nullptr, nullptr};      // staging of rvio_hip_frame (host buffers), by frame parity
@@ -167,7 +163,6 @@ struct rvio_hip {
     const rvio_imu* time_imu = nullptr; int time_m = 0;   // the IMU batch of the last fused frame (rvio_hip_debug_time_kernel(8) only: the caller's buffer)
     int fuse_m = -1;                      // >= 0 while such a propagate is pending
     bool fuse_ok = false;
-    bool one_stream = false;
     bool wide_px = false;            // throughput forms of the image kernels (several pixels per thread): batch handles of >= 8 instances
     bool front_end = true;           // a batch handle may carry the filter only
     bool det_in_slab = false;        // batch handle with front end: the detector's buffers are slab members too
@@ -186,7 +181,7 @@ struct rvio_hip {
     LmOut lm = {nullptr, nullptr, nullptr, nullptr, 0};
 };
 
-// ---------------------------------------------------------------- environment surface of the SHIPPING library: two variables.
+// ---------------------------------------------------------------- environment surface of the library: three variables of its own, plus the profiler's.
 //   RVIO_PARANOID     every cross-queue hand-off in its most conservative form (A/B against the default, and the thing to set when a
 //                     runtime / firmware is suspected).  "1" = all of it; a larger value is a bit mask for bisection:
 //                       2  events with the default flags (system-scope release at every record) instead of hipEventDisableSystemFence
@@ -195,8 +190,11 @@ struct rvio_hip {
 //                      16  rvio_hip_frame waits on the host for its H2D staging copies before it enqueues the frame
 //                      32  every whole-frame call drains all streams of the handle before it returns
 //   RVIO_NO_RUNAHEAD  the pipelined path without the run-ahead image chains (book-keeping back on the tracker stream)
-// Every other RVIO_* switch (kernel forms, stream layouts, unsafe timing experiments) exists in the instrumented build only
-// (-DRVIO_DBG_CLOCKS, tools/chain_clocks.py): a stray environment variable cannot change what the shipping pipeline launches.
+//   RVIO_NO_LITERAL   no literal sweep: the structural rank rule alone, as up to round 5 (read when a handle is created)
+//   ROCPROF_COUNTER_COLLECTION  (exported by rocprofv3 --pmc) a counter-collecting profiler serialises kernels across queues: no device-side polls
+// Kernel forms and stream layouts follow from what the code observes (window length, batch size, the LDS budget of launch_plan.h), never from
+// the environment; the instrumented build (-DRVIO_DBG_CLOCKS, tools/chain_clocks.py) launches what the shipping build launches and adds its
+// stamps (and RVIO_DBG_HOST, which prints host-side enqueue times and selects nothing).
 enum { PAR_SYSFENCE = 2, PAR_NO_DEVPOLL = 4, PAR_PLAIN_STREAMS = 8, PAR_SYNC_COPIES = 16, PAR_DRAIN = 32, PAR_ALL = 62 };
 static int paranoid_bits() {
     static const int v = [] {
@@ -207,25 +205,15 @@ static int paranoid_bits() {
     }();
     return v;
 }
-#ifdef RVIO_DBG_CLOCKS
-static const char* ab_env(const char* name) { return getenv(name); }
-#else
-static const char* ab_env(const char*) { return nullptr; }
-#endif
+static bool no_runahead() {
+    static const bool v = getenv("RVIO_NO_RUNAHEAD") != nullptr;
+    return v;
+}
 // The handle's events only order kernels of ONE device across its streams; the host only ever WAITS for them (hipEventSynchronize on the
 // pinned ring's events, hipStreamSynchronize elsewhere): no timing, and no system-scope fence when they are recorded — that fence writes the
 // dirty L2 lines of the recording queue back before the NEXT kernel of that queue may start (measured: a 35 us hole in the tracker stream per frame)
-static unsigned ev_flags() { return (paranoid_bits() & PAR_SYSFENCE) || ab_env("RVIO_EVENT_SYSFENCE") ? hipEventDisableTiming : (hipEventDisableTiming | hipEventDisableSystemFence); }
+static unsigned ev_flags() { return (paranoid_bits() & PAR_SYSFENCE) ? hipEventDisableTiming : (hipEventDisableTiming | hipEventDisableSystemFence); }
 #define kEvFlags ev_flags()
-// Timing experiments that DROP correctness-critical stream waits exist only in an instrumented build (-DRVIO_DBG_CLOCKS, tools/chain_clocks.py):
-// a stray environment variable must not be able to turn the shipping pipeline racy.
-#ifdef RVIO_DBG_CLOCKS
-static const int kDbgSkip = getenv("RVIO_DBG_SKIP") ? atoi(getenv("RVIO_DBG_SKIP")) : 0;
-static const int kRaDepth = getenv("RVIO_RA_DEPTH") ? std::max(1, std::min(3, atoi(getenv("RVIO_RA_DEPTH")))) : 3;   // 2 = the image chain waits for book-keeping(k-2)
-#else
-static constexpr int kDbgSkip = 0;
-static constexpr int kRaDepth = 3;
-#endif
 #define HIPCHK(h, call)                                                                          \
     do {                                                                                         \
         hipError_t e_ = (call);                                                                  \
@@ -259,7 +247,6 @@ static int dalloc(rvio_hip* h, T** p, size_t n) {
 #define SYNC_FRONT(h)                                                                     \
     do {                                                                                  \
         if ((h)->stream_c) HIPCHK(h, hipStreamSynchronize((h)->stream_c));                \
-        if ((h)->stream_e) HIPCHK(h, hipStreamSynchronize((h)->stream_e));                \
         if ((h)->stream_d) HIPCHK(h, hipStreamSynchronize((h)->stream_d));                \
         HIPCHK(h, hipStreamSynchronize((h)->stream_t));                                   \
     } while (0)
@@ -358,8 +345,7 @@ static int alloc_filter_slab(rvio_hip* h, bool need_tm_global) {
         DALLOC(h, h->lit_rows, lit_rows_doubles(d.ldh, d.rho_max));
         if (h->lit_state_global) DALLOC(h, h->lit_state, lit_state_doubles(d.ldh - 1));
     }
-    static const bool no_geom4 = ab_env("RVIO_NO_GEOM4") != nullptr;   // A/B timing
-    if (h->batch > 1 && d.max_len <= GEOM4_ML && !no_geom4) { DALLOC(h, h->gpose, (size_t)d.Fu * (d.max_len - 1) * 24); DALLOC(h, h->gvalid, d.Fu); }
+    if (h->batch > 1 && d.max_len <= GEOM4_ML) { DALLOC(h, h->gpose, (size_t)d.Fu * (d.max_len - 1) * 24); DALLOC(h, h->gvalid, d.Fu); }
     return RVIO_OK;
 }
 
@@ -411,18 +397,14 @@ static int alloc_frontend_slab(rvio_hip* h) {
 // of the rate of eight handles on the shared pool), so only the first live handle of a process takes private queues; the others share the pool
 // as before (many streams per GPU are what batch handles are for).
 static std::atomic<int> g_private_queue_handles{0};
-static hipError_t make_stream(rvio_hip* h, hipStream_t* s, bool front_end = false) {
-    static const int mode = (paranoid_bits() & PAR_PLAIN_STREAMS) ? 0 : (ab_env("RVIO_STREAM_MODE") ? atoi(ab_env("RVIO_STREAM_MODE")) : 1);
-    if (mode == 0 || !h->private_queues) { h->queues_shared = true; return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
+static hipError_t make_stream(rvio_hip* h, hipStream_t* s) {
+    if ((paranoid_bits() & PAR_PLAIN_STREAMS) || !h->private_queues) { h->queues_shared = true; return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
     hipDeviceProp_t prop;
     hipError_t e = hipGetDeviceProperties(&prop, h->device);
     if (e != hipSuccess) return e;
     const int words = (prop.multiProcessorCount + 31) / 32;
     std::vector<uint32_t> mask((size_t)std::max(words, 1), 0xffffffffu);
     if (prop.multiProcessorCount % 32) mask.back() = (1u << (prop.multiProcessorCount % 32)) - 1u;
-    // experiment: the front-end streams leave every `fe_skip`-th CU to the filter stream (RVIO_FE_SKIP=4: three quarters of the chip)
-    static const int fe_skip = ab_env("RVIO_FE_SKIP") ? atoi(ab_env("RVIO_FE_SKIP")) : 0;
-    if (front_end && fe_skip > 1) for (int c = 0; c < prop.multiProcessorCount; ++c) if (c % fe_skip == 0) mask[c / 32] &= ~(1u << (c % 32));
     e = hipExtStreamCreateWithCUMask(s, (uint32_t)mask.size(), mask.data());
     if (e != hipSuccess) { (void)hipGetLastError(); h->queues_shared = true; return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
     return e;
@@ -431,6 +413,13 @@ static hipError_t make_stream(rvio_hip* h, hipStream_t* s, bool front_end = fals
 static bool profiler_serialises() {
     const char* e = getenv("ROCPROF_COUNTER_COLLECTION");
     return e && *e && std::strcmp(e, "0") != 0 && std::strcmp(e, "False") != 0 && std::strcmp(e, "false") != 0;
+}
+// Stream-level events instead of device-side polls (StageSync counters, gate / signal kernels): on request (RVIO_PARANOID), and when a
+// counter-collecting profiler is attached (rocprofv3 --pmc exports ROCPROF_COUNTER_COLLECTION): it serialises kernels across queues, and a
+// kernel that polls a counter another queue's kernel bumps would sit there until its 30 s time-out.
+static bool no_device_polls() {
+    static const bool v = (paranoid_bits() & PAR_NO_DEVPOLL) || profiler_serialises();
+    return v;
 }
 
 // The dynamic-LDS limit of a kernel is a property of the PROCESS, not of a handle: a later handle with a smaller need (a shorter window, a
@@ -505,8 +494,7 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
     rvio_hip* h = new rvio_hip();
     h->cfg = *cfg; h->device = device; h->batch = batch;
     h->front_end = front_end; h->det_in_slab = front_end && batch > 1;
-    h->wide_px = batch >= 8;
-    if (const char* e = ab_env("RVIO_WIDE_PX")) h->wide_px = atoi(e) != 0;   // A/B timing and tests (the two forms must agree bit for bit)
+    h->wide_px = batch >= 8;   // (tests switch it through rvio_hip_debug_kernel_forms: the two forms must agree bit for bit)
     fill_devcfg(cfg, &h->dc);
     const DevCfg& d = h->dc;
     if (d.grid_cols * d.grid_rows < 1) { delete h; return RVIO_ERR_INVALID; }
@@ -514,40 +502,27 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
     HIPCHK(h, hipSetDevice(device));
     // launch geometry (launch_plan.h: LDS sizes, kernel variants, what moves from LDS to global memory) — before anything is allocated: a configuration
     // whose footprint does not fit a CU beside the kernels' static LDS is refused here, not by a failed launch
-    LaunchSwitches sw;
-    sw.solve6 = ab_env("RVIO_SOLVE6") != nullptr; sw.solve7 = ab_env("RVIO_SOLVE7") != nullptr; sw.s9_batch = S9_BATCH;
-    sw.batch_solve7 = ab_env("RVIO_BATCH_SOLVE7") != nullptr; sw.no_joseph_fused = ab_env("RVIO_NO_JOSEPH_FUSED") != nullptr;
-    sw.no_fused_propagate = ab_env("RVIO_NO_FUSED_PROPAGATE") != nullptr;
-#ifdef RVIO_DBG_CLOCKS
-    sw.dbg_build = true;
-#endif
     const size_t* statics = nullptr;
     HIPCHK(h, static_lds_table(&statics));
-    const LaunchPlan plan = launch_plan(cfg->max_track_len, cfg->n_features, batch, statics, sw);
+    const LaunchPlan plan = launch_plan(cfg->max_track_len, cfg->n_features, batch, statics);
     if (plan.rc) { h->err = plan.why; return RVIO_ERR_UNSUPPORTED; }
     h->private_queues = g_private_queue_handles.fetch_add(1) == 0;
     if (!h->private_queues) g_private_queue_handles.fetch_sub(1);
     HIPCHK(h, make_stream(h, &h->stream));
-    h->one_stream = ab_env("RVIO_ONE_STREAM") != nullptr;   // profiling only: every kernel on the filter stream (clean per-kernel times)
-    if (h->one_stream) h->stream_t = h->stream_d = h->stream_c = h->stream_e = h->stream;
-    else {
-        HIPCHK(h, make_stream(h, &h->stream_t, true));
-        HIPCHK(h, make_stream(h, &h->stream_d, true));
-        HIPCHK(h, make_stream(h, &h->stream_c, true));
-        // Image chains in flight (plan.n_ic).  Two (default): with the filter, tracker and side streams that makes FOUR busy queues.  A third chain on a
-        // fifth queue was measured (RVIO_IC=3): the frame period goes from 131 to 180-250 us whatever CUs the front end is kept off — beyond
-        // four busy queues the command processor time-slices them.
-        // Long windows (96 < 6n <= 192: the solve in its split form, filter chain >= 250 us): ONE image chain in flight is enough (the chain is ~180 us),
-        // and the queue that frees runs the Cholesky factor of the clone block beside the filter chain (augment_compose_dev).  A FIFTH queue for it was
-        // measured: cfg C 3.2 k frames/s instead of 3.9 k — the command processor time-slices beyond four busy queues.
-        h->n_ic = plan.n_ic;
-        if (const char* e = ab_env("RVIO_IC")) h->n_ic = std::max(1, std::min((int)rvio_hip::kIC, atoi(e)));
-        if (h->n_ic > 2) HIPCHK(h, make_stream(h, &h->stream_e, true));
-        if (plan.chol_queue && h->n_ic == 1) {
-            h->stream_l = h->stream_c;
-            HIPCHK(h, hipEventCreateWithFlags(&h->evA, kEvFlags));
-            HIPCHK(h, hipEventCreateWithFlags(&h->evL, kEvFlags));
-        }
+    HIPCHK(h, make_stream(h, &h->stream_t));
+    HIPCHK(h, make_stream(h, &h->stream_d));
+    HIPCHK(h, make_stream(h, &h->stream_c));
+    // Image chains in flight (plan.n_ic).  Two (default): with the filter, tracker and side streams that makes FOUR busy queues.  A third chain on a
+    // fifth queue was measured: the frame period goes from 131 to 180-250 us whatever CUs the front end is kept off — beyond
+    // four busy queues the command processor time-slices them.
+    // Long windows (96 < 6n <= 192: the solve in its split form, filter chain >= 250 us): ONE image chain in flight is enough (the chain is ~180 us),
+    // and the queue that frees runs the Cholesky factor of the clone block beside the filter chain (augment_compose_dev).  A FIFTH queue for it was
+    // measured: cfg C 3.2 k frames/s instead of 3.9 k — the command processor time-slices beyond four busy queues.
+    h->n_ic = plan.n_ic;
+    if (plan.chol_queue) {
+        h->stream_l = h->stream_c;
+        HIPCHK(h, hipEventCreateWithFlags(&h->evA, kEvFlags));
+        HIPCHK(h, hipEventCreateWithFlags(&h->evL, kEvFlags));
     }
     HIPCHK(h, hipEventCreateWithFlags(&h->evD0, kEvFlags));
     HIPCHK(h, hipEventCreateWithFlags(&h->evD1, kEvFlags));
@@ -563,7 +538,6 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
         HIPCHK(h, hipEventCreateWithFlags(&h->evIn[b], kEvFlags));
     }
     h->feat_threads = plan.feat_threads;
-    if (const char* ft = ab_env("RVIO_FEAT_THREADS")) h->feat_threads = atoi(ft);   // A/B timing only (64, 128 or 256)
     h->trunc_lds = plan.trunc_lds; h->lit_state_global = plan.lit_state_global; h->lit_batch_lds = plan.lit_batch_lds;
     h->feat_lds = plan.feat_lds;
     const bool need_tm_global = plan.tm_global;
@@ -617,14 +591,6 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
     if (h->solve9_nt) DALLOC(h, h->S9scr, S9_SLAB_DOUBLES(h->solve9_nt) * (size_t)batch);
     for (int k = 0; k < LPK_COUNT; ++k)
         if (plan.attr[k]) HIPCHK(h, lds_attr(lp_kernel_fn(k), (int)plan.attr[k]));
-#ifdef RVIO_DBG_CLOCKS
-    if (h->solve7_variant == 1)
-    {
-        HIPCHK(h, lds_attr((const void*)solve7_kernel<1, 16, 4>, (3 * 64 * 65 + 24 * 64) * (int)sizeof(double)));
-        HIPCHK(h, lds_attr((const void*)solve7_kernel<1, 8, 8>, (3 * 64 * 65 + 24 * 64) * (int)sizeof(double)));
-        HIPCHK(h, lds_attr((const void*)solve7_kernel<1, 4, 16>, (3 * 64 * 65 + 24 * 64) * (int)sizeof(double)));
-    }
-#endif
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RVIO_OK;
 }
@@ -641,7 +607,6 @@ void rvio_hip_destroy(rvio_hip* h) {
     if (!h) return;
     hipSetDevice(h->device);
     if (h->stream_c) hipStreamSynchronize(h->stream_c);
-    if (h->stream_e) hipStreamSynchronize(h->stream_e);
     if (h->stream_d) hipStreamSynchronize(h->stream_d);
     if (h->stream_t) hipStreamSynchronize(h->stream_t);
     if (h->stream) hipStreamSynchronize(h->stream);
@@ -653,14 +618,13 @@ void rvio_hip_destroy(rvio_hip* h) {
     if (h->evL) hipEventDestroy(h->evL);
     if (h->evD0) hipEventDestroy(h->evD0);
     if (h->evD1) hipEventDestroy(h->evD1);
-    if (h->stream_d && !h->one_stream) hipStreamDestroy(h->stream_d);
-    if (h->stream_c && !h->one_stream) hipStreamDestroy(h->stream_c);
-    if (h->stream_e && !h->one_stream) hipStreamDestroy(h->stream_e);
+    if (h->stream_d) hipStreamDestroy(h->stream_d);
+    if (h->stream_c) hipStreamDestroy(h->stream_c);
     for (int b = 0; b < rvio_hip::kIC; ++b) if (h->evC[b]) hipEventDestroy(h->evC[b]);
     for (int b = 0; b < 4; ++b) { if (h->evT[b]) hipEventDestroy(h->evT[b]); if (h->evH[b]) hipEventDestroy(h->evH[b]); }
     for (int b = 0; b < rvio_hip::kHand; ++b) if (h->evF[b]) hipEventDestroy(h->evF[b]);
     for (int b = 0; b < 2; ++b) if (h->evIn[b]) hipEventDestroy(h->evIn[b]);
-    if (h->stream_t && !h->one_stream) hipStreamDestroy(h->stream_t);
+    if (h->stream_t) hipStreamDestroy(h->stream_t);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
 }
@@ -824,10 +788,9 @@ static int ensure_imu_capacity(rvio_hip* h, int m) {
     return RVIO_OK;
 }
 static int propagate_dev(rvio_hip* h, const rvio_imu* d_imu, int m, size_t imu_bs = 0, hipStream_t st = nullptr) {   // imu_bs = 0: every instance integrates the same samples
-    static const bool prop_b = ab_env("RVIO_NO_PROP_B") == nullptr;   // A/B timing
     if (!st) st = h->stream;
     h->time_imu = d_imu; h->time_m = m;   // (rvio_hip_debug_time_kernel(8))
-    if (h->batch > 8 && prop_b)
+    if (h->batch > 8)
         hipLaunchKernelGGL(propagate_kernel3b, dim3(1, 1, h->batch), dim3(256), 0, st, h->dc, h->meta, h->n_clones_host, h->x[h->cur], h->P[h->cur], d_imu, m,
                            h->slab_bytes, imu_bs);
     else if (h->batch == 1 && h->solve9_nt && h->solve9_nt <= 6 && h->n_clones_host >= 1 && !imu_bs) {
@@ -886,43 +849,57 @@ static void launch_gram_batch(rvio_hip* h, int n) {
                            (const unsigned char*)h->t.types, (const int*)h->t.len, h->block, h->slab_bytes, h->bin, lit_args(h, h->lit_batch_lds));
 }
 
+// U1..U5 of shard `rank` of `world`, one workgroup per feature slot: the latency form for one stream (every operand load of a gate tile in flight at
+// once), the throughput form for a batch (with geom4_kernel's pose chains where the handle has them)
+static void launch_feat_build(rvio_hip* h, int n, int rank, int world) {
+    const DevCfg& d = h->dc;
+    const dim3 g(d.Fu, 1, h->batch), b(h->feat_threads);
+    if (h->batch == 1)
+        hipLaunchKernelGGL(feat_build_kernel<16>, g, b, h->feat_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
+                           h->t.n_feat, h->t.types, h->t.len, h->t.meas, rank, world, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv,
+                           h->tm_global, h->slab_bytes, h->bin, h->meta, (const double*)nullptr, (const int*)nullptr, h->lit_rows);
+    else
+        hipLaunchKernelGGL(feat_build_kernel<4>, g, b, h->feat_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
+                           h->t.n_feat, h->t.types, h->t.len, h->t.meas, rank, world, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv,
+                           h->tm_global, h->slab_bytes, h->bin, h->meta, (const double*)h->gpose, (const int*)h->gvalid, h->lit_rows);
+}
+// propagate + U1..U5 in one launch (independent: see feat_prop_kernel); single instance (sharded or not: every rank propagates, builds its features)
+static void launch_feat_prop(rvio_hip* h, int n, const rvio_imu* d_imu, int m, int rank, int world) {
+    const DevCfg& d = h->dc;
+    // solve9 at 6n <= 96: the Cholesky of the clone block as one more workgroup of this launch (the solve of this very update follows on the stream)
+    const bool chol = h->solve9_nt && h->solve9_nt <= 6 && n >= 1;
+    hipLaunchKernelGGL(feat_prop_kernel, dim3(d.Fu + 1 + (chol ? 1 : 0)), dim3(256), h->fprop_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
+                       h->t.n_feat, h->t.types, h->t.len, h->t.meas, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv, h->tm_global, h->bin,
+                       h->meta, d_imu, m, chol ? h->S9scr : (double*)nullptr, h->solve9_nt, rank, world, h->lit_rows);
+    h->chol_ready = chol;
+}
+// reduction of the per-feature shares; finish: the last workgroup turns the block into [A|b] in place (rank truncation included)
+// one stream: 64 elements per workgroup (the shares are remote reads: spread them over many CUs); batch handles: 256 (fewer, fuller workgroups)
+static void launch_gram_reduce(rvio_hip* h, int n, bool finish) {
+    const DevCfg& d = h->dc;
+    const int B = h->batch, gram_chunk = (B == 1) ? 64 : 256;
+    hipLaunchKernelGGL(gram_reduce_kernel, dim3(std::max(1, std::min(1024, (6 * n * d.ldh + gram_chunk - 1) / gram_chunk)), 1, B), dim3(256), h->trunc_lds, h->stream, d, n,
+                       h->partial, h->nrows, h->t.types, h->t.len, h->block, h->gram_cnt, finish ? 1 : 0, (B == 1) ? 1 : 0, h->slab_bytes, h->bin, lit_args(h, h->trunc_lds));
+}
+
 static int update_local_dev(rvio_hip* h, int rank, int world, bool combine) {
     const DevCfg& d = h->dc;
     const int n = h->n_clones_host;
-    const size_t bs = h->slab_bytes;
     const int B = h->batch;
-    if (h->fuse_m >= 0) {   // propagate + U1..U5 in one launch (independent: see feat_prop_kernel); single instance (sharded or not: every rank propagates, builds its features)
-        // solve9 at 6n <= 96: the Cholesky of the clone block as one more workgroup of this launch (the solve of this very update follows on the stream)
-        const bool chol = h->solve9_nt && h->solve9_nt <= 6 && n >= 1;
-        double* cs = chol ? h->S9scr : (double*)nullptr;
-        const int extra = 1 + (chol ? 1 : 0);
-        hipLaunchKernelGGL(feat_prop_kernel, dim3(d.Fu + extra), dim3(256), h->fprop_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
-                           h->t.n_feat, h->t.types, h->t.len, h->t.meas, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv, h->tm_global, h->bin,
-                           h->meta, h->fuse_imu, h->fuse_m, cs, h->solve9_nt, rank, world, h->lit_rows);
-        h->chol_ready = chol;
+    if (h->fuse_m >= 0) {
+        launch_feat_prop(h, n, h->fuse_imu, h->fuse_m, rank, world);
         h->fuse_m = -1;
-    } else
-    if (B == 1)   // one stream: the latency form (every operand load of a gate tile in flight at once)
-    hipLaunchKernelGGL(feat_build_kernel<16>, dim3(d.Fu, 1, B), dim3(h->feat_threads), h->feat_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
-                       h->t.n_feat, h->t.types, h->t.len, h->t.meas, rank, world, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv,
-                       h->tm_global, bs, h->bin, h->meta, (const double*)nullptr, (const int*)nullptr, h->lit_rows);
-    else {
-    if (h->gpose)   // U1 + U2 four features per wave, ahead of the per-feature kernel (which then only fetches the pose chain and the triple)
-        hipLaunchKernelGGL(geom4_kernel, dim3((d.Fu + 3) / 4, 1, B), dim3(64), 0, h->stream, d, n, h->x[h->cur], h->t.n_feat, h->t.types, h->t.len, h->t.meas,
-                           h->gpose, h->pfinv, h->gvalid, bs, h->bin);
-    hipLaunchKernelGGL(feat_build_kernel<4>, dim3(d.Fu, 1, B), dim3(h->feat_threads), h->feat_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
-                       h->t.n_feat, h->t.types, h->t.len, h->t.meas, rank, world, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv,
-                       h->tm_global, bs, h->bin, h->meta, (const double*)h->gpose, (const int*)h->gvalid, h->lit_rows);
+    } else {
+        if (h->gpose)   // U1 + U2 four features per wave, ahead of the per-feature kernel (which then only fetches the pose chain and the triple)
+            hipLaunchKernelGGL(geom4_kernel, dim3((d.Fu + 3) / 4, 1, B), dim3(64), 0, h->stream, d, n, h->x[h->cur], h->t.n_feat, h->t.types, h->t.len, h->t.meas,
+                               h->gpose, h->pfinv, h->gvalid, h->slab_bytes, h->bin);
+        launch_feat_build(h, n, rank, world);
     }
-    // unsharded: the last workgroup turns the block into [A|b] in place (rank truncation included); sharded: the block is the payload
-    // one stream: 64 elements per workgroup (the shares are remote reads: spread them over many CUs); batch handles: 256 (fewer, fuller workgroups)
-    const int gram_chunk = (B == 1) ? 64 : 256;
-    static const bool no_gram_batch = ab_env("RVIO_NO_GRAM_BATCH") != nullptr;   // A/B timing
-    if (B >= 128 && world == 1 && combine && h->gram_batch_lds && !no_gram_batch)   // batch handle, [A|b] fits in LDS: one workgroup per instance, stored tiles only
+    // unsharded: the reduction finishes into [A|b]; sharded: the block is the payload
+    if (B >= 128 && world == 1 && combine && h->gram_batch_lds)   // batch handle, [A|b] fits in LDS: one workgroup per instance, stored tiles only
         launch_gram_batch(h, n);
     else
-    hipLaunchKernelGGL(gram_reduce_kernel, dim3(std::max(1, std::min(1024, (6 * n * d.ldh + gram_chunk - 1) / gram_chunk)), 1, B), dim3(256), h->trunc_lds, h->stream, d, n,
-                       h->partial, h->nrows, h->t.types, h->t.len, h->block, h->gram_cnt, (world == 1 && combine) ? 1 : 0, (B == 1) ? 1 : 0, bs, h->bin, lit_args(h, h->trunc_lds));
+        launch_gram_reduce(h, n, world == 1 && combine);
     HIPCHK(h, hipGetLastError());
     return RVIO_OK;
 }
@@ -931,101 +908,57 @@ static void launch_solve(rvio_hip* h, int n, const double* Ab, bool defer_dx = f
     const DevCfg& d = h->dc;
     double *xin = h->x[h->cur], *xout = h->x[h->cur ^ 1], *Pc = h->P[h->cur];
     const dim3 gb(1, 1, h->batch);
-    if (h->solve9_nt) {   // blocked SPD factorisations on the matrix cores (solve9.hip): one workgroup, one launch
+    if (h->solve9_nt) {   // one instance: blocked SPD factorisations on the matrix cores (solve9.hip)
         if (h->chol_async && hipStreamWaitEvent(h->stream, h->evL, 0) != hipSuccess) { h->chol_async = false; h->chol_ready = false; }   // the factor that started behind the last augment / compose (a failed wait: the solve factors Pcc itself)
         const bool pre = h->chol_ready || h->chol_async;   // L, G of the clone block are in the slab already (role workgroup of this update's per-feature / propagate launch; stream_l)
         h->chol_ready = false; h->chol_async = false;
+        const size_t bs = h->slab_bytes;
         switch (h->solve9_nt) {
         case 4:
-            static const bool s9_generic = ab_env("RVIO_S9_GENERIC") != nullptr;   // A/B timing: the generic kernel (tiles through the L2 slab) at 6n <= 64
-            if (pre && !s9_generic) {
-                // in the frame's update the Joseph stage follows on the stream: dx = Pc y and the state injection become role workgroups of that launch (launch_ug_final)
-                static const bool no_dx_small = ab_env("RVIO_S9_NO_DX_ROLE") != nullptr;   // A/B timing
-                const bool role = defer_dx && h->batch == 1 && 6 * n <= 60 && !no_dx_small && !ab_env("RVIO_NO_JOSEPH_LDS");
+            // in the frame's update the Joseph stage follows on the stream (6n <= 60 here: joseph_lds_kernel): dx = Pc y and the state injection become role
+            // workgroups of that launch (launch_ug_final)
+            if (pre) {
                 hipLaunchKernelGGL(solve9_small_kernel, dim3(1), dim3(1024), sizeof(S9SmallLds), h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout,
-                                   role ? h->S9scr + S9_YP_OFF(4) : (double*)nullptr);
-                h->dx_pending = role;
+                                   defer_dx ? h->S9scr + S9_YP_OFF(4) : (double*)nullptr);
+                h->dx_pending = defer_dx;
             }
-#ifdef RVIO_DBG_CLOCKS   // (A/B form RVIO_S9_GENERIC: compiled into the instrumented build only — round 6, kernel forms no handle of the shipping library launches)
-            else if (pre) hipLaunchKernelGGL((solve9_kernel<1, 4, true>), gb, dim3(1024), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, h->slab_bytes, (size_t)0);
-#endif
-            else hipLaunchKernelGGL((solve9_kernel<1, 4>), gb, dim3(1024), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, h->slab_bytes,
-                                    h->batch > 1 ? S9_SLAB_DOUBLES(4) * sizeof(double) : (size_t)0);
+            else hipLaunchKernelGGL((solve9_kernel<1, 4>), gb, dim3(1024), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, bs, (size_t)0);
             return;
         case 6:
-        {
-            // the frame's update at 64 < 6n_max <= 96: dx = Pc y and the state injection ride in the Joseph stage's launch (joseph_lds_kernel while the window still
-            // holds <= 10 clones, ug_tile_kernel<0> beyond 64 columns; the two-launch LDS form in between has no roles)
-            static const bool no_dx_mid = ab_env("RVIO_S9_NO_DX_ROLE") != nullptr;   // A/B timing
-            const bool role = defer_dx && h->batch == 1 && !no_dx_mid && (6 * n <= 60 ? !ab_env("RVIO_NO_JOSEPH_LDS") : (6 * n > 64 && !ab_env("RVIO_NO_UG_TILE")));
-            if (pre) hipLaunchKernelGGL((solve9_kernel<2, 3, true>), gb, dim3(576), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, h->slab_bytes, (size_t)0, role ? 1 : 0);
-            else hipLaunchKernelGGL((solve9_kernel<2, 3>), gb, dim3(576), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, h->slab_bytes, (size_t)0, role ? 1 : 0);
-            h->dx_pending = role;
-        }
+            // the frame's update at 64 < 6n_max <= 96: dx = Pc y and the state injection ride in the Joseph stage's launch — joseph_lds_kernel while the window still
+            // holds <= 10 clones, ug_tile_kernel<0> from 11 clones on (no window has 60 < 6n <= 64: the two-launch LDS form, which has no roles, serves the
+            // separately timed stages of rvio_hip_debug_time_kernel only)
+            if (pre) hipLaunchKernelGGL((solve9_kernel<2, 3, true>), gb, dim3(576), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, bs, (size_t)0, defer_dx ? 1 : 0);
+            else hipLaunchKernelGGL((solve9_kernel<2, 3>), gb, dim3(576), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, bs, (size_t)0, defer_dx ? 1 : 0);
+            h->dx_pending = defer_dx;
             return;
         default: break;
         }
         // 6n > 96: the split form — the four product phases as launches that fill the chip, the two factorisations as one workgroup each (solve9.hip)
-        static const bool s9_one = ab_env("RVIO_S9_ONE") != nullptr;   // A/B timing: everything in ONE workgroup
         const int NT = h->solve9_nt, nwg = (NT * NT + 3) / 4;
-        if (s9_one) {
-            if (NT == 8) hipLaunchKernelGGL((solve9_kernel<2, 4>), gb, dim3(1024), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, h->slab_bytes, (size_t)0);
-            else hipLaunchKernelGGL((solve9_kernel<3, 4>), gb, dim3(1024), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, h->slab_bytes, (size_t)0);
-            return;
-        }
         if (!pre) {
             if (NT == 8) hipLaunchKernelGGL((solve9_chol_kernel<2, 4>), dim3(1), dim3(1024), 0, h->stream, d, n, Pc, h->S9scr);
             else hipLaunchKernelGGL((solve9_chol_kernel<3, 4>), dim3(1), dim3(1024), 0, h->stream, d, n, Pc, h->S9scr);
         }
         hipLaunchKernelGGL(solve9_prod_kernel<0>, dim3(nwg), dim3(256), 0, h->stream, d, n, Ab, h->S9scr, h->W, NT);
         hipLaunchKernelGGL(solve9_prod_kernel<1>, dim3(nwg), dim3(256), 0, h->stream, d, n, Ab, h->S9scr, h->W, NT);
-        static const bool sweep4 = ab_env("RVIO_S9_SWEEP4") != nullptr;   // A/B timing: the sweep on 2 x 2 waves with 16 / 36 tiles each (no spills, one wave per matrix pipe)
-#ifdef RVIO_DBG_CLOCKS
-        if (sweep4) {
-            if (NT == 8) hipLaunchKernelGGL((solve9_sweep_kernel<4, 2>), dim3(1), dim3(256), 0, h->stream, d, Ab, h->S9scr);
-            else hipLaunchKernelGGL((solve9_sweep_kernel<6, 2>), dim3(1), dim3(256), 0, h->stream, d, Ab, h->S9scr);
-        } else
-#else
-        (void)sweep4;
-#endif
         if (NT == 8) hipLaunchKernelGGL((solve9_sweep_kernel<2, 4>), dim3(1), dim3(1024), 0, h->stream, d, Ab, h->S9scr);
         else hipLaunchKernelGGL((solve9_sweep_kernel<3, 4>), dim3(1), dim3(1024), 0, h->stream, d, Ab, h->S9scr);
         hipLaunchKernelGGL(solve9_prod_kernel<2>, dim3(nwg), dim3(256), 0, h->stream, d, n, Ab, h->S9scr, h->W, NT);
         hipLaunchKernelGGL(solve9_prod_kernel<3>, dim3(nwg), dim3(256), 0, h->stream, d, n, Ab, h->S9scr, h->W, NT);
-        static const bool no_dx_role = ab_env("RVIO_S9_NO_DX_ROLE") != nullptr;   // A/B timing
-        if (defer_dx && 6 * n > 64 && !no_dx_role && !ab_env("RVIO_NO_UG_TILE")) h->dx_pending = true;   // (6n <= 64 while the window fills: launch_ug_final takes its short-window kernels)
+        if (defer_dx && 6 * n > 64) h->dx_pending = true;   // (6n <= 64 while the window fills: launch_ug_final takes its short-window kernels)
         else hipLaunchKernelGGL(solve9_dx_kernel, dim3(1), dim3(1024), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, NT);
         return;
     }
-    switch (h->solve7_variant) {   // T = s2 I + A Pcc is formed by the kernel itself
-#ifdef RVIO_DBG_CLOCKS   // (the register-tableau solve of rounds 3-4 at 6n <= 128: plain handles run solve9, batch handles solve6 there — A/B forms of the instrumented build)
-    case 1: {
-        static const int nw = ab_env("RVIO_S7_NW") ? atoi(ab_env("RVIO_S7_NW")) : 4;
-        const size_t lds = (size_t)(3 * 64 * 65 + 24 * 64) * sizeof(double);
-        if (nw == 8) hipLaunchKernelGGL((solve7_kernel<1, 8, 8>), gb, dim3(512), lds, h->stream, d, h->meta, n, Ab, xin, Pc, h->Tbuf, h->W, xout, h->slab_bytes);
-        else if (nw == 16) hipLaunchKernelGGL((solve7_kernel<1, 4, 16>), gb, dim3(1024), lds, h->stream, d, h->meta, n, Ab, xin, Pc, h->Tbuf, h->W, xout, h->slab_bytes);
-        else hipLaunchKernelGGL((solve7_kernel<1, 16, 4>), gb, dim3(256), lds, h->stream, d, h->meta, n, Ab, xin, Pc, h->Tbuf, h->W, xout, h->slab_bytes);
-        return;
-    }
-    case 2: {
-        static const int nw2 = ab_env("RVIO_S7_V2") ? atoi(ab_env("RVIO_S7_V2")) : 12;   // waves of the 6n <= 96 form (measured at 6n = 84: 8 -> 109 us, 12 -> 102, 16 -> 119)
-        if (nw2 == 16) hipLaunchKernelGGL((solve7_kernel<2, 6, 16>), gb, dim3(1024), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->Tbuf, h->W, xout, h->slab_bytes);
-        else if (nw2 == 12) hipLaunchKernelGGL((solve7_kernel<2, 8, 12>), gb, dim3(768), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->Tbuf, h->W, xout, h->slab_bytes);
-        else hipLaunchKernelGGL((solve7_kernel<2, 12, 8>), gb, dim3(512), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->Tbuf, h->W, xout, h->slab_bytes);
-        return;
-    }
-    case 3: hipLaunchKernelGGL((solve7_kernel<2, 16, 8>), gb, dim3(512), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->Tbuf, h->W, xout, h->slab_bytes); return;
-    case 5: hipLaunchKernelGGL((solve7_kernel<1, 16, 4, false, 8>), gb, dim3(256), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->Tbuf, h->W, xout, h->slab_bytes); return;
-#endif
-    case 4: hipLaunchKernelGGL((solve7_kernel<3, 16, 12>), gb, dim3(768), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->Tbuf, h->W, xout, h->slab_bytes); return;
-    default: break;
-    }
-    if (h->solve5_variant == 1)
-        hipLaunchKernelGGL((solve6_kernel<1, 8, 8>), dim3(1, 1, h->batch), dim3(512), h->solve5_lds, h->stream, d, h->meta, n, h->Tbuf, Ab, xin, Pc, h->W, xout, h->slab_bytes);
+    // batch handles.  Beyond solve6's windows (6n > 126) the register-tableau solve: T = s2 I + A Pcc is formed by the kernel itself
+    if (h->solve7_variant == 4)
+        hipLaunchKernelGGL((solve7_kernel<3, 16, 12>), gb, dim3(768), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->Tbuf, h->W, xout, h->slab_bytes);
+    else if (h->solve5_variant == 1)
+        hipLaunchKernelGGL((solve6_kernel<1, 8, 8>), gb, dim3(512), h->solve5_lds, h->stream, d, h->meta, n, h->Tbuf, Ab, xin, Pc, h->W, xout, h->slab_bytes);
     else if (h->solve5_variant == 2)
-        hipLaunchKernelGGL((solve6_kernel<2, 12, 8>), dim3(1, 1, h->batch), dim3(512), h->solve5_lds, h->stream, d, h->meta, n, h->Tbuf, Ab, xin, Pc, h->W, xout, h->slab_bytes);
+        hipLaunchKernelGGL((solve6_kernel<2, 12, 8>), gb, dim3(512), h->solve5_lds, h->stream, d, h->meta, n, h->Tbuf, Ab, xin, Pc, h->W, xout, h->slab_bytes);
     else if (h->solve5_variant == 3)
-        hipLaunchKernelGGL((solve6_kernel<2, 16, 8>), dim3(1, 1, h->batch), dim3(512), h->solve5_lds, h->stream, d, h->meta, n, h->Tbuf, Ab, xin, Pc, h->W, xout, h->slab_bytes);
+        hipLaunchKernelGGL((solve6_kernel<2, 16, 8>), gb, dim3(512), h->solve5_lds, h->stream, d, h->meta, n, h->Tbuf, Ab, xin, Pc, h->W, xout, h->slab_bytes);
 }
 
 // U = Pc W, G = U A  (K H = [0 | G]);  Joseph form (Updater.cc:615-619): P1 = (I-KH) P,  P+ = sym(P1 - P1c G^T + s2 G U^T)
@@ -1035,19 +968,17 @@ static void launch_ug_final(rvio_hip* h, int n, const double* Ab, double* Pn, bo
     const size_t bs = h->slab_bytes;
     double* Pc = h->P[h->cur];
     const int nt = (dd + 15) / 16, npair = nt * (nt + 1) / 2;
-    static const bool no_ugl = ab_env("RVIO_NO_UGL") != nullptr;   // A/B timing
-    static const bool no_jl = ab_env("RVIO_NO_JOSEPH_LDS") != nullptr;   // A/B timing
     if (h->jb_lds && ug && fin) {   // batch handle, 6n <= 60: P -> P+ in one kernel (U, G, P1 never leave the CU)
         hipLaunchKernelGGL(joseph_batch_kernel, dim3(1, 1, B), dim3(JB_THREADS), h->jb_lds, h->stream, d, n, Pc, h->W, Ab, Pn, bs);
-    } else if (B == 1 && c6 <= 60 && ug && fin && !no_jl) {   // one instance, short window: both stages in ONE launch, a workgroup per tile pair of P+
+    } else if (B == 1 && c6 <= 60 && ug && fin) {   // one instance, short window: both stages in ONE launch, a workgroup per tile pair of P+
         const bool dxr = h->dx_pending;   // the all-LDS solve left dx = Pc y and the state injection to role workgroups of this launch
         h->dx_pending = false;
         hipLaunchKernelGGL(joseph_lds_kernel, dim3(npair + (dxr ? (dd + 23) / 24 : 0)), dim3(256), JL_LDS_DOUBLES * sizeof(double), h->stream, d, n, Pc, h->W, Ab, Pn,
                            h->meta, (const double*)h->x[h->cur], h->x[h->cur ^ 1], dxr ? (const double*)h->S9scr : (const double*)nullptr, npair, h->solve9_nt);
-    } else if (B == 1 && c6 <= 64 && !no_ugl) {   // one instance, short window: every operand of a workgroup staged in LDS with one batch of loads
+    } else if (B == 1 && c6 <= 64) {   // ... one stage at a time (rvio_hip_debug_time_kernel): every operand of a workgroup staged in LDS with one batch of loads
         if (ug) hipLaunchKernelGGL(ug_lds_kernel, dim3(nt), dim3(256), UGL_LDS_DOUBLES * sizeof(double), h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1);
         if (fin) hipLaunchKernelGGL(final_lds_kernel, dim3((npair + 3) / 4), dim3(256), FNL_LDS_DOUBLES * sizeof(double), h->stream, d, n, h->Pt1, h->G, h->U, Pn);
-    } else if (B == 1 && !ab_env("RVIO_NO_UG_TILE")) {   // one instance, 6n > 64: one wave per output tile, the chip is this instance's alone
+    } else if (B == 1) {   // one instance, 6n > 64: one wave per output tile, the chip is this instance's alone
         const int c6t = (c6 + 15) / 16;
         if (ug) {
             const bool dxr = h->dx_pending;   // the split solve left dx = Pc y and the state injection to role workgroups of this launch
@@ -1059,7 +990,7 @@ static void launch_ug_final(rvio_hip* h, int n, const double* Ab, double* Pn, bo
             hipLaunchKernelGGL(ug_tile_kernel<2>, dim3((nt * nt + 3) / 4), dim3(256), 0, h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1, h->meta, nod, (double*)nullptr, nod, 0);
         }
         if (fin) hipLaunchKernelGGL(final_tile_kernel, dim3(npair), dim3(256), 0, h->stream, d, n, h->Pt1, h->G, h->U, Pn);
-    } else {
+    } else {   // batch handles
         if (ug) hipLaunchKernelGGL(ug_kernel, dim3((dd + 15) / 16, 1, B), dim3(256), h->ug_lds, h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1, bs);
         if (fin) hipLaunchKernelGGL(final_kernel, dim3((npair + 3) / 4, 1, B), dim3(256), 0, h->stream, d, n, h->Pt1, h->G, h->U, Pn, bs);
     }
@@ -1071,6 +1002,19 @@ static void launch_landmarks(rvio_hip* h, int n, const LmOut& out) {
     hipLaunchKernelGGL(landmark_kernel, dim3(1, 1, h->batch), dim3(T), 0, h->stream, h->dc, n, (const double*)h->x[h->cur ^ 1], (const double*)h->x[h->cur],
                        (const int*)h->t.n_feat, (const unsigned char*)h->t.types, (const int*)h->t.len, (const int*)h->acc, (const double*)h->pfinv,
                        h->slab_bytes, h->bin, out);
+}
+// cornerSubPix on the detector's raw corners, for B instances (frame: the instrumented build's stamp)
+static void launch_subpix(rvio_hip* h, const DetDev& q, const uint8_t* img, int stride, size_t src_bs, unsigned B, int frame, hipStream_t st) {
+    const DevCfg& d = h->dc;
+    const size_t bs = h->slab_bytes;
+    if (q.sp_win > 15)        // Tracker.nMinDist >= 32: the summation grid no longer fits LDS whole
+        hipLaunchKernelGGL(subpix_wide_kernel, dim3(d.F, 1, B), dim3(SPG_T), subpix_wide_lds(q.sp_win), st, img, stride, q, src_bs, bs);
+    else if (q.sp_win != SP_WIN)   // a cornerSubPix window other than the stock 7: the plain form
+        hipLaunchKernelGGL(subpix_generic_kernel, dim3(d.F, 1, B), dim3(SPG_T), 0, st, img, stride, q, src_bs, bs);
+    else if (h->wide_px)
+        hipLaunchKernelGGL(subpix_kernel16, dim3((d.F + 3) / 4, 1, B), dim3(64), 0, st, img, stride, q, src_bs, bs);
+    else
+        hipLaunchKernelGGL(subpix_kernel, dim3(d.F, 1, B), dim3(SP_T), 0, st, img, stride, q, src_bs, bs, frame);
 }
 // the cloud buffers of every instance in one allocation (count | feat[Fu] | p_r[Fu][3] | p_w[Fu][3], 256-byte aligned parts)
 static int lm_alloc(rvio_hip* h, LmOut* out) {
@@ -1103,9 +1047,8 @@ static int update_global_dev(rvio_hip* h, const double* d_blocks, int world, boo
         Ab = h->Ab;
     }
     const int tt = (c6 + 31) / 32;
-    static const bool no_gtl = ab_env("RVIO_NO_GEMM_T_LDS") != nullptr;   // A/B timing
     if (!h->solve7_variant && !h->solve9_nt) {
-        if (B >= 128 && d.ldh - 1 <= 64 && !no_gtl)
+        if (B >= 128 && d.ldh - 1 <= 64)
             hipLaunchKernelGGL(gemm_T_lds_kernel, dim3(1, 1, B), dim3(256), (size_t)2 * c6 * (c6 + 1) * sizeof(double), h->stream, d, n, Ab, Pc, h->Tbuf, bs);
         else
             hipLaunchKernelGGL(gemm_T_kernel, dim3(tt, tt, B), dim3(256), 0, h->stream, d, n, Ab, Pc, h->Tbuf, bs);
@@ -1215,8 +1158,7 @@ static int augment_compose_dev(rvio_hip* h, int do_augment) {
     const int c = h->cur, o = c ^ 1;
     // one stream: width (one entry per thread, ~29 workgroups); a batch: every workgroup builds Vk first (a serial section of one thread),
     // so few fat workgroups per instance (the chip is full anyway)
-    static const int aug_wgs = ab_env("RVIO_AUG_WGS") ? atoi(ab_env("RVIO_AUG_WGS")) : 4;   // A/B timing
-    const int cg = 1 + (h->batch >= 128 ? std::max(1, aug_wgs) : std::max(1, std::min(64, (d.dmax * d.dmax + 255) / 256)));
+    const int cg = 1 + (h->batch >= 128 ? 4 : std::max(1, std::min(64, (d.dmax * d.dmax + 255) / 256)));
     unsigned long long* done = nullptr;
     if (h->batch == 1) { done = &h->stage_sync->aug; h->stage_tgt.aug += (unsigned long long)cg; }
     if (h->chol_async) { HIPCHK(h, hipStreamWaitEvent(h->stream, h->evL, 0)); h->chol_async = false; }   // (a frame without an update: its factor was never consumed)
@@ -1229,8 +1171,7 @@ static int augment_compose_dev(rvio_hip* h, int do_augment) {
     // Long windows (6n > 96, solve in its split form): Pcc = L L^T of the NEXT update is known from here on — propagation leaves the clone block
     // alone — so the factor starts now on a stream of its own and runs beside propagate, the wait for the tracker and the per-feature stage; the
     // solve's first product waits for it (launch_solve).  ~35 us at 6n = 120, ~95 us at 6n = 180 off the filter chain.
-    static const bool no_async = ab_env("RVIO_S9_NO_ASYNC") != nullptr;   // A/B timing
-    if (h->solve9_nt >= 8 && h->stream_l && !no_async && !profiler_serialises() && h->n_clones_host >= 1) {
+    if (h->solve9_nt >= 8 && h->stream_l && !profiler_serialises() && h->n_clones_host >= 1) {
         HIPCHK(h, hipEventRecord(h->evA, h->stream));
         HIPCHK(h, hipStreamWaitEvent(h->stream_l, h->evA, 0));
         if (h->solve9_nt == 8) hipLaunchKernelGGL((solve9_chol_kernel<2, 4>), dim3(1), dim3(1024), 0, h->stream_l, d, h->n_clones_host, h->P[h->cur], h->S9scr);
@@ -1261,11 +1202,7 @@ static int detector_alloc_set(rvio_hip* h, DetDev& q) {   // the scratch of ONE 
     q.W = d.W; q.H = d.H; q.F = d.F; q.min_dist = h->cfg.min_dist; q.quality = (double)h->cfg.qual_lvl;
     q.max_cells = ((d.W + cell1 - 1) / cell1) * ((d.H + cell1 - 1) / cell1);
     q.first = h->t.first;
-#ifdef RVIO_DBG_CLOCKS
-    DALLOC(h, q.eig, npx);   // the two-pass A/B form (RVIO_DET_TWO_PASS) sends the map through HBM
-#else
     q.eig = nullptr;   // (the pipeline keeps the min-eigenvalue map in LDS; rvio_hip_get_corners(eig) allocates ONE map per handle on first use)
-#endif
     DALLOC(h, q.maxkey, 1); DALLOC(h, q.counters, 4); DALLOC(h, q.cell_cnt, (size_t)q.max_cells);
     DALLOC(h, q.cell_ent, (size_t)(d.W + cell2) * (d.H + cell2)); DALLOC(h, q.cell_ci, (size_t)(d.W + cell2) * (d.H + cell2));
     q.n_cap = (int)std::min(npx, (size_t)16384);
@@ -1329,7 +1266,7 @@ static DetDev det_view(const rvio_hip* h) {
 // the stream CLAHE and the detector of the call in progress run on: in run-ahead mode the image chains of consecutive frames
 // alternate between two streams (each with its own detector scratch and CLAHE LUTs), so that two of them are in flight — the chain is
 // ~150 us long, the longest of the frame, and with one stream it WAS the frame period
-static hipStream_t image_stream_of(const rvio_hip* h, int ic) { return ic == 0 ? h->stream_t : (ic == 1 ? h->stream_c : h->stream_e); }
+static hipStream_t image_stream_of(const rvio_hip* h, int ic) { return ic == 0 ? h->stream_t : h->stream_c; }
 static hipStream_t image_stream(const rvio_hip* h) { return h->runahead ? image_stream_of(h, h->ic) : h->ts; }
 static int detect_dev(rvio_hip* h, const uint8_t* img, int stride, size_t src_bs, hipEvent_t first_flag_ready) {
     const DevCfg& d = h->dc;
@@ -1338,43 +1275,23 @@ static int detect_dev(rvio_hip* h, const uint8_t* img, int stride, size_t src_bs
     const DetDev q = det_view(h);
     const hipStream_t ds = image_stream(h);
     h->det_set_last = h->runahead ? h->ic : 0;
-    static const bool two_pass = ab_env("RVIO_DET_TWO_PASS") != nullptr;   // A/B timing
-    if (h->pyr_signal && (h->wide_px || two_pass)) { hipLaunchKernelGGL(stage_signal_kernel, dim3(1), dim3(64), 0, ds, h->pyr_signal); h->pyr_signal = nullptr; }   // (forms without the folded signal)
-    if (h->wide_px && !two_pass) {
-        // batch handles of >= 8 instances: the fused pass in its throughput form (one wave per strip, rows walked with the state in registers)
+    if (h->wide_px) {
+        // batch handles of >= 8 instances: the fused pass in its throughput form (one wave per strip, rows walked with the state in registers), which has no folded signal
+        if (h->pyr_signal) { hipLaunchKernelGGL(stage_signal_kernel, dim3(1), dim3(64), 0, ds, h->pyr_signal); h->pyr_signal = nullptr; }
         hipLaunchKernelGGL(mineig_nms_strip_kernel, dim3((d.W + DET_SW - 1) / DET_SW, (d.H + DET_SH - 1) / DET_SH, B), dim3(64), 0, ds, img, stride, q, src_bs, bs);
-        if (first_flag_ready && !(kDbgSkip & 2)) HIPCHK(h, hipStreamWaitEvent(ds, first_flag_ready, 0));
-        hipLaunchKernelGGL(nms_threshold_kernel, dim3(16, 1, B), dim3(NMS_T), 0, ds, q, bs);
-    }
-#ifdef RVIO_DBG_CLOCKS
-    else if (two_pass) {   // rounds 1-3: the map through HBM
-        const dim3 g((d.W + DET_TW - 1) / DET_TW, (d.H + DET_TH - 1) / DET_TH, B);
-        hipLaunchKernelGGL(mineig_kernel, g, dim3(DET_T), 0, ds, img, stride, q, src_bs, bs, (int)h->frame_no);
-        if (first_flag_ready && !(kDbgSkip & 2)) HIPCHK(h, hipStreamWaitEvent(ds, first_flag_ready, 0));   // nms reads mbIsTheFirstImage as book-keeping(k-1) left it
-        hipLaunchKernelGGL(nms_kernel, g, dim3(DET_T), 0, ds, q, bs);
-    }
-#endif
-    else {
+    } else {
         // one stream: min-eigenvalue map + strict 3x3 local maxima in one pass (the map stays in LDS), then the image-wide threshold on the provisional list
         hipLaunchKernelGGL(mineig_nms_kernel, dim3((d.W + DET_TW - 1) / DET_TW, (d.H + DET_FH - 1) / DET_FH, B), dim3(DET_T), 0, ds, img, stride, q, src_bs, bs, (int)h->frame_no, h->pyr_signal);
         h->pyr_signal = nullptr;
-        if (first_flag_ready && !(kDbgSkip & 2)) HIPCHK(h, hipStreamWaitEvent(ds, first_flag_ready, 0));   // the threshold pass reads mbIsTheFirstImage (cell size) as book-keeping(k-1) left it
-        hipLaunchKernelGGL(nms_threshold_kernel, dim3(16, 1, B), dim3(NMS_T), 0, ds, q, bs);
     }
+    if (first_flag_ready) HIPCHK(h, hipStreamWaitEvent(ds, first_flag_ready, 0));   // the threshold pass reads mbIsTheFirstImage (cell size) as book-keeping(k-1) left it
+    hipLaunchKernelGGL(nms_threshold_kernel, dim3(16, 1, B), dim3(NMS_T), 0, ds, q, bs);
     // (every workgroup rebuilds the candidate buckets in its LDS before it walks its share of the candidates: 8 of them for the latency of one
     //  stream, fewer for batch handles, whose width comes from the streams)
-    static const int nb_env = ab_env("RVIO_NEIGH_BLOCKS") ? atoi(ab_env("RVIO_NEIGH_BLOCKS")) : 0;   // A/B timing
-    const unsigned neigh_blocks = nb_env > 0 ? (unsigned)nb_env : (h->wide_px ? NEIGH_BLOCKS_WIDE : NEIGH_BLOCKS);
+    const unsigned neigh_blocks = h->wide_px ? NEIGH_BLOCKS_WIDE : NEIGH_BLOCKS;
     hipLaunchKernelGGL(neigh_kernel, dim3(neigh_blocks, 1, B), dim3(NEIGH_T), NEIGH_LDS, ds, q, bs);
     hipLaunchKernelGGL(greedy_kernel, dim3(1, 1, B), dim3(GREEDY_T), GREEDY_LDS, ds, q, bs);
-    if (q.sp_win > 15)        // Tracker.nMinDist >= 32: the summation grid no longer fits LDS whole
-        hipLaunchKernelGGL(subpix_wide_kernel, dim3(d.F, 1, B), dim3(SPG_T), subpix_wide_lds(q.sp_win), ds, img, stride, q, src_bs, bs);
-    else if (q.sp_win != SP_WIN)   // a cornerSubPix window other than the stock 7: the plain form
-        hipLaunchKernelGGL(subpix_generic_kernel, dim3(d.F, 1, B), dim3(SPG_T), 0, ds, img, stride, q, src_bs, bs);
-    else if (h->wide_px)
-        hipLaunchKernelGGL(subpix_kernel16, dim3((d.F + 3) / 4, 1, B), dim3(64), 0, ds, img, stride, q, src_bs, bs);
-    else
-        hipLaunchKernelGGL(subpix_kernel, dim3(d.F, 1, B), dim3(SP_T), 0, ds, img, stride, q, src_bs, bs, (int)h->frame_no);
+    launch_subpix(h, q, img, stride, src_bs, B, (int)h->frame_no, ds);
     HIPCHK(h, hipGetLastError());
     return RVIO_OK;
 }
@@ -1393,18 +1310,13 @@ static int build_pyramid_dev(rvio_hip* h, const uint8_t* d_img, int stride, int 
         PyrDev pv = p;
         const bool own = h->cfg.enable_equalizer != 0;   // d_img is the handle's equalised image: level 0 without a copy
         if (own) { h->pyr[b].img[0] = d_img; pv.img[0] = d_img; }
-#ifdef RVIO_DBG_CLOCKS
-        static const bool pyr_v1 = ab_env("RVIO_PYR_V1") != nullptr;   // A/B timing: the 25-tap gather form
-        if (pyr_v1) hipLaunchKernelGGL(pyramid_kernel_v1, dim3((w3 + 7) / 8, (h3 + 7) / 8, B), dim3(PYR_T), 0, st, d_img, stride, pv, d.levels, own ? 0 : 1, src_bs, bs);
-        else
-#endif
         hipLaunchKernelGGL(pyramid_kernel, dim3((w3 + 7) / 8, (h3 + 7) / 8, B), dim3(PYR_T), 0, st, d_img, stride, pv, d.levels, own ? 0 : 1, src_bs, bs);
     };
     // Run-ahead mode: the image chain of frame k (CLAHE, detector; with the equaliser also the pyramid) rewrites buffers that book-keeping /
     // KLT of earlier frames read — equalised image k % 4, corner list and count k % 3 — so it starts behind book-keeping(k-3), with or
     // without the equaliser (the detector alone rewrites det_xy2[k % 3] / det_nout[k % 3], which bookkeep_b(k-3) reads).
-    if (h->runahead && h->frame_no >= (long)kRaDepth && !(kDbgSkip & 1))
-        HIPCHK(h, hipStreamWaitEvent(image_stream(h), h->evT[(h->frame_no - kRaDepth) & 3], 0));
+    if (h->runahead && h->frame_no >= 3)
+        HIPCHK(h, hipStreamWaitEvent(image_stream(h), h->evT[(h->frame_no - 3) & 3], 0));
     if (h->cfg.enable_equalizer) {   // clahe->apply(im, im), Tracker.cc:198-202
         // The equalised image of frame k doubles as level 0 of frame k's pyramid (no copy), so it lives until the KLT of frame k+1 has
         // matched against it: four buffers in rotation (like the pyramids, and three corner lists).  Slot k % 4 was last read by KLT(k-3)
@@ -1417,8 +1329,7 @@ static int build_pyramid_dev(rvio_hip* h, const uint8_t* d_img, int stride, int 
         uint8_t* lut = h->d_lut2[h->runahead ? h->ic : h->par];
         // (lane-private 16-bit histogram columns, no LDS-atomic conflicts: every handle.  A counter sees the pixels of ONE lane column of the tile,
         // ceil(tw / 64) th of them — 1296 at 1080p —, so 16 bits hold for any image a camera delivers; the 32-bit per-wave form stays as the fall-back)
-        static const bool lut1 = ab_env("RVIO_CLAHE_LUT1") != nullptr;   // A/B timing
-        if (((h->cl_tw + 63) / 64) * h->cl_th <= 65535 && !lut1)
+        if (((h->cl_tw + 63) / 64) * h->cl_th <= 65535)
             if (h->wide_px) {
                 // (eight rows of byte loads in flight per thread instead of four: the histogram of a batch is load-latency bound; 135.5 -> 136.7 k frames/s at 128 streams)
                 hipLaunchKernelGGL((clahe_lut_kernel2<256, 8>), dim3(h->cl_tx * h->cl_ty, 1, B), dim3(256), 0, cs, d_img, d.W, d.H, stride, h->cl_tx, h->cl_tw, h->cl_th,
@@ -1441,14 +1352,13 @@ static int build_pyramid_dev(rvio_hip* h, const uint8_t* d_img, int stride, int 
             // the longest serial chain of the front end — 19 us less of it; the image chain has the slack
             launch_pyramid(cs);
             pyramid_done = true;
-            static const bool no_pyr_poll = ab_env("RVIO_NO_PYR_POLL") != nullptr;   // A/B timing
             // klt_kernel3 polls the chain's counter itself (no barrier packet on the side stream) — on a handle whose four streams own their hardware queues only (the first
             // live handle of the process, make_stream): 200 polling workgroups per frame in front of kernels of OTHER handles on a shared queue timed the eight-handle
             // leg of the bench out (a consumer may only spin where everything it waits for was submitted earlier to queues nobody else feeds)
             // ... and not on a handle that runs the sharded frame over a real collective, nor at long windows (6n > 96: the Cholesky factor's launches share the
             // copy queue): with the forced-sharded cfg E run of the bench two runs in six stalled for the poll's full 30 s (none in six without it) — more busy
             // queues than the command processor keeps resident, and a queue of spinning workgroups in front of the one that would release them
-            if (h->dev_sync && h->private_queues && !h->queues_shared && !h->extra_queues && 6 * h->dc.nmax <= 96 && !h->wide_px && !no_pyr_poll) {
+            if (h->dev_sync && h->private_queues && !h->queues_shared && !h->extra_queues && 6 * h->dc.nmax <= 96 && !h->wide_px) {
                 h->pyr_signal = &h->stage_sync->pyr[h->ic];      // bumped by the detector's first launch on this queue (detect_dev), right behind the pyramid
                 h->stage_tgt.pyr[h->ic]++;
                 h->klt_wait = &h->stage_sync->pyr[h->ic]; h->klt_target = h->stage_tgt.pyr[h->ic];
@@ -1481,10 +1391,7 @@ static int build_pyramid_dev(rvio_hip* h, const uint8_t* d_img, int stride, int 
         // corners of frame k ready (the refill half of book-keeping on the side stream waits for it): a one-workgroup signal behind
         // cornerSubPix that book-keeping polls, or a stream-level event
         // (one counter per image chain: each has ONE producer queue, so "count >= the frames this chain has been handed" means THIS frame's corners)
-        // (instrumented build, RVIO_DBG_ONE_CORNERS: round 3's single counter for both chains — what tests/test_gpu_flatout.py was measured against)
-        static const bool one_corners = ab_env("RVIO_DBG_ONE_CORNERS") != nullptr;
-        const int cix = one_corners ? 0 : h->ic;
-        if (h->dev_sync) { hipLaunchKernelGGL(stage_signal_kernel, dim3(1), dim3(64), 0, image_stream(h), &h->stage_sync->corners[cix]); h->stage_tgt.corners[cix]++; }
+        if (h->dev_sync) { hipLaunchKernelGGL(stage_signal_kernel, dim3(1), dim3(64), 0, image_stream(h), &h->stage_sync->corners[h->ic]); h->stage_tgt.corners[h->ic]++; }
         else if (h->runahead) HIPCHK(h, hipEventRecord(h->evD1, image_stream(h)));
     }
     if (!pyramid_done) launch_pyramid(h->side);
@@ -1497,8 +1404,7 @@ static int post_klt_dev(rvio_hip* h, const rvio_imu* d_imu, int m, const float* 
     const size_t bs = h->slab_bytes;
     const unsigned B = (unsigned)h->batch;
     // run-ahead mode: RANSAC rides in the launch of book-keeping's hand-over half (both one workgroup, back to back on the side stream)
-    static const bool no_ra_fuse = ab_env("RVIO_NO_FUSED_RANSAC") != nullptr;
-    const bool fused = h->use_det && h->runahead && !no_ra_fuse;
+    const bool fused = h->use_det && h->runahead;
     if (!fused)
     hipLaunchKernelGGL(ransac_kernel, dim3(1, 1, B), dim3(256), (size_t)8 * h->dc.F + 16, h->side, h->dc, h->t.n_pts, h->t.tracked, h->t.un1, h->t.un2,
                        h->t.status, d_imu, m, h->rng, h->d_info, bs, h->imu_bs);
@@ -1510,31 +1416,26 @@ static int post_klt_dev(rvio_hip* h, const rvio_imu* d_imu, int m, const float* 
         const float* xy = h->det_xy2[h->dslot];
         const int* nout = h->det_nout + h->dslot;
         if (h->runahead) {   // book-keeping on the side stream, behind RANSAC: the hand-over half once filter(k-2) has let go of the tables, the refill half once the corners are there
-            if (h->book_wait && !(kDbgSkip & 4)) HIPCHK(h, hipStreamWaitEvent(h->side, h->book_wait, 0));
+            if (h->book_wait) HIPCHK(h, hipStreamWaitEvent(h->side, h->book_wait, 0));
             h->book_wait = nullptr;
-            if (h->book_dev && !(kDbgSkip & 4)) { done = &h->stage_sync->aug; done_target = h->book_target; }
+            if (h->book_dev) { done = &h->stage_sync->aug; done_target = h->book_target; }
             h->book_dev = false;
             h->tail = h->side;
             unsigned long long* hand = nullptr;
             if (h->dev_sync) { hand = &h->stage_sync->handover; h->stage_tgt.handover++; }
             // one stream, device-side counters: RANSAC and both halves of book-keeping are ONE launch (the refill half polls the detector's counter inside it)
-            static const bool no_book_fuse = ab_env("RVIO_NO_FUSED_BOOK") != nullptr;   // A/B timing
-            if (fused && h->dev_sync && !no_book_fuse && h->book_fused) {
-                const int cix = ab_env("RVIO_DBG_ONE_CORNERS") ? 0 : h->ic;
+            if (h->dev_sync && h->book_fused) {
                 h->gate_pending = true; h->gate_target = h->stage_tgt.handover;
                 hipLaunchKernelGGL(ransac_book_kernel, dim3(1, 1, B), dim3(64 * h->book_waves), h->book_lds, h->tail, h->dc, h->t, d_imu, m, h->rng, bs, h->imu_bs,
-                                   done, done_target, h->meta, hand, xy, nout, &h->stage_sync->corners[cix], h->stage_tgt.corners[cix]);
+                                   done, done_target, h->meta, hand, xy, nout, &h->stage_sync->corners[h->ic], h->stage_tgt.corners[h->ic]);
                 HIPCHK(h, hipGetLastError());
                 return RVIO_OK;
             }
-            if (fused)
-                hipLaunchKernelGGL(ransac_book_a_kernel, dim3(1, 1, B), dim3(256), (size_t)8 * h->dc.F + 16, h->tail, h->dc, h->t, d_imu, m, h->rng, bs, h->imu_bs,
-                                   done, done_target, h->meta, hand);
-            else
-            hipLaunchKernelGGL(bookkeep_a_kernel, dim3(1, 1, B), dim3(256), 0, h->tail, h->dc, h->t, bs, done, done_target, h->meta, hand);
+            hipLaunchKernelGGL(ransac_book_a_kernel, dim3(1, 1, B), dim3(256), (size_t)8 * h->dc.F + 16, h->tail, h->dc, h->t, d_imu, m, h->rng, bs, h->imu_bs,
+                               done, done_target, h->meta, hand);
             // the Updater's input is complete: the filter of this frame waits for THIS — the gate kernel on the filter stream polls the
             // counter the launch above bumps, and the refill half below polls the detector's; or two stream-level events
-            if (h->dev_sync) { h->gate_pending = true; h->gate_target = h->stage_tgt.handover; const int cix = ab_env("RVIO_DBG_ONE_CORNERS") ? 0 : h->ic; corners = &h->stage_sync->corners[cix]; corners_target = h->stage_tgt.corners[cix]; }
+            if (h->dev_sync) { h->gate_pending = true; h->gate_target = h->stage_tgt.handover; corners = &h->stage_sync->corners[h->ic]; corners_target = h->stage_tgt.corners[h->ic]; }
             else {
                 HIPCHK(h, hipEventRecord(h->evH[h->frame_no & 3], h->tail));
                 h->handover_evt = true;
@@ -1561,23 +1462,17 @@ static int track_dev_impl(rvio_hip* h, const uint8_t* d_img, int stride, const r
     int rc;
     h->use_det = (d_cand == nullptr);   // no corner list from the caller: run FeatureDetector::DetectWithSubPix on the device
     if (h->use_det && (rc = detector_init(h)) != RVIO_OK) return rc;
-    const bool piped_call = h->ts == h->stream_t && !h->one_stream;
+    const bool piped_call = h->ts == h->stream_t;
     h->par = piped_call ? (int)(h->frame_no & 1) : 0;
-    static const bool no_runahead = getenv("RVIO_NO_RUNAHEAD") != nullptr;   // A/B timing only
-    h->runahead = piped_call && h->use_det && !no_runahead;
-    // A/B timing: stream-level events instead.  Also when a counter-collecting profiler is attached (rocprofv3 --pmc exports
-    // ROCPROF_COUNTER_COLLECTION): it serialises kernels across queues, and a kernel that polls a counter another queue's kernel bumps would sit
-    // there until its 30 s time-out.
-    static const bool no_devsync = (paranoid_bits() & PAR_NO_DEVPOLL) || ab_env("RVIO_NO_DEVFLAG") != nullptr || ab_env("RVIO_NO_DEVSYNC") != nullptr || profiler_serialises();
-    h->dev_sync = h->runahead && h->batch == 1 && !no_devsync;
+    h->runahead = piped_call && h->use_det && !no_runahead();
+    h->dev_sync = h->runahead && h->batch == 1 && !no_device_polls();
     h->gate_pending = false;
     h->dslot = h->runahead ? (int)(h->frame_no % 3) : h->par;
     h->ic = h->runahead ? (int)(h->frame_no % h->n_ic) : h->par;
     const int nb = (h->pyr_cur + 1) % 4;   // pyramid of the new image; pyr_cur holds mLastImage's (slot nb was last read by KLT(k-3))
     rc = build_pyramid_dev(h, d_img, stride, nb);
     if (rc != RVIO_OK) return rc;
-    static const bool klt3 = ab_env("RVIO_KLT3") != nullptr;   // A/B timing
-    if (h->wide_px && !klt3)    // batch handles of >= 8 instances: the throughput form, four features per wave
+    if (h->wide_px)    // batch handles of >= 8 instances: the throughput form, four features per wave
         hipLaunchKernelGGL(klt_kernel16, dim3((h->dc.F + 3) / 4, 1, h->batch), dim3(64), 0, h->side, h->pyr[h->pyr_cur], h->pyr[nb], h->dc.levels, h->t.n_pts, h->t.feats,
                            h->t.tracked, h->t.status, h->slab_bytes);
     else
@@ -1723,8 +1618,7 @@ int rvio_hip_frame_tracks_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride
     // A filter-only batch: PreIntegrator::propagate (one latency-bound workgroup per instance, two per CU) runs on the handle's second stream
     // BESIDE the per-feature stage of the update — U1-U5 and the share reduction read only the clone states and P[24:,24:], which propagation does
     // not touch (the reason feat_prop_kernel may fuse them for one stream) — and joins in front of the solve, which needs the propagated rows.
-    static const bool no_overlap = ab_env("RVIO_NO_PROP_OVERLAP") != nullptr;   // A/B timing
-    const bool overlap = upd && h->batch > 1 && !h->front_end && !h->one_stream && !no_overlap;
+    const bool overlap = upd && h->batch > 1 && !h->front_end;
     int rc;
     if (overlap) {
         HIPCHK(h, hipEventRecord(h->evD0, h->stream));
@@ -1758,8 +1652,7 @@ static int frame_dev_impl(rvio_hip* h, const uint8_t* d_img, int stride, const r
     const int b = (int)(h->frame_no & 1);                   // parity: the staging of rvio_hip_frame
     const int hb = (int)(h->frame_no % rvio_hip::kHand);    // hand-over table of this frame
     h->t.n_feat = h->tout[hb].n_feat; h->t.types = h->tout[hb].types; h->t.len = h->tout[hb].len; h->t.meas = h->tout[hb].meas;
-    static const bool no_ra = getenv("RVIO_NO_RUNAHEAD") != nullptr;
-    const bool ra = !d_cand && !h->one_stream && !no_ra;   // run-ahead mode (track_dev_impl): book-keeping runs on the side stream
+    const bool ra = !d_cand && !no_runahead();   // run-ahead mode (track_dev_impl): book-keeping runs on the side stream
     if (h->frame_no >= rvio_hip::kHand) {   // the filter of frame k - kHand has consumed this hand-over buffer: only the stream that runs book-keeping has to know.
         // (In run-ahead mode the image chains — CLAHE, detector — never touch the hand-over: making them wait here tied image(k) to
         // filter(k-2) and with it the frame period to image chain + filter chain over two frames.)
@@ -1772,7 +1665,11 @@ static int frame_dev_impl(rvio_hip* h, const uint8_t* d_img, int stride, const r
     } else if (!h->piped) HIPCHK(h, hipStreamSynchronize(h->stream));   // first pipelined frame: everything enqueued so far is done
     h->piped = true;
     if (m < 0) return RVIO_ERR_INVALID;
-    static const bool dbg_host = ab_env("RVIO_DBG_HOST") != nullptr;
+#ifdef RVIO_DBG_CLOCKS
+    static const bool dbg_host = getenv("RVIO_DBG_HOST") != nullptr;   // host-side enqueue times on stderr (selects nothing)
+#else
+    constexpr bool dbg_host = false;
+#endif
     static double acc[5] = {0, 0, 0, 0, 0}; static long nacc = 0;
     auto now = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = dbg_host ? now() : 0;
@@ -1796,9 +1693,9 @@ static int frame_dev_impl(rvio_hip* h, const uint8_t* d_img, int stride, const r
     HIPCHK(h, hipEventRecord(h->evT[h->frame_no & 3], h->tail));      // behind book-keeping, on the stream that ran it
     // the filter needs the hand-over, not the refill: in run-ahead mode it waits for the first half of book-keeping only
     if (h->gate_pending) {
-        if (!(kDbgSkip & 16)) hipLaunchKernelGGL(stage_gate_kernel, dim3(1), dim3(64), 0, h->stream, &h->stage_sync->handover, h->gate_target, h->meta, h->t.n_feat, (int)h->frame_no);
+        hipLaunchKernelGGL(stage_gate_kernel, dim3(1), dim3(64), 0, h->stream, &h->stage_sync->handover, h->gate_target, h->meta, h->t.n_feat, (int)h->frame_no);
         h->gate_pending = false;
-    } else if (!(kDbgSkip & 16)) HIPCHK(h, hipStreamWaitEvent(h->stream, h->handover_evt ? h->evH[h->frame_no & 3] : h->evT[h->frame_no & 3], 0));
+    } else HIPCHK(h, hipStreamWaitEvent(h->stream, h->handover_evt ? h->evH[h->frame_no & 3] : h->evT[h->frame_no & 3], 0));
     const double t3 = dbg_host ? now() : 0;
     if (begin_only) {   // the caller sequences update / augment itself, then rvio_hip_frame_end
         h->in_frame = true;
@@ -1812,9 +1709,8 @@ static int frame_dev_impl(rvio_hip* h, const uint8_t* d_img, int stride, const r
     const double t4 = dbg_host ? now() : 0;
     // the filter of this frame is finished when ... single instance in run-ahead mode: its last kernel has bumped the device-side counter
     // (book-keeping of frame k+2 polls it); otherwise an event behind it
-    static const bool no_devflag = (paranoid_bits() & PAR_NO_DEVPOLL) || ab_env("RVIO_NO_DEVFLAG") != nullptr || profiler_serialises();
-    if (ra && h->batch == 1 && !no_devflag) { h->fin_mode[hb] = 1; h->fin_target[hb] = h->stage_tgt.aug; }
-    else { if (!(kDbgSkip & 8)) HIPCHK(h, hipEventRecord(h->evF[hb], h->stream)); h->fin_mode[hb] = 0; }
+    if (ra && h->batch == 1 && !no_device_polls()) { h->fin_mode[hb] = 1; h->fin_target[hb] = h->stage_tgt.aug; }
+    else { HIPCHK(h, hipEventRecord(h->evF[hb], h->stream)); h->fin_mode[hb] = 0; }
     if (dbg_host) {
         const double t5 = now();
         acc[0] += t1 - t0; acc[1] += t2 - t1; acc[2] += t3 - t2; acc[3] += t4 - t3; acc[4] += t5 - t4;
@@ -1958,8 +1854,7 @@ int rvio_hip_frame(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* 
     else for (int y = 0; y < h->dc.H; ++y) std::memcpy(pp + (size_t)y * h->dc.W, img + (size_t)y * stride, (size_t)h->dc.W);
     if (m > 0) std::memcpy(pp + h->pin_imu, imu, sizeof(rvio_imu) * m);
     if (nc > 0) std::memcpy(pp + pin_cand, cand_xy, sizeof(float) * 2 * nc);
-    static const bool no_runahead = getenv("RVIO_NO_RUNAHEAD") != nullptr;
-    const bool ra = !cand_xy && !h->one_stream && !no_runahead;
+    const bool ra = !cand_xy && !no_runahead();
     int imu_slot = b;
     if (ra) {
         // run-ahead mode.  The IMU batch goes to the SIDE stream (RANSAC runs there; propagate on the filter stream waits for evIn): it
@@ -1993,7 +1888,6 @@ int rvio_hip_frame(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* 
         HIPCHK(h, hipStreamSynchronize(h->stream_d));
         HIPCHK(h, hipStreamSynchronize(h->stream_t));
         if (h->stream_c) HIPCHK(h, hipStreamSynchronize(h->stream_c));
-        if (h->stream_e) HIPCHK(h, hipStreamSynchronize(h->stream_e));
     }
     return frame_dev_impl(h, h->hb_img[b], h->dc.W, h->hb_imu[imu_slot], m, cand_xy ? h->hb_cand[b] : nullptr, nc, true);
 }
@@ -2137,17 +2031,14 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
         if (which == 8) {
             // feat_prop_kernel exactly as the pipelined frame launches it: the per-feature workgroups of the last hand-over table + PreIntegrator::propagate on the
             // IMU batch of the last frame (the caller's device buffer must still be alive) + at 6n <= 96 the Cholesky role
-            const bool chol = h->solve9_nt && h->solve9_nt <= 6;
-            hipLaunchKernelGGL(feat_prop_kernel, dim3(d.Fu + 1 + (chol ? 1 : 0)), dim3(256), h->fprop_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
-                               h->t.n_feat, h->t.types, h->t.len, h->t.meas, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv, h->tm_global, h->bin,
-                               h->meta, h->time_imu, h->time_m, chol ? h->S9scr : (double*)nullptr, h->solve9_nt, 0, 1, h->lit_rows);
+            launch_feat_prop(h, n, h->time_imu, h->time_m, 0, 1);
         } else if (which == 9) {   // the detector's selection kernel (one workgroup: priority-ordered maximal independent set) on the candidates of the last detector call
             if (h->batch > 1 || !h->det_ready) return RVIO_ERR_UNSUPPORTED;
             const DetDev q = [&] { DetDev v = h->dets[h->det_set_last]; v.xy = h->det_xy2[h->dslot]; v.n_out = h->det_nout + h->dslot; return v; }();
             hipLaunchKernelGGL(greedy_kernel, dim3(1, 1, 1), dim3(GREEDY_T), GREEDY_LDS, h->stream, q, h->slab_bytes);
         } else
         if (which == 0) {
-            h->chol_ready = h->solve9_nt && (h->solve9_nt <= 6 || h->stream_l) && !ab_env("RVIO_S9_FULL");   // (time what the chain sees: the Cholesky factor rides in the per-feature launch / runs on its own queue; the slab holds the factor of the last update)
+            h->chol_ready = h->solve9_nt && (h->solve9_nt <= 6 || h->stream_l);   // (time what the chain sees: the Cholesky factor rides in the per-feature launch / runs on its own queue; the slab holds the factor of the last update)
             launch_solve(h, n, h->block, /*defer_dx=*/true);   // as the frame's update launches it: dx = Pc y and the state injection are roles of the Joseph launch behind it
             h->dx_pending = false;
         } else if (which == 1) {
@@ -2158,19 +2049,11 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
             hipLaunchKernelGGL(klt_kernel3, dim3(d.F), dim3(64), 0, h->stream, h->pyr[h->pyr_cur], h->pyr[(h->pyr_cur + 3) % 4], d.levels, h->t.n_pts, h->t.feats,
                                h->t.tracked, h->t.status, (size_t)0, (const unsigned long long*)nullptr, 0ull, h->meta);
         } else if (which == 2) {
-            if (h->batch == 1)
-            hipLaunchKernelGGL(feat_build_kernel<16>, dim3(d.Fu, 1, h->batch), dim3(h->feat_threads), h->feat_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
-                               h->t.n_feat, h->t.types, h->t.len, h->t.meas, 0, 1, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv, h->tm_global,
-                               h->slab_bytes, h->bin, h->meta, (const double*)nullptr, (const int*)nullptr, h->lit_rows);
-            else
-            hipLaunchKernelGGL(feat_build_kernel<4>, dim3(d.Fu, 1, h->batch), dim3(h->feat_threads), h->feat_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
-                               h->t.n_feat, h->t.types, h->t.len, h->t.meas, 0, 1, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv, h->tm_global,
-                               h->slab_bytes, h->bin, h->meta, (const double*)h->gpose, (const int*)h->gvalid, h->lit_rows);
+            launch_feat_build(h, n, 0, 1);   // (a batch handle: on the pose chains geom4_kernel left in the last update)
         } else if (which == 3 && h->batch >= 128 && h->gram_batch_lds) {
             launch_gram_batch(h, n);
         } else if (which == 3) {   // reduction of the per-feature shares + rank truncation (reads `partial`, rewrites `block`: idempotent)
-            hipLaunchKernelGGL(gram_reduce_kernel, dim3(std::max(1, std::min(1024, (6 * n * d.ldh + (h->batch == 1 ? 63 : 255)) / (h->batch == 1 ? 64 : 256))), 1, h->batch), dim3(256), h->trunc_lds, h->stream, d, n,
-                               h->partial, h->nrows, h->t.types, h->t.len, h->block, h->gram_cnt, 1, (h->batch == 1) ? 1 : 0, h->slab_bytes, h->bin, lit_args(h, h->trunc_lds));
+            launch_gram_reduce(h, n, true);
         } else if (which == 4 || which == 5) {   // U, G, P1 strips / the Joseph form on the operands of the last update, in the form the handle launches
             launch_ug_final(h, n, h->block, h->P[h->cur ^ 1], which == 4, which == 5);   // (outputs: scratch / the spare covariance buffer, overwritten by the next stage anyway)
         } else if (which == 7) {   // U, G, P1 + the Joseph form as the handle launches them for a whole update (one instance, 6n <= 60: ONE kernel)
@@ -2179,10 +2062,7 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
             if (h->batch > 1 || !h->det_ready) return RVIO_ERR_UNSUPPORTED;
             const DetDev q = [&] { DetDev v = h->dets[h->det_set_last]; v.xy = h->det_xy2[h->dslot]; v.n_out = h->det_nout + h->dslot; return v; }();
             const uint8_t* im = h->pyr[h->pyr_cur].img[0];   // level 0 of the current pyramid = the image the detector saw
-            if (q.sp_win > 15) hipLaunchKernelGGL(subpix_wide_kernel, dim3(d.F, 1, 1), dim3(SPG_T), subpix_wide_lds(q.sp_win), h->stream, im, d.W, q, (size_t)0, h->slab_bytes);
-            else if (q.sp_win != SP_WIN) hipLaunchKernelGGL(subpix_generic_kernel, dim3(d.F, 1, 1), dim3(SPG_T), 0, h->stream, im, d.W, q, (size_t)0, h->slab_bytes);
-            else if (h->wide_px) hipLaunchKernelGGL(subpix_kernel16, dim3((d.F + 3) / 4, 1, 1), dim3(64), 0, h->stream, im, d.W, q, (size_t)0, h->slab_bytes);
-            else hipLaunchKernelGGL(subpix_kernel, dim3(d.F, 1, 1), dim3(SP_T), 0, h->stream, im, d.W, q, (size_t)0, h->slab_bytes, 0);
+            launch_subpix(h, q, im, d.W, (size_t)0, 1u, 0, h->stream);
         } else return RVIO_ERR_INVALID;
     }
     HIPCHK(h, hipEventRecord(e1, h->stream));

@@ -14,8 +14,8 @@
 //   * pivot candidates are 32-bit keys (high word of |value| with the low 8 bits replaced by 255 - row): unsigned max, ties -> smaller
 //     row, magnitudes resolved to 2^-12 relative — the chosen pivot is within 0.025 % of the column maximum, deterministic.
 // solve6_kernel spent ~1900 cycles per column on five dependent LDS round trips behind a barrier; this one spends one, unsynchronised.
-// The prologue forms T on the FP64 matrix cores (the former gemm_T_kernel).  6n <= 64: A and Pcc are staged in LDS with one batch
-// of coalesced loads, the tiles go to LDS and from there into the register layout; longer windows use the T scratch buffer in L2.
+// The prologue forms T on the FP64 matrix cores (the former gemm_T_kernel); the tiles reach the register layout through the T scratch buffer in L2.
+// One instantiation is launched: <3, 16, 12>, batch handles at 126 < 6n <= 192 (plain handles run solve9.hip, shorter batch windows solve6.hip).
 // Result as before: T^-1[k][p_j] = M[p_k][j] / piv_k,  y[k] = M[p_k][b] / piv_k.
 #pragma once
 #include <type_traits>
@@ -34,21 +34,15 @@ __device__ __forceinline__ void s7_for(F&& f) {
 
 #define S7_RING 32     // slots of the publication ring: >= NW + 2 (a wave lags the publisher by less than NW + 1 steps)
 
-// STAGE (6n <= 64 only): T's operands through LDS (one stream: latency); false: T through the scratch buffer in L2 like the longer windows —
-// 11 KB of LDS instead of 112 KB, eight workgroups per CU: the throughput form batch handles use (with RING = 8 publication slots).
-template <int RPL, int CPW, int NW, bool STAGE_ = (RPL == 1), int RING = S7_RING>
+template <int RPL, int CPW, int NW>
 __global__ __launch_bounds__(64 * NW) void solve7_kernel(DevCfg cfg, FilterMeta* __restrict__ meta, int n, const double* __restrict__ Ab,
                                                          const double* __restrict__ x, const double* __restrict__ P, double* __restrict__ Tscr,
                                                          double* __restrict__ Wout, double* __restrict__ x_out, size_t bs) {
     meta = zoff(meta, bs); Ab = zoff(Ab, bs); x = zoff(x, bs); P = zoff(P, bs); Tscr = zoff(Tscr, bs); Wout = zoff(Wout, bs); x_out = zoff(x_out, bs);
+    constexpr int NT = 64 * NW, NR = 64 * RPL, RING = S7_RING;
     static_assert(RPL >= 1 && RPL <= 3, "rows per lane");
     static_assert(CPW % 2 == 0, "a wave owns pairs of columns");
     static_assert(RING >= NW + 2 && (RING & (RING - 1)) == 0, "ring depth");
-    static_assert(!STAGE_ || RPL == 1, "staging needs 6n <= 64");
-    constexpr int NT = 64 * NW, NR = 64 * RPL;
-    constexpr bool STAGE = STAGE_;                      // 6n <= 64: T through LDS
-    constexpr int LS = 65;                              // LDS row stride of the staged 64 x 64 operands
-    extern __shared__ __align__(16) double s7_dyn[];    // STAGE: As | Ps | Ts (3 x 64 x LS) | Pt (24 x 64); As is reused for the dx partial sums
     __shared__ double s_f[RING][2][NR];
     __shared__ int s_p[RING][2], s_flag[RING];
     __shared__ int s_prow[6 * RVIO_MAX_LEN], s_invp[NR];
@@ -72,57 +66,7 @@ __global__ __launch_bounds__(64 * NW) void solve7_kernel(DevCfg cfg, FilterMeta*
     const double s2 = cfg.sigma_im * cfg.sigma_im;
     double mcol[CPW][RPL], mbv[RPL];                    // the tableau: register column cc of this wave, this lane's RPL rows; the right-hand side
     // ---- T = s2 I + A Pcc on the matrix cores: A = Ab (row-major, ld = ldh), B = Pcc = P[24:,24:] (column-major, ld = dmax)
-    if constexpr (STAGE) {
-        double* As = s7_dyn; double* Ps = s7_dyn + 64 * LS; double* Ts = s7_dyn + 2 * 64 * LS; double* Pt = s7_dyn + 3 * 64 * LS;
-        // ONE batch of coalesced loads, all in flight before the first store: As[i][k] = A[i][k], Ps[j][k] = Pcc[k][j] (zero-padded to
-        // 64 x 64), Pt[j][i] = P[i][24 + j] for the 24 IMU rows (dx = Pc y at the end reads Pc from LDS)
-        {
-            constexpr int NB = 64 * 64 / NT, NB2 = (24 * 64 + NT - 1) / NT;
-            double va[NB], vp[NB], vt[NB2];
-#pragma unroll
-            for (int u = 0; u < NB; ++u) {
-                const int e = tid + u * NT, a = e >> 6, k = e & 63;
-                const bool ok = a < c6 && k < c6;
-                va[u] = ok ? Ab[(size_t)a * ldh + k] : 0.0;
-                vp[u] = ok ? P[(size_t)(24 + k) + (size_t)(24 + a) * ld] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < NB2; ++u) {
-                const int e = tid + u * NT, j = e / 24, i = e - j * 24;
-                vt[u] = (e < 24 * 64 && j < c6) ? P[(size_t)i + (size_t)(24 + j) * ld] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < NB; ++u) { const int e = tid + u * NT, a = e >> 6, k = e & 63; As[a * LS + k] = va[u]; Ps[a * LS + k] = vp[u]; }
-#pragma unroll
-            for (int u = 0; u < NB2; ++u) { const int e = tid + u * NT; if (e < 24 * 64) Pt[e] = vt[u]; }
-        }
-        __syncthreads();
-        const int nt = (c6 + 15) / 16, li = lane & 15, lk = lane >> 4;
-        for (int t = wv; t < nt * nt; t += NW) {
-            const int i0 = (t / nt) * 16, j0 = (t % nt) * 16;
-            const double* ap = As + (i0 + li) * LS;
-            const double* bp = Ps + (j0 + li) * LS;
-            s7_d4 acc = {0, 0, 0, 0};
-            double av[16], bv[16];                      // every operand of the tile in flight before the first MFMA
-#pragma unroll
-            for (int u = 0; u < 16; ++u) { av[u] = ap[4 * u + lk]; bv[u] = bp[4 * u + lk]; }
-#pragma unroll
-            for (int u = 0; u < 16; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = i0 + lk + 4 * r, col = j0 + li;
-                Ts[row * LS + col] = acc[r] + ((row == col && row < c6) ? s2 : 0.0);
-            }
-        }
-        __syncthreads();
-        DBG_T(57);
-#pragma unroll
-        for (int cc = 0; cc < CPW; ++cc) {
-            const int j = 2 * ((cc >> 1) * NW + wv) + (cc & 1);
-            mcol[cc][0] = (lane < c6 && j < c6) ? Ts[lane * LS + j] : 0.0;
-        }
-        mbv[0] = (lane < c6) ? Ab[(size_t)lane * ldh + c6] : 0.0;
-    } else {
+    {
         const int nt = (c6 + 15) / 16, li = lane & 15, lk = lane >> 4;
         for (int t = wv; t < nt * nt; t += NW) {
             const int i0 = (t / nt) * 16, j0 = (t % nt) * 16;
@@ -312,18 +256,13 @@ __global__ __launch_bounds__(64 * NW) void solve7_kernel(DevCfg cfg, FilterMeta*
     DBG_T(61);
     // dx = K r = Pc y   (Updater.cc:544): NT / d threads per row, each a contiguous share of the columns; partial sums added in a fixed order
     {
-        double* part = STAGE ? s7_dyn : &s_f[0][0][0];         // (As is idle now; the ring is idle too: 2 NR RING >= 1024 doubles >= np d)
+        double* part = &s_f[0][0][0];         // (the ring is idle now: 2 NR RING >= 1024 doubles >= np d)
         const int np = max(1, min(4, NT / d)), share = (c6 + np - 1) / np;
         const int pt = tid / d, i = tid - pt * d;
         if (pt < np) {
             double acc = 0;
             const int k1 = min(c6, (pt + 1) * share);
-            if constexpr (STAGE) {   // Pc from LDS: rows 0..23 = Pt[k][i], rows 24.. = Pcc[i-24][k] = Ps[k][i-24]
-                const double* src = (i < 24) ? (s7_dyn + 3 * 64 * LS + i) : (s7_dyn + 64 * LS + (i - 24));
-                const int st = (i < 24) ? 24 : LS;
-                for (int k = pt * share; k < k1; ++k) acc += src[k * st] * s_y[k];
-            } else
-                for (int k = pt * share; k < k1; ++k) acc += P[(size_t)i + (size_t)(24 + k) * ld] * s_y[k];
+            for (int k = pt * share; k < k1; ++k) acc += P[(size_t)i + (size_t)(24 + k) * ld] * s_y[k];
             part[pt * d + i] = acc;
         }
         __syncthreads();

@@ -1,10 +1,11 @@
 #!/bin/bash
 # A/B of two builds of the library on the batched legs (same box, alternating):  tools/ab_batch.sh <base.so> [reps]
+set -eo pipefail   # a run that fails or overruns its time limit ends the A/B: nothing more is started on the GPU behind it
 BASE=$1; REPS=${2:-2}
 for rep in $(seq $REPS); do
 for v in base new; do
   if [ $v = base ]; then export RVIO_HIP_LIB=$BASE; else unset RVIO_HIP_LIB; fi
-  python bench.py --steps 20 --warmup 5 --full --no-cpu --no-latency --no-streams --batch 2048 --batch-streams 128 2>/dev/null | python -c "
+  timeout -k 10 600 python bench.py --steps 20 --warmup 5 --full --no-cpu --no-latency --no-streams --batch 2048 --batch-streams 128 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 bf=d['batched_filter']['sizes'][-1]; bs=d['batched_streams']['sizes'][-1]; dl=d.get('batched_filter_at_defined_load',{}).get('sizes',[{}])[-1]

@@ -1,7 +1,7 @@
-"""A/B of two kernel forms on one full-load update: dumps the updated state / covariance so that two runs (e.g. the instrumented build with and without a
-switch such as RVIO_NO_UG_TILE=1) can be compared bit for bit.
+"""A/B of two builds of the library on one full-load update: dumps the updated state / covariance so that two runs (each build selected through
+RVIO_HIP_LIB, e.g. a build with a changed kernel form against the shipping one) can be compared bit for bit.
 
-    RVIO_HIP_LIB=r-vio_amd/librvio_dbg.so [SWITCH=1] python tools/form_ab.py out.npz [A C E]; python tools/form_ab.py --compare a.npz b.npz"""
+    RVIO_HIP_LIB=<build>.so python tools/form_ab.py out.npz [A C E]; python tools/form_ab.py --compare a.npz b.npz"""
 import os
 import sys
 

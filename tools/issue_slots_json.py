@@ -50,4 +50,4 @@ if __name__ == "__main__":
         i = args.index("--streams"); streams = int(args[i + 1]); del args[i:i + 2]
     print(json.dumps(summarise(collect(args, streams), streams,
                                "rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_WAVES -- python bench.py "
-                               "--full --no-cpu --batch '' --no-streams --no-latency --batch-streams %d --steps 20 --warmup 5 (tools/final_measure.sh)" % streams)))
+                               "--full --no-cpu --batch '' --no-streams --no-latency --batch-streams %d --steps 20 --warmup 5" % streams)))

@@ -1,6 +1,6 @@
 """Parity + live time of the solve kernel on a full-load update at the BASELINE windows (cfg B 6n = 60, A 84, C 120, E 180).
 
-    python tools/solve9_probe.py [B A C E]          # RVIO_SOLVE7=1 in the environment selects the register-tableau elimination (solve7.hip)
+    python tools/solve9_probe.py [B A C E]
 
 Per config: the full-load update of SURVEY.md 8(d) (ceil(F/2) features, half type '2') on the device against the oracle (state, covariance),
 then HIP-event timing of the solve kernel alone on those inputs (rvio_hip_debug_time_kernel(0))."""
@@ -35,9 +35,9 @@ for name in names:
     info = h.frame_info()
     dxs, dP = S.state_delta(x, xo), float(np.max(np.abs(P - Po)))
     us = h.time_kernel(0, 50)
-    print("cfg %s 6n=%d: accepted %d/%d rows %d | state delta %.2e  P delta %.2e (|P| %.1e) err=%d | solve kernel %.1f us (form: %s) | oracle update %.0f ms"
+    print("cfg %s 6n=%d: accepted %d/%d rows %d | state delta %.2e  P delta %.2e (|P| %.1e) err=%d | solve kernel %.1f us | oracle update %.0f ms"
           % (name, 6 * (cfg.max_track_len - 1), info["n_feat_accepted"], len(types), info["n_rows"], dxs, dP, float(np.max(np.abs(Po))), info["reserved"][0] if "reserved" in info else -1,
-             us, "solve7" if os.environ.get("RVIO_SOLVE7") else "solve9", 1e3 * t_or), flush=True)
+             us, 1e3 * t_or), flush=True)
     if hasattr(h.L, "rvio_hip_debug_clocks") and os.environ.get("RVIO_HIP_LIB", "").endswith("dbg.so"):
         import ctypes as C
         if not os.environ.get("RVIO_PROBE_CHAIN"):   # default: the stamps of the update's own solve launch (the full kernel); RVIO_PROBE_CHAIN=1: of the launches just timed (the chain's form)
