@@ -5,6 +5,13 @@
 // g++ and sweeps every accepted configuration on the CPU (tests/test_launch_plan.py) — a configuration whose footprint does not fit a CU is
 // found by arithmetic, not by a failed launch.  The one input that is not arithmetic is the STATIC LDS of each kernel, which the compiler
 // decides: create_impl reads it from the loaded code object (hipFuncGetAttributes), the test from the notes of the built library.
+//
+// The plan is what is fixed when the handle is created; the handle keeps it (rvio_hip::plan) and its launch sites read it.  WHICH kernels an update
+// launches also depends on the clone count n, which grows from 0 to max_track_len - 1 while the window fills: update_forms() at the end of this file
+// is the one place that decides it — the Cholesky role, the share reduction, the T product, the solve, where dx = Pc y and the state injection run,
+// and the Joseph stage, each as an enum with its grid and, for every launch with dynamic LDS, the byte count and the LpKernel whose limit
+// (plan.attr) covers it.  The launch functions of rvio_hip.hip switch on what it returns and rvio_hip_debug_time_kernel asks it for the forms the
+// frame would get; the same sweep on the CPU checks every (window, n, batch): roles only where the Joseph launch has them, LDS within the limit.
 #pragma once
 #include <stddef.h>
 
@@ -106,6 +113,7 @@ struct LaunchPlan {
     bool chol_queue = false;     // long windows (96 < 6n <= 192, one instance): the queue a second image chain would take runs the Cholesky factor of the clone block
     size_t trunc_lds = 0, lit_batch_lds = 0, feat_lds = 0, fprop_lds = 0, gram_batch_lds = 0, book_lds = 0, solve5_lds = 0, jb_lds = 0, ug_lds = 0;
     bool lit_state_global = false, tm_global = false, fuse_ok = false;
+    bool lit_ok = false;         // the window admits the literal sweep (literal.h): its row / rotation tables and one raw feature block fit where they are staged
     int book_waves = 4;
     bool book_fused = false;     // RANSAC + both halves of book-keeping in one launch (ransac_book_kernel) fit one CU; else ransac_book_a_kernel + bookkeep_b_kernel
     int solve5_variant = 0, solve7_variant = 0, solve9_nt = 0;
@@ -129,6 +137,7 @@ inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size
     // and the queue that frees runs the Cholesky factor of the clone block beside the filter chain.
     if (batch == 1 && c6m > 96 && c6m <= 192) { p.n_ic = 1; p.chol_queue = true; }
     p.feat_threads = (p.ldh <= 128) ? FEAT_T_SMALL : 256;
+    p.lit_ok = p.ldh <= 190 && nmax + 1 <= 40 && p.rho_max < 254 && lit_slab_doubles(p.ldh, p.rho_max) * sizeof(double) <= 144 * 1024;
     p.trunc_lds = trunc_lds_doubles(max_len) * sizeof(double);
     {   // the literal sweep runs in the workgroup that finishes the reduction (literal.h): its ring / rotation tables always in that launch's LDS, the
         // array's state too when it fits beside gram_reduce_kernel's static LDS — else, and for batch handles (occupancy), in the slab
@@ -223,4 +232,112 @@ inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size
     for (int k = 0; k < LPK_COUNT; ++k)
         if (p.attr[k] && p.attr[k] + statics[k] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
     return p;
+}
+
+// ---------------------------------------------------------------- the forms of ONE update: what depends on the clone count n as well
+enum LpChol {            // who factors the clone block Pcc = L L^T ahead of the solve
+    LPC_NONE,            //   nobody: the solve does it (batch handles; n = 0)
+    LPC_ROLE,            //   6n_max <= 96: one more workgroup of feat_prop_kernel (pipelined frame) or of propagate_chol_kernel<2|3> (staged entry points)
+    LPC_QUEUE            //   6n_max > 96: solve9_chol_kernel on the queue plan.chol_queue frees, started behind augment / compose
+};
+enum LpGram { LPG_REDUCE, LPG_BATCH4, LPG_BATCH6 };   // gram_reduce_kernel, gram_reduce_batch_kernel<4>, <6>
+enum LpTprod { LPT_NONE, LPT_GEMM, LPT_GEMM_LDS };    // no launch (the solve forms T itself), gemm_T_kernel, gemm_T_lds_kernel
+enum LpSolve {
+    LPS_NONE, LPS_SMALL, LPS_S9_1_4, LPS_S9_2_3, LPS_S9_2_3_PRE,   // solve9_small_kernel, solve9_kernel<1, 4>, <2, 3>, <2, 3, true>
+    LPS_SPLIT,                                                      // the split form: solve9_prod / _sweep launches at split_nt = 8 | 12, behind a solve9_chol launch if own_chol
+    LPS_SOLVE7, LPS_SOLVE6_1, LPS_SOLVE6_2, LPS_SOLVE6_3            // solve7_kernel<3, 16, 12>, solve6_kernel<1, 8, 8>, <2, 12, 8>, <2, 16, 8>
+};
+enum LpDx { LPD_INSIDE, LPD_KERNEL, LPD_ROLES };   // dx = Pc y and the state injection: in the solve kernel, a solve9_dx_kernel launch, role workgroups of the Joseph launch
+enum LpJoseph {
+    LPJ_BATCH,       // joseph_batch_kernel                                     grid[0]
+    LPJ_LDS,         // joseph_lds_kernel (has roles)                           grid[0]
+    LPJ_LDS_PAIR,    // ug_lds_kernel, final_lds_kernel                         grid[0], grid[1]
+    LPJ_TILE,        // ug_tile_kernel<0> (has roles), <1>, <2>, final_tile_kernel   grid[0..3]
+    LPJ_STRIPS       // ug_kernel, final_kernel                                 grid[0], grid[1]
+};
+struct LpLds { size_t bytes = 0; int kernel = -1; };   // dynamic LDS of one launch, and the LpKernel whose limit (plan.attr) covers it; kernel < 0: the launch has none
+
+struct UpdateForms {
+    LpChol chol = LPC_NONE;
+    LpGram gram = LPG_REDUCE;
+    int gram_grid = 1;           // workgroups per instance
+    bool gram_finish = false;    // gram_reduce_kernel: the last workgroup turns the block into [A|b] (the batch kernels always do)
+    bool lit_batch = false;      // lit_batch_kernel follows the batch reduction
+    LpLds gram_lds, lit_lds;
+    LpTprod tprod = LPT_NONE;
+    int tprod_grid = 0;          // gemm_T_kernel: tprod_grid x tprod_grid workgroups per instance
+    LpLds tprod_lds;
+    LpSolve solve = LPS_NONE;
+    int split_nt = 0;
+    bool own_chol = false;
+    LpLds solve_lds;
+    LpDx dx = LPD_INSIDE;
+    LpJoseph joseph = LPJ_STRIPS;
+    int grid[4] = {0, 0, 0, 0};  // workgroups per instance of the Joseph stage's launches, WITHOUT the roles
+    int role_wgs = 0;            // dx == LPD_ROLES: workgroups added to the first Joseph launch
+    LpLds ug_lds, fin_lds;       // of the first (or only) Joseph launch, and of final_lds_kernel
+};
+
+// plan: of this handle; batch: its instances; n: clones in the window now; pre: a factor of the clone block is in the slab already (or in flight on
+// the Cholesky queue); whole_update: the solve with both Joseph stages right behind it (else: one separately timed stage); combined: the unsharded
+// update (world == 1, the reduction finishes into [A|b]); lit: the handle has the literal path's buffers.
+// A branch that no handle can reach is kept and marked.
+inline UpdateForms update_forms(const LaunchPlan& p, int batch, int n, bool pre, bool whole_update, bool combined, bool lit) {
+    UpdateForms f;
+    const int B = batch, c6 = 6 * n, dd = 24 + c6, NT = p.solve9_nt;
+    const int nt = (dd + 15) / 16, npair = nt * (nt + 1) / 2;
+    // the Cholesky of the clone block: it does not depend on the measurements, so it runs off the chain
+    if (NT && NT <= 6 && n >= 1) f.chol = LPC_ROLE;
+    else if (NT >= 8 && p.chol_queue && n >= 1) f.chol = LPC_QUEUE;
+    // the share reduction.  A batch handle whose [A|b] fits in LDS (6n <= 90): one workgroup per instance, tiles of 16, 4 x 4 up to 6n = 63, 6 x 6 beyond;
+    // else 64 elements per workgroup for one stream (the shares are remote reads: spread them over many CUs), 256 for a batch (fewer, fuller workgroups)
+    if (B >= 128 && combined && p.gram_batch_lds) {
+        const bool four = p.ldh - 1 <= 63;
+        f.gram = four ? LPG_BATCH4 : LPG_BATCH6;
+        f.gram_lds = {p.gram_batch_lds, four ? LPK_GRAM_BATCH4 : LPK_GRAM_BATCH6};
+        f.lit_batch = lit;
+        if (lit) f.lit_lds = {p.lit_batch_lds, LPK_LIT_BATCH};
+    } else {
+        const int chunk = (B == 1) ? 64 : 256, want = (6 * n * p.ldh + chunk - 1) / chunk;
+        f.gram_grid = want > 1024 ? 1024 : want < 1 ? 1 : want;
+        f.gram_finish = combined;
+        f.gram_lds = {p.trunc_lds, LPK_GRAM_REDUCE};
+    }
+    // T = s2 I + A Pcc as a launch of its own: for the solves that do not form it themselves (solve6: batch handles up to 6n = 126)
+    if (!p.solve7_variant && !NT) {
+        if (B >= 128 && p.ldh - 1 <= 64) { f.tprod = LPT_GEMM_LDS; f.tprod_lds = {(size_t)2 * c6 * (c6 + 1) * sizeof(double), LPK_GEMM_T_LDS}; }
+        else { f.tprod = LPT_GEMM; f.tprod_grid = (c6 + 31) / 32; }
+    }
+    // the solve
+    if (NT == 4) {          // 6n <= 60: in a whole update joseph_lds_kernel follows, whose role workgroups take dx over from the all-LDS solve
+        if (pre) { f.solve = LPS_SMALL; f.solve_lds = {LP_S9SMALL_BYTES, LPK_SOLVE9_SMALL}; f.dx = whole_update ? LPD_ROLES : LPD_INSIDE; }
+        else f.solve = LPS_S9_1_4;
+    } else if (NT == 6) {   // 64 < 6n_max <= 96: roles of joseph_lds_kernel while the window holds <= 10 clones, of ug_tile_kernel<0> from 11 on
+        f.solve = pre ? LPS_S9_2_3_PRE : LPS_S9_2_3;
+        f.dx = whole_update ? LPD_ROLES : LPD_INSIDE;
+    } else if (NT) {        // 6n_max > 96: the split form — the product phases fill the chip, the two factorisations are one workgroup each
+        f.solve = LPS_SPLIT; f.split_nt = NT; f.own_chol = !pre;
+        f.dx = (whole_update && c6 > 64) ? LPD_ROLES : LPD_KERNEL;   // (6n <= 64 while the window fills: the Joseph stage takes its short-window kernels)
+    }
+    else if (p.solve7_variant == 4) f.solve = LPS_SOLVE7;
+    else if (p.solve5_variant == 1) { f.solve = LPS_SOLVE6_1; f.solve_lds = {p.solve5_lds, LPK_SOLVE6_1}; }
+    else if (p.solve5_variant == 2) { f.solve = LPS_SOLVE6_2; f.solve_lds = {p.solve5_lds, LPK_SOLVE6_2}; }
+    else if (p.solve5_variant == 3) { f.solve = LPS_SOLVE6_3; f.solve_lds = {p.solve5_lds, LPK_SOLVE6_3}; }
+    // the Joseph stage: U = Pc W, G = U A, P1 = (I - KH) P, then P+ = sym(P1 - P1c G^T + s2 G U^T)
+    if (p.jb_lds && whole_update) {   // batch handle, 6n <= 60: P -> P+ in one kernel (U, G, P1 never leave the CU)
+        f.joseph = LPJ_BATCH; f.grid[0] = 1; f.ug_lds = {p.jb_lds, LPK_JOSEPH_BATCH};
+    } else if (B == 1 && c6 <= 60 && whole_update) {   // one instance, short window: both stages in ONE launch, a workgroup per tile pair of P+
+        f.joseph = LPJ_LDS; f.grid[0] = npair; f.ug_lds = {LP_JL_BYTES, LPK_JOSEPH_LDS};
+    } else if (B == 1 && c6 <= 64) {   // ... one stage at a time: every operand of a workgroup staged in LDS with one batch of loads.  It has no roles and
+        // needs none: no window has 60 < 6n <= 64, so a whole update never gets here (unreachable with whole_update; the sweep of tests/test_launch_plan.py holds it to that)
+        f.joseph = LPJ_LDS_PAIR; f.grid[0] = nt; f.grid[1] = (npair + 3) / 4;
+        f.ug_lds = {LP_UGL_BYTES, LPK_UG_LDS}; f.fin_lds = {LP_FNL_BYTES, LPK_FINAL_LDS};
+    } else if (B == 1) {   // one instance, 6n > 64: one wave per output tile, the chip is this instance's alone
+        const int c6t = (c6 + 15) / 16;
+        f.joseph = LPJ_TILE; f.grid[0] = f.grid[1] = (nt * c6t + 3) / 4; f.grid[2] = (nt * nt + 3) / 4; f.grid[3] = npair;
+    } else {   // batch handles
+        f.joseph = LPJ_STRIPS; f.grid[0] = (dd + 15) / 16; f.grid[1] = (npair + 3) / 4; f.ug_lds = {p.ug_lds, LPK_UG};
+    }
+    if (f.dx == LPD_ROLES) f.role_wgs = (dd + 23) / 24;
+    return f;
 }

@@ -64,28 +64,18 @@ struct rvio_hip {
     int *nrows = nullptr, *acc = nullptr, *ndof = nullptr, *gram_cnt = nullptr;
     double* gpose = nullptr;   // batch handles (max_len <= 16): the pose chains geom4_kernel leaves for feat_build_kernel<4>, [Fu][(max_len-1) x 24]
     int* gvalid = nullptr;     // ... and the validity flag of each triangulation
-    size_t trunc_lds = 0, gram_batch_lds = 0;   // gram_batch_lds != 0: batch handle whose [A|b] fits in LDS (gram_reduce_batch_kernel)
+    LaunchPlan plan;           // launch_plan.h: every LDS size and kernel variant that follows from (max_track_len, n_features, batch)
     // round 6 (literal.h): the rows of an update of <= LIT_FEATS features, exported by the per-feature kernel for the reference's literal sweep; the
     // state of the systolic array when it does not fit in the reduction's LDS (long windows, batch handles); nullptr: no literal path on this handle
     double *lit_rows = nullptr, *lit_state = nullptr;
-    bool lit_state_global = false;
-    size_t lit_batch_lds = 0;                   // dynamic LDS of lit_batch_kernel
     const double* last_Ab = nullptr;            // the [A|b] block of the last update (its meta row: frame_info)
-    int feat_threads = 64;
-    size_t feat_lds = 0, fprop_lds = 0, ug_lds = 0, book_lds = 0, jb_lds = 0;
-    int book_waves = 4;
-    bool book_fused = true;      // RANSAC + both halves of book-keeping fit one launch's LDS (launch_plan.h)
-    int solve5_variant = 0;      // solve6_kernel (the LDS-tableau solve behind gemm_T_kernel: batch handles): 0 none, 1: <1,8,8>  2: <2,12,8>  3: <2,16,8>
     StageSync* stage_sync = nullptr;   // device-side completion counter of the filter chain (aug) and the value it reaches after the launches so far
     StageSync stage_tgt = {};
     const unsigned long long* klt_wait = nullptr; unsigned long long klt_target = 0;
     unsigned long long* pyr_signal = nullptr;   // pending: the next detector launch on the image chain's queue bumps it   // this frame's klt_kernel3 polls the image chain's pyramid counter
-    int solve7_variant = 0;      // register-tableau solve with the T prologue (solve7.hip): 4: batch handles at 126 < 6n <= 192, 0: not used
-    int solve9_nt = 0;           // solve9_kernel (solve9.hip): tiles per side of the padded clone block (4, 6, 8, 12), 0: not used (batch handles)
-    double* S9scr = nullptr;     // its slab of tiles in L2: 5 NT^2 x 256 doubles (+ the verdict of the Cholesky role)
+    double* S9scr = nullptr;     // solve9's slab of tiles in L2 (plan.solve9_nt != 0): 5 NT^2 x 256 doubles (+ the verdict of the Cholesky role)
     bool chol_ready = false;     // the slab holds L, G of the clone block the next solve will see (written by the role workgroup of the per-feature / propagate launch)
     float* eig_map = nullptr;    // W x H min-eigenvalue map of rvio_hip_get_corners(eig): allocated on first use
-    size_t solve5_lds = 0, cholt_lds = 0;
     // staging
     rvio_imu* d_imu = nullptr;
     double* gathered = nullptr;   // rvio_hip_frame_sharded_dev: world x [S2 | S1] as the all-gather delivers them (allocated on first use)
@@ -100,13 +90,11 @@ struct rvio_hip {
     bool det_ready = false, use_det = false;
     hipStream_t stream_l = nullptr;               // long windows (6n > 96): = stream_c (one image chain in flight); the Cholesky factor of the clone block runs here, beside propagate / the per-feature stage of the frame it serves
     hipEvent_t evA = nullptr, evL = nullptr;      // augment/compose done (filter stream) -> stream_l;  factor in the slab (stream_l) -> the solve
-    bool dx_pending = false;                      // split solve: dx = Pc y and the state injection ride in the Joseph stage's first launch (launch_ug_final)
     bool chol_async = false;                      // a factor of the CURRENT clone block is in flight on (or has left) stream_l
     hipStream_t stream_d = nullptr;               // side stream of the front end: forks from / joins the tracker stream (see build_pyramid_dev)
     hipStream_t stream_c = nullptr;               // CLAHE stream of the run-ahead mode (frame k+1 is equalised while frame k is still being detected)
     hipEvent_t evC[kIC] = {nullptr, nullptr, nullptr};   // equalised image + pyramid of the frame ready, by image chain
-    int n_ic = 2;                                 // image chains in flight (<= kIC)
-    int ic = 0;                                   // image chain (stream / detector scratch / LUT set) of the call in progress: frame_no % n_ic in run-ahead mode, else the parity
+    int ic = 0;                                   // image chain (stream / detector scratch / LUT set) of the call in progress: frame_no % plan.n_ic (<= kIC) in run-ahead mode, else the parity
     hipStream_t side = nullptr;                   // stream of pyramid / KLT / RANSAC of the call in progress (stream_d beside the detector, else ts)
     hipEvent_t evD0 = nullptr, evD1 = nullptr;
     uint8_t* hb_img[2] = {nullptr, nullptr};      // staging of rvio_hip_frame (host buffers), by frame parity
@@ -162,7 +150,6 @@ struct rvio_hip {
     const rvio_imu* fuse_imu = nullptr;   // whole-frame path: propagate of this frame rides in the per-feature launch (feat_prop_kernel)
     const rvio_imu* time_imu = nullptr; int time_m = 0;   // the IMU batch of the last fused frame (rvio_hip_debug_time_kernel(8) only: the caller's buffer)
     int fuse_m = -1;                      // >= 0 while such a propagate is pending
-    bool fuse_ok = false;
     bool wide_px = false;            // throughput forms of the image kernels (several pixels per thread): batch handles of >= 8 instances
     bool front_end = true;           // a batch handle may carry the filter only
     bool det_in_slab = false;        // batch handle with front end: the detector's buffers are slab members too
@@ -320,7 +307,7 @@ static void fill_devcfg(const rvio_config* c, DevCfg* d) {
 }
 
 // The per-instance filter buffers (state, update scratch, Tracker -> Updater hand-over, IMU staging): called twice — sizes, then pointers
-static int alloc_filter_slab(rvio_hip* h, bool need_tm_global) {
+static int alloc_filter_slab(rvio_hip* h) {
     const DevCfg& d = h->dc;
     const size_t dm = d.dmax, PP = dm * dm, ldh = d.ldh;
     TrackerDev& t = h->t;
@@ -339,11 +326,11 @@ static int alloc_filter_slab(rvio_hip* h, bool need_tm_global) {
     DALLOC(h, h->d_imu, RVIO_MAX_IMU);
     DALLOC(h, h->d_info, 1); DALLOC(h, h->d_pose, 8);
     DALLOC(h, t.n_feat, 1); DALLOC(h, t.types, d.Fu); DALLOC(h, t.len, d.Fu); DALLOC(h, t.meas, (size_t)2 * d.Fu * d.max_len);
-    if (need_tm_global) DALLOC(h, h->tm_global, (size_t)d.Fu * d.rho_max * ldh);
+    if (h->plan.tm_global) DALLOC(h, h->tm_global, (size_t)d.Fu * d.rho_max * ldh);
     static const bool no_lit = getenv("RVIO_NO_LITERAL") != nullptr;   // A/B: the structural rank rule alone, as up to round 5
-    if (!no_lit && d.ldh <= 190 && d.nmax + 1 <= 40 && d.rho_max < 254 && lit_slab_doubles(d.ldh, d.rho_max) * sizeof(double) <= 144 * 1024) {
+    if (!no_lit && h->plan.lit_ok) {
         DALLOC(h, h->lit_rows, lit_rows_doubles(d.ldh, d.rho_max));
-        if (h->lit_state_global) DALLOC(h, h->lit_state, lit_state_doubles(d.ldh - 1));
+        if (h->plan.lit_state_global) DALLOC(h, h->lit_state, lit_state_doubles(d.ldh - 1));
     }
     if (h->batch > 1 && d.max_len <= GEOM4_ML) { DALLOC(h, h->gpose, (size_t)d.Fu * (d.max_len - 1) * 24); DALLOC(h, h->gvalid, d.Fu); }
     return RVIO_OK;
@@ -361,7 +348,7 @@ static int alloc_frontend_slab(rvio_hip* h) {
         DALLOC(h, h->d_eq2[0], (size_t)d.W * d.H); DALLOC(h, h->d_eq2[1], (size_t)d.W * d.H); DALLOC(h, h->d_eq2[2], (size_t)d.W * d.H);
         DALLOC(h, h->d_eq2[3], (size_t)d.W * d.H);
         h->d_eq = h->d_eq2[0];
-        for (int k = 0; k < std::max(2, h->n_ic); ++k) DALLOC(h, h->d_lut2[k], (size_t)h->cl_tx * h->cl_ty * 256);
+        for (int k = 0; k < std::max(2, h->plan.n_ic); ++k) DALLOC(h, h->d_lut2[k], (size_t)h->cl_tx * h->cl_ty * 256);
     }
     DALLOC(h, h->d_in_xy, (size_t)2 * d.F); DALLOC(h, h->d_in_st, d.F);
     DALLOC(h, h->rng, 40); DALLOC(h, h->cand_scratch, (size_t)2 * d.F + 8);
@@ -504,7 +491,8 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
     // whose footprint does not fit a CU beside the kernels' static LDS is refused here, not by a failed launch
     const size_t* statics = nullptr;
     HIPCHK(h, static_lds_table(&statics));
-    const LaunchPlan plan = launch_plan(cfg->max_track_len, cfg->n_features, batch, statics);
+    h->plan = launch_plan(cfg->max_track_len, cfg->n_features, batch, statics);
+    const LaunchPlan& plan = h->plan;
     if (plan.rc) { h->err = plan.why; return RVIO_ERR_UNSUPPORTED; }
     h->private_queues = g_private_queue_handles.fetch_add(1) == 0;
     if (!h->private_queues) g_private_queue_handles.fetch_sub(1);
@@ -518,7 +506,6 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
     // Long windows (96 < 6n <= 192: the solve in its split form, filter chain >= 250 us): ONE image chain in flight is enough (the chain is ~180 us),
     // and the queue that frees runs the Cholesky factor of the clone block beside the filter chain (augment_compose_dev).  A FIFTH queue for it was
     // measured: cfg C 3.2 k frames/s instead of 3.9 k — the command processor time-slices beyond four busy queues.
-    h->n_ic = plan.n_ic;
     if (plan.chol_queue) {
         h->stream_l = h->stream_c;
         HIPCHK(h, hipEventCreateWithFlags(&h->evA, kEvFlags));
@@ -537,10 +524,6 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
         HIPCHK(h, hipEventCreateWithFlags(&h->evF[b + 2], kEvFlags));
         HIPCHK(h, hipEventCreateWithFlags(&h->evIn[b], kEvFlags));
     }
-    h->feat_threads = plan.feat_threads;
-    h->trunc_lds = plan.trunc_lds; h->lit_state_global = plan.lit_state_global; h->lit_batch_lds = plan.lit_batch_lds;
-    h->feat_lds = plan.feat_lds;
-    const bool need_tm_global = plan.tm_global;
     if (front_end && cfg->enable_equalizer) {   // CLAHE(3.0, 5x5), Tracker.cc:198-202
         h->cl_tx = 5; h->cl_ty = 5;
         int ew = d.W, eh = d.H;
@@ -553,7 +536,7 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
     if (h->det_in_slab) { int rc = detector_check(h); if (rc != RVIO_OK) return rc; }
     // instance slab(s)
     h->slab_mode = true; h->slab = nullptr; h->slab_off = 0;
-    { int rc = alloc_filter_slab(h, need_tm_global); if (rc != RVIO_OK) return rc; }
+    { int rc = alloc_filter_slab(h); if (rc != RVIO_OK) return rc; }
     if (front_end) { int rc = alloc_frontend_slab(h); if (rc != RVIO_OK) return rc; }
     h->slab_bytes = h->slab_off;
     {
@@ -563,7 +546,7 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
         h->allocs.push_back(q);
         h->slab = (char*)q; h->slab_off = 0;
     }
-    { int rc = alloc_filter_slab(h, need_tm_global); if (rc != RVIO_OK) return rc; }
+    { int rc = alloc_filter_slab(h); if (rc != RVIO_OK) return rc; }
     if (front_end) { int rc = alloc_frontend_slab(h); if (rc != RVIO_OK) return rc; }
     h->slab_mode = false;
     h->bin = {0, h->slab_bytes, h->slab_bytes, h->slab_bytes, h->slab_bytes};
@@ -583,12 +566,7 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
         HIPCHK(h, hipMemcpy2DAsync(t.first, h->slab_bytes, ones.data(), sizeof(int), sizeof(int), (size_t)batch, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    h->gram_batch_lds = plan.gram_batch_lds;
-    h->fprop_lds = plan.fprop_lds; h->fuse_ok = plan.fuse_ok;
-    h->book_waves = plan.book_waves; h->book_lds = plan.book_lds; h->book_fused = plan.book_fused;
-    h->solve5_variant = plan.solve5_variant; h->solve7_variant = plan.solve7_variant; h->solve9_nt = plan.solve9_nt;
-    h->solve5_lds = plan.solve5_lds; h->jb_lds = plan.jb_lds; h->ug_lds = plan.ug_lds;
-    if (h->solve9_nt) DALLOC(h, h->S9scr, S9_SLAB_DOUBLES(h->solve9_nt) * (size_t)batch);
+    if (plan.solve9_nt) DALLOC(h, h->S9scr, S9_SLAB_DOUBLES(plan.solve9_nt) * (size_t)batch);
     for (int k = 0; k < LPK_COUNT; ++k)
         if (plan.attr[k]) HIPCHK(h, lds_attr(lp_kernel_fn(k), (int)plan.attr[k]));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -787,17 +765,21 @@ static int ensure_imu_capacity(rvio_hip* h, int m) {
     h->imu_cap = cap;
     return RVIO_OK;
 }
+// the forms of an update at clone count n (launch_plan.h update_forms): every launch function below takes its decisions from here
+static UpdateForms forms_at(const rvio_hip* h, int n, bool pre = false, bool whole_update = true, bool combined = true) {
+    return update_forms(h->plan, h->batch, n, pre, whole_update, combined, h->lit_rows != nullptr);
+}
 static int propagate_dev(rvio_hip* h, const rvio_imu* d_imu, int m, size_t imu_bs = 0, hipStream_t st = nullptr) {   // imu_bs = 0: every instance integrates the same samples
     if (!st) st = h->stream;
     h->time_imu = d_imu; h->time_m = m;   // (rvio_hip_debug_time_kernel(8))
     if (h->batch > 8)
         hipLaunchKernelGGL(propagate_kernel3b, dim3(1, 1, h->batch), dim3(256), 0, st, h->dc, h->meta, h->n_clones_host, h->x[h->cur], h->P[h->cur], d_imu, m,
                            h->slab_bytes, imu_bs);
-    else if (h->batch == 1 && h->solve9_nt && h->solve9_nt <= 6 && h->n_clones_host >= 1 && !imu_bs) {
+    else if (forms_at(h, h->n_clones_host).chol == LPC_ROLE && !imu_bs) {
         // plain handle, 6n <= 96: the Cholesky role of the solve (solve9.hip) as a second workgroup — the clone block it factors is the one the update
         // behind this propagate will see (propagation does not touch it)
         const int nc = h->n_clones_host;
-        if (h->solve9_nt == 4) hipLaunchKernelGGL(propagate_chol_kernel<2>, dim3(2), dim3(256), 0, st, h->dc, h->meta, nc, h->x[h->cur], h->P[h->cur], d_imu, m, h->S9scr);
+        if (h->plan.solve9_nt == 4) hipLaunchKernelGGL(propagate_chol_kernel<2>, dim3(2), dim3(256), 0, st, h->dc, h->meta, nc, h->x[h->cur], h->P[h->cur], d_imu, m, h->S9scr);
         else hipLaunchKernelGGL(propagate_chol_kernel<3>, dim3(2), dim3(256), 0, st, h->dc, h->meta, nc, h->x[h->cur], h->P[h->cur], d_imu, m, h->S9scr);
         h->chol_ready = true;
     }
@@ -837,29 +819,17 @@ static int upload_tracks(rvio_hip* h, const rvio_tracks* tr) {
 }
 
 static LitArgs lit_args(const rvio_hip* h, size_t lds_bytes) { return LitArgs{h->lit_rows, h->lit_rows ? h->lit_state : nullptr, h->t.n_feat, lds_bytes / sizeof(double)}; }
-// the share reduction of a batch handle whose [A|b] fits in LDS (6n <= 90): tiles of 16, 4 x 4 up to 6n = 63, 6 x 6 beyond
-static void launch_gram_batch(rvio_hip* h, int n) {
-    const dim3 g(1, 1, h->batch), b(256);
-    if (h->dc.ldh - 1 <= 63)
-        hipLaunchKernelGGL(gram_reduce_batch_kernel<4>, g, b, h->gram_batch_lds, h->stream, h->dc, n, h->partial, h->nrows, h->t.types, h->t.len, h->block, h->slab_bytes, h->bin);
-    else
-        hipLaunchKernelGGL(gram_reduce_batch_kernel<6>, g, b, h->gram_batch_lds, h->stream, h->dc, n, h->partial, h->nrows, h->t.types, h->t.len, h->block, h->slab_bytes, h->bin);
-    if (h->lit_rows)   // the literal sweep for the instances whose small stacks need it (literal.h)
-        hipLaunchKernelGGL(lit_batch_kernel, g, b, h->lit_batch_lds, h->stream, h->dc, n, (const int*)h->nrows,
-                           (const unsigned char*)h->t.types, (const int*)h->t.len, h->block, h->slab_bytes, h->bin, lit_args(h, h->lit_batch_lds));
-}
-
 // U1..U5 of shard `rank` of `world`, one workgroup per feature slot: the latency form for one stream (every operand load of a gate tile in flight at
 // once), the throughput form for a batch (with geom4_kernel's pose chains where the handle has them)
 static void launch_feat_build(rvio_hip* h, int n, int rank, int world) {
     const DevCfg& d = h->dc;
-    const dim3 g(d.Fu, 1, h->batch), b(h->feat_threads);
+    const dim3 g(d.Fu, 1, h->batch), b(h->plan.feat_threads);
     if (h->batch == 1)
-        hipLaunchKernelGGL(feat_build_kernel<16>, g, b, h->feat_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
+        hipLaunchKernelGGL(feat_build_kernel<16>, g, b, h->plan.feat_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
                            h->t.n_feat, h->t.types, h->t.len, h->t.meas, rank, world, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv,
                            h->tm_global, h->slab_bytes, h->bin, h->meta, (const double*)nullptr, (const int*)nullptr, h->lit_rows);
     else
-        hipLaunchKernelGGL(feat_build_kernel<4>, g, b, h->feat_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
+        hipLaunchKernelGGL(feat_build_kernel<4>, g, b, h->plan.feat_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
                            h->t.n_feat, h->t.types, h->t.len, h->t.meas, rank, world, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv,
                            h->tm_global, h->slab_bytes, h->bin, h->meta, (const double*)h->gpose, (const int*)h->gvalid, h->lit_rows);
 }
@@ -867,19 +837,29 @@ static void launch_feat_build(rvio_hip* h, int n, int rank, int world) {
 static void launch_feat_prop(rvio_hip* h, int n, const rvio_imu* d_imu, int m, int rank, int world) {
     const DevCfg& d = h->dc;
     // solve9 at 6n <= 96: the Cholesky of the clone block as one more workgroup of this launch (the solve of this very update follows on the stream)
-    const bool chol = h->solve9_nt && h->solve9_nt <= 6 && n >= 1;
-    hipLaunchKernelGGL(feat_prop_kernel, dim3(d.Fu + 1 + (chol ? 1 : 0)), dim3(256), h->fprop_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
+    const bool chol = forms_at(h, n).chol == LPC_ROLE;
+    hipLaunchKernelGGL(feat_prop_kernel, dim3(d.Fu + 1 + (chol ? 1 : 0)), dim3(256), h->plan.fprop_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
                        h->t.n_feat, h->t.types, h->t.len, h->t.meas, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv, h->tm_global, h->bin,
-                       h->meta, d_imu, m, chol ? h->S9scr : (double*)nullptr, h->solve9_nt, rank, world, h->lit_rows);
+                       h->meta, d_imu, m, chol ? h->S9scr : (double*)nullptr, h->plan.solve9_nt, rank, world, h->lit_rows);
     h->chol_ready = chol;
 }
-// reduction of the per-feature shares; finish: the last workgroup turns the block into [A|b] in place (rank truncation included)
-// one stream: 64 elements per workgroup (the shares are remote reads: spread them over many CUs); batch handles: 256 (fewer, fuller workgroups)
-static void launch_gram_reduce(rvio_hip* h, int n, bool finish) {
+// reduction of the per-feature shares into [S2 | S1]; gram_finish: the last workgroup turns the block into [A|b] in place (rank truncation included), as the
+// batch kernels always do — behind them the literal sweep for the instances whose small stacks need it (literal.h)
+static void launch_gram(rvio_hip* h, const UpdateForms& f, int n) {
     const DevCfg& d = h->dc;
-    const int B = h->batch, gram_chunk = (B == 1) ? 64 : 256;
-    hipLaunchKernelGGL(gram_reduce_kernel, dim3(std::max(1, std::min(1024, (6 * n * d.ldh + gram_chunk - 1) / gram_chunk)), 1, B), dim3(256), h->trunc_lds, h->stream, d, n,
-                       h->partial, h->nrows, h->t.types, h->t.len, h->block, h->gram_cnt, finish ? 1 : 0, (B == 1) ? 1 : 0, h->slab_bytes, h->bin, lit_args(h, h->trunc_lds));
+    const int B = h->batch;
+    const dim3 g(f.gram_grid, 1, B), b(256);
+    switch (f.gram) {
+    case LPG_REDUCE:
+        hipLaunchKernelGGL(gram_reduce_kernel, g, b, f.gram_lds.bytes, h->stream, d, n, h->partial, h->nrows, h->t.types, h->t.len, h->block, h->gram_cnt,
+                           f.gram_finish ? 1 : 0, (B == 1) ? 1 : 0, h->slab_bytes, h->bin, lit_args(h, f.gram_lds.bytes));
+        break;
+    case LPG_BATCH4: hipLaunchKernelGGL(gram_reduce_batch_kernel<4>, g, b, f.gram_lds.bytes, h->stream, d, n, h->partial, h->nrows, h->t.types, h->t.len, h->block, h->slab_bytes, h->bin); break;
+    case LPG_BATCH6: hipLaunchKernelGGL(gram_reduce_batch_kernel<6>, g, b, f.gram_lds.bytes, h->stream, d, n, h->partial, h->nrows, h->t.types, h->t.len, h->block, h->slab_bytes, h->bin); break;
+    }
+    if (f.lit_batch)
+        hipLaunchKernelGGL(lit_batch_kernel, g, b, f.lit_lds.bytes, h->stream, d, n, (const int*)h->nrows,
+                           (const unsigned char*)h->t.types, (const int*)h->t.len, h->block, h->slab_bytes, h->bin, lit_args(h, f.lit_lds.bytes));
 }
 
 static int update_local_dev(rvio_hip* h, int rank, int world, bool combine) {
@@ -896,103 +876,98 @@ static int update_local_dev(rvio_hip* h, int rank, int world, bool combine) {
         launch_feat_build(h, n, rank, world);
     }
     // unsharded: the reduction finishes into [A|b]; sharded: the block is the payload
-    if (B >= 128 && world == 1 && combine && h->gram_batch_lds)   // batch handle, [A|b] fits in LDS: one workgroup per instance, stored tiles only
-        launch_gram_batch(h, n);
-    else
-        launch_gram_reduce(h, n, world == 1 && combine);
+    launch_gram(h, forms_at(h, n, false, true, world == 1 && combine), n);
     HIPCHK(h, hipGetLastError());
     return RVIO_OK;
 }
 
-static void launch_solve(rvio_hip* h, int n, const double* Ab, bool defer_dx = false) {   // defer_dx: the caller launches the Joseph stage right behind (update_global_dev)
+// The code object lists its template kernels in the order the host code first names them.  EVERY template kernel of solve9.hip is named here, in
+// the order the code object has them: which function below launches which of them then has no bearing on the device code, and
+// tools/device_text_md5.sh can tell a host-side change from one that touched a kernel.  (Nothing reads the table.)
+[[maybe_unused]] static const void* const kSolve9Order[] = {
+    (const void*)solve9_kernel<1, 4>, (const void*)solve9_kernel<2, 3, true>, (const void*)solve9_kernel<2, 3>, (const void*)solve9_chol_kernel<2, 4>,
+    (const void*)solve9_chol_kernel<3, 4>, (const void*)solve9_prod_kernel<0>, (const void*)solve9_prod_kernel<1>, (const void*)solve9_sweep_kernel<2, 4>,
+    (const void*)solve9_sweep_kernel<3, 4>, (const void*)solve9_prod_kernel<2>, (const void*)solve9_prod_kernel<3>};
+// the two single-workgroup factorisations of the split solve, by tiles per side of the padded clone block (NT = 8 | 12)
+static void launch_s9_chol(rvio_hip* h, int NT, int n, double* Pc, hipStream_t st) {
+    if (NT == 8) hipLaunchKernelGGL((solve9_chol_kernel<2, 4>), dim3(1), dim3(1024), 0, st, h->dc, n, Pc, h->S9scr);
+    else hipLaunchKernelGGL((solve9_chol_kernel<3, 4>), dim3(1), dim3(1024), 0, st, h->dc, n, Pc, h->S9scr);
+}
+static void launch_s9_sweep(rvio_hip* h, int NT, const double* Ab) {
+    if (NT == 8) hipLaunchKernelGGL((solve9_sweep_kernel<2, 4>), dim3(1), dim3(1024), 0, h->stream, h->dc, Ab, h->S9scr);
+    else hipLaunchKernelGGL((solve9_sweep_kernel<3, 4>), dim3(1), dim3(1024), 0, h->stream, h->dc, Ab, h->S9scr);
+}
+// Is a factor of the clone block in the slab (role workgroup of this update's per-feature / propagate launch), or about to be (stream_l: the solve
+// waits for it; a failed wait: the solve factors Pcc itself)?  The solve behind this call consumes it.
+static bool take_chol(rvio_hip* h) {
+    if (h->chol_async && hipStreamWaitEvent(h->stream, h->evL, 0) != hipSuccess) { h->chol_async = false; h->chol_ready = false; }
+    const bool pre = h->chol_ready || h->chol_async;
+    h->chol_ready = false; h->chol_async = false;
+    return pre;
+}
+
+static void launch_solve(rvio_hip* h, const UpdateForms& f, int n, const double* Ab) {
     const DevCfg& d = h->dc;
     double *xin = h->x[h->cur], *xout = h->x[h->cur ^ 1], *Pc = h->P[h->cur];
     const dim3 gb(1, 1, h->batch);
-    if (h->solve9_nt) {   // one instance: blocked SPD factorisations on the matrix cores (solve9.hip)
-        if (h->chol_async && hipStreamWaitEvent(h->stream, h->evL, 0) != hipSuccess) { h->chol_async = false; h->chol_ready = false; }   // the factor that started behind the last augment / compose (a failed wait: the solve factors Pcc itself)
-        const bool pre = h->chol_ready || h->chol_async;   // L, G of the clone block are in the slab already (role workgroup of this update's per-feature / propagate launch; stream_l)
-        h->chol_ready = false; h->chol_async = false;
-        const size_t bs = h->slab_bytes;
-        switch (h->solve9_nt) {
-        case 4:
-            // in the frame's update the Joseph stage follows on the stream (6n <= 60 here: joseph_lds_kernel): dx = Pc y and the state injection become role
-            // workgroups of that launch (launch_ug_final)
-            if (pre) {
-                hipLaunchKernelGGL(solve9_small_kernel, dim3(1), dim3(1024), sizeof(S9SmallLds), h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout,
-                                   defer_dx ? h->S9scr + S9_YP_OFF(4) : (double*)nullptr);
-                h->dx_pending = defer_dx;
-            }
-            else hipLaunchKernelGGL((solve9_kernel<1, 4>), gb, dim3(1024), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, bs, (size_t)0);
-            return;
-        case 6:
-            // the frame's update at 64 < 6n_max <= 96: dx = Pc y and the state injection ride in the Joseph stage's launch — joseph_lds_kernel while the window still
-            // holds <= 10 clones, ug_tile_kernel<0> from 11 clones on (no window has 60 < 6n <= 64: the two-launch LDS form, which has no roles, serves the
-            // separately timed stages of rvio_hip_debug_time_kernel only)
-            if (pre) hipLaunchKernelGGL((solve9_kernel<2, 3, true>), gb, dim3(576), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, bs, (size_t)0, defer_dx ? 1 : 0);
-            else hipLaunchKernelGGL((solve9_kernel<2, 3>), gb, dim3(576), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, bs, (size_t)0, defer_dx ? 1 : 0);
-            h->dx_pending = defer_dx;
-            return;
-        default: break;
-        }
-        // 6n > 96: the split form — the four product phases as launches that fill the chip, the two factorisations as one workgroup each (solve9.hip)
-        const int NT = h->solve9_nt, nwg = (NT * NT + 3) / 4;
-        if (!pre) {
-            if (NT == 8) hipLaunchKernelGGL((solve9_chol_kernel<2, 4>), dim3(1), dim3(1024), 0, h->stream, d, n, Pc, h->S9scr);
-            else hipLaunchKernelGGL((solve9_chol_kernel<3, 4>), dim3(1), dim3(1024), 0, h->stream, d, n, Pc, h->S9scr);
-        }
+    const size_t bs = h->slab_bytes;
+    const bool roles = f.dx == LPD_ROLES;   // dx = Pc y and the state injection are left to role workgroups of the Joseph launch behind this one
+    switch (f.solve) {
+    case LPS_NONE: break;
+    // one instance: blocked SPD factorisations on the matrix cores (solve9.hip)
+    case LPS_SMALL: hipLaunchKernelGGL(solve9_small_kernel, dim3(1), dim3(1024), f.solve_lds.bytes, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, roles ? h->S9scr + S9_YP_OFF(4) : (double*)nullptr); break;
+    case LPS_S9_1_4: hipLaunchKernelGGL((solve9_kernel<1, 4>), gb, dim3(1024), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, bs, (size_t)0); break;
+    case LPS_S9_2_3_PRE: hipLaunchKernelGGL((solve9_kernel<2, 3, true>), gb, dim3(576), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, bs, (size_t)0, roles ? 1 : 0); break;
+    case LPS_S9_2_3: hipLaunchKernelGGL((solve9_kernel<2, 3>), gb, dim3(576), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, bs, (size_t)0, roles ? 1 : 0); break;
+    case LPS_SPLIT: {   // the four product phases as launches that fill the chip, the two factorisations as one workgroup each
+        const int NT = f.split_nt, nwg = (NT * NT + 3) / 4;
+        if (f.own_chol) launch_s9_chol(h, NT, n, Pc, h->stream);
         hipLaunchKernelGGL(solve9_prod_kernel<0>, dim3(nwg), dim3(256), 0, h->stream, d, n, Ab, h->S9scr, h->W, NT);
         hipLaunchKernelGGL(solve9_prod_kernel<1>, dim3(nwg), dim3(256), 0, h->stream, d, n, Ab, h->S9scr, h->W, NT);
-        if (NT == 8) hipLaunchKernelGGL((solve9_sweep_kernel<2, 4>), dim3(1), dim3(1024), 0, h->stream, d, Ab, h->S9scr);
-        else hipLaunchKernelGGL((solve9_sweep_kernel<3, 4>), dim3(1), dim3(1024), 0, h->stream, d, Ab, h->S9scr);
+        launch_s9_sweep(h, NT, Ab);
         hipLaunchKernelGGL(solve9_prod_kernel<2>, dim3(nwg), dim3(256), 0, h->stream, d, n, Ab, h->S9scr, h->W, NT);
         hipLaunchKernelGGL(solve9_prod_kernel<3>, dim3(nwg), dim3(256), 0, h->stream, d, n, Ab, h->S9scr, h->W, NT);
-        if (defer_dx && 6 * n > 64) h->dx_pending = true;   // (6n <= 64 while the window fills: launch_ug_final takes its short-window kernels)
-        else hipLaunchKernelGGL(solve9_dx_kernel, dim3(1), dim3(1024), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, NT);
-        return;
+        if (f.dx == LPD_KERNEL) hipLaunchKernelGGL(solve9_dx_kernel, dim3(1), dim3(1024), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->S9scr, h->W, xout, NT);
+        break;
     }
     // batch handles.  Beyond solve6's windows (6n > 126) the register-tableau solve: T = s2 I + A Pcc is formed by the kernel itself
-    if (h->solve7_variant == 4)
-        hipLaunchKernelGGL((solve7_kernel<3, 16, 12>), gb, dim3(768), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->Tbuf, h->W, xout, h->slab_bytes);
-    else if (h->solve5_variant == 1)
-        hipLaunchKernelGGL((solve6_kernel<1, 8, 8>), gb, dim3(512), h->solve5_lds, h->stream, d, h->meta, n, h->Tbuf, Ab, xin, Pc, h->W, xout, h->slab_bytes);
-    else if (h->solve5_variant == 2)
-        hipLaunchKernelGGL((solve6_kernel<2, 12, 8>), gb, dim3(512), h->solve5_lds, h->stream, d, h->meta, n, h->Tbuf, Ab, xin, Pc, h->W, xout, h->slab_bytes);
-    else if (h->solve5_variant == 3)
-        hipLaunchKernelGGL((solve6_kernel<2, 16, 8>), gb, dim3(512), h->solve5_lds, h->stream, d, h->meta, n, h->Tbuf, Ab, xin, Pc, h->W, xout, h->slab_bytes);
+    case LPS_SOLVE7: hipLaunchKernelGGL((solve7_kernel<3, 16, 12>), gb, dim3(768), 0, h->stream, d, h->meta, n, Ab, xin, Pc, h->Tbuf, h->W, xout, bs); break;
+    case LPS_SOLVE6_1: hipLaunchKernelGGL((solve6_kernel<1, 8, 8>), gb, dim3(512), f.solve_lds.bytes, h->stream, d, h->meta, n, h->Tbuf, Ab, xin, Pc, h->W, xout, bs); break;
+    case LPS_SOLVE6_2: hipLaunchKernelGGL((solve6_kernel<2, 12, 8>), gb, dim3(512), f.solve_lds.bytes, h->stream, d, h->meta, n, h->Tbuf, Ab, xin, Pc, h->W, xout, bs); break;
+    case LPS_SOLVE6_3: hipLaunchKernelGGL((solve6_kernel<2, 16, 8>), gb, dim3(512), f.solve_lds.bytes, h->stream, d, h->meta, n, h->Tbuf, Ab, xin, Pc, h->W, xout, bs); break;
+    }
 }
 
 // U = Pc W, G = U A  (K H = [0 | G]);  Joseph form (Updater.cc:615-619): P1 = (I-KH) P,  P+ = sym(P1 - P1c G^T + s2 G U^T)
-static void launch_ug_final(rvio_hip* h, int n, const double* Ab, double* Pn, bool ug, bool fin) {
+// ug, fin: the stages to launch (both: a whole update; the one-launch forms exist for a whole update only).  roles: the solve of these forms ran ahead
+// and left dx = Pc y and the state injection to f.role_wgs more workgroups of the first launch.
+static void launch_ug_final(rvio_hip* h, const UpdateForms& f, int n, const double* Ab, double* Pn, bool ug, bool fin, bool roles) {
     const DevCfg& d = h->dc;
-    const int c6 = 6 * n, dd = 24 + c6, B = h->batch;
+    const int B = h->batch;
     const size_t bs = h->slab_bytes;
     double* Pc = h->P[h->cur];
-    const int nt = (dd + 15) / 16, npair = nt * (nt + 1) / 2;
-    if (h->jb_lds && ug && fin) {   // batch handle, 6n <= 60: P -> P+ in one kernel (U, G, P1 never leave the CU)
-        hipLaunchKernelGGL(joseph_batch_kernel, dim3(1, 1, B), dim3(JB_THREADS), h->jb_lds, h->stream, d, n, Pc, h->W, Ab, Pn, bs);
-    } else if (B == 1 && c6 <= 60 && ug && fin) {   // one instance, short window: both stages in ONE launch, a workgroup per tile pair of P+
-        const bool dxr = h->dx_pending;   // the all-LDS solve left dx = Pc y and the state injection to role workgroups of this launch
-        h->dx_pending = false;
-        hipLaunchKernelGGL(joseph_lds_kernel, dim3(npair + (dxr ? (dd + 23) / 24 : 0)), dim3(256), JL_LDS_DOUBLES * sizeof(double), h->stream, d, n, Pc, h->W, Ab, Pn,
-                           h->meta, (const double*)h->x[h->cur], h->x[h->cur ^ 1], dxr ? (const double*)h->S9scr : (const double*)nullptr, npair, h->solve9_nt);
-    } else if (B == 1 && c6 <= 64) {   // ... one stage at a time (rvio_hip_debug_time_kernel): every operand of a workgroup staged in LDS with one batch of loads
-        if (ug) hipLaunchKernelGGL(ug_lds_kernel, dim3(nt), dim3(256), UGL_LDS_DOUBLES * sizeof(double), h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1);
-        if (fin) hipLaunchKernelGGL(final_lds_kernel, dim3((npair + 3) / 4), dim3(256), FNL_LDS_DOUBLES * sizeof(double), h->stream, d, n, h->Pt1, h->G, h->U, Pn);
-    } else if (B == 1) {   // one instance, 6n > 64: one wave per output tile, the chip is this instance's alone
-        const int c6t = (c6 + 15) / 16;
+    const int role_wgs = roles ? f.role_wgs : 0;
+    const double *nod = nullptr, *yp = role_wgs ? (const double*)h->S9scr : nod;
+    switch (f.joseph) {
+    case LPJ_BATCH: hipLaunchKernelGGL(joseph_batch_kernel, dim3(1, 1, B), dim3(JB_THREADS), f.ug_lds.bytes, h->stream, d, n, Pc, h->W, Ab, Pn, bs); break;
+    case LPJ_LDS: hipLaunchKernelGGL(joseph_lds_kernel, dim3(f.grid[0] + role_wgs), dim3(256), f.ug_lds.bytes, h->stream, d, n, Pc, h->W, Ab, Pn, h->meta, (const double*)h->x[h->cur], h->x[h->cur ^ 1], yp, f.grid[0], h->plan.solve9_nt); break;
+    case LPJ_LDS_PAIR:
+        if (ug) hipLaunchKernelGGL(ug_lds_kernel, dim3(f.grid[0]), dim3(256), f.ug_lds.bytes, h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1);
+        if (fin) hipLaunchKernelGGL(final_lds_kernel, dim3(f.grid[1]), dim3(256), f.fin_lds.bytes, h->stream, d, n, h->Pt1, h->G, h->U, Pn);
+        break;
+    case LPJ_TILE:
         if (ug) {
-            const bool dxr = h->dx_pending;   // the split solve left dx = Pc y and the state injection to role workgroups of this launch
-            h->dx_pending = false;
-            const double* nod = nullptr;
-            hipLaunchKernelGGL(ug_tile_kernel<0>, dim3((nt * c6t + 3) / 4 + (dxr ? (dd + 23) / 24 : 0)), dim3(256), 0, h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1,
-                               h->meta, (const double*)h->x[h->cur], h->x[h->cur ^ 1], dxr ? (const double*)h->S9scr : nod, h->solve9_nt);
-            hipLaunchKernelGGL(ug_tile_kernel<1>, dim3((nt * c6t + 3) / 4), dim3(256), 0, h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1, h->meta, nod, (double*)nullptr, nod, 0);
-            hipLaunchKernelGGL(ug_tile_kernel<2>, dim3((nt * nt + 3) / 4), dim3(256), 0, h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1, h->meta, nod, (double*)nullptr, nod, 0);
+            hipLaunchKernelGGL(ug_tile_kernel<0>, dim3(f.grid[0] + role_wgs), dim3(256), 0, h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1,
+                               h->meta, (const double*)h->x[h->cur], h->x[h->cur ^ 1], yp, h->plan.solve9_nt);
+            hipLaunchKernelGGL(ug_tile_kernel<1>, dim3(f.grid[1]), dim3(256), 0, h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1, h->meta, nod, (double*)nullptr, nod, 0);
+            hipLaunchKernelGGL(ug_tile_kernel<2>, dim3(f.grid[2]), dim3(256), 0, h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1, h->meta, nod, (double*)nullptr, nod, 0);
         }
-        if (fin) hipLaunchKernelGGL(final_tile_kernel, dim3(npair), dim3(256), 0, h->stream, d, n, h->Pt1, h->G, h->U, Pn);
-    } else {   // batch handles
-        if (ug) hipLaunchKernelGGL(ug_kernel, dim3((dd + 15) / 16, 1, B), dim3(256), h->ug_lds, h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1, bs);
-        if (fin) hipLaunchKernelGGL(final_kernel, dim3((npair + 3) / 4, 1, B), dim3(256), 0, h->stream, d, n, h->Pt1, h->G, h->U, Pn, bs);
+        if (fin) hipLaunchKernelGGL(final_tile_kernel, dim3(f.grid[3]), dim3(256), 0, h->stream, d, n, h->Pt1, h->G, h->U, Pn);
+        break;
+    case LPJ_STRIPS:
+        if (ug) hipLaunchKernelGGL(ug_kernel, dim3(f.grid[0], 1, B), dim3(256), f.ug_lds.bytes, h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1, bs);
+        if (fin) hipLaunchKernelGGL(final_kernel, dim3(f.grid[1], 1, B), dim3(256), 0, h->stream, d, n, h->Pt1, h->G, h->U, Pn, bs);
+        break;
     }
 }
 
@@ -1032,7 +1007,7 @@ static int lm_alloc(rvio_hip* h, LmOut* out) {
 // combined: d_blocks is the handle's own block, already turned into [A|b] by gram_reduce_kernel (unsharded update)
 static int update_global_dev(rvio_hip* h, const double* d_blocks, int world, bool combined) {
     const DevCfg& d = h->dc;
-    const int n = h->n_clones_host, c6 = 6 * n, dd = 24 + c6;
+    const int n = h->n_clones_host, c6 = 6 * n;
     const long ldh = d.ldh;
     double* Pc = h->P[h->cur];
     double* Pn = h->P[h->cur ^ 1];
@@ -1042,20 +1017,19 @@ static int update_global_dev(rvio_hip* h, const double* d_blocks, int world, boo
     if (B > 1 && !combined) { h->err = "a batch handle runs the unsharded updater only"; return RVIO_ERR_UNSUPPORTED; }
     if (!combined) {   // gathered shards [S2 | S1]: sum both parts in rank order, then the rank truncation -> Ab = [A|b]
         const int eg = std::max(1, std::min(64, (int)((c6 * ldh + 255) / 256)));
-        hipLaunchKernelGGL(block_sum_kernel, dim3(eg), dim3(256), h->trunc_lds, h->stream, d, n, d_blocks, world, (size_t)shard_payload_doubles(c6, d.max_len), h->Ab, h->gram_cnt,
-                           (const int*)h->nrows, (const unsigned char*)h->t.types, (const int*)h->t.len, lit_args(h, h->trunc_lds));
+        hipLaunchKernelGGL(block_sum_kernel, dim3(eg), dim3(256), h->plan.trunc_lds, h->stream, d, n, d_blocks, world, (size_t)shard_payload_doubles(c6, d.max_len), h->Ab, h->gram_cnt,
+                           (const int*)h->nrows, (const unsigned char*)h->t.types, (const int*)h->t.len, lit_args(h, h->plan.trunc_lds));
         Ab = h->Ab;
     }
-    const int tt = (c6 + 31) / 32;
-    if (!h->solve7_variant && !h->solve9_nt) {
-        if (B >= 128 && d.ldh - 1 <= 64)
-            hipLaunchKernelGGL(gemm_T_lds_kernel, dim3(1, 1, B), dim3(256), (size_t)2 * c6 * (c6 + 1) * sizeof(double), h->stream, d, n, Ab, Pc, h->Tbuf, bs);
-        else
-            hipLaunchKernelGGL(gemm_T_kernel, dim3(tt, tt, B), dim3(256), 0, h->stream, d, n, Ab, Pc, h->Tbuf, bs);
-    }
+    // the forms of this update, decided once: the solve and the Joseph stage see the same value (who runs dx = Pc y is settled between them here)
+    const UpdateForms f = forms_at(h, n, take_chol(h), true, combined);
+    if (f.tprod == LPT_GEMM_LDS)
+        hipLaunchKernelGGL(gemm_T_lds_kernel, dim3(1, 1, B), dim3(256), f.tprod_lds.bytes, h->stream, d, n, Ab, Pc, h->Tbuf, bs);
+    else if (f.tprod == LPT_GEMM)
+        hipLaunchKernelGGL(gemm_T_kernel, dim3(f.tprod_grid, f.tprod_grid, B), dim3(256), 0, h->stream, d, n, Ab, Pc, h->Tbuf, bs);
     h->last_Ab = Ab;
-    launch_solve(h, n, Ab, /*defer_dx=*/true);
-    launch_ug_final(h, n, Ab, Pn, true, true);
+    launch_solve(h, f, n, Ab);
+    launch_ug_final(h, f, n, Ab, Pn, true, true, f.dx == LPD_ROLES);
     HIPCHK(h, hipGetLastError());
     h->cur ^= 1;
     if (h->lm_on) {   // the cloud: x[cur] is xk1k1 now, x[cur ^ 1] still xk1k (every update form writes the other buffer; augcomp_kernel2 rewrites it next)
@@ -1171,11 +1145,10 @@ static int augment_compose_dev(rvio_hip* h, int do_augment) {
     // Long windows (6n > 96, solve in its split form): Pcc = L L^T of the NEXT update is known from here on — propagation leaves the clone block
     // alone — so the factor starts now on a stream of its own and runs beside propagate, the wait for the tracker and the per-feature stage; the
     // solve's first product waits for it (launch_solve).  ~35 us at 6n = 120, ~95 us at 6n = 180 off the filter chain.
-    if (h->solve9_nt >= 8 && h->stream_l && !profiler_serialises() && h->n_clones_host >= 1) {
+    if (forms_at(h, h->n_clones_host).chol == LPC_QUEUE && !profiler_serialises()) {
         HIPCHK(h, hipEventRecord(h->evA, h->stream));
         HIPCHK(h, hipStreamWaitEvent(h->stream_l, h->evA, 0));
-        if (h->solve9_nt == 8) hipLaunchKernelGGL((solve9_chol_kernel<2, 4>), dim3(1), dim3(1024), 0, h->stream_l, d, h->n_clones_host, h->P[h->cur], h->S9scr);
-        else hipLaunchKernelGGL((solve9_chol_kernel<3, 4>), dim3(1), dim3(1024), 0, h->stream_l, d, h->n_clones_host, h->P[h->cur], h->S9scr);
+        launch_s9_chol(h, h->plan.solve9_nt, h->n_clones_host, h->P[h->cur], h->stream_l);
         HIPCHK(h, hipEventRecord(h->evL, h->stream_l));
         h->chol_async = true;
     }
@@ -1214,8 +1187,8 @@ static int detector_alloc_set(rvio_hip* h, DetDev& q) {   // the scratch of ONE 
 static int detector_alloc(rvio_hip* h) {   // DALLOCs only (runs twice for a slab)
     const DevCfg& d = h->dc;
     int rc = RVIO_OK;
-    for (int k = 0; k < h->n_ic; ++k) if ((rc = detector_alloc_set(h, h->dets[k])) != RVIO_OK) return rc;
-    for (int k = h->n_ic; k < rvio_hip::kIC; ++k) h->dets[k] = h->dets[0];
+    for (int k = 0; k < h->plan.n_ic; ++k) if ((rc = detector_alloc_set(h, h->dets[k])) != RVIO_OK) return rc;
+    for (int k = h->plan.n_ic; k < rvio_hip::kIC; ++k) h->dets[k] = h->dets[0];
     DALLOC(h, h->det_xy2[0], (size_t)2 * d.F); DALLOC(h, h->det_xy2[1], (size_t)2 * d.F); DALLOC(h, h->det_xy2[2], (size_t)2 * d.F);
     DALLOC(h, h->det_nout, 3);
     float* mask = nullptr;
@@ -1424,9 +1397,9 @@ static int post_klt_dev(rvio_hip* h, const rvio_imu* d_imu, int m, const float* 
             unsigned long long* hand = nullptr;
             if (h->dev_sync) { hand = &h->stage_sync->handover; h->stage_tgt.handover++; }
             // one stream, device-side counters: RANSAC and both halves of book-keeping are ONE launch (the refill half polls the detector's counter inside it)
-            if (h->dev_sync && h->book_fused) {
+            if (h->dev_sync && h->plan.book_fused) {
                 h->gate_pending = true; h->gate_target = h->stage_tgt.handover;
-                hipLaunchKernelGGL(ransac_book_kernel, dim3(1, 1, B), dim3(64 * h->book_waves), h->book_lds, h->tail, h->dc, h->t, d_imu, m, h->rng, bs, h->imu_bs,
+                hipLaunchKernelGGL(ransac_book_kernel, dim3(1, 1, B), dim3(64 * h->plan.book_waves), h->plan.book_lds, h->tail, h->dc, h->t, d_imu, m, h->rng, bs, h->imu_bs,
                                    done, done_target, h->meta, hand, xy, nout, &h->stage_sync->corners[h->ic], h->stage_tgt.corners[h->ic]);
                 HIPCHK(h, hipGetLastError());
                 return RVIO_OK;
@@ -1446,10 +1419,10 @@ static int post_klt_dev(rvio_hip* h, const rvio_imu* d_imu, int m, const float* 
             HIPCHK(h, hipStreamWaitEvent(h->ts, h->evD1, 0));
             hipLaunchKernelGGL(bookkeep_a_kernel, dim3(1, 1, B), dim3(256), 0, h->tail, h->dc, h->t, bs, done, done_target, h->meta, (unsigned long long*)nullptr);
         }
-        hipLaunchKernelGGL(bookkeep_b_kernel, dim3(1, 1, B), dim3(64 * h->book_waves), h->book_lds, h->tail, h->dc, h->t, xy, 0, nout, bs, corners, corners_target, h->meta);
+        hipLaunchKernelGGL(bookkeep_b_kernel, dim3(1, 1, B), dim3(64 * h->plan.book_waves), h->plan.book_lds, h->tail, h->dc, h->t, xy, 0, nout, bs, corners, corners_target, h->meta);
     } else {
         hipLaunchKernelGGL(bookkeep_a_kernel, dim3(1), dim3(256), 0, h->ts, h->dc, h->t, (size_t)0, (const unsigned long long*)nullptr, 0ull, h->meta, (unsigned long long*)nullptr);
-        hipLaunchKernelGGL(bookkeep_b_kernel, dim3(1), dim3(64 * h->book_waves), h->book_lds, h->ts, h->dc, h->t, d_cand, n_cand, (const int*)nullptr, (size_t)0,
+        hipLaunchKernelGGL(bookkeep_b_kernel, dim3(1), dim3(64 * h->plan.book_waves), h->plan.book_lds, h->ts, h->dc, h->t, d_cand, n_cand, (const int*)nullptr, (size_t)0,
                            (const unsigned long long*)nullptr, 0ull, h->meta);
     }
     HIPCHK(h, hipGetLastError());
@@ -1468,7 +1441,7 @@ static int track_dev_impl(rvio_hip* h, const uint8_t* d_img, int stride, const r
     h->dev_sync = h->runahead && h->batch == 1 && !no_device_polls();
     h->gate_pending = false;
     h->dslot = h->runahead ? (int)(h->frame_no % 3) : h->par;
-    h->ic = h->runahead ? (int)(h->frame_no % h->n_ic) : h->par;
+    h->ic = h->runahead ? (int)(h->frame_no % h->plan.n_ic) : h->par;
     const int nb = (h->pyr_cur + 1) % 4;   // pyramid of the new image; pyr_cur holds mLastImage's (slot nb was last read by KLT(k-3))
     rc = build_pyramid_dev(h, d_img, stride, nb);
     if (rc != RVIO_OK) return rc;
@@ -1679,7 +1652,7 @@ static int frame_dev_impl(rvio_hip* h, const uint8_t* d_img, int stride, const r
     }
     // propagate: with an update in this frame (and nobody sequencing the update from outside) it rides in the per-feature launch,
     // otherwise it goes to the filter stream right behind augment/compose(k-1)
-    const bool fuse = h->fuse_ok && (!begin_only || defer_propagate) && h->n_clones_host > h->cfg.min_track_len - 1;
+    const bool fuse = h->plan.fuse_ok && (!begin_only || defer_propagate) && h->n_clones_host > h->cfg.min_track_len - 1;
     int rc = RVIO_OK;
     h->fuse_m = -1;
     if (!fuse) rc = propagate_dev(h, d_imu, m, h->imu_bs);
@@ -1870,7 +1843,7 @@ int rvio_hip_frame(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* 
         // The image goes to the stream of this frame's image chain (image_stream: tracker stream / fourth stream by parity).  hb_img[b]
         // was last read by frame k-2: its CLAHE / detector (same stream, earlier) and — without the equaliser — its pyramid on the side
         // stream, which book-keeping(k-2) followed.
-        hipStream_t is = image_stream_of(h, (int)(h->frame_no % h->n_ic));
+        hipStream_t is = image_stream_of(h, (int)(h->frame_no % h->plan.n_ic));
         if (h->frame_no >= 2) HIPCHK(h, hipStreamWaitEvent(is, h->evT[(h->frame_no - 2) & 3], 0));
         HIPCHK(h, hipMemcpyAsync(h->hb_img[b], pp, npx, hipMemcpyHostToDevice, is));
         HIPCHK(h, hipEventRecord(h->evPin2[ps], is));
@@ -2009,7 +1982,7 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
     hipEvent_t e0, e1;
     double *bx = nullptr, *bP = nullptr;
     if (which == 8) {   // (the fused launch propagates in place: the state is put aside and restored behind the timed launches)
-        if (h->batch > 1 || !h->fuse_ok || !h->time_imu || n < 1) return RVIO_ERR_UNSUPPORTED;
+        if (h->batch > 1 || !h->plan.fuse_ok || !h->time_imu || n < 1) return RVIO_ERR_UNSUPPORTED;
         HIPCHK(h, hipMalloc(&bx, sizeof(double) * d.xdmax)); HIPCHK(h, hipMalloc(&bP, sizeof(double) * d.dmax * d.dmax));
         HIPCHK(h, hipMemcpyAsync(bx, h->x[h->cur], sizeof(double) * d.xdmax, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(bP, h->P[h->cur], sizeof(double) * d.dmax * d.dmax, hipMemcpyDeviceToDevice, h->stream));
@@ -2020,6 +1993,10 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
         const int rc = lm_alloc(h, &lmt);
         if (rc != RVIO_OK) return rc;
     }
+    // the forms the frame's update would get at this window (time what the chain sees: the Cholesky factor rides in the per-feature launch / runs on its own
+    // queue; the slab holds the factor of the last update): fw for a whole update, fs for one separately timed stage
+    const bool pre = h->plan.solve9_nt && (h->plan.solve9_nt <= 6 || h->plan.chol_queue);
+    const UpdateForms fw = forms_at(h, n, pre, true), fs = forms_at(h, n, pre, false);
     HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
     HIPCHK(h, hipEventRecord(e0, h->stream));
     for (int it = 0; it < iters; ++it) {
@@ -2038,9 +2015,7 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
             hipLaunchKernelGGL(greedy_kernel, dim3(1, 1, 1), dim3(GREEDY_T), GREEDY_LDS, h->stream, q, h->slab_bytes);
         } else
         if (which == 0) {
-            h->chol_ready = h->solve9_nt && (h->solve9_nt <= 6 || h->stream_l);   // (time what the chain sees: the Cholesky factor rides in the per-feature launch / runs on its own queue; the slab holds the factor of the last update)
-            launch_solve(h, n, h->block, /*defer_dx=*/true);   // as the frame's update launches it: dx = Pc y and the state injection are roles of the Joseph launch behind it
-            h->dx_pending = false;
+            launch_solve(h, fw, n, h->block);   // as the frame's update launches it: dx = Pc y and the state injection are roles of the Joseph launch behind it (not run here)
         } else if (which == 1) {
             // KLT as the frame ran it cannot be repeated (book-keeping has moved the features to where they were tracked): match the CURRENT
             // image back onto the PREVIOUS one from the current feature positions instead — the same displacement magnitudes, reversed, the
@@ -2050,14 +2025,12 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
                                h->t.tracked, h->t.status, (size_t)0, (const unsigned long long*)nullptr, 0ull, h->meta);
         } else if (which == 2) {
             launch_feat_build(h, n, 0, 1);   // (a batch handle: on the pose chains geom4_kernel left in the last update)
-        } else if (which == 3 && h->batch >= 128 && h->gram_batch_lds) {
-            launch_gram_batch(h, n);
         } else if (which == 3) {   // reduction of the per-feature shares + rank truncation (reads `partial`, rewrites `block`: idempotent)
-            launch_gram_reduce(h, n, true);
+            launch_gram(h, fw, n);
         } else if (which == 4 || which == 5) {   // U, G, P1 strips / the Joseph form on the operands of the last update, in the form the handle launches
-            launch_ug_final(h, n, h->block, h->P[h->cur ^ 1], which == 4, which == 5);   // (outputs: scratch / the spare covariance buffer, overwritten by the next stage anyway)
+            launch_ug_final(h, fs, n, h->block, h->P[h->cur ^ 1], which == 4, which == 5, false);   // (outputs: scratch / the spare covariance buffer, overwritten by the next stage anyway)
         } else if (which == 7) {   // U, G, P1 + the Joseph form as the handle launches them for a whole update (one instance, 6n <= 60: ONE kernel)
-            launch_ug_final(h, n, h->block, h->P[h->cur ^ 1], true, true);
+            launch_ug_final(h, fw, n, h->block, h->P[h->cur ^ 1], true, true, false);   // (no solve ran ahead of the timed launch: no dx waits for its roles)
         } else if (which == 6) {   // cornerSubPix on the corners of the last detector call (reads raw_xy, rewrites xy with the same values)
             if (h->batch > 1 || !h->det_ready) return RVIO_ERR_UNSUPPORTED;
             const DetDev q = [&] { DetDev v = h->dets[h->det_set_last]; v.xy = h->det_xy2[h->dslot]; v.n_out = h->det_nout + h->dslot; return v; }();
@@ -2066,6 +2039,9 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
         } else return RVIO_ERR_INVALID;
     }
     HIPCHK(h, hipEventRecord(e1, h->stream));
+    // the timed solves ran on the slab: the next update factors the clone block itself.  (No wait for evL in front of them and none here: drain_all() above
+    // has synchronised stream_c, which IS stream_l, so a factor that was in flight has landed.)
+    if (which == 0) { h->chol_ready = false; h->chol_async = false; }
     if (which == 8) {
         HIPCHK(h, hipMemcpyAsync(h->x[h->cur], bx, sizeof(double) * d.xdmax, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->P[h->cur], bP, sizeof(double) * d.dmax * d.dmax, hipMemcpyDeviceToDevice, h->stream));
@@ -2115,7 +2091,7 @@ int rvio_hip_debug_poison(rvio_hip* h, int what) {
         HIPCHK(h, fill(h->block, sizeof(double) * 2 * ldh * ldh)); HIPCHK(h, fill(h->Ab, sizeof(double) * 2 * ldh * ldh));
         HIPCHK(h, fill(h->Tbuf, sizeof(double) * ldh * ldh)); HIPCHK(h, fill(h->W, sizeof(double) * ldh * ldh));
         if (h->S9scr) {   // the slab holds the Cholesky factor a PRE solve would read (role workgroup / stream_l): it goes with the slab — the next solve factors Pcc itself
-            HIPCHK(h, hipMemsetAsync(h->S9scr, 0xff, sizeof(double) * S9_SLAB_DOUBLES(h->solve9_nt), h->stream));
+            HIPCHK(h, hipMemsetAsync(h->S9scr, 0xff, sizeof(double) * S9_SLAB_DOUBLES(h->plan.solve9_nt), h->stream));
             h->chol_ready = false; h->chol_async = false;   // (drain_all above has waited for stream_l)
         }
         HIPCHK(h, fill(h->U, sizeof(double) * dm * ldh)); HIPCHK(h, fill(h->G, sizeof(double) * dm * ldh));

@@ -1,7 +1,8 @@
 // plan_emu.cpp — r-vio_amd/csrc/launch_plan.h compiled with g++: the launch geometry create_impl derives from a configuration, evaluated on the
-// CPU for every accepted (max_track_len, n_features, batch).  tests/test_launch_plan.py feeds it the static LDS of each kernel as the built
-// library's code object has it and checks static + dynamic against a CU's LDS.
+// CPU for every accepted (max_track_len, n_features, batch), and the forms of an update (update_forms) for every clone count of every window.
+// tests/test_launch_plan.py feeds it the static LDS of each kernel as the built library's code object has it and checks static + dynamic against a CU's LDS.
 #include "../../r-vio_amd/csrc/launch_plan.h"
+#include <initializer_list>
 #include <string.h>
 
 extern "C" {
@@ -11,13 +12,14 @@ long lp_lds_limit() { return RVIO_LDS_LIMIT; }
 int lp_max_features() { return RVIO_MAX_FEATURES; }
 int lp_max_len() { return RVIO_MAX_LEN; }
 
-// one configuration.  attr[LPK_COUNT]: dynamic LDS per kernel; info[16]: see below; why: the refusal's text (<= 255 chars).  Returns plan.rc
+// one configuration.  attr[LPK_COUNT]: dynamic LDS per kernel; info[18]: see below; why: the refusal's text (<= 255 chars).  Returns plan.rc
 int lp_eval(int max_len, int n_features, int batch, const size_t* statics, size_t* attr, long* info, char* why) {
     const LaunchPlan p = launch_plan(max_len, n_features, batch, statics);
     for (int k = 0; k < LPK_COUNT; ++k) attr[k] = p.attr[k];
     info[0] = p.book_waves; info[1] = (long)p.book_lds; info[2] = p.book_fused; info[3] = p.tm_global; info[4] = p.lit_state_global;
     info[5] = p.solve5_variant; info[6] = p.solve7_variant; info[7] = p.solve9_nt; info[8] = p.n_ic; info[9] = p.feat_threads;
     info[10] = (long)p.feat_lds; info[11] = (long)p.fprop_lds; info[12] = (long)p.trunc_lds; info[13] = p.fuse_ok; info[14] = (long)p.jb_lds; info[15] = (long)p.gram_batch_lds;
+    info[16] = p.chol_queue; info[17] = p.lit_ok;
     why[0] = 0;
     if (p.why) { strncpy(why, p.why, 255); why[255] = 0; }
     return p.rc;
@@ -42,6 +44,24 @@ long lp_sweep(int ml0, int ml1, int f0, int f1, int batch, const size_t* statics
         }
     *n_unsupported = uns;
     return bad;
+}
+
+// the forms of one update of that configuration at clone count n (update_forms).  out[LP_FORMS_LEN]: the enums and grids in the order below, then
+// (bytes, LpKernel) of each launch with dynamic LDS — reduction, literal sweep, T product, solve, first Joseph launch, final_lds_kernel.  Returns plan.rc
+enum { LP_FORMS_LEN = 32 };
+int lp_forms_len() { return LP_FORMS_LEN; }
+int lp_forms(int max_len, int n_features, int batch, const size_t* statics, int n, int pre, int whole_update, int combined, int lit, long* out) {
+    const LaunchPlan p = launch_plan(max_len, n_features, batch, statics);
+    if (p.rc) return p.rc;
+    const UpdateForms f = update_forms(p, batch, n, pre != 0, whole_update != 0, combined != 0, lit != 0);
+    int k = 0;
+    out[k++] = f.chol; out[k++] = f.gram; out[k++] = f.gram_grid; out[k++] = f.gram_finish; out[k++] = f.lit_batch;
+    out[k++] = f.tprod; out[k++] = f.tprod_grid; out[k++] = f.solve; out[k++] = f.split_nt; out[k++] = f.own_chol; out[k++] = f.dx;
+    out[k++] = f.joseph; for (int g = 0; g < 4; ++g) out[k++] = f.grid[g];
+    out[k++] = f.role_wgs;
+    for (const LpLds* l : {&f.gram_lds, &f.lit_lds, &f.tprod_lds, &f.solve_lds, &f.ug_lds, &f.fin_lds}) { out[k++] = (long)l->bytes; out[k++] = l->kernel; }
+    while (k < LP_FORMS_LEN) out[k++] = 0;
+    return 0;
 }
 
 // diagnostics in the [A|b] block: one past the last double written (stamps: the instrumented build), and the block's size

@@ -172,3 +172,46 @@ def test_sharded_updater_fake_shards_on_one_gpu(hipB, recB, world):
     x, P = hipB.get_state()
     assert S.state_delta(x, xo) <= X_TOL
     assert p_close(P, Po)
+
+
+@pytest.mark.parametrize("ml", [4, 13])     # 13: the window crosses 6n = 60 -> 66 while it fills — joseph_lds_kernel, then the ug_tile set (both have roles)
+def test_timing_hook_leaves_the_filter_alone(gpu_required, ml):
+    """rvio_hip_debug_time_kernel re-launches the solve (0), the share reduction (3), the Joseph stages (4, 5) and the whole Joseph form (7) in
+    the forms the frame's update gets, on the operands the last frame left behind: a free run with those calls between its frames ends every
+    frame on the same bits as one without.  (Not the windows with the Cholesky queue, 6n_max > 96: there the timed solve consumes the factor in
+    flight, and the next update factors the clone block itself.  Not on the empty window either, which only the first frame leaves behind: no
+    update is ever launched at n = 0, and joseph_lds_kernel's strip rounds take a tile index modulo ceil(6n / 16) = 0 there.)"""
+    from rvio_amd import hip
+    cfg = abi.config_named("B", enable_equalizer=0, max_track_len=ml, n_features=40)
+    n = ml + 4
+    seq = rv.synth.SynthSequence(cfg, duration=(38 + n + 4) / 20.0, seed=3)
+    w, a, ni = seq.init_from_static(38)
+
+    def run(timed):
+        h = hip.RvioHip(cfg)
+        h.initialize(w, a, ni)
+        drv = rv.synth.DirectTrackDriver(seq)
+        out, updated = [], 0
+        for k in range(39, 39 + n):
+            inp = drv.inputs(k)
+            h.frame_points(inp["tracked"], inp["status"], inp["imu"], inp["cand"])
+            drv.after(h.get_points()[0])
+            info = h.frame_info()
+            assert info["device_error"] == 0, (k, info)
+            updated += info["updated"]
+            out.append(h.get_state())
+            n_clones = (len(out[-1][0]) - 26) // 7
+            assert n_clones == min(k - 39, ml - 1)
+            if timed and n_clones >= 1:     # (not on the empty window behind the first frame: see the docstring)
+                for which in (0, 3, 4, 5, 7):
+                    assert h.time_kernel(which, 2) > 0
+        assert h.frame_info()["device_error"] == 0
+        h.close()
+        return out, updated
+
+    plain, upd = run(False)
+    timed, upd_t = run(True)
+    # (the CPU oracle applies 4 updates on this sequence at max_track_len 4, all on the full window, and 5 at 13: with 5 and 8 clones, then three with 12)
+    assert upd >= 4 and upd_t == upd
+    for k, ((xa, Pa), (xb, Pb)) in enumerate(zip(plain, timed)):
+        assert np.array_equal(xa, xb) and np.array_equal(Pa, Pb), k

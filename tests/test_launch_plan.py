@@ -4,7 +4,9 @@ rvio_hip_create / rvio_hip_create_batch accept max_track_len 3..32, n_features 2
 from them every dynamic-LDS size, the kernel variants and what moves from LDS to global memory, and create_impl applies exactly that text.
 tests/hostemu/plan_emu.cpp compiles the same header with g++; this file sweeps EVERY window x EVERY feature count x batch in {1, 8, 128} and
 checks, for every kernel that is given a dynamic-LDS limit, that dynamic + static fits the 163 840 B of a gfx950 CU — or that the plan refuses
-the configuration with a message.  The static part is the compiler's decision: it is read from the BUILT library (the .hip_fatbin section ->
+the configuration with a message.  The forms of an update (update_forms(): which kernels it launches at clone count n) are swept the same way
+for every n of every window: roles only where the Joseph launch has them, every launch's dynamic LDS inside its kernel's limit, every threshold
+pinned on both sides.  The static part is the compiler's decision: it is read from the BUILT library (the .hip_fatbin section ->
 the gfx950 code object -> the kernel descriptors' notes), not from a table — the library must have been built (`__graft_entry__.build()`).
 
 What this would have caught (and the arithmetic of the commit before it, kept here as `parent_book_lds`): book-keeping's LDS was budgeted
@@ -86,10 +88,10 @@ def statics(emu, static_lds):
 
 def evaluate(emu, statics, ml, F, batch):
     n = emu.lp_num_kernels()
-    attr, info, why = (C.c_size_t * n)(), (C.c_long * 16)(), C.create_string_buffer(256)
+    attr, info, why = (C.c_size_t * n)(), (C.c_long * 18)(), C.create_string_buffer(256)
     rc = emu.lp_eval(ml, F, batch, statics, attr, info, why)
     keys = ("book_waves", "book_lds", "book_fused", "tm_global", "lit_state_global", "solve5_variant", "solve7_variant", "solve9_nt", "n_ic", "feat_threads",
-            "feat_lds", "fprop_lds", "trunc_lds", "fuse_ok", "jb_lds", "gram_batch_lds")
+            "feat_lds", "fprop_lds", "trunc_lds", "fuse_ok", "jb_lds", "gram_batch_lds", "chol_queue", "lit_ok")
     d = dict(zip(keys, info))
     d.update(rc=rc, why=why.value.decode(), attr={emu.lp_kernel_name(k).decode(): int(attr[k]) for k in range(n)})
     return d
@@ -233,3 +235,193 @@ def test_diagnostics_stay_inside_the_block(emu):
     m = re.search(r"#ifdef RVIO_DBG_CLOCKS\n#define LIT_STAMP\(k\)[^\n]*lit_stamp_fits[^\n]*\n#else\n#define LIT_STAMP\(k\) do \{ \} while \(0\)\n#endif", src)
     assert m, "LIT_STAMP must be empty in the shipping build and bounded in the instrumented one"
     assert len(re.findall(r"#define LIT_STAMP", src)) == 2
+
+
+# ---------------------------------------------------------------- update_forms(): the kernels of ONE update, by clone count
+CHOL = ("none", "role", "queue")
+GRAM = ("reduce", "batch4", "batch6")
+TPROD = ("none", "gemm", "gemm_lds")
+SOLVE = ("none", "small", "s9_1_4", "s9_2_3", "s9_2_3_pre", "split", "solve7", "solve6_1", "solve6_2", "solve6_3")
+DX = ("inside", "kernel", "roles")
+JOSEPH = ("batch", "lds", "lds_pair", "tile", "strips")
+LDS_SLOTS = ("gram_lds", "lit_lds", "tprod_lds", "solve_lds", "ug_lds", "fin_lds")
+FORM_BATCHES = (1, 3, 8, 128)
+
+
+def forms(emu, statics, ml, batch, n, pre, whole, combined, lit=1, F=200):
+    out = (C.c_long * emu.lp_forms_len())()
+    assert emu.lp_forms(ml, F, batch, statics, n, int(pre), int(whole), int(combined), int(lit), out) == 0
+    v = list(out)
+    d = dict(chol=CHOL[v[0]], gram=GRAM[v[1]], gram_grid=v[2], gram_finish=v[3], lit_batch=v[4], tprod=TPROD[v[5]], tprod_grid=v[6], solve=SOLVE[v[7]],
+             split_nt=v[8], own_chol=v[9], dx=DX[v[10]], joseph=JOSEPH[v[11]], grid=tuple(v[12:16]), role_wgs=v[16])
+    for i, slot in enumerate(LDS_SLOTS):   # (bytes, the kernel whose limit covers them | None)
+        k = v[18 + 2 * i]
+        d[slot] = (v[17 + 2 * i], emu.lp_kernel_name(k).decode() if k >= 0 else None)
+    return d
+
+
+def trunc_lds_doubles(ml):
+    m = 6 * ((ml + 1) // 2 - 1)
+    return m * (m | 1) + m + 8
+
+
+def expected_forms(ml, B, n, pre, whole, combined, lit):
+    """the rules as the launch functions of rvio_hip.hip held them before update_forms() (propagate_dev, update_local_dev, launch_solve,
+    launch_ug_final, update_global_dev, augment_compose_dev), written out: NOT computed through launch_plan.h"""
+    c6m, c6 = 6 * (ml - 1), 6 * n
+    ldh, dd = c6m + 1, 24 + c6
+    nt = (dd + 15) // 16
+    npair = nt * (nt + 1) // 2
+    e = dict(split_nt=0, own_chol=0, role_wgs=0, tprod_grid=0, lit_batch=0, gram_grid=1, gram_finish=0, dx="inside", chol="none", tprod="none")
+    kern = dict.fromkeys(LDS_SLOTS)
+    # share reduction
+    gram_batch_fits = B > 1 and 8 * max(c6m * ldh, trunc_lds_doubles(ml)) <= 64 * 1024
+    if B >= 128 and combined and gram_batch_fits:
+        e["gram"] = "batch4" if c6m <= 63 else "batch6"
+        kern["gram_lds"] = "gram_reduce_batch_kernel<4>" if c6m <= 63 else "gram_reduce_batch_kernel<6>"
+        e["lit_batch"] = int(lit)
+        if lit:
+            kern["lit_lds"] = "lit_batch_kernel"
+    else:
+        chunk = 64 if B == 1 else 256
+        e.update(gram="reduce", gram_grid=max(1, min(1024, (c6 * ldh + chunk - 1) // chunk)), gram_finish=int(combined))
+        kern["gram_lds"] = "gram_reduce_kernel"
+    if B == 1:
+        NT = 4 if c6m <= 64 else 6 if c6m <= 96 else 8 if c6m <= 128 else 12
+        if NT <= 6 and n >= 1:
+            e["chol"] = "role"
+        if 96 < c6m <= 192 and n >= 1:
+            e["chol"] = "queue"
+        if NT == 4:
+            e["solve"] = "small" if pre else "s9_1_4"
+            e["dx"] = "roles" if pre and whole else "inside"
+            if pre:
+                kern["solve_lds"] = "solve9_small_kernel"
+        elif NT == 6:
+            e["solve"] = "s9_2_3_pre" if pre else "s9_2_3"
+            e["dx"] = "roles" if whole else "inside"
+        else:
+            e.update(solve="split", split_nt=NT, own_chol=int(not pre), dx="roles" if whole and c6 > 64 else "kernel")
+        if whole and c6 <= 60:
+            e.update(joseph="lds", grid=(npair, 0, 0, 0))
+            kern["ug_lds"] = "joseph_lds_kernel"
+        elif c6 <= 64:
+            e.update(joseph="lds_pair", grid=(nt, (npair + 3) // 4, 0, 0))
+            kern["ug_lds"], kern["fin_lds"] = "ug_lds_kernel", "final_lds_kernel"
+        else:
+            c6t = (c6 + 15) // 16
+            e.update(joseph="tile", grid=((nt * c6t + 3) // 4, (nt * c6t + 3) // 4, (nt * nt + 3) // 4, npair))
+    else:
+        if c6m > 126:
+            e["solve"] = "solve7"
+        else:
+            v = 1 if c6m <= 60 else 2 if c6m <= 96 else 3
+            e["solve"] = "solve6_%d" % v
+            kern["solve_lds"] = ("solve6_kernel<1, 8, 8>", "solve6_kernel<2, 12, 8>", "solve6_kernel<2, 16, 8>")[v - 1]
+            if B >= 128 and c6m <= 64:
+                e["tprod"] = "gemm_lds"
+                kern["tprod_lds"] = "gemm_T_lds_kernel"
+            else:
+                e.update(tprod="gemm", tprod_grid=(c6 + 31) // 32)
+        if B >= 128 and c6m <= 60 and whole:
+            e.update(joseph="batch", grid=(1, 0, 0, 0))
+            kern["ug_lds"] = "joseph_batch_kernel"
+        else:
+            e.update(joseph="strips", grid=((dd + 15) // 16, (npair + 3) // 4, 0, 0))
+            kern["ug_lds"] = "ug_kernel"
+    if e["dx"] == "roles":
+        e["role_wgs"] = (dd + 23) // 24
+    return e, kern
+
+
+def test_update_forms_for_every_window_and_clone_count(emu, statics, static_lds):
+    seen = {k: set() for k in ("chol", "gram", "tprod", "solve", "dx", "joseph", "split", "lds_kernel")}
+    for B in FORM_BATCHES:
+        for ml in range(3, 33):
+            p = evaluate(emu, statics, ml, 200, B)
+            assert p["rc"] == 0 and p["lit_ok"] == 1
+            for n in range(0, ml):
+                c6, dd = 6 * n, 24 + 6 * n
+                for pre in (0, 1):
+                    for whole in (0, 1):
+                        for combined in (0, 1):
+                            f = forms(emu, statics, ml, B, n, pre, whole, combined)
+                            at = (B, ml, n, pre, whole, combined)
+                            # c. the parent's rules, both sides of every threshold (every n of every window is visited)
+                            e, kern = expected_forms(ml, B, n, pre, whole, combined, 1)
+                            for k, v in e.items():
+                                assert f[k] == v, (at, k, f[k], v)
+                            # a. roles only in a whole update, only where the Joseph launch has them, (24 + 6n + 23) / 24 of them
+                            if f["dx"] == "roles":
+                                assert whole and f["joseph"] in ("lds", "tile") and f["role_wgs"] == (dd + 23) // 24, at
+                            else:
+                                assert f["role_wgs"] == 0, at
+                            assert not (whole and f["joseph"] == "lds_pair"), at      # (no window has 60 < 6n <= 64)
+                            # b. every launch with dynamic LDS: bytes within the limit create_impl sets for the kernel it is budgeted under, which fits a CU
+                            for slot in LDS_SLOTS:
+                                nbytes, k = f[slot]
+                                assert k == kern[slot], (at, slot, k, kern[slot])
+                                if k is None:
+                                    assert nbytes == 0, (at, slot)
+                                    continue
+                                assert nbytes > 0 or (k == "gemm_T_lds_kernel" and n == 0), (at, slot)
+                                assert nbytes <= p["attr"][k] and p["attr"][k] + static_lds[k] <= LIMIT, (at, slot, nbytes, p["attr"][k])
+                                seen["lds_kernel"].add(k)
+                            # ... and the sizes the kernel files fix are used inside the windows they were fixed for
+                            if f["joseph"] == "lds":
+                                assert c6 <= 60 and f["ug_lds"][0] == (3 * 60 * 61 + 8 * 16 * 61 + 16) * 8, at
+                            if f["joseph"] == "lds_pair":
+                                assert c6 <= 64 and f["ug_lds"][0] == (2 * 64 * 65 + 88 * 65 + 2 * 16 * 65) * 8 and f["fin_lds"][0] == (3 * 88 * 65 + 4 * 16 * 17) * 8, at
+                            if f["tprod"] == "gemm_lds":
+                                assert f["tprod_lds"][0] == 2 * c6 * (c6 + 1) * 8 <= 2 * 64 * 65 * 8, at
+                            if B < 128:
+                                assert f["gram"] == "reduce" and f["tprod"] != "gemm_lds" and f["joseph"] != "batch", at
+                            for k in ("chol", "gram", "tprod", "solve", "dx", "joseph"):
+                                seen[k].add(f[k])
+                            if f["solve"] == "split":
+                                seen["split"].add((f["split_nt"], f["own_chol"]))
+                        # d. sharded or not, one instance launches the same kernels: only the reduction's `finish` differs
+                        if B == 1:
+                            fa, fb = forms(emu, statics, ml, B, n, pre, whole, 1), forms(emu, statics, ml, B, n, pre, whole, 0)
+                            assert (fa.pop("gram_finish"), fb.pop("gram_finish")) == (1, 0) and fa == fb, (ml, n, pre, whole)
+    # every form was visited
+    assert seen["chol"] == set(CHOL) and seen["gram"] == set(GRAM) and seen["tprod"] == set(TPROD) and seen["dx"] == set(DX) and seen["joseph"] == set(JOSEPH)
+    assert seen["solve"] == set(SOLVE) - {"none"}
+    assert seen["split"] == {(8, 0), (8, 1), (12, 0), (12, 1)}
+    assert seen["lds_kernel"] == {"gram_reduce_kernel", "gram_reduce_batch_kernel<4>", "gram_reduce_batch_kernel<6>", "lit_batch_kernel", "gemm_T_lds_kernel",
+                                  "solve9_small_kernel", "solve6_kernel<1, 8, 8>", "solve6_kernel<2, 12, 8>", "solve6_kernel<2, 16, 8>", "joseph_batch_kernel",
+                                  "ug_kernel", "ug_lds_kernel", "final_lds_kernel", "joseph_lds_kernel"}
+
+
+def test_update_form_thresholds(emu, statics):
+    """single points on both sides of each threshold, as numbers (the sweep above checks the rule; this pins where it falls)"""
+    def f1(ml, n, pre=1, whole=1, combined=1, B=1, lit=1):
+        return forms(emu, statics, ml, B, n, pre, whole, combined, lit)
+    # NT = 4 (6n_max <= 60), 6 (66..96), 8 (102..126), 12 (132..186)
+    assert f1(11, 10)["solve"] == "small" and f1(11, 10, pre=0)["solve"] == "s9_1_4" and f1(11, 10, pre=0)["dx"] == "inside"
+    assert f1(11, 10)["dx"] == "roles" and f1(11, 10, whole=0)["dx"] == "inside"
+    assert f1(12, 11)["solve"] == "s9_2_3_pre" and f1(17, 16, pre=0)["solve"] == "s9_2_3" and f1(18, 17)["solve"] == "split"
+    assert (f1(18, 17)["split_nt"], f1(22, 21)["split_nt"], f1(23, 22)["split_nt"], f1(32, 31)["split_nt"]) == (8, 8, 12, 12)
+    assert f1(18, 17)["own_chol"] == 0 and f1(18, 17, pre=0)["own_chol"] == 1
+    # the split solve's dx: its own launch while the window holds <= 10 clones (6n <= 64), roles from 11 on; always its own launch in a timed stage
+    assert f1(18, 10)["dx"] == "kernel" and f1(18, 11)["dx"] == "roles" and f1(18, 11, whole=0)["dx"] == "kernel"
+    # Joseph, one instance: 6n = 60 | 66
+    assert f1(13, 10)["joseph"] == "lds" and f1(13, 11)["joseph"] == "tile" and f1(13, 10, whole=0)["joseph"] == "lds_pair" and f1(13, 11, whole=0)["joseph"] == "tile"
+    assert f1(13, 10)["grid"][0] == 21 and f1(13, 10)["role_wgs"] == 4 and f1(13, 11)["role_wgs"] == 4 and f1(13, 12)["role_wgs"] == 4 and f1(17, 16)["role_wgs"] == 5
+    # the Cholesky role
+    assert [f1(ml, 1)["chol"] for ml in (3, 11, 12, 17, 18, 32)] == ["role", "role", "role", "role", "queue", "queue"]
+    assert f1(11, 0)["chol"] == "none" and f1(18, 0)["chol"] == "none" and f1(11, 5, B=128)["chol"] == "none"
+    # the reduction's grid: ceil(6n ldh / 64), at least 1, at most 1024
+    assert (f1(11, 0)["gram_grid"], f1(11, 10)["gram_grid"], f1(32, 31)["gram_grid"]) == (1, 58, 544)
+    assert f1(11, 10, B=8)["gram_grid"] == 15 and f1(11, 10, B=3)["gram"] == "reduce"
+    # batches: the [A|b]-in-LDS reduction up to 6n_max = 90 (4 x 4 tiles up to 60), for >= 128 unsharded instances
+    assert [f1(ml, 2, B=128)["gram"] for ml in (11, 12, 16, 17)] == ["batch4", "batch6", "batch6", "reduce"]
+    assert f1(11, 2, B=128, combined=0)["gram"] == "reduce" and f1(11, 2, B=8)["gram"] == "reduce"
+    assert f1(11, 2, B=128)["lit_batch"] == 1 and f1(11, 2, B=128, lit=0)["lit_batch"] == 0 and f1(17, 2, B=128)["lit_batch"] == 0
+    # T product: in LDS up to 6n_max = 60 (<= 64), its own grid beyond, none behind solve7 (6n_max >= 132) and for one instance
+    assert [f1(ml, 2, B=128)["tprod"] for ml in (11, 12, 22, 23)] == ["gemm_lds", "gemm", "gemm", "none"] and f1(11, 2, B=8)["tprod"] == "gemm"
+    assert f1(12, 11, B=128)["tprod_grid"] == 3 and f1(11, 10)["tprod"] == "none"
+    assert [f1(ml, 2, B=8)["solve"] for ml in (11, 12, 17, 18, 22, 23)] == ["solve6_1", "solve6_2", "solve6_2", "solve6_3", "solve6_3", "solve7"]
+    # Joseph, batches
+    assert f1(11, 10, B=128)["joseph"] == "batch" and f1(12, 10, B=128)["joseph"] == "strips" and f1(11, 10, B=128, whole=0)["joseph"] == "strips"
+    assert f1(11, 10, B=8)["joseph"] == "strips" and f1(11, 10, B=8)["grid"][:2] == ((24 + 60 + 15) // 16, (6 * 7 // 2 + 3) // 4)
