@@ -249,10 +249,19 @@ int System::MonoVIO(PoseLine* pose) {
     // (any number of samples: a gap of a few dropped images is integrated in one go as upstream does, PreIntegrator.cc:96-97; beyond
     // RVIO_HIP_MAX_IMU = 192 the library grows its staging once)
     if (image.width != s_.cfg.width || image.height != s_.cfg.height) { err_ = "image size does not match Camera.width/height"; return -1; }
-    to_gray(&image, s_.is_rgb != 0);                   // Tracker.cc:182-196
+    // "Convert to gray scale" (Tracker.cc:182-196) runs on the device: the handle is told what a pixel is — once, and again only when the channel
+    // count of the stream changes — and takes the interleaved bytes as they are (to_gray below is the host form of the same arithmetic)
+    if (image.channels != pix_ch_) {
+        if (image.channels != 1 && image.channels != 3 && image.channels != 4) { err_ = "images of 1, 3 or 4 channels are supported"; return -1; }
+        const int fmt = image.channels == 1 ? RVIO_PIX_MONO8 : image.channels == 3 ? (s_.is_rgb ? RVIO_PIX_RGB8 : RVIO_PIX_BGR8) : (s_.is_rgb ? RVIO_PIX_RGBA8 : RVIO_PIX_BGRA8);
+        if (rvio_hip_set_image_format(h_, fmt) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+        pix_ch_ = image.channels;
+    }
+    const int row_bytes = image.width * image.channels;
+    if (image.px.size() < (size_t)row_bytes * image.height) { err_ = "image holds fewer bytes than width x height x channels"; return -1; }
     // the timed body of MonoVIO (System.cc:253-367): track -> propagate -> update -> augment -> compose
     if (!rec_) {
-        if (rvio_hip_frame(h_, image.px.data(), image.width, pi, m, nullptr, 0) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+        if (rvio_hip_frame(h_, image.px.data(), row_bytes, pi, m, nullptr, 0) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
         if (pose) {
             pose->t = image.t;
             if (rvio_hip_get_pose(h_, pose->p, pose->q) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
@@ -264,7 +273,7 @@ int System::MonoVIO(PoseLine* pose) {
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     auto fail = [&] { err_ = rvio_hip_last_error(h_); return -1; };
     const double t1 = now();
-    if (rvio_hip_track(h_, image.px.data(), image.width, pi, m, nullptr, 0) != RVIO_OK || rvio_hip_sync(h_) != RVIO_OK) return fail();   // System.cc:258
+    if (rvio_hip_track(h_, image.px.data(), row_bytes, pi, m, nullptr, 0) != RVIO_OK || rvio_hip_sync(h_) != RVIO_OK) return fail();   // System.cc:258
     const double t2 = now();
     int do_update = 0, do_augment = 0;
     if (rvio_hip_frame_plan(h_, &do_update, &do_augment) != RVIO_OK) return fail();

@@ -34,6 +34,8 @@ struct ImageData {        // InputBuffer.h:53-63 (cv::Mat -> packed bytes, `chan
 };
 // Tracker::track's "Convert to gray scale" (Tracker.cc:182-196): cvtColor CV_RGB2GRAY / CV_BGR2GRAY (3 channels) or the RGBA / BGRA forms
 // (4 channels, alpha ignored) on 8-bit data = OpenCV's fixed-point  (R 4899 + G 9617 + B 1868 + 8192) >> 14.  In place; 1 channel: no-op.
+// The host form of what the library does on the device (rvio_hip_set_image_format: System::MonoVIO hands colour images over as they are);
+// kept for callers that want the gray image itself (rvio_replay --check-image).
 void to_gray(ImageData* im, bool is_rgb);
 
 struct Settings {
@@ -104,6 +106,7 @@ private:
     double wm_[3] = {0, 0, 0}, am_[3] = {0, 0, 0};
     int n_imu_ = 0, n_img_ = 0;
     bool rec_ = false;
+    int pix_ch_ = 1;              // channels of the image format the handle was last told (rvio_hip_set_image_format)
     void* f_pose_ = nullptr;      // std::ofstream* (kept out of the header)
     void* f_time_ = nullptr;
     void* f_lm_ = nullptr;        // std::ofstream* of record_landmarks_to

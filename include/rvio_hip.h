@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at) */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -162,7 +162,7 @@ int rvio_hip_update(rvio_hip* h, const rvio_tracks* tracks);
 int rvio_hip_augment_compose(rvio_hip* h, int do_augment);
 
 /* --- visual front end ------------------------------------------------------ */
-/* Tracker::track (Tracker.h:50, call site System.cc:258) on a W x H u8 image.
+/* Tracker::track (Tracker.h:50, call site System.cc:258) on a W x H u8 image (interleaved colour pixels: rvio_hip_set_image_format).
  * `cand`/`n_cand` are the detector's corner list for this frame, i.e. the
  * output of FeatureDetector::DetectWithSubPix (FeatureDetector.cc:55-75; the
  * detector itself is outside the hot path); the grid-based
@@ -188,6 +188,27 @@ int rvio_hip_track_points(rvio_hip* h, const float* tracked_xy, const unsigned c
  * detector's last result out: refined corners, the corners before cornerSubPix and the
  * min-eigenvalue map (W*H floats); each pointer may be NULL. */
 int rvio_hip_get_corners(rvio_hip* h, int32_t* n, float* xy, float* raw_xy, float* eig);
+
+/* Pixel format of the images handed to the image entry points: "Convert to gray scale" at the head of Tracker::track
+ * (Tracker.cc:182-196: cvtColor with CV_RGB2GRAY / CV_BGR2GRAY for three channels, CV_RGBA2GRAY / CV_BGRA2GRAY for four, chosen by
+ * Camera.RGB) on the device.  OpenCV's 8-bit fixed-point form: Y = (R * 4899 + G * 9617 + B * 1868 + 8192) >> 14; alpha is ignored. */
+typedef enum rvio_pixel_format {
+    RVIO_PIX_MONO8 = 0,   /* default: one byte per pixel, nothing is converted */
+    RVIO_PIX_RGB8 = 1,    /* three bytes per pixel, R first (Camera.RGB: 1) */
+    RVIO_PIX_BGR8 = 2,    /* three bytes per pixel, B first (Camera.RGB: 0) */
+    RVIO_PIX_RGBA8 = 3,   /* four bytes per pixel, R first */
+    RVIO_PIX_BGRA8 = 4    /* four bytes per pixel, B first */
+} rvio_pixel_format;
+/* Off (RVIO_PIX_MONO8) by default: such a handle allocates and launches what it did before these two entry points existed.  With a colour
+ * format `img` / `d_img` / `d_imgs` of rvio_hip_track, _track_dev, _frame, _frame_dev, _frame_begin_dev, _frame_sharded_dev and
+ * _frame_batch_dev are interleaved pixels; `stride` (and `img_stride`) stay in BYTES, and stride < width * channels is RVIO_ERR_INVALID.
+ * One more launch converts the image at the head of the frame's image chain (in front of CLAHE; with the equaliser off in front of the
+ * detector and the pyramid) into a gray buffer of the handle, which every later stage reads; the host-buffer entry points stage the
+ * caller's colour bytes, no pixel is converted on the host.  A change of format drains the handle and takes effect from the next image
+ * handed over; the first colour format allocates the gray buffers.  RVIO_ERR_INVALID: unknown format; RVIO_ERR_UNSUPPORTED: a colour format
+ * on a batch handle created without its front end (it takes no image).  get: the current format, RVIO_ERR_INVALID for a NULL handle. */
+int rvio_hip_set_image_format(rvio_hip* h, int format);
+int rvio_hip_get_image_format(const rvio_hip* h);
 
 /* Copy the device-resident mvFeatTypesForUpdate / mvlFeatMeasForUpdate out.
  * Buffers must hold ceil(n_features/2) entries (x max_track_len x 2 floats). */
@@ -338,12 +359,14 @@ int rvio_hip_debug_tracked(rvio_hip* h, int n, float* xy, float* un_xy);
  * 7 = U/G/P1 + Joseph form as this handle launches them for an update (one instance, 6n <= 60: one fused kernel),
  * 8 = the per-feature kernel with propagate fused in, as the pipelined frame launches it, 9 = the detector's selection kernel,
  * 10 = the landmark cloud kernel on the hand-over table and per-feature results of the last update (into buffers of its own: the
- * cloud rvio_hip_get_landmarks returns is left alone; RVIO_ERR_UNSUPPORTED unless the cloud was enabled). */
+ * cloud rvio_hip_get_landmarks returns is left alone; RVIO_ERR_UNSUPPORTED unless the cloud was enabled),
+ * 11 = the gray conversion of the last image handed over, in the form the frame launched (a _dev entry point: the caller's image must
+ * still be alive; RVIO_ERR_UNSUPPORTED without a colour format or before the first image). */
 int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us);
 /* Test hook against results that depend on LEFT-OVER state (scratch in HBM, LDS contents, stale hand-over entries).  Drains every stream of
  * the handle, then: what & 1 fills the filter's scratch and the spare state / covariance buffer with 0xff bytes (NaN); & 2 rewrites the LDS
- * of the whole chip with NaN patterns; & 4 does the same to the Tracker -> Updater hand-over tables (types / len / meas; counts stay) and the
- * tracker's per-frame scratch; & 8 sets the device-side error bit 4 ("a stage counter timed out", RVIO_ERR_STATE at the next
+ * of the whole chip with NaN patterns; & 4 does the same to the Tracker -> Updater hand-over tables (types / len / meas; counts stay), the
+ * tracker's per-frame scratch and the gray buffers of a colour handle; & 8 sets the device-side error bit 4 ("a stage counter timed out", RVIO_ERR_STATE at the next
  * rvio_hip_sync) so that the recovery path — rvio_hip_initialize — can be exercised.  1 | 2 | 4 between the frames of a sequence must not
  * change any result. */
 int rvio_hip_debug_poison(rvio_hip* h, int what);

@@ -9,6 +9,10 @@ import numpy as np
 
 ABI_VERSION = 6
 
+# rvio_pixel_format (rvio_hip_set_image_format): what the image entry points are handed
+RVIO_PIX_MONO8, RVIO_PIX_RGB8, RVIO_PIX_BGR8, RVIO_PIX_RGBA8, RVIO_PIX_BGRA8 = 0, 1, 2, 3, 4
+PIX_CHANNELS = {RVIO_PIX_MONO8: 1, RVIO_PIX_RGB8: 3, RVIO_PIX_BGR8: 3, RVIO_PIX_RGBA8: 4, RVIO_PIX_BGRA8: 4}
+
 
 class rvio_config(C.Structure):
     _fields_ = [

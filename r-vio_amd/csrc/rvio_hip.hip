@@ -29,6 +29,7 @@
 #include "klt16.hip"
 #include "clahe.hip"
 #include "detector.hip"
+#include "gray.hip"        // Tracker.cc:182-196 for colour cameras (rvio_hip_set_image_format)
 #pragma clang fp contract(fast)
 
 struct rvio_hip {
@@ -166,6 +167,14 @@ struct rvio_hip {
     bool lm_on = false;
     int lm_frame = -1;       // nImageCountAfterInit when the update behind the cloud was enqueued, -1: none since create / initialize
     LmOut lm = {nullptr, nullptr, nullptr, nullptr, 0};
+    // colour input (rvio_hip_set_image_format): the gray images every stage behind gray_kernel reads instead of the caller's.  Allocated with the
+    // first colour format, outside the slab (a mono handle keeps its memory layout), instance stride W * H; four in rotation like d_eq2[] (see
+    // build_pyramid_dev for who reads a slot last)
+    int pix_fmt = RVIO_PIX_MONO8, pix_ch = 1;
+    uint8_t* d_gray[4] = {nullptr, nullptr, nullptr, nullptr};
+    int gray_slot = 0;
+    size_t img_cap = 0;              // bytes of one staged image the host-side staging (d_img, hb_img[]) holds: W * H, grows with the channel count
+    const uint8_t* gray_src = nullptr; int gray_stride = 0; size_t gray_bs = 0;   // the last image handed over (rvio_hip_debug_time_kernel(11))
 };
 
 // ---------------------------------------------------------------- environment surface of the library: three variables of its own, plus the profiler's.
@@ -484,6 +493,7 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
     h->wide_px = batch >= 8;   // (tests switch it through rvio_hip_debug_kernel_forms: the two forms must agree bit for bit)
     fill_devcfg(cfg, &h->dc);
     const DevCfg& d = h->dc;
+    h->img_cap = (size_t)d.W * d.H;
     if (d.grid_cols * d.grid_rows < 1) { delete h; return RVIO_ERR_INVALID; }
     *out = h;   // returned even on allocation failure so last_error is readable
     HIPCHK(h, hipSetDevice(device));
@@ -1269,6 +1279,62 @@ static int detect_dev(rvio_hip* h, const uint8_t* img, int stride, size_t src_bs
     return RVIO_OK;
 }
 
+// ------------------------------------------------------------------ gray conversion (Tracker.cc:182-196)
+static int pix_channels(int fmt) { return fmt == RVIO_PIX_MONO8 ? 1 : (fmt == RVIO_PIX_RGB8 || fmt == RVIO_PIX_BGR8) ? 3 : 4; }
+// B interleaved images -> B packed gray images (instance stride W * H) on `st`.  The wide form wherever every row of every instance starts
+// on a dword and holds whole groups of four pixels, the byte form otherwise (same bits: gray.h)
+static void launch_gray(rvio_hip* h, const uint8_t* src, int stride, size_t src_bs, uint8_t* dst, hipStream_t st) {
+    const DevCfg& d = h->dc;
+    const int bgr = (h->pix_fmt == RVIO_PIX_BGR8 || h->pix_fmt == RVIO_PIX_BGRA8) ? 1 : 0;
+    const size_t bs = (size_t)d.W * d.H;
+    const dim3 g((d.W + 255) / 256, (d.H + 3) / 4, h->batch), b(256);
+    const bool wide = d.W % 4 == 0 && stride % 4 == 0 && ((uintptr_t)src & 3) == 0 && src_bs % 4 == 0;
+    if (h->pix_ch == 3) {
+        if (wide) hipLaunchKernelGGL(gray_kernel4<3>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs);
+        else hipLaunchKernelGGL(gray_kernel<3>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs);
+    } else {
+        if (wide) hipLaunchKernelGGL(gray_kernel4<4>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs);
+        else hipLaunchKernelGGL(gray_kernel<4>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs);
+    }
+}
+int rvio_hip_get_image_format(const rvio_hip* h) { return h ? h->pix_fmt : RVIO_ERR_INVALID; }
+int rvio_hip_set_image_format(rvio_hip* h, int format) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (format < RVIO_PIX_MONO8 || format > RVIO_PIX_BGRA8) { h->err = "unknown image format"; return RVIO_ERR_INVALID; }
+    if (format != RVIO_PIX_MONO8 && !h->front_end) { h->err = "this batch handle was created without its front end: it takes no image"; return RVIO_ERR_UNSUPPORTED; }
+    if (format == h->pix_fmt) return RVIO_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    { const int rc = drain_all(h); if (rc != RVIO_OK) return rc; }   // nothing in flight reads the staging or a gray buffer any more
+    const int ch = pix_channels(format);
+    const size_t npx = (size_t)h->dc.W * h->dc.H;
+    if (ch > 1 && !h->d_gray[0]) {   // first colour format: the gray buffers of every instance
+        uint8_t* p = nullptr;
+        HIPCHK(h, hipMalloc((void**)&p, 4 * npx * (size_t)h->batch));
+        h->allocs.push_back(p);
+        HIPCHK(h, hipMemsetAsync(p, 0, 4 * npx * (size_t)h->batch, h->stream));
+        for (int k = 0; k < 4; ++k) h->d_gray[k] = p + (size_t)k * npx * h->batch;
+    }
+    if (npx * ch > h->img_cap) {     // the staging of the host-buffer entry points grows to the interleaved image (the old blocks stay where they were, as in ensure_imu_capacity)
+        auto grow = [&](uint8_t** q) -> int {
+            void* n = nullptr;
+            HIPCHK(h, hipMalloc(&n, npx * ch));
+            h->allocs.push_back(n);
+            *q = (uint8_t*)n;
+            return RVIO_OK;
+        };
+        int rc = grow(&h->d_img);
+        for (int k = 0; k < 2 && rc == RVIO_OK; ++k) if (h->hb_img[k]) rc = grow(&h->hb_img[k]);
+        if (rc != RVIO_OK) return rc;
+        h->img_cap = npx * ch;
+    }
+    if (ch != h->pix_ch)             // rvio_hip_frame lays the pinned ring out again (the image slot changes size)
+        for (int k = 0; k < rvio_hip::kPin; ++k) if (h->pin[k]) { hipHostFree(h->pin[k]); h->pin[k] = nullptr; }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->pix_fmt = format; h->pix_ch = ch;
+    h->gray_src = nullptr;
+    return RVIO_OK;
+}
+
 // ------------------------------------------------------------------ T1..T6
 static int build_pyramid_dev(rvio_hip* h, const uint8_t* d_img, int stride, int b) {
     const DevCfg& d = h->dc;
@@ -1290,6 +1356,23 @@ static int build_pyramid_dev(rvio_hip* h, const uint8_t* d_img, int stride, int 
     // without the equaliser (the detector alone rewrites det_xy2[k % 3] / det_nout[k % 3], which bookkeep_b(k-3) reads).
     if (h->runahead && h->frame_no >= 3)
         HIPCHK(h, hipStreamWaitEvent(image_stream(h), h->evT[(h->frame_no - 3) & 3], 0));
+    if (h->pix_ch > 1) {   // colour camera: "Convert to gray scale", Tracker.cc:182-196 — the first launch of the image chain; every later reader sees the handle's gray image
+        // Four gray buffers in rotation (one step per image, so slot k % 4 on the whole-frame paths).  Who read slot k % 4 last — gray image k-4:
+        //  * equaliser on: CLAHE(k-4), nobody else (the equalised image is what detector, pyramid and KLT see);
+        //  * equaliser off: detector(k-4) incl. cornerSubPix on its image stream, pyramid(k-4) (which copies it into level 0) on the side stream.
+        // Run-ahead mode (single and batch handles, device polls or RVIO_PARANOID's stream events alike): book-keeping(k-4) followed pyramid(k-4) /
+        // KLT(k-4) on the side stream and its refill half waited for the corners of detector(k-4); book-keeping(k-3) followed it there, and the wait
+        // above puts this launch behind book-keeping(k-3) — the wait that protects equalised image k % 4 and corner list k % 3 covers the gray slot
+        // too (with two image chains, or one at long windows, CLAHE(k-4) also sits earlier on this very stream).
+        // Every other mode — RVIO_NO_RUNAHEAD, a caller-side corner list, the per-stage calls — has ONE image stream (h->ts) for every frame: CLAHE /
+        // detector of earlier images are earlier on it, and a pyramid that ran on the side stream was joined back into it in front of that
+        // image's book-keeping (post_klt_dev).  No wait of its own anywhere.
+        h->gray_slot = (h->gray_slot + 1) % 4;
+        uint8_t* g = h->d_gray[h->gray_slot];
+        h->gray_src = d_img; h->gray_stride = stride; h->gray_bs = src_bs;
+        launch_gray(h, d_img, stride, src_bs, g, image_stream(h));
+        d_img = g; stride = d.W; src_bs = (size_t)d.W * d.H;
+    }
     if (h->cfg.enable_equalizer) {   // clahe->apply(im, im), Tracker.cc:198-202
         // The equalised image of frame k doubles as level 0 of frame k's pyramid (no copy), so it lives until the KLT of frame k+1 has
         // matched against it: four buffers in rotation (like the pyramids, and three corner lists).  Slot k % 4 was last read by KLT(k-3)
@@ -1457,21 +1540,22 @@ static int track_dev_impl(rvio_hip* h, const uint8_t* d_img, int stride, const r
     return rc;
 }
 int rvio_hip_track_dev(rvio_hip* h, const uint8_t* d_img, int stride, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand) {
-    if (!h || !d_img || m < 0 || n_cand < 0) return RVIO_ERR_INVALID;
+    if (!h || !d_img || m < 0 || n_cand < 0 || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     return track_dev_impl(h, d_img, stride, d_imu, m, d_cand, n_cand);
 }
 
 int rvio_hip_track(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* imu, int m, const float* cand_xy, int n_cand) {
-    if (!h || !img || (!imu && m > 0) || m < 0 || n_cand < 0 || stride < h->dc.W) return RVIO_ERR_INVALID;
+    if (!h || !img || (!imu && m > 0) || m < 0 || n_cand < 0 || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     { const int rcg = ensure_imu_capacity(h, m); if (rcg != RVIO_OK) return rcg; }
     const int nc = std::min(n_cand, h->dc.F);
-    HIPCHK(h, hipMemcpy2DAsync(h->d_img, h->dc.W, img, stride, h->dc.W, h->dc.H, hipMemcpyHostToDevice, h->stream));
+    const int rowb = h->dc.W * h->pix_ch;   // bytes of an image row (interleaved pixels with a colour format)
+    HIPCHK(h, hipMemcpy2DAsync(h->d_img, rowb, img, stride, rowb, h->dc.H, hipMemcpyHostToDevice, h->stream));
     if (m > 0) HIPCHK(h, hipMemcpyAsync(h->d_imu, imu, sizeof(rvio_imu) * m, hipMemcpyHostToDevice, h->stream));
     if (nc > 0 && cand_xy) HIPCHK(h, hipMemcpyAsync(h->d_cand, cand_xy, sizeof(float) * 2 * nc, hipMemcpyHostToDevice, h->stream));
-    return rvio_hip_track_dev(h, h->d_img, h->dc.W, h->d_imu, m, cand_xy ? h->d_cand : nullptr, cand_xy ? nc : 0);
+    return rvio_hip_track_dev(h, h->d_img, rowb, h->d_imu, m, cand_xy ? h->d_cand : nullptr, cand_xy ? nc : 0);
 }
 
 // direct-track mode: the caller supplies the KLT result
@@ -1694,7 +1778,7 @@ static int frame_dev_impl(rvio_hip* h, const uint8_t* d_img, int stride, const r
     return rc;
 }
 int rvio_hip_frame_dev(rvio_hip* h, const uint8_t* d_img, int stride, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand) {
-    if (!h || !d_img) return RVIO_ERR_INVALID;
+    if (!h || !d_img || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     return frame_dev_impl(h, d_img, stride, d_imu, m, d_cand, n_cand, false);
@@ -1703,7 +1787,7 @@ int rvio_hip_frame_dev(rvio_hip* h, const uint8_t* d_img, int stride, const rvio
 // row stride `stride`), d_imu[B][imu_stride] (0: shared).  Same pipelined body as rvio_hip_frame_dev, every launch with gridDim.z = B;
 // corners always come from the device detector.
 int rvio_hip_frame_batch_dev(rvio_hip* h, const uint8_t* d_imgs, int stride, size_t img_stride, const rvio_imu* d_imu, int imu_stride, int m) {
-    if (!h || !d_imgs || (!d_imu && m > 0) || imu_stride < 0 || (imu_stride > 0 && imu_stride < m) || stride < h->dc.W) return RVIO_ERR_INVALID;
+    if (!h || !d_imgs || (!d_imu && m > 0) || imu_stride < 0 || (imu_stride > 0 && imu_stride < m) || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
     if (!h->front_end) { h->err = "this batch handle was created without its front end"; return RVIO_ERR_UNSUPPORTED; }
     if (h->batch > 1 && img_stride < (size_t)stride * h->dc.H) return RVIO_ERR_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
@@ -1718,7 +1802,7 @@ int rvio_hip_frame_batch_dev(rvio_hip* h, const uint8_t* d_imgs, int stride, siz
 //       all on the filter stream (rvio_hip_stream) ...
 //   frame_end         closes the frame (hand-over buffer released for frame k+2)
 int rvio_hip_frame_begin_dev(rvio_hip* h, const uint8_t* d_img, int stride, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand) {
-    if (!h || !d_img) return RVIO_ERR_INVALID;
+    if (!h || !d_img || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     return frame_dev_impl(h, d_img, stride, d_imu, m, d_cand, n_cand, false, /*begin_only=*/true);
@@ -1757,7 +1841,7 @@ static nccl_allgather_fn resolve_allgather(std::string* why) {
 // ncclAllGather from the loaded process image; a caller may hand in the entry point itself (same signature).
 int rvio_hip_frame_sharded_dev(rvio_hip* h, const uint8_t* d_img, int stride, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand,
                                int rank, int world, void* comm, void* allgather) {
-    if (!h || !d_img || world < 1 || rank < 0 || rank >= world || (!comm && world > 1)) return RVIO_ERR_INVALID;
+    if (!h || !d_img || world < 1 || rank < 0 || rank >= world || (!comm && world > 1) || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     if (comm) h->extra_queues = true;   // the collective brings queues of its own: more than the four this handle's chains own (see the pyramid poll, build_pyramid_dev)
@@ -1793,20 +1877,20 @@ int rvio_hip_frame_sharded_dev(rvio_hip* h, const uint8_t* d_img, int stride, co
 // The three H2D copies go to the tracker stream into staging buffers double-buffered by frame parity, so they overlap
 // the previous frame's filter work like the tracker kernels do.
 int rvio_hip_frame(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* imu, int m, const float* cand_xy, int n_cand) {
-    if (!h || !img || (!imu && m > 0) || m < 0 || n_cand < 0 || stride < h->dc.W) return RVIO_ERR_INVALID;
+    if (!h || !img || (!imu && m > 0) || m < 0 || n_cand < 0 || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     { const int rcg = ensure_imu_capacity(h, m); if (rcg != RVIO_OK) return rcg; }
     const int nc = cand_xy ? std::min(n_cand, h->dc.F) : 0;   // cand_xy == NULL: device detector
     if (!h->hb_img[0])
         for (int k = 0; k < 2; ++k) {
-            DALLOC(h, h->hb_img[k], (size_t)h->dc.W * h->dc.H);
+            DALLOC(h, h->hb_img[k], h->img_cap);
             DALLOC(h, h->hb_imu[k], (size_t)h->imu_cap);
             if (k == 1) for (int q = 2; q <= rvio_hip::kHand; ++q) DALLOC(h, h->hb_imu[q], (size_t)h->imu_cap);
             DALLOC(h, h->hb_cand[k], (size_t)2 * h->dc.F);
             HIPCHK(h, hipStreamSynchronize(h->stream));   // DALLOC clears on the filter stream
         }
-    const size_t npx = (size_t)h->dc.W * h->dc.H;
+    const size_t rowb = (size_t)h->dc.W * h->pix_ch, npx = rowb * h->dc.H;   // bytes of a row / of the image as staged (interleaved pixels with a colour format: gray_kernel converts them on the device)
     if (!h->pin[0]) {
         h->pin_img = 0; h->pin_imu = (npx + 255) & ~(size_t)255;
         const size_t pin_cand = h->pin_imu + ((sizeof(rvio_imu) * (size_t)h->imu_cap + 255) & ~(size_t)255);
@@ -1823,8 +1907,8 @@ int rvio_hip_frame(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* 
     const size_t pin_cand = h->pin_imu + ((sizeof(rvio_imu) * (size_t)h->imu_cap + 255) & ~(size_t)255);
     HIPCHK(h, hipEventSynchronize(h->evPin[ps]));   // the copies issued from this slot three frames ago are done (no-op before its first use)
     HIPCHK(h, hipEventSynchronize(h->evPin2[ps]));
-    if (stride == h->dc.W) std::memcpy(pp, img, npx);   // (a continuous cv::Mat: one copy)
-    else for (int y = 0; y < h->dc.H; ++y) std::memcpy(pp + (size_t)y * h->dc.W, img + (size_t)y * stride, (size_t)h->dc.W);
+    if ((size_t)stride == rowb) std::memcpy(pp, img, npx);   // (a continuous cv::Mat: one copy)
+    else for (int y = 0; y < h->dc.H; ++y) std::memcpy(pp + (size_t)y * rowb, img + (size_t)y * stride, rowb);
     if (m > 0) std::memcpy(pp + h->pin_imu, imu, sizeof(rvio_imu) * m);
     if (nc > 0) std::memcpy(pp + pin_cand, cand_xy, sizeof(float) * 2 * nc);
     const bool ra = !cand_xy && !no_runahead();
@@ -1843,6 +1927,8 @@ int rvio_hip_frame(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* 
         // The image goes to the stream of this frame's image chain (image_stream: tracker stream / fourth stream by parity).  hb_img[b]
         // was last read by frame k-2: its CLAHE / detector (same stream, earlier) and — without the equaliser — its pyramid on the side
         // stream, which book-keeping(k-2) followed.
+        // (A colour format: hb_img[b] holds the interleaved pixels and has ONE reader, gray_kernel(k-2), the first launch of that frame's image
+        // chain — on this very stream, since k-2 and k share their image chain with one or two chains in flight; the wait below is then more than needed.)
         hipStream_t is = image_stream_of(h, (int)(h->frame_no % h->plan.n_ic));
         if (h->frame_no >= 2) HIPCHK(h, hipStreamWaitEvent(is, h->evT[(h->frame_no - 2) & 3], 0));
         HIPCHK(h, hipMemcpyAsync(h->hb_img[b], pp, npx, hipMemcpyHostToDevice, is));
@@ -1862,7 +1948,7 @@ int rvio_hip_frame(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* 
         HIPCHK(h, hipStreamSynchronize(h->stream_t));
         if (h->stream_c) HIPCHK(h, hipStreamSynchronize(h->stream_c));
     }
-    return frame_dev_impl(h, h->hb_img[b], h->dc.W, h->hb_imu[imu_slot], m, cand_xy ? h->hb_cand[b] : nullptr, nc, true);
+    return frame_dev_impl(h, h->hb_img[b], (int)rowb, h->hb_imu[imu_slot], m, cand_xy ? h->hb_cand[b] : nullptr, nc, true);
 }
 // direct-track variant of the whole frame (host inputs)
 int rvio_hip_frame_points(rvio_hip* h, const float* tracked_xy, const unsigned char* status, int n_pts,
@@ -1987,6 +2073,7 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
         HIPCHK(h, hipMemcpyAsync(bx, h->x[h->cur], sizeof(double) * d.xdmax, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(bP, h->P[h->cur], sizeof(double) * d.dmax * d.dmax, hipMemcpyDeviceToDevice, h->stream));
     }
+    if (which == 11 && (h->pix_ch < 2 || !h->gray_src)) { h->err = "no colour image has been handed over (rvio_hip_set_image_format)"; return RVIO_ERR_UNSUPPORTED; }
     LmOut lmt = {nullptr, nullptr, nullptr, nullptr, 0};
     if (which == 10) {   // (into buffers of its own: the getter's cloud stays the last update's)
         if (!h->lm.count) return RVIO_ERR_UNSUPPORTED;
@@ -2036,6 +2123,8 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
             const DetDev q = [&] { DetDev v = h->dets[h->det_set_last]; v.xy = h->det_xy2[h->dslot]; v.n_out = h->det_nout + h->dslot; return v; }();
             const uint8_t* im = h->pyr[h->pyr_cur].img[0];   // level 0 of the current pyramid = the image the detector saw
             launch_subpix(h, q, im, d.W, (size_t)0, 1u, 0, h->stream);
+        } else if (which == 11) {   // gray_kernel on the last image handed over, in the form the frame launched, into the slot it wrote (the same values again)
+            launch_gray(h, h->gray_src, h->gray_stride, h->gray_bs, h->d_gray[h->gray_slot], h->stream);
         } else return RVIO_ERR_INVALID;
     }
     HIPCHK(h, hipEventRecord(e1, h->stream));
@@ -2112,6 +2201,7 @@ int rvio_hip_debug_poison(rvio_hip* h, int what) {
         HIPCHK(h, fill(t.tmp_feats, sizeof(float) * 2 * d.F)); HIPCHK(h, fill(t.tmp_un, sizeof(float) * 2 * d.F)); HIPCHK(h, fill(t.tmp_slot, sizeof(int) * d.F));
         HIPCHK(h, fill(t.cand_acc, sizeof(int) * d.F));
         HIPCHK(h, fill(t.cell_pts, sizeof(float) * (size_t)d.grid_cols * d.grid_rows * 2 * d.F * 2));
+        if (h->d_gray[0]) HIPCHK(h, hipMemsetAsync(h->d_gray[0], 0xff, 4 * (size_t)d.W * d.H * h->batch, h->stream));   // (one allocation: every slot of every instance)
     }
     if (what & 2) {
         static bool attr = false;

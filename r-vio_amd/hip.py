@@ -25,6 +25,7 @@ SYMBOLS = [
     "rvio_hip_create_batch", "rvio_hip_batch_size", "rvio_hip_set_state_at", "rvio_hip_get_state_at", "rvio_hip_frame_tracks_dev",
     "rvio_hip_frame_batch_dev", "rvio_hip_get_tracker_points_at", "rvio_hip_frame_sharded_dev", "rvio_hip_debug_poison", "rvio_hip_debug_stall", "rvio_hip_debug_noise", "rvio_hip_debug_kernel_forms",
     "rvio_hip_set_landmarks", "rvio_hip_get_landmarks", "rvio_hip_get_landmarks_at",
+    "rvio_hip_set_image_format", "rvio_hip_get_image_format",
 ]
 
 _LIB = None
@@ -87,6 +88,7 @@ class RvioHip:
             raise RvioHipError("rvio_hip_create failed: rc=%d %s" % (rc, msg))
         self.nmax = cfg.max_track_len - 1
         self.Fu = abi.fu(cfg)
+        self.channels = 1
 
     def close(self):
         if getattr(self, "h", None):
@@ -207,11 +209,26 @@ class RvioHip:
         cand = np.ascontiguousarray(cand, np.float32)
         return _p(cand, fp), len(cand), cand
 
-    @staticmethod
-    def _img(img):
-        """(array, row stride in bytes): a row-strided uint8 view is handed over as it is (cv::Mat::step), anything else is packed"""
+    # ---- colour cameras (Tracker.cc:182-196)
+    def set_image_format(self, fmt):
+        """abi.RVIO_PIX_*: what img / d_img of the image entry points hold from the next image on (colour: interleaved pixels, converted on the device)"""
+        self._ck(self.L.rvio_hip_set_image_format(self.h, int(fmt)), "set_image_format")
+        self.channels = abi.PIX_CHANNELS[int(fmt)]
+
+    def image_format(self):
+        return int(self.L.rvio_hip_get_image_format(self.h))
+
+    def _img(self, img):
+        """(array, row stride in bytes): a row-strided uint8 view is handed over as it is (cv::Mat::step), anything else is packed.
+        H x W with the mono format, H x W x 3|4 (interleaved) with a colour format: any other shape is refused"""
         img = np.asarray(img)
-        if img.dtype != np.uint8 or img.ndim != 2 or img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+        ch = self.channels
+        if img.ndim != (2 if ch == 1 else 3) or (ch > 1 and img.shape[2] != ch):
+            raise RvioHipError("image of shape %s handed to a handle whose format has %d byte(s) per pixel (set_image_format)" % (img.shape, ch))
+        if ch == 1:
+            if img.dtype != np.uint8 or img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+                img = np.ascontiguousarray(img, np.uint8)
+        elif img.dtype != np.uint8 or img.strides[2] != 1 or img.strides[1] != ch or img.strides[0] < img.shape[1] * ch:
             img = np.ascontiguousarray(img, np.uint8)
         return img, img.strides[0]
 
@@ -377,13 +394,13 @@ class RvioHip:
         return xy, un
 
     def time_kernel(self, which, iters=20):
-        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection, 10 the landmark cloud kernel (HIP events, handle stream)"""
+        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection, 10 the landmark cloud kernel, 11 the gray conversion of the last colour image (HIP events, handle stream)"""
         us = C.c_float(0)
         self._ck(self.L.rvio_hip_debug_time_kernel(self.h, int(which), int(iters), C.byref(us)), "debug_time_kernel")
         return float(us.value)
 
     def poison(self, what=7):
-        """drain the handle, then overwrite left-over state: 1 filter scratch, 2 LDS of the chip, 4 hand-over tables + tracker scratch, 8 set error bit 4"""
+        """drain the handle, then overwrite left-over state: 1 filter scratch, 2 LDS of the chip, 4 hand-over tables + tracker scratch + gray buffers, 8 set error bit 4"""
         self._ck(self.L.rvio_hip_debug_poison(self.h, int(what)), "debug_poison")
 
     def stall(self, which, usec):
