@@ -155,6 +155,8 @@ System::System(const Settings& s, int device) : s_(s) {
     }
 }
 System::~System() {
+    if (f_od_ && h_) (void)flush_odometry();
+    delete static_cast<std::ofstream*>(f_od_);
     delete static_cast<std::ofstream*>(f_pose_);
     delete static_cast<std::ofstream*>(f_time_);
     delete static_cast<std::ofstream*>(f_lm_);
@@ -182,6 +184,57 @@ int System::write_landmarks(double t) {
     lm_last_ = frame;
     auto& f = *static_cast<std::ofstream*>(f_lm_);
     f << format_landmarks(t, frame, n, lm_feat_.data(), lm_pw_.data(), lm_pr_.data());
+    f.flush();
+    return 0;
+}
+
+bool System::record_odometry_to(const std::string& path, int ring) {
+    if (!h_) return false;
+    if (ring < 1) { err_ = "the odometry ring holds at least one record"; return false; }
+    auto* f = new std::ofstream(path, std::ofstream::out);
+    if (!*f) { delete f; err_ = "cannot write " + path; return false; }
+    if (f_od_) (void)flush_odometry();
+    if (rvio_hip_set_odometry(h_, ring) != RVIO_OK) { delete f; err_ = rvio_hip_last_error(h_); return false; }
+    delete static_cast<std::ofstream*>(f_od_);
+    f_od_ = f;
+    od_ring_ = ring;
+    od_buf_.assign((size_t)ring, rvio_odom{});
+    // (records written from here on are read from here on; the handle's seq restarts with rvio_hip_initialize, which MonoVIO issues before
+    // its first frame, and with a new ring)
+    od_seq_ = od_read_ = ready_ ? last_seq() : 0;
+    od_t_.clear();
+    return true;
+}
+
+// seq of the newest record the handle has written (0: none)
+long long System::last_seq() {
+    rvio_odom r{};
+    int64_t s = 0;
+    return rvio_hip_get_odometry_all(h_, &r, &s) == RVIO_OK ? (long long)s : 0;
+}
+
+// behind a frame handed to the filter: its timestamp joins the queue; the ring is read when half of it is outstanding
+int System::note_odometry(double t) {
+    ++od_seq_;
+    od_t_.push_back(t);
+    if (od_seq_ - od_read_ >= std::max(1, od_ring_ / 2)) return flush_odometry();
+    return 0;
+}
+
+int System::flush_odometry() {
+    if (!f_od_ || od_seq_ == od_read_) return 0;
+    int32_t n = 0;
+    if (rvio_hip_get_odometry(h_, 0, od_read_ + 1, od_ring_, od_buf_.data(), &n) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+    auto& f = *static_cast<std::ofstream*>(f_od_);
+    for (int i = 0; i < n; ++i) {
+        const rvio_odom& r = od_buf_[(size_t)i];
+        // (a record the ring no longer holds was overwritten before it was read: its timestamp goes with it)
+        while (od_read_ + 1 < r.seq && !od_t_.empty()) { od_t_.pop_front(); ++od_read_; }
+        if (od_t_.empty()) break;
+        f << format_odometry(od_t_.front(), r);
+        od_t_.pop_front();
+        od_read_ = r.seq;
+    }
     f.flush();
     return 0;
 }
@@ -267,6 +320,7 @@ int System::MonoVIO(PoseLine* pose) {
             if (rvio_hip_get_pose(h_, pose->p, pose->q) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
         }
         if (f_lm_ && write_landmarks(image.t) < 0) return -1;
+        if (f_od_ && note_odometry(image.t) < 0) return -1;
         return 1;
     }
     // INI.RecordOutputs: the same body stage by stage with the host waiting behind each, t1 / t2 / t3 taken where upstream takes them
@@ -289,6 +343,7 @@ int System::MonoVIO(PoseLine* pose) {
     fp << format_pose(pl); fp.flush();
     ft << format_time_cost(n_img_, t2 - t1, t3 - t2); ft.flush();
     if (f_lm_ && write_landmarks(image.t) < 0) return -1;
+    if (f_od_ && note_odometry(image.t) < 0) return -1;
     if (pose) *pose = pl;
     return 1;
 }
@@ -303,6 +358,20 @@ std::string format_pose(const PoseLine& p) {
     char buf[512];
     std::snprintf(buf, sizeof buf, "%.19g %.19g %.19g %.19g %.19g %.19g %.19g %.19g\n", p.t, p.p[0], p.p[1], p.p[2], p.q[0], p.q[1], p.q[2], p.q[3]);
     return buf;
+}
+
+std::string format_odometry(double t, const rvio_odom& r) {
+    char buf[64];
+    std::string out;
+    auto add = [&](double v) { std::snprintf(buf, sizeof buf, " %.19g", v); out += buf; };
+    std::snprintf(buf, sizeof buf, "%.19g %lld", t, (long long)r.seq);
+    out = buf;
+    for (double v : r.p) add(v);
+    for (double v : r.q) add(v);
+    for (double v : r.v) add(v);
+    for (double v : r.pose_cov) add(v);
+    out += "\n";
+    return out;
 }
 
 std::string format_landmarks(double t, int frame, int n, const int32_t* feat, const double* p_world, const double* p_r) {

@@ -89,6 +89,12 @@ public:
     // handle (rvio_hip_set_landmarks) and appends the cloud to `path` behind every frame whose update stamp is new — one line per point,
     // format_landmarks.  The settings file has no key for it.
     bool record_landmarks_to(const std::string& path);
+    // What the reference publishes every frame as nav_msgs::Odometry and appends to its nav_msgs::Path (System.cc:402-434): enables the
+    // handle's odometry ring (rvio_hip_set_odometry, `ring` records) and keeps the image timestamps by seq on the host.  The ring is read
+    // with ONE rvio_hip_get_odometry whenever ring / 2 frames are outstanding and once more at the end (flush_odometry, also run by the
+    // destructor): the pipelined frame is no longer drained once per image for its pose.  One line per frame, format_odometry.
+    bool record_odometry_to(const std::string& path, int ring = 256);
+    int flush_odometry();         // 0, or -1 on a library error (error())
     // the handle's sticky device-side flags (rvio_frame_info.reserved[0]: 1 singular pivot, 2 a track dropped, 4 a stage counter timed out,
     // 8 a non-positive gate pivot; 0 = none) — waits for everything in flight, so a replay reads it once at its end.  -1: the query failed.
     int device_flags();
@@ -114,6 +120,13 @@ private:
     std::vector<int32_t> lm_feat_;
     std::vector<double> lm_pr_, lm_pw_;
     int write_landmarks(double t);
+    void* f_od_ = nullptr;        // std::ofstream* of record_odometry_to
+    int od_ring_ = 0;
+    long long od_seq_ = 0, od_read_ = 0;   // frames handed to the filter since initialisation / records written to the file
+    std::deque<double> od_t_;     // image timestamps of the records not yet written: front() belongs to seq od_read_ + 1
+    std::vector<rvio_odom> od_buf_;
+    int note_odometry(double t);
+    long long last_seq();
 };
 
 // 8-bit PNG (non-interlaced; gray, RGB or RGBA: channels in file order = RGB) or binary PGM / PPM (P5 / P6, maxval 255)
@@ -129,6 +142,8 @@ bool read_asl(const std::string& root, AslDataset* out, std::string* err);
 std::string format_pose(const PoseLine& p);               // one line of stamped_pose_ests.dat, setprecision(19)
 // the points of one cloud (rvio_hip_get_landmarks), one line each: t frame feat xw yw zw xr yr zr (world frame, then {Rk} as published), %.19g
 std::string format_landmarks(double t, int frame, int n, const int32_t* feat, const double* p_world, const double* p_r);
+// one record of the odometry ring: t seq px py pz qx qy qz qw vx vy vz c00 ... c55 (pose_cov row by row), %.19g
+std::string format_odometry(double t, const rvio_odom& r);
 std::string format_time_cost(int n_img, double track_ms, double filter_ms);   // one line of time_cost.dat (System.cc:376-378)
 
 }  // namespace rvio

@@ -3,7 +3,9 @@
 // the two ROS callbacks would (every image triggers System::MonoVIO, rvio_mono.cc:78-80); poses are written in the format
 // of stamped_pose_ests.dat (System.cc:369-374).
 //
-//   rvio_replay <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--landmarks FILE]
+//   rvio_replay <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--landmarks FILE] [--odometry FILE [--odometry-ring N]]
+//                                        --odometry: pose, velocity and pose covariance of every frame, read in bulk from the handle's ring of N
+//                                        records (default 256; System::record_odometry_to); without <poses_out.dat> no frame is drained for its pose
 //                                        --landmarks: Updater::update's landmark cloud behind every updating frame (System::record_landmarks_to)
 //   rvio_replay --check-settings <settings.yaml>        print the parsed configuration (no GPU needed)
 //   rvio_replay --check-dataset <asl_root>              print what the dataset reader found (no GPU needed)
@@ -80,6 +82,8 @@ struct PassOptions {
     long dump_at = -1;               // filtered-frame index behind which the streams are drained and the hand-over is read back
     long max_frames = -1;
     const char* landmarks = nullptr; // System::record_landmarks_to
+    const char* odometry = nullptr;  // System::record_odometry_to
+    int odometry_ring = 256;
 };
 static bool dump_frame(System& sys, const rvio_config& c, FrameDump* d) {
     rvio_hip* h = sys.handle();
@@ -98,6 +102,7 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
     System sys(s, device);
     if (!sys.ok()) { *err = sys.error(); return 1; }
     if (o.landmarks && !sys.record_landmarks_to(o.landmarks)) { *err = sys.error(); return 1; }
+    if (o.odometry && !sys.record_odometry_to(o.odometry, o.odometry_ring)) { *err = sys.error(); return 1; }
     size_t ii = 0;
     long n_images = 0, n_frames = 0;
     double t_filter = 0;
@@ -130,6 +135,7 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
             if (o.dump_at >= 0 && n_frames > o.dump_at) break;
         }
     }
+    if (sys.flush_odometry() < 0) { *err = sys.error(); return 1; }
     if (ms_per_call) *ms_per_call = n_images ? 1e3 * t_filter / n_images : 0.0;
     if (flags) *flags = sys.device_flags();
     return 0;
@@ -207,12 +213,13 @@ int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "--check-image")) return check_image(argv[2], !(argc >= 4 && !std::strcmp(argv[3], "--bgr")));
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--record-dir DIR] [--record]\n"
-                             "          [--landmarks FILE] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n", argv[0]);
+                             "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n", argv[0]);
         return 2;
     }
     const char* out_path = nullptr;
     int device = 0; long max_frames = -1, stall_seed = -1;
     const char* landmarks = nullptr;
+    const char* odometry = nullptr; int odometry_ring = 256;
     const char* record_dir = "."; bool force_record = false, sync_every = false, self = false; int noise_wgs = 0;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -223,6 +230,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--stall-seed") && i + 1 < argc) stall_seed = std::atol(argv[++i]);   // sleeping kernels on random streams (A/B of the ordering)
         else if (!std::strcmp(argv[i], "--noise") && i + 1 < argc) noise_wgs = std::atoi(argv[++i]);         // a loaded chip beside the replay (A/B of timing inside kernels)
         else if (!std::strcmp(argv[i], "--landmarks") && i + 1 < argc) landmarks = argv[++i];   // the landmark cloud of every update, one point per line
+        else if (!std::strcmp(argv[i], "--odometry") && i + 1 < argc) odometry = argv[++i];     // one line per frame: pose, velocity, pose covariance (read in bulk from the ring)
+        else if (!std::strcmp(argv[i], "--odometry-ring") && i + 1 < argc) odometry_ring = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--selfcheck")) self = true;
         else out_path = argv[i];
     }
@@ -235,7 +244,7 @@ int main(int argc, char** argv) {
     if (self) return selfcheck(s, d, device, max_frames, stall_seed, noise_wgs);
     if (sync_every || stall_seed >= 0 || noise_wgs > 0) {   // the plain replay with one of the two A/B pacings
         std::vector<PoseLine> poses; double ms = 0; int flags = 0;
-        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks;
+        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring;
         if (run_pass(s, d, device, o, &poses, nullptr, &ms, &flags, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
         if (out_path) { std::ofstream out(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } for (const PoseLine& p : poses) out << format_pose(p); }
         std::fprintf(stderr, "rvio_replay: %zu filtered frames, %.3f ms per MonoVIO call, device flags %d\n", poses.size(), ms, flags);
@@ -245,6 +254,7 @@ int main(int argc, char** argv) {
     if (!sys.ok()) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (!sys.record_to(record_dir, force_record)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (landmarks && !sys.record_landmarks_to(landmarks)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
+    if (odometry && !sys.record_odometry_to(odometry, odometry_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     std::ofstream out;
     if (out_path) { out.open(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } }
 
@@ -262,11 +272,13 @@ int main(int argc, char** argv) {
         ++n_images;
         PoseLine p;
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = sys.MonoVIO(&p);
+        // (with --odometry and no pose file nobody reads the pose line: the frame stays in flight, the ring is read in bulk)
+        const int rc = sys.MonoVIO(odometry && !out.is_open() ? nullptr : &p);
         t_filter += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (rc < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
         if (rc == 1) { ++n_frames; if (out.is_open()) out << format_pose(p); }
     }
+    if (sys.flush_odometry() < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     std::fprintf(stderr, "rvio_replay: %ld images, %ld filtered frames, %.3f ms per MonoVIO call (host wall clock, pose read-back included)\n",
                  n_images, n_frames, n_images ? 1e3 * t_filter / n_images : 0.0);
     // anything only the device saw (0 in every test and bench run): said out loud, the poses above are suspect if it is not 0

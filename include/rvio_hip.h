@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -293,6 +293,44 @@ int rvio_hip_frame_points(rvio_hip* h, const float* tracked_xy, const unsigned c
 int rvio_hip_get_frame_info(rvio_hip* h, rvio_frame_info* info);
 /* pose line of stamped_pose_ests.dat (System.cc:371-374): pGk(3), qkG(4) */
 int rvio_hip_get_pose(rvio_hip* h, double p[3], double q[4]);
+/* the same line of one instance of a batch handle (RVIO_ERR_INVALID out of range); on a plain handle instance 0 is rvio_hip_get_pose */
+int rvio_hip_get_pose_at(rvio_hip* h, int instance, double p[3], double q[4]);
+
+/* --- odometry ring ----------------------------------------------------------- */
+/* What System::MonoVIO publishes every frame — nav_msgs::Odometry (System.cc:402-418: the pose, twist.linear = vk) and the pose appended to
+ * nav_msgs::Path (System.cc:420-434) — kept on the device: one record per instance and frame, written by a kernel of its own behind the
+ * augmentation / composition stage of EVERY path (stage by stage, rvio_hip_frame*, rvio_hip_frame_points, the sharded frame, batch handles),
+ * into a ring that is read back in bulk.  A host that wants every pose no longer drains the pipeline once per frame. */
+typedef struct rvio_odom {          /* 464 bytes, no padding */
+    int64_t seq;        /* 1, 2, ...: augment/compose stages of this handle recorded since create / rvio_hip_initialize (stages run while the ring is off are not counted) */
+    int32_t img_count;  /* nImageCountAfterInit of that frame (System.cc:251) */
+    int32_t n_clones;   /* nCloneStates after the frame */
+    int32_t reserved[2];/* 0 */
+    double p[3];        /* pGk, System.cc:341  -- the bits rvio_hip_get_pose returns */
+    double q[4];        /* qkG, System.cc:339  -- the same */
+    double v[3];        /* vk,  System.cc:331,414-416 = x[17..19] behind the frame */
+    double pose_cov[36];/* row-major 6x6, order (x, y, z, rot X, rot Y, rot Z): nav_msgs/Odometry pose.covariance (the reference leaves it at zero).
+                         * With R = R(qkG), p = pkG = x[4..6] and P6 = P[0..5][0..5] behind the frame — the error (dth, dp) of the reference's
+                         * injection (Updater.cc:549-566), R_true ~ (I - [dth x]) R — and the published pGk = -R^T p, R_wb = R^T, world-frame rotation
+                         * error phi (R_wb,true ~ (I + [phi x]) R_wb):  J = [ R^T [p x], -R^T ; R^T, 0 ],  pose_cov = (C + C^T) / 2, C = J P6 J^T.
+                         * Exactly symmetric. */
+    double vel_cov[9];  /* row-major P[15..17][15..17] behind the frame, copied */
+} rvio_odom;
+/* capacity = records kept per instance: 0 = off (the default: such a handle allocates and launches what it did before these entry points
+ * existed), 1 .. 65536.  The first enable drains the handle and allocates the ring, outside the filter slab, laid out
+ * ring[(seq - 1) % capacity][instance] (one frame's records of all instances are contiguous); another capacity drains, reallocates and
+ * empties the ring (seq restarts at 1); 0 stops the launches and keeps the ring and its records; the same capacity again resumes.
+ * rvio_hip_initialize empties the ring, rvio_hip_set_state leaves it alone.  RVIO_ERR_INVALID: NULL handle, capacity outside 0 .. 65536;
+ * RVIO_ERR_UNSUPPORTED (rvio_hip_last_error names the size): capacity x instances x 464 bytes exceeds 1 GiB. */
+int rvio_hip_set_odometry(rvio_hip* h, int capacity);
+/* The records of one instance with seq in [max(first_seq, newest - capacity + 1, 1), newest], oldest first, at most max_n; *n = how many
+ * (0 with RVIO_OK when none qualifies).  `newest` is counted on the host: nothing is read from the device to learn it.  Waits for the
+ * filter stream only, like rvio_hip_get_pose.  RVIO_ERR_STATE: the ring was never enabled; RVIO_ERR_INVALID: instance out of range,
+ * max_n < 0, out == NULL with max_n > 0. */
+int rvio_hip_get_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_odom* out, int32_t* n);
+/* The newest record of every instance in one copy: out holds rvio_hip_batch_size records, *seq their seq (0 before the first frame: nothing
+ * is copied).  Where all robots of a fleet are, per frame, without one state read-back per instance. */
+int rvio_hip_get_odometry_all(rvio_hip* h, rvio_odom* out /* batch records */, int64_t* seq);
 
 /* --- feature-sharded updater (no reference counterpart) ------ */
 /* Stage A: per-feature build + gate on the features f with f % world == rank,
@@ -361,7 +399,9 @@ int rvio_hip_debug_tracked(rvio_hip* h, int n, float* xy, float* un_xy);
  * 10 = the landmark cloud kernel on the hand-over table and per-feature results of the last update (into buffers of its own: the
  * cloud rvio_hip_get_landmarks returns is left alone; RVIO_ERR_UNSUPPORTED unless the cloud was enabled),
  * 11 = the gray conversion of the last image handed over, in the form the frame launched (a _dev entry point: the caller's image must
- * still be alive; RVIO_ERR_UNSUPPORTED without a colour format or before the first image). */
+ * still be alive; RVIO_ERR_UNSUPPORTED without a colour format or before the first image),
+ * 12 = the odometry record kernel on the composed state the last frame left, all instances (into a slot of its own: the ring is left alone;
+ * RVIO_ERR_UNSUPPORTED unless the ring was enabled). */
 int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us);
 /* Test hook against results that depend on LEFT-OVER state (scratch in HBM, LDS contents, stale hand-over entries).  Drains every stream of
  * the handle, then: what & 1 fills the filter's scratch and the spare state / covariance buffer with 0xff bytes (NaN); & 2 rewrites the LDS

@@ -62,6 +62,46 @@ class rvio_frame_info(C.Structure):
         return d
 
 
+class rvio_odom(C.Structure):
+    _fields_ = [("seq", C.c_int64), ("img_count", C.c_int32), ("n_clones", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("p", C.c_double * 3), ("q", C.c_double * 4), ("v", C.c_double * 3), ("pose_cov", C.c_double * 36), ("vel_cov", C.c_double * 9)]
+
+
+ODOM_DTYPE = np.dtype([("seq", "i8"), ("img_count", "i4"), ("n_clones", "i4"), ("reserved", "i4", 2),
+                       ("p", "f8", 3), ("q", "f8", 4), ("v", "f8", 3), ("pose_cov", "f8", (6, 6)), ("vel_cov", "f8", (3, 3))])
+assert ODOM_DTYPE.itemsize == C.sizeof(rvio_odom) == 464
+
+
+def _skew(w):
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def quat_to_rot(q):
+    """QuatToRot (util/Numerics.h:111-120), JPL: I - 2 w [q]x + 2 [q]x^2"""
+    qx = _skew(q[:3])
+    return np.eye(3) - 2.0 * q[3] * qx + 2.0 * (qx @ qx)
+
+
+def odom_pose_jacobian(q, p):
+    """d(published pose error) / d(error state) of the composed state: q = qkG, p = pkG (x[0:4], x[4:7] behind the frame).  Columns: the
+    reference's injected (dth, dp) (Updater.cc:549-566: R_true ~ (I - [dth x]) R); rows: the error of pGk = -R^T p and the world-frame rotation
+    error phi of R_wb = R^T (R_wb,true ~ (I + [phi x]) R_wb)."""
+    R = quat_to_rot(np.asarray(q, float))
+    J = np.zeros((6, 6))
+    J[:3, :3] = R.T @ _skew(np.asarray(p, float))
+    J[:3, 3:] = -R.T
+    J[3:, :3] = R.T
+    return J
+
+
+def odom_pose_cov(x, P):
+    """NumPy mirror of rvio_odom.pose_cov (csrc/odom.hip): (C + C^T) / 2 with C = J P[0:6, 0:6] J^T, order (x, y, z, rot X, rot Y, rot Z)"""
+    x, P = np.asarray(x, float), np.asarray(P, float)
+    J = odom_pose_jacobian(x[0:4], x[4:7])
+    Cm = J @ P[:6, :6] @ J.T
+    return 0.5 * (Cm + Cm.T)
+
+
 # Camera.T_BC0 of config/rvio_euroc.yaml:55-62 (row-major)
 _T_BC0 = [0.0148655429818, -0.999880929698, 0.00414029679422, -0.0216401454975,
           0.999557249008, 0.0149672133247, 0.025715529948, -0.064676986768,

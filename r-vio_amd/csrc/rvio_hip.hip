@@ -23,6 +23,7 @@
 #include "solve7.hip"
 #include "solve9.hip"   // round 5: the solve as blocked SPD factorisations on the matrix cores (one instance; every window up to 6n = 192)
 #include "landmarks.hip"   // Updater::update's landmark cloud (rvio_hip_set_landmarks)
+#include "odom.hip"        // the per-frame odometry record: pose, velocity, covariance (rvio_hip_set_odometry)
 #pragma clang fp contract(off)
 #include "frontend_kernels.hip"
 #include "klt3.hip"
@@ -167,6 +168,12 @@ struct rvio_hip {
     bool lm_on = false;
     int lm_frame = -1;       // nImageCountAfterInit when the update behind the cloud was enqueued, -1: none since create / initialize
     LmOut lm = {nullptr, nullptr, nullptr, nullptr, 0};
+    // odometry ring (odom_kernel behind every augment/compose stage): allocated by rvio_hip_set_odometry, outside the slab (a handle that never
+    // enables it keeps its memory layout and its launches), laid out ring[(seq - 1) % odom_cap][instance]
+    rvio_odom* odom_ring = nullptr;
+    int odom_cap = 0;          // records per instance the ring holds
+    bool odom_on = false;
+    long long odom_seq = 0;    // records written since create / rvio_hip_initialize / the last change of capacity: the newest record's seq
     // colour input (rvio_hip_set_image_format): the gray images every stage behind gray_kernel reads instead of the caller's.  Allocated with the
     // first colour format, outside the slab (a mono handle keeps its memory layout), instance stride W * H; four in rotation like d_eq2[] (see
     // build_pyramid_dev for who reads a slot last)
@@ -600,6 +607,7 @@ void rvio_hip_destroy(rvio_hip* h) {
     if (h->stream) hipStreamSynchronize(h->stream);
     if (h->private_queues) g_private_queue_handles.fetch_sub(1);
     for (void* p : h->allocs) hipFree(p);
+    if (h->odom_ring) hipFree(h->odom_ring);
     for (int k = 0; k < rvio_hip::kPin; ++k) { if (h->pin[k]) hipHostFree(h->pin[k]); if (h->evPin[k]) hipEventDestroy(h->evPin[k]); if (h->evPin2[k]) hipEventDestroy(h->evPin2[k]); }
     if (h->first_mirror) hipHostFree(h->first_mirror);
     if (h->evA) hipEventDestroy(h->evA);
@@ -724,6 +732,7 @@ int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n
     for (int i = 21; i < 24; ++i) D(i, n_imu * dt * std::pow(c.sigma_wa, 2));
     h->img_count = 0;
     h->lm_frame = -1;   // no cloud since initialisation (the enable flag stays)
+    h->odom_seq = 0;    // ... and no odometry record: seq restarts at 1 (the getters read nothing beyond odom_seq)
     // a (re-)initialised filter starts with an empty window: the tracker starts over too (mbIsTheFirstImage, Tracker.cc:88), or its
     // histories would be longer than the window they refer to
     if (h->front_end) {
@@ -1136,6 +1145,63 @@ int rvio_hip_get_landmarks(rvio_hip* h, int32_t* n, int32_t* frame, int32_t* fea
     return rvio_hip_get_landmarks_at(h, 0, n, frame, feat, p_r, p_world);
 }
 
+// ------------------------------------------------------------------ odometry ring (System.cc:402-434)
+// odom_kernel on the composed state of every instance (h->cur already toggled), into `slot` (batch records)
+static void launch_odom(rvio_hip* h, rvio_odom* slot, long long seq) {
+    hipLaunchKernelGGL(odom_kernel, dim3((h->batch + 3) / 4), dim3(256), 0, h->stream, h->batch, h->dc.dmax, (const double*)h->x[h->cur], (const double*)h->P[h->cur],
+                       (const double*)h->d_pose, h->slab_bytes, seq, h->img_count, h->n_clones_host, (unsigned long long*)slot);
+}
+int rvio_hip_set_odometry(rvio_hip* h, int capacity) {
+    if (!h || capacity < 0 || capacity > 65536) return RVIO_ERR_INVALID;
+    if (capacity == 0) { h->odom_on = false; return RVIO_OK; }   // (the launches stop, the ring and its records stay)
+    if (capacity != h->odom_cap) {
+        const size_t bytes = (size_t)capacity * h->batch * sizeof(rvio_odom);
+        if (bytes > ((size_t)1 << 30)) {
+            h->err = "odometry ring of " + std::to_string(capacity) + " x " + std::to_string(h->batch) + " records = " + std::to_string(bytes) + " bytes exceeds 1 GiB";
+            return RVIO_ERR_UNSUPPORTED;
+        }
+        // (first enable or another capacity: with nothing in flight; a new ring is empty)
+        { const int rc = drain_all(h); if (rc != RVIO_OK) return rc; }
+        rvio_odom* p = nullptr;
+        HIPCHK(h, hipMalloc((void**)&p, bytes));
+        if (h->odom_ring) (void)hipFree(h->odom_ring);
+        h->odom_ring = p; h->odom_cap = capacity; h->odom_seq = 0;
+        HIPCHK(h, hipMemsetAsync(p, 0, bytes, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    h->odom_on = true;
+    return RVIO_OK;
+}
+// the filter stream only, like rvio_hip_get_pose: every record is written on it
+int rvio_hip_get_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_odom* out, int32_t* n) {
+    if (!h || instance < 0 || instance >= h->batch || max_n < 0 || (!out && max_n > 0)) return RVIO_ERR_INVALID;
+    if (!h->odom_ring) { h->err = "the odometry ring was never enabled (rvio_hip_set_odometry)"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const long long newest = h->odom_seq, cap = h->odom_cap;
+    const long long lo = std::max<long long>(std::max<long long>(first_seq, newest - cap + 1), 1);
+    const long long cnt = std::max<long long>(0, std::min<long long>(newest - lo + 1, max_n));
+    if (n) *n = (int32_t)cnt;
+    if (cnt == 0) return RVIO_OK;
+    // instance i's records lie batch records apart; the range wraps around the end of the ring at most once
+    const size_t pitch = sizeof(rvio_odom) * h->batch;
+    const long long s0 = (lo - 1) % cap, c0 = std::min(cnt, cap - s0);
+    HIPCHK(h, hipMemcpy2DAsync(out, sizeof(rvio_odom), h->odom_ring + (size_t)s0 * h->batch + instance, pitch, sizeof(rvio_odom), (size_t)c0, hipMemcpyDeviceToHost, h->stream));
+    if (cnt > c0)
+        HIPCHK(h, hipMemcpy2DAsync(out + c0, sizeof(rvio_odom), h->odom_ring + instance, pitch, sizeof(rvio_odom), (size_t)(cnt - c0), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RVIO_OK;
+}
+int rvio_hip_get_odometry_all(rvio_hip* h, rvio_odom* out, int64_t* seq) {
+    if (!h || !out) return RVIO_ERR_INVALID;
+    if (!h->odom_ring) { h->err = "the odometry ring was never enabled (rvio_hip_set_odometry)"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (seq) *seq = h->odom_seq;
+    if (h->odom_seq == 0) return RVIO_OK;
+    HIPCHK(h, hipMemcpyAsync(out, h->odom_ring + (size_t)((h->odom_seq - 1) % h->odom_cap) * h->batch, sizeof(rvio_odom) * h->batch, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RVIO_OK;
+}
+
 // ------------------------------------------------------------------ S1 + S2
 static int augment_compose_dev(rvio_hip* h, int do_augment) {
     const DevCfg& d = h->dc;
@@ -1161,6 +1227,15 @@ static int augment_compose_dev(rvio_hip* h, int do_augment) {
         launch_s9_chol(h, h->plan.solve9_nt, h->n_clones_host, h->P[h->cur], h->stream_l);
         HIPCHK(h, hipEventRecord(h->evL, h->stream_l));
         h->chol_async = true;
+    }
+    // the odometry record of this frame: behind evA (the run-ahead factor above starts when it did before), on the filter stream (whatever waits
+    // for "the filter has finished" through an event waits for the record too; the device-side counter augcomp_kernel2 bumps guards the hand-over
+    // tables, which the record does not read).  It reads x / P / pose as augcomp_kernel2 left them; the next writer of either is the next frame's
+    // propagate, behind it on this stream.
+    if (h->odom_on) {
+        h->odom_seq++;
+        launch_odom(h, h->odom_ring + (size_t)((h->odom_seq - 1) % h->odom_cap) * h->batch, h->odom_seq);
+        HIPCHK(h, hipGetLastError());
     }
     return RVIO_OK;
 }
@@ -1985,6 +2060,17 @@ int rvio_hip_get_pose(rvio_hip* h, double p[3], double q[4]) {
     if (q) for (int i = 0; i < 4; ++i) q[i] = buf[3 + i];
     return RVIO_OK;
 }
+// the same line of one instance of a batch handle: augcomp_kernel2 writes d_pose at the slab stride
+int rvio_hip_get_pose_at(rvio_hip* h, int instance, double p[3], double q[4]) {
+    if (!h || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
+    HIPCHK(h, hipSetDevice(h->device));
+    double buf[8];
+    HIPCHK(h, hipMemcpyAsync(buf, (const char*)h->d_pose + (size_t)instance * h->slab_bytes, sizeof buf, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (p) for (int i = 0; i < 3; ++i) p[i] = buf[i];
+    if (q) for (int i = 0; i < 4; ++i) q[i] = buf[3 + i];
+    return RVIO_OK;
+}
 
 }  // extern "C"
 
@@ -2074,6 +2160,11 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
         HIPCHK(h, hipMemcpyAsync(bP, h->P[h->cur], sizeof(double) * d.dmax * d.dmax, hipMemcpyDeviceToDevice, h->stream));
     }
     if (which == 11 && (h->pix_ch < 2 || !h->gray_src)) { h->err = "no colour image has been handed over (rvio_hip_set_image_format)"; return RVIO_ERR_UNSUPPORTED; }
+    rvio_odom* odt = nullptr;
+    if (which == 12) {   // (into a slot of its own: the ring stays what the frames wrote)
+        if (!h->odom_ring) { h->err = "the odometry ring was never enabled (rvio_hip_set_odometry)"; return RVIO_ERR_UNSUPPORTED; }
+        HIPCHK(h, hipMalloc((void**)&odt, sizeof(rvio_odom) * h->batch));
+    }
     LmOut lmt = {nullptr, nullptr, nullptr, nullptr, 0};
     if (which == 10) {   // (into buffers of its own: the getter's cloud stays the last update's)
         if (!h->lm.count) return RVIO_ERR_UNSUPPORTED;
@@ -2087,6 +2178,9 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
     HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
     HIPCHK(h, hipEventRecord(e0, h->stream));
     for (int it = 0; it < iters; ++it) {
+        if (which == 12) {   // odom_kernel as augment_compose_dev launches it, on the composed state the last frame left
+            launch_odom(h, odt, h->odom_seq);
+        } else
         if (which == 10) {
             // landmark_kernel as the update launches it, on the hand-over table, accept flags and (phi, psi, rho) of the last update; the state
             // buffers are the ones it reads (behind a whole frame: the composed state and xk1k1 — the same arithmetic)
@@ -2141,6 +2235,7 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
     HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
     hipEventDestroy(e0); hipEventDestroy(e1);
     if (bx) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(bx); (void)hipFree(bP); }
+    if (odt) (void)hipFree(odt);   // (the event above has drained the stream)
     if (lmt.count) { h->allocs.pop_back(); (void)hipFree(lmt.count); }   // (lm_alloc pushed it last; the event above has drained the stream)
     *avg_us = ms * 1e3f / iters;
     HIPCHK(h, hipGetLastError());

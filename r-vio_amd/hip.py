@@ -26,6 +26,7 @@ SYMBOLS = [
     "rvio_hip_frame_batch_dev", "rvio_hip_get_tracker_points_at", "rvio_hip_frame_sharded_dev", "rvio_hip_debug_poison", "rvio_hip_debug_stall", "rvio_hip_debug_noise", "rvio_hip_debug_kernel_forms",
     "rvio_hip_set_landmarks", "rvio_hip_get_landmarks", "rvio_hip_get_landmarks_at",
     "rvio_hip_set_image_format", "rvio_hip_get_image_format",
+    "rvio_hip_set_odometry", "rvio_hip_get_odometry", "rvio_hip_get_odometry_all", "rvio_hip_get_pose_at",
 ]
 
 _LIB = None
@@ -394,7 +395,7 @@ class RvioHip:
         return xy, un
 
     def time_kernel(self, which, iters=20):
-        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection, 10 the landmark cloud kernel, 11 the gray conversion of the last colour image (HIP events, handle stream)"""
+        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection, 10 the landmark cloud kernel, 11 the gray conversion of the last colour image, 12 the odometry record kernel (HIP events, handle stream)"""
         us = C.c_float(0)
         self._ck(self.L.rvio_hip_debug_time_kernel(self.h, int(which), int(iters), C.byref(us)), "debug_time_kernel")
         return float(us.value)
@@ -424,3 +425,34 @@ class RvioHip:
         p, q = np.zeros(3), np.zeros(4)
         self._ck(self.L.rvio_hip_get_pose(self.h, _p(p, dp), _p(q, dp)), "get_pose")
         return p, q
+
+    get_pose = pose
+
+    def get_pose_at(self, i):
+        """pose line (pGk, qkG) of instance i of a batch handle"""
+        p, q = np.zeros(3), np.zeros(4)
+        self._ck(self.L.rvio_hip_get_pose_at(self.h, int(i), _p(p, dp), _p(q, dp)), "get_pose_at")
+        return p, q
+
+    # ---- odometry ring (System.cc:402-434)
+    def set_odometry(self, capacity):
+        """keep an rvio_odom record of every frame from the next augment/compose stage on, `capacity` per instance on the device; 0: off"""
+        self._ck(self.L.rvio_hip_set_odometry(self.h, int(capacity)), "set_odometry")
+        if capacity:
+            self._odom_cap = int(capacity)
+
+    def odometry(self, instance=0, first_seq=1, max_n=None):
+        """records of one instance still in the ring with seq >= first_seq, oldest first (at most max_n): a structured array (abi.ODOM_DTYPE)"""
+        cap = getattr(self, "_odom_cap", 0) if max_n is None else int(max_n)
+        out = np.zeros(max(cap, 0), abi.ODOM_DTYPE)
+        n = C.c_int32(0)
+        self._ck(self.L.rvio_hip_get_odometry(self.h, int(instance), C.c_int64(int(first_seq)), cap,
+                                              out.ctypes.data_as(C.POINTER(abi.rvio_odom)) if len(out) else None, C.byref(n)), "get_odometry")
+        return out[: n.value].copy()
+
+    def odometry_all(self):
+        """(seq, the newest record of every instance); seq = 0 and zeroed records before the first frame"""
+        out = np.zeros(self.batch, abi.ODOM_DTYPE)
+        seq = C.c_int64(0)
+        self._ck(self.L.rvio_hip_get_odometry_all(self.h, out.ctypes.data_as(C.POINTER(abi.rvio_odom)), C.byref(seq)), "get_odometry_all")
+        return int(seq.value), out
