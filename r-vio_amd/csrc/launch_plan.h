@@ -12,6 +12,12 @@
 // and the Joseph stage, each as an enum with its grid and, for every launch with dynamic LDS, the byte count and the LpKernel whose limit
 // (plan.attr) covers it.  The launch functions of rvio_hip.hip switch on what it returns and rvio_hip_debug_time_kernel asks it for the forms the
 // frame would get; the same sweep on the CPU checks every (window, n, batch): roles only where the Joseph launch has them, LDS within the limit.
+//
+// The FRONT END of a frame has its decider too: front_forms() behind update_forms().  From the plan, the handle's geometry and what is known about ONE
+// call (piped or per-stage, corner list or device detector, frame number, the environment's two switches, whether the handle's queues are its own) it
+// derives the call's mode (run-ahead, device-side counters, which of the buffers in rotation), every cross-queue wait and signal as a flag, the stream
+// ROLE of every stage, and the form of every kernel — gray, CLAHE, pyramid, detector, cornerSubPix, KLT, RANSAC / book-keeping — with grid, workgroup
+// size and dynamic LDS.  rvio_hip.hip computes that value once per call and passes it down; tests/test_launch_plan.py sweeps it on the CPU.
 #pragma once
 #include <stddef.h>
 
@@ -339,5 +345,267 @@ inline UpdateForms update_forms(const LaunchPlan& p, int batch, int n, bool pre,
         f.joseph = LPJ_STRIPS; f.grid[0] = (dd + 15) / 16; f.grid[1] = (npair + 3) / 4; f.ug_lds = {p.ug_lds, LPK_UG};
     }
     if (f.dx == LPD_ROLES) f.role_wgs = (dd + 23) / 24;
+    return f;
+}
+
+// ---------------------------------------------------------------- the forms of ONE front-end call: mode, synchronisation, stream roles, kernel forms
+// What a front-end call launches, and how its chains are ordered against each other, follows from values known when the call is made: front_forms()
+// is the one place that derives them.  track_dev_impl / frame_dev_impl / rvio_hip_frame (rvio_hip.hip) compute ONE FrontForms per call and hand that
+// value down to every stage; the stages switch on its enums and take grids and LDS from it.  Stream and event OBJECTS stay in rvio_hip.hip
+// (stream_of maps a role to the handle's stream).
+//
+// sizes the front-end kernel files fix: rvio_hip.hip static_asserts each against its definition (detector.hip, clahe.hip, pyr_sep.h)
+#define LP_DET_TW 64              // DET_TW: tile of the detector's fused first pass, columns
+#define LP_DET_FH 16              // DET_FH: ... rows
+#define LP_DET_T 512              // DET_T
+#define LP_DET_SW 60              // DET_SW: strip of the throughput form, columns a wave owns
+#define LP_DET_SH 16              // DET_SH: ... rows it walks
+#define LP_NEIGH_T 1024           // NEIGH_T
+#define LP_NEIGH_BLOCKS 8         // NEIGH_BLOCKS
+#define LP_NEIGH_BLOCKS_WIDE 2    // NEIGH_BLOCKS_WIDE
+#define LP_NEIGH_LDS 53256        // NEIGH_LDS
+#define LP_GREEDY_T 1024          // GREEDY_T
+#define LP_GREEDY_LDS 122896      // GREEDY_LDS
+#define LP_SP_WIN 7               // SP_WIN: the stock cornerSubPix half-window (Tracker.nMinDist = 15)
+#define LP_SP_T 256               // SP_T
+#define LP_SPG_T 256              // SPG_T
+#define LP_SPW_C 16               // SPW_C
+#define LP_PYR_T 256              // PYR_T
+#define LP_CLAHE_LUT_T 1024       // CLAHE_LUT_T
+// dynamic LDS of subpix_wide_kernel for a half-window (detector.hip subpix_wide_lds: the summation grid in two sizes)
+LP_HD inline size_t lp_subpix_wide_lds(int win) {
+    const int G = 2 * win + 1 <= 64 ? 64 : 128;
+    return sizeof(double) * ((size_t)5 * G * (LP_SPW_C + 1) + 5 * G + 8);
+}
+
+// who covers the dynamic LDS of a front-end launch (LpLaunch::kernel) when it is not a kernel of plan.attr
+enum {
+    LPF_NONE = -1,          // the launch has none
+    LPF_DEFAULT = -2,       // no limit is set for the kernel: within the 64 KiB any kernel may ask for (RANSAC's 8 F + 16 <= 32 784 at F <= 4096)
+    LPF_NEIGH = -3,         // LP_NEIGH_LDS   (detector_init sets it)
+    LPF_GREEDY = -4,        // LP_GREEDY_LDS  (detector_init sets it)
+    LPF_SUBPIX_WIDE = -5    // lp_subpix_wide_lds(half-window)   (detector_init sets it)
+};
+struct LpLaunch { int gx = 0, gy = 1, gz = 1, threads = 0; size_t lds = 0; int kernel = LPF_NONE; };   // gx == 0: not launched
+
+enum LpStream {          // the ROLE of a stream in a call; stream_of (rvio_hip.hip) maps it to one of the handle's four
+    LPR_FILTER,          //   the filter stream: every launch of a per-stage call that is not forked to the side stream
+    LPR_TRACKER,         //   the tracker stream of the pipelined whole-frame path
+    LPR_SIDE,            //   the side stream: pyramid / KLT / RANSAC beside the detector; book-keeping too in run-ahead mode
+    LPR_IMAGE            //   run-ahead mode: the image chain `ic` of this frame (chain 0 shares the tracker stream's queue, chain 1 has the fourth)
+};
+enum LpGray { LPGR_NONE, LPGR_DWORD3, LPGR_BYTE3, LPGR_DWORD4, LPGR_BYTE4 };   // mono: no launch; gray_kernel4<3>, gray_kernel<3>, gray_kernel4<4>, gray_kernel<4>
+enum LpClaheLut { LPCL_NONE, LPCL_COL16_256X8, LPCL_COL16_1024, LPCL_WAVE32 };   // equaliser off; clahe_lut_kernel2<256, 8>, clahe_lut_kernel2<1024>, clahe_lut_kernel
+enum LpClaheInterp { LPCI_NONE, LPCI_PX4, LPCI_PX1 };                            // equaliser off; clahe_interp_kernel4, clahe_interp_kernel
+enum LpPyramid { LPP_COPY, LPP_OWN };     // pyramid_kernel copies the image into level 0 | level 0 IS the handle's equalised image: no copy
+enum LpDetFirst { LPDF_NONE, LPDF_TILE, LPDF_STRIP };   // caller-side corner list: no detector; mineig_nms_kernel, mineig_nms_strip_kernel
+enum LpSubpix { LPSP_NONE, LPSP_WIDE_WIN, LPSP_GENERIC, LPSP_X16, LPSP_STOCK };   // subpix_wide_kernel, subpix_generic_kernel, subpix_kernel16, subpix_kernel
+enum LpKlt { LPKL_K3, LPKL_K16 };         // klt_kernel3, klt_kernel16
+enum LpAnnounce { LPA_NONE, LPA_SIGNAL, LPA_EVENT };   // how "the corners of this frame are there" reaches book-keeping's refill half
+enum LpBook {
+    LPB_PLAIN,       // ransac_kernel, bookkeep_a_kernel, bookkeep_b_kernel on one stream: the caller's corner list (and the direct-track entry point)
+    LPB_JOIN,        // the same kernels, RANSAC on the side stream, which joins back in front of book-keeping: the device detector outside run-ahead mode
+    LPB_FUSED,       // ransac_book_kernel: RANSAC and both halves of book-keeping in ONE launch on the side stream
+    LPB_PAIR         // ransac_book_a_kernel, bookkeep_b_kernel on the side stream
+};
+
+// what a call is made with.  Of the handle: the first three blocks; of the call: the fourth; of the process / the handle's queues: the last
+struct FrontIn {
+    int batch = 1;
+    bool throughput = false;       // the throughput forms of the image kernels (rvio_hip::wide_px: batch handles of >= 8 instances; rvio_hip_debug_kernel_forms)
+    int W = 0, H = 0, F = 0, nmax = 0;
+    bool equalizer = false;
+    int cl_tx = 0, cl_ty = 0, cl_tw = 0, cl_th = 0;   // CLAHE tile grid and tile size
+    int sp_win = LP_SP_WIN;        // cornerSubPix half-window, floor(Tracker.nMinDist / 2)
+    int channels = 1;              // bytes per pixel of the caller's images (1: mono)
+
+    bool piped_call = false;       // a whole-frame call of the pipelined path (else: a per-stage entry point, everything on the filter stream)
+    bool have_corner_list = false; // the caller hands in the corners: no device detector
+    long frame_no = 0;
+    bool first_cleared = false;    // mbIsTheFirstImage has gone to 0 in every instance (it never comes back: Tracker.cc:233)
+    bool src_dword = false;        // the caller's image: base address, row stride and instance stride are multiples of four bytes
+
+    bool no_runahead = false;      // RVIO_NO_RUNAHEAD
+    bool no_device_polls = false;  // RVIO_PARANOID's bit 4, or a counter-collecting profiler that serialises kernels across queues
+    bool own_queues = false;       // the handle's four streams own their hardware queues and nothing else feeds queues beside them:
+                                   // private_queues && !queues_shared && !extra_queues
+};
+
+struct FrontForms {
+    // ---- mode
+    bool use_det = false;        // FeatureDetector::DetectWithSubPix on the device
+    bool piped = false;
+    bool runahead = false;       // pipelined whole-frame call with the device detector: image chains of consecutive frames in flight, book-keeping on the side stream
+    bool dev_sync = false;       // ... of ONE instance: hand-over -> filter and corners -> refill go through device-side counters (StageSync)
+    int par = 0;                 // frame parity of a piped call, else 0
+    int dslot = 0;               // corner list / count of this call: three in rotation in run-ahead mode, else by parity
+    int ic = 0;                  // image chain of a run-ahead call: its stream, event and counters (< plan.n_ic); else 0
+    int lut_set = 0;             // CLAHE LUT set
+    int det_set = 0;             // detector scratch set
+    // ---- synchronisation
+    bool filter_done_by_counter = false;   // "the filter of this frame has finished" is stage_sync->aug reaching a target (no marker packet on the filter stream), else an event
+    bool wait_book_k3 = false;             // the image chain starts behind book-keeping(k-3): it rewrites equalised image k % 4 and corner list k % 3
+    bool wait_first_flag = false;          // the detector's threshold pass waits for book-keeping(k-1): it reads mbIsTheFirstImage
+    bool pyr_on_image = false;             // the pyramid rides on the image chain (run-ahead mode with the equaliser): the side stream's KLT has to be told when it is there
+    bool klt_polls_pyramid = false;        // ... klt_kernel3 polls the image chain's pyramid counter itself; else an event (evC) in front of it on the side stream
+    bool det_folds_signal = false;         // ... which the detector's first launch bumps, right behind the pyramid on the chain's queue (the tile form: the strip
+                                           // form has no folded signal, and the poll is never taken with it)
+    bool fork_side = false;                // the side stream forks from the image stream with an event of its own (evD0): nothing above has ordered it yet
+    LpAnnounce corners = LPA_NONE;
+    // ---- stream roles
+    LpStream base = LPR_FILTER;   // the call's own stream: where everything runs that is not forked off
+    LpStream image = LPR_FILTER;  // gray, CLAHE, detector
+    LpStream pyr = LPR_FILTER;    // the pyramid
+    LpStream side = LPR_FILTER;   // KLT, RANSAC
+    LpStream book = LPR_FILTER;   // book-keeping: the hand-over event is recorded here
+    // ---- kernel forms
+    LpGray gray = LPGR_NONE;             LpLaunch gray_l;
+    LpClaheLut clahe_lut = LPCL_NONE;    LpLaunch clahe_lut_l;
+    LpClaheInterp clahe_interp = LPCI_NONE; LpLaunch clahe_interp_l;
+    LpPyramid pyramid = LPP_COPY;        LpLaunch pyramid_l;
+    LpDetFirst det_first = LPDF_NONE;    LpLaunch det_first_l;
+    LpLaunch neigh_l, greedy_l;
+    LpSubpix subpix = LPSP_NONE;         LpLaunch subpix_l;
+    LpKlt klt = LPKL_K3;                 LpLaunch klt_l;
+    LpBook book_form = LPB_PLAIN;
+    LpLaunch ransac_l;                   // the launch RANSAC is in: ransac_kernel, ransac_book_a_kernel or ransac_book_kernel
+    LpLaunch book_a_l, book_b_l;         // bookkeep_a_kernel, bookkeep_b_kernel where they are launches of their own
+};
+
+inline FrontForms front_forms(const LaunchPlan& p, const FrontIn& in) {
+    FrontForms f;
+    const int B = in.batch, W = in.W, H = in.H, F = in.F;
+    const bool wide = in.throughput;
+    // ---- mode.  Two of them:
+    //  * plain (per-stage calls, or a caller-side corner list): one image stream; the side stream joins back and book-keeping runs on the call's stream;
+    //  * run-ahead (pipelined whole-frame path with the device detector): book-keeping runs on the SIDE stream, so the image stream is free for CLAHE +
+    //    detector of frame k+1 as soon as the detector of frame k is done — the image chain never reads tracker state, except mbIsTheFirstImage (the
+    //    detector's distance factor), hence one wait on book-keeping(k-1) in front of the threshold pass.  What book-keeping(k) still reads while frame
+    //    k+1 is being detected is buffered in rotation (equalised image, corner list).
+    f.use_det = !in.have_corner_list;   // no corner list from the caller: run FeatureDetector::DetectWithSubPix on the device
+    f.piped = in.piped_call;
+    f.par = f.piped ? (int)(in.frame_no & 1) : 0;
+    f.runahead = f.piped && f.use_det && !in.no_runahead;
+    // device-side counters for ONE instance only: a batch handle's kernels have one workgroup per instance, and a counter says nothing about which of them have finished
+    f.dev_sync = f.runahead && B == 1 && !in.no_device_polls;
+    f.dslot = f.runahead ? (int)(in.frame_no % 3) : f.par;
+    // in run-ahead mode the image chains of consecutive frames alternate between plan.n_ic streams (each with its own detector scratch and CLAHE LUTs), so
+    // that as many are in flight — the chain is ~150 us long, the longest of the frame, and with one stream it WAS the frame period
+    // (outside run-ahead mode there is ONE image stream, the call's own: no chain to name; the LUTs still alternate by parity)
+    f.ic = f.runahead ? (int)(in.frame_no % p.n_ic) : 0;
+    f.lut_set = f.runahead ? f.ic : f.par;
+    f.det_set = f.runahead ? f.ic : 0;
+    // ---- synchronisation
+    // single instance in run-ahead mode: the filter's last kernel bumps the device-side counter (book-keeping of a later frame polls it); otherwise an event behind it
+    f.filter_done_by_counter = f.dev_sync;
+    // Run-ahead mode: the image chain of frame k (CLAHE, detector; with the equaliser also the pyramid) rewrites buffers that book-keeping / KLT of earlier
+    // frames read — equalised image k % 4, corner list and count k % 3 — so it starts behind book-keeping(k-3), with or without the equaliser (the detector
+    // alone rewrites det_xy2[k % 3] / det_nout[k % 3], which bookkeep_b(k-3) reads).
+    f.wait_book_k3 = f.runahead && in.frame_no >= 3;
+    // run-ahead: book-keeping(k-1) ran on the side stream; its event also says that mbIsTheFirstImage is final ... until the flag has gone to 0 in every
+    // instance: the host sees that in the mirror book-keeping writes (a stale 1 only keeps the wait one frame longer) and the detector chain then paces itself
+    f.wait_first_flag = f.runahead && in.frame_no >= 1 && !in.first_cleared;
+    // With the equaliser the pyramid of a run-ahead frame rides on the image chain (see the stream roles), and the side stream's KLT has to wait for it.  klt_kernel3 polls
+    // the chain's counter itself (no barrier packet on the side stream) —
+    //  * own_queues: on a handle whose four streams own their hardware queues only (the first live handle of the process): 200 polling workgroups per frame
+    //    in front of kernels of OTHER handles on a shared queue timed the eight-handle leg of the bench out (a consumer may only spin where everything it
+    //    waits for was submitted earlier to queues nobody else feeds) ... and not on a handle that runs the sharded frame over a real collective,
+    //  * 6 nmax <= 96: nor at long windows (the Cholesky factor's launches share the copy queue): with the forced-sharded cfg E run of the bench two runs in
+    //    six stalled for the poll's full 30 s (none in six without it) — more busy queues than the command processor keeps resident, and a queue of spinning
+    //    workgroups in front of the one that would release them,
+    //  * !throughput: klt_kernel16 has no poll, and the strip form of the detector's first pass no folded signal.
+    // Without it: an event (evC) recorded behind the pyramid, which the side stream waits for.
+    f.pyr_on_image = in.equalizer && f.runahead;
+    f.klt_polls_pyramid = f.pyr_on_image && f.dev_sync && in.own_queues && 6 * in.nmax <= 96 && !wide;
+    f.fork_side = f.use_det && !f.pyr_on_image;   // (there the pyramid's event or counter has ordered the side stream behind the image already)
+    // corners of frame k ready (the refill half of book-keeping on the side stream waits for it): a one-workgroup signal behind cornerSubPix that
+    // book-keeping polls, or a stream-level event.  (One counter per image chain: each has ONE producer queue, so "count >= the frames this chain has been
+    // handed" means THIS frame's corners.)
+    f.corners = !f.use_det ? LPA_NONE : f.dev_sync ? LPA_SIGNAL : f.runahead ? LPA_EVENT : LPA_NONE;
+    // ---- stream roles.  The IMAGE stream carries CLAHE and FeatureDetector::DetectWithSubPix: the longest chain, ~170 us; the side stream pyramid, KLT,
+    // RANSAC: ~90 us
+    f.base = f.piped ? LPR_TRACKER : LPR_FILTER;
+    f.image = f.runahead ? LPR_IMAGE : f.base;
+    f.side = f.use_det ? LPR_SIDE : f.base;      // fork: pyramid / KLT / RANSAC go to the side stream, the detector stays where the image was completed
+    // the pyramid of an equalised run-ahead frame rides on the image stream: it needs nothing from the side stream's chain (KLT(k-1), RANSAC, book-keeping),
+    // which is the longest serial chain of the front end — 19 us less of it; the image chain has the slack
+    f.pyr = f.pyr_on_image ? f.image : f.side;
+    f.book = f.runahead ? LPR_SIDE : f.base;
+    // ---- kernel forms
+    // gray conversion: B interleaved images -> B packed gray images.  The dword form wherever every row of every instance starts on a dword and holds whole
+    // groups of four pixels, the byte form otherwise (same bits: gray.h)
+    const bool gray_dword = W % 4 == 0 && in.src_dword;
+    if (in.channels > 1) {
+        f.gray = in.channels == 3 ? (gray_dword ? LPGR_DWORD3 : LPGR_BYTE3) : (gray_dword ? LPGR_DWORD4 : LPGR_BYTE4);
+        f.gray_l = {(W + 255) / 256, (H + 3) / 4, B, 256};
+    }
+    // what CLAHE reads: the caller's image, or the handle's gray buffer (row stride W, instance stride W H, slots W H B apart in one allocation)
+    const bool eq_src_dword = in.channels > 1 ? W % 4 == 0 : in.src_dword;
+    if (in.equalizer) {
+        // lane-private 16-bit histogram columns, no LDS-atomic conflicts: every handle.  A counter sees the pixels of ONE lane column of the tile,
+        // ceil(tw / 64) th of them — 1296 at 1080p —, so 16 bits hold for any image a camera delivers; the 32-bit per-wave form stays as the fall-back
+        if (((in.cl_tw + 63) / 64) * in.cl_th <= 65535) {
+            // (throughput: eight rows of byte loads in flight per thread instead of four: the histogram of a batch is load-latency bound; 135.5 -> 136.7 k frames/s at 128 streams)
+            f.clahe_lut = wide ? LPCL_COL16_256X8 : LPCL_COL16_1024;
+            f.clahe_lut_l = {in.cl_tx * in.cl_ty, 1, B, wide ? 256 : 1024};
+        } else {
+            f.clahe_lut = LPCL_WAVE32;
+            f.clahe_lut_l = {in.cl_tx * in.cl_ty, 1, B, LP_CLAHE_LUT_T};
+        }
+        // interpolation: four pixels per thread in the throughput form where rows start on dwords and hold whole groups of four, else one
+        if (wide && W % 4 == 0 && eq_src_dword) { f.clahe_interp = LPCI_PX4; f.clahe_interp_l = {(W / 4 + 63) / 64, (H + 15) / 16, B, 256}; }
+        else { f.clahe_interp = LPCI_PX1; f.clahe_interp_l = {(W + 63) / 64, (H + 3) / 4, B, 256}; }
+    }
+    {   // the whole pyramid in one launch (pyrDown chain + the copy of the frame into level 0); one workgroup per 8x8 tile of level 3
+        const int w3 = (((W + 1) / 2 + 1) / 2 + 1) / 2, h3 = (((H + 1) / 2 + 1) / 2 + 1) / 2;
+        f.pyramid = in.equalizer ? LPP_OWN : LPP_COPY;   // the equalised image of frame k doubles as level 0 of frame k's pyramid
+        f.pyramid_l = {(w3 + 7) / 8, (h3 + 7) / 8, B, LP_PYR_T};
+    }
+    if (f.use_det) {
+        if (wide) {   // batch handles of >= 8 instances: the fused pass in its throughput form (one wave per strip, rows walked with the state in registers), which has no folded signal
+            f.det_first = LPDF_STRIP;
+            f.det_first_l = {(W + LP_DET_SW - 1) / LP_DET_SW, (H + LP_DET_SH - 1) / LP_DET_SH, B, 64};
+        } else {      // one stream: min-eigenvalue map + strict 3x3 local maxima in one pass (the map stays in LDS), then the image-wide threshold on the provisional list
+            f.det_first = LPDF_TILE;
+            f.det_first_l = {(W + LP_DET_TW - 1) / LP_DET_TW, (H + LP_DET_FH - 1) / LP_DET_FH, B, LP_DET_T};
+            f.det_folds_signal = f.klt_polls_pyramid;
+        }
+        // every workgroup rebuilds the candidate buckets in its LDS before it walks its share of the candidates: 8 of them for the latency of one stream,
+        // fewer for batch handles, whose width comes from the streams (measured at 128 streams: 8 -> 134.5 k frames/s, 4 -> 135.3, 2 -> 136.0, 1 -> 135.9)
+        f.neigh_l = {wide ? LP_NEIGH_BLOCKS_WIDE : LP_NEIGH_BLOCKS, 1, B, LP_NEIGH_T, LP_NEIGH_LDS, LPF_NEIGH};
+        f.greedy_l = {1, 1, B, LP_GREEDY_T, LP_GREEDY_LDS, LPF_GREEDY};
+        // cornerSubPix on the detector's raw corners
+        if (in.sp_win > 15) {               // Tracker.nMinDist >= 32: the summation grid no longer fits LDS whole
+            f.subpix = LPSP_WIDE_WIN; f.subpix_l = {F, 1, B, LP_SPG_T, lp_subpix_wide_lds(in.sp_win), LPF_SUBPIX_WIDE};
+        } else if (in.sp_win != LP_SP_WIN) {   // a cornerSubPix window other than the stock 7: the plain form
+            f.subpix = LPSP_GENERIC; f.subpix_l = {F, 1, B, LP_SPG_T};
+        } else if (wide) {                  // four corners per wave
+            f.subpix = LPSP_X16; f.subpix_l = {(F + 3) / 4, 1, B, 64};
+        } else {
+            f.subpix = LPSP_STOCK; f.subpix_l = {F, 1, B, LP_SP_T};
+        }
+    }
+    // KLT: a wave per feature, or (batch handles of >= 8 instances) the throughput form, four features per wave
+    if (wide) { f.klt = LPKL_K16; f.klt_l = {(F + 3) / 4, 1, B, 64}; }
+    else { f.klt = LPKL_K3; f.klt_l = {F, 1, B, 64}; }
+    // RANSAC and book-keeping.  The refill half's geometry is the plan's (book_waves waves, book_lds bytes).  A caller-side corner list is ONE list: the
+    // entry points that take one address a single instance, and book-keeping of that shape is one workgroup on instance 0 whatever the batch
+    const LpLaunch ransac = {1, 1, B, 256, (size_t)8 * F + 16, LPF_DEFAULT};
+    const LpLaunch book_b = {1, 1, B, 64 * p.book_waves, p.book_lds, LPK_BOOKKEEP_B};
+    if (!f.runahead) {
+        // the side stream (long finished when the detector is) joins back in front of book-keeping; with a caller-side list there is nothing to join
+        f.book_form = f.use_det ? LPB_JOIN : LPB_PLAIN;
+        const int bz = f.use_det ? B : 1;
+        f.ransac_l = ransac; f.book_a_l = {1, 1, bz, 256}; f.book_b_l = {1, 1, bz, book_b.threads, book_b.lds, book_b.kernel};
+    } else if (f.dev_sync && p.book_fused) {
+        // one instance, device-side counters: RANSAC and both halves of book-keeping are ONE launch (the refill half polls the detector's counter inside it)
+        f.book_form = LPB_FUSED;
+        f.ransac_l = {1, 1, B, 64 * p.book_waves, p.book_lds, LPK_RANSAC_BOOK};
+    } else {
+        // RANSAC rides in the launch of book-keeping's hand-over half (both one workgroup, back to back on the side stream); the refill half follows once the
+        // corners are there (a poll inside it, or an event in front of it)
+        f.book_form = LPB_PAIR;
+        f.ransac_l = ransac; f.book_b_l = book_b;
+    }
     return f;
 }

@@ -39,7 +39,6 @@ struct rvio_hip {
     int device = 0;
     hipStream_t stream = nullptr;     // filter stream (and the stream of every non-pipelined call)
     hipStream_t stream_t = nullptr;   // tracker stream of the pipelined whole-frame path
-    hipStream_t ts = nullptr;         // stream the tracker kernels of the call in progress go to
     hipEvent_t evT[4] = {nullptr, nullptr, nullptr, nullptr};   // book-keeping(k) done: a ring by frame number (the image chain of frame k waits for frame k-3's)
     hipEvent_t evH[4] = {nullptr, nullptr, nullptr, nullptr};   // hand-over of frame k written (bookkeep_a_kernel): what the filter of frame k waits for
     // Tracker -> Updater hand-over tables in rotation: book-keeping(k) rewrites table k % kHand once filter(k - kHand) has read it.  Two
@@ -73,8 +72,6 @@ struct rvio_hip {
     const double* last_Ab = nullptr;            // the [A|b] block of the last update (its meta row: frame_info)
     StageSync* stage_sync = nullptr;   // device-side completion counter of the filter chain (aug) and the value it reaches after the launches so far
     StageSync stage_tgt = {};
-    const unsigned long long* klt_wait = nullptr; unsigned long long klt_target = 0;
-    unsigned long long* pyr_signal = nullptr;   // pending: the next detector launch on the image chain's queue bumps it   // this frame's klt_kernel3 polls the image chain's pyramid counter
     double* S9scr = nullptr;     // solve9's slab of tiles in L2 (plan.solve9_nt != 0): 5 NT^2 x 256 doubles (+ the verdict of the Cholesky role)
     bool chol_ready = false;     // the slab holds L, G of the clone block the next solve will see (written by the role workgroup of the per-feature / propagate launch)
     float* eig_map = nullptr;    // W x H min-eigenvalue map of rvio_hip_get_corners(eig): allocated on first use
@@ -88,26 +85,20 @@ struct rvio_hip {
     static const int kIC = 3;                     // image chains in flight in run-ahead mode (streams, detector scratch sets, CLAHE LUT sets)
     DetDev dets[kIC] = {};                        // device detector (T7), allocated on first use: kIC sets of scratch — in run-ahead mode the
                                                   // detectors of consecutive frames run on two streams, by frame parity
-    int det_set_last = 0;                         // the set the last call used (rvio_hip_get_corners)
-    bool det_ready = false, use_det = false;
+    bool det_ready = false;
     hipStream_t stream_l = nullptr;               // long windows (6n > 96): = stream_c (one image chain in flight); the Cholesky factor of the clone block runs here, beside propagate / the per-feature stage of the frame it serves
     hipEvent_t evA = nullptr, evL = nullptr;      // augment/compose done (filter stream) -> stream_l;  factor in the slab (stream_l) -> the solve
     bool chol_async = false;                      // a factor of the CURRENT clone block is in flight on (or has left) stream_l
     hipStream_t stream_d = nullptr;               // side stream of the front end: forks from / joins the tracker stream (see build_pyramid_dev)
     hipStream_t stream_c = nullptr;               // CLAHE stream of the run-ahead mode (frame k+1 is equalised while frame k is still being detected)
     hipEvent_t evC[kIC] = {nullptr, nullptr, nullptr};   // equalised image + pyramid of the frame ready, by image chain
-    int ic = 0;                                   // image chain (stream / detector scratch / LUT set) of the call in progress: frame_no % plan.n_ic (<= kIC) in run-ahead mode, else the parity
-    hipStream_t side = nullptr;                   // stream of pyramid / KLT / RANSAC of the call in progress (stream_d beside the detector, else ts)
     hipEvent_t evD0 = nullptr, evD1 = nullptr;
     uint8_t* hb_img[2] = {nullptr, nullptr};      // staging of rvio_hip_frame (host buffers), by frame parity
     rvio_imu* hb_imu[kHand + 1] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // (run-ahead mode rotates kHand + 1 slots: see rvio_hip_frame)
-    hipEvent_t book_wait = nullptr;   // run-ahead: the event book-keeping of the frame in flight has to wait for (filter k-2)
     // how "the filter of the frame with parity b has finished" is known: 0 = evF[b] was recorded behind it, 1 = the device-side counter
     // stage_sync->aug reaches fin_target[b] (single instance, run-ahead mode: no marker packet on the filter stream)
     int fin_mode[kHand] = {0, 0, 0, 0};
-    unsigned long long fin_target[kHand] = {0, 0, 0, 0}, book_target = 0;
-    bool book_dev = false;
-    bool handover_evt = false;        // frame in flight: evH was recorded behind the hand-over half of book-keeping
+    unsigned long long fin_target[kHand] = {0, 0, 0, 0};
     bool last_ra = false;             // the previous rvio_hip_frame call ran in run-ahead mode
     float* hb_cand[2] = {nullptr, nullptr};
     // pinned host ring of rvio_hip_frame: the caller's (pageable) buffers are packed into it on the host, the H2D copies then run
@@ -121,18 +112,18 @@ struct rvio_hip {
     // image chain on the pipelined path, see track_dev_impl): equalised image, detector corner list and its count, by frame parity
     uint8_t* d_eq2[4] = {nullptr, nullptr, nullptr, nullptr};   // four, in rotation: the equalised image IS level 0 of its pyramid, which the KLT of the NEXT frame still reads
     int eq_slot = 0;
-    float* det_xy2[3] = {nullptr, nullptr, nullptr};   // corner lists: by parity, in run-ahead mode three in rotation (dslot)
-    int dslot = 0;
+    float* det_xy2[3] = {nullptr, nullptr, nullptr};   // corner lists: by parity, in run-ahead mode three in rotation (FrontForms::dslot)
     int* det_nout = nullptr;
-    int par = 0;                                  // parity of the call in progress / of the last call (getters)
-    hipStream_t tail = nullptr;                   // stream that ran book-keeping in the call in progress (the hand-over event is recorded there)
-    bool runahead = false;                        // call in progress: pipelined whole-frame path with the device detector
+    // What the getters and rvio_hip_debug_time_kernel need to know about the LAST front-end call, written when that call has enqueued its launches.  (The
+    // mode of a call in progress is no handle state: it is the FrontForms value the call computes once and passes down.)
+    struct Last {
+        int dslot = 0;                            // its corner list / count (rvio_hip_get_corners)
+        int det_set = 0;                          // the detector scratch set it used
+        const uint8_t* gray_src = nullptr; int gray_stride = 0; size_t gray_bs = 0;   // the last colour image handed over (rvio_hip_debug_time_kernel(11))
+    } last;
     bool private_queues = false;                  // this handle's streams own hardware queues (make_stream)
     bool queues_shared = false;                   // ... unless one of them had to come from the shared pool after all
     bool extra_queues = false;                    // a collective's queues run beside this handle's (rvio_hip_frame_sharded_dev with a communicator)
-    bool dev_sync = false;                        // ... of ONE instance: hand-over -> filter and corners -> refill go through device-side counters (StageSync)
-    bool gate_pending = false;                    // the filter of the frame in flight starts behind stage_gate_kernel (target: gate_target)
-    unsigned long long gate_target = 0;
     int cl_tx = 0, cl_ty = 0, cl_tw = 0, cl_th = 0, cl_clip = 0;
     float cl_scale = 0.f;
     float* d_in_xy = nullptr;
@@ -152,7 +143,7 @@ struct rvio_hip {
     const rvio_imu* fuse_imu = nullptr;   // whole-frame path: propagate of this frame rides in the per-feature launch (feat_prop_kernel)
     const rvio_imu* time_imu = nullptr; int time_m = 0;   // the IMU batch of the last fused frame (rvio_hip_debug_time_kernel(8) only: the caller's buffer)
     int fuse_m = -1;                      // >= 0 while such a propagate is pending
-    bool wide_px = false;            // throughput forms of the image kernels (several pixels per thread): batch handles of >= 8 instances
+    bool wide_px = false;            // throughput forms of the image kernels (several pixels per thread): batch handles of >= 8 instances.  An INPUT of front_forms(), read nowhere else
     bool front_end = true;           // a batch handle may carry the filter only
     bool det_in_slab = false;        // batch handle with front end: the detector's buffers are slab members too
     size_t img_bs = 0, imu_bs = 0;   // instance strides (bytes) of the image / IMU batch of the call in progress
@@ -181,7 +172,6 @@ struct rvio_hip {
     uint8_t* d_gray[4] = {nullptr, nullptr, nullptr, nullptr};
     int gray_slot = 0;
     size_t img_cap = 0;              // bytes of one staged image the host-side staging (d_img, hb_img[]) holds: W * H, grows with the channel count
-    const uint8_t* gray_src = nullptr; int gray_stride = 0; size_t gray_bs = 0;   // the last image handed over (rvio_hip_debug_time_kernel(11))
 };
 
 // ---------------------------------------------------------------- environment surface of the library: three variables of its own, plus the profiler's.
@@ -444,6 +434,10 @@ static_assert(LP_S9SMALL_BYTES == sizeof(S9SmallLds), "launch_plan.h: solve9's L
 static_assert(LP_PROP3_BYTES == sizeof(Prop3Lds<16>), "launch_plan.h: propagate's LDS struct");
 static_assert(LP_JB_TL_DOUBLES == JB_TL_DOUBLES && LP_UGL_BYTES == UGL_LDS_DOUBLES * sizeof(double) && LP_FNL_BYTES == FNL_LDS_DOUBLES * sizeof(double) &&
               LP_JL_BYTES == JL_LDS_DOUBLES * sizeof(double), "launch_plan.h: the Joseph-form kernels' LDS");
+static_assert(LP_DET_TW == DET_TW && LP_DET_FH == DET_FH && LP_DET_T == DET_T && LP_DET_SW == DET_SW && LP_DET_SH == DET_SH && LP_NEIGH_T == NEIGH_T &&
+              LP_NEIGH_BLOCKS == NEIGH_BLOCKS && LP_NEIGH_BLOCKS_WIDE == NEIGH_BLOCKS_WIDE && LP_NEIGH_LDS == NEIGH_LDS && LP_GREEDY_T == GREEDY_T &&
+              LP_GREEDY_LDS == GREEDY_LDS && LP_SP_WIN == SP_WIN && LP_SP_T == SP_T && LP_SPG_T == SPG_T && LP_SPW_C == SPW_C, "launch_plan.h: the detector's launch geometry");
+static_assert(LP_PYR_T == PYR_T && LP_CLAHE_LUT_T == CLAHE_LUT_T, "launch_plan.h: pyramid / CLAHE workgroup sizes");
 static const void* lp_kernel_fn(int k) {
     switch (k) {
         case LPK_FEAT_BUILD16: return (const void*)feat_build_kernel<16>;
@@ -531,7 +525,6 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
     HIPCHK(h, hipEventCreateWithFlags(&h->evD0, kEvFlags));
     HIPCHK(h, hipEventCreateWithFlags(&h->evD1, kEvFlags));
     for (int b = 0; b < rvio_hip::kIC; ++b) HIPCHK(h, hipEventCreateWithFlags(&h->evC[b], kEvFlags));
-    h->ts = h->stream;
     for (int b = 0; b < 2; ++b) {
         HIPCHK(h, hipEventCreateWithFlags(&h->evT[b], kEvFlags));
         HIPCHK(h, hipEventCreateWithFlags(&h->evT[b + 2], kEvFlags));
@@ -744,7 +737,7 @@ int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n
         HIPCHK(h, hipMemsetAsync(h->stage_sync, 0, sizeof(StageSync), h->stream));
         h->stage_tgt = StageSync{};
         for (int b = 0; b < rvio_hip::kHand; ++b) { h->fin_mode[b] = 0; h->fin_target[b] = 0; }
-        h->book_wait = nullptr; h->book_dev = false; h->book_target = 0; h->gate_pending = false; h->gate_target = 0; h->last_ra = false;
+        h->last_ra = false;
         std::vector<int> ones((size_t)h->batch, 1);
         HIPCHK(h, hipMemcpy2DAsync(h->t.first, h->slab_bytes, ones.data(), sizeof(int), sizeof(int), (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
         for (int i = 0; i < h->batch; ++i) {
@@ -997,18 +990,20 @@ static void launch_landmarks(rvio_hip* h, int n, const LmOut& out) {
                        (const int*)h->t.n_feat, (const unsigned char*)h->t.types, (const int*)h->t.len, (const int*)h->acc, (const double*)h->pfinv,
                        h->slab_bytes, h->bin, out);
 }
-// cornerSubPix on the detector's raw corners, for B instances (frame: the instrumented build's stamp)
-static void launch_subpix(rvio_hip* h, const DetDev& q, const uint8_t* img, int stride, size_t src_bs, unsigned B, int frame, hipStream_t st) {
-    const DevCfg& d = h->dc;
+// grid / workgroup of a front-end launch as front_forms() (launch_plan.h) fixed them
+static dim3 lp_grid(const LpLaunch& l) { return dim3((unsigned)l.gx, (unsigned)l.gy, (unsigned)l.gz); }
+static dim3 lp_block(const LpLaunch& l) { return dim3((unsigned)l.threads); }
+// cornerSubPix on the detector's raw corners, in the form f names (frame: the instrumented build's stamp)
+static void launch_subpix(rvio_hip* h, const FrontForms& f, const DetDev& q, const uint8_t* img, int stride, size_t src_bs, int frame, hipStream_t st) {
     const size_t bs = h->slab_bytes;
-    if (q.sp_win > 15)        // Tracker.nMinDist >= 32: the summation grid no longer fits LDS whole
-        hipLaunchKernelGGL(subpix_wide_kernel, dim3(d.F, 1, B), dim3(SPG_T), subpix_wide_lds(q.sp_win), st, img, stride, q, src_bs, bs);
-    else if (q.sp_win != SP_WIN)   // a cornerSubPix window other than the stock 7: the plain form
-        hipLaunchKernelGGL(subpix_generic_kernel, dim3(d.F, 1, B), dim3(SPG_T), 0, st, img, stride, q, src_bs, bs);
-    else if (h->wide_px)
-        hipLaunchKernelGGL(subpix_kernel16, dim3((d.F + 3) / 4, 1, B), dim3(64), 0, st, img, stride, q, src_bs, bs);
-    else
-        hipLaunchKernelGGL(subpix_kernel, dim3(d.F, 1, B), dim3(SP_T), 0, st, img, stride, q, src_bs, bs, frame);
+    const LpLaunch& l = f.subpix_l;
+    switch (f.subpix) {
+    case LPSP_NONE: break;
+    case LPSP_WIDE_WIN: hipLaunchKernelGGL(subpix_wide_kernel, lp_grid(l), lp_block(l), l.lds, st, img, stride, q, src_bs, bs); break;
+    case LPSP_GENERIC: hipLaunchKernelGGL(subpix_generic_kernel, lp_grid(l), lp_block(l), 0, st, img, stride, q, src_bs, bs); break;
+    case LPSP_X16: hipLaunchKernelGGL(subpix_kernel16, lp_grid(l), lp_block(l), 0, st, img, stride, q, src_bs, bs); break;
+    case LPSP_STOCK: hipLaunchKernelGGL(subpix_kernel, lp_grid(l), lp_block(l), 0, st, img, stride, q, src_bs, bs, frame); break;
+    }
 }
 // the cloud buffers of every instance in one allocation (count | feat[Fu] | p_r[Fu][3] | p_w[Fu][3], 256-byte aligned parts)
 static int lm_alloc(rvio_hip* h, LmOut* out) {
@@ -1298,7 +1293,10 @@ static int detector_init(rvio_hip* h) {
     }
     HIPCHK(h, hipMemcpyAsync(const_cast<float*>(q.spmask), hm.data(), sizeof(float) * hm.size(), hipMemcpyHostToDevice, h->stream));   // one copy, shared by all instances
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (hm is a local)
-    if (spw > 15) HIPCHK(h, lds_attr((const void*)subpix_wide_kernel, (int)subpix_wide_lds(spw)));
+    if (spw > 15) {   // (the limit from the kernel file's own formula; front_forms() hands the launch launch_plan.h's copy of it)
+        if (lp_subpix_wide_lds(spw) != subpix_wide_lds(spw)) { h->err = "launch_plan.h: lp_subpix_wide_lds disagrees with detector.hip"; return RVIO_ERR_UNSUPPORTED; }
+        HIPCHK(h, lds_attr((const void*)subpix_wide_kernel, (int)subpix_wide_lds(spw)));
+    }
     std::vector<int> minkey((size_t)h->batch, (int)0x80000000);
     for (DetDev* qq : {&h->dets[0], &h->dets[1], &h->dets[2]})
         HIPCHK(h, hipMemcpy2DAsync(qq->maxkey, h->slab_bytes ? h->slab_bytes : sizeof(int), minkey.data(), sizeof(int), sizeof(int), (size_t)(h->det_in_slab ? h->batch : 1),
@@ -1309,67 +1307,87 @@ static int detector_init(rvio_hip* h) {
     h->det_ready = true;
     return RVIO_OK;
 }
-// Front-end sequencing.  Two streams: the IMAGE stream h->ts (CLAHE and FeatureDetector::DetectWithSubPix: the longest chain, ~170 us)
-// and the side stream h->side (pyramid, KLT, RANSAC: ~90 us).  Two modes:
-//  * plain (per-stage calls, or a caller-side corner list): the side stream joins back and book-keeping runs on h->ts;
-//  * run-ahead (pipelined whole-frame path with the device detector): book-keeping runs on the SIDE stream, so the image stream is
-//    free for CLAHE + detector of frame k+1 as soon as the detector of frame k is done — the image chain never reads tracker state,
-//    except mbIsTheFirstImage (the detector's distance factor), hence one wait on book-keeping(k-1) in front of nms(k).  What
-//    book-keeping(k) still reads while frame k+1 is being detected is double-buffered by frame parity (equalised image, corner list).
-static DetDev det_view(const rvio_hip* h) {
-    DetDev q = h->dets[h->runahead ? h->ic : 0];
-    q.xy = h->det_xy2[h->dslot]; q.n_out = h->det_nout + h->dslot;
+// Front-end sequencing.  What a call launches and how its chains are ordered against each other is decided in ONE place, front_forms()
+// (launch_plan.h): the mode (plain | run-ahead, device-side counters | stream events), every wait and signal between the queues, the stream
+// role of every stage and the form of every kernel — the reasons stand there, next to the rule.  A call computes that value once (call_forms)
+// and passes it down by const&; the stages below switch on it and keep the stream and event OBJECTS.
+static DetDev det_view(const rvio_hip* h, int det_set, int dslot) {
+    DetDev q = h->dets[det_set];
+    q.xy = h->det_xy2[dslot]; q.n_out = h->det_nout + dslot;
     return q;
 }
-// the stream CLAHE and the detector of the call in progress run on: in run-ahead mode the image chains of consecutive frames
-// alternate between two streams (each with its own detector scratch and CLAHE LUTs), so that two of them are in flight — the chain is
-// ~150 us long, the longest of the frame, and with one stream it WAS the frame period
-static hipStream_t image_stream_of(const rvio_hip* h, int ic) { return ic == 0 ? h->stream_t : h->stream_c; }
-static hipStream_t image_stream(const rvio_hip* h) { return h->runahead ? image_stream_of(h, h->ic) : h->ts; }
-static int detect_dev(rvio_hip* h, const uint8_t* img, int stride, size_t src_bs, hipEvent_t first_flag_ready) {
+// a stream role of front_forms() -> the handle's stream (ic: the image chain of the call, for LPR_IMAGE)
+static hipStream_t stream_of(const rvio_hip* h, LpStream role, int ic) {
+    switch (role) {
+    case LPR_FILTER: break;
+    case LPR_TRACKER: return h->stream_t;
+    case LPR_SIDE: return h->stream_d;
+    case LPR_IMAGE: return ic == 0 ? h->stream_t : h->stream_c;
+    }
+    return h->stream;
+}
+// mbIsTheFirstImage: the host sees it in the mirror book-keeping writes, until it has gone to 0 in every instance (cached: it never comes back).  The
+// entry points refresh the cache in front of a call that runs the detector; call_forms() below only reads it
+static void refresh_first_cleared(rvio_hip* h) {
+    if (h->first_cleared) return;
+    bool all0 = true;
+    for (int i = 0; i < h->batch && all0; ++i) all0 = ((volatile int*)h->first_mirror)[i] == 0;
+    h->first_cleared = all0;
+}
+// The forms of ONE front-end call: the only place the mode of a call is derived.  img / stride / img_bs: the caller's image (nullptr: none)
+static FrontForms call_forms(const rvio_hip* h, bool piped_call, bool have_corner_list, const uint8_t* img, int stride, size_t img_bs) {
     const DevCfg& d = h->dc;
+    FrontIn in;
+    in.batch = h->batch; in.throughput = h->wide_px;
+    in.W = d.W; in.H = d.H; in.F = d.F; in.nmax = d.nmax;
+    in.equalizer = h->cfg.enable_equalizer != 0;
+    in.cl_tx = h->cl_tx; in.cl_ty = h->cl_ty; in.cl_tw = h->cl_tw; in.cl_th = h->cl_th;
+    in.sp_win = (int)std::floor(.5 * h->cfg.min_dist);   // cornerSubPix half-window, FeatureDetector.cc:68
+    in.channels = h->pix_ch;
+    in.piped_call = piped_call; in.have_corner_list = have_corner_list; in.frame_no = h->frame_no; in.first_cleared = h->first_cleared;
+    in.src_dword = stride % 4 == 0 && ((uintptr_t)img & 3) == 0 && img_bs % 4 == 0;
+    in.no_runahead = no_runahead(); in.no_device_polls = no_device_polls();
+    in.own_queues = h->private_queues && !h->queues_shared && !h->extra_queues;
+    return front_forms(h->plan, in);
+}
+static int detect_dev(rvio_hip* h, const FrontForms& f, const uint8_t* img, int stride, size_t src_bs) {
     const size_t bs = h->slab_bytes;
     const unsigned B = (unsigned)h->batch;
-    const DetDev q = det_view(h);
-    const hipStream_t ds = image_stream(h);
-    h->det_set_last = h->runahead ? h->ic : 0;
-    if (h->wide_px) {
-        // batch handles of >= 8 instances: the fused pass in its throughput form (one wave per strip, rows walked with the state in registers), which has no folded signal
-        if (h->pyr_signal) { hipLaunchKernelGGL(stage_signal_kernel, dim3(1), dim3(64), 0, ds, h->pyr_signal); h->pyr_signal = nullptr; }
-        hipLaunchKernelGGL(mineig_nms_strip_kernel, dim3((d.W + DET_SW - 1) / DET_SW, (d.H + DET_SH - 1) / DET_SH, B), dim3(64), 0, ds, img, stride, q, src_bs, bs);
-    } else {
-        // one stream: min-eigenvalue map + strict 3x3 local maxima in one pass (the map stays in LDS), then the image-wide threshold on the provisional list
-        hipLaunchKernelGGL(mineig_nms_kernel, dim3((d.W + DET_TW - 1) / DET_TW, (d.H + DET_FH - 1) / DET_FH, B), dim3(DET_T), 0, ds, img, stride, q, src_bs, bs, (int)h->frame_no, h->pyr_signal);
-        h->pyr_signal = nullptr;
+    const DetDev q = det_view(h, f.det_set, f.dslot);
+    const hipStream_t ds = stream_of(h, f.image, f.ic);
+    switch (f.det_first) {
+    case LPDF_NONE: break;
+    case LPDF_STRIP:
+        hipLaunchKernelGGL(mineig_nms_strip_kernel, lp_grid(f.det_first_l), lp_block(f.det_first_l), 0, ds, img, stride, q, src_bs, bs);
+        break;
+    case LPDF_TILE:
+        hipLaunchKernelGGL(mineig_nms_kernel, lp_grid(f.det_first_l), lp_block(f.det_first_l), 0, ds, img, stride, q, src_bs, bs, (int)h->frame_no,
+                           f.det_folds_signal ? &h->stage_sync->pyr[f.ic] : (unsigned long long*)nullptr);   // what this frame's klt_kernel3 polls, if it polls (build_pyramid_dev)
+        break;
     }
-    if (first_flag_ready) HIPCHK(h, hipStreamWaitEvent(ds, first_flag_ready, 0));   // the threshold pass reads mbIsTheFirstImage (cell size) as book-keeping(k-1) left it
+    if (f.wait_first_flag) HIPCHK(h, hipStreamWaitEvent(ds, h->evT[(h->frame_no - 1) & 3], 0));   // the threshold pass reads mbIsTheFirstImage (cell size) as book-keeping(k-1) left it
     hipLaunchKernelGGL(nms_threshold_kernel, dim3(16, 1, B), dim3(NMS_T), 0, ds, q, bs);
-    // (every workgroup rebuilds the candidate buckets in its LDS before it walks its share of the candidates: 8 of them for the latency of one
-    //  stream, fewer for batch handles, whose width comes from the streams)
-    const unsigned neigh_blocks = h->wide_px ? NEIGH_BLOCKS_WIDE : NEIGH_BLOCKS;
-    hipLaunchKernelGGL(neigh_kernel, dim3(neigh_blocks, 1, B), dim3(NEIGH_T), NEIGH_LDS, ds, q, bs);
-    hipLaunchKernelGGL(greedy_kernel, dim3(1, 1, B), dim3(GREEDY_T), GREEDY_LDS, ds, q, bs);
-    launch_subpix(h, q, img, stride, src_bs, B, (int)h->frame_no, ds);
+    hipLaunchKernelGGL(neigh_kernel, lp_grid(f.neigh_l), lp_block(f.neigh_l), f.neigh_l.lds, ds, q, bs);
+    hipLaunchKernelGGL(greedy_kernel, lp_grid(f.greedy_l), lp_block(f.greedy_l), f.greedy_l.lds, ds, q, bs);
+    launch_subpix(h, f, q, img, stride, src_bs, (int)h->frame_no, ds);
     HIPCHK(h, hipGetLastError());
     return RVIO_OK;
 }
 
 // ------------------------------------------------------------------ gray conversion (Tracker.cc:182-196)
 static int pix_channels(int fmt) { return fmt == RVIO_PIX_MONO8 ? 1 : (fmt == RVIO_PIX_RGB8 || fmt == RVIO_PIX_BGR8) ? 3 : 4; }
-// B interleaved images -> B packed gray images (instance stride W * H) on `st`.  The wide form wherever every row of every instance starts
-// on a dword and holds whole groups of four pixels, the byte form otherwise (same bits: gray.h)
-static void launch_gray(rvio_hip* h, const uint8_t* src, int stride, size_t src_bs, uint8_t* dst, hipStream_t st) {
+// B interleaved images -> B packed gray images (instance stride W * H) on `st`, in the form f names
+static void launch_gray(rvio_hip* h, const FrontForms& f, const uint8_t* src, int stride, size_t src_bs, uint8_t* dst, hipStream_t st) {
     const DevCfg& d = h->dc;
     const int bgr = (h->pix_fmt == RVIO_PIX_BGR8 || h->pix_fmt == RVIO_PIX_BGRA8) ? 1 : 0;
     const size_t bs = (size_t)d.W * d.H;
-    const dim3 g((d.W + 255) / 256, (d.H + 3) / 4, h->batch), b(256);
-    const bool wide = d.W % 4 == 0 && stride % 4 == 0 && ((uintptr_t)src & 3) == 0 && src_bs % 4 == 0;
-    if (h->pix_ch == 3) {
-        if (wide) hipLaunchKernelGGL(gray_kernel4<3>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs);
-        else hipLaunchKernelGGL(gray_kernel<3>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs);
-    } else {
-        if (wide) hipLaunchKernelGGL(gray_kernel4<4>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs);
-        else hipLaunchKernelGGL(gray_kernel<4>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs);
+    const dim3 g = lp_grid(f.gray_l), b = lp_block(f.gray_l);
+    switch (f.gray) {
+    case LPGR_NONE: break;
+    case LPGR_DWORD3: hipLaunchKernelGGL(gray_kernel4<3>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs); break;
+    case LPGR_BYTE3: hipLaunchKernelGGL(gray_kernel<3>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs); break;
+    case LPGR_DWORD4: hipLaunchKernelGGL(gray_kernel4<4>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs); break;
+    case LPGR_BYTE4: hipLaunchKernelGGL(gray_kernel<4>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs); break;
     }
 }
 int rvio_hip_get_image_format(const rvio_hip* h) { return h ? h->pix_fmt : RVIO_ERR_INVALID; }
@@ -1406,32 +1424,34 @@ int rvio_hip_set_image_format(rvio_hip* h, int format) {
         for (int k = 0; k < rvio_hip::kPin; ++k) if (h->pin[k]) { hipHostFree(h->pin[k]); h->pin[k] = nullptr; }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->pix_fmt = format; h->pix_ch = ch;
-    h->gray_src = nullptr;
+    h->last.gray_src = nullptr;
     return RVIO_OK;
 }
 
 // ------------------------------------------------------------------ T1..T6
-static int build_pyramid_dev(rvio_hip* h, const uint8_t* d_img, int stride, int b) {
+// Per-call values one stage hands to the next (no handle state: a call that fails half-way leaves nothing behind).
+struct KltWait { const unsigned long long* counter = nullptr; unsigned long long target = 0; };   // what this call's klt_kernel3 polls (nullptr: nothing)
+// what run-ahead book-keeping waits for before it rewrites the hand-over table — the filter that read it last: an event in front of it, or the filter
+// chain's counter (stage_sync->aug) reaching `target` inside it
+struct BookWait { hipEvent_t evt = nullptr; bool dev = false; unsigned long long target = 0; };
+// what book-keeping left for the filter of this frame: it starts behind stage_gate_kernel (gate, gate_target), else behind an event — evH recorded behind
+// the hand-over half (handover_evt), else the caller's own behind all of book-keeping
+struct BookOut { bool gate = false; unsigned long long gate_target = 0; bool handover_evt = false; };
+
+static int build_pyramid_dev(rvio_hip* h, const FrontForms& f, const uint8_t* d_img, int stride, int b, KltWait* klt) {
     const DevCfg& d = h->dc;
     PyrDev& p = h->pyr[b];
     const size_t bs = h->slab_bytes;
-    const unsigned B = (unsigned)h->batch;
     size_t src_bs = h->img_bs;       // the caller's images: instance stride of the call in progress
-    bool forked = false, pyramid_done = false;
-    // the whole pyramid in one launch (pyrDown chain + the copy of the frame into level 0); one workgroup per 8x8 tile of level 3
+    const hipStream_t is = stream_of(h, f.image, f.ic);
     auto launch_pyramid = [&](hipStream_t st) {
-        const int w3 = (((d.W + 1) / 2 + 1) / 2 + 1) / 2, h3 = (((d.H + 1) / 2 + 1) / 2 + 1) / 2;
         PyrDev pv = p;
-        const bool own = h->cfg.enable_equalizer != 0;   // d_img is the handle's equalised image: level 0 without a copy
+        const bool own = f.pyramid == LPP_OWN;   // d_img is the handle's equalised image: level 0 without a copy
         if (own) { h->pyr[b].img[0] = d_img; pv.img[0] = d_img; }
-        hipLaunchKernelGGL(pyramid_kernel, dim3((w3 + 7) / 8, (h3 + 7) / 8, B), dim3(PYR_T), 0, st, d_img, stride, pv, d.levels, own ? 0 : 1, src_bs, bs);
+        hipLaunchKernelGGL(pyramid_kernel, lp_grid(f.pyramid_l), lp_block(f.pyramid_l), 0, st, d_img, stride, pv, d.levels, own ? 0 : 1, src_bs, bs);
     };
-    // Run-ahead mode: the image chain of frame k (CLAHE, detector; with the equaliser also the pyramid) rewrites buffers that book-keeping /
-    // KLT of earlier frames read — equalised image k % 4, corner list and count k % 3 — so it starts behind book-keeping(k-3), with or
-    // without the equaliser (the detector alone rewrites det_xy2[k % 3] / det_nout[k % 3], which bookkeep_b(k-3) reads).
-    if (h->runahead && h->frame_no >= 3)
-        HIPCHK(h, hipStreamWaitEvent(image_stream(h), h->evT[(h->frame_no - 3) & 3], 0));
-    if (h->pix_ch > 1) {   // colour camera: "Convert to gray scale", Tracker.cc:182-196 — the first launch of the image chain; every later reader sees the handle's gray image
+    if (f.wait_book_k3) HIPCHK(h, hipStreamWaitEvent(is, h->evT[(h->frame_no - 3) & 3], 0));
+    if (f.gray != LPGR_NONE) {   // colour camera: "Convert to gray scale", Tracker.cc:182-196 — the first launch of the image chain; every later reader sees the handle's gray image
         // Four gray buffers in rotation (one step per image, so slot k % 4 on the whole-frame paths).  Who read slot k % 4 last — gray image k-4:
         //  * equaliser on: CLAHE(k-4), nobody else (the equalised image is what detector, pyramid and KLT see);
         //  * equaliser off: detector(k-4) incl. cornerSubPix on its image stream, pyramid(k-4) (which copies it into level 0) on the side stream.
@@ -1439,16 +1459,15 @@ static int build_pyramid_dev(rvio_hip* h, const uint8_t* d_img, int stride, int 
         // KLT(k-4) on the side stream and its refill half waited for the corners of detector(k-4); book-keeping(k-3) followed it there, and the wait
         // above puts this launch behind book-keeping(k-3) — the wait that protects equalised image k % 4 and corner list k % 3 covers the gray slot
         // too (with two image chains, or one at long windows, CLAHE(k-4) also sits earlier on this very stream).
-        // Every other mode — RVIO_NO_RUNAHEAD, a caller-side corner list, the per-stage calls — has ONE image stream (h->ts) for every frame: CLAHE /
+        // Every other mode — RVIO_NO_RUNAHEAD, a caller-side corner list, the per-stage calls — has ONE image stream for every frame: CLAHE /
         // detector of earlier images are earlier on it, and a pyramid that ran on the side stream was joined back into it in front of that
         // image's book-keeping (post_klt_dev).  No wait of its own anywhere.
         h->gray_slot = (h->gray_slot + 1) % 4;
         uint8_t* g = h->d_gray[h->gray_slot];
-        h->gray_src = d_img; h->gray_stride = stride; h->gray_bs = src_bs;
-        launch_gray(h, d_img, stride, src_bs, g, image_stream(h));
+        launch_gray(h, f, d_img, stride, src_bs, g, is);
         d_img = g; stride = d.W; src_bs = (size_t)d.W * d.H;
     }
-    if (h->cfg.enable_equalizer) {   // clahe->apply(im, im), Tracker.cc:198-202
+    if (f.clahe_lut != LPCL_NONE) {   // clahe->apply(im, im), Tracker.cc:198-202
         // The equalised image of frame k doubles as level 0 of frame k's pyramid (no copy), so it lives until the KLT of frame k+1 has
         // matched against it: four buffers in rotation (like the pyramids, and three corner lists).  Slot k % 4 was last read by KLT(k-3)
         // (as the previous image) and by the detector / pyramid of frame k-4; in run-ahead mode CLAHE(k) waits for book-keeping(k-3), which
@@ -1456,168 +1475,146 @@ static int build_pyramid_dev(rvio_hip* h, const uint8_t* d_img, int stride, int 
         // was for book-keeping(k-2): an image chain is ~190 us long, so it started late enough to hold book-keeping(k) up.)
         h->eq_slot = (h->eq_slot + 1) % 4;
         uint8_t* eq = h->d_eq2[h->eq_slot];
-        hipStream_t cs = image_stream(h);
-        uint8_t* lut = h->d_lut2[h->runahead ? h->ic : h->par];
-        // (lane-private 16-bit histogram columns, no LDS-atomic conflicts: every handle.  A counter sees the pixels of ONE lane column of the tile,
-        // ceil(tw / 64) th of them — 1296 at 1080p —, so 16 bits hold for any image a camera delivers; the 32-bit per-wave form stays as the fall-back)
-        if (((h->cl_tw + 63) / 64) * h->cl_th <= 65535)
-            if (h->wide_px) {
-                // (eight rows of byte loads in flight per thread instead of four: the histogram of a batch is load-latency bound; 135.5 -> 136.7 k frames/s at 128 streams)
-                hipLaunchKernelGGL((clahe_lut_kernel2<256, 8>), dim3(h->cl_tx * h->cl_ty, 1, B), dim3(256), 0, cs, d_img, d.W, d.H, stride, h->cl_tx, h->cl_tw, h->cl_th,
-                                   h->cl_clip, h->cl_scale, lut, src_bs, bs, (int)h->frame_no);
-            }
-            else hipLaunchKernelGGL(clahe_lut_kernel2<1024>, dim3(h->cl_tx * h->cl_ty, 1, B), dim3(1024), 0, cs, d_img, d.W, d.H, stride, h->cl_tx, h->cl_tw, h->cl_th,
-                                    h->cl_clip, h->cl_scale, lut, src_bs, bs, (int)h->frame_no);
-        else
-        hipLaunchKernelGGL(clahe_lut_kernel, dim3(h->cl_tx * h->cl_ty, 1, B), dim3(CLAHE_LUT_T), 0, cs, d_img, d.W, d.H, stride, h->cl_tx, h->cl_tw, h->cl_th,
-                           h->cl_clip, h->cl_scale, lut, src_bs, bs, (int)h->frame_no);
-        if (h->wide_px && d.W % 4 == 0 && stride % 4 == 0 && ((uintptr_t)d_img & 3) == 0 && src_bs % 4 == 0)
-            hipLaunchKernelGGL(clahe_interp_kernel4, dim3((d.W / 4 + 63) / 64, (d.H + 15) / 16, B), dim3(256), 0, cs, d_img, d.W, d.H, stride, h->cl_tx, h->cl_ty,
-                               1.0f / (float)h->cl_tw, 1.0f / (float)h->cl_th, lut, eq, src_bs, bs);
-        else
-            hipLaunchKernelGGL(clahe_interp_kernel, dim3((d.W + 63) / 64, (d.H + 3) / 4, B), dim3(256), 0, cs, d_img, d.W, d.H, stride, h->cl_tx, h->cl_ty,
-                               1.0f / (float)h->cl_tw, 1.0f / (float)h->cl_th, lut, eq, src_bs, bs);
+        uint8_t* lut = h->d_lut2[f.lut_set];
+        const dim3 lg = lp_grid(f.clahe_lut_l), lb = lp_block(f.clahe_lut_l), ig = lp_grid(f.clahe_interp_l), ib = lp_block(f.clahe_interp_l);
+        switch (f.clahe_lut) {
+        case LPCL_NONE: break;
+        case LPCL_COL16_256X8:
+            hipLaunchKernelGGL((clahe_lut_kernel2<256, 8>), lg, lb, 0, is, d_img, d.W, d.H, stride, h->cl_tx, h->cl_tw, h->cl_th, h->cl_clip, h->cl_scale, lut, src_bs, bs, (int)h->frame_no);
+            break;
+        case LPCL_COL16_1024:
+            hipLaunchKernelGGL(clahe_lut_kernel2<1024>, lg, lb, 0, is, d_img, d.W, d.H, stride, h->cl_tx, h->cl_tw, h->cl_th, h->cl_clip, h->cl_scale, lut, src_bs, bs, (int)h->frame_no);
+            break;
+        case LPCL_WAVE32:
+            hipLaunchKernelGGL(clahe_lut_kernel, lg, lb, 0, is, d_img, d.W, d.H, stride, h->cl_tx, h->cl_tw, h->cl_th, h->cl_clip, h->cl_scale, lut, src_bs, bs, (int)h->frame_no);
+            break;
+        }
+        switch (f.clahe_interp) {
+        case LPCI_NONE: break;
+        case LPCI_PX4:
+            hipLaunchKernelGGL(clahe_interp_kernel4, ig, ib, 0, is, d_img, d.W, d.H, stride, h->cl_tx, h->cl_ty, 1.0f / (float)h->cl_tw, 1.0f / (float)h->cl_th, lut, eq, src_bs, bs);
+            break;
+        case LPCI_PX1:
+            hipLaunchKernelGGL(clahe_interp_kernel, ig, ib, 0, is, d_img, d.W, d.H, stride, h->cl_tx, h->cl_ty, 1.0f / (float)h->cl_tw, 1.0f / (float)h->cl_th, lut, eq, src_bs, bs);
+            break;
+        }
         d_img = eq; stride = d.W; src_bs = bs;
-        if (h->runahead) {   // the side stream (KLT) waits for the pyramid of the equalised image; the detector follows on the image stream itself
-            // the pyramid rides on the image stream: it needs nothing from the side stream's chain (KLT(k-1), RANSAC, book-keeping), which is
-            // the longest serial chain of the front end — 19 us less of it; the image chain has the slack
-            launch_pyramid(cs);
-            pyramid_done = true;
-            // klt_kernel3 polls the chain's counter itself (no barrier packet on the side stream) — on a handle whose four streams own their hardware queues only (the first
-            // live handle of the process, make_stream): 200 polling workgroups per frame in front of kernels of OTHER handles on a shared queue timed the eight-handle
-            // leg of the bench out (a consumer may only spin where everything it waits for was submitted earlier to queues nobody else feeds)
-            // ... and not on a handle that runs the sharded frame over a real collective, nor at long windows (6n > 96: the Cholesky factor's launches share the
-            // copy queue): with the forced-sharded cfg E run of the bench two runs in six stalled for the poll's full 30 s (none in six without it) — more busy
-            // queues than the command processor keeps resident, and a queue of spinning workgroups in front of the one that would release them
-            if (h->dev_sync && h->private_queues && !h->queues_shared && !h->extra_queues && 6 * h->dc.nmax <= 96 && !h->wide_px) {
-                h->pyr_signal = &h->stage_sync->pyr[h->ic];      // bumped by the detector's first launch on this queue (detect_dev), right behind the pyramid
-                h->stage_tgt.pyr[h->ic]++;
-                h->klt_wait = &h->stage_sync->pyr[h->ic]; h->klt_target = h->stage_tgt.pyr[h->ic];
+        if (f.pyr_on_image) {   // the side stream (KLT) waits for the pyramid of the equalised image; the detector follows on the image stream itself
+            launch_pyramid(is);
+            if (f.klt_polls_pyramid) {   // the counter is bumped by the detector's first launch on this queue (detect_dev), right behind the pyramid
+                h->stage_tgt.pyr[f.ic]++;
+                klt->counter = &h->stage_sync->pyr[f.ic]; klt->target = h->stage_tgt.pyr[f.ic];
             } else {
-                HIPCHK(h, hipEventRecord(h->evC[h->ic], cs));
-                HIPCHK(h, hipStreamWaitEvent(h->stream_d, h->evC[h->ic], 0));
+                HIPCHK(h, hipEventRecord(h->evC[f.ic], is));
+                HIPCHK(h, hipStreamWaitEvent(h->stream_d, h->evC[f.ic], 0));
             }
-            forked = true;
         }
     }
-    h->side = h->ts;
-    if (h->use_det) {   // FeatureDetector::DetectWithSubPix on the image the tracker sees (Tracker.cc:207,350)
-        // fork: pyramid / KLT / RANSAC go to the side stream (the image is complete on ts here), the detector stays on ts
-        if (!forked) {
-            HIPCHK(h, hipEventRecord(h->evD0, image_stream(h)));
+    if (f.use_det) {   // FeatureDetector::DetectWithSubPix on the image the tracker sees (Tracker.cc:207,350)
+        if (f.fork_side) {   // fork: pyramid / KLT / RANSAC go to the side stream (the image is complete on the image stream here), the detector stays
+            HIPCHK(h, hipEventRecord(h->evD0, is));
             HIPCHK(h, hipStreamWaitEvent(h->stream_d, h->evD0, 0));
         }
-        h->side = h->stream_d;
-        // run-ahead: book-keeping(k-1) ran on the side stream; its hand-over event also says that mbIsTheFirstImage is final
-        // ... until the flag has gone to 0 in every instance (it never comes back: Tracker.cc:233): the host sees that in the mirror
-        // book-keeping writes (a stale 1 only keeps the wait one frame longer) and the detector chain then paces itself
-        if (!h->first_cleared) {
-            bool all0 = true;
-            for (int i = 0; i < h->batch && all0; ++i) all0 = ((volatile int*)h->first_mirror)[i] == 0;
-            h->first_cleared = all0;
-        }
-        const hipEvent_t flag = (h->runahead && h->frame_no >= 1 && !h->first_cleared) ? h->evT[(h->frame_no - 1) & 3] : nullptr;
-        const int rc = detect_dev(h, d_img, stride, src_bs, flag);
+        const int rc = detect_dev(h, f, d_img, stride, src_bs);
         if (rc != RVIO_OK) return rc;
-        // corners of frame k ready (the refill half of book-keeping on the side stream waits for it): a one-workgroup signal behind
-        // cornerSubPix that book-keeping polls, or a stream-level event
-        // (one counter per image chain: each has ONE producer queue, so "count >= the frames this chain has been handed" means THIS frame's corners)
-        if (h->dev_sync) { hipLaunchKernelGGL(stage_signal_kernel, dim3(1), dim3(64), 0, image_stream(h), &h->stage_sync->corners[h->ic]); h->stage_tgt.corners[h->ic]++; }
-        else if (h->runahead) HIPCHK(h, hipEventRecord(h->evD1, image_stream(h)));
+        switch (f.corners) {   // corners of frame k ready: the refill half of book-keeping on the side stream waits for it
+        case LPA_NONE: break;
+        case LPA_SIGNAL: hipLaunchKernelGGL(stage_signal_kernel, dim3(1), dim3(64), 0, is, &h->stage_sync->corners[f.ic]); h->stage_tgt.corners[f.ic]++; break;
+        case LPA_EVENT: HIPCHK(h, hipEventRecord(h->evD1, is)); break;
+        }
     }
-    if (!pyramid_done) launch_pyramid(h->side);
+    if (!f.pyr_on_image) launch_pyramid(stream_of(h, f.pyr, f.ic));
     HIPCHK(h, hipGetLastError());
     return RVIO_OK;
 }
 
 // everything after Tracker.cc:246; status/tracked already on the device
-static int post_klt_dev(rvio_hip* h, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand) {
+static int post_klt_dev(rvio_hip* h, const FrontForms& f, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand, const BookWait& bw, BookOut* out) {
     const size_t bs = h->slab_bytes;
-    const unsigned B = (unsigned)h->batch;
-    // run-ahead mode: RANSAC rides in the launch of book-keeping's hand-over half (both one workgroup, back to back on the side stream)
-    const bool fused = h->use_det && h->runahead;
-    if (!fused)
-    hipLaunchKernelGGL(ransac_kernel, dim3(1, 1, B), dim3(256), (size_t)8 * h->dc.F + 16, h->side, h->dc, h->t.n_pts, h->t.tracked, h->t.un1, h->t.un2,
-                       h->t.status, d_imu, m, h->rng, h->d_info, bs, h->imu_bs);
-    h->tail = h->ts;
-    h->handover_evt = false;
-    const unsigned long long* done = nullptr; unsigned long long done_target = 0;
-    const unsigned long long* corners = nullptr; unsigned long long corners_target = 0;
-    if (h->use_det) {   // the detector's corner list replaces the caller's
-        const float* xy = h->det_xy2[h->dslot];
-        const int* nout = h->det_nout + h->dslot;
-        if (h->runahead) {   // book-keeping on the side stream, behind RANSAC: the hand-over half once filter(k-2) has let go of the tables, the refill half once the corners are there
-            if (h->book_wait) HIPCHK(h, hipStreamWaitEvent(h->side, h->book_wait, 0));
-            h->book_wait = nullptr;
-            if (h->book_dev) { done = &h->stage_sync->aug; done_target = h->book_target; }
-            h->book_dev = false;
-            h->tail = h->side;
-            unsigned long long* hand = nullptr;
-            if (h->dev_sync) { hand = &h->stage_sync->handover; h->stage_tgt.handover++; }
-            // one stream, device-side counters: RANSAC and both halves of book-keeping are ONE launch (the refill half polls the detector's counter inside it)
-            if (h->dev_sync && h->plan.book_fused) {
-                h->gate_pending = true; h->gate_target = h->stage_tgt.handover;
-                hipLaunchKernelGGL(ransac_book_kernel, dim3(1, 1, B), dim3(64 * h->plan.book_waves), h->plan.book_lds, h->tail, h->dc, h->t, d_imu, m, h->rng, bs, h->imu_bs,
-                                   done, done_target, h->meta, hand, xy, nout, &h->stage_sync->corners[h->ic], h->stage_tgt.corners[h->ic]);
-                HIPCHK(h, hipGetLastError());
-                return RVIO_OK;
-            }
-            hipLaunchKernelGGL(ransac_book_a_kernel, dim3(1, 1, B), dim3(256), (size_t)8 * h->dc.F + 16, h->tail, h->dc, h->t, d_imu, m, h->rng, bs, h->imu_bs,
-                               done, done_target, h->meta, hand);
-            // the Updater's input is complete: the filter of this frame waits for THIS — the gate kernel on the filter stream polls the
-            // counter the launch above bumps, and the refill half below polls the detector's; or two stream-level events
-            if (h->dev_sync) { h->gate_pending = true; h->gate_target = h->stage_tgt.handover; corners = &h->stage_sync->corners[h->ic]; corners_target = h->stage_tgt.corners[h->ic]; }
-            else {
-                HIPCHK(h, hipEventRecord(h->evH[h->frame_no & 3], h->tail));
-                h->handover_evt = true;
-                HIPCHK(h, hipStreamWaitEvent(h->side, h->evD1, 0));
-            }
-        } else {             // join the side stream (long finished when the detector is)
-            HIPCHK(h, hipEventRecord(h->evD1, h->side));
-            HIPCHK(h, hipStreamWaitEvent(h->ts, h->evD1, 0));
-            hipLaunchKernelGGL(bookkeep_a_kernel, dim3(1, 1, B), dim3(256), 0, h->tail, h->dc, h->t, bs, done, done_target, h->meta, (unsigned long long*)nullptr);
+    const hipStream_t base = stream_of(h, f.base, f.ic), side = stream_of(h, f.side, f.ic), tail = stream_of(h, f.book, f.ic);
+    const LpLaunch &lr = f.ransac_l, &la = f.book_a_l, &lb = f.book_b_l;
+    const float* xy = h->det_xy2[f.dslot];      // the detector's corner list replaces the caller's
+    const int* nout = h->det_nout + f.dslot;
+    const unsigned long long* const no_counter = nullptr;
+    *out = BookOut{};
+    switch (f.book_form) {
+    case LPB_PLAIN:
+        hipLaunchKernelGGL(ransac_kernel, lp_grid(lr), lp_block(lr), lr.lds, side, h->dc, h->t.n_pts, h->t.tracked, h->t.un1, h->t.un2, h->t.status, d_imu, m, h->rng, h->d_info, bs, h->imu_bs);
+        hipLaunchKernelGGL(bookkeep_a_kernel, lp_grid(la), lp_block(la), 0, base, h->dc, h->t, (size_t)0, no_counter, 0ull, h->meta, (unsigned long long*)nullptr);
+        hipLaunchKernelGGL(bookkeep_b_kernel, lp_grid(lb), lp_block(lb), lb.lds, base, h->dc, h->t, d_cand, n_cand, (const int*)nullptr, (size_t)0, no_counter, 0ull, h->meta);
+        break;
+    case LPB_JOIN:   // join the side stream (long finished when the detector is)
+        hipLaunchKernelGGL(ransac_kernel, lp_grid(lr), lp_block(lr), lr.lds, side, h->dc, h->t.n_pts, h->t.tracked, h->t.un1, h->t.un2, h->t.status, d_imu, m, h->rng, h->d_info, bs, h->imu_bs);
+        HIPCHK(h, hipEventRecord(h->evD1, side));
+        HIPCHK(h, hipStreamWaitEvent(base, h->evD1, 0));
+        hipLaunchKernelGGL(bookkeep_a_kernel, lp_grid(la), lp_block(la), 0, tail, h->dc, h->t, bs, no_counter, 0ull, h->meta, (unsigned long long*)nullptr);
+        hipLaunchKernelGGL(bookkeep_b_kernel, lp_grid(lb), lp_block(lb), lb.lds, tail, h->dc, h->t, xy, 0, nout, bs, no_counter, 0ull, h->meta);
+        break;
+    case LPB_FUSED:
+    case LPB_PAIR: {   // book-keeping on the side stream, behind RANSAC: the hand-over half once the filter that read the table last has let go of it, the refill half once the corners are there
+        if (bw.evt) HIPCHK(h, hipStreamWaitEvent(side, bw.evt, 0));
+        const unsigned long long* done = bw.dev ? &h->stage_sync->aug : nullptr;
+        const unsigned long long done_target = bw.dev ? bw.target : 0;
+        unsigned long long* hand = nullptr;
+        if (f.dev_sync) { hand = &h->stage_sync->handover; h->stage_tgt.handover++; }
+        if (f.book_form == LPB_FUSED) {
+            out->gate = true; out->gate_target = h->stage_tgt.handover;
+            hipLaunchKernelGGL(ransac_book_kernel, lp_grid(lr), lp_block(lr), lr.lds, tail, h->dc, h->t, d_imu, m, h->rng, bs, h->imu_bs,
+                               done, done_target, h->meta, hand, xy, nout, &h->stage_sync->corners[f.ic], h->stage_tgt.corners[f.ic]);
+            break;
         }
-        hipLaunchKernelGGL(bookkeep_b_kernel, dim3(1, 1, B), dim3(64 * h->plan.book_waves), h->plan.book_lds, h->tail, h->dc, h->t, xy, 0, nout, bs, corners, corners_target, h->meta);
-    } else {
-        hipLaunchKernelGGL(bookkeep_a_kernel, dim3(1), dim3(256), 0, h->ts, h->dc, h->t, (size_t)0, (const unsigned long long*)nullptr, 0ull, h->meta, (unsigned long long*)nullptr);
-        hipLaunchKernelGGL(bookkeep_b_kernel, dim3(1), dim3(64 * h->plan.book_waves), h->plan.book_lds, h->ts, h->dc, h->t, d_cand, n_cand, (const int*)nullptr, (size_t)0,
-                           (const unsigned long long*)nullptr, 0ull, h->meta);
+        hipLaunchKernelGGL(ransac_book_a_kernel, lp_grid(lr), lp_block(lr), lr.lds, tail, h->dc, h->t, d_imu, m, h->rng, bs, h->imu_bs, done, done_target, h->meta, hand);
+        // the Updater's input is complete: the filter of this frame waits for THIS — the gate kernel on the filter stream polls the
+        // counter the launch above bumps, and the refill half below polls the detector's; or two stream-level events
+        const unsigned long long* corners = nullptr; unsigned long long corners_target = 0;
+        if (f.dev_sync) { out->gate = true; out->gate_target = h->stage_tgt.handover; corners = &h->stage_sync->corners[f.ic]; corners_target = h->stage_tgt.corners[f.ic]; }
+        else {
+            HIPCHK(h, hipEventRecord(h->evH[h->frame_no & 3], tail));
+            out->handover_evt = true;
+            HIPCHK(h, hipStreamWaitEvent(side, h->evD1, 0));
+        }
+        hipLaunchKernelGGL(bookkeep_b_kernel, lp_grid(lb), lp_block(lb), lb.lds, tail, h->dc, h->t, xy, 0, nout, bs, corners, corners_target, h->meta);
+        break;
+    }
     }
     HIPCHK(h, hipGetLastError());
     return RVIO_OK;
 }
 
-static int track_dev_impl(rvio_hip* h, const uint8_t* d_img, int stride, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand) {
+static int track_dev_impl(rvio_hip* h, const FrontForms& f, const uint8_t* d_img, int stride, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand,
+                          const BookWait& bw, BookOut* out) {
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->piped && h->ts == h->stream) SYNC_FRONT(h);
+    if (h->piped && !f.piped) SYNC_FRONT(h);
     int rc;
-    h->use_det = (d_cand == nullptr);   // no corner list from the caller: run FeatureDetector::DetectWithSubPix on the device
-    if (h->use_det && (rc = detector_init(h)) != RVIO_OK) return rc;
-    const bool piped_call = h->ts == h->stream_t;
-    h->par = piped_call ? (int)(h->frame_no & 1) : 0;
-    h->runahead = piped_call && h->use_det && !no_runahead();
-    h->dev_sync = h->runahead && h->batch == 1 && !no_device_polls();
-    h->gate_pending = false;
-    h->dslot = h->runahead ? (int)(h->frame_no % 3) : h->par;
-    h->ic = h->runahead ? (int)(h->frame_no % h->plan.n_ic) : h->par;
+    if (f.use_det && (rc = detector_init(h)) != RVIO_OK) return rc;
     const int nb = (h->pyr_cur + 1) % 4;   // pyramid of the new image; pyr_cur holds mLastImage's (slot nb was last read by KLT(k-3))
-    rc = build_pyramid_dev(h, d_img, stride, nb);
+    KltWait kw;
+    rc = build_pyramid_dev(h, f, d_img, stride, nb, &kw);
     if (rc != RVIO_OK) return rc;
-    if (h->wide_px)    // batch handles of >= 8 instances: the throughput form, four features per wave
-        hipLaunchKernelGGL(klt_kernel16, dim3((h->dc.F + 3) / 4, 1, h->batch), dim3(64), 0, h->side, h->pyr[h->pyr_cur], h->pyr[nb], h->dc.levels, h->t.n_pts, h->t.feats,
-                           h->t.tracked, h->t.status, h->slab_bytes);
-    else
-        hipLaunchKernelGGL(klt_kernel3, dim3(h->dc.F, 1, h->batch), dim3(64), 0, h->side, h->pyr[h->pyr_cur], h->pyr[nb], h->dc.levels, h->t.n_pts, h->t.feats,
-                           h->t.tracked, h->t.status, h->slab_bytes, h->klt_wait, h->klt_target, h->meta);
-    h->klt_wait = nullptr;
-    rc = post_klt_dev(h, d_imu, m, d_cand, std::min(n_cand, h->dc.F));
+    const hipStream_t side = stream_of(h, f.side, f.ic);
+    switch (f.klt) {
+    case LPKL_K16:
+        hipLaunchKernelGGL(klt_kernel16, lp_grid(f.klt_l), lp_block(f.klt_l), 0, side, h->pyr[h->pyr_cur], h->pyr[nb], h->dc.levels, h->t.n_pts, h->t.feats, h->t.tracked, h->t.status, h->slab_bytes);
+        break;
+    case LPKL_K3:
+        hipLaunchKernelGGL(klt_kernel3, lp_grid(f.klt_l), lp_block(f.klt_l), 0, side, h->pyr[h->pyr_cur], h->pyr[nb], h->dc.levels, h->t.n_pts, h->t.feats, h->t.tracked, h->t.status, h->slab_bytes,
+                           kw.counter, kw.target, h->meta);
+        break;
+    }
+    rc = post_klt_dev(h, f, d_imu, m, d_cand, std::min(n_cand, h->dc.F), bw, out);
     h->pyr_cur = nb;   // im.copyTo(mLastImage), Tracker.cc:395
+    h->last.dslot = f.dslot;
+    if (f.use_det) h->last.det_set = f.det_set;
+    if (f.gray != LPGR_NONE) { h->last.gray_src = d_img; h->last.gray_stride = stride; h->last.gray_bs = h->img_bs; }
     return rc;
 }
 int rvio_hip_track_dev(rvio_hip* h, const uint8_t* d_img, int stride, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand) {
     if (!h || !d_img || m < 0 || n_cand < 0 || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
-    return track_dev_impl(h, d_img, stride, d_imu, m, d_cand, n_cand);
+    if (!d_cand) refresh_first_cleared(h);
+    const FrontForms f = call_forms(h, false, d_cand != nullptr, d_img, stride, h->img_bs);   // a per-stage call: everything on the filter stream
+    BookOut bo;
+    return track_dev_impl(h, f, d_img, stride, d_imu, m, d_cand, n_cand, BookWait{}, &bo);
 }
 
 int rvio_hip_track(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* imu, int m, const float* cand_xy, int n_cand) {
@@ -1648,9 +1645,9 @@ int rvio_hip_track_points(rvio_hip* h, const float* tracked_xy, const unsigned c
     if (m > 0) HIPCHK(h, hipMemcpyAsync(h->d_imu, imu, sizeof(rvio_imu) * m, hipMemcpyHostToDevice, h->stream));
     if (nc > 0) HIPCHK(h, hipMemcpyAsync(h->d_cand, cand_xy, sizeof(float) * 2 * nc, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(load_points_kernel, dim3(8), dim3(256), 0, h->stream, h->t.n_pts, h->d_in_xy, h->d_in_st, h->t.tracked, h->t.status);   // (single instance only)
-    h->use_det = false;   // no image in this mode
-    h->side = h->ts;
-    return post_klt_dev(h, h->d_imu, m, h->d_cand, nc);
+    const FrontForms f = call_forms(h, false, true, nullptr, 0, 0);   // no image in this mode: the caller's corner list, everything on the filter stream
+    BookOut bo;
+    return post_klt_dev(h, f, h->d_imu, m, h->d_cand, nc, BookWait{}, &bo);
 }
 
 int rvio_hip_get_tracks(rvio_hip* h, int32_t* n_feat, unsigned char* types, int32_t* len, float* meas) {
@@ -1778,22 +1775,27 @@ int rvio_hip_frame_tracks_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride
 // on its own stream while frame k-1's propagate/update/augment still occupy the filter stream.  The Tracker -> Updater
 // hand-over is double-buffered; two events per buffer order (a) update(k) after track(k), (b) track(k+2) after update(k).
 // PreIntegrator::propagate needs nothing from the tracker either: it is enqueued first and runs beside the front end.
-static int frame_dev_impl(rvio_hip* h, const uint8_t* d_img, int stride, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand, bool staged,
+// the forms of a whole-frame call (the entry points compute them: rvio_hip_frame needs the mode ahead of its staging copies)
+static FrontForms frame_forms(rvio_hip* h, const uint8_t* d_img, int stride, const float* d_cand) {
+    if (!d_cand) refresh_first_cleared(h);
+    return call_forms(h, true, d_cand != nullptr, d_img, stride, h->img_bs);
+}
+static int frame_dev_impl(rvio_hip* h, const FrontForms& f, const uint8_t* d_img, int stride, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand, bool staged,
                           bool begin_only = false, bool defer_propagate = false) {   // defer_propagate: the caller runs update_local_dev itself right behind (the sharded frame)
     if (h->in_frame) { h->err = "rvio_hip_frame_begin_dev without rvio_hip_frame_end"; return RVIO_ERR_INVALID; }
     const int b = (int)(h->frame_no & 1);                   // parity: the staging of rvio_hip_frame
     const int hb = (int)(h->frame_no % rvio_hip::kHand);    // hand-over table of this frame
     h->t.n_feat = h->tout[hb].n_feat; h->t.types = h->tout[hb].types; h->t.len = h->tout[hb].len; h->t.meas = h->tout[hb].meas;
-    const bool ra = !d_cand && !no_runahead();   // run-ahead mode (track_dev_impl): book-keeping runs on the side stream
+    BookWait bw;   // run-ahead mode: book-keeping runs on the side stream, and what it has to wait for goes there with it
     if (h->frame_no >= rvio_hip::kHand) {   // the filter of frame k - kHand has consumed this hand-over buffer: only the stream that runs book-keeping has to know.
         // (In run-ahead mode the image chains — CLAHE, detector — never touch the hand-over: making them wait here tied image(k) to
         // filter(k-2) and with it the frame period to image chain + filter chain over two frames.)
         // Run-ahead: of the side stream's chain (pyramid, KLT, RANSAC, book-keeping) only book-keeping writes the hand-over, so the wait
         // goes right in front of it (post_klt_dev) — at the head of the frame it tied KLT(k) to filter(k-2) and made
         // [side chain + filter chain] the period of two frames.
-        if (!ra) { int rcw = wait_filter_done(h, hb, h->stream_t); if (rcw == RVIO_OK) rcw = wait_filter_done(h, hb, h->stream_d); if (rcw != RVIO_OK) return rcw; }
-        else if (h->fin_mode[hb] == 0) h->book_wait = h->evF[hb];
-        else { h->book_dev = true; h->book_target = h->fin_target[hb]; }
+        if (!f.runahead) { int rcw = wait_filter_done(h, hb, h->stream_t); if (rcw == RVIO_OK) rcw = wait_filter_done(h, hb, h->stream_d); if (rcw != RVIO_OK) return rcw; }
+        else if (h->fin_mode[hb] == 0) bw.evt = h->evF[hb];
+        else { bw.dev = true; bw.target = h->fin_target[hb]; }
     } else if (!h->piped) HIPCHK(h, hipStreamSynchronize(h->stream));   // first pipelined frame: everything enqueued so far is done
     h->piped = true;
     if (m < 0) return RVIO_ERR_INVALID;
@@ -1817,17 +1819,14 @@ static int frame_dev_impl(rvio_hip* h, const uint8_t* d_img, int stride, const r
     if (!fuse) rc = propagate_dev(h, d_imu, m, h->imu_bs);
     if (rc != RVIO_OK) return rc;
     const double t1 = dbg_host ? now() : 0;
-    h->ts = h->stream_t;
-    rc = track_dev_impl(h, d_img, stride, d_imu, m, d_cand, n_cand);
-    h->ts = h->stream;
+    BookOut bo;
+    rc = track_dev_impl(h, f, d_img, stride, d_imu, m, d_cand, n_cand, bw, &bo);
     if (rc != RVIO_OK) return rc;
     const double t2 = dbg_host ? now() : 0;
-    HIPCHK(h, hipEventRecord(h->evT[h->frame_no & 3], h->tail));      // behind book-keeping, on the stream that ran it
+    HIPCHK(h, hipEventRecord(h->evT[h->frame_no & 3], stream_of(h, f.book, f.ic)));      // behind book-keeping, on the stream that ran it
     // the filter needs the hand-over, not the refill: in run-ahead mode it waits for the first half of book-keeping only
-    if (h->gate_pending) {
-        hipLaunchKernelGGL(stage_gate_kernel, dim3(1), dim3(64), 0, h->stream, &h->stage_sync->handover, h->gate_target, h->meta, h->t.n_feat, (int)h->frame_no);
-        h->gate_pending = false;
-    } else HIPCHK(h, hipStreamWaitEvent(h->stream, h->handover_evt ? h->evH[h->frame_no & 3] : h->evT[h->frame_no & 3], 0));
+    if (bo.gate) hipLaunchKernelGGL(stage_gate_kernel, dim3(1), dim3(64), 0, h->stream, &h->stage_sync->handover, bo.gate_target, h->meta, h->t.n_feat, (int)h->frame_no);
+    else HIPCHK(h, hipStreamWaitEvent(h->stream, bo.handover_evt ? h->evH[h->frame_no & 3] : h->evT[h->frame_no & 3], 0));
     const double t3 = dbg_host ? now() : 0;
     if (begin_only) {   // the caller sequences update / augment itself, then rvio_hip_frame_end
         h->in_frame = true;
@@ -1841,7 +1840,7 @@ static int frame_dev_impl(rvio_hip* h, const uint8_t* d_img, int stride, const r
     const double t4 = dbg_host ? now() : 0;
     // the filter of this frame is finished when ... single instance in run-ahead mode: its last kernel has bumped the device-side counter
     // (book-keeping of frame k+2 polls it); otherwise an event behind it
-    if (ra && h->batch == 1 && !no_device_polls()) { h->fin_mode[hb] = 1; h->fin_target[hb] = h->stage_tgt.aug; }
+    if (f.filter_done_by_counter) { h->fin_mode[hb] = 1; h->fin_target[hb] = h->stage_tgt.aug; }
     else { HIPCHK(h, hipEventRecord(h->evF[hb], h->stream)); h->fin_mode[hb] = 0; }
     if (dbg_host) {
         const double t5 = now();
@@ -1856,7 +1855,7 @@ int rvio_hip_frame_dev(rvio_hip* h, const uint8_t* d_img, int stride, const rvio
     if (!h || !d_img || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
-    return frame_dev_impl(h, d_img, stride, d_imu, m, d_cand, n_cand, false);
+    return frame_dev_impl(h, frame_forms(h, d_img, stride, d_cand), d_img, stride, d_imu, m, d_cand, n_cand, false);
 }
 // One camera frame of EVERY instance of a batch handle created with its front end: d_imgs[B] (instance stride img_stride bytes,
 // row stride `stride`), d_imu[B][imu_stride] (0: shared).  Same pipelined body as rvio_hip_frame_dev, every launch with gridDim.z = B;
@@ -1867,7 +1866,7 @@ int rvio_hip_frame_batch_dev(rvio_hip* h, const uint8_t* d_imgs, int stride, siz
     if (h->batch > 1 && img_stride < (size_t)stride * h->dc.H) return RVIO_ERR_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
     h->img_bs = img_stride; h->imu_bs = (size_t)imu_stride * sizeof(rvio_imu);
-    const int rc = frame_dev_impl(h, d_imgs, stride, d_imu, m, nullptr, 0, false);
+    const int rc = frame_dev_impl(h, frame_forms(h, d_imgs, stride, nullptr), d_imgs, stride, d_imu, m, nullptr, 0, false);
     h->img_bs = 0; h->imu_bs = 0;
     return rc;
 }
@@ -1880,7 +1879,7 @@ int rvio_hip_frame_begin_dev(rvio_hip* h, const uint8_t* d_img, int stride, cons
     if (!h || !d_img || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
-    return frame_dev_impl(h, d_img, stride, d_imu, m, d_cand, n_cand, false, /*begin_only=*/true);
+    return frame_dev_impl(h, frame_forms(h, d_img, stride, d_cand), d_img, stride, d_imu, m, d_cand, n_cand, false, /*begin_only=*/true);
 }
 int rvio_hip_frame_end(rvio_hip* h) {
     if (!h || !h->in_frame) return RVIO_ERR_INVALID;
@@ -1930,7 +1929,7 @@ int rvio_hip_frame_sharded_dev(rvio_hip* h, const uint8_t* d_img, int stride, co
         h->allocs.push_back(q);
         h->gathered = (double*)q; h->gathered_world = world;
     }
-    int rc = frame_dev_impl(h, d_img, stride, d_imu, m, d_cand, n_cand, false, /*begin_only=*/true, /*defer_propagate=*/true);
+    int rc = frame_dev_impl(h, frame_forms(h, d_img, stride, d_cand), d_img, stride, d_imu, m, d_cand, n_cand, false, /*begin_only=*/true, /*defer_propagate=*/true);
     if (rc != RVIO_OK) return rc;
     h->img_count++;
     if (h->n_clones_host > h->cfg.min_track_len - 1) {   // System.cc:266
@@ -1986,7 +1985,9 @@ int rvio_hip_frame(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* 
     else for (int y = 0; y < h->dc.H; ++y) std::memcpy(pp + (size_t)y * rowb, img + (size_t)y * stride, rowb);
     if (m > 0) std::memcpy(pp + h->pin_imu, imu, sizeof(rvio_imu) * m);
     if (nc > 0) std::memcpy(pp + pin_cand, cand_xy, sizeof(float) * 2 * nc);
-    const bool ra = !cand_xy && !no_runahead();
+    // the forms of this frame, ahead of the staging copies: which streams they go to depends on the mode
+    const FrontForms f = frame_forms(h, h->hb_img[b], (int)rowb, cand_xy);
+    const bool ra = f.runahead;
     int imu_slot = b;
     if (ra) {
         // run-ahead mode.  The IMU batch goes to the SIDE stream (RANSAC runs there; propagate on the filter stream waits for evIn): it
@@ -1999,12 +2000,12 @@ int rvio_hip_frame(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* 
         if (m > 0) HIPCHK(h, hipMemcpyAsync(h->hb_imu[imu_slot], pp + h->pin_imu, sizeof(rvio_imu) * m, hipMemcpyHostToDevice, h->stream_d));
         HIPCHK(h, hipEventRecord(h->evIn[b], h->stream_d));
         HIPCHK(h, hipEventRecord(h->evPin[ps], h->stream_d));
-        // The image goes to the stream of this frame's image chain (image_stream: tracker stream / fourth stream by parity).  hb_img[b]
+        // The image goes to the stream of this frame's image chain (tracker stream / fourth stream in rotation).  hb_img[b]
         // was last read by frame k-2: its CLAHE / detector (same stream, earlier) and — without the equaliser — its pyramid on the side
         // stream, which book-keeping(k-2) followed.
         // (A colour format: hb_img[b] holds the interleaved pixels and has ONE reader, gray_kernel(k-2), the first launch of that frame's image
         // chain — on this very stream, since k-2 and k share their image chain with one or two chains in flight; the wait below is then more than needed.)
-        hipStream_t is = image_stream_of(h, (int)(h->frame_no % h->plan.n_ic));
+        hipStream_t is = stream_of(h, f.image, f.ic);
         if (h->frame_no >= 2) HIPCHK(h, hipStreamWaitEvent(is, h->evT[(h->frame_no - 2) & 3], 0));
         HIPCHK(h, hipMemcpyAsync(h->hb_img[b], pp, npx, hipMemcpyHostToDevice, is));
         HIPCHK(h, hipEventRecord(h->evPin2[ps], is));
@@ -2023,7 +2024,7 @@ int rvio_hip_frame(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* 
         HIPCHK(h, hipStreamSynchronize(h->stream_t));
         if (h->stream_c) HIPCHK(h, hipStreamSynchronize(h->stream_c));
     }
-    return frame_dev_impl(h, h->hb_img[b], (int)rowb, h->hb_imu[imu_slot], m, cand_xy ? h->hb_cand[b] : nullptr, nc, true);
+    return frame_dev_impl(h, f, h->hb_img[b], (int)rowb, h->hb_imu[imu_slot], m, cand_xy ? h->hb_cand[b] : nullptr, nc, true);
 }
 // direct-track variant of the whole frame (host inputs)
 int rvio_hip_frame_points(rvio_hip* h, const float* tracked_xy, const unsigned char* status, int n_pts,
@@ -2086,11 +2087,11 @@ int rvio_hip_get_corners(rvio_hip* h, int32_t* n, float* xy, float* raw_xy, floa
     SYNC_FRONT(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     int cnt = 0;
-    HIPCHK(h, hipMemcpyAsync(&cnt, h->det_nout + h->dslot, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&cnt, h->det_nout + h->last.dslot, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (n) *n = cnt;
-    if (xy && cnt > 0) HIPCHK(h, hipMemcpyAsync(xy, h->det_xy2[h->dslot], sizeof(float) * 2 * cnt, hipMemcpyDeviceToHost, h->stream));
-    const DetDev& ds_ = h->dets[h->det_set_last];
+    if (xy && cnt > 0) HIPCHK(h, hipMemcpyAsync(xy, h->det_xy2[h->last.dslot], sizeof(float) * 2 * cnt, hipMemcpyDeviceToHost, h->stream));
+    const DetDev& ds_ = h->dets[h->last.det_set];
     if (raw_xy && cnt > 0) HIPCHK(h, hipMemcpyAsync(raw_xy, ds_.raw_xy, sizeof(float) * 2 * cnt, hipMemcpyDeviceToHost, h->stream));
     if (eig) {
         // the pipeline no longer stores the min-eigenvalue map (mineig_nms_kernel keeps it in LDS): recomputed on demand from the image the
@@ -2159,7 +2160,7 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
         HIPCHK(h, hipMemcpyAsync(bx, h->x[h->cur], sizeof(double) * d.xdmax, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(bP, h->P[h->cur], sizeof(double) * d.dmax * d.dmax, hipMemcpyDeviceToDevice, h->stream));
     }
-    if (which == 11 && (h->pix_ch < 2 || !h->gray_src)) { h->err = "no colour image has been handed over (rvio_hip_set_image_format)"; return RVIO_ERR_UNSUPPORTED; }
+    if (which == 11 && (h->pix_ch < 2 || !h->last.gray_src)) { h->err = "no colour image has been handed over (rvio_hip_set_image_format)"; return RVIO_ERR_UNSUPPORTED; }
     rvio_odom* odt = nullptr;
     if (which == 12) {   // (into a slot of its own: the ring stays what the frames wrote)
         if (!h->odom_ring) { h->err = "the odometry ring was never enabled (rvio_hip_set_odometry)"; return RVIO_ERR_UNSUPPORTED; }
@@ -2175,6 +2176,10 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
     // queue; the slab holds the factor of the last update): fw for a whole update, fs for one separately timed stage
     const bool pre = h->plan.solve9_nt && (h->plan.solve9_nt <= 6 || h->plan.chol_queue);
     const UpdateForms fw = forms_at(h, n, pre, true), fs = forms_at(h, n, pre, false);
+    // ... and the kernel forms a front-end call with the device detector gets on the last image handed over (1, 6, 9, 11)
+    const bool front_hook = which == 1 || which == 6 || which == 9 || which == 11;
+    if (front_hook && !h->front_end) { h->err = "this batch handle was created without its front end"; return RVIO_ERR_UNSUPPORTED; }
+    const FrontForms ff = front_hook ? call_forms(h, false, false, h->last.gray_src, h->last.gray_stride, h->last.gray_bs) : FrontForms();
     HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
     HIPCHK(h, hipEventRecord(e0, h->stream));
     for (int it = 0; it < iters; ++it) {
@@ -2192,8 +2197,8 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
             launch_feat_prop(h, n, h->time_imu, h->time_m, 0, 1);
         } else if (which == 9) {   // the detector's selection kernel (one workgroup: priority-ordered maximal independent set) on the candidates of the last detector call
             if (h->batch > 1 || !h->det_ready) return RVIO_ERR_UNSUPPORTED;
-            const DetDev q = [&] { DetDev v = h->dets[h->det_set_last]; v.xy = h->det_xy2[h->dslot]; v.n_out = h->det_nout + h->dslot; return v; }();
-            hipLaunchKernelGGL(greedy_kernel, dim3(1, 1, 1), dim3(GREEDY_T), GREEDY_LDS, h->stream, q, h->slab_bytes);
+            const DetDev q = det_view(h, h->last.det_set, h->last.dslot);
+            hipLaunchKernelGGL(greedy_kernel, lp_grid(ff.greedy_l), lp_block(ff.greedy_l), ff.greedy_l.lds, h->stream, q, h->slab_bytes);
         } else
         if (which == 0) {
             launch_solve(h, fw, n, h->block);   // as the frame's update launches it: dx = Pc y and the state injection are roles of the Joseph launch behind it (not run here)
@@ -2201,9 +2206,14 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
             // KLT as the frame ran it cannot be repeated (book-keeping has moved the features to where they were tracked): match the CURRENT
             // image back onto the PREVIOUS one from the current feature positions instead — the same displacement magnitudes, reversed, the
             // refilled corners included (they exist in the previous image too).  Outputs land in t.tracked / t.status (scratch between frames).
+            // (the form the frames of this handle get: klt_kernel16 once rvio_hip_debug_kernel_forms has switched it to the throughput forms)
             if (h->batch > 1) return RVIO_ERR_UNSUPPORTED;
-            hipLaunchKernelGGL(klt_kernel3, dim3(d.F), dim3(64), 0, h->stream, h->pyr[h->pyr_cur], h->pyr[(h->pyr_cur + 3) % 4], d.levels, h->t.n_pts, h->t.feats,
-                               h->t.tracked, h->t.status, (size_t)0, (const unsigned long long*)nullptr, 0ull, h->meta);
+            if (ff.klt == LPKL_K16)
+                hipLaunchKernelGGL(klt_kernel16, lp_grid(ff.klt_l), lp_block(ff.klt_l), 0, h->stream, h->pyr[h->pyr_cur], h->pyr[(h->pyr_cur + 3) % 4], d.levels, h->t.n_pts, h->t.feats,
+                                   h->t.tracked, h->t.status, (size_t)0);
+            else
+                hipLaunchKernelGGL(klt_kernel3, lp_grid(ff.klt_l), lp_block(ff.klt_l), 0, h->stream, h->pyr[h->pyr_cur], h->pyr[(h->pyr_cur + 3) % 4], d.levels, h->t.n_pts, h->t.feats,
+                                   h->t.tracked, h->t.status, (size_t)0, (const unsigned long long*)nullptr, 0ull, h->meta);
         } else if (which == 2) {
             launch_feat_build(h, n, 0, 1);   // (a batch handle: on the pose chains geom4_kernel left in the last update)
         } else if (which == 3) {   // reduction of the per-feature shares + rank truncation (reads `partial`, rewrites `block`: idempotent)
@@ -2214,11 +2224,11 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
             launch_ug_final(h, fw, n, h->block, h->P[h->cur ^ 1], true, true, false);   // (no solve ran ahead of the timed launch: no dx waits for its roles)
         } else if (which == 6) {   // cornerSubPix on the corners of the last detector call (reads raw_xy, rewrites xy with the same values)
             if (h->batch > 1 || !h->det_ready) return RVIO_ERR_UNSUPPORTED;
-            const DetDev q = [&] { DetDev v = h->dets[h->det_set_last]; v.xy = h->det_xy2[h->dslot]; v.n_out = h->det_nout + h->dslot; return v; }();
+            const DetDev q = det_view(h, h->last.det_set, h->last.dslot);
             const uint8_t* im = h->pyr[h->pyr_cur].img[0];   // level 0 of the current pyramid = the image the detector saw
-            launch_subpix(h, q, im, d.W, (size_t)0, 1u, 0, h->stream);
+            launch_subpix(h, ff, q, im, d.W, (size_t)0, 0, h->stream);
         } else if (which == 11) {   // gray_kernel on the last image handed over, in the form the frame launched, into the slot it wrote (the same values again)
-            launch_gray(h, h->gray_src, h->gray_stride, h->gray_bs, h->d_gray[h->gray_slot], h->stream);
+            launch_gray(h, ff, h->last.gray_src, h->last.gray_stride, h->last.gray_bs, h->d_gray[h->gray_slot], h->stream);
         } else return RVIO_ERR_INVALID;
     }
     HIPCHK(h, hipEventRecord(e1, h->stream));

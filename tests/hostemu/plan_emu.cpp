@@ -1,5 +1,6 @@
 // plan_emu.cpp — r-vio_amd/csrc/launch_plan.h compiled with g++: the launch geometry create_impl derives from a configuration, evaluated on the
-// CPU for every accepted (max_track_len, n_features, batch), and the forms of an update (update_forms) for every clone count of every window.
+// CPU for every accepted (max_track_len, n_features, batch), the forms of an update (update_forms) for every clone count of every window, and the
+// forms of a front-end call (front_forms) for every mode, geometry and environment a call can be made in.
 // tests/test_launch_plan.py feeds it the static LDS of each kernel as the built library's code object has it and checks static + dynamic against a CU's LDS.
 #include "../../r-vio_amd/csrc/launch_plan.h"
 #include <initializer_list>
@@ -61,6 +62,42 @@ int lp_forms(int max_len, int n_features, int batch, const size_t* statics, int 
     out[k++] = f.role_wgs;
     for (const LpLds* l : {&f.gram_lds, &f.lit_lds, &f.tprod_lds, &f.solve_lds, &f.ug_lds, &f.fin_lds}) { out[k++] = (long)l->bytes; out[k++] = l->kernel; }
     while (k < LP_FORMS_LEN) out[k++] = 0;
+    return 0;
+}
+
+// the forms of one front-end call of that configuration (front_forms).  in[LP_FRONT_IN]: the fields of FrontIn in the order below.  out[LP_FRONT_LEN]:
+// mode, synchronisation flags, stream roles, form enums, then (gx, gy, gz, threads, lds, kernel) of each launch in the order of FrontForms.  Returns plan.rc
+enum { LP_FRONT_IN = 18, LP_FRONT_LEN = 120 };
+int lp_front_in_len() { return LP_FRONT_IN; }
+int lp_front_len() { return LP_FRONT_LEN; }
+long lp_subpix_wide_lds_bytes(int win) { return (long)lp_subpix_wide_lds(win); }
+long lp_neigh_lds() { return LP_NEIGH_LDS; }
+long lp_greedy_lds() { return LP_GREEDY_LDS; }
+int lp_front_forms(int max_len, int n_features, int batch, const size_t* statics, const long* in, long* out) {
+    const LaunchPlan p = launch_plan(max_len, n_features, batch, statics);
+    if (p.rc) return p.rc;
+    FrontIn i;
+    int k = 0;
+    i.batch = batch; i.F = n_features; i.nmax = max_len - 1;
+    i.throughput = in[k++] != 0; i.W = (int)in[k++]; i.H = (int)in[k++];
+    i.equalizer = in[k++] != 0; i.cl_tx = (int)in[k++]; i.cl_ty = (int)in[k++]; i.cl_tw = (int)in[k++]; i.cl_th = (int)in[k++];
+    i.sp_win = (int)in[k++]; i.channels = (int)in[k++];
+    i.piped_call = in[k++] != 0; i.have_corner_list = in[k++] != 0; i.frame_no = in[k++]; i.first_cleared = in[k++] != 0; i.src_dword = in[k++] != 0;
+    i.no_runahead = in[k++] != 0; i.no_device_polls = in[k++] != 0; i.own_queues = in[k++] != 0;
+    const FrontForms f = front_forms(p, i);
+    k = 0;
+    out[k++] = f.use_det; out[k++] = f.piped; out[k++] = f.runahead; out[k++] = f.dev_sync; out[k++] = f.par; out[k++] = f.dslot; out[k++] = f.ic;
+    out[k++] = f.lut_set; out[k++] = f.det_set;
+    out[k++] = f.filter_done_by_counter; out[k++] = f.wait_book_k3; out[k++] = f.wait_first_flag; out[k++] = f.pyr_on_image; out[k++] = f.klt_polls_pyramid;
+    out[k++] = f.det_folds_signal; out[k++] = f.fork_side; out[k++] = f.corners;
+    out[k++] = f.base; out[k++] = f.image; out[k++] = f.pyr; out[k++] = f.side; out[k++] = f.book;
+    out[k++] = f.gray; out[k++] = f.clahe_lut; out[k++] = f.clahe_interp; out[k++] = f.pyramid; out[k++] = f.det_first; out[k++] = f.subpix; out[k++] = f.klt;
+    out[k++] = f.book_form;
+    for (const LpLaunch* l : {&f.gray_l, &f.clahe_lut_l, &f.clahe_interp_l, &f.pyramid_l, &f.det_first_l, &f.neigh_l, &f.greedy_l, &f.subpix_l, &f.klt_l,
+                              &f.ransac_l, &f.book_a_l, &f.book_b_l}) {
+        out[k++] = l->gx; out[k++] = l->gy; out[k++] = l->gz; out[k++] = l->threads; out[k++] = (long)l->lds; out[k++] = l->kernel;
+    }
+    while (k < LP_FRONT_LEN) out[k++] = 0;
     return 0;
 }
 

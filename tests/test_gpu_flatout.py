@@ -338,3 +338,47 @@ def test_recovery_after_a_stage_counter_time_out(gpu_required, stock_b):
     xb, Pb = h2.get_state()
     h2.close()
     assert np.array_equal(xa, xb) and np.array_equal(Pa, Pb)
+
+
+def run_mode_switch(d, sync_every):
+    """the frames of d through rvio_hip_frame, d["detector"][i] choosing the corner source of frame i; the pose is read behind every frame"""
+    from rvio_amd import hip
+    h = hip.RvioHip(d["cfg"])
+    h.initialize(*d["init"])
+    poses, updated = [], []
+    for i, (img, imu, cand) in enumerate(zip(d["imgs"], d["imus"], d["cands"])):
+        h.frame(img.copy(), imu.copy(), None if d["detector"][i] else cand.copy())
+        if sync_every:
+            h.sync()
+            updated.append(h.frame_info()["updated"])
+        p, q = h.pose()
+        poses.append(np.concatenate((p, q)))
+    h.sync()
+    x, P = h.get_state()
+    pts, hl = h.get_points()
+    info = h.frame_info()
+    h.close()
+    return dict(poses=np.array(poses), x=x, P=P, pts=pts, hl=hl, info=info, updated=updated)
+
+
+def test_a_handle_that_changes_mode_mid_sequence(gpu_required):
+    """one handle, rvio_hip_frame (host buffers), the corner source switching every four frames: device detector (run-ahead image chains, device-side
+    counters), caller-side list (one image stream, stream events), detector, list, ...  Every switch crosses the paths that exist for it only — the IMU
+    staging's waits for the filters in flight when a call enters run-ahead mode, the host wait for a filter whose completion only a device-side counter
+    records when a call leaves it — so the flat-out run must reproduce the run with rvio_hip_sync behind every frame bit for bit"""
+    cfg = abi.config_named("B", n_features=40, max_track_len=4, enable_equalizer=1)
+    seq = rv.synth.SynthSequence(cfg, duration=9.0)
+    ks = list(range(K0 + 1, K0 + 1 + 24))
+    cands = []
+    for k in ks:
+        xy, vis = seq.project(k, noise=False)
+        cands.append(seq.candidates(k, xy, vis)[0].astype(np.float32))
+    detector = [(i // 4) % 2 == 0 for i in range(len(ks))]       # detector, list, detector, list, ...
+    d = dict(cfg=cfg, init=seq.init_from_static(K0), imgs=[seq.render(k) for k in ks], imus=[seq.imu_between(k) for k in ks], cands=cands, detector=detector)
+    ref = run_mode_switch(d, sync_every=True)
+    assert ref["info"]["device_error"] == 0, ref["info"]
+    upd = np.array(ref["updated"]) == 1
+    assert upd[np.array(detector)].any() and upd[~np.array(detector)].any(), ref["updated"]      # an update ran in each mode
+    r = run_mode_switch(d, sync_every=False)
+    assert r["info"]["device_error"] == 0, r["info"]
+    assert same_bits(r, ref), first_diff(r, ref)

@@ -425,3 +425,280 @@ def test_update_form_thresholds(emu, statics):
     # Joseph, batches
     assert f1(11, 10, B=128)["joseph"] == "batch" and f1(12, 10, B=128)["joseph"] == "strips" and f1(11, 10, B=128, whole=0)["joseph"] == "strips"
     assert f1(11, 10, B=8)["joseph"] == "strips" and f1(11, 10, B=8)["grid"][:2] == ((24 + 60 + 15) // 16, (6 * 7 // 2 + 3) // 4)
+
+
+# ---------------------------------------------------------------- front_forms(): mode, synchronisation, stream roles and kernel forms of ONE front-end call
+STREAM = ("filter", "tracker", "side", "image")
+GRAY = ("none", "dword3", "byte3", "dword4", "byte4")
+CLAHE_LUT = ("none", "col16_256x8", "col16_1024", "wave32")
+CLAHE_INTERP = ("none", "px4", "px1")
+PYRAMID = ("copy", "own")
+DET_FIRST = ("none", "tile", "strip")
+SUBPIX = ("none", "wide_win", "generic", "x16", "stock")
+KLT = ("k3", "k16")
+ANNOUNCE = ("none", "signal", "event")
+BOOK = ("plain", "join", "fused", "pair")
+FRONT_LAUNCHES = ("gray_l", "clahe_lut_l", "clahe_interp_l", "pyramid_l", "det_first_l", "neigh_l", "greedy_l", "subpix_l", "klt_l", "ransac_l", "book_a_l", "book_b_l")
+FIXED_LDS = {-1: "none", -2: "default", -3: "neigh", -4: "greedy", -5: "subpix_wide"}
+FRONT_DEFAULT = dict(throughput=0, W=752, H=480, equalizer=1, sp_win=7, channels=1, piped=1, have_list=0, frame_no=5, first_cleared=1, src_dword=1,
+                     no_runahead=0, no_device_polls=0, own_queues=1)
+
+
+def clahe_tiles(W, H):
+    """createCLAHE(3.0, (5, 5)): a 5 x 5 tile grid over the image padded up to multiples of 5 (Tracker.cc:198-202)"""
+    ew, eh = (W, H) if W % 5 == 0 and H % 5 == 0 else (W + 5 - W % 5, H + 5 - H % 5)
+    return 5, 5, ew // 5, eh // 5
+
+
+def front(emu, statics, ml, F, B, **kw):
+    a = dict(FRONT_DEFAULT, **kw)
+    tx, ty, tw, th = clahe_tiles(a["W"], a["H"]) if a["equalizer"] else (0, 0, 0, 0)
+    vin = (a["throughput"], a["W"], a["H"], a["equalizer"], tx, ty, tw, th, a["sp_win"], a["channels"], a["piped"], a["have_list"], a["frame_no"],
+           a["first_cleared"], a["src_dword"], a["no_runahead"], a["no_device_polls"], a["own_queues"])
+    assert len(vin) == emu.lp_front_in_len()
+    out = (C.c_long * emu.lp_front_len())()
+    assert emu.lp_front_forms(ml, F, B, statics, (C.c_long * len(vin))(*vin), out) == 0
+    v = list(out)
+    keys = ("use_det", "piped", "runahead", "dev_sync", "par", "dslot", "ic", "lut_set", "det_set", "filter_done_by_counter", "wait_book_k3", "wait_first_flag",
+            "pyr_on_image", "klt_polls_pyramid", "det_folds_signal", "fork_side")
+    d = dict(zip(keys, v))
+    k = len(keys)
+    d["corners"] = ANNOUNCE[v[k]]
+    for i, r in enumerate(("base", "image", "pyr", "side", "book")):
+        d[r] = STREAM[v[k + 1 + i]]
+    k += 6
+    for i, (name, tab) in enumerate((("gray", GRAY), ("clahe_lut", CLAHE_LUT), ("clahe_interp", CLAHE_INTERP), ("pyramid", PYRAMID), ("det_first", DET_FIRST),
+                                     ("subpix", SUBPIX), ("klt", KLT), ("book_form", BOOK))):
+        d[name] = tab[v[k + i]]
+    k += 8
+    for i, name in enumerate(FRONT_LAUNCHES):   # (grid, threads, dynamic LDS, who covers it: a kernel of plan.attr | one of FIXED_LDS)
+        gx, gy, gz, t, lds, kern = v[k + 6 * i: k + 6 * i + 6]
+        d[name] = ((gx, gy, gz), t, lds, emu.lp_kernel_name(kern).decode() if kern >= 0 else FIXED_LDS[kern])
+    return d
+
+
+def cdiv(a, b):
+    return (a + b - 1) // b
+
+
+def expected_front(p, ml, F, B, a):
+    """The front end's rules as DESIGN.md §3 and the comments at the launch sites state them, written out: NOT computed through launch_plan.h.
+    p: the plan of the configuration (n_ic, book_fused, book_waves, book_lds); a: the call"""
+    W, H, wide, eq = a["W"], a["H"], a["throughput"], a["equalizer"]
+    e = {}
+    # the pipelined whole-frame path with the device detector runs the front end in run-ahead form (unless RVIO_NO_RUNAHEAD); device-side counters for ONE
+    # instance, unless stream events were asked for (RVIO_PARANOID) or a counter-collecting profiler serialises the queues
+    det = not a["have_list"]
+    ra = bool(a["piped"] and det and not a["no_runahead"])
+    dev = ra and B == 1 and not a["no_device_polls"]
+    k = a["frame_no"]
+    par = k % 2 if a["piped"] else 0
+    chain = k % p["n_ic"] if ra else 0                 # image chains exist in run-ahead mode only; the CLAHE LUTs alternate by parity outside it
+    e.update(use_det=int(det), piped=a["piped"], runahead=int(ra), dev_sync=int(dev), par=par, dslot=k % 3 if ra else par, ic=chain, lut_set=chain if ra else par, det_set=chain)
+    e["filter_done_by_counter"] = int(dev)
+    e["wait_book_k3"] = int(ra and k >= 3)                                 # four equalised images, three corner lists in rotation: image chain k behind book-keeping(k-3)
+    e["wait_first_flag"] = int(ra and k >= 1 and not a["first_cleared"])   # nms(k) behind book-keeping(k-1) until mbIsTheFirstImage is 0 everywhere
+    on_image = bool(eq and ra)                                             # the pyramid rides on the image stream behind CLAHE
+    polls = on_image and dev and a["own_queues"] and 6 * (ml - 1) <= 96 and not wide
+    e.update(pyr_on_image=int(on_image), klt_polls_pyramid=int(polls), det_folds_signal=int(polls), fork_side=int(det and not on_image))
+    e["corners"] = "signal" if dev else "event" if ra else "none"
+    base = "tracker" if a["piped"] else "filter"
+    e.update(base=base, image="image" if ra else base, side="side" if det else base, book="side" if ra else base)
+    e["pyr"] = e["image"] if on_image else e["side"]
+    # kernel forms
+    L = {}
+    no = ((0, 1, 1), 0, 0, "none")
+    ch = a["channels"]
+    if ch > 1:
+        dword = W % 4 == 0 and a["src_dword"]
+        e["gray"] = ("dword" if dword else "byte") + str(ch)
+        L["gray_l"] = ((cdiv(W, 256), cdiv(H, 4), B), 256, 0, "none")
+    else:
+        e["gray"], L["gray_l"] = "none", no
+    if eq:
+        tx, ty, tw, th = clahe_tiles(W, H)
+        col16 = cdiv(tw, 64) * th <= 65535                # a 16-bit counter sees one lane column of the tile
+        e["clahe_lut"] = ("col16_256x8" if wide else "col16_1024") if col16 else "wave32"
+        L["clahe_lut_l"] = ((tx * ty, 1, B), 256 if (wide and col16) else 1024, 0, "none")
+        src_dword = W % 4 == 0 if ch > 1 else a["src_dword"]   # the handle's gray buffer: rows of W bytes, W H apart
+        px4 = wide and W % 4 == 0 and src_dword
+        e["clahe_interp"] = "px4" if px4 else "px1"
+        L["clahe_interp_l"] = ((cdiv(W // 4, 64), cdiv(H, 16), B), 256, 0, "none") if px4 else ((cdiv(W, 64), cdiv(H, 4), B), 256, 0, "none")
+    else:
+        e["clahe_lut"], e["clahe_interp"], L["clahe_lut_l"], L["clahe_interp_l"] = "none", "none", no, no
+    w3, h3 = W, H
+    for _ in range(3):
+        w3, h3 = (w3 + 1) // 2, (h3 + 1) // 2
+    e["pyramid"] = "own" if eq else "copy"                # level 0 is the equalised image itself
+    L["pyramid_l"] = ((cdiv(w3, 8), cdiv(h3, 8), B), 256, 0, "none")
+    if det:
+        e["det_first"] = "strip" if wide else "tile"
+        L["det_first_l"] = ((cdiv(W, 60), cdiv(H, 16), B), 64, 0, "none") if wide else ((cdiv(W, 64), cdiv(H, 16), B), 512, 0, "none")
+        L["neigh_l"] = ((2 if wide else 8, 1, B), 1024, 2048 * 18 + 4098 * 4, "neigh")
+        L["greedy_l"] = ((1, 1, B), 1024, 4096 * 8 + 32768 + 24576 * 2 + 2052 * 4, "greedy")
+        win = a["sp_win"]
+        if win > 15:
+            G = 64 if 2 * win + 1 <= 64 else 128
+            e["subpix"], L["subpix_l"] = "wide_win", ((F, 1, B), 256, 8 * (5 * G * 17 + 5 * G + 8), "subpix_wide")
+        elif win != 7:
+            e["subpix"], L["subpix_l"] = "generic", ((F, 1, B), 256, 0, "none")
+        elif wide:
+            e["subpix"], L["subpix_l"] = "x16", ((cdiv(F, 4), 1, B), 64, 0, "none")
+        else:
+            e["subpix"], L["subpix_l"] = "stock", ((F, 1, B), 256, 0, "none")
+    else:
+        e["det_first"], e["subpix"] = "none", "none"
+        L["det_first_l"] = L["neigh_l"] = L["greedy_l"] = L["subpix_l"] = no
+    e["klt"] = "k16" if wide else "k3"
+    L["klt_l"] = ((cdiv(F, 4) if wide else F, 1, B), 64, 0, "none")
+    ransac = ((1, 1, B), 256, 8 * F + 16, "default")
+    book_b = ((1, 1, B), 64 * p["book_waves"], p["book_lds"], "bookkeep_b_kernel")
+    if not ra:
+        e["book_form"] = "join" if det else "plain"
+        bz = B if det else 1                               # the caller's list is ONE list: book-keeping of instance 0, one workgroup
+        L.update(ransac_l=ransac, book_a_l=((1, 1, bz), 256, 0, "none"), book_b_l=((1, 1, bz),) + book_b[1:])
+    elif dev and p["book_fused"]:
+        e["book_form"] = "fused"
+        L.update(ransac_l=((1, 1, B), 64 * p["book_waves"], p["book_lds"], "ransac_book_kernel"), book_a_l=no, book_b_l=no)
+    else:
+        e["book_form"] = "pair"
+        L.update(ransac_l=ransac, book_a_l=no, book_b_l=book_b)
+    e.update(L)
+    return e
+
+
+def check_front(emu, statics, static_lds, p, ml, F, B, a, seen):
+    f = front(emu, statics, ml, F, B, **a)
+    at = (ml, F, B, a)
+    a = dict(FRONT_DEFAULT, **a)
+    for k, v in expected_front(p, ml, F, B, a).items():
+        assert f[k] == v, (at, k, f[k], v)
+    # the invariants a change to one rule must not break
+    assert (not f["dev_sync"] or f["runahead"]) and (not f["runahead"] or (f["use_det"] and f["piped"])), at
+    if f["klt_polls_pyramid"]:
+        assert f["dev_sync"] and a["equalizer"] and not a["throughput"] and 6 * (ml - 1) <= 96 and a["own_queues"], at
+    assert bool(f["klt_polls_pyramid"]) == bool(f["det_folds_signal"]) and (not f["det_folds_signal"] or f["det_first"] == "tile"), at   # polled <=> a launch bumps it
+    if f["book_form"] == "fused":
+        assert f["dev_sync"] and p["book_fused"], at
+    if f["piped"]:
+        assert f["filter_done_by_counter"] == f["dev_sync"], at
+    else:
+        assert not f["filter_done_by_counter"], at
+    assert 0 <= f["ic"] < p["n_ic"] and 0 <= f["dslot"] < 3 and 0 <= f["lut_set"] < max(2, p["n_ic"]) and 0 <= f["det_set"] < p["n_ic"], at
+    # every launch: a workgroup the hardware takes, dynamic LDS within the limit that covers it
+    for name in FRONT_LAUNCHES:
+        (gx, gy, gz), t, lds, kern = f[name]
+        if gx == 0:
+            assert lds == 0 and kern == "none", (at, name)
+            continue
+        assert gx >= 1 and gy >= 1 and gz == (1 if name in ("book_a_l", "book_b_l") and f["book_form"] == "plain" else B) and 64 <= t <= 1024 and t % 64 == 0, (at, name, f[name])
+        if kern == "none":
+            assert lds == 0, (at, name)
+        elif kern == "default":
+            assert 0 < lds <= 64 * 1024, (at, name, lds)
+        elif kern == "neigh":
+            assert lds == emu.lp_neigh_lds() <= 64 * 1024, (at, name)
+        elif kern == "greedy":
+            assert lds == emu.lp_greedy_lds() <= LIMIT, (at, name)
+        elif kern == "subpix_wide":
+            assert lds == emu.lp_subpix_wide_lds_bytes(a["sp_win"]) <= LIMIT, (at, name)
+        else:
+            assert 0 < lds <= p["attr"][kern] and p["attr"][kern] + static_lds[kern] <= LIMIT, (at, name, lds, p["attr"][kern])
+        seen["lds"].add(kern)
+    for k in ("corners", "base", "image", "pyr", "side", "book", "gray", "clahe_lut", "clahe_interp", "pyramid", "det_first", "subpix", "klt", "book_form"):
+        seen[k].add(f[k])
+    seen["neigh"].add(f["neigh_l"][0][0])
+    return f
+
+
+def test_front_forms_for_every_mode_and_geometry(emu, statics, static_lds):
+    seen = {k: set() for k in ("corners", "base", "image", "pyr", "side", "book", "gray", "clahe_lut", "clahe_interp", "pyramid", "det_first", "subpix", "klt",
+                               "book_form", "neigh", "lds")}
+    n = 0
+    # a. the mode of a call: every combination of what it depends on, on both sides of 6n = 96 (windows 11, 17 | 18), F on both sides of the fused book-keeping launch
+    for B in FORM_BATCHES:
+        for ml, F in ((11, 200), (17, 200), (18, 200), (11, 3000)):
+            p = evaluate(emu, statics, ml, F, B)
+            assert p["rc"] == 0
+            for eq in (0, 1):
+                for thr in (0, 1):
+                    for have_list in (0, 1):
+                        for piped in (0, 1):
+                            for no_ra in (0, 1):
+                                for no_polls in (0, 1):
+                                    for own in (0, 1):
+                                        for first_cleared in (0, 1):
+                                            for k in range(9):
+                                                check_front(emu, statics, static_lds, p, ml, F, B, dict(equalizer=eq, throughput=thr, have_list=have_list, piped=piped,
+                                                            no_runahead=no_ra, no_device_polls=no_polls, own_queues=own, first_cleared=first_cleared, frame_no=k), seen)
+                                                n += 1
+    # b. the kernel forms: image sizes (the third breaks the 16-bit histogram bound: tiles of 4096 x 1024, 64 lane columns x 1024 rows = 65 536), channel
+    #    counts, alignment, cornerSubPix half-windows, for a run-ahead frame, a frame with a corner list and a per-stage call
+    for B in FORM_BATCHES:
+        p = evaluate(emu, statics, 11, 200, B)
+        for W, H in ((752, 480), (1920, 1080), (20480, 5120), (750, 481)):
+            for eq in (0, 1):
+                for ch in (1, 3, 4):
+                    for al in (0, 1):
+                        for thr in (0, 1):
+                            for win in (1, 7, 15, 16, 63):
+                                for piped, have_list in ((1, 0), (1, 1), (0, 0)):
+                                    check_front(emu, statics, static_lds, p, 11, 200, B, dict(W=W, H=H, equalizer=eq, channels=ch, src_dword=al, throughput=thr, sp_win=win,
+                                                piped=piped, have_list=have_list), seen)
+                                    n += 1
+    print("front_forms: %d calls checked" % n)
+    # every form, role and announcement was visited
+    assert seen["corners"] == set(ANNOUNCE) and seen["gray"] == set(GRAY) and seen["clahe_lut"] == set(CLAHE_LUT) and seen["clahe_interp"] == set(CLAHE_INTERP)
+    assert seen["pyramid"] == set(PYRAMID) and seen["det_first"] == set(DET_FIRST) and seen["subpix"] == set(SUBPIX) and seen["klt"] == set(KLT) and seen["book_form"] == set(BOOK)
+    assert seen["base"] == {"filter", "tracker"} and seen["image"] == {"filter", "tracker", "image"} and seen["side"] == {"filter", "tracker", "side"}
+    assert seen["pyr"] == set(STREAM) and seen["book"] == {"filter", "tracker", "side"} and seen["neigh"] == {0, 2, 8}
+    assert seen["lds"] == {"none", "default", "neigh", "greedy", "subpix_wide", "bookkeep_b_kernel", "ransac_book_kernel"}
+
+
+def test_front_form_thresholds(emu, statics):
+    """single points on both sides of each threshold, by name (the sweep above checks the rule; this pins where it falls)"""
+    def f1(ml=11, F=200, B=1, **kw):
+        return front(emu, statics, ml, F, B, **kw)
+    # run-ahead: a piped call with the device detector, unless RVIO_NO_RUNAHEAD; device-side counters: one instance, unless asked not to poll
+    assert f1()["runahead"] and f1()["dev_sync"] and not f1(have_list=1)["runahead"] and not f1(piped=0)["runahead"] and not f1(no_runahead=1)["runahead"]
+    assert f1(B=3)["runahead"] and not f1(B=3)["dev_sync"] and not f1(no_device_polls=1)["dev_sync"] and f1(no_device_polls=1)["runahead"]
+    assert (f1()["corners"], f1(B=3)["corners"], f1(no_runahead=1)["corners"], f1(have_list=1)["corners"]) == ("signal", "event", "none", "none")
+    # buffers in rotation: corner lists by frame % 3, image chains by frame % n_ic (two; ONE at 96 < 6n <= 192), else everything by parity
+    assert [f1(frame_no=k)["dslot"] for k in range(6)] == [0, 1, 2, 0, 1, 2] and [f1(frame_no=k)["ic"] for k in range(4)] == [0, 1, 0, 1]
+    assert [f1(ml=18, frame_no=k)["ic"] for k in range(4)] == [0, 0, 0, 0] and [f1(ml=17, frame_no=k)["ic"] for k in range(4)] == [0, 1, 0, 1]
+    assert [(f1(have_list=1, frame_no=k)["dslot"], f1(have_list=1, frame_no=k)["lut_set"], f1(have_list=1, frame_no=k)["ic"]) for k in range(3)] == [(0, 0, 0), (1, 1, 0), (0, 0, 0)]
+    assert [f1(piped=0, frame_no=k)["dslot"] for k in range(3)] == [0, 0, 0] and f1(no_runahead=1, frame_no=3)["det_set"] == 0 and f1(frame_no=3)["det_set"] == 1
+    # the waits of the image chain: book-keeping(k-3) from frame 3 on, book-keeping(k-1) from frame 1 on until the first-image flag is gone
+    assert [f1(frame_no=k)["wait_book_k3"] for k in (2, 3)] == [0, 1] and not f1(no_runahead=1, frame_no=5)["wait_book_k3"]
+    assert [f1(frame_no=k, first_cleared=0)["wait_first_flag"] for k in (0, 1)] == [0, 1] and not f1(frame_no=5, first_cleared=1)["wait_first_flag"]
+    # klt_kernel3 polls the pyramid counter: every term of the condition, one at a time
+    assert f1()["klt_polls_pyramid"] and f1()["det_folds_signal"] and f1(ml=17)["klt_polls_pyramid"] and not f1(ml=18)["klt_polls_pyramid"]
+    for off in (dict(equalizer=0), dict(throughput=1), dict(own_queues=0), dict(no_device_polls=1), dict(B=3), dict(no_runahead=1), dict(have_list=1), dict(piped=0)):
+        assert not f1(**off)["klt_polls_pyramid"] and not f1(**off)["det_folds_signal"], off
+    # where the pyramid runs, and who forks the side stream
+    assert (f1()["pyr"], f1(equalizer=0)["pyr"], f1(no_runahead=1)["pyr"], f1(have_list=1)["pyr"], f1(piped=0, have_list=1)["pyr"]) == ("image", "side", "side", "tracker", "filter")
+    assert (f1()["fork_side"], f1(equalizer=0)["fork_side"], f1(no_runahead=1)["fork_side"], f1(have_list=1)["fork_side"]) == (0, 1, 1, 0)
+    assert (f1()["pyramid"], f1(equalizer=0)["pyramid"]) == ("own", "copy") and f1()["pyramid_l"][0] == (12, 8, 1) and f1(W=1920, H=1080)["pyramid_l"][0] == (30, 17, 1)
+    # RANSAC / book-keeping: four shapes; the fused launch up to F = 2850 (one CU's LDS), with device-side counters only
+    assert (f1()["book_form"], f1(F=2850)["book_form"], f1(F=2851)["book_form"], f1(B=3)["book_form"], f1(no_device_polls=1)["book_form"]) == ("fused", "fused", "pair", "pair", "pair")
+    assert (f1(no_runahead=1)["book_form"], f1(have_list=1)["book_form"], f1(piped=0)["book_form"], f1(piped=0, have_list=1)["book_form"]) == ("join", "plain", "join", "plain")
+    assert (f1()["book"], f1(no_runahead=1)["book"], f1(piped=0)["book"]) == ("side", "tracker", "filter")
+    assert f1()["ransac_l"][1:] == (1024, 20 * 200 + 16 * 200 * 8 + 16, "ransac_book_kernel") and f1(B=3)["ransac_l"][1:] == (256, 1616, "default")
+    assert f1(F=1600, ml=31)["ransac_l"][1] == 512 and f1(B=8)["book_b_l"][1] == 256
+    # gray: dword form where W and the caller's base / strides are multiples of four
+    assert (f1(channels=3)["gray"], f1(channels=3, src_dword=0)["gray"], f1(channels=4)["gray"], f1(channels=4, W=750)["gray"], f1()["gray"]) == ("dword3", "byte3", "dword4", "byte4", "none")
+    assert f1(channels=3)["gray_l"][0] == (3, 120, 1) and f1(channels=3, B=8)["gray_l"][0] == (3, 120, 8)
+    # CLAHE: 16-bit columns while ceil(tw / 64) * th <= 65535 — 20480 x 5115: 64 x 1023 = 65 472; 20480 x 5120: 64 x 1024 = 65 536; 1080p: 6 x 216
+    assert (f1(W=20480, H=5115)["clahe_lut"], f1(W=20480, H=5120)["clahe_lut"], f1(W=1920, H=1080)["clahe_lut"]) == ("col16_1024", "wave32", "col16_1024")
+    assert (f1(throughput=1)["clahe_lut"], f1(throughput=1)["clahe_lut_l"][1], f1()["clahe_lut_l"][1], f1(equalizer=0)["clahe_lut"]) == ("col16_256x8", 256, 1024, "none")
+    assert (f1(throughput=1)["clahe_interp"], f1(throughput=1, src_dword=0)["clahe_interp"], f1(throughput=1, W=750)["clahe_interp"], f1()["clahe_interp"]) == ("px4", "px1", "px1", "px1")
+    assert f1(throughput=1, channels=3, src_dword=0)["clahe_interp"] == "px4"      # (CLAHE then reads the handle's gray buffer, not the caller's image)
+    assert f1(throughput=1)["clahe_interp_l"][0] == (3, 30, 1) and f1()["clahe_interp_l"][0] == (12, 120, 1)
+    # detector: tile | strip first pass, 8 | 2 neighbour blocks; cornerSubPix: the stock window 7, other windows up to 15, the wide grid from 16 on (two sizes: 31 | 32)
+    assert (f1()["det_first"], f1()["det_first_l"][0], f1(throughput=1)["det_first"], f1(throughput=1)["det_first_l"][0]) == ("tile", (12, 30, 1), "strip", (13, 30, 1))
+    assert (f1()["neigh_l"][0][0], f1(throughput=1)["neigh_l"][0][0], f1(have_list=1)["neigh_l"][0][0]) == (8, 2, 0)
+    assert [f1(sp_win=w)["subpix"] for w in (1, 6, 7, 8, 15, 16, 63)] == ["generic", "generic", "stock", "generic", "generic", "wide_win", "wide_win"]
+    assert (f1(throughput=1)["subpix"], f1(throughput=1, sp_win=8)["subpix"], f1(throughput=1)["subpix_l"][0], f1(have_list=1)["subpix"]) == ("x16", "generic", (50, 1, 1), "none")
+    assert (f1(sp_win=31)["subpix_l"][2], f1(sp_win=32)["subpix_l"][2]) == (46144, 92224)
+    # KLT
+    assert (f1()["klt"], f1()["klt_l"][0], f1(throughput=1)["klt"], f1(throughput=1)["klt_l"][0]) == ("k3", (200, 1, 1), "k16", (50, 1, 1))
