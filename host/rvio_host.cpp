@@ -1,5 +1,6 @@
 // host/rvio_host.cpp — see rvio_host.hpp.  No ROS / OpenCV / Eigen; zlib for PNG.
 #include "rvio_host.hpp"
+#include "../r-vio_amd/csrc/raw.h"   // the arithmetic of the device's raw-sensor gray conversion, as the kernels compile it
 
 #include <zlib.h>
 
@@ -30,6 +31,7 @@ std::string strip_comment(const std::string& s) {
 struct Yaml {
     std::map<std::string, double> num;
     std::map<std::string, std::vector<double>> mat;
+    std::map<std::string, std::string> str;   // non-numeric scalars, quotes removed (Camera.Encoding)
 };
 bool parse_yaml(const std::string& text, Yaml* y, std::string* err) {
     std::istringstream in(text);
@@ -68,6 +70,11 @@ bool parse_yaml(const std::string& text, Yaml* y, std::string* err) {
         char* end = nullptr;
         const double d = std::strtod(val.c_str(), &end);
         if (end != val.c_str()) y->num[key] = d;   // non-numeric scalars (strings) are not used by the reference's hot path
+        else {
+            std::string v = val;
+            if (v.size() >= 2 && (v.front() == '"' || v.front() == '\'') && v.back() == v.front()) v = v.substr(1, v.size() - 2);
+            y->str[key] = v;
+        }
     }
     return true;
 }
@@ -117,6 +124,12 @@ bool parse_settings(const std::string& text, Settings* out, std::string* err) {
     out->cam_time_offset = num("Camera.nTimeOffset", 0.0);
     out->record_outputs = (int)num("INI.RecordOutputs", 0.0);
     out->is_rgb = (int)num("Camera.RGB", 0.0);
+    out->encoding.clear();
+    auto e = y.str.find("Camera.Encoding");
+    if (e != y.str.end()) {
+        if (encoding_format(e->second) < 0) { if (err) *err = "settings: Camera.Encoding: unknown encoding '" + e->second + "'"; return false; }
+        out->encoding = e->second;
+    }
     return true;
 }
 
@@ -304,13 +317,14 @@ int System::MonoVIO(PoseLine* pose) {
     if (image.width != s_.cfg.width || image.height != s_.cfg.height) { err_ = "image size does not match Camera.width/height"; return -1; }
     // "Convert to gray scale" (Tracker.cc:182-196) runs on the device: the handle is told what a pixel is — once, and again only when the channel
     // count of the stream changes — and takes the interleaved bytes as they are (to_gray below is the host form of the same arithmetic)
-    if (image.channels != pix_ch_) {
-        if (image.channels != 1 && image.channels != 3 && image.channels != 4) { err_ = "images of 1, 3 or 4 channels are supported"; return -1; }
-        const int fmt = image.channels == 1 ? RVIO_PIX_MONO8 : image.channels == 3 ? (s_.is_rgb ? RVIO_PIX_RGB8 : RVIO_PIX_BGR8) : (s_.is_rgb ? RVIO_PIX_RGBA8 : RVIO_PIX_BGRA8);
+    // (... and what cv_bridge converts in front of Tracker::track, rvio_mono.cc:64: 16-bit samples and Bayer mosaics go over unconverted too)
+    const int fmt = image_format(image, s_, &err_);
+    if (fmt < 0) return -1;
+    if (fmt != pix_fmt_) {
         if (rvio_hip_set_image_format(h_, fmt) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
-        pix_ch_ = image.channels;
+        pix_fmt_ = fmt;
     }
-    const int row_bytes = image.width * image.channels;
+    const int row_bytes = image.width * image.channels * (image.bits / 8);
     if (image.px.size() < (size_t)row_bytes * image.height) { err_ = "image holds fewer bytes than width x height x channels"; return -1; }
     // the timed body of MonoVIO (System.cc:253-367): track -> propagate -> update -> augment -> compose
     if (!rec_) {
@@ -386,8 +400,68 @@ std::string format_landmarks(double t, int frame, int n, const int32_t* feat, co
 }
 
 // ------------------------------------------------------------------ images
+int encoding_format(const std::string& name) {
+    static const struct { const char* n; int f; } table[] = {
+        {"mono8", RVIO_PIX_MONO8}, {"rgb8", RVIO_PIX_RGB8}, {"bgr8", RVIO_PIX_BGR8}, {"rgba8", RVIO_PIX_RGBA8}, {"bgra8", RVIO_PIX_BGRA8},
+        {"mono16", RVIO_PIX_MONO16}, {"rgb16", RVIO_PIX_RGB16}, {"bgr16", RVIO_PIX_BGR16}, {"rgba16", RVIO_PIX_RGBA16}, {"bgra16", RVIO_PIX_BGRA16},
+        {"bayer_rggb8", RVIO_PIX_BAYER_RGGB8}, {"bayer_bggr8", RVIO_PIX_BAYER_BGGR8}, {"bayer_gbrg8", RVIO_PIX_BAYER_GBRG8}, {"bayer_grbg8", RVIO_PIX_BAYER_GRBG8},
+        {"bayer_rggb16", RVIO_PIX_BAYER_RGGB16}, {"bayer_bggr16", RVIO_PIX_BAYER_BGGR16}, {"bayer_gbrg16", RVIO_PIX_BAYER_GBRG16},
+        {"bayer_grbg16", RVIO_PIX_BAYER_GRBG16}};
+    for (const auto& e : table) if (name == e.n) return e.f;
+    return -1;
+}
+namespace {
+// rvio_pixel_format: bit 4 = 16-bit samples, bit 5 = a mosaic, else 0 mono, 1 / 2 three samples, 3 / 4 four
+int fmt_bits(int f) { return (f & 16) ? 16 : 8; }
+bool fmt_bayer(int f) { return (f & 32) != 0; }
+int fmt_samples(int f) { return fmt_bayer(f) || (f & 15) == 0 ? 1 : (f & 15) <= 2 ? 3 : 4; }
+bool fmt_bgr(int f) { return !fmt_bayer(f) && ((f & 15) == 2 || (f & 15) == 4); }
+}  // namespace
+
+int image_format(const ImageData& im, const Settings& s, std::string* err) {
+    if ((im.channels != 1 && im.channels != 3 && im.channels != 4) || (im.bits != 8 && im.bits != 16)) {
+        if (err) *err = "images of 1, 3 or 4 channels and 8 or 16 bits are supported";
+        return -1;
+    }
+    if (s.encoding.empty()) {
+        const int k = im.channels == 1 ? RVIO_PIX_MONO8 : im.channels == 3 ? (s.is_rgb ? RVIO_PIX_RGB8 : RVIO_PIX_BGR8) : (s.is_rgb ? RVIO_PIX_RGBA8 : RVIO_PIX_BGRA8);
+        return im.bits == 16 ? (k | 16) : k;
+    }
+    const int f = encoding_format(s.encoding);
+    if (f < 0 || fmt_samples(f) != im.channels || fmt_bits(f) != im.bits) {
+        if (err) *err = "Camera.Encoding: " + s.encoding + " contradicts the image (" + std::to_string(im.channels) + " channel(s) of " + std::to_string(im.bits) + " bits)";
+        return -1;
+    }
+    return f;
+}
+
+bool to_gray(ImageData* im, int format, std::string* err) {
+    if (format < 0 || fmt_samples(format) != im->channels || fmt_bits(format) != im->bits) { if (err) *err = "the image format does not fit the image's channels and bit depth"; return false; }
+    const size_t n = (size_t)im->width * im->height;
+    if (im->px.size() < n * im->channels * (im->bits / 8)) { if (err) *err = "image holds fewer bytes than width x height x channels"; return false; }
+    if (fmt_bayer(format)) {
+        if (im->width < 3 || im->height < 3) { if (err) *err = "a Bayer mosaic needs at least 3 x 3 pixels"; return false; }
+        std::vector<uint8_t> g(n);
+        const BayerP b = bayer_pattern(format & 3);
+        for (int y = 0; y < im->height; ++y)
+            for (int x = 0; x < im->width; ++x)
+                g[(size_t)y * im->width + x] = (uint8_t)(im->bits == 16 ? bayer_at<uint16_t>((const uint16_t*)im->px.data(), im->width, im->width, im->height, x, y, b)
+                                                                         : bayer_at<uint8_t>(im->px.data(), im->width, im->width, im->height, x, y, b));
+        im->px.swap(g);
+    } else if (im->bits == 16) {
+        const GrayW w = gray_weights(fmt_bgr(format) ? 1 : 0);
+        const int c = im->channels;
+        const uint16_t* p = (const uint16_t*)im->px.data();   // (in place: pixel i is read before byte i is written)
+        for (size_t i = 0; i < n; ++i) im->px[i] = (uint8_t)(c == 1 ? raw_depth8(p[i]) : raw16_px(p[i * c], p[i * c + 1], p[i * c + 2], w));
+        im->px.resize(n);
+    } else to_gray(im, !fmt_bgr(format));
+    im->channels = 1; im->bits = 8;
+    return true;
+}
+
 void to_gray(ImageData* im, bool is_rgb) {
     const int c = im->channels;
+    if (im->bits == 16) { to_gray(im, (c == 1 ? RVIO_PIX_MONO16 : c == 3 ? (is_rgb ? RVIO_PIX_RGB16 : RVIO_PIX_BGR16) : (is_rgb ? RVIO_PIX_RGBA16 : RVIO_PIX_BGRA16)), nullptr); return; }
     if (c != 3 && c != 4) return;
     const size_t n = (size_t)im->width * im->height;
     const int ir = is_rgb ? 0 : 2, ib = is_rgb ? 2 : 0;          // byte position of R and B inside a pixel
@@ -404,7 +478,7 @@ bool decode_png_gray8(const uint8_t* d, size_t n, ImageData* out, std::string* e
     if (n < 8 || std::memcmp(d, sig, 8) != 0) { if (err) *err = "not a PNG"; return false; }
     auto be32 = [&](size_t o) { return ((uint32_t)d[o] << 24) | ((uint32_t)d[o + 1] << 16) | ((uint32_t)d[o + 2] << 8) | d[o + 3]; };
     size_t o = 8;
-    uint32_t w = 0, h = 0, bpp = 1;
+    uint32_t w = 0, h = 0, bpp = 1, depth = 8;
     std::vector<uint8_t> z;
     bool have_hdr = false;
     while (o + 12 <= n) {
@@ -414,8 +488,9 @@ bool decode_png_gray8(const uint8_t* d, size_t n, ImageData* out, std::string* e
         const uint8_t* p = d + o + 8;
         if (!std::memcmp(type, "IHDR", 4)) {
             w = be32(o + 8); h = be32(o + 12);
-            if (p[8] != 8 || (p[9] != 0 && p[9] != 2 && p[9] != 6) || p[12] != 0) { if (err) *err = "PNG: only 8-bit gray / RGB / RGBA, non-interlaced images are supported"; return false; }
-            bpp = p[9] == 0 ? 1 : (p[9] == 2 ? 3 : 4);
+            if ((p[8] != 8 && p[8] != 16) || (p[9] != 0 && p[9] != 2 && p[9] != 6) || p[12] != 0) { if (err) *err = "PNG: only 8- and 16-bit gray / RGB / RGBA, non-interlaced images are supported"; return false; }
+            depth = p[8];
+            bpp = (p[9] == 0 ? 1 : (p[9] == 2 ? 3 : 4)) * (depth / 8);   // bytes per pixel: the distance the filters look back
             have_hdr = true;
         } else if (!std::memcmp(type, "IDAT", 4)) z.insert(z.end(), p, p + len);
         else if (!std::memcmp(type, "IEND", 4)) break;
@@ -426,7 +501,7 @@ bool decode_png_gray8(const uint8_t* d, size_t n, ImageData* out, std::string* e
     std::vector<uint8_t> raw((rowb + 1) * h);
     uLongf rl = (uLongf)raw.size();
     if (uncompress(raw.data(), &rl, z.data(), (uLong)z.size()) != Z_OK || rl != raw.size()) { if (err) *err = "PNG: inflate failed"; return false; }
-    out->width = (int)w; out->height = (int)h; out->channels = (int)bpp; out->px.assign(rowb * h, 0);
+    out->width = (int)w; out->height = (int)h; out->channels = (int)(bpp / (depth / 8)); out->bits = (int)depth; out->px.assign(rowb * h, 0);
     for (uint32_t y = 0; y < h; ++y) {                 // un-filter
         const uint8_t ft = raw[(size_t)y * (rowb + 1)];
         const uint8_t* s = &raw[(size_t)y * (rowb + 1) + 1];
@@ -447,6 +522,10 @@ bool decode_png_gray8(const uint8_t* d, size_t n, ImageData* out, std::string* e
             r[x] = (uint8_t)(s[x] + pred);
         }
     }
+    if (depth == 16) {   // big-endian samples -> host order
+        uint16_t* q = (uint16_t*)out->px.data();
+        for (size_t i = 0; i < out->px.size() / 2; ++i) q[i] = (uint16_t)((out->px[2 * i] << 8) | out->px[2 * i + 1]);
+    }
     return true;
 }
 
@@ -466,9 +545,14 @@ bool read_image(const std::string& path, ImageData* out, std::string* err) {
             v[k] = x;
         }
         ++o;
-        if (v[2] != 255 || o + (size_t)v[0] * v[1] * ch > buf.size()) { if (err) *err = "PGM/PPM: only maxval 255 is supported (" + path + ")"; return false; }
-        out->width = (int)v[0]; out->height = (int)v[1]; out->channels = (int)ch;
-        out->px.assign(buf.begin() + o, buf.begin() + o + (size_t)v[0] * v[1] * ch);
+        const size_t sb = v[2] > 255 ? 2 : 1;   // Netpbm: two bytes per sample, most significant first, from maxval 256 on
+        if (v[2] < 255 || v[2] > 65535 || o + (size_t)v[0] * v[1] * ch * sb > buf.size()) { if (err) *err = "PGM/PPM: only maxval 255 (8 bits) and 256 .. 65535 (16 bits) are supported (" + path + ")"; return false; }
+        out->width = (int)v[0]; out->height = (int)v[1]; out->channels = (int)ch; out->bits = (int)(8 * sb);
+        out->px.assign(buf.begin() + o, buf.begin() + o + (size_t)v[0] * v[1] * ch * sb);
+        if (sb == 2) {
+            uint16_t* q = (uint16_t*)out->px.data();
+            for (size_t i = 0; i < out->px.size() / 2; ++i) q[i] = (uint16_t)((out->px[2 * i] << 8) | out->px[2 * i + 1]);
+        }
         return true;
     }
     std::string e;

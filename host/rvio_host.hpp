@@ -26,23 +26,32 @@ struct ImuData {          // InputBuffer.h:35-51
     double w[3], a[3];
     double t, dt;
 };
-struct ImageData {        // InputBuffer.h:53-63 (cv::Mat -> packed bytes, `channels` interleaved bytes per pixel: 1, 3 or 4)
+struct ImageData {        // InputBuffer.h:53-63 (cv::Mat -> packed bytes, `channels` interleaved samples per pixel: 1, 3 or 4)
     std::vector<uint8_t> px;
     int width = 0, height = 0;
     int channels = 1;
     double t = 0;
+    int bits = 8;         // bits per sample: 8, or 16 (two bytes per sample in host byte order, as a cv::Mat of CV_16U holds them)
 };
 // Tracker::track's "Convert to gray scale" (Tracker.cc:182-196): cvtColor CV_RGB2GRAY / CV_BGR2GRAY (3 channels) or the RGBA / BGRA forms
 // (4 channels, alpha ignored) on 8-bit data = OpenCV's fixed-point  (R 4899 + G 9617 + B 1868 + 8192) >> 14.  In place; 1 channel: no-op.
 // The host form of what the library does on the device (rvio_hip_set_image_format: System::MonoVIO hands colour images over as they are);
 // kept for callers that want the gray image itself (rvio_replay --check-image).
 void to_gray(ImageData* im, bool is_rgb);
+// What the reference's node does in front of all that, cv_bridge::toCvShare(msg, MONO8) (rvio_mono.cc:64), for any rvio_pixel_format: 16-bit samples
+// ("gray at 16 bits, then 16 -> 8": (v + 128) / 257) and Bayer mosaics (cvtColor's bilinear COLOR_Bayer*2GRAY, borders replicated) besides the
+// 8-bit formats above.  The host form of the device's arithmetic: it compiles the kernels' own header (r-vio_amd/csrc/raw.h).  In place; false
+// with a message when the format does not fit the image (channels, bit depth, a mosaic smaller than 3 x 3).
+bool to_gray(ImageData* im, int format, std::string* err);
+// a ROS encoding name (mono8, mono16, rgb8 ... bgra16, bayer_rggb8 ... bayer_grbg16) as rvio_pixel_format; -1: unknown
+int encoding_format(const std::string& name);
 
 struct Settings {
     rvio_config cfg;              // everything the hot path needs
     double cam_time_offset = 0;   // Camera.nTimeOffset
     int record_outputs = 0;       // INI.RecordOutputs
     int is_rgb = 0;               // Camera.RGB (Tracker.cc:64-65): channel order of a 3 / 4-channel image, 1 = RGB(A), 0 = BGR(A)
+    std::string encoding;         // Camera.Encoding (optional): sensor_msgs' name of what the camera delivers — the only way to declare a Bayer mosaic
     std::vector<std::string> missing;   // keys the reference reads (cv::FileStorage would yield 0 for them) that the file does not hold:
                                         // they keep the EuRoC defaults here, and the caller is told (rvio_replay prints them)
 };
@@ -50,6 +59,9 @@ struct Settings {
 // "Key: !!opencv-matrix" blocks (rows / cols / dt / data: [ ... ]).  Missing keys keep the EuRoC defaults.
 bool read_settings(const std::string& path, Settings* out, std::string* err);
 bool parse_settings(const std::string& text, Settings* out, std::string* err);
+// The rvio_pixel_format of an image under these settings: Camera.Encoding when it is set — an error when it contradicts the image's channel count
+// or bit depth —, else what follows from channels, bit depth and Camera.RGB.  -1 with a message.
+int image_format(const ImageData& im, const Settings& s, std::string* err);
 
 class InputBuffer {       // InputBuffer.cc:29-81
 public:
@@ -112,7 +124,7 @@ private:
     double wm_[3] = {0, 0, 0}, am_[3] = {0, 0, 0};
     int n_imu_ = 0, n_img_ = 0;
     bool rec_ = false;
-    int pix_ch_ = 1;              // channels of the image format the handle was last told (rvio_hip_set_image_format)
+    int pix_fmt_ = RVIO_PIX_MONO8;   // the image format the handle was last told (rvio_hip_set_image_format)
     void* f_pose_ = nullptr;      // std::ofstream* (kept out of the header)
     void* f_time_ = nullptr;
     void* f_lm_ = nullptr;        // std::ofstream* of record_landmarks_to
@@ -129,7 +141,8 @@ private:
     long long last_seq();
 };
 
-// 8-bit PNG (non-interlaced; gray, RGB or RGBA: channels in file order = RGB) or binary PGM / PPM (P5 / P6, maxval 255)
+// 8- or 16-bit PNG (non-interlaced; gray, RGB or RGBA: channels in file order = RGB) or binary PGM / PPM (P5 / P6; maxval 255: 8 bits, 256 ..
+// 65535: 16 bits).  Both file formats store 16-bit samples big endian; ImageData holds them in host byte order.
 bool read_image(const std::string& path, ImageData* out, std::string* err);
 bool decode_png_gray8(const uint8_t* data, size_t n, ImageData* out, std::string* err);
 

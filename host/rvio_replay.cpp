@@ -42,7 +42,7 @@ static int check_settings(const char* path) {
                 c.qual_lvl, c.block_x, c.block_y, c.enable_equalizer, c.use_sampson, c.inlier_thr, c.ini_thr_angle, c.ini_thr_displ,
                 c.ini_enable_alignment, s.cam_time_offset, s.record_outputs, s.is_rgb);
     for (int i = 0; i < 16; ++i) std::printf("%s%.17g", i ? ", " : "", c.T_bc[i]);
-    std::printf("]}\n");
+    std::printf("], \"encoding\": \"%s\"}\n", s.encoding.c_str());
     return 0;
 }
 
@@ -56,14 +56,24 @@ static int check_dataset(const char* root) {
     return 0;
 }
 
-static int check_image(const char* path, bool is_rgb) {
+// encoding: a ROS encoding name (Camera.Encoding), or nullptr: what follows from the file and the channel order
+static int check_image(const char* path, bool is_rgb, const char* encoding) {
     ImageData im; std::string err;
     if (!read_image(path, &im, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
-    const int channels = im.channels;
-    to_gray(&im, is_rgb);
+    const int channels = im.channels, bits = im.bits;
+    Settings s;
+    s.is_rgb = is_rgb ? 1 : 0;
+    if (encoding) {
+        if (encoding_format(encoding) < 0) { std::fprintf(stderr, "unknown encoding '%s'\n", encoding); return 1; }
+        s.encoding = encoding;
+    }
+    const int fmt = image_format(im, s, &err);
+    if (fmt < 0 || !to_gray(&im, fmt, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
     unsigned long long sum = 0, wsum = 0;
     for (size_t i = 0; i < im.px.size(); ++i) { sum += im.px[i]; wsum += (unsigned long long)im.px[i] * (i % 251 + 1); }
-    std::printf("{\"width\": %d, \"height\": %d, \"channels\": %d, \"sum\": %llu, \"wsum\": %llu}\n", im.width, im.height, channels, sum, wsum);
+    std::printf("{\"width\": %d, \"height\": %d, \"channels\": %d, ", im.width, im.height, channels);
+    if (bits != 8 || encoding) std::printf("\"bits\": %d, \"format\": %d, ", bits, fmt);   // (an 8-bit file without --encoding prints what it always printed)
+    std::printf("\"sum\": %llu, \"wsum\": %llu}\n", sum, wsum);
     return 0;
 }
 
@@ -210,7 +220,14 @@ static int selfcheck(const Settings& s, const AslDataset& d, int device, long ma
 int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "--check-settings")) return check_settings(argv[2]);
     if (argc >= 3 && !std::strcmp(argv[1], "--check-dataset")) return check_dataset(argv[2]);
-    if (argc >= 3 && !std::strcmp(argv[1], "--check-image")) return check_image(argv[2], !(argc >= 4 && !std::strcmp(argv[3], "--bgr")));
+    if (argc >= 3 && !std::strcmp(argv[1], "--check-image")) {   // --check-image FILE [--bgr] [--encoding NAME]
+        bool rgb = true; const char* enc = nullptr;
+        for (int i = 3; i < argc; ++i) {
+            if (!std::strcmp(argv[i], "--bgr")) rgb = false;
+            else if (!std::strcmp(argv[i], "--encoding") && i + 1 < argc) enc = argv[++i];
+        }
+        return check_image(argv[2], rgb, enc);
+    }
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--record-dir DIR] [--record]\n"
                              "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n", argv[0]);

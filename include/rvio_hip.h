@@ -197,7 +197,23 @@ typedef enum rvio_pixel_format {
     RVIO_PIX_RGB8 = 1,    /* three bytes per pixel, R first (Camera.RGB: 1) */
     RVIO_PIX_BGR8 = 2,    /* three bytes per pixel, B first (Camera.RGB: 0) */
     RVIO_PIX_RGBA8 = 3,   /* four bytes per pixel, R first */
-    RVIO_PIX_BGRA8 = 4    /* four bytes per pixel, B first */
+    RVIO_PIX_BGRA8 = 4,   /* four bytes per pixel, B first */
+    /* Raw sensor data (added within 6): what cv_bridge::toCvShare(msg, MONO8) converts in front of Tracker::track (rvio_mono.cc:64).  Bit 4: 16-bit
+     * samples in host byte order (little endian); bit 5: a Bayer mosaic, one sample per pixel, named as ROS does by the top-left 2 x 2 block in
+     * reading order (RGGB: (0,0) = R, (1,0) = G, (0,1) = G, (1,1) = B).  Every value that is not listed here is RVIO_ERR_INVALID. */
+    RVIO_PIX_MONO16 = 16, /* two bytes per pixel: y8 = (v + 128) / 257, the round-to-nearest of v * 255 / 65535 */
+    RVIO_PIX_RGB16 = 17,  /* six bytes per pixel: y16 = (R * 4899 + G * 9617 + B * 1868 + 8192) >> 14, then the depth step */
+    RVIO_PIX_BGR16 = 18,
+    RVIO_PIX_RGBA16 = 19, /* eight bytes per pixel, alpha ignored */
+    RVIO_PIX_BGRA16 = 20,
+    RVIO_PIX_BAYER_RGGB8 = 32,   /* one byte per pixel: cvtColor's bilinear COLOR_Bayer*2GRAY, borders replicated (the arithmetic: csrc/raw.h) */
+    RVIO_PIX_BAYER_BGGR8 = 33,
+    RVIO_PIX_BAYER_GBRG8 = 34,
+    RVIO_PIX_BAYER_GRBG8 = 35,
+    RVIO_PIX_BAYER_RGGB16 = 48,  /* two bytes per pixel: the same formulas on 16-bit samples, then the depth step */
+    RVIO_PIX_BAYER_BGGR16 = 49,
+    RVIO_PIX_BAYER_GBRG16 = 50,
+    RVIO_PIX_BAYER_GRBG16 = 51
 } rvio_pixel_format;
 /* Off (RVIO_PIX_MONO8) by default: such a handle allocates and launches what it did before these two entry points existed.  With a colour
  * format `img` / `d_img` / `d_imgs` of rvio_hip_track, _track_dev, _frame, _frame_dev, _frame_begin_dev, _frame_sharded_dev and
@@ -206,7 +222,10 @@ typedef enum rvio_pixel_format {
  * detector and the pyramid) into a gray buffer of the handle, which every later stage reads; the host-buffer entry points stage the
  * caller's colour bytes, no pixel is converted on the host.  A change of format drains the handle and takes effect from the next image
  * handed over; the first colour format allocates the gray buffers.  RVIO_ERR_INVALID: unknown format; RVIO_ERR_UNSUPPORTED: a colour format
- * on a batch handle created without its front end (it takes no image).  get: the current format, RVIO_ERR_INVALID for a NULL handle. */
+ * on a batch handle created without its front end (it takes no image).  get: the current format, RVIO_ERR_INVALID for a NULL handle.
+ * The raw formats follow the same rules: stride < width * bytes per pixel is RVIO_ERR_INVALID; a 16-bit format also refuses an odd `stride`,
+ * an odd `img_stride` and an odd device address (rvio_hip_last_error says so); a Bayer format on an image narrower or lower than 3 pixels is
+ * RVIO_ERR_INVALID here; the staging of the host-buffer entry points grows to width * height * bytes per pixel. */
 int rvio_hip_set_image_format(rvio_hip* h, int format);
 int rvio_hip_get_image_format(const rvio_hip* h);
 

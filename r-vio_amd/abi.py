@@ -12,6 +12,21 @@ ABI_VERSION = 6
 # rvio_pixel_format (rvio_hip_set_image_format): what the image entry points are handed
 RVIO_PIX_MONO8, RVIO_PIX_RGB8, RVIO_PIX_BGR8, RVIO_PIX_RGBA8, RVIO_PIX_BGRA8 = 0, 1, 2, 3, 4
 PIX_CHANNELS = {RVIO_PIX_MONO8: 1, RVIO_PIX_RGB8: 3, RVIO_PIX_BGR8: 3, RVIO_PIX_RGBA8: 4, RVIO_PIX_BGRA8: 4}
+# raw sensor data (within ABI 6): bit 4 = 16-bit samples (host byte order), bit 5 = a Bayer mosaic named by its top-left 2 x 2 block
+RVIO_PIX_MONO16, RVIO_PIX_RGB16, RVIO_PIX_BGR16, RVIO_PIX_RGBA16, RVIO_PIX_BGRA16 = 16, 17, 18, 19, 20
+RVIO_PIX_BAYER_RGGB8, RVIO_PIX_BAYER_BGGR8, RVIO_PIX_BAYER_GBRG8, RVIO_PIX_BAYER_GRBG8 = 32, 33, 34, 35
+RVIO_PIX_BAYER_RGGB16, RVIO_PIX_BAYER_BGGR16, RVIO_PIX_BAYER_GBRG16, RVIO_PIX_BAYER_GRBG16 = 48, 49, 50, 51
+# every format: (bytes per pixel as staged, dtype of the array handed over, trailing dimension of that array or None for H x W)
+PIX_LAYOUT = {RVIO_PIX_MONO8: (1, "uint8", None), RVIO_PIX_RGB8: (3, "uint8", 3), RVIO_PIX_BGR8: (3, "uint8", 3),
+              RVIO_PIX_RGBA8: (4, "uint8", 4), RVIO_PIX_BGRA8: (4, "uint8", 4),
+              RVIO_PIX_MONO16: (2, "uint16", None), RVIO_PIX_RGB16: (6, "uint16", 3), RVIO_PIX_BGR16: (6, "uint16", 3),
+              RVIO_PIX_RGBA16: (8, "uint16", 4), RVIO_PIX_BGRA16: (8, "uint16", 4)}
+PIX_LAYOUT.update({f: (1, "uint8", None) for f in (32, 33, 34, 35)})
+PIX_LAYOUT.update({f: (2, "uint16", None) for f in (48, 49, 50, 51)})
+# the names cv_bridge / sensor_msgs give the encodings
+PIX_ENCODING = {"mono8": 0, "rgb8": 1, "bgr8": 2, "rgba8": 3, "bgra8": 4, "mono16": 16, "rgb16": 17, "bgr16": 18, "rgba16": 19, "bgra16": 20,
+                "bayer_rggb8": 32, "bayer_bggr8": 33, "bayer_gbrg8": 34, "bayer_grbg8": 35,
+                "bayer_rggb16": 48, "bayer_bggr16": 49, "bayer_gbrg16": 50, "bayer_grbg16": 51}
 
 
 class rvio_config(C.Structure):

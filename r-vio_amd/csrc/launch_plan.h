@@ -394,7 +394,12 @@ enum LpStream {          // the ROLE of a stream in a call; stream_of (rvio_hip.
     LPR_SIDE,            //   the side stream: pyramid / KLT / RANSAC beside the detector; book-keeping too in run-ahead mode
     LPR_IMAGE            //   run-ahead mode: the image chain `ic` of this frame (chain 0 shares the tracker stream's queue, chain 1 has the fourth)
 };
-enum LpGray { LPGR_NONE, LPGR_DWORD3, LPGR_BYTE3, LPGR_DWORD4, LPGR_BYTE4 };   // mono: no launch; gray_kernel4<3>, gray_kernel<3>, gray_kernel4<4>, gray_kernel<4>
+enum LpGray {
+    LPGR_NONE, LPGR_DWORD3, LPGR_BYTE3, LPGR_DWORD4, LPGR_BYTE4,   // mono: no launch; gray_kernel4<3>, gray_kernel<3>, gray_kernel4<4>, gray_kernel<4>
+    // raw sensor data (raw.hip), each family in its wide form (aligned dword loads, four pixels per lane) and its plain form:
+    LPGR_W16_1, LPGR_P16_1, LPGR_W16_3, LPGR_P16_3, LPGR_W16_4, LPGR_P16_4,   // 16-bit samples: raw16_kernel4<1|3|4>, raw16_kernel<1|3|4>
+    LPGR_BAYER8_W, LPGR_BAYER8_P, LPGR_BAYER16_W, LPGR_BAYER16_P              // mosaics: bayer_kernel4<uint8_t>, bayer_kernel<uint8_t>, ...<uint16_t>
+};
 enum LpClaheLut { LPCL_NONE, LPCL_COL16_256X8, LPCL_COL16_1024, LPCL_WAVE32 };   // equaliser off; clahe_lut_kernel2<256, 8>, clahe_lut_kernel2<1024>, clahe_lut_kernel
 enum LpClaheInterp { LPCI_NONE, LPCI_PX4, LPCI_PX1 };                            // equaliser off; clahe_interp_kernel4, clahe_interp_kernel
 enum LpPyramid { LPP_COPY, LPP_OWN };     // pyramid_kernel copies the image into level 0 | level 0 IS the handle's equalised image: no copy
@@ -417,7 +422,7 @@ struct FrontIn {
     bool equalizer = false;
     int cl_tx = 0, cl_ty = 0, cl_tw = 0, cl_th = 0;   // CLAHE tile grid and tile size
     int sp_win = LP_SP_WIN;        // cornerSubPix half-window, floor(Tracker.nMinDist / 2)
-    int channels = 1;              // bytes per pixel of the caller's images (1: mono)
+    int channels = 1;              // samples per pixel of the caller's images (1: mono or a mosaic)
 
     bool piped_call = false;       // a whole-frame call of the pipelined path (else: a per-stage entry point, everything on the filter stream)
     bool have_corner_list = false; // the caller hands in the corners: no device detector
@@ -429,6 +434,9 @@ struct FrontIn {
     bool no_device_polls = false;  // RVIO_PARANOID's bit 4, or a counter-collecting profiler that serialises kernels across queues
     bool own_queues = false;       // the handle's four streams own their hardware queues and nothing else feeds queues beside them:
                                    // private_queues && !queues_shared && !extra_queues
+    // raw sensor data (rvio_hip_set_image_format): both off = the 8-bit formats above
+    int bits = 8;                  // bits per sample: 8 | 16
+    bool bayer = false;            // the image is a Bayer mosaic (channels == 1): converted even at one byte per pixel
 };
 
 struct FrontForms {
@@ -534,13 +542,18 @@ inline FrontForms front_forms(const LaunchPlan& p, const FrontIn& in) {
     // ---- kernel forms
     // gray conversion: B interleaved images -> B packed gray images.  The dword form wherever every row of every instance starts on a dword and holds whole
     // groups of four pixels, the byte form otherwise (same bits: gray.h)
+    // Raw sensor data (raw.hip) has the same two forms under the same condition: 16-bit samples put a lane's four pixels into 2 / 6 / 8 aligned dwords,
+    // a mosaic into one (8 bit) or two (16 bit) per row of its 3 x 3 window.  A mosaic of one byte per pixel is converted too: whether a conversion is
+    // launched follows from the format, not from the bytes per pixel.
     const bool gray_dword = W % 4 == 0 && in.src_dword;
-    if (in.channels > 1) {
-        f.gray = in.channels == 3 ? (gray_dword ? LPGR_DWORD3 : LPGR_BYTE3) : (gray_dword ? LPGR_DWORD4 : LPGR_BYTE4);
-        f.gray_l = {(W + 255) / 256, (H + 3) / 4, B, 256};
-    }
+    const bool converted = in.channels > 1 || in.bits == 16 || in.bayer;
+    if (in.bayer) f.gray = in.bits == 16 ? (gray_dword ? LPGR_BAYER16_W : LPGR_BAYER16_P) : (gray_dword ? LPGR_BAYER8_W : LPGR_BAYER8_P);
+    else if (in.bits == 16) f.gray = in.channels == 1 ? (gray_dword ? LPGR_W16_1 : LPGR_P16_1) : in.channels == 3 ? (gray_dword ? LPGR_W16_3 : LPGR_P16_3)
+                                                                                                                    : (gray_dword ? LPGR_W16_4 : LPGR_P16_4);
+    else if (in.channels > 1) f.gray = in.channels == 3 ? (gray_dword ? LPGR_DWORD3 : LPGR_BYTE3) : (gray_dword ? LPGR_DWORD4 : LPGR_BYTE4);
+    if (converted) f.gray_l = {(W + 255) / 256, (H + 3) / 4, B, 256};
     // what CLAHE reads: the caller's image, or the handle's gray buffer (row stride W, instance stride W H, slots W H B apart in one allocation)
-    const bool eq_src_dword = in.channels > 1 ? W % 4 == 0 : in.src_dword;
+    const bool eq_src_dword = converted ? W % 4 == 0 : in.src_dword;
     if (in.equalizer) {
         // lane-private 16-bit histogram columns, no LDS-atomic conflicts: every handle.  A counter sees the pixels of ONE lane column of the tile,
         // ceil(tw / 64) th of them — 1296 at 1080p —, so 16 bits hold for any image a camera delivers; the 32-bit per-wave form stays as the fall-back

@@ -31,6 +31,7 @@
 #include "clahe.hip"
 #include "detector.hip"
 #include "gray.hip"        // Tracker.cc:182-196 for colour cameras (rvio_hip_set_image_format)
+#include "raw.hip"         // ... and for 16-bit and Bayer cameras: cv_bridge's conversion to MONO8 (rvio_mono.cc:64)
 #pragma clang fp contract(fast)
 
 struct rvio_hip {
@@ -168,7 +169,7 @@ struct rvio_hip {
     // colour input (rvio_hip_set_image_format): the gray images every stage behind gray_kernel reads instead of the caller's.  Allocated with the
     // first colour format, outside the slab (a mono handle keeps its memory layout), instance stride W * H; four in rotation like d_eq2[] (see
     // build_pyramid_dev for who reads a slot last)
-    int pix_fmt = RVIO_PIX_MONO8, pix_ch = 1;
+    int pix_fmt = RVIO_PIX_MONO8, pix_ch = 1;   // pix_ch: BYTES per pixel as staged (samples per pixel x bytes per sample)
     uint8_t* d_gray[4] = {nullptr, nullptr, nullptr, nullptr};
     int gray_slot = 0;
     size_t img_cap = 0;              // bytes of one staged image the host-side staging (d_img, hb_img[]) holds: W * H, grows with the channel count
@@ -1334,6 +1335,29 @@ static void refresh_first_cleared(rvio_hip* h) {
     for (int i = 0; i < h->batch && all0; ++i) all0 = ((volatile int*)h->first_mirror)[i] == 0;
     h->first_cleared = all0;
 }
+// rvio_pixel_format: bit 4 = 16-bit samples, bit 5 = Bayer mosaic (low bits: the pattern), else the five 8-bit formats
+static bool pix_is16(int fmt) { return (fmt & 16) != 0; }
+static bool pix_is_bayer(int fmt) { return (fmt & 32) != 0; }
+static bool pix_known(int fmt) {
+    if (fmt < 0 || (fmt & ~63)) return false;
+    return pix_is_bayer(fmt) ? (fmt & 15) <= 3 : (fmt & 15) <= 4;
+}
+static int pix_samples(int fmt) {   // samples per pixel
+    if (pix_is_bayer(fmt)) return 1;
+    const int k = fmt & 15;
+    return k == 0 ? 1 : k <= 2 ? 3 : 4;
+}
+static int pix_bytes(int fmt) { return pix_samples(fmt) * (pix_is16(fmt) ? 2 : 1); }   // bytes per pixel as staged
+// what every image entry point checks of the caller's image: the row holds W pixels; 16-bit samples lie on even addresses (d_img: a DEVICE address,
+// nullptr for a host buffer, which is staged row by row)
+static int check_image(rvio_hip* h, const void* d_img, int stride, size_t img_stride) {
+    if (stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
+    if (pix_is16(h->pix_fmt) && ((stride & 1) || (img_stride & 1) || ((uintptr_t)d_img & 1))) {
+        h->err = "a 16-bit image format needs an even row stride, instance stride and device address";
+        return RVIO_ERR_INVALID;
+    }
+    return RVIO_OK;
+}
 // The forms of ONE front-end call: the only place the mode of a call is derived.  img / stride / img_bs: the caller's image (nullptr: none)
 static FrontForms call_forms(const rvio_hip* h, bool piped_call, bool have_corner_list, const uint8_t* img, int stride, size_t img_bs) {
     const DevCfg& d = h->dc;
@@ -1343,7 +1367,7 @@ static FrontForms call_forms(const rvio_hip* h, bool piped_call, bool have_corne
     in.equalizer = h->cfg.enable_equalizer != 0;
     in.cl_tx = h->cl_tx; in.cl_ty = h->cl_ty; in.cl_tw = h->cl_tw; in.cl_th = h->cl_th;
     in.sp_win = (int)std::floor(.5 * h->cfg.min_dist);   // cornerSubPix half-window, FeatureDetector.cc:68
-    in.channels = h->pix_ch;
+    in.channels = pix_samples(h->pix_fmt); in.bits = pix_is16(h->pix_fmt) ? 16 : 8; in.bayer = pix_is_bayer(h->pix_fmt);
     in.piped_call = piped_call; in.have_corner_list = have_corner_list; in.frame_no = h->frame_no; in.first_cleared = h->first_cleared;
     in.src_dword = stride % 4 == 0 && ((uintptr_t)img & 3) == 0 && img_bs % 4 == 0;
     in.no_runahead = no_runahead(); in.no_device_polls = no_device_polls();
@@ -1375,11 +1399,11 @@ static int detect_dev(rvio_hip* h, const FrontForms& f, const uint8_t* img, int 
 }
 
 // ------------------------------------------------------------------ gray conversion (Tracker.cc:182-196)
-static int pix_channels(int fmt) { return fmt == RVIO_PIX_MONO8 ? 1 : (fmt == RVIO_PIX_RGB8 || fmt == RVIO_PIX_BGR8) ? 3 : 4; }
 // B interleaved images -> B packed gray images (instance stride W * H) on `st`, in the form f names
 static void launch_gray(rvio_hip* h, const FrontForms& f, const uint8_t* src, int stride, size_t src_bs, uint8_t* dst, hipStream_t st) {
     const DevCfg& d = h->dc;
-    const int bgr = (h->pix_fmt == RVIO_PIX_BGR8 || h->pix_fmt == RVIO_PIX_BGRA8) ? 1 : 0;
+    const int bgr = (!pix_is_bayer(h->pix_fmt) && ((h->pix_fmt & 15) == RVIO_PIX_BGR8 || (h->pix_fmt & 15) == RVIO_PIX_BGRA8)) ? 1 : 0;
+    const int pat = h->pix_fmt & 3;   // of a mosaic: RGGB, BGGR, GBRG, GRBG
     const size_t bs = (size_t)d.W * d.H;
     const dim3 g = lp_grid(f.gray_l), b = lp_block(f.gray_l);
     switch (f.gray) {
@@ -1388,19 +1412,30 @@ static void launch_gray(rvio_hip* h, const FrontForms& f, const uint8_t* src, in
     case LPGR_BYTE3: hipLaunchKernelGGL(gray_kernel<3>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs); break;
     case LPGR_DWORD4: hipLaunchKernelGGL(gray_kernel4<4>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs); break;
     case LPGR_BYTE4: hipLaunchKernelGGL(gray_kernel<4>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs); break;
+    case LPGR_W16_1: hipLaunchKernelGGL(raw16_kernel4<1>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs); break;
+    case LPGR_P16_1: hipLaunchKernelGGL(raw16_kernel<1>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs); break;
+    case LPGR_W16_3: hipLaunchKernelGGL(raw16_kernel4<3>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs); break;
+    case LPGR_P16_3: hipLaunchKernelGGL(raw16_kernel<3>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs); break;
+    case LPGR_W16_4: hipLaunchKernelGGL(raw16_kernel4<4>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs); break;
+    case LPGR_P16_4: hipLaunchKernelGGL(raw16_kernel<4>, g, b, 0, st, src, d.W, d.H, stride, bgr, dst, src_bs, bs); break;
+    case LPGR_BAYER8_W: hipLaunchKernelGGL(bayer_kernel4<uint8_t>, g, b, 0, st, src, d.W, d.H, stride, pat, dst, src_bs, bs); break;
+    case LPGR_BAYER8_P: hipLaunchKernelGGL(bayer_kernel<uint8_t>, g, b, 0, st, src, d.W, d.H, stride, pat, dst, src_bs, bs); break;
+    case LPGR_BAYER16_W: hipLaunchKernelGGL(bayer_kernel4<uint16_t>, g, b, 0, st, src, d.W, d.H, stride, pat, dst, src_bs, bs); break;
+    case LPGR_BAYER16_P: hipLaunchKernelGGL(bayer_kernel<uint16_t>, g, b, 0, st, src, d.W, d.H, stride, pat, dst, src_bs, bs); break;
     }
 }
 int rvio_hip_get_image_format(const rvio_hip* h) { return h ? h->pix_fmt : RVIO_ERR_INVALID; }
 int rvio_hip_set_image_format(rvio_hip* h, int format) {
     if (!h) return RVIO_ERR_INVALID;
-    if (format < RVIO_PIX_MONO8 || format > RVIO_PIX_BGRA8) { h->err = "unknown image format"; return RVIO_ERR_INVALID; }
+    if (!pix_known(format)) { h->err = "unknown image format"; return RVIO_ERR_INVALID; }
     if (format != RVIO_PIX_MONO8 && !h->front_end) { h->err = "this batch handle was created without its front end: it takes no image"; return RVIO_ERR_UNSUPPORTED; }
     if (format == h->pix_fmt) return RVIO_OK;
+    if (pix_is_bayer(format) && (h->dc.W < 3 || h->dc.H < 3)) { h->err = "a Bayer format needs an image of at least 3 x 3 pixels"; return RVIO_ERR_INVALID; }
     HIPCHK(h, hipSetDevice(h->device));
     { const int rc = drain_all(h); if (rc != RVIO_OK) return rc; }   // nothing in flight reads the staging or a gray buffer any more
-    const int ch = pix_channels(format);
+    const int ch = pix_bytes(format);   // bytes per pixel as staged
     const size_t npx = (size_t)h->dc.W * h->dc.H;
-    if (ch > 1 && !h->d_gray[0]) {   // first colour format: the gray buffers of every instance
+    if (format != RVIO_PIX_MONO8 && !h->d_gray[0]) {   // first converting format: the gray buffers of every instance
         uint8_t* p = nullptr;
         HIPCHK(h, hipMalloc((void**)&p, 4 * npx * (size_t)h->batch));
         h->allocs.push_back(p);
@@ -1609,7 +1644,7 @@ static int track_dev_impl(rvio_hip* h, const FrontForms& f, const uint8_t* d_img
     return rc;
 }
 int rvio_hip_track_dev(rvio_hip* h, const uint8_t* d_img, int stride, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand) {
-    if (!h || !d_img || m < 0 || n_cand < 0 || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
+    if (!h || !d_img || m < 0 || n_cand < 0 || check_image(h, d_img, stride, 0) != RVIO_OK) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     if (!d_cand) refresh_first_cleared(h);
     const FrontForms f = call_forms(h, false, d_cand != nullptr, d_img, stride, h->img_bs);   // a per-stage call: everything on the filter stream
@@ -1618,7 +1653,7 @@ int rvio_hip_track_dev(rvio_hip* h, const uint8_t* d_img, int stride, const rvio
 }
 
 int rvio_hip_track(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* imu, int m, const float* cand_xy, int n_cand) {
-    if (!h || !img || (!imu && m > 0) || m < 0 || n_cand < 0 || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
+    if (!h || !img || (!imu && m > 0) || m < 0 || n_cand < 0 || check_image(h, nullptr, stride, 0) != RVIO_OK) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     { const int rcg = ensure_imu_capacity(h, m); if (rcg != RVIO_OK) return rcg; }
@@ -1852,7 +1887,7 @@ static int frame_dev_impl(rvio_hip* h, const FrontForms& f, const uint8_t* d_img
     return rc;
 }
 int rvio_hip_frame_dev(rvio_hip* h, const uint8_t* d_img, int stride, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand) {
-    if (!h || !d_img || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
+    if (!h || !d_img || check_image(h, d_img, stride, 0) != RVIO_OK) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     return frame_dev_impl(h, frame_forms(h, d_img, stride, d_cand), d_img, stride, d_imu, m, d_cand, n_cand, false);
@@ -1861,7 +1896,7 @@ int rvio_hip_frame_dev(rvio_hip* h, const uint8_t* d_img, int stride, const rvio
 // row stride `stride`), d_imu[B][imu_stride] (0: shared).  Same pipelined body as rvio_hip_frame_dev, every launch with gridDim.z = B;
 // corners always come from the device detector.
 int rvio_hip_frame_batch_dev(rvio_hip* h, const uint8_t* d_imgs, int stride, size_t img_stride, const rvio_imu* d_imu, int imu_stride, int m) {
-    if (!h || !d_imgs || (!d_imu && m > 0) || imu_stride < 0 || (imu_stride > 0 && imu_stride < m) || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
+    if (!h || !d_imgs || (!d_imu && m > 0) || imu_stride < 0 || (imu_stride > 0 && imu_stride < m) || check_image(h, d_imgs, stride, h->batch > 1 ? img_stride : 0) != RVIO_OK) return RVIO_ERR_INVALID;
     if (!h->front_end) { h->err = "this batch handle was created without its front end"; return RVIO_ERR_UNSUPPORTED; }
     if (h->batch > 1 && img_stride < (size_t)stride * h->dc.H) return RVIO_ERR_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
@@ -1876,7 +1911,7 @@ int rvio_hip_frame_batch_dev(rvio_hip* h, const uint8_t* d_imgs, int stride, siz
 //       all on the filter stream (rvio_hip_stream) ...
 //   frame_end         closes the frame (hand-over buffer released for frame k+2)
 int rvio_hip_frame_begin_dev(rvio_hip* h, const uint8_t* d_img, int stride, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand) {
-    if (!h || !d_img || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
+    if (!h || !d_img || check_image(h, d_img, stride, 0) != RVIO_OK) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     return frame_dev_impl(h, frame_forms(h, d_img, stride, d_cand), d_img, stride, d_imu, m, d_cand, n_cand, false, /*begin_only=*/true);
@@ -1915,7 +1950,7 @@ static nccl_allgather_fn resolve_allgather(std::string* why) {
 // ncclAllGather from the loaded process image; a caller may hand in the entry point itself (same signature).
 int rvio_hip_frame_sharded_dev(rvio_hip* h, const uint8_t* d_img, int stride, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand,
                                int rank, int world, void* comm, void* allgather) {
-    if (!h || !d_img || world < 1 || rank < 0 || rank >= world || (!comm && world > 1) || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
+    if (!h || !d_img || world < 1 || rank < 0 || rank >= world || (!comm && world > 1) || check_image(h, d_img, stride, 0) != RVIO_OK) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     if (comm) h->extra_queues = true;   // the collective brings queues of its own: more than the four this handle's chains own (see the pyramid poll, build_pyramid_dev)
@@ -1951,7 +1986,7 @@ int rvio_hip_frame_sharded_dev(rvio_hip* h, const uint8_t* d_img, int stride, co
 // The three H2D copies go to the tracker stream into staging buffers double-buffered by frame parity, so they overlap
 // the previous frame's filter work like the tracker kernels do.
 int rvio_hip_frame(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* imu, int m, const float* cand_xy, int n_cand) {
-    if (!h || !img || (!imu && m > 0) || m < 0 || n_cand < 0 || stride < h->dc.W * h->pix_ch) return RVIO_ERR_INVALID;
+    if (!h || !img || (!imu && m > 0) || m < 0 || n_cand < 0 || check_image(h, nullptr, stride, 0) != RVIO_OK) return RVIO_ERR_INVALID;
     FRONT_END_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     { const int rcg = ensure_imu_capacity(h, m); if (rcg != RVIO_OK) return rcg; }
@@ -2160,7 +2195,7 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
         HIPCHK(h, hipMemcpyAsync(bx, h->x[h->cur], sizeof(double) * d.xdmax, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(bP, h->P[h->cur], sizeof(double) * d.dmax * d.dmax, hipMemcpyDeviceToDevice, h->stream));
     }
-    if (which == 11 && (h->pix_ch < 2 || !h->last.gray_src)) { h->err = "no colour image has been handed over (rvio_hip_set_image_format)"; return RVIO_ERR_UNSUPPORTED; }
+    if (which == 11 && (h->pix_fmt == RVIO_PIX_MONO8 || !h->last.gray_src)) { h->err = "no colour or raw image has been handed over (rvio_hip_set_image_format)"; return RVIO_ERR_UNSUPPORTED; }
     rvio_odom* odt = nullptr;
     if (which == 12) {   // (into a slot of its own: the ring stays what the frames wrote)
         if (!h->odom_ring) { h->err = "the odometry ring was never enabled (rvio_hip_set_odometry)"; return RVIO_ERR_UNSUPPORTED; }

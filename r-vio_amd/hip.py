@@ -90,6 +90,7 @@ class RvioHip:
         self.nmax = cfg.max_track_len - 1
         self.Fu = abi.fu(cfg)
         self.channels = 1
+        self.sample_dtype = "uint8"
 
     def close(self):
         if getattr(self, "h", None):
@@ -212,25 +213,32 @@ class RvioHip:
 
     # ---- colour cameras (Tracker.cc:182-196)
     def set_image_format(self, fmt):
-        """abi.RVIO_PIX_*: what img / d_img of the image entry points hold from the next image on (colour: interleaved pixels, converted on the device)"""
+        """abi.RVIO_PIX_*: what img / d_img of the image entry points hold from the next image on (colour: interleaved pixels; 16-bit formats: uint16
+        samples in host byte order; Bayer: the mosaic, one sample per pixel — all converted on the device)"""
         self._ck(self.L.rvio_hip_set_image_format(self.h, int(fmt)), "set_image_format")
-        self.channels = abi.PIX_CHANNELS[int(fmt)]
+        bpp, self.sample_dtype, ch = abi.PIX_LAYOUT[int(fmt)]
+        self.channels = ch or 1
 
     def image_format(self):
         return int(self.L.rvio_hip_get_image_format(self.h))
 
     def _img(self, img):
-        """(array, row stride in bytes): a row-strided uint8 view is handed over as it is (cv::Mat::step), anything else is packed.
-        H x W with the mono format, H x W x 3|4 (interleaved) with a colour format: any other shape is refused"""
+        """(array, row stride in bytes): a row-strided view of the format's sample type is handed over as it is (cv::Mat::step), anything else is
+        packed.  H x W with the mono formats and the Bayer mosaics, H x W x 3|4 (interleaved) with a colour format, uint16 samples with a 16-bit
+        format (abi.PIX_LAYOUT): any other shape is refused, and so is an array that is not uint16 handed to a 16-bit format"""
         img = np.asarray(img)
         ch = self.channels
+        dt = np.dtype(getattr(self, "sample_dtype", "uint8"))
         if img.ndim != (2 if ch == 1 else 3) or (ch > 1 and img.shape[2] != ch):
-            raise RvioHipError("image of shape %s handed to a handle whose format has %d byte(s) per pixel (set_image_format)" % (img.shape, ch))
+            raise RvioHipError("image of shape %s handed to a handle whose format has %d sample(s) per pixel (set_image_format)" % (img.shape, ch))
+        if dt == np.uint16 and img.dtype != np.uint16:
+            raise RvioHipError("%s image handed to a handle whose format has 16-bit samples (set_image_format)" % img.dtype)
+        sz = dt.itemsize
         if ch == 1:
-            if img.dtype != np.uint8 or img.strides[1] != 1 or img.strides[0] < img.shape[1]:
-                img = np.ascontiguousarray(img, np.uint8)
-        elif img.dtype != np.uint8 or img.strides[2] != 1 or img.strides[1] != ch or img.strides[0] < img.shape[1] * ch:
-            img = np.ascontiguousarray(img, np.uint8)
+            if img.dtype != dt or img.strides[1] != sz or img.strides[0] < img.shape[1] * sz:
+                img = np.ascontiguousarray(img, dt)
+        elif img.dtype != dt or img.strides[2] != sz or img.strides[1] != ch * sz or img.strides[0] < img.shape[1] * ch * sz:
+            img = np.ascontiguousarray(img, dt)
         return img, img.strides[0]
 
     def track(self, img, imu, cand=None):
@@ -395,7 +403,7 @@ class RvioHip:
         return xy, un
 
     def time_kernel(self, which, iters=20):
-        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection, 10 the landmark cloud kernel, 11 the gray conversion of the last colour image, 12 the odometry record kernel (HIP events, handle stream)"""
+        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection, 10 the landmark cloud kernel, 11 the gray conversion of the last colour or raw (16-bit, Bayer) image in the form the frame launched, 12 the odometry record kernel (HIP events, handle stream)"""
         us = C.c_float(0)
         self._ck(self.L.rvio_hip_debug_time_kernel(self.h, int(which), int(iters), C.byref(us)), "debug_time_kernel")
         return float(us.value)
