@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -271,7 +271,7 @@ int rvio_hip_frame_plan(rvio_hip* h, int* do_update, int* do_augment);
 int rvio_hip_propagate_dev(rvio_hip* h, const rvio_imu* d_imu, int m);
 
 /* --- batched instances ---------------------------------- */
-/* B independent instances (B robots / B replays of the same sensor rate) behind one handle:
+/* B independent instances (B robots, each with its own camera: rvio_hip_set_calibration_at below) behind one handle:
  * every buffer of instance i lives in slab i, and every stage is ONE launch with
  * gridDim.z = B, i.e. the single-workgroup stages of one filter become B workgroups.  The
  * arithmetic of an instance is the arithmetic of a plain handle, bit for bit.  The reference
@@ -282,12 +282,52 @@ int rvio_hip_propagate_dev(rvio_hip* h, const rvio_imu* d_imu, int m);
  * rvio_hip_frame_batch_dev).  The single-instance entry points return RVIO_ERR_UNSUPPORTED on
  * a batch handle; the window length is common to all instances (it depends on the frame count
  * only, System.cc:266,280).  rvio_hip_set_state / rvio_hip_initialize give every instance the
- * same state, rvio_hip_get_state reads instance 0. */
+ * same state (rvio_hip_set_state_at / rvio_hip_initialize_at: one instance), rvio_hip_get_state reads instance 0.  Every instance starts
+ * with the camera calibration of `cfg`; a fleet then binds each robot's own (see "per-instance calibration"). */
 int rvio_hip_create_batch(const rvio_config* cfg, int device, int n_instances, int front_end,
                           rvio_hip** out);
 int rvio_hip_batch_size(const rvio_hip* h);
 int rvio_hip_set_state_at(rvio_hip* h, int instance, const double* x, int xdim, const double* P, int d);
 int rvio_hip_get_state_at(rvio_hip* h, int instance, double* x, int* xdim, double* P, int* d);
+/* System::initialize (System.cc:115-170) for ONE instance: each robot has its own gravity direction and biases.  The x(26), P(24 x 24) that
+ * rvio_hip_initialize computes from (w, a, n_imu), stored as rvio_hip_set_state_at stores them — and none of the handle-wide resets of
+ * rvio_hip_initialize (frame count, tracker, landmark cloud, odometry ring), so it belongs between create / rvio_hip_initialize and the
+ * first frame: RVIO_ERR_STATE when the window is not empty, RVIO_ERR_INVALID for a NULL argument or an instance out of range. */
+int rvio_hip_initialize_at(rvio_hip* h, int instance, const double w[3], const double a[3], int n_imu);
+
+/* --- per-instance calibration ---------------------------------------------------- */
+/* What differs between two physical cameras: the intrinsics, the distortion model and the camera-IMU extrinsic.  A handle is created with
+ * one rvio_config, and every instance starts with that config's calibration; these entry points give instance i its own, so that a batch
+ * handle serves B different robots.  The calibration is read by the undistortion (Tracker.cc:100-130) and RANSAC's gyro prior
+ * (Ransac.cc:120-155) in the front end, and by the per-feature triangulation / Jacobian stage (Updater.cc:114-375) and the landmark cloud
+ * (Updater.cc:430-448) in the filter: the arithmetic of an instance is that of a handle created with its calibration in the config, bit for
+ * bit.
+ * DELIBERATELY HANDLE-WIDE (common to all instances, taken from the config at create): the image size (width, height); sigma_px / sigma_py
+ * (the measurement noise sigma_im); every Tracker.* key (n_features, max_track_len, min_track_len, min_dist, qual_lvl, block_x, block_y,
+ * enable_equalizer, use_sampson, inlier_thr); every IMU.* key (imu_rate, the four sigmas, gravity, small_angle); every INI.* key. */
+typedef struct rvio_calibration {   /* 168 bytes, no padding */
+    float fx, fy, cx, cy;           /* Tracker.cc:39-42 */
+    float k1, k2, p1, p2, k3;       /* Tracker.cc:51-61 */
+    int32_t fisheye;                /* Camera.Fisheye */
+    double T_bc[16];                /* Camera.T_BC0, ROW-major 4x4, rows 0..2 are read (Updater.cc:46-53) */
+} rvio_calibration;
+/* the calibration members of a config, copied */
+void rvio_calibration_from_config(const rvio_config* cfg, rvio_calibration* out);
+/* set: one instance / all of them (`all` holds rvio_hip_batch_size entries, uploaded in one copy).  A setter drains the handle, as
+ * rvio_hip_set_image_format does, and holds from the next call enqueued.  The first setter allocates a table of one entry per instance
+ * outside the filter slab (filled from the config); a handle on which none was ever called allocates nothing and launches what it launched
+ * before these entry points existed.  A plain handle is accepted with instance 0 only: re-calibration without re-creating the handle, also for
+ * the ranks of the feature-sharded updater (set every rank alike).
+ * Meant to be called BEFORE THE FIRST FRAME: observations already in a tracking history keep the normalised coordinates they were recorded
+ * with (they were undistorted under the calibration of their frame), so a change in mid-sequence mixes the two until those tracks have ended.
+ * rvio_hip_initialize, rvio_hip_set_state and rvio_hip_set_state_at leave calibrations alone, and so does rvio_hip_debug_poison.
+ * RVIO_ERR_INVALID: NULL handle or calibration, instance out of range, a non-finite member (any of the nine floats or sixteen doubles), fx or
+ * fy equal to 0 (rvio_hip_last_error names the instance).
+ * get: what instance i computes with — the config's values until a setter changed them. */
+int rvio_hip_set_calibration_at(rvio_hip* h, int instance, const rvio_calibration* cal);
+int rvio_hip_set_calibrations(rvio_hip* h, const rvio_calibration* all /* rvio_hip_batch_size entries, one copy */);
+int rvio_hip_get_calibration_at(rvio_hip* h, int instance, rvio_calibration* cal);
+
 /* rvio_hip_get_tracker_points of one instance (batch handle with front end): Tracker::mvFeatsToTrack
  * and the length of each feature's tracking history. */
 int rvio_hip_get_tracker_points_at(rvio_hip* h, int instance, int32_t* n, float* xy, int32_t* hist_len);

@@ -50,6 +50,30 @@ class rvio_config(C.Structure):
     ]
 
 
+class rvio_calibration(C.Structure):
+    """what differs between two physical cameras (rvio_hip_set_calibration_at): 168 bytes, no padding"""
+    _fields_ = [
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("k1", C.c_float), ("k2", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("k3", C.c_float),
+        ("fisheye", C.c_int32),
+        ("T_bc", C.c_double * 16),
+    ]
+
+
+assert C.sizeof(rvio_calibration) == 168
+
+
+def calibration_from_config(cfg):
+    """the calibration members of an rvio_config (same as C rvio_calibration_from_config)"""
+    k = rvio_calibration()
+    for name, _ in rvio_calibration._fields_:
+        if name != "T_bc":
+            setattr(k, name, getattr(cfg, name))
+    for i in range(16):
+        k.T_bc[i] = cfg.T_bc[i]
+    return k
+
+
 class rvio_imu(C.Structure):
     _fields_ = [("w", C.c_double * 3), ("a", C.c_double * 3), ("t", C.c_double), ("dt", C.c_double)]
 

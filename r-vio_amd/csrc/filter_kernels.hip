@@ -123,12 +123,12 @@ __device__ __forceinline__ double ldlt_gamma_wave(const double* S, int lds_s, in
 
 // HOIST: k-values whose operand loads are in flight before the first MFMA of a gate tile (16: one stream, latency; 4: batch handles, 128 VGPRs)
 template <int HOIST>
-__device__ __forceinline__ void feat_build_body(DevCfg cfg, int n, const double* x, const double* P,
+__device__ __forceinline__ void feat_build_body(const DevCfg& cfg, int n, const double* x, const double* P,
                                                 const int* n_feat_ptr, const unsigned char* types, const int* lens, const float* meas,
                                                 int shard_rank, int shard_world,
                                                 double* Gshare, int* nrows_out, int* acc_out, int* ndof_out, double* gamma_out,
                                                 double* pfinv_out, double* tm_global, size_t bs, BatchIn bin, FilterMeta* meta, const int f,
-                                                const double* gpose = nullptr, const int* gvalid = nullptr, double* lit_rows = nullptr) {
+                                                const CamCal* __restrict__ cal, const double* gpose = nullptr, const int* gvalid = nullptr, double* lit_rows = nullptr) {
     extern __shared__ __align__(16) double lds[];
     DBG_P0();
     const BatchIdx bi = batch_plain();
@@ -187,8 +187,9 @@ __device__ __forceinline__ void feat_build_body(DevCfg cfg, int n, const double*
     else for (int e = tid; e < 7 * n; e += T) xcl[e] = x[26 + e];
     const bool wave0 = tid < 64;
     const double sig = cfg.sigma_im, sig2 = sig * sig;
-    const m33 Ric = ldm33(cfg.Ric), Rci = ldm33(cfg.Rci);
-    const d3 tic = ld3(cfg.tic), tci = ld3(cfg.tci);
+    const CamCal cam = cam_of(cfg, cal, bi.z);
+    const m33 Ric = ldm33(cam.Ric), Rci = ldm33(cam.Rci);
+    const d3 tic = ld3(cam.tic), tci = ld3(cam.tci);
     DBG_T(30); DBG_P(30);
     __syncthreads();
     DBG_T(31); DBG_P(31);
@@ -694,9 +695,9 @@ __global__ __launch_bounds__(HOIST > 4 ? 256 : 1024) void feat_build_kernel(DevC
                                   int shard_rank, int shard_world,
                                   double* Gshare, int* nrows_out, int* acc_out, int* ndof_out, double* gamma_out,
                                   double* pfinv_out, double* tm_global, size_t bs, BatchIn bin, FilterMeta* meta,
-                                  const double* gpose, const int* gvalid, double* lit_rows) {
+                                  const double* gpose, const int* gvalid, double* lit_rows, const CamCal* __restrict__ cal) {
     feat_build_body<HOIST>(cfg, n, x, P, n_feat_ptr, types, lens, meas, shard_rank, shard_world, Gshare, nrows_out, acc_out, ndof_out, gamma_out, pfinv_out,
-                           tm_global, bs, bin, meta, (int)blockIdx.x, gpose, gvalid, lit_rows);
+                           tm_global, bs, bin, meta, (int)blockIdx.x, cal, gpose, gvalid, lit_rows);
 }
 
 // =============================================================== U1 + U2, four features per wave (batch handles, max_len <= 16)
@@ -717,7 +718,8 @@ __device__ __forceinline__ double row16_sum_b(double v) {
 #define GEOM4_ML 16
 __global__ __launch_bounds__(64) void geom4_kernel(DevCfg cfg, int n, const double* __restrict__ x, const int* __restrict__ n_feat_ptr,
                                                    const unsigned char* __restrict__ types, const int* __restrict__ lens, const float* __restrict__ meas,
-                                                   double* __restrict__ gpose, double* __restrict__ pfinv_out, int* __restrict__ gvalid, size_t bs, BatchIn bin) {
+                                                   double* __restrict__ gpose, double* __restrict__ pfinv_out, int* __restrict__ gvalid, size_t bs, BatchIn bin,
+                                                   const CamCal* __restrict__ cal) {
     const int z = blockIdx.z;
     x = zoffi(x, bs, z); gpose = zoffi(gpose, bs, z); pfinv_out = zoffi(pfinv_out, bs, z); gvalid = zoffi(gvalid, bs, z);
     n_feat_ptr = zoffi(n_feat_ptr, bin.n_feat, z); types = zoffi(types, bin.types, z); lens = zoffi(lens, bin.len, z); meas = zoffi(meas, bin.meas, z);
@@ -736,8 +738,9 @@ __global__ __launch_bounds__(64) void geom4_kernel(DevCfg cfg, int n, const doub
     if (active && l < L) { const float* mz = meas + (size_t)f * ML * 2; mxv = mz[2 * l]; myv = mz[2 * l + 1]; }
     for (int e = lane; e < 7 * n; e += 64) xcl[e] = x[26 + e];
     const double sig = cfg.sigma_im, sig2 = sig * sig;
-    const m33 Ric = ldm33(cfg.Ric), Rci = ldm33(cfg.Rci);
-    const d3 tic = ld3(cfg.tic), tci = ld3(cfg.tci);
+    const CamCal cam = cam_of(cfg, cal, z);
+    const m33 Ric = ldm33(cam.Ric), Rci = ldm33(cam.Rci);
+    const d3 tic = ld3(cam.tic), tci = ld3(cam.tci);
     __syncthreads();
     double* pose = poses[g];
     // ---- U1 (feat_build_kernel, same expressions: the chain as a prefix scan inside the feature's 16-lane row)

@@ -341,7 +341,7 @@ __global__ __launch_bounds__(256) void feat_prop_kernel(DevCfg cfg, int n, doubl
                                                         double* Gshare, int* nrows_out, int* acc_out, int* ndof_out, double* gamma_out,
                                                         double* pfinv_out, double* tm_global, BatchIn bin,
                                                         FilterMeta* meta, const rvio_imu* imu, int m, double* chol_scr, int chol_nt, int shard_rank, int shard_world,
-                                                        double* lit_rows) {
+                                                        double* lit_rows, const CamCal* __restrict__ cal) {
     DBG_R(blockIdx.x == 0, 0);
     DBG_W(blockIdx.x == 0 && threadIdx.x == 0, 28);
     extern __shared__ __align__(16) double fp_dyn[];
@@ -351,7 +351,7 @@ __global__ __launch_bounds__(256) void feat_prop_kernel(DevCfg cfg, int n, doubl
         else s9_chol_role<3>(cfg, n, P, chol_scr, *reinterpret_cast<S9CholLds<6, 4>*>(fp_dyn));
         return;
     }
-    feat_build_body<16>(cfg, n, x, P, n_feat_ptr, types, lens, meas, shard_rank, shard_world, Gshare, nrows_out, acc_out, ndof_out, gamma_out, pfinv_out, tm_global, 0, bin, meta, (int)blockIdx.x, nullptr, nullptr, lit_rows);
+    feat_build_body<16>(cfg, n, x, P, n_feat_ptr, types, lens, meas, shard_rank, shard_world, Gshare, nrows_out, acc_out, ndof_out, gamma_out, pfinv_out, tm_global, 0, bin, meta, (int)blockIdx.x, cal, nullptr, nullptr, lit_rows);
 }
 
 // =============================================================== S1 + S2 fused (v2): augmentation/slide + composition

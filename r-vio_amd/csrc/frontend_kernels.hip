@@ -77,7 +77,7 @@ __device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1)
 // (the KLT kernel itself is klt_kernel3 in klt3.hip)
 
 // ------------------------------------------------------------------ undistort (cv::undistortPoints, 5 fixed iterations)
-__device__ __forceinline__ void undistort_pt(const DevCfg& c, float u, float v, float* ox, float* oy) {
+__device__ __forceinline__ void undistort_pt(const CamCal& c, float u, float v, float* ox, float* oy) {
     const double fx = c.fx, fy = c.fy, cx = c.cx, cy = c.cy;
     if (c.fisheye) {   // cv::fisheye::undistortPoints (Tracker.cc:118-119) with D = (k1, k2, p1, p2): ten fixed-point iterations on theta
         const double k0 = c.k1, k1 = c.k2, k2 = c.p1, k3 = c.p2;
@@ -204,7 +204,7 @@ __device__ __forceinline__ double algebraic_err(d3 p1, d3 p2, const m33& E) {  /
 // UndistortAndNormalize of the tracked points + Ransac::FindInliers.  One workgroup, 256 threads.
 // un1: previous-frame normalised coords (mPoints1ForRansac, z = 1), un2: output for this frame.
 // Dynamic LDS: cand[F] ints + first[F] ints (SetPointPair).
-__device__ __forceinline__ void ransac_body(const DevCfg& cfg, const int* n_pts_ptr, const float* tracked, const float* un1, float* un2,
+__device__ __forceinline__ void ransac_body(const DevCfg& cfg, const CamCal* __restrict__ cal, const int* n_pts_ptr, const float* tracked, const float* un1, float* un2,
                                             unsigned char* status, const rvio_imu* imu, int m, int* rng,
                                             rvio_frame_info* info, size_t bs, size_t imu_bs, unsigned char* dsh) {
     __shared__ int s_w[16];
@@ -222,6 +222,7 @@ __device__ __forceinline__ void ransac_body(const DevCfg& cfg, const int* n_pts_
     int* cand = (int*)dsh;
     int* first = cand + cfg.F;   // SetPointPair: index of the first draw that produced each candidate position
     const int tid = threadIdx.x, T = blockDim.x, N = *n_pts_ptr;   // T: 256 .. 1024 threads (a multiple of 256)
+    const CamCal cam = cam_of(cfg, cal, blockIdx.z);
     // one batch of global reads: RNG state, IMU samples (-> per-sample delta rotations), the points
     if (tid < 35) s_rng[tid] = rng[tid];
     // GetRotation, Ransac.cc:120-155 (raw gyro, no bias removal): per-sample dR
@@ -240,7 +241,7 @@ __device__ __forceinline__ void ransac_body(const DevCfg& cfg, const int* n_pts_
         const m33 dR = gyro_dR(s);
         for (int k = 0; k < 9; ++k) dRs[s][k] = dR.m[k];
     }
-    for (int i = tid; i < N; i += T) undistort_pt(cfg, tracked[2 * i], tracked[2 * i + 1], &un2[2 * i], &un2[2 * i + 1]);
+    for (int i = tid; i < N; i += T) undistort_pt(cam, tracked[2 * i], tracked[2 * i + 1], &un2[2 * i], &un2[2 * i + 1]);
     // ordered compaction of candidate indices (status != 0)
     int nc = 0;
     for (int base = 0; base < N; base += T) {
@@ -300,7 +301,7 @@ __device__ __forceinline__ void ransac_body(const DevCfg& cfg, const int* n_pts_
         if (lane < 35) rng[lane] = s_rng[lane];
     }
     else if (tid < 128) {   // beside the pair selection: the gyro prior R = Rci (dR_m-1 ... dR_0) Ric, a serial product of the per-sample rotations (same for the 16 models)
-        const m33 Ric = ldm33(cfg.Ric), Rci = ldm33(cfg.Rci);
+        const m33 Ric = ldm33(cam.Ric), Rci = ldm33(cam.Rci);
         m33 R = eye33();
         for (int s = 0; s < m_lds; ++s) R = mul33(ldm33(dRs[s]), R);
         for (int s = m_lds; s < m; ++s) R = mul33(gyro_dR(s), R);
@@ -364,9 +365,9 @@ __device__ __forceinline__ void ransac_body(const DevCfg& cfg, const int* n_pts_
 }
 __global__ __launch_bounds__(256) void ransac_kernel(DevCfg cfg, const int* n_pts_ptr, const float* tracked, const float* un1, float* un2,
                                                      unsigned char* status, const rvio_imu* imu, int m, int* rng,
-                                                     rvio_frame_info* info, size_t bs, size_t imu_bs) {
+                                                     rvio_frame_info* info, size_t bs, size_t imu_bs, const CamCal* __restrict__ cal) {
     extern __shared__ __align__(16) unsigned char dsh_r[];
-    ransac_body(cfg, n_pts_ptr, tracked, un1, un2, status, imu, m, rng, info, bs, imu_bs, dsh_r);
+    ransac_body(cfg, cal, n_pts_ptr, tracked, un1, un2, status, imu, m, rng, info, bs, imu_bs, dsh_r);
 }
 
 // ------------------------------------------------------------------ T6 book-keeping + refill
@@ -504,9 +505,9 @@ __global__ __launch_bounds__(64) void stage_signal_kernel(unsigned long long* ct
 // separates them since the hand-over does not wait for the detector): one launch boundary less before the filter may start
 __global__ __launch_bounds__(256) void ransac_book_a_kernel(DevCfg cfg, TrackerDev t, const rvio_imu* imu, int m, int* rng, size_t bs, size_t imu_bs,
                                                             const unsigned long long* done, unsigned long long done_target, FilterMeta* meta,
-                                                            unsigned long long* hand) {
+                                                            unsigned long long* hand, const CamCal* __restrict__ cal) {
     extern __shared__ __align__(16) unsigned char dsh_ra[];
-    ransac_body(cfg, t.n_pts, t.tracked, t.un1, t.un2, t.status, imu, m, rng, t.info, bs, imu_bs, dsh_ra);
+    ransac_body(cfg, cal, t.n_pts, t.tracked, t.un1, t.un2, t.status, imu, m, rng, t.info, bs, imu_bs, dsh_ra);
     __threadfence_block();
     __syncthreads();
     bookkeep_a_body(cfg, t, bs, done, done_target, meta);
@@ -514,7 +515,7 @@ __global__ __launch_bounds__(256) void ransac_book_a_kernel(DevCfg cfg, TrackerD
 }
 
 // corners / corners_target (single instance, run-ahead mode): the counter stage_signal_kernel bumps behind this frame's cornerSubPix
-__device__ __forceinline__ void bookkeep_b_body(const DevCfg& cfg, TrackerDev t, const float* cand, int n_cand, const int* n_cand_dev, size_t bs,
+__device__ __forceinline__ void bookkeep_b_body(const DevCfg& cfg, const CamCal* __restrict__ cal, TrackerDev t, const float* cand, int n_cand, const int* n_cand_dev, size_t bs,
                                                 const unsigned long long* corners, unsigned long long corners_target, FilterMeta* meta, unsigned char* dsh) {
     if (corners && !stage_wait(corners, corners_target, meta)) return;   // (timed out: error bit 4 is set)
     DBG_S(blockIdx.z == 0, 6);
@@ -522,6 +523,7 @@ __device__ __forceinline__ void bookkeep_b_body(const DevCfg& cfg, TrackerDev t,
     tracker_shift(t, (size_t)blockIdx.z * bs); cand = zoff(cand, bs); if (n_cand_dev) n_cand_dev = zoff(n_cand_dev, bs);
     __shared__ int s_w[16];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, F = cfg.F, ML = cfg.max_len;
+    const CamCal cam = cam_of(cfg, cal, blockIdx.z);
     const int T = blockDim.x, nwv = T >> 6;   // 4 waves for batch handles, up to 16 for one stream: the cell walk below is one wave per grid cell
     float2* tfs = (float2*)dsh;
     float2* cds = tfs + F;
@@ -543,7 +545,7 @@ __device__ __forceinline__ void bookkeep_b_body(const DevCfg& cfg, TrackerDev t,
         for (int i = tid; i < F; i += T) {
             if (i < n0) {
                 float ux, uy;
-                undistort_pt(cfg, cds[i].x, cds[i].y, &ux, &uy);
+                undistort_pt(cam, cds[i].x, cds[i].y, &ux, &uy);
                 feats[i] = cds[i];
                 un1[i] = make_float2(ux, uy);
                 hist[(size_t)i * ML] = make_float2(ux, uy);
@@ -648,7 +650,7 @@ __device__ __forceinline__ void bookkeep_b_body(const DevCfg& cfg, TrackerDev t,
             if (fr && k < nNew) {
                 float ux, uy;
                 const float2 p = tfs[nIn + k];
-                undistort_pt(cfg, p.x, p.y, &ux, &uy);
+                undistort_pt(cam, p.x, p.y, &ux, &uy);
                 tu[nIn + k] = make_float2(ux, uy);
                 t.tmp_slot[nIn + k] = s;
                 hist[(size_t)s * ML] = make_float2(ux, uy);
@@ -667,9 +669,10 @@ __device__ __forceinline__ void bookkeep_b_body(const DevCfg& cfg, TrackerDev t,
 }
 
 __global__ __launch_bounds__(1024) void bookkeep_b_kernel(DevCfg cfg, TrackerDev t, const float* cand, int n_cand, const int* n_cand_dev, size_t bs,
-                                                          const unsigned long long* corners, unsigned long long corners_target, FilterMeta* meta) {
+                                                          const unsigned long long* corners, unsigned long long corners_target, FilterMeta* meta,
+                                                          const CamCal* __restrict__ cal) {
     extern __shared__ __align__(16) unsigned char dsh[];
-    bookkeep_b_body(cfg, t, cand, n_cand, n_cand_dev, bs, corners, corners_target, meta, dsh);
+    bookkeep_b_body(cfg, cal, t, cand, n_cand, n_cand_dev, bs, corners, corners_target, meta, dsh);
 }
 // (round 6) RANSAC and BOTH halves of book-keeping in one launch, for one stream in run-ahead mode: the hand-over counter is bumped between the
 // halves exactly where the two-kernel form bumps it, the refill half polls the detector's counter as before — one launch boundary (~8 us) less
@@ -678,9 +681,10 @@ __global__ __launch_bounds__(1024) void bookkeep_b_kernel(DevCfg cfg, TrackerDev
 __global__ __launch_bounds__(1024) void ransac_book_kernel(DevCfg cfg, TrackerDev t, const rvio_imu* imu, int m, int* rng, size_t bs, size_t imu_bs,
                                                            const unsigned long long* done, unsigned long long done_target, FilterMeta* meta,
                                                            unsigned long long* hand, const float* cand, const int* n_cand_dev,
-                                                           const unsigned long long* corners, unsigned long long corners_target) {
+                                                           const unsigned long long* corners, unsigned long long corners_target,
+                                                           const CamCal* __restrict__ cal) {
     extern __shared__ __align__(16) unsigned char dsh_rb[];
-    ransac_body(cfg, t.n_pts, t.tracked, t.un1, t.un2, t.status, imu, m, rng, t.info, bs, imu_bs, dsh_rb);
+    ransac_body(cfg, cal, t.n_pts, t.tracked, t.un1, t.un2, t.status, imu, m, rng, t.info, bs, imu_bs, dsh_rb);
     __threadfence_block();
     __syncthreads();
     bookkeep_a_body(cfg, t, bs, done, done_target, meta);
@@ -689,7 +693,7 @@ __global__ __launch_bounds__(1024) void ransac_book_kernel(DevCfg cfg, TrackerDe
     // device-scope fence here — an L2 write-back on the multi-XCD part — sat on the side chain's serial path)
     if (hand) stage_signal(hand);
     else { __threadfence(); __syncthreads(); }
-    bookkeep_b_body(cfg, t, cand, 0, n_cand_dev, bs, corners, corners_target, meta, dsh_rb);
+    bookkeep_b_body(cfg, cal, t, cand, 0, n_cand_dev, bs, corners, corners_target, meta, dsh_rb);
 }
 // direct-track mode: the caller supplies vFeatsTracked / vInlierFlag (the KLT result)
 __global__ void load_points_kernel(const int* n_pts_ptr, const float* in_xy, const unsigned char* in_st, float* tracked, unsigned char* status) {

@@ -18,7 +18,7 @@ struct LmOut { int* count; int* feat; double* p_r; double* p_w; size_t bs; };   
 
 __global__ __launch_bounds__(LM_MAX_T) void landmark_kernel(DevCfg cfg, int n, const double* __restrict__ xk1k, const double* __restrict__ xk1k1,
                                                            const int* n_feat_ptr, const unsigned char* types, const int* lens,
-                                                           const int* acc, const double* pfinv, size_t bs, BatchIn bin, LmOut out) {
+                                                           const int* acc, const double* pfinv, size_t bs, BatchIn bin, LmOut out, const CamCal* __restrict__ cal) {
     __shared__ int wave_cnt[LM_MAX_T / 64];
     const int z = blockIdx.z;
     xk1k = zoffi(xk1k, bs, z); xk1k1 = zoffi(xk1k1, bs, z); acc = zoffi(acc, bs, z); pfinv = zoffi(pfinv, bs, z);
@@ -29,8 +29,9 @@ __global__ __launch_bounds__(LM_MAX_T) void landmark_kernel(DevCfg cfg, int n, c
     double* p_w = zoffi(out.p_w, out.bs, z);
     const int nf = min(max(*n_feat_ptr, 0), cfg.Fu);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    const m33 Ric = ldm33(cfg.Ric);
-    const d3 tic = ld3(cfg.tic);
+    const CamCal cam = cam_of(cfg, cal, z);
+    const m33 Ric = ldm33(cam.Ric);
+    const d3 tic = ld3(cam.tic);
     const m33 RG = q2r(ldq(xk1k1));
     const d3 pG = ld3(xk1k1 + 4);
     int base = 0;   // members in the chunks before this one

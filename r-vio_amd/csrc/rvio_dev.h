@@ -17,13 +17,21 @@
 
 #define RVIO_MAX_IMU 192     // IMU samples per call (= RVIO_HIP_MAX_IMU of the header): RANSAC forms one delta rotation per thread
 
+// What one physical camera contributes: Camera.fx .. k3, Camera.Fisheye and Camera.T_BC0 split into its rotations and lever arms.  Every
+// instance of a handle has one: the handle's common copy (DevCfg::cam) or, once rvio_hip_set_calibration* was called, its entry of a table
+// of B entries outside the filter slab.  232 bytes, no padding.
+struct CamCal {
+    double Ric[9], Rci[9], tic[3], tci[3];  // row-major 3x3 (Updater.cc:46-53)
+    float fx, fy, cx, cy, k1, k2, p1, p2, k3;
+    int fisheye;   // Camera.Fisheye: cv::fisheye::undistortPoints instead of cv::undistortPoints (Tracker.cc:116-119)
+};
+
 struct DevCfg {
     double gravity, small_angle;
     double sg2, swg2, sa2, swa2;  // squared IMU sigmas (ImuNoiseMatrix diagonal, PreIntegrator.cc:40-44)
     double sigma_im;              // max(sigma_px, sigma_py) as float->double (Updater.cc:42-44)
     double inlier_thr;
-    double Ric[9], Rci[9], tic[3], tci[3];  // row-major 3x3 (Updater.cc:46-53)
-    float fx, fy, cx, cy, k1, k2, p1, p2, k3;
+    CamCal cam;    // the calibration of the config the handle was created with; kernels read it through cam_of() only
     float min_dist, off_x, off_y, max_per_block;  // FeatureDetector.cc:29-52; the last three hold the reference's INT members (FeatureDetector.h:69-77)
     float block_x, block_y;                       // float members upstream (FeatureDetector.h:72-73)
     int W, H;
@@ -33,7 +41,6 @@ struct DevCfg {
     int ldh;       // row stride (doubles) of stacked [Hx | r] rows = 6*nmax + 1
     int grid_cols, grid_rows;
     int use_sampson;
-    int fisheye;   // Camera.Fisheye: cv::fisheye::undistortPoints instead of cv::undistortPoints (Tracker.cc:116-119)
     int levels;    // pyramid levels actually used (maxLevel+1)
 };
 
@@ -71,6 +78,26 @@ __device__ __forceinline__ BatchIdx batch_remap() {
 // (measured, B = 2048: the remap pays for ug / final / gemm_T — few workgroups per instance sharing W, A, Pc, G, U — and costs
 // 8-12 % for feat_build / gram_mfma, whose active workgroups are the first few of 100 / 13 slots: those keep the plain order)
 __device__ __forceinline__ BatchIdx batch_plain() { return {(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z}; }
+// The calibration of instance z — the ONE place device code reads cfg.cam.  cal == nullptr (no setter was ever called on the handle): the
+// common copy in the kernel arguments, as before the table existed.  z must be the instance index the kernel itself uses and a pure
+// blockIdx expression: the entry then arrives by scalar loads, like the kernel arguments it replaces.  Both sources are addressed in the
+// CONSTANT address space (the kernel-argument segment lies there; the table is only rewritten on a drained handle, so it is constant for
+// every kernel that reads it): the choice is a select between two pointers of one address space and every member a uniform load from it.
+// (Chosen between a generic pointer to the table and the arguments, the compiler merged the two into flat — vector — loads.)
+// cfg must be the kernel's own DevCfg argument.
+typedef const __attribute__((address_space(4))) CamCal* CamCalConst;
+__device__ __forceinline__ CamCal cam_of(const DevCfg& cfg, const CamCal* __restrict__ cal, int z) {
+    const CamCalConst p = cal ? (CamCalConst)cal + z : (CamCalConst)&cfg.cam;
+    CamCal c;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { c.Ric[i] = p->Ric[i]; c.Rci[i] = p->Rci[i]; }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { c.tic[i] = p->tic[i]; c.tci[i] = p->tci[i]; }
+    c.fx = p->fx; c.fy = p->fy; c.cx = p->cx; c.cy = p->cy;
+    c.k1 = p->k1; c.k2 = p->k2; c.p1 = p->p1; c.p2 = p->p2; c.k3 = p->k3;
+    c.fisheye = p->fisheye;
+    return c;
+}
 // strides (bytes) of the per-instance inputs of a batched call: IMU samples and the Tracker -> Updater hand-over
 struct BatchIn { size_t imu, n_feat, types, len, meas; };
 

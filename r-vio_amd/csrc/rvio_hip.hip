@@ -172,6 +172,11 @@ struct rvio_hip {
     int pix_fmt = RVIO_PIX_MONO8, pix_ch = 1;   // pix_ch: BYTES per pixel as staged (samples per pixel x bytes per sample)
     uint8_t* d_gray[4] = {nullptr, nullptr, nullptr, nullptr};
     int gray_slot = 0;
+    // per-instance calibration (rvio_hip_set_calibration*): `cals` is what the getter returns, one entry per instance, the config's until a setter
+    // changes it; `cal` is the device table the calibrated kernels index by instance, allocated by the FIRST setter, outside the slab — a
+    // handle that never calls one passes nullptr and its kernels read DevCfg::cam from their arguments, as before the table existed
+    std::vector<rvio_calibration> cals;
+    CamCal* cal = nullptr;
     size_t img_cap = 0;              // bytes of one staged image the host-side staging (d_img, hb_img[]) holds: W * H, grows with the channel count
 };
 
@@ -276,13 +281,17 @@ void rvio_config_euroc(rvio_config* c) {
     c->ini_thr_angle = 0.005; c->ini_thr_displ = 0.01; c->ini_enable_alignment = 1;
 }
 
-static void fill_devcfg(const rvio_config* c, DevCfg* d) {
+void rvio_calibration_from_config(const rvio_config* c, rvio_calibration* k) {
+    if (!c || !k) return;
+    std::memset(k, 0, sizeof *k);
+    k->fx = c->fx; k->fy = c->fy; k->cx = c->cx; k->cy = c->cy;
+    k->k1 = c->k1; k->k2 = c->k2; k->p1 = c->p1; k->p2 = c->p2; k->k3 = c->k3;
+    k->fisheye = c->fisheye;
+    std::memcpy(k->T_bc, c->T_bc, sizeof k->T_bc);
+}
+// the device form of one calibration: the ONE place it is computed (the config's at create, a setter's later: the same bits either way)
+static void fill_camcal(const rvio_calibration* c, CamCal* d) {
     std::memset(d, 0, sizeof *d);
-    d->gravity = c->gravity; d->small_angle = c->small_angle;
-    d->sg2 = c->sigma_g * c->sigma_g; d->swg2 = c->sigma_wg * c->sigma_wg;
-    d->sa2 = c->sigma_a * c->sigma_a; d->swa2 = c->sigma_wa * c->sigma_wa;
-    d->sigma_im = (double)std::max(c->sigma_px, c->sigma_py);   // float max, widened (Updater.cc:42-44)
-    d->inlier_thr = c->inlier_thr;
     for (int i = 0; i < 3; ++i) {
         for (int j = 0; j < 3; ++j) { d->Ric[3 * i + j] = c->T_bc[4 * i + j]; d->Rci[3 * j + i] = c->T_bc[4 * i + j]; }
         d->tic[i] = c->T_bc[4 * i + 3];
@@ -290,6 +299,17 @@ static void fill_devcfg(const rvio_config* c, DevCfg* d) {
     for (int i = 0; i < 3; ++i) d->tci[i] = -(d->Rci[3 * i] * d->tic[0] + d->Rci[3 * i + 1] * d->tic[1] + d->Rci[3 * i + 2] * d->tic[2]);
     d->fx = c->fx; d->fy = c->fy; d->cx = c->cx; d->cy = c->cy;
     d->k1 = c->k1; d->k2 = c->k2; d->p1 = c->p1; d->p2 = c->p2; d->k3 = c->k3;
+    d->fisheye = c->fisheye ? 1 : 0;
+}
+
+static void fill_devcfg(const rvio_config* c, DevCfg* d) {
+    std::memset(d, 0, sizeof *d);
+    d->gravity = c->gravity; d->small_angle = c->small_angle;
+    d->sg2 = c->sigma_g * c->sigma_g; d->swg2 = c->sigma_wg * c->sigma_wg;
+    d->sa2 = c->sigma_a * c->sigma_a; d->swa2 = c->sigma_wa * c->sigma_wa;
+    d->sigma_im = (double)std::max(c->sigma_px, c->sigma_py);   // float max, widened (Updater.cc:42-44)
+    d->inlier_thr = c->inlier_thr;
+    { rvio_calibration k; rvio_calibration_from_config(c, &k); fill_camcal(&k, &d->cam); }
     d->W = c->width; d->H = c->height;
     d->F = c->n_features; d->Fu = (int)std::ceil(.5 * c->n_features);
     d->max_len = c->max_track_len; d->min_len = c->min_track_len;
@@ -306,7 +326,6 @@ static void fill_devcfg(const rvio_config* c, DevCfg* d) {
     d->off_y = (float)(int)(.5 * (c->height - d->grid_rows * c->block_y));
     d->max_per_block = (d->grid_cols * d->grid_rows > 0) ? (float)(int)((float)c->n_features / (d->grid_cols * d->grid_rows)) : 0.f;
     d->use_sampson = c->use_sampson;
-    d->fisheye = c->fisheye ? 1 : 0;
     // buildOpticalFlowPyramid: stop when a level is not larger than the window
     int w = c->width, hgt = c->height, lv = 1;
     for (int l = 1; l <= 3; ++l) { w = (w + 1) / 2; hgt = (hgt + 1) / 2; if (w <= 15 || hgt <= 15) break; lv++; }
@@ -494,6 +513,7 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
     h->front_end = front_end; h->det_in_slab = front_end && batch > 1;
     h->wide_px = batch >= 8;   // (tests switch it through rvio_hip_debug_kernel_forms: the two forms must agree bit for bit)
     fill_devcfg(cfg, &h->dc);
+    { rvio_calibration k; rvio_calibration_from_config(cfg, &k); h->cals.assign((size_t)batch, k); }
     const DevCfg& d = h->dc;
     h->img_cap = (size_t)d.W * d.H;
     if (d.grid_cols * d.grid_rows < 1) { delete h; return RVIO_ERR_INVALID; }
@@ -687,10 +707,8 @@ int rvio_hip_get_state_at(rvio_hip* h, int instance, double* x, int* xdim, doubl
 }
 int rvio_hip_get_state(rvio_hip* h, double* x, int* xdim, double* P, int* d) { return rvio_hip_get_state_at(h, 0, x, xdim, P, d); }
 
-// System::initialize (System.cc:115-170): runs once, on the host; result uploaded.
-int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n_imu) {
-    if (!h || !w || !a) return RVIO_ERR_INVALID;
-    const rvio_config& c = h->cfg;
+// System::initialize (System.cc:115-170) on the host: the gravity-aligned x(26) and the diagonal P(24 x 24) of one filter
+static void initial_state(const rvio_config& c, const double w[3], const double a[3], int n_imu, double x[26], double P[576]) {
     double an = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
     double g[3] = {a[0] / an, a[1] / an, a[2] / an};
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
@@ -714,7 +732,7 @@ int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n
     double qn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     for (int i = 0; i < 4; ++i) q[i] /= qn;
     if (q[3] < 0) for (int i = 0; i < 4; ++i) q[i] = -q[i];
-    double x[26] = {0}; double P[576] = {0};
+    std::memset(x, 0, sizeof(double) * 26); std::memset(P, 0, sizeof(double) * 576);
     for (int i = 0; i < 4; ++i) x[i] = q[i];
     for (int i = 0; i < 3; ++i) x[7 + i] = g[i];
     if (n_imu > 1) for (int i = 0; i < 3; ++i) { x[20 + i] = w[i]; x[23 + i] = a[i] - c.gravity * g[i]; }
@@ -724,6 +742,12 @@ int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n
     for (int i = 6; i < 9; ++i) D(i, n_imu * dt * std::pow(c.sigma_a, 2));
     for (int i = 18; i < 21; ++i) D(i, n_imu * dt * std::pow(c.sigma_wg, 2));
     for (int i = 21; i < 24; ++i) D(i, n_imu * dt * std::pow(c.sigma_wa, 2));
+}
+// ... runs once; result uploaded to every instance, and the handle starts over (frame count, tracker, cloud, odometry ring).  Calibrations stay.
+int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n_imu) {
+    if (!h || !w || !a) return RVIO_ERR_INVALID;
+    double x[26], P[576];
+    initial_state(h->cfg, w, a, n_imu, x, P);
     h->img_count = 0;
     h->lm_frame = -1;   // no cloud since initialisation (the enable flag stays)
     h->odom_seq = 0;    // ... and no odometry record: seq restarts at 1 (the getters read nothing beyond odom_seq)
@@ -753,6 +777,57 @@ int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n
         h->first_cleared = false;
     }
     return rvio_hip_set_state(h, x, 26, P, 24);
+}
+// The same state for ONE instance (each robot of a fleet has its own gravity direction and biases), stored as rvio_hip_set_state_at stores it:
+// none of the handle-wide resets above, so it belongs in front of the first frame — the window must be empty
+int rvio_hip_initialize_at(rvio_hip* h, int instance, const double w[3], const double a[3], int n_imu) {
+    if (!h || !w || !a || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
+    if (h->n_clones_host != 0) { h->err = "rvio_hip_initialize_at needs an empty window (call it before the first frame)"; return RVIO_ERR_STATE; }
+    double x[26], P[576];
+    initial_state(h->cfg, w, a, n_imu, x, P);
+    return set_state_range(h, instance, instance + 1, x, 26, P, 24);
+}
+
+// ------------------------------------------------------------------ per-instance calibration
+static bool calibration_ok(const rvio_calibration* c) {
+    const float f[9] = {c->fx, c->fy, c->cx, c->cy, c->k1, c->k2, c->p1, c->p2, c->k3};
+    for (float v : f) if (!std::isfinite(v)) return false;
+    for (double v : c->T_bc) if (!std::isfinite(v)) return false;
+    return c->fx != 0.f && c->fy != 0.f;
+}
+// entries [lo, hi) become src[0 .. hi - lo): drain the handle (like rvio_hip_set_image_format: nothing in flight reads the table), allocate the
+// table on first use — every instance starts from the config's calibration — and upload what changed
+static int set_calibration_range(rvio_hip* h, int lo, int hi, const rvio_calibration* src) {
+    for (int i = lo; i < hi; ++i)
+        if (!calibration_ok(src + (i - lo))) { h->err = "calibration of instance " + std::to_string(i) + ": a non-finite member, or fx / fy = 0"; return RVIO_ERR_INVALID; }
+    { const int rc = drain_all(h); if (rc != RVIO_OK) return rc; }
+    const bool fresh = !h->cal;
+    if (fresh) {
+        CamCal* p = nullptr;
+        HIPCHK(h, hipMalloc((void**)&p, sizeof(CamCal) * (size_t)h->batch));
+        h->allocs.push_back(p);
+        h->cal = p;
+    }
+    for (int i = lo; i < hi; ++i) h->cals[(size_t)i] = src[i - lo];
+    const int first = fresh ? 0 : lo, last = fresh ? h->batch : hi;
+    std::vector<CamCal> dev((size_t)(last - first));
+    for (int i = first; i < last; ++i) fill_camcal(&h->cals[(size_t)i], &dev[(size_t)(i - first)]);
+    HIPCHK(h, hipMemcpyAsync(h->cal + first, dev.data(), sizeof(CamCal) * dev.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // (`dev` is a stack-lifetime staging buffer)
+    return RVIO_OK;
+}
+int rvio_hip_set_calibration_at(rvio_hip* h, int instance, const rvio_calibration* c) {
+    if (!h || !c || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
+    return set_calibration_range(h, instance, instance + 1, c);
+}
+int rvio_hip_set_calibrations(rvio_hip* h, const rvio_calibration* all) {
+    if (!h || !all) return RVIO_ERR_INVALID;
+    return set_calibration_range(h, 0, h->batch, all);
+}
+int rvio_hip_get_calibration_at(rvio_hip* h, int instance, rvio_calibration* c) {
+    if (!h || !c || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
+    *c = h->cals[(size_t)instance];
+    return RVIO_OK;
 }
 
 // ------------------------------------------------------------------ P1
@@ -840,11 +915,11 @@ static void launch_feat_build(rvio_hip* h, int n, int rank, int world) {
     if (h->batch == 1)
         hipLaunchKernelGGL(feat_build_kernel<16>, g, b, h->plan.feat_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
                            h->t.n_feat, h->t.types, h->t.len, h->t.meas, rank, world, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv,
-                           h->tm_global, h->slab_bytes, h->bin, h->meta, (const double*)nullptr, (const int*)nullptr, h->lit_rows);
+                           h->tm_global, h->slab_bytes, h->bin, h->meta, (const double*)nullptr, (const int*)nullptr, h->lit_rows, (const CamCal*)h->cal);
     else
         hipLaunchKernelGGL(feat_build_kernel<4>, g, b, h->plan.feat_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
                            h->t.n_feat, h->t.types, h->t.len, h->t.meas, rank, world, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv,
-                           h->tm_global, h->slab_bytes, h->bin, h->meta, (const double*)h->gpose, (const int*)h->gvalid, h->lit_rows);
+                           h->tm_global, h->slab_bytes, h->bin, h->meta, (const double*)h->gpose, (const int*)h->gvalid, h->lit_rows, (const CamCal*)h->cal);
 }
 // propagate + U1..U5 in one launch (independent: see feat_prop_kernel); single instance (sharded or not: every rank propagates, builds its features)
 static void launch_feat_prop(rvio_hip* h, int n, const rvio_imu* d_imu, int m, int rank, int world) {
@@ -853,7 +928,7 @@ static void launch_feat_prop(rvio_hip* h, int n, const rvio_imu* d_imu, int m, i
     const bool chol = forms_at(h, n).chol == LPC_ROLE;
     hipLaunchKernelGGL(feat_prop_kernel, dim3(d.Fu + 1 + (chol ? 1 : 0)), dim3(256), h->plan.fprop_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
                        h->t.n_feat, h->t.types, h->t.len, h->t.meas, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv, h->tm_global, h->bin,
-                       h->meta, d_imu, m, chol ? h->S9scr : (double*)nullptr, h->plan.solve9_nt, rank, world, h->lit_rows);
+                       h->meta, d_imu, m, chol ? h->S9scr : (double*)nullptr, h->plan.solve9_nt, rank, world, h->lit_rows, (const CamCal*)h->cal);
     h->chol_ready = chol;
 }
 // reduction of the per-feature shares into [S2 | S1]; gram_finish: the last workgroup turns the block into [A|b] in place (rank truncation included), as the
@@ -885,7 +960,7 @@ static int update_local_dev(rvio_hip* h, int rank, int world, bool combine) {
     } else {
         if (h->gpose)   // U1 + U2 four features per wave, ahead of the per-feature kernel (which then only fetches the pose chain and the triple)
             hipLaunchKernelGGL(geom4_kernel, dim3((d.Fu + 3) / 4, 1, B), dim3(64), 0, h->stream, d, n, h->x[h->cur], h->t.n_feat, h->t.types, h->t.len, h->t.meas,
-                               h->gpose, h->pfinv, h->gvalid, h->slab_bytes, h->bin);
+                               h->gpose, h->pfinv, h->gvalid, h->slab_bytes, h->bin, (const CamCal*)h->cal);
         launch_feat_build(h, n, rank, world);
     }
     // unsharded: the reduction finishes into [A|b]; sharded: the block is the payload
@@ -989,7 +1064,7 @@ static void launch_landmarks(rvio_hip* h, int n, const LmOut& out) {
     const int T = std::min(LM_MAX_T, 64 * ((h->dc.Fu + 63) / 64));
     hipLaunchKernelGGL(landmark_kernel, dim3(1, 1, h->batch), dim3(T), 0, h->stream, h->dc, n, (const double*)h->x[h->cur ^ 1], (const double*)h->x[h->cur],
                        (const int*)h->t.n_feat, (const unsigned char*)h->t.types, (const int*)h->t.len, (const int*)h->acc, (const double*)h->pfinv,
-                       h->slab_bytes, h->bin, out);
+                       h->slab_bytes, h->bin, out, (const CamCal*)h->cal);
 }
 // grid / workgroup of a front-end launch as front_forms() (launch_plan.h) fixed them
 static dim3 lp_grid(const LpLaunch& l) { return dim3((unsigned)l.gx, (unsigned)l.gy, (unsigned)l.gz); }
@@ -1574,16 +1649,16 @@ static int post_klt_dev(rvio_hip* h, const FrontForms& f, const rvio_imu* d_imu,
     *out = BookOut{};
     switch (f.book_form) {
     case LPB_PLAIN:
-        hipLaunchKernelGGL(ransac_kernel, lp_grid(lr), lp_block(lr), lr.lds, side, h->dc, h->t.n_pts, h->t.tracked, h->t.un1, h->t.un2, h->t.status, d_imu, m, h->rng, h->d_info, bs, h->imu_bs);
+        hipLaunchKernelGGL(ransac_kernel, lp_grid(lr), lp_block(lr), lr.lds, side, h->dc, h->t.n_pts, h->t.tracked, h->t.un1, h->t.un2, h->t.status, d_imu, m, h->rng, h->d_info, bs, h->imu_bs, (const CamCal*)h->cal);
         hipLaunchKernelGGL(bookkeep_a_kernel, lp_grid(la), lp_block(la), 0, base, h->dc, h->t, (size_t)0, no_counter, 0ull, h->meta, (unsigned long long*)nullptr);
-        hipLaunchKernelGGL(bookkeep_b_kernel, lp_grid(lb), lp_block(lb), lb.lds, base, h->dc, h->t, d_cand, n_cand, (const int*)nullptr, (size_t)0, no_counter, 0ull, h->meta);
+        hipLaunchKernelGGL(bookkeep_b_kernel, lp_grid(lb), lp_block(lb), lb.lds, base, h->dc, h->t, d_cand, n_cand, (const int*)nullptr, (size_t)0, no_counter, 0ull, h->meta, (const CamCal*)h->cal);
         break;
     case LPB_JOIN:   // join the side stream (long finished when the detector is)
-        hipLaunchKernelGGL(ransac_kernel, lp_grid(lr), lp_block(lr), lr.lds, side, h->dc, h->t.n_pts, h->t.tracked, h->t.un1, h->t.un2, h->t.status, d_imu, m, h->rng, h->d_info, bs, h->imu_bs);
+        hipLaunchKernelGGL(ransac_kernel, lp_grid(lr), lp_block(lr), lr.lds, side, h->dc, h->t.n_pts, h->t.tracked, h->t.un1, h->t.un2, h->t.status, d_imu, m, h->rng, h->d_info, bs, h->imu_bs, (const CamCal*)h->cal);
         HIPCHK(h, hipEventRecord(h->evD1, side));
         HIPCHK(h, hipStreamWaitEvent(base, h->evD1, 0));
         hipLaunchKernelGGL(bookkeep_a_kernel, lp_grid(la), lp_block(la), 0, tail, h->dc, h->t, bs, no_counter, 0ull, h->meta, (unsigned long long*)nullptr);
-        hipLaunchKernelGGL(bookkeep_b_kernel, lp_grid(lb), lp_block(lb), lb.lds, tail, h->dc, h->t, xy, 0, nout, bs, no_counter, 0ull, h->meta);
+        hipLaunchKernelGGL(bookkeep_b_kernel, lp_grid(lb), lp_block(lb), lb.lds, tail, h->dc, h->t, xy, 0, nout, bs, no_counter, 0ull, h->meta, (const CamCal*)h->cal);
         break;
     case LPB_FUSED:
     case LPB_PAIR: {   // book-keeping on the side stream, behind RANSAC: the hand-over half once the filter that read the table last has let go of it, the refill half once the corners are there
@@ -1595,10 +1670,10 @@ static int post_klt_dev(rvio_hip* h, const FrontForms& f, const rvio_imu* d_imu,
         if (f.book_form == LPB_FUSED) {
             out->gate = true; out->gate_target = h->stage_tgt.handover;
             hipLaunchKernelGGL(ransac_book_kernel, lp_grid(lr), lp_block(lr), lr.lds, tail, h->dc, h->t, d_imu, m, h->rng, bs, h->imu_bs,
-                               done, done_target, h->meta, hand, xy, nout, &h->stage_sync->corners[f.ic], h->stage_tgt.corners[f.ic]);
+                               done, done_target, h->meta, hand, xy, nout, &h->stage_sync->corners[f.ic], h->stage_tgt.corners[f.ic], (const CamCal*)h->cal);
             break;
         }
-        hipLaunchKernelGGL(ransac_book_a_kernel, lp_grid(lr), lp_block(lr), lr.lds, tail, h->dc, h->t, d_imu, m, h->rng, bs, h->imu_bs, done, done_target, h->meta, hand);
+        hipLaunchKernelGGL(ransac_book_a_kernel, lp_grid(lr), lp_block(lr), lr.lds, tail, h->dc, h->t, d_imu, m, h->rng, bs, h->imu_bs, done, done_target, h->meta, hand, (const CamCal*)h->cal);
         // the Updater's input is complete: the filter of this frame waits for THIS — the gate kernel on the filter stream polls the
         // counter the launch above bumps, and the refill half below polls the detector's; or two stream-level events
         const unsigned long long* corners = nullptr; unsigned long long corners_target = 0;
@@ -1608,7 +1683,7 @@ static int post_klt_dev(rvio_hip* h, const FrontForms& f, const rvio_imu* d_imu,
             out->handover_evt = true;
             HIPCHK(h, hipStreamWaitEvent(side, h->evD1, 0));
         }
-        hipLaunchKernelGGL(bookkeep_b_kernel, lp_grid(lb), lp_block(lb), lb.lds, tail, h->dc, h->t, xy, 0, nout, bs, corners, corners_target, h->meta);
+        hipLaunchKernelGGL(bookkeep_b_kernel, lp_grid(lb), lp_block(lb), lb.lds, tail, h->dc, h->t, xy, 0, nout, bs, corners, corners_target, h->meta, (const CamCal*)h->cal);
         break;
     }
     }

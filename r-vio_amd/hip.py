@@ -27,6 +27,7 @@ SYMBOLS = [
     "rvio_hip_set_landmarks", "rvio_hip_get_landmarks", "rvio_hip_get_landmarks_at",
     "rvio_hip_set_image_format", "rvio_hip_get_image_format",
     "rvio_hip_set_odometry", "rvio_hip_get_odometry", "rvio_hip_get_odometry_all", "rvio_hip_get_pose_at",
+    "rvio_calibration_from_config", "rvio_hip_set_calibration_at", "rvio_hip_set_calibrations", "rvio_hip_get_calibration_at", "rvio_hip_initialize_at",
 ]
 
 _LIB = None
@@ -152,6 +153,30 @@ class RvioHip:
         w = np.ascontiguousarray(w, float)
         a = np.ascontiguousarray(a, float)
         self._ck(self.L.rvio_hip_initialize(self.h, _p(w, dp), _p(a, dp), int(n_imu)), "initialize")
+
+    def initialize_at(self, i, w, a, n_imu):
+        """System::initialize for instance i alone (its own gravity direction and biases); before the first frame, no handle-wide reset"""
+        w = np.ascontiguousarray(w, float)
+        a = np.ascontiguousarray(a, float)
+        self._ck(self.L.rvio_hip_initialize_at(self.h, int(i), _p(w, dp), _p(a, dp), int(n_imu)), "initialize_at")
+
+    # ---- per-instance calibration (intrinsics, distortion model, camera-IMU extrinsic)
+    def set_calibration_at(self, i, cal):
+        """instance i computes with abi.rvio_calibration `cal` from the next call on (drains the handle; call it before the first frame)"""
+        self._ck(self.L.rvio_hip_set_calibration_at(self.h, int(i), C.byref(cal)), "set_calibration_at")
+
+    def set_calibrations(self, cals):
+        """one abi.rvio_calibration per instance, uploaded in one copy"""
+        cals = list(cals)
+        if len(cals) != self.batch:
+            raise RvioHipError("set_calibrations: %d calibrations for %d instances" % (len(cals), self.batch))
+        arr = (abi.rvio_calibration * self.batch)(*cals)
+        self._ck(self.L.rvio_hip_set_calibrations(self.h, arr), "set_calibrations")
+
+    def get_calibration_at(self, i):
+        cal = abi.rvio_calibration()
+        self._ck(self.L.rvio_hip_get_calibration_at(self.h, int(i), C.byref(cal)), "get_calibration_at")
+        return cal
 
     # ---- stages
     def propagate(self, imu):
