@@ -2020,13 +2020,16 @@ __global__ __launch_bounds__(256) void final_lds_kernel(DevCfg cfg, int n, const
 //      X(I, J) = (P(I, J) - G_I Pc_J^T) - P1c_I G_J^T + s2 G_I U_J^T,        P+(I, J) = .5 (X(I, J) + X(J, I)^T)
 // exactly as the two kernels do (same operand order in every product, the same rounded intermediate P1 tile), so the result is theirs bit for
 // bit.  The strips are recomputed by every pair that touches them (~3.5x the products of the two-kernel form, spread over 21 CUs instead of 6).
+// Eight waves (512 threads; one workgroup per CU by its 150 KB of LDS, so the second wave per SIMD costs nothing): a strip round is one tile per wave, the
+// closing stage one product per wave, the load batch 28 instead of 53 loads per thread.  The dx roles ride at 512 threads unchanged (s9_dx_role strides by
+// blockDim.x; ten column groups of 24 threads).  The figures below are those of the four-wave form (profiles/solve_joseph_reschedule.md has both).
 // Measured (tools/solve_probe.py, full-load update at cfg B): 16.8 us against 9.2 + 8.9 us for the two launches — the workgroup is bound by
 // its 480 FP64 MFMAs on four SIMDs (64 cycles each) plus the operand reads in front of every chain (loads 10.5 k cycles, the three strip
 // rounds ~7 k each, the closing stage 4.3 k) —, so what the fusion buys the pipelined frame is one launch boundary and one launch less for
 // the host: +1-2 % frames/s in same-box A/Bs (8.39 / 8.42 k against 8.32 / 8.30 k; a box whose host is the limit: 7.58 / 7.70 against 7.56 / 7.53).
 #define JL_LS 61
 #define JL_LDS_DOUBLES (3 * 60 * JL_LS + 8 * 16 * JL_LS + 16)
-__global__ __launch_bounds__(256) void joseph_lds_kernel(DevCfg cfg, int n, const double* __restrict__ P, const double* __restrict__ W, const double* __restrict__ Ab,
+__global__ __launch_bounds__(LP_JL_THREADS) void joseph_lds_kernel(DevCfg cfg, int n, const double* __restrict__ P, const double* __restrict__ W, const double* __restrict__ Ab,
                                                          double* __restrict__ Pout, FilterMeta* __restrict__ meta, const double* __restrict__ x, double* __restrict__ x_out,
                                                          const double* __restrict__ dx_scr, int n_pairs, int dx_nt) {
     // dx_scr != NULL (round 6): the workgroups behind the n_pairs tile pairs are the solve's dx / state-injection roles (solve9.hip s9_dx_role): dx = Pc y
@@ -2037,7 +2040,7 @@ __global__ __launch_bounds__(256) void joseph_lds_kernel(DevCfg cfg, int n, cons
         return;
     }
     extern __shared__ __align__(16) double jl[];
-    constexpr int LS = JL_LS;
+    constexpr int LS = JL_LS, NTH = LP_JL_THREADS;   // eight waves: one tile of a strip round each
     double* const Wl = jl;                         // W[k][j]      (c6 x c6)
     double* const Al = Wl + 60 * LS;               // A[k][j]
     double* const Ccl = Al + 60 * LS;              // Pcc[c][k] = P[24 + c][24 + k]
@@ -2078,76 +2081,72 @@ __global__ __launch_bounds__(256) void joseph_lds_kernel(DevCfg cfg, int n, cons
     // and are stored up to column 60), so the products add the same exact zeros the masks produced.  Columns 60..63 of a tile's B operand read past
     // the row (finite or not: a column of the product nobody stores; the A operand is always initialised).
     auto ldz = [](const double* __restrict__ p, size_t i, bool ok) { const double v = p[ok ? i : 0]; return ok ? v : 0.0; };
-    double vw[15], va[15], vc[15], vs[8];
+    double vw[8], va[8], vc[8], vs[4];
 #pragma unroll
-    for (int u = 0; u < 15; ++u) {
-        const int e = tid + u * 256, k = e / 60, j = e - k * 60;            // 3600 = 60 x 60 elements
+    for (int u = 0; u < 8; ++u) {
+        const int e = tid + u * NTH, k = e / 60, j = e - k * 60;            // 3600 = 60 x 60 elements
         vw[u] = ldz(W, (size_t)k * ldh + j, e < 3600 && k < c6 && j < c6);
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int e = tid + u * 256, sidx = e / 960, ee = e - sidx * 960, k = ee >> 4, rr = ee & 15;     // 2 strips x 60 columns x 16 rows
+    for (int u = 0; u < 4; ++u) {
+        const int e = tid + u * NTH, sidx = e / 960, ee = e - sidx * 960, k = ee >> 4, rr = ee & 15;     // 2 strips x 60 columns x 16 rows
         const int row = r0of(sidx & 1) + rr;
         vs[u] = ldz(P, (size_t)row + (size_t)(24 + k) * ld, e < 1920 && k < c6 && row < d);
     }
 #pragma unroll
-    for (int u = 0; u < 15; ++u) {
-        const int e = tid + u * 256, k = e / 60, j = e - k * 60;
+    for (int u = 0; u < 8; ++u) {
+        const int e = tid + u * NTH, k = e / 60, j = e - k * 60;
         va[u] = ldz(Ab, (size_t)k * ldh + j, e < 3600 && k < c6 && j < c6);
     }
 #pragma unroll
-    for (int u = 0; u < 15; ++u) {
-        const int e = tid + u * 256, k = e / 60, j = e - k * 60;
+    for (int u = 0; u < 8; ++u) {
+        const int e = tid + u * NTH, k = e / 60, j = e - k * 60;
         vc[u] = ldz(P, (size_t)(24 + j) + (size_t)(24 + k) * ld, e < 3600 && k < c6 && j < c6);      // element (row c = j, k) of Pcc read down column k: consecutive threads, consecutive rows
     }
-    for (int e = tid; e < 6 * SS; e += 256) Us[e] = 0.0;     // U, G, P1c strips (contiguous): zero beyond the columns the rounds store
+    for (int e = tid; e < 6 * SS; e += NTH) Us[e] = 0.0;     // U, G, P1c strips (contiguous): zero beyond the columns the rounds store
 #pragma unroll
-    for (int u = 0; u < 15; ++u) {
-        const int e = tid + u * 256, k = e / 60, j = e - k * 60;
+    for (int u = 0; u < 8; ++u) {
+        const int e = tid + u * NTH, k = e / 60, j = e - k * 60;
         if (e < 3600) Wl[k * LS + j] = vw[u];
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int e = tid + u * 256, sidx = e / 960, ee = e - sidx * 960, k = ee >> 4, rr = ee & 15;
+    for (int u = 0; u < 4; ++u) {
+        const int e = tid + u * NTH, sidx = e / 960, ee = e - sidx * 960, k = ee >> 4, rr = ee & 15;
         if (e < 1920) PcS[(sidx & 1) * SS + rr * LS + k] = vs[u];
     }
     __syncthreads();
     DBG_T(21);
     const int ntj = (c6 + 15) / 16;
-    // strip products: out[s][row][c] = sum_k X[s][row][k] * Y(k, c) for the 2 strips x ntj column tiles.  A wave takes tiles `wave` and `wave + 4`
-    // TOGETHER: all operands of both in flight, then the two accumulation chains interleaved (a lone chain of dependent FP64 MFMAs leaves the
-    // matrix pipe idle between issues; the pipe of one SIMD — 64 cycles per 16x16x4 — is what bounds this kernel).  Yt: Y(k, c) = Ym[c * LS + k]
+    // strip products: out[s][row][c] = sum_k X[s][row][k] * Y(k, c) for the 2 strips x ntj column tiles (at most eight): ONE tile per wave, two waves to a
+    // SIMD.  (With four waves a wave took tiles `wave` and `wave + 4` together — 60 operand reads in front of two interleaved chains of fifteen MFMAs; a
+    // round was paced by those reads and by issue, 3.3-5.8 k cycles against 1.9 k of matrix-pipe time.  Now each chain has half the reads in front of it
+    // and the SIMD's second wave fills the pipe between the issues of the first.  A tile's chain is the same fifteen MFMAs in the same order.)
+    // Yt: Y(k, c) = Ym[c * LS + k]
     auto strips = [&](const double* X, const double* Ym, bool Yt, double* out, const double* sub) {
-        const int t0 = wave, t1 = wave + 4, ntile = 2 * ntj;
-        const bool v0 = t0 < ntile, v1 = t1 < ntile;      // (a tile past the last one: computed on clamped operands, not stored)
-        const int s0 = min(t0 / ntj, 1), c0 = (t0 % ntj) * 16 + li, s1 = min(t1 / ntj, 1), c1 = (t1 % ntj) * 16 + li;
-        double a0[15], b0[15], a1[15], b1[15];     // 6n <= 60: fifteen k-blocks (a sixteenth would add zeros)
+        const int t0 = wave, ntile = 2 * ntj;
+        const bool v0 = t0 < ntile;                       // (a tile past the last one: computed on clamped operands, not stored)
+        const int s0 = min(t0 / ntj, 1), c0 = (t0 % ntj) * 16 + li;
+        double a0[15], b0[15];                     // 6n <= 60: fifteen k-blocks (a sixteenth would add zeros)
 #pragma unroll
         for (int u = 0; u < 15; ++u) {
             const int k = 4 * u + lk;
             a0[u] = X[s0 * SS + li * LS + k];
             b0[u] = Yt ? Ym[c0 * LS + k] : Ym[k * LS + c0];
-            a1[u] = X[s1 * SS + li * LS + k];
-            b1[u] = Yt ? Ym[c1 * LS + k] : Ym[k * LS + c1];
         }
-        d4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
+        d4 acc0 = {0, 0, 0, 0};
 #pragma unroll
-        for (int u = 0; u < 15; ++u) {
-            acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[u], b0[u], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[u], b1[u], acc1, 0, 0, 0);
-        }
-        const bool st0 = v0 && c0 < 60, st1 = v1 && c1 < 60;
+        for (int u = 0; u < 15; ++u) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[u], b0[u], acc0, 0, 0, 0);
+        const bool st0 = v0 && c0 < 60;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int row = lk + 4 * q;
             if (st0) out[s0 * SS + row * LS + c0] = sub ? (sub[s0 * SS + row * LS + min(c0, 59)] - acc0[q]) : acc0[q];
-            if (st1) out[s1 * SS + row * LS + c1] = sub ? (sub[s1 * SS + row * LS + min(c1, 59)] - acc1[q]) : acc1[q];
         }
     };
     strips(PcS, Wl, false, Us, nullptr);             // U = Pc W
 #pragma unroll
-    for (int u = 0; u < 15; ++u) {
-        const int e = tid + u * 256, k = e / 60, j = e - k * 60;
+    for (int u = 0; u < 8; ++u) {
+        const int e = tid + u * NTH, k = e / 60, j = e - k * 60;
         if (e < 3600) { Al[k * LS + j] = va[u]; Ccl[j * LS + k] = vc[u]; }
     }
     __syncthreads();
@@ -2159,7 +2158,7 @@ __global__ __launch_bounds__(256) void joseph_lds_kernel(DevCfg cfg, int n, cons
     __syncthreads();
     DBG_T(24);
     // The closing stage: six 16 x 16 x 60 products — for X(I, J): a = G_I Pc_J^T, b = P1c_I G_J^T, c = G_I U_J^T; for X(J, I) the same with
-    // the strips exchanged — spread over the four waves (products w and w + 4), parked in LDS (W's buffer: W is dead), combined by wave 0 in
+    // the strips exchanged — one per wave (waves 0..5), parked in LDS (W's buffer: W is dead), combined by wave 0 in
     // the two kernels' order:  x = ((p0 - a) - b) + s2 c,  P+(I, J) = .5 (x_IJ + x_JI^T).   I == J: three products, x_JI = x_IJ.
     double (*const xt)[16][17] = reinterpret_cast<double (*)[16][17]>(Wl);
     const int nprod = (I == J) ? 3 : 6;
@@ -2175,16 +2174,10 @@ __global__ __launch_bounds__(256) void joseph_lds_kernel(DevCfg cfg, int n, cons
         for (int u = 0; u < 15; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[u], b1[u], acc, 0, 0, 0);
         return acc;
     };
-    {
-        const bool two = wave + 4 < nprod;
-        d4 pa = {0, 0, 0, 0}, pb = {0, 0, 0, 0};
-        if (wave < nprod) pa = product(wave);
-        if (two) pb = product(wave + 4);
+    if (wave < nprod) {
+        const d4 pa = product(wave);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (wave < nprod) xt[wave][lk + 4 * q][li] = pa[q];
-            if (two) xt[wave + 4][lk + 4 * q][li] = pb[q];
-        }
+        for (int q = 0; q < 4; ++q) xt[wave][lk + 4 * q][li] = pa[q];
     }
     __syncthreads();
     DBG_T(25);

@@ -89,11 +89,17 @@ LP_HD inline size_t lit_diag_end(int ldh, bool stamps) {
 #define LP_S9CHOL4_BYTES 35976       // sizeof(S9CholLds<4, 4>)   (solve9.hip)
 #define LP_S9CHOL6_BYTES 44424       // sizeof(S9CholLds<6, 4>)
 #define LP_S9SMALL_BYTES 160328      // sizeof(S9SmallLds)
+// solve9_small_kernel's Q / R phase: the tile 4 ti + tj that wave w forms, nibble w.  Tile (ti, tj) is (4 - tj) + (4 - ti) tile products; the hardware deals
+// the waves of a workgroup to the four SIMDs round-robin (wave w on SIMD w & 3), so with the natural map w -> tile w the matrix pipes carry 26 / 22 / 18 / 14
+// of the 80 products.  This map gives each of them 20:  SIMD 0: tiles 0 3 12 15 (8 + 5 + 5 + 2), SIMD 1: 1 2 7 11 (7 + 6 + 4 + 3), SIMD 2: 4 8 13 14
+// (7 + 6 + 4 + 3), SIMD 3: 5 6 9 10 (6 + 5 + 5 + 4)   (tests/test_solve9_qr_map.py)
+#define LP_S9SMALL_QR_MAP 0xAEBF9D7C68235410ull
 #define LP_PROP3_BYTES 86432         // sizeof(Prop3Lds<16>)      (filter_kernels2.hip)
 #define LP_JB_TL_DOUBLES (12 * 16 * 17)                        // JB_TL_DOUBLES   (filter_kernels.hip)
 #define LP_UGL_BYTES ((2 * 64 * 65 + 88 * 65 + 2 * 16 * 65) * 8)   // UGL_LDS_DOUBLES
 #define LP_FNL_BYTES ((3 * 88 * 65 + 4 * 16 * 17) * 8)             // FNL_LDS_DOUBLES
 #define LP_JL_BYTES ((3 * 60 * 61 + 8 * 16 * 61 + 16) * 8)         // JL_LDS_DOUBLES
+#define LP_JL_THREADS 512                                          // joseph_lds_kernel's workgroup: eight waves, one tile of a strip round each
 #define LP_GEMM_T_LDS_BYTES (2 * 64 * 65 * 8)                      // gemm_T_lds_kernel's operands
 
 // ---------------------------------------------------------------- the kernels create_impl gives a dynamic-LDS limit

@@ -1038,7 +1038,7 @@ static void launch_ug_final(rvio_hip* h, const UpdateForms& f, int n, const doub
     const double *nod = nullptr, *yp = role_wgs ? (const double*)h->S9scr : nod;
     switch (f.joseph) {
     case LPJ_BATCH: hipLaunchKernelGGL(joseph_batch_kernel, dim3(1, 1, B), dim3(JB_THREADS), f.ug_lds.bytes, h->stream, d, n, Pc, h->W, Ab, Pn, bs); break;
-    case LPJ_LDS: hipLaunchKernelGGL(joseph_lds_kernel, dim3(f.grid[0] + role_wgs), dim3(256), f.ug_lds.bytes, h->stream, d, n, Pc, h->W, Ab, Pn, h->meta, (const double*)h->x[h->cur], h->x[h->cur ^ 1], yp, f.grid[0], h->plan.solve9_nt); break;
+    case LPJ_LDS: hipLaunchKernelGGL(joseph_lds_kernel, dim3(f.grid[0] + role_wgs), dim3(LP_JL_THREADS), f.ug_lds.bytes, h->stream, d, n, Pc, h->W, Ab, Pn, h->meta, (const double*)h->x[h->cur], h->x[h->cur ^ 1], yp, f.grid[0], h->plan.solve9_nt); break;
     case LPJ_LDS_PAIR:
         if (ug) hipLaunchKernelGGL(ug_lds_kernel, dim3(f.grid[0]), dim3(256), f.ug_lds.bytes, h->stream, d, n, Pc, h->W, Ab, h->U, h->G, h->Pt1);
         if (fin) hipLaunchKernelGGL(final_lds_kernel, dim3(f.grid[1]), dim3(256), f.fin_lds.bytes, h->stream, d, n, h->Pt1, h->G, h->U, Pn);

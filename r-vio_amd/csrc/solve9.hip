@@ -92,8 +92,10 @@ __device__ __forceinline__ s9_d4 s9_transpose_tb(const s9_d4& v, double* tb_, in
 // E ends as F = (chol m)^-1.  A pivot <= tol * ref[p] (ref: the ORIGINAL diagonal of the matrix the tile belongs to; nullptr: plain
 // positivity) is a zero direction: no elimination with it, row p of F is zero (the convention of a semi-definite Cholesky).
 // returns F and F^T; bad |= 1 when a pivot is not positive (or NaN) where it has to be.
-// Serial chain per block step: one LDS round trip (block rows of m and E out, 10 + 8 doubles back), four inverse square roots
-// (v_rsq_f64 + two Newton steps) with a handful of FMAs between them, two MFMAs.  Four block steps per tile.
+// Serial chain per block step: the ten entries of the pivot block by v_readlane (compile-time lanes of register b), four inverse square roots
+// (v_rsq_f64 + two Newton steps) with a handful of FMAs between them, two MFMAs; the LDS round trip of the block rows of m and E (8 doubles
+// back per lane) runs under the pivot chain instead of in front of it.  Four block steps per tile.  Shared by the Cholesky phase / role
+// (ref_ non-null) and by every form of the sweep (ref_ null).
 __device__ __forceinline__ double s9_rsqrt(double t) {
     double y = __builtin_amdgcn_rsq(t);
     const double h = 0.5 * t;
@@ -112,10 +114,13 @@ __device__ __forceinline__ void s9_factor(s9_d4 m, const double* ref_, double to
         s9_vlp rb = (s9_vlp)ws->rowb[b & 1];
         rb[lane] = m[b];                                // R(lk, li)  = m(4 b + lk, li)
         rb[64 + lane] = e[b];                           // Re(lk, li) = E(4 b + lk, li)
-        const double a00 = rb[0 * 16 + 4 * b + 0];
-        const double a10 = rb[1 * 16 + 4 * b + 0], a11 = rb[1 * 16 + 4 * b + 1];
-        const double a20 = rb[2 * 16 + 4 * b + 0], a21 = rb[2 * 16 + 4 * b + 1], a22 = rb[2 * 16 + 4 * b + 2];
-        const double a30 = rb[3 * 16 + 4 * b + 0], a31 = rb[3 * 16 + 4 * b + 1], a32 = rb[3 * 16 + 4 * b + 2], a33 = rb[3 * 16 + 4 * b + 3];
+        // the 4 x 4 pivot block a(i, j) = m(4 b + i, 4 b + j) sits in register b of lane 16 i + 4 b + j — a lane known at compile time: v_readlane, and
+        // the pivot chain below starts at once; the rows Rv / Ev come back from LDS under it (the same values as the round trip gave: the same bits)
+        auto piv = [&](int i, int j) { return readlane_f64(m[b], 16 * i + 4 * b + j); };
+        const double a00 = piv(0, 0);
+        const double a10 = piv(1, 0), a11 = piv(1, 1);
+        const double a20 = piv(2, 0), a21 = piv(2, 1), a22 = piv(2, 2);
+        const double a30 = piv(3, 0), a31 = piv(3, 1), a32 = piv(3, 2), a33 = piv(3, 3);
         double Rv[4], Ev[4];
 #pragma unroll
         for (int v = 0; v < 4; ++v) { Rv[v] = rb[v * 16 + li]; Ev[v] = rb[64 + v * 16 + li]; }
@@ -801,7 +806,10 @@ __device__ __forceinline__ void s9_dx_role(const DevCfg& cfg, FilterMeta* __rest
 // The pipelined frame's solve at the headline window (6n = 60).  The generic kernel above sends every phase's tiles through the L2 slab
 // (one L2 round trip per product step, ~1 k cycles, four or five steps per phase) and reads Pc for dx = Pc y from HBM at the very end; here
 //   * L and G come from the slab ONCE (written by the role workgroup of the per-feature launch) and every later tile lives in LDS,
-//   * 16 waves, one 16 x 16 tile each, no register blocking needed,
+//   * 16 waves, one 16 x 16 tile each, no register blocking needed; in the Q / R phase alone the tiles are dealt by LP_S9SMALL_QR_MAP (twenty
+//     tile products to each SIMD's matrix pipe instead of 26 / 22 / 18 / 14),
+//   * the sweep is two barrier intervals per step: the wave that owns the next diagonal tile factors it from its registers right behind its own
+//     update and publishes F / F^T while the rest of that row publishes the row panel (the diagonal tile never goes to LDS and back),
 //   * W^T = (I - L Mi (G A)) / s2 — the transposed Woodbury form: with R = G A beside Q = A L no tile is ever transposed
 //       Q = A L, R = G A;   M = s2 I + L^T Q;   Mi = M^-1 (sweep);   V = Mi R;   W^T = (I - L V) / s2,   y = W b
 //   * the IMU rows and the clone block of P (dx = Pc y) are fetched into registers at the start and parked in LDS once Q and R are dead.
@@ -873,16 +881,19 @@ __global__ __launch_bounds__(1024) void solve9_small_kernel(DevCfg cfg, FilterMe
     __syncthreads();
     DBG_T(32);
     // ---- Q = A L (Q(i, j) = sum_{k >= j} A(k, i)^T L(k, j)),  R = G A (R(i, j) = sum_{k >= i} L(k, i)^T A(k, j)); A leaves the Q region behind a barrier
+    // Tile (qi, qj) is (4 - qj) + (4 - qi) products: THIS phase deals the tiles to the waves by LP_S9SMALL_QR_MAP, twenty products to every SIMD's matrix
+    // pipe (wave w -> tile w gave 26 / 22 / 18 / 14: SIMD 0's pipe alone was most of the phase).  Each tile keeps its k order; every other phase keeps (ti, tj).
     {
+        const int qt = (int)((LP_S9SMALL_QR_MAP >> (4 * wv)) & 15), qi = qt >> 2, qj = qt & 3;
         s9_d4 q = s9_zero(), rr = s9_zero();
 #pragma unroll
         for (int k = 0; k < NT; ++k) {
-            if (k >= tj) q = s9_tn(s9_lds(sh.Q[k * NT + ti], lane), s9_lds(sh.L[k * NT + tj], lane), q);
-            if (k >= ti) rr = s9_tn(s9_lds(sh.L[k * NT + ti], lane), s9_lds(sh.Q[k * NT + tj], lane), rr);
+            if (k >= qj) q = s9_tn(s9_lds(sh.Q[k * NT + qi], lane), s9_lds(sh.L[k * NT + qj], lane), q);
+            if (k >= qi) rr = s9_tn(s9_lds(sh.L[k * NT + qi], lane), s9_lds(sh.Q[k * NT + qj], lane), rr);
         }
         __syncthreads();
-        s9_sts(sh.Q[wv], lane, q);
-        s9_sts(sh.R[wv], lane, rr);
+        s9_sts(sh.Q[qt], lane, q);
+        s9_sts(sh.R[qt], lane, rr);
     }
     __syncthreads();
     DBG_T(33);
@@ -897,25 +908,33 @@ __global__ __launch_bounds__(1024) void solve9_small_kernel(DevCfg cfg, FilterMe
     }
     DBG_T(34);
     // ---- the symmetric sweep (as in solve9_kernel); the tableau ends as -M^-1
+    // Two barrier intervals per step, the factor one step AHEAD of them.  The wave that owns the diagonal tile (k, k) holds it in registers when its
+    // update of step k - 1 ends (wave 0 holds M(0, 0)): it factors it right there, in the same interval, and publishes F / F^T itself, while the other
+    // waves of row k publish their tiles to the row panel.  (Until this change a step had three barriers: the whole row panel went to LDS, wave 0 loaded
+    // the diagonal tile back and factored it with fifteen waves waiting, and only then were the Z tiles formed.  The tile in the owner's registers is the
+    // tile that made that round trip: the same bits.)
+    //   interval A (this step's F and row panel are in LDS):  every wave fetches F; waves t = 0..3, t != k, form Z(t) = F rowp[t]   (Z(k) had no reader)
+    //   interval B:  every wave updates its tile from Z and F; then the owner of (k + 1, k + 1) factors, row k + 1 publishes        (top of the next pass)
+    // sh.F is read in interval A only and rewritten in interval B only; sh.Z the other way round; sh.ws has one user (the factoring wave) per interval.
     int bad = 0;
 #pragma unroll 1
     for (int k = 0; k < NT; ++k) {
         double (*rowp)[S9_TILE] = sh.rowp[k & 1];
-        if (ti == k) s9_sts(rowp[tj], lane, S);
-        __syncthreads();
-        s9_d4 F, Ft;
-        if (wv == 0) {
-            s9_factor(s9_lds(rowp[k], lane), nullptr, 0.0, &sh.ws, li, lk, F, Ft, bad);
-            s9_sts(sh.F[0], lane, F);
-            s9_sts(sh.F[1], lane, Ft);
+        if (ti == k) {
+            if (tj == k) {
+                s9_d4 F, Ft;
+                s9_factor(S, nullptr, 0.0, &sh.ws, li, lk, F, Ft, bad);
+                s9_sts(sh.F[0], lane, F);
+                s9_sts(sh.F[1], lane, Ft);
+            } else s9_sts(rowp[tj], lane, S);
         }
         __syncthreads();
-        // (round 6) Z(t) = Ft^T rowp[t], t = 0..3, formed ONCE by waves 0..3 (one per SIMD) and shared through LDS: every wave used to form its own Zr = Z(ti)
+        // (round 6) Z(t) = Ft^T rowp[t] formed ONCE by waves 0..3 (one per SIMD) and shared through LDS: every wave used to form its own Zr = Z(ti)
         // and Zc = Z(tj) — 32 tile products per step for 4 distinct results, and the FP64 matrix pipe of a SIMD (64 cycles per 16x16x4, four waves to a
-        // SIMD) was the step: 12 MFMAs x 4 waves = 3 k cycles.  Now 4 + 4 x 4 = 1.3 k and a barrier.  Same products on the same operands: same bits.
-        F = s9_lds(sh.F[0], lane);
-        if (wv < NT) {
-            Ft = s9_lds(sh.F[1], lane);
+        // SIMD) was the step: 12 MFMAs x 4 waves = 3 k cycles.  Now 3 + 4 x 4 = 1.2 k and a barrier.  Same products on the same operands: same bits.
+        const s9_d4 F = s9_lds(sh.F[0], lane);
+        if (wv < NT && wv != k) {
+            const s9_d4 Ft = s9_lds(sh.F[1], lane);
             s9_sts(sh.Z[wv], lane, s9_tn(Ft, s9_lds(rowp[wv], lane), s9_zero()));
         }
         __syncthreads();

@@ -45,7 +45,7 @@ stages = [0, 1, 2, 3, 5, 6] if fused else [0, 1, 2, 3, 4, 5, 6]
 if fused:
     names[3] = "joseph_lds"
 for a, b in zip(stages[:-1], stages[1:]):
-    print("%-12s -> %-12s %.1f us" % (names[a], names[b], np.mean(r[1:, b] - r[1:, a])))
+    print("%-12s -> %-12s %.1f us (frame to frame: std %.2f, median %.1f)" % (names[a], names[b], np.mean(r[1:, b] - r[1:, a]), np.std(r[1:, b] - r[1:, a]), np.median(r[1:, b] - r[1:, a])))
 print("solve start -> solve end (thread 0): %.1f us; solve end -> ug start: %.1f us" % (np.mean(r[1:, 7] - r[1:, 2]), np.mean(r[1:, 3] - r[1:, 7])))
 print("augcomp end -> next feat_prop: %.1f us" % np.mean(r[1:, 0] - r[:-1, 6]))
 out2 = (C.c_longlong * 512)()
