@@ -169,7 +169,9 @@ System::System(const Settings& s, int device) : s_(s) {
 }
 System::~System() {
     if (f_od_ && h_) (void)flush_odometry();
+    if (f_io_ && h_) (void)flush_imu_odometry();
     delete static_cast<std::ofstream*>(f_od_);
+    delete static_cast<std::ofstream*>(f_io_);
     delete static_cast<std::ofstream*>(f_pose_);
     delete static_cast<std::ofstream*>(f_time_);
     delete static_cast<std::ofstream*>(f_lm_);
@@ -249,6 +251,52 @@ int System::flush_odometry() {
         od_read_ = r.seq;
     }
     f.flush();
+    return 0;
+}
+
+bool System::record_imu_odometry_to(const std::string& path, int ring) {
+    if (!h_) return false;
+    if (ring < 1) { err_ = "the IMU-rate odometry ring holds at least one record"; return false; }
+    auto* f = new std::ofstream(path, std::ofstream::out);
+    if (!*f) { delete f; err_ = "cannot write " + path; return false; }
+    if (f_io_) (void)flush_imu_odometry();
+    if (rvio_hip_set_imu_odometry(h_, ring) != RVIO_OK) { delete f; err_ = rvio_hip_last_error(h_); return false; }
+    delete static_cast<std::ofstream*>(f_io_);
+    f_io_ = f;
+    io_ring_ = ring;
+    io_buf_.assign((size_t)ring, rvio_imu_pose{});
+    // (records written from here on are read from here on: the handle's seq restarts with rvio_hip_initialize, which MonoVIO issues before its
+    // first frame, and with a new ring; a ring that goes on holds its newest seq in its newest record)
+    int32_t n = 0;
+    io_seq_ = io_read_ = 0;
+    if (ready_ && rvio_hip_get_imu_odometry(h_, 0, 1, ring, io_buf_.data(), &n) == RVIO_OK && n > 0) io_seq_ = io_read_ = io_buf_[(size_t)n - 1].seq;
+    return true;
+}
+
+// behind a frame handed to the filter: its m samples are m records; the ring is read when half of it is outstanding
+int System::note_imu_odometry(int m) {
+    io_seq_ += m;
+    if (io_seq_ - io_read_ >= std::max(1, io_ring_ / 2)) return flush_imu_odometry();
+    return 0;
+}
+
+int System::flush_imu_odometry() {
+    if (!f_io_ || io_seq_ == io_read_) return 0;
+    int32_t n = 0;
+    if (rvio_hip_get_imu_odometry(h_, 0, io_read_ + 1, io_ring_, io_buf_.data(), &n) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+    auto& f = *static_cast<std::ofstream*>(f_io_);
+    for (int i = 0; i < n; ++i) f << format_imu_odometry(io_buf_[(size_t)i]);
+    f.flush();
+    // every outstanding sample must have come back: a ring smaller than the samples that arrive between two reads (a read follows the frame that
+    // makes ring / 2 of them outstanding, so a ring below about three frames' samples, or one long batch behind dropped images) has overwritten
+    // records before they were read.  The file would silently miss lines: that is an error, with the numbers that say how large the ring must be.
+    const long long want = io_seq_ - io_read_;
+    io_read_ = io_seq_;
+    if (n != want) {
+        err_ = "IMU-rate odometry: " + std::to_string(want - n) + " of " + std::to_string(want) + " records were overwritten before they were read (ring of " +
+               std::to_string(io_ring_) + " samples: use a larger --imu-odometry-ring)";
+        return -1;
+    }
     return 0;
 }
 
@@ -335,6 +383,7 @@ int System::MonoVIO(PoseLine* pose) {
         }
         if (f_lm_ && write_landmarks(image.t) < 0) return -1;
         if (f_od_ && note_odometry(image.t) < 0) return -1;
+        if (f_io_ && note_imu_odometry(m) < 0) return -1;
         return 1;
     }
     // INI.RecordOutputs: the same body stage by stage with the host waiting behind each, t1 / t2 / t3 taken where upstream takes them
@@ -358,6 +407,7 @@ int System::MonoVIO(PoseLine* pose) {
     ft << format_time_cost(n_img_, t2 - t1, t3 - t2); ft.flush();
     if (f_lm_ && write_landmarks(image.t) < 0) return -1;
     if (f_od_ && note_odometry(image.t) < 0) return -1;
+    if (f_io_ && note_imu_odometry(m) < 0) return -1;
     if (pose) *pose = pl;
     return 1;
 }
@@ -384,6 +434,19 @@ std::string format_odometry(double t, const rvio_odom& r) {
     for (double v : r.q) add(v);
     for (double v : r.v) add(v);
     for (double v : r.pose_cov) add(v);
+    out += "\n";
+    return out;
+}
+
+std::string format_imu_odometry(const rvio_imu_pose& r) {
+    char buf[64];
+    std::string out;
+    auto add = [&](double v) { std::snprintf(buf, sizeof buf, " %.19g", v); out += buf; };
+    std::snprintf(buf, sizeof buf, "%.19g", r.t);
+    out = buf;
+    for (double v : r.p) add(v);
+    for (double v : r.q) add(v);
+    for (double v : r.v) add(v);
     out += "\n";
     return out;
 }

@@ -107,6 +107,14 @@ public:
     // destructor): the pipelined frame is no longer drained once per image for its pose.  One line per frame, format_odometry.
     bool record_odometry_to(const std::string& path, int ring = 256);
     int flush_odometry();         // 0, or -1 on a library error (error())
+    // A dense trajectory: one pose per IMU sample (200 Hz against the 20 Hz of stamped_pose_ests.dat), the pose line MonoVIO would write if an
+    // image arrived right behind that sample and ran no update.  Enables the handle's IMU-rate ring (rvio_hip_set_imu_odometry, `ring` samples)
+    // and reads it with ONE rvio_hip_get_imu_odometry whenever ring / 2 samples are outstanding and once more at the end
+    // (flush_imu_odometry, also run by the destructor): no frame is drained for it.  One line per sample, format_imu_odometry.  A read that
+    // returns fewer records than are outstanding — the ring was too small for the samples between two reads and has overwritten some — is an
+    // error (MonoVIO / flush_imu_odometry return -1, error() names the counts): the file never misses lines silently.
+    bool record_imu_odometry_to(const std::string& path, int ring = 4096);
+    int flush_imu_odometry();     // 0, or -1 on a library error or on records lost to a ring too small (error())
     // the handle's sticky device-side flags (rvio_frame_info.reserved[0]: 1 singular pivot, 2 a track dropped, 4 a stage counter timed out,
     // 8 a non-positive gate pivot; 0 = none) — waits for everything in flight, so a replay reads it once at its end.  -1: the query failed.
     int device_flags();
@@ -139,6 +147,11 @@ private:
     std::vector<rvio_odom> od_buf_;
     int note_odometry(double t);
     long long last_seq();
+    void* f_io_ = nullptr;        // std::ofstream* of record_imu_odometry_to
+    int io_ring_ = 0;
+    long long io_seq_ = 0, io_read_ = 0;   // IMU samples handed to the filter since initialisation / up to which the ring has been read
+    std::vector<rvio_imu_pose> io_buf_;
+    int note_imu_odometry(int m);
 };
 
 // 8- or 16-bit PNG (non-interlaced; gray, RGB or RGBA: channels in file order = RGB) or binary PGM / PPM (P5 / P6; maxval 255: 8 bits, 256 ..
@@ -157,6 +170,8 @@ std::string format_pose(const PoseLine& p);               // one line of stamped
 std::string format_landmarks(double t, int frame, int n, const int32_t* feat, const double* p_world, const double* p_r);
 // one record of the odometry ring: t seq px py pz qx qy qz qw vx vy vz c00 ... c55 (pose_cov row by row), %.19g
 std::string format_odometry(double t, const rvio_odom& r);
+// one record of the IMU-rate ring: t px py pz qx qy qz qw vx vy vz, %.19g (setprecision(19), like stamped_pose_ests.dat)
+std::string format_imu_odometry(const rvio_imu_pose& r);
 std::string format_time_cost(int n_img, double track_ms, double filter_ms);   // one line of time_cost.dat (System.cc:376-378)
 
 }  // namespace rvio

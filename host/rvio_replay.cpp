@@ -4,6 +4,9 @@
 // of stamped_pose_ests.dat (System.cc:369-374).
 //
 //   rvio_replay <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--landmarks FILE] [--odometry FILE [--odometry-ring N]]
+//                                        [--imu-odometry FILE [--imu-odometry-ring N]]
+//                                        --imu-odometry: the pose and velocity behind every IMU sample the filter consumes, read in bulk from the handle's
+//                                        IMU-rate ring of N samples (default 4096; System::record_imu_odometry_to)
 //                                        --odometry: pose, velocity and pose covariance of every frame, read in bulk from the handle's ring of N
 //                                        records (default 256; System::record_odometry_to); without <poses_out.dat> no frame is drained for its pose
 //                                        --landmarks: Updater::update's landmark cloud behind every updating frame (System::record_landmarks_to)
@@ -94,6 +97,8 @@ struct PassOptions {
     const char* landmarks = nullptr; // System::record_landmarks_to
     const char* odometry = nullptr;  // System::record_odometry_to
     int odometry_ring = 256;
+    const char* imu_odometry = nullptr;  // System::record_imu_odometry_to
+    int imu_odometry_ring = 4096;
 };
 static bool dump_frame(System& sys, const rvio_config& c, FrameDump* d) {
     rvio_hip* h = sys.handle();
@@ -113,6 +118,7 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
     if (!sys.ok()) { *err = sys.error(); return 1; }
     if (o.landmarks && !sys.record_landmarks_to(o.landmarks)) { *err = sys.error(); return 1; }
     if (o.odometry && !sys.record_odometry_to(o.odometry, o.odometry_ring)) { *err = sys.error(); return 1; }
+    if (o.imu_odometry && !sys.record_imu_odometry_to(o.imu_odometry, o.imu_odometry_ring)) { *err = sys.error(); return 1; }
     size_t ii = 0;
     long n_images = 0, n_frames = 0;
     double t_filter = 0;
@@ -145,7 +151,7 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
             if (o.dump_at >= 0 && n_frames > o.dump_at) break;
         }
     }
-    if (sys.flush_odometry() < 0) { *err = sys.error(); return 1; }
+    if (sys.flush_odometry() < 0 || sys.flush_imu_odometry() < 0) { *err = sys.error(); return 1; }
     if (ms_per_call) *ms_per_call = n_images ? 1e3 * t_filter / n_images : 0.0;
     if (flags) *flags = sys.device_flags();
     return 0;
@@ -230,13 +236,14 @@ int main(int argc, char** argv) {
     }
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--record-dir DIR] [--record]\n"
-                             "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n", argv[0]);
+                             "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n", argv[0]);
         return 2;
     }
     const char* out_path = nullptr;
     int device = 0; long max_frames = -1, stall_seed = -1;
     const char* landmarks = nullptr;
     const char* odometry = nullptr; int odometry_ring = 256;
+    const char* imu_odometry = nullptr; int imu_odometry_ring = 4096;
     const char* record_dir = "."; bool force_record = false, sync_every = false, self = false; int noise_wgs = 0;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -249,6 +256,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--landmarks") && i + 1 < argc) landmarks = argv[++i];   // the landmark cloud of every update, one point per line
         else if (!std::strcmp(argv[i], "--odometry") && i + 1 < argc) odometry = argv[++i];     // one line per frame: pose, velocity, pose covariance (read in bulk from the ring)
         else if (!std::strcmp(argv[i], "--odometry-ring") && i + 1 < argc) odometry_ring = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--imu-odometry") && i + 1 < argc) imu_odometry = argv[++i];   // one line per IMU sample: pose and velocity (read in bulk from the IMU-rate ring)
+        else if (!std::strcmp(argv[i], "--imu-odometry-ring") && i + 1 < argc) imu_odometry_ring = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--selfcheck")) self = true;
         else out_path = argv[i];
     }
@@ -261,7 +270,7 @@ int main(int argc, char** argv) {
     if (self) return selfcheck(s, d, device, max_frames, stall_seed, noise_wgs);
     if (sync_every || stall_seed >= 0 || noise_wgs > 0) {   // the plain replay with one of the two A/B pacings
         std::vector<PoseLine> poses; double ms = 0; int flags = 0;
-        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring;
+        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring;
         if (run_pass(s, d, device, o, &poses, nullptr, &ms, &flags, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
         if (out_path) { std::ofstream out(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } for (const PoseLine& p : poses) out << format_pose(p); }
         std::fprintf(stderr, "rvio_replay: %zu filtered frames, %.3f ms per MonoVIO call, device flags %d\n", poses.size(), ms, flags);
@@ -272,6 +281,7 @@ int main(int argc, char** argv) {
     if (!sys.record_to(record_dir, force_record)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (landmarks && !sys.record_landmarks_to(landmarks)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (odometry && !sys.record_odometry_to(odometry, odometry_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
+    if (imu_odometry && !sys.record_imu_odometry_to(imu_odometry, imu_odometry_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     std::ofstream out;
     if (out_path) { out.open(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } }
 
@@ -295,7 +305,7 @@ int main(int argc, char** argv) {
         if (rc < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
         if (rc == 1) { ++n_frames; if (out.is_open()) out << format_pose(p); }
     }
-    if (sys.flush_odometry() < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
+    if (sys.flush_odometry() < 0 || sys.flush_imu_odometry() < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     std::fprintf(stderr, "rvio_replay: %ld images, %ld filtered frames, %.3f ms per MonoVIO call (host wall clock, pose read-back included)\n",
                  n_images, n_frames, n_images ? 1e3 * t_filter / n_images : 0.0);
     // anything only the device saw (0 in every test and bench run): said out loud, the poses above are suspect if it is not 0

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry) */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -391,6 +391,49 @@ int rvio_hip_get_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_
  * is copied).  Where all robots of a fleet are, per frame, without one state read-back per instance. */
 int rvio_hip_get_odometry_all(rvio_hip* h, rvio_odom* out /* batch records */, int64_t* seq);
 
+/* --- IMU-rate odometry ------------------------------------------------------- */
+/* A pose at every IMU sample.  PreIntegrator::propagate has (Rk, pk, vk) complete at the bottom of every iteration of its sample loop
+ * (PreIntegrator.cc:168-176) and keeps only the last; a kernel of its own (csrc/imu_pose.hip) runs the same loop on the states alone — no
+ * Phi, no Q, no covariance — and keeps them all.  Record j is the pose line System::MonoVIO would write if an image arrived right behind
+ * sample j and that frame ran no update; both branches of nSmallAngle are carried.  The loop starts from x[0..25] = qG, pG, g, qk, pk, v,
+ * bg, ba as they are, a non-identity qk included (Rk starts at QuatToRot(qk); pk is rebuilt from v, g, Dt and dp, as upstream).
+ * Two uses: dead reckoning between two images (rvio_hip_predict*: no side effect on the filter) and a dense trajectory (the ring). */
+typedef struct rvio_imu_pose {   /* 104 bytes, no padding */
+    int64_t seq;        /* ring records: 1, 2, ... IMU samples of this handle recorded since create / rvio_hip_initialize; rvio_hip_predict*: 0 */
+    int32_t img_count;  /* nImageCountAfterInit of the frame whose propagate consumes the sample (predict: the handle's current count) */
+    int32_t index;      /* j: position of the sample in its batch */
+    double t;           /* imu[j].t, copied */
+    double p[3];        /* pGj = R(qG)^T (pk_j - pG)                   (System.cc:341 with pk_j for pk) */
+    double q[4];        /* qjG = QuatMul(RotToQuat(Rk_j), qG), JPL xyzw (System.cc:339, PreIntegrator.cc:182) */
+    double v[3];        /* vk_j                                        (PreIntegrator.cc:176; what twist.linear carries, System.cc:414-416) */
+} rvio_imu_pose;
+/* Dead reckoning: the records of imu[0 .. m) from the CURRENT state of one instance.  Mutates nothing — not x, P, the frame count, the tracker
+ * or either ring.  Host buffers in and out, staged through device buffers of the call's own (allocated by the first call, outside the
+ * filter slab; m > RVIO_HIP_MAX_IMU grows them); waits for the filter stream like rvio_hip_get_pose, so the state is the one behind every
+ * frame enqueued so far.  m == 0: RVIO_OK, nothing written.  RVIO_ERR_INVALID: NULL handle, instance out of range, m < 0, a NULL buffer with
+ * m > 0; RVIO_ERR_STATE: before the first rvio_hip_set_state / rvio_hip_initialize. */
+int rvio_hip_predict(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio_imu_pose* out);
+/* The same for EVERY instance in one launch, device buffers, asynchronous on rvio_hip_stream (it reads the state behind everything already
+ * enqueued there): d_out[z * out_stride + j] for instance z, out_stride >= m records; d_imu[z * imu_stride + j], imu_stride = 0: one batch
+ * shared by all instances, else >= m (the rules of rvio_hip_frame_tracks_dev).  Violations: RVIO_ERR_INVALID. */
+int rvio_hip_predict_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride, int m, rvio_imu_pose* d_out, int out_stride);
+/* The IMU-rate ring: every IMU sample that ANY propagate of this handle consumes leaves a record (stage by stage, rvio_hip_frame*,
+ * rvio_hip_frame_points, rvio_hip_frame_begin_dev, the sharded frame — every rank alike —, both batch frames), written by the same kernel
+ * directly in front of the launch that propagates in place, on that launch's stream.  img_count is the count of the frame the samples
+ * belong to; a caller that sequences the stages itself calls rvio_hip_frame_plan ahead of rvio_hip_propagate*, as System::MonoVIO's order
+ * has it.  capacity = samples kept per instance: 0 = off (the default: such a handle allocates and launches what it did before these entry
+ * points existed), 1 .. 1048576.  The first enable drains the handle and allocates the ring, outside the filter slab, laid out
+ * ring[(seq - 1) % capacity][instance]; another capacity drains, reallocates and empties the ring (seq restarts at 1); 0 stops the launches
+ * and keeps the ring and its records; the same capacity again resumes.  Of a batch longer than the capacity the last `capacity` records
+ * survive.  rvio_hip_initialize empties the ring; rvio_hip_set_state* and rvio_hip_debug_poison leave it alone.  RVIO_ERR_INVALID: NULL
+ * handle, capacity outside 0 .. 1048576; RVIO_ERR_UNSUPPORTED (rvio_hip_last_error names the size): capacity x instances x 104 bytes
+ * exceeds 1 GiB. */
+int rvio_hip_set_imu_odometry(rvio_hip* h, int capacity);
+/* rvio_hip_get_odometry's semantics on that ring: the records of one instance with seq in [max(first_seq, newest - capacity + 1, 1), newest],
+ * oldest first, at most max_n; *n = how many.  `newest` is counted on the host from the m of each call.  Waits for the filter stream only.
+ * RVIO_ERR_STATE: the ring was never enabled; RVIO_ERR_INVALID: instance out of range, max_n < 0, out == NULL with max_n > 0. */
+int rvio_hip_get_imu_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_imu_pose* out, int32_t* n);
+
 /* --- feature-sharded updater (no reference counterpart) ------ */
 /* Stage A: per-feature build + gate on the features f with f % world == rank,
  * then local compression to this shard's share of the information block
@@ -460,7 +503,9 @@ int rvio_hip_debug_tracked(rvio_hip* h, int n, float* xy, float* un_xy);
  * 11 = the gray conversion of the last image handed over, in the form the frame launched (a _dev entry point: the caller's image must
  * still be alive; RVIO_ERR_UNSUPPORTED without a colour format or before the first image),
  * 12 = the odometry record kernel on the composed state the last frame left, all instances (into a slot of its own: the ring is left alone;
- * RVIO_ERR_UNSUPPORTED unless the ring was enabled). */
+ * RVIO_ERR_UNSUPPORTED unless the ring was enabled),
+ * 13 = the IMU-pose kernel on the state and the IMU batch of the last frame, all instances (a _dev entry point: the caller's IMU buffer must
+ * still be alive; into a buffer of its own; RVIO_ERR_UNSUPPORTED unless the IMU-rate ring was enabled and a frame has propagated). */
 int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us);
 /* Test hook against results that depend on LEFT-OVER state (scratch in HBM, LDS contents, stale hand-over entries).  Drains every stream of
  * the handle, then: what & 1 fills the filter's scratch and the spare state / covariance buffer with 0xff bytes (NaN); & 2 rewrites the LDS

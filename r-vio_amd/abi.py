@@ -141,6 +141,96 @@ def odom_pose_cov(x, P):
     return 0.5 * (Cm + Cm.T)
 
 
+class ImuPose(C.Structure):
+    """rvio_imu_pose: the pose line behind one IMU sample (rvio_hip_predict*, rvio_hip_get_imu_odometry): 104 bytes, no padding"""
+    _fields_ = [("seq", C.c_int64), ("img_count", C.c_int32), ("index", C.c_int32), ("t", C.c_double),
+                ("p", C.c_double * 3), ("q", C.c_double * 4), ("v", C.c_double * 3)]
+
+
+IMU_POSE_DTYPE = np.dtype([("seq", "i8"), ("img_count", "i4"), ("index", "i4"), ("t", "f8"), ("p", "f8", 3), ("q", "f8", 4), ("v", "f8", 3)])
+assert IMU_POSE_DTYPE.itemsize == C.sizeof(ImuPose) == 104
+
+
+def _quat_norm_pos(q):
+    q = q / math.sqrt(float(q @ q))
+    return -q if q[3] < 0 else q
+
+
+def quat_mul(a, b):
+    """QuatMul (util/Numerics.h:30-63), JPL xyzw: normalised, w >= 0"""
+    ax, ay, az, aw = a
+    bx, by, bz, bw = b
+    return _quat_norm_pos(np.array([aw * bx + az * by - ay * bz + ax * bw,
+                                    -az * bx + aw * by + ax * bz + ay * bw,
+                                    ay * bx - ax * by + aw * bz + az * bw,
+                                    -ax * bx - ay * by - az * bz + aw * bw]))
+
+
+def rot_to_quat(R):
+    """RotToQuat (util/Numerics.h:126-167): the four-branch form, normalised, w >= 0"""
+    T = R[0, 0] + R[1, 1] + R[2, 2]
+    d = [R[0, 0], R[1, 1], R[2, 2]]
+    q = np.zeros(4)
+    big = [i for i in range(3) if d[i] > T and all(d[i] > d[j] for j in range(3) if j != i)]
+    if big:
+        i = big[0]
+        j, k = (i + 1) % 3, (i + 2) % 3
+        q[i] = math.sqrt((1 + 2 * d[i] - T) / 4)
+        s = 1 / (4 * q[i])
+        q[j] = s * (R[i, j] + R[j, i])
+        q[k] = s * (R[i, k] + R[k, i])
+        q[3] = s * (R[j, k] - R[k, j])
+    else:
+        q[3] = math.sqrt((1 + T) / 4)
+        s = 1 / (4 * q[3])
+        q[0], q[1], q[2] = s * (R[1, 2] - R[2, 1]), s * (R[2, 0] - R[0, 2]), s * (R[0, 1] - R[1, 0])
+    return _quat_norm_pos(q)
+
+
+def imu_pose_model(cfg, x, imu):
+    """NumPy model of csrc/imu_pose.hip: the records (abi.IMU_POSE_DTYPE; seq = 0, img_count = 0) of the IMU batch `imu` (abi.IMU_DTYPE) from
+    the state head x[0:26].  Sample loop of PreIntegrator::propagate (PreIntegrator.cc:97-179) on the states alone, then the pose line
+    (System.cc:339-341) behind every sample.  Calls nothing from the library or the oracle: a third implementation."""
+    x = np.asarray(x, float)
+    qG, pG, gR, vR, bg, ba = x[0:4], x[4:7], x[7:10].copy(), x[17:20].copy(), x[20:23], x[23:26]
+    Rk = quat_to_rot(x[10:14])
+    RG = quat_to_rot(qG)
+    dp, dv, Dt = np.zeros(3), np.zeros(3), 0.0
+    I = np.eye(3)
+    g = float(cfg.gravity)
+    out = np.zeros(len(imu), IMU_POSE_DTYPE)
+    for j, u in enumerate(imu):
+        dt = float(u["dt"])
+        Dt += dt
+        w, a = u["w"] - bg, u["a"] - ba
+        w1 = math.sqrt(float(w @ w))
+        wdt = w1 * dt
+        wx = _skew(w)
+        wx2 = wx @ wx
+        if w1 < cfg.small_angle:
+            dR = I - dt * wx + (dt ** 2 / 2) * wx2
+            f1, f2, f3, f4 = -dt ** 3 / 3, dt ** 4 / 8, -dt ** 2 / 2, dt ** 3 / 6
+        else:
+            c, s = math.cos(wdt), math.sin(wdt)
+            dR = I - (s / w1) * wx + ((1 - c) / w1 ** 2) * wx2
+            f1 = (wdt * c - s) / w1 ** 3
+            f2 = .5 * (wdt * wdt - 2 * c - 2 * wdt * s + 2) / w1 ** 4
+            f3 = (c - 1) / w1 ** 2
+            f4 = (wdt - s) / w1 ** 3
+        Rk = dR @ Rk
+        dp = dp + dv * dt
+        dp = dp + Rk.T @ ((.5 * dt ** 2 * I + f1 * wx + f2 * wx2) @ a)
+        dv = dv + Rk.T @ ((dt * I + f3 * wx + f4 * wx2) @ a)
+        pk = vR * Dt - .5 * g * gR * Dt ** 2 + dp
+        vk = Rk @ (vR - g * gR * Dt + dv)
+        r = out[j]
+        r["index"], r["t"] = j, u["t"]
+        r["p"] = RG.T @ (pk - pG)
+        r["q"] = quat_mul(rot_to_quat(Rk), qG)
+        r["v"] = vk
+    return out
+
+
 # Camera.T_BC0 of config/rvio_euroc.yaml:55-62 (row-major)
 _T_BC0 = [0.0148655429818, -0.999880929698, 0.00414029679422, -0.0216401454975,
           0.999557249008, 0.0149672133247, 0.025715529948, -0.064676986768,

@@ -101,19 +101,24 @@ LP_HD inline size_t lit_diag_end(int ldh, bool stamps) {
 #define LP_JL_BYTES ((3 * 60 * 61 + 8 * 16 * 61 + 16) * 8)         // JL_LDS_DOUBLES
 #define LP_JL_THREADS 512                                          // joseph_lds_kernel's workgroup: eight waves, one tile of a strip round each
 #define LP_GEMM_T_LDS_BYTES (2 * 64 * 65 * 8)                      // gemm_T_lds_kernel's operands
+// imu_pose_kernel (imu_pose.hip), odom_kernel's geometry: one wave per instance, four instances per workgroup; per wave 16 words x 64 samples of LDS
+#define LP_IMUP_T 256
+#define LP_IMUP_WAVES (LP_IMUP_T / 64)
+#define LP_IMUP_WAVE_BYTES (16 * 64 * 8)
+#define LP_IMUP_LDS_BYTES (LP_IMUP_WAVES * LP_IMUP_WAVE_BYTES)
 
 // ---------------------------------------------------------------- the kernels create_impl gives a dynamic-LDS limit
 enum LpKernel {
     LPK_FEAT_BUILD16, LPK_FEAT_BUILD4, LPK_GRAM_REDUCE, LPK_BLOCK_SUM, LPK_LIT_BATCH, LPK_GEMM_T_LDS, LPK_GRAM_BATCH4, LPK_GRAM_BATCH6, LPK_FEAT_PROP,
     LPK_BOOKKEEP_B, LPK_RANSAC_BOOK, LPK_SOLVE9_SMALL, LPK_SOLVE6_1, LPK_SOLVE6_2, LPK_SOLVE6_3, LPK_JOSEPH_BATCH, LPK_UG, LPK_UG_LDS, LPK_FINAL_LDS,
-    LPK_JOSEPH_LDS, LPK_COUNT
+    LPK_JOSEPH_LDS, LPK_IMU_POSE, LPK_COUNT
 };
 // (as c++filt prints them, without return type and arguments: how the test finds each kernel's static LDS in the code object's notes)
 static const char* const kLpKernelName[LPK_COUNT] = {
     "feat_build_kernel<16>", "feat_build_kernel<4>", "gram_reduce_kernel", "block_sum_kernel", "lit_batch_kernel", "gemm_T_lds_kernel",
     "gram_reduce_batch_kernel<4>", "gram_reduce_batch_kernel<6>", "feat_prop_kernel", "bookkeep_b_kernel", "ransac_book_kernel", "solve9_small_kernel",
     "solve6_kernel<1, 8, 8>", "solve6_kernel<2, 12, 8>", "solve6_kernel<2, 16, 8>", "joseph_batch_kernel", "ug_kernel", "ug_lds_kernel", "final_lds_kernel",
-    "joseph_lds_kernel"
+    "joseph_lds_kernel", "imu_pose_kernel"
 };
 
 struct LaunchPlan {
@@ -239,6 +244,7 @@ inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size
     p.attr[LPK_UG_LDS] = LP_UGL_BYTES;
     p.attr[LPK_FINAL_LDS] = LP_FNL_BYTES;
     p.attr[LPK_JOSEPH_LDS] = LP_JL_BYTES;
+    p.attr[LPK_IMU_POSE] = LP_IMUP_LDS_BYTES;
     if (batch > 1 && !p.solve5_variant && !p.solve7_variant) { p.rc = 1; p.why = "batched filter: clone window too long for the unrolled solve kernel (6n <= 126)"; return p; }
     // nothing above may ask for more than a CU has: a configuration that would is refused here, by name, not by a failed hipFuncSetAttribute / launch
     for (int k = 0; k < LPK_COUNT; ++k)
@@ -393,6 +399,8 @@ enum {
     LPF_SUBPIX_WIDE = -5    // lp_subpix_wide_lds(half-window)   (detector_init sets it)
 };
 struct LpLaunch { int gx = 0, gy = 1, gz = 1, threads = 0; size_t lds = 0; int kernel = LPF_NONE; };   // gx == 0: not launched
+// imu_pose_kernel on `instances` instances (rvio_hip_predict: one; rvio_hip_predict_dev and the IMU-rate ring: the handle's batch)
+LP_HD inline LpLaunch imu_pose_launch(int instances) { return {(instances + LP_IMUP_WAVES - 1) / LP_IMUP_WAVES, 1, 1, LP_IMUP_T, LP_IMUP_LDS_BYTES, LPK_IMU_POSE}; }
 
 enum LpStream {          // the ROLE of a stream in a call; stream_of (rvio_hip.hip) maps it to one of the handle's four
     LPR_FILTER,          //   the filter stream: every launch of a per-stage call that is not forked to the side stream

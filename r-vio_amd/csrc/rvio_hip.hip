@@ -24,6 +24,7 @@
 #include "solve9.hip"   // round 5: the solve as blocked SPD factorisations on the matrix cores (one instance; every window up to 6n = 192)
 #include "landmarks.hip"   // Updater::update's landmark cloud (rvio_hip_set_landmarks)
 #include "odom.hip"        // the per-frame odometry record: pose, velocity, covariance (rvio_hip_set_odometry)
+#include "imu_pose.hip"    // IMU-rate odometry: a pose per IMU sample (rvio_hip_predict, rvio_hip_set_imu_odometry)
 #pragma clang fp contract(off)
 #include "frontend_kernels.hip"
 #include "klt3.hip"
@@ -166,6 +167,18 @@ struct rvio_hip {
     int odom_cap = 0;          // records per instance the ring holds
     bool odom_on = false;
     long long odom_seq = 0;    // records written since create / rvio_hip_initialize / the last change of capacity: the newest record's seq
+    // IMU-rate ring (imu_pose_kernel in front of whatever propagates in place): allocated by rvio_hip_set_imu_odometry, outside the slab, laid
+    // out ring[(seq - 1) % imuo_cap][instance]; imuo_seq counts the samples recorded (the m of every propagate while the ring is on)
+    rvio_imu_pose* imuo_ring = nullptr;
+    int imuo_cap = 0;
+    bool imuo_on = false;
+    long long imuo_seq = 0;
+    size_t time_imu_bs = 0;    // instance stride of time_imu (rvio_hip_debug_time_kernel(13))
+    // staging of rvio_hip_predict (host in / host out), allocated by its first call, outside the slab: samples in, records out
+    rvio_imu* pred_imu = nullptr;
+    rvio_imu_pose* pred_out = nullptr;
+    int pred_cap = 0;
+    bool has_state = false;    // rvio_hip_set_state* / rvio_hip_initialize* has run (rvio_hip_predict* refuses to extrapolate from nothing)
     // colour input (rvio_hip_set_image_format): the gray images every stage behind gray_kernel reads instead of the caller's.  Allocated with the
     // first colour format, outside the slab (a mono handle keeps its memory layout), instance stride W * H; four in rotation like d_eq2[] (see
     // build_pyramid_dev for who reads a slot last)
@@ -480,6 +493,7 @@ static const void* lp_kernel_fn(int k) {
         case LPK_UG_LDS: return (const void*)ug_lds_kernel;
         case LPK_FINAL_LDS: return (const void*)final_lds_kernel;
         case LPK_JOSEPH_LDS: return (const void*)joseph_lds_kernel;
+        case LPK_IMU_POSE: return (const void*)imu_pose_kernel;
     }
     return nullptr;
 }
@@ -622,6 +636,9 @@ void rvio_hip_destroy(rvio_hip* h) {
     if (h->private_queues) g_private_queue_handles.fetch_sub(1);
     for (void* p : h->allocs) hipFree(p);
     if (h->odom_ring) hipFree(h->odom_ring);
+    if (h->imuo_ring) hipFree(h->imuo_ring);
+    if (h->pred_imu) hipFree(h->pred_imu);
+    if (h->pred_out) hipFree(h->pred_out);
     for (int k = 0; k < rvio_hip::kPin; ++k) { if (h->pin[k]) hipHostFree(h->pin[k]); if (h->evPin[k]) hipEventDestroy(h->evPin[k]); if (h->evPin2[k]) hipEventDestroy(h->evPin2[k]); }
     if (h->first_mirror) hipHostFree(h->first_mirror);
     if (h->evA) hipEventDestroy(h->evA);
@@ -682,6 +699,7 @@ static int set_state_range(rvio_hip* h, int lo, int hi, const double* x, int xdi
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->n_clones_host = n;
     h->chol_ready = false;   // (the slab's factor belongs to the covariance that was just replaced)
+    h->has_state = true;
     return RVIO_OK;
 }
 // (a batch handle: every instance receives the same state)
@@ -751,6 +769,7 @@ int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n
     h->img_count = 0;
     h->lm_frame = -1;   // no cloud since initialisation (the enable flag stays)
     h->odom_seq = 0;    // ... and no odometry record: seq restarts at 1 (the getters read nothing beyond odom_seq)
+    h->imuo_seq = 0;    // ... nor an IMU-rate record
     // a (re-)initialised filter starts with an empty window: the tracker starts over too (mbIsTheFirstImage, Tracker.cc:88), or its
     // histories would be longer than the window they refer to
     if (h->front_end) {
@@ -857,9 +876,29 @@ static int ensure_imu_capacity(rvio_hip* h, int m) {
 static UpdateForms forms_at(const rvio_hip* h, int n, bool pre = false, bool whole_update = true, bool combined = true) {
     return update_forms(h->plan, h->batch, n, pre, whole_update, combined, h->lit_rows != nullptr);
 }
-static int propagate_dev(rvio_hip* h, const rvio_imu* d_imu, int m, size_t imu_bs = 0, hipStream_t st = nullptr) {   // imu_bs = 0: every instance integrates the same samples
+// imu_pose_kernel (imu_pose.hip) on `instances` instances whose state starts at x: records of d_imu[0 .. m) from that state.  cap == 0: into
+// out[z * out_stride + j] (rvio_hip_predict*); cap > 0: into the ring `out`, record j with seq = seq0 + j
+static void launch_imu_pose(rvio_hip* h, hipStream_t st, int instances, const double* x, const rvio_imu* d_imu, size_t imu_bs, int m, rvio_imu_pose* out,
+                            long long out_stride, long long seq0, int cap, int img_count) {
+    const LpLaunch l = imu_pose_launch(instances);
+    hipLaunchKernelGGL(imu_pose_kernel, dim3((unsigned)l.gx), dim3((unsigned)l.threads), l.lds, st, h->dc.small_angle, h->dc.gravity, instances, x, h->slab_bytes, d_imu, imu_bs, m,
+                       (unsigned long long*)out, out_stride, seq0, cap, img_count);
+}
+// The IMU-rate ring's launch: directly in front of whatever propagates in place, on the stream that propagate runs on (it reads the state that
+// propagate is about to overwrite, and the same samples).  img_count: nImageCountAfterInit of the frame that consumes the samples.
+static int imu_ring_record(rvio_hip* h, const rvio_imu* d_imu, int m, size_t imu_bs, hipStream_t st, int img_count) {
+    if (!h->imuo_on || m <= 0) return RVIO_OK;
+    launch_imu_pose(h, st, h->batch, h->x[h->cur], d_imu, imu_bs, m, h->imuo_ring, 0, h->imuo_seq + 1, h->imuo_cap, img_count);
+    HIPCHK(h, hipGetLastError());
+    h->imuo_seq += m;   // (counted once the launch is known to be enqueued: the getter serves nothing beyond imuo_seq)
+    return RVIO_OK;
+}
+// img_count: nImageCountAfterInit of the frame this propagate belongs to, for the IMU-rate ring's records (-1: the handle's current count — every caller
+// that has advanced it already; the pipelined frame propagates ahead of frame_tail_dev's increment and passes the next count)
+static int propagate_dev(rvio_hip* h, const rvio_imu* d_imu, int m, size_t imu_bs = 0, hipStream_t st = nullptr, int img_count = -1) {   // imu_bs = 0: every instance integrates the same samples
     if (!st) st = h->stream;
-    h->time_imu = d_imu; h->time_m = m;   // (rvio_hip_debug_time_kernel(8))
+    h->time_imu = d_imu; h->time_m = m; h->time_imu_bs = imu_bs;   // (rvio_hip_debug_time_kernel(8), (13))
+    if (h->imuo_on) { const int rci = imu_ring_record(h, d_imu, m, imu_bs, st, img_count < 0 ? h->img_count : img_count); if (rci != RVIO_OK) return rci; }
     if (h->batch > 8)
         hipLaunchKernelGGL(propagate_kernel3b, dim3(1, 1, h->batch), dim3(256), 0, st, h->dc, h->meta, h->n_clones_host, h->x[h->cur], h->P[h->cur], d_imu, m,
                            h->slab_bytes, imu_bs);
@@ -955,6 +994,8 @@ static int update_local_dev(rvio_hip* h, int rank, int world, bool combine) {
     const int n = h->n_clones_host;
     const int B = h->batch;
     if (h->fuse_m >= 0) {
+        // (the frame count is this frame's: frame_tail_dev / the sharded frame have advanced it)
+        if (h->imuo_on) { const int rci = imu_ring_record(h, h->fuse_imu, h->fuse_m, 0, h->stream, h->img_count); if (rci != RVIO_OK) return rci; }
         launch_feat_prop(h, n, h->fuse_imu, h->fuse_m, rank, world);
         h->fuse_m = -1;
     } else {
@@ -1269,6 +1310,87 @@ int rvio_hip_get_odometry_all(rvio_hip* h, rvio_odom* out, int64_t* seq) {
     if (seq) *seq = h->odom_seq;
     if (h->odom_seq == 0) return RVIO_OK;
     HIPCHK(h, hipMemcpyAsync(out, h->odom_ring + (size_t)((h->odom_seq - 1) % h->odom_cap) * h->batch, sizeof(rvio_odom) * h->batch, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RVIO_OK;
+}
+
+// ------------------------------------------------------------------ IMU-rate odometry (imu_pose.hip)
+static int predict_check(rvio_hip* h) {
+    if (!h->has_state) { h->err = "rvio_hip_predict before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
+    return RVIO_OK;
+}
+// every instance, asynchronous on the filter stream: behind everything enqueued there, ahead of everything enqueued later
+int rvio_hip_predict_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride, int m, rvio_imu_pose* d_out, int out_stride) {
+    if (!h || m < 0 || (m > 0 && (!d_imu || !d_out)) || imu_stride < 0 || (imu_stride > 0 && imu_stride < m) || out_stride < m) return RVIO_ERR_INVALID;
+    { const int rc = predict_check(h); if (rc != RVIO_OK) return rc; }
+    if (m == 0) return RVIO_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    launch_imu_pose(h, h->stream, h->batch, h->x[h->cur], d_imu, (size_t)imu_stride * sizeof(rvio_imu), m, d_out, out_stride, 0, 0, h->img_count);
+    HIPCHK(h, hipGetLastError());
+    return RVIO_OK;
+}
+// one instance, host buffers: staged through buffers of its own (the staging of the other host-buffer entry points may still be read by a
+// frame in flight), which grow with m; waits for the filter stream only, like rvio_hip_get_pose
+int rvio_hip_predict(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio_imu_pose* out) {
+    if (!h || instance < 0 || instance >= h->batch || m < 0 || (m > 0 && (!imu || !out))) return RVIO_ERR_INVALID;
+    { const int rc = predict_check(h); if (rc != RVIO_OK) return rc; }
+    if (m == 0) return RVIO_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (m > h->pred_cap) {   // (every earlier call has waited for its copies: nothing reads the old blocks)
+        const int cap = std::max(std::max(2 * h->pred_cap, RVIO_HIP_MAX_IMU), (m + 63) & ~63);
+        rvio_imu* pi = nullptr; rvio_imu_pose* po = nullptr;
+        HIPCHK(h, hipMalloc((void**)&pi, sizeof(rvio_imu) * (size_t)cap));
+        if (hipMalloc((void**)&po, sizeof(rvio_imu_pose) * (size_t)cap) != hipSuccess) { (void)hipFree(pi); h->err = "hipMalloc of the predict staging failed"; return RVIO_ERR_NO_DEVICE; }
+        if (h->pred_imu) (void)hipFree(h->pred_imu);
+        if (h->pred_out) (void)hipFree(h->pred_out);
+        h->pred_imu = pi; h->pred_out = po; h->pred_cap = cap;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->pred_imu, imu, sizeof(rvio_imu) * (size_t)m, hipMemcpyHostToDevice, h->stream));
+    launch_imu_pose(h, h->stream, 1, (const double*)((const char*)h->x[h->cur] + (size_t)instance * h->slab_bytes), h->pred_imu, 0, m, h->pred_out, m, 0, 0, h->img_count);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out, h->pred_out, sizeof(rvio_imu_pose) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RVIO_OK;
+}
+// the ring: rvio_hip_set_odometry's clauses, one record per IMU sample instead of one per frame
+int rvio_hip_set_imu_odometry(rvio_hip* h, int capacity) {
+    if (!h || capacity < 0 || capacity > 1048576) return RVIO_ERR_INVALID;
+    if (capacity == 0) { h->imuo_on = false; return RVIO_OK; }   // (the launches stop, the ring and its records stay)
+    if (capacity != h->imuo_cap) {
+        const size_t bytes = (size_t)capacity * h->batch * sizeof(rvio_imu_pose);
+        if (bytes > ((size_t)1 << 30)) {
+            h->err = "IMU-rate odometry ring of " + std::to_string(capacity) + " x " + std::to_string(h->batch) + " records = " + std::to_string(bytes) + " bytes exceeds 1 GiB";
+            return RVIO_ERR_UNSUPPORTED;
+        }
+        // (first enable or another capacity: with nothing in flight; a new ring is empty)
+        { const int rc = drain_all(h); if (rc != RVIO_OK) return rc; }
+        HIPCHK(h, hipSetDevice(h->device));
+        rvio_imu_pose* p = nullptr;
+        HIPCHK(h, hipMalloc((void**)&p, bytes));
+        if (h->imuo_ring) (void)hipFree(h->imuo_ring);
+        h->imuo_ring = p; h->imuo_cap = capacity; h->imuo_seq = 0;
+        HIPCHK(h, hipMemsetAsync(p, 0, bytes, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    h->imuo_on = true;
+    return RVIO_OK;
+}
+// the filter stream only: every record is written on it, or on a stream it has joined since (the overlapped propagate of rvio_hip_frame_tracks_dev)
+int rvio_hip_get_imu_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_imu_pose* out, int32_t* n) {
+    if (!h || instance < 0 || instance >= h->batch || max_n < 0 || (!out && max_n > 0)) return RVIO_ERR_INVALID;
+    if (!h->imuo_ring) { h->err = "the IMU-rate odometry ring was never enabled (rvio_hip_set_imu_odometry)"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const long long newest = h->imuo_seq, cap = h->imuo_cap;
+    const long long lo = std::max<long long>(std::max<long long>(first_seq, newest - cap + 1), 1);
+    const long long cnt = std::max<long long>(0, std::min<long long>(newest - lo + 1, max_n));
+    if (n) *n = (int32_t)cnt;
+    if (cnt == 0) return RVIO_OK;
+    // instance i's records lie batch records apart; the range wraps around the end of the ring at most once
+    const size_t pitch = sizeof(rvio_imu_pose) * h->batch;
+    const long long s0 = (lo - 1) % cap, c0 = std::min(cnt, cap - s0);
+    HIPCHK(h, hipMemcpy2DAsync(out, sizeof(rvio_imu_pose), h->imuo_ring + (size_t)s0 * h->batch + instance, pitch, sizeof(rvio_imu_pose), (size_t)c0, hipMemcpyDeviceToHost, h->stream));
+    if (cnt > c0)
+        HIPCHK(h, hipMemcpy2DAsync(out + c0, sizeof(rvio_imu_pose), h->imuo_ring + instance, pitch, sizeof(rvio_imu_pose), (size_t)(cnt - c0), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RVIO_OK;
 }
@@ -1926,7 +2048,7 @@ static int frame_dev_impl(rvio_hip* h, const FrontForms& f, const uint8_t* d_img
     const bool fuse = h->plan.fuse_ok && (!begin_only || defer_propagate) && h->n_clones_host > h->cfg.min_track_len - 1;
     int rc = RVIO_OK;
     h->fuse_m = -1;
-    if (!fuse) rc = propagate_dev(h, d_imu, m, h->imu_bs);
+    if (!fuse) rc = propagate_dev(h, d_imu, m, h->imu_bs, nullptr, h->img_count + 1);   // (this frame's count: frame_tail_dev / rvio_hip_frame_plan advance it behind this call)
     if (rc != RVIO_OK) return rc;
     const double t1 = dbg_host ? now() : 0;
     BookOut bo;
@@ -1944,7 +2066,7 @@ static int frame_dev_impl(rvio_hip* h, const FrontForms& f, const uint8_t* d_img
         return RVIO_OK;
     }
     if (fuse) { h->fuse_imu = d_imu; h->fuse_m = m; }   // consumed by the per-feature launch of this frame's update (same condition: it runs)
-    if (fuse) { h->time_imu = d_imu; h->time_m = m; }
+    if (fuse) { h->time_imu = d_imu; h->time_m = m; h->time_imu_bs = 0; }
     rc = frame_tail_dev(h, d_imu, m, /*propagated=*/true);
     h->fuse_m = -1;
     const double t4 = dbg_host ? now() : 0;
@@ -2276,6 +2398,12 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
         if (!h->odom_ring) { h->err = "the odometry ring was never enabled (rvio_hip_set_odometry)"; return RVIO_ERR_UNSUPPORTED; }
         HIPCHK(h, hipMalloc((void**)&odt, sizeof(rvio_odom) * h->batch));
     }
+    rvio_imu_pose* ipt = nullptr;
+    if (which == 13) {   // (into a buffer of its own, in the ring's layout: the ring stays what the frames wrote)
+        if (!h->imuo_ring) { h->err = "the IMU-rate odometry ring was never enabled (rvio_hip_set_imu_odometry)"; return RVIO_ERR_UNSUPPORTED; }
+        if (!h->time_imu || h->time_m < 1) { h->err = "no frame has propagated an IMU batch yet"; return RVIO_ERR_UNSUPPORTED; }
+        HIPCHK(h, hipMalloc((void**)&ipt, sizeof(rvio_imu_pose) * (size_t)h->time_m * h->batch));
+    }
     LmOut lmt = {nullptr, nullptr, nullptr, nullptr, 0};
     if (which == 10) {   // (into buffers of its own: the getter's cloud stays the last update's)
         if (!h->lm.count) return RVIO_ERR_UNSUPPORTED;
@@ -2295,6 +2423,9 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
     for (int it = 0; it < iters; ++it) {
         if (which == 12) {   // odom_kernel as augment_compose_dev launches it, on the composed state the last frame left
             launch_odom(h, odt, h->odom_seq);
+        } else
+        if (which == 13) {   // imu_pose_kernel as the ring launches it: the IMU batch of the last frame (the caller's device buffer must still be alive), the state that frame left
+            launch_imu_pose(h, h->stream, h->batch, h->x[h->cur], h->time_imu, h->time_imu_bs, h->time_m, ipt, 0, 1, h->time_m, h->img_count);
         } else
         if (which == 10) {
             // landmark_kernel as the update launches it, on the hand-over table, accept flags and (phi, psi, rho) of the last update; the state
@@ -2356,6 +2487,7 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
     hipEventDestroy(e0); hipEventDestroy(e1);
     if (bx) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(bx); (void)hipFree(bP); }
     if (odt) (void)hipFree(odt);   // (the event above has drained the stream)
+    if (ipt) (void)hipFree(ipt);
     if (lmt.count) { h->allocs.pop_back(); (void)hipFree(lmt.count); }   // (lm_alloc pushed it last; the event above has drained the stream)
     *avg_us = ms * 1e3f / iters;
     HIPCHK(h, hipGetLastError());

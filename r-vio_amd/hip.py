@@ -28,6 +28,7 @@ SYMBOLS = [
     "rvio_hip_set_image_format", "rvio_hip_get_image_format",
     "rvio_hip_set_odometry", "rvio_hip_get_odometry", "rvio_hip_get_odometry_all", "rvio_hip_get_pose_at",
     "rvio_calibration_from_config", "rvio_hip_set_calibration_at", "rvio_hip_set_calibrations", "rvio_hip_get_calibration_at", "rvio_hip_initialize_at",
+    "rvio_hip_predict", "rvio_hip_predict_dev", "rvio_hip_set_imu_odometry", "rvio_hip_get_imu_odometry",
 ]
 
 _LIB = None
@@ -428,7 +429,7 @@ class RvioHip:
         return xy, un
 
     def time_kernel(self, which, iters=20):
-        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection, 10 the landmark cloud kernel, 11 the gray conversion of the last colour or raw (16-bit, Bayer) image in the form the frame launched, 12 the odometry record kernel (HIP events, handle stream)"""
+        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection, 10 the landmark cloud kernel, 11 the gray conversion of the last colour or raw (16-bit, Bayer) image in the form the frame launched, 12 the odometry record kernel, 13 the IMU-pose kernel on the state and IMU batch of the last frame (HIP events, handle stream)"""
         us = C.c_float(0)
         self._ck(self.L.rvio_hip_debug_time_kernel(self.h, int(which), int(iters), C.byref(us)), "debug_time_kernel")
         return float(us.value)
@@ -489,3 +490,31 @@ class RvioHip:
         seq = C.c_int64(0)
         self._ck(self.L.rvio_hip_get_odometry_all(self.h, out.ctypes.data_as(C.POINTER(abi.rvio_odom)), C.byref(seq)), "get_odometry_all")
         return int(seq.value), out
+
+    # ---- IMU-rate odometry (PreIntegrator.cc:168-176 kept per sample)
+    def predict(self, imu, instance=0):
+        """dead reckoning: the pose behind every sample of `imu` from the CURRENT state of one instance (abi.IMU_POSE_DTYPE); mutates nothing"""
+        imu = np.ascontiguousarray(imu)
+        out = np.zeros(len(imu), abi.IMU_POSE_DTYPE)
+        self._ck(self.L.rvio_hip_predict(self.h, int(instance), imu.ctypes.data_as(C.POINTER(abi.rvio_imu)) if len(imu) else None, len(imu),
+                                         out.ctypes.data_as(C.POINTER(abi.ImuPose)) if len(out) else None), "predict")
+        return out
+
+    def predict_dev(self, d_imu_ptr, imu_stride, m, d_out_ptr, out_stride):
+        """the same for every instance, device buffers, asynchronous on the filter stream: d_out[z * out_stride + j]"""
+        self._ck(self.L.rvio_hip_predict_dev(self.h, C.c_void_p(d_imu_ptr), int(imu_stride), int(m), C.c_void_p(d_out_ptr), int(out_stride)), "predict_dev")
+
+    def set_imu_odometry(self, capacity):
+        """keep an rvio_imu_pose record of every IMU sample any propagate consumes from now on, `capacity` per instance on the device; 0: off"""
+        self._ck(self.L.rvio_hip_set_imu_odometry(self.h, int(capacity)), "set_imu_odometry")
+        if capacity:
+            self._imuo_cap = int(capacity)
+
+    def get_imu_odometry(self, instance=0, first_seq=1, max_n=None):
+        """records of one instance still in the IMU-rate ring with seq >= first_seq, oldest first (at most max_n): abi.IMU_POSE_DTYPE"""
+        cap = getattr(self, "_imuo_cap", 0) if max_n is None else int(max_n)
+        out = np.zeros(max(cap, 0), abi.IMU_POSE_DTYPE)
+        n = C.c_int32(0)
+        self._ck(self.L.rvio_hip_get_imu_odometry(self.h, int(instance), C.c_int64(int(first_seq)), cap,
+                                                  out.ctypes.data_as(C.POINTER(abi.ImuPose)) if len(out) else None, C.byref(n)), "get_imu_odometry")
+        return out[: n.value].copy()
