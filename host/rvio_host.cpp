@@ -318,6 +318,30 @@ int System::device_flags() {
     return fi.reserved[0];
 }
 
+int System::state_dim() const {
+    const int n = std::min(std::max(n_img_ - 1, 0), s_.cfg.max_track_len - 1);   // (System.cc:280: the first frame augments nothing)
+    return 24 + 6 * n;
+}
+int System::update_aux(const rvio_aux_meas& meas) {
+    if (!h_ || !ready_) { err_ = "System::update_aux before the filter is initialised"; return -1; }
+    if (rvio_hip_update_aux(h_, -1, &meas) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+    return 0;
+}
+int System::velocity(const double v[3], double sigma, bool gate) {
+    const int d = state_dim();
+    std::vector<double> H((size_t)3 * d, 0.0);
+    for (int i = 0; i < 3; ++i) H[(size_t)i * d + 15 + i] = 1.0;
+    const double z[3] = {v[0], v[1], v[2]}, sg[3] = {sigma, sigma, sigma};
+    rvio_aux_meas ms{};
+    ms.m = 3; ms.mode = RVIO_AUX_VALUE; ms.gate = gate ? 1 : 0;
+    ms.H = H.data(); ms.v = z; ms.sigma = sg;
+    return update_aux(ms);
+}
+int System::zero_velocity(double sigma, bool gate) {
+    const double z[3] = {0, 0, 0};
+    return velocity(z, sigma, gate);
+}
+
 int System::MonoVIO(PoseLine* pose) {
     ImageData image;
     std::vector<ImuData> imus;

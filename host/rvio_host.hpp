@@ -118,6 +118,17 @@ public:
     // the handle's sticky device-side flags (rvio_frame_info.reserved[0]: 1 singular pivot, 2 a track dropped, 4 a stage counter timed out,
     // 8 a non-positive gate pivot; 0 = none) — waits for everything in flight, so a replay reads it once at its end.  -1: the query failed.
     int device_flags();
+    // The auxiliary measurement update (rvio_hip_update_aux): what is not a camera track — wheel odometry, standing still, a speed-over-ground
+    // sensor — fused into the filter on the device, behind the last frame handed over and ahead of the next; no frame is drained for it.
+    // update_aux: any measurement the caller has linearised, m <= RVIO_AUX_MAX_ROWS rows over state_dim() columns.  velocity: the velocity in
+    // the IMU frame {Rk} (state slot v, error columns 15..17) was measured as v, each axis with standard deviation sigma; zero_velocity: it
+    // was 0.  gate: apply only if the measurement passes the 95 % chi-square test the features pass.  0, or -1 with error().
+    int update_aux(const rvio_aux_meas& meas);
+    int zero_velocity(double sigma, bool gate);
+    int velocity(const double v[3], double sigma, bool gate);
+    // columns of an auxiliary H right now: 24 + 6 clones, the clones counted as the library counts them (one per frame behind the first, up
+    // to Tracker.nMaxTrackingLength - 1) — no read-back
+    int state_dim() const;
     bool recording() const { return rec_; }
     bool is_ready() const { return ready_; }
     int frames_after_init() const { return n_img_; }

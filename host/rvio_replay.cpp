@@ -10,6 +10,11 @@
 //                                        --odometry: pose, velocity and pose covariance of every frame, read in bulk from the handle's ring of N
 //                                        records (default 256; System::record_odometry_to); without <poses_out.dat> no frame is drained for its pose
 //                                        --landmarks: Updater::update's landmark cloud behind every updating frame (System::record_landmarks_to)
+//                                        [--velocity FILE [--velocity-sigma S] [--velocity-gate]]
+//                                        --velocity: a CSV of `t_ns, vx, vy, vz` — the velocity in the IMU frame, e.g. from wheel encoders — fused on the
+//                                        device (System::velocity) right behind the frame whose image stamp is nearest to t_ns, within half an image
+//                                        period; at most one row per frame (the last one wins), rows that match no frame are counted and the count is
+//                                        printed.  S: the standard deviation per axis in m/s (default 0.05); --velocity-gate: the 95 % chi-square gate
 //   rvio_replay --check-settings <settings.yaml>        print the parsed configuration (no GPU needed)
 //   rvio_replay --check-dataset <asl_root>              print what the dataset reader found (no GPU needed)
 //   rvio_replay --check-image <file.png|.pgm>           decode one image and print its size and checksum (no GPU needed)
@@ -80,6 +85,49 @@ static int check_image(const char* path, bool is_rgb, const char* encoding) {
     return 0;
 }
 
+// ---------------------------------------------------------------- --velocity
+struct VelocityRows {
+    std::vector<int> has;                 // per image of the dataset: a row was matched to it
+    std::vector<double> v;                // ... and its velocity, 3 per image
+    long rows = 0, unmatched = 0, applied = 0;
+    double sigma = 0.05; bool gate = false;
+};
+// lines of `t_ns, vx, vy, vz` ('#' lines and a header line without a leading digit are skipped); the image whose stamp is nearest, if that is
+// within half the mean image period, takes the row
+static bool read_velocity(const char* path, const AslDataset& d, VelocityRows* out, std::string* err) {
+    std::ifstream in(path);
+    if (!in) { *err = std::string("cannot read ") + path; return false; }
+    const size_t N = d.images.size();
+    out->has.assign(N, 0); out->v.assign(3 * N, 0.0);
+    const double period = N > 1 ? (d.images.back().first - d.images.front().first) / (double)(N - 1) : 0.0;
+    std::string line;
+    while (std::getline(in, line)) {
+        size_t b = line.find_first_not_of(" \t\r");
+        if (b == std::string::npos || line[b] == '#' || !(line[b] >= '0' && line[b] <= '9')) continue;
+        long long ns = 0; double v[3];
+        if (std::sscanf(line.c_str() + b, "%lld , %lf , %lf , %lf", &ns, &v[0], &v[1], &v[2]) != 4) { *err = std::string(path) + ": not `t_ns, vx, vy, vz`: " + line; return false; }
+        ++out->rows;
+        const double t = (double)(ns / 1000000000LL) + 1e-9 * (double)(ns % 1000000000LL);
+        auto it = std::lower_bound(d.images.begin(), d.images.end(), t, [](const std::pair<double, std::string>& im, double tt) { return im.first < tt; });
+        size_t k = (size_t)(it - d.images.begin());
+        if (k == N || (k > 0 && t - d.images[k - 1].first <= d.images[k].first - t)) k = k > 0 ? k - 1 : k;
+        if (N == 0 || std::fabs(d.images[k].first - t) > 0.5 * period) { ++out->unmatched; continue; }
+        out->has[k] = 1;
+        for (int i = 0; i < 3; ++i) out->v[3 * k + i] = v[i];
+    }
+    return true;
+}
+// behind the frame of image k, if the filter processed it
+static int apply_velocity(System& sys, VelocityRows* vr, size_t k) {
+    if (!vr || k >= vr->has.size() || !vr->has[k]) return 0;
+    if (sys.velocity(&vr->v[3 * k], vr->sigma, vr->gate) < 0) return -1;
+    ++vr->applied;
+    return 0;
+}
+static void print_velocity(const VelocityRows& vr) {
+    std::fprintf(stderr, "rvio_replay: velocity: %ld rows, %ld applied, %ld matched no frame\n", vr.rows, vr.applied, vr.unmatched);
+}
+
 // ---------------------------------------------------------------- replay passes
 struct FrameDump {            // what the device holds behind a frame (read with every stream drained)
     rvio_frame_info info{};
@@ -99,6 +147,7 @@ struct PassOptions {
     int odometry_ring = 256;
     const char* imu_odometry = nullptr;  // System::record_imu_odometry_to
     int imu_odometry_ring = 4096;
+    VelocityRows* velocity = nullptr;    // --velocity
 };
 static bool dump_frame(System& sys, const rvio_config& c, FrameDump* d) {
     rvio_hip* h = sys.handle();
@@ -124,7 +173,9 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
     double t_filter = 0;
     unsigned long long lcg = 0x9e3779b97f4a7c15ull ^ (unsigned long long)(o.stall_seed + 1);
     auto rnd = [&](unsigned mod) { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; return (unsigned)((lcg >> 33) % mod); };
+    size_t image_k = (size_t)-1;
     for (const auto& im : d.images) {
+        ++image_k;
         if (o.max_frames >= 0 && n_images >= o.max_frames) break;
         while (ii < d.imu.size() && (d.imu[ii].t <= im.first + s.cam_time_offset || (ii > 0 && d.imu[ii - 1].t <= im.first + s.cam_time_offset))) sys.PushImuData(d.imu[ii++]);
         ImageData img;
@@ -142,6 +193,7 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
         if (rc < 0) { *err = sys.error(); return 1; }
         if (rc == 1) {
             poses->push_back(p);
+            if (apply_velocity(sys, o.velocity, image_k) < 0) { *err = sys.error(); return 1; }
             if (o.sync_every_frame || o.dump_at == n_frames) {
                 FrameDump fd;
                 if (!dump_frame(sys, s.cfg, &fd)) { *err = rvio_hip_last_error(sys.handle()); return 1; }
@@ -236,7 +288,8 @@ int main(int argc, char** argv) {
     }
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--record-dir DIR] [--record]\n"
-                             "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n", argv[0]);
+                             "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n"
+                             "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate]\n", argv[0]);
         return 2;
     }
     const char* out_path = nullptr;
@@ -244,6 +297,7 @@ int main(int argc, char** argv) {
     const char* landmarks = nullptr;
     const char* odometry = nullptr; int odometry_ring = 256;
     const char* imu_odometry = nullptr; int imu_odometry_ring = 4096;
+    const char* velocity = nullptr; double velocity_sigma = 0.05; bool velocity_gate = false;
     const char* record_dir = "."; bool force_record = false, sync_every = false, self = false; int noise_wgs = 0;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -259,6 +313,9 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--imu-odometry") && i + 1 < argc) imu_odometry = argv[++i];   // one line per IMU sample: pose and velocity (read in bulk from the IMU-rate ring)
         else if (!std::strcmp(argv[i], "--imu-odometry-ring") && i + 1 < argc) imu_odometry_ring = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--selfcheck")) self = true;
+        else if (!std::strcmp(argv[i], "--velocity") && i + 1 < argc) velocity = argv[++i];   // `t_ns, vx, vy, vz` rows fused behind the nearest frame (System::velocity)
+        else if (!std::strcmp(argv[i], "--velocity-sigma") && i + 1 < argc) velocity_sigma = std::atof(argv[++i]);
+        else if (!std::strcmp(argv[i], "--velocity-gate")) velocity_gate = true;
         else out_path = argv[i];
     }
     Settings s; std::string err;
@@ -266,14 +323,23 @@ int main(int argc, char** argv) {
     for (const std::string& k : s.missing) std::fprintf(stderr, "settings: %s is missing (upstream would read 0); the EuRoC default is used\n", k.c_str());
     AslDataset d;
     if (!read_asl(argv[2], &d, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
+    VelocityRows vrows; VelocityRows* vr = nullptr;
+    if (velocity) {
+        if (!(velocity_sigma > 0)) { std::fprintf(stderr, "--velocity-sigma must be > 0\n"); return 1; }
+        if (self) { std::fprintf(stderr, "--velocity and --selfcheck do not combine\n"); return 1; }
+        if (!read_velocity(velocity, d, &vrows, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
+        vrows.sigma = velocity_sigma; vrows.gate = velocity_gate;
+        vr = &vrows;
+    }
     print_runtime();
     if (self) return selfcheck(s, d, device, max_frames, stall_seed, noise_wgs);
     if (sync_every || stall_seed >= 0 || noise_wgs > 0) {   // the plain replay with one of the two A/B pacings
         std::vector<PoseLine> poses; double ms = 0; int flags = 0;
-        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring;
+        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.velocity = vr;
         if (run_pass(s, d, device, o, &poses, nullptr, &ms, &flags, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
         if (out_path) { std::ofstream out(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } for (const PoseLine& p : poses) out << format_pose(p); }
         std::fprintf(stderr, "rvio_replay: %zu filtered frames, %.3f ms per MonoVIO call, device flags %d\n", poses.size(), ms, flags);
+        if (vr) print_velocity(*vr);
         return 0;
     }
     System sys(s, device);
@@ -288,7 +354,9 @@ int main(int argc, char** argv) {
     size_t ii = 0;
     long n_frames = 0, n_images = 0;
     double t_filter = 0;
+    size_t image_k = (size_t)-1;
     for (const auto& im : d.images) {
+        ++image_k;
         if (max_frames >= 0 && n_images >= max_frames) break;
         // IMU callbacks that precede this image (plus one sample beyond it, so that GetMeasurements sees enough data)
         while (ii < d.imu.size() && (d.imu[ii].t <= im.first + s.cam_time_offset || (ii > 0 && d.imu[ii - 1].t <= im.first + s.cam_time_offset))) sys.PushImuData(d.imu[ii++]);
@@ -304,10 +372,12 @@ int main(int argc, char** argv) {
         t_filter += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (rc < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
         if (rc == 1) { ++n_frames; if (out.is_open()) out << format_pose(p); }
+        if (rc == 1 && apply_velocity(sys, vr, image_k) < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     }
     if (sys.flush_odometry() < 0 || sys.flush_imu_odometry() < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     std::fprintf(stderr, "rvio_replay: %ld images, %ld filtered frames, %.3f ms per MonoVIO call (host wall clock, pose read-back included)\n",
                  n_images, n_frames, n_images ? 1e3 * t_filter / n_images : 0.0);
+    if (vr) print_velocity(*vr);
     // anything only the device saw (0 in every test and bench run): said out loud, the poses above are suspect if it is not 0
     const int flags = sys.device_flags();
     if (flags) std::fprintf(stderr, "rvio_replay: DEVICE-SIDE FLAGS %d (1 singular pivot in the solve, 2 a track the window cannot hold was dropped, "

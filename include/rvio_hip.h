@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry) */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag) */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -433,6 +433,60 @@ int rvio_hip_set_imu_odometry(rvio_hip* h, int capacity);
  * oldest first, at most max_n; *n = how many.  `newest` is counted on the host from the m of each call.  Waits for the filter stream only.
  * RVIO_ERR_STATE: the ring was never enabled; RVIO_ERR_INVALID: instance out of range, max_n < 0, out == NULL with max_n > 0. */
 int rvio_hip_get_imu_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_imu_pose* out, int32_t* n);
+
+/* --- auxiliary measurement update (no reference counterpart) ----------------- */
+/* Fuses what is not a camera track — wheel odometry, a zero-velocity update, a speed-over-ground sensor — on the device: at most
+ * RVIO_AUX_MAX_ROWS rows of a measurement the caller has linearised, z = h(x) + noise, with a FULL-WIDTH Jacobian.  The arithmetic of
+ * Updater.cc:540-619 on the whitened rows H~ = H / sigma, v~ = v / sigma (row-wise; R = diag(sigma^2) becomes I):
+ *   S = H~ P H~^T + I,   K = P H~^T S^-1,   dx = K v~,   gamma = v~^T S^-1 v~,   P <- (I - K H~) P (I - K H~)^T + K K^T   (Joseph form)
+ * H: m x d ROW-major, d = 24 + 6 n for the window as it is NOW (rvio_hip_get_state's d).  Its columns are the ERROR-state coordinates in the
+ * order of P: 0-2 rotation of qG, 3-5 pG, 6-8 g, 9-11 rotation of qk, 12-14 pk, 15-17 v (IMU frame), 18-20 bg, 21-23 ba, then per clone p
+ * (oldest first) 24+6p .. 26+6p rotation, 27+6p .. 29+6p position.  State injection is Updater.cc:546-613: q <- QuatMul([dth / 2; sqrt(1 -
+ * |dth / 2|^2)], q) in the three kinds of rotation slots, g re-normalised behind its addition, everything else x <- x + dx.  (An all-zero qk — what
+ * System::initialize leaves until the first composition, read as I by QuatToRot — is injected as the identity it stands for.)  P stays
+ * symmetric bit for bit.
+ * mode: RVIO_AUX_RESIDUAL: v is the residual r = z - h(x), formed by the caller.  RVIO_AUX_VALUE: v is the measured value z of a LINEAR
+ *   measurement of the additive coordinates and the device forms r = z - H xi(x), where xi(x) is x in error-state order with 0 in every rotation
+ *   slot: xi[3..8] = x[4..9], xi[12..23] = x[14..25], xi[27+6p .. 29+6p] = x[30+7p .. 32+7p].  Zero velocity: m = 3, H = I at columns 15..17,
+ *   z = 0; a velocity in the IMU frame: the same with z = v_meas.  No state is read back to form a residual.
+ * gate: 0: always apply; 1: apply iff |gamma| < chi2inv(0.95, m), the table and the comparison of the feature gate (Updater.cc:422).
+ * In place: x and P of the current buffer are updated where they lie (no double-buffer toggle); an instance that is gated out, inactive or
+ * indefinite is not written at all.  The pose line (rvio_hip_get_pose[_at]) is rewritten from the updated state, (pGk, qkG) =
+ * (R(qG)^T (pk - pG), QuatMul(qk, qG)); NO record is appended to the odometry ring or the IMU-rate ring: those stay one record per frame /
+ * per IMU sample.  A clone-block factor kept for the next visual update is dropped (that update factors the new covariance itself).
+ * When: whenever the handle has a state — behind rvio_hip_initialize with an empty window (d = 24), between two whole frames, between the
+ * stage entry points.  RVIO_ERR_STATE: no state yet, or between rvio_hip_frame_begin_dev and rvio_hip_frame_end.
+ * Handle-wide: the window length (hence d) and m, mode, gate of a call; per instance: H, v, sigma (by stride) and whether the call applies.
+ * Plain, batch (with or without front end) and sharded handles alike; a sharded rank holds a replica of the state: call it on every rank
+ * alike, as the calibration setters.  A handle that never calls these allocates and launches what it did before they existed.
+ * A non-positive pivot of S (the covariance handed in was indefinite) sets the sticky device error bit 8 (rvio_frame_info.reserved[0]) and
+ * leaves that instance untouched, applied = 0 — what the feature gate does. */
+#define RVIO_AUX_MAX_ROWS 16
+typedef enum { RVIO_AUX_RESIDUAL = 0, RVIO_AUX_VALUE = 1 } rvio_aux_mode;
+typedef struct rvio_aux_meas {   /* 40 bytes; host pointers */
+    int32_t m;            /* rows, 1 .. RVIO_AUX_MAX_ROWS */
+    int32_t mode;         /* rvio_aux_mode */
+    int32_t gate;         /* 0 | 1 */
+    int32_t reserved;
+    const double* H;      /* m x d row-major */
+    const double* v;      /* m: r (RESIDUAL) or z (VALUE) */
+    const double* sigma;  /* m standard deviations, finite and > 0 */
+} rvio_aux_meas;
+/* Host buffers: checked, staged through a pinned block of the call's own (allocated by the first call, outside the filter slab) and
+ * enqueued on the filter stream; the call does not wait for that stream.  instance: 0 .. B - 1, or -1: every instance, the same measurement.
+ * RVIO_ERR_INVALID: a NULL argument, m or instance out of range, an unknown mode, gate not 0 | 1, a non-finite value in H, v or sigma, a
+ * sigma <= 0, or — VALUE mode — a non-zero entry in a rotation column of H (xi is 0 there, so the residual would silently ignore it). */
+int rvio_hip_update_aux(rvio_hip* h, int instance, const rvio_aux_meas* meas);
+/* Device buffers, EVERY instance in one launch, asynchronous on rvio_hip_stream with no host synchronisation: instance z reads
+ * d_H + z * H_stride, d_v + z * v_stride, d_sigma + z * sigma_stride (strides in doubles; 0: one array shared by all instances, else
+ * H_stride >= m d and the others >= m).  d_active: NULL = all instances, else B flags, 0 = leave that instance untouched (applied = 0).
+ * Values are NOT checked: finite entries, sigma > 0 and — VALUE mode — zero rotation columns of H are the caller's responsibility.
+ * RVIO_ERR_INVALID: a NULL handle, d_H, d_v or d_sigma, m outside 1 .. RVIO_AUX_MAX_ROWS, an unknown mode, gate not 0 | 1, a stride too short. */
+int rvio_hip_update_aux_dev(rvio_hip* h, int m, int mode, int gate, const double* d_H, size_t H_stride, const double* d_v, size_t v_stride,
+                            const double* d_sigma, size_t sigma_stride, const int32_t* d_active);
+/* gamma (as compared: |v~^T S^-1 v~|) and applied (1 applied; 0 gated out, inactive or a bad pivot) of one instance in the LAST call.  Waits
+ * for the filter stream only.  RVIO_ERR_STATE before the first rvio_hip_update_aux* call; RVIO_ERR_INVALID: instance out of range. */
+int rvio_hip_get_aux_diag(rvio_hip* h, int instance, double* gamma, int32_t* applied);
 
 /* --- feature-sharded updater (no reference counterpart) ------ */
 /* Stage A: per-feature build + gate on the features f with f % world == rank,

@@ -231,6 +231,102 @@ def imu_pose_model(cfg, x, imu):
     return out
 
 
+# ---- auxiliary measurement update (rvio_hip_update_aux*, csrc/aux_update.hip)
+RVIO_AUX_MAX_ROWS = 16
+RVIO_AUX_RESIDUAL, RVIO_AUX_VALUE = 0, 1
+
+
+class rvio_aux_meas(C.Structure):
+    """one auxiliary measurement, host pointers: 40 bytes"""
+    _fields_ = [("m", C.c_int32), ("mode", C.c_int32), ("gate", C.c_int32), ("reserved", C.c_int32),
+                ("H", C.POINTER(C.c_double)), ("v", C.POINTER(C.c_double)), ("sigma", C.POINTER(C.c_double))]
+
+
+assert C.sizeof(rvio_aux_meas) == 40
+
+
+def make_aux_meas(H, v, sigma, mode=RVIO_AUX_RESIDUAL, gate=0):
+    """an rvio_aux_meas over contiguous copies of the arrays (kept alive by the struct)"""
+    H = np.ascontiguousarray(np.atleast_2d(np.asarray(H, float)))
+    v, sigma = np.ascontiguousarray(v, float).reshape(-1), np.ascontiguousarray(sigma, float).reshape(-1)
+    assert len(v) == len(sigma) == H.shape[0]
+    dp = C.POINTER(C.c_double)
+    ms = rvio_aux_meas(H.shape[0], int(mode), int(gate), 0, H.ctypes.data_as(dp), v.ctypes.data_as(dp), sigma.ctypes.data_as(dp))
+    ms._keep = (H, v, sigma)
+    return ms
+
+
+def aux_xi(x):
+    """xi(x): the additive state coordinates in error-state order (the column order of P), 0 in every rotation slot"""
+    x = np.asarray(x, float)
+    n = (len(x) - 26) // 7
+    xi = np.zeros(24 + 6 * n)
+    xi[3:9] = x[4:10]
+    xi[12:24] = x[14:26]
+    for p in range(n):
+        xi[27 + 6 * p: 30 + 6 * p] = x[30 + 7 * p: 33 + 7 * p]
+    return xi
+
+
+def small_quat(e):
+    """dq of an error angle (Updater.cc:549-563), JPL xyzw"""
+    q = np.zeros(4)
+    q[:3] = 0.5 * np.asarray(e, float)
+    nrm = math.sqrt(float(q[:3] @ q[:3]))
+    if nrm < 1:
+        q[3] = math.sqrt(1 - nrm * nrm)
+    else:
+        k = 1 / math.sqrt(1 + nrm * nrm)
+        q[:3] *= k
+        q[3] = k
+    return q
+
+
+def inject_state(x, dx):
+    """Updater.cc:546-613: small-angle quaternions on the rotation slots, g re-normalised, the rest additive"""
+    x, dx = np.asarray(x, float), np.asarray(dx, float)
+    n = (len(x) - 26) // 7
+    xo = x.copy()
+    xo[0:4] = quat_mul(small_quat(dx[0:3]), x[0:4])
+    xo[4:10] = dx[3:9] + x[4:10]
+    xo[7:10] = xo[7:10] / math.sqrt(float(xo[7:10] @ xo[7:10]))
+    # (System::initialize leaves qk all zero until the first composition; QuatToRot reads it as I, and the identity is what dq multiplies)
+    xo[10:14] = quat_mul(small_quat(dx[9:12]), x[10:14] if x[10:14].any() else np.array([0.0, 0.0, 0.0, 1.0]))
+    xo[14:26] = dx[12:24] + x[14:26]
+    for p in range(n):
+        a, b = 26 + 7 * p, 24 + 6 * p
+        xo[a: a + 4] = quat_mul(small_quat(dx[b: b + 3]), x[a: a + 4])
+        xo[a + 4: a + 7] = dx[b + 3: b + 6] + x[a + 4: a + 7]
+    return xo
+
+
+def pose_line(x):
+    """(pGk, qkG) of a state (System.cc:339-341): R(qG)^T (pk - pG), QuatMul(qk, qG)"""
+    x = np.asarray(x, float)
+    return quat_to_rot(x[0:4]).T @ (x[14:17] - x[4:7]), quat_mul(x[10:14], x[0:4])
+
+
+def aux_update_model(x, P, H, v, sigma, mode=RVIO_AUX_RESIDUAL):
+    """NumPy model of csrc/aux_update.hip, the arithmetic of Updater.cc:540-619 with a full-width H on whitened rows: returns (x', P', gamma).
+    H: m x d in the error-state order of P; v: the residual (RESIDUAL) or the measured value z (VALUE: r = z - H xi(x)); R = diag(sigma^2).
+    The textbook Joseph form, symmetrised; no gate (the caller compares gamma).  Calls nothing from the library or the oracle."""
+    x, P = np.asarray(x, float), np.asarray(P, float)
+    H = np.atleast_2d(np.asarray(H, float))
+    v, sigma = np.asarray(v, float).reshape(-1), np.asarray(sigma, float).reshape(-1)
+    m, d = H.shape
+    assert P.shape == (d, d) and len(v) == m and len(sigma) == m and len(x) == 26 + 7 * ((d - 24) // 6)
+    r = v - H @ aux_xi(x) if mode == RVIO_AUX_VALUE else v
+    Hw, rw = H / sigma[:, None], r / sigma
+    T = P @ Hw.T
+    S = Hw @ T + np.eye(m)
+    S = 0.5 * (S + S.T)
+    K = np.linalg.solve(S, T.T).T
+    gamma = abs(float(rw @ np.linalg.solve(S, rw)))
+    IKH = np.eye(d) - K @ Hw
+    Pn = IKH @ P @ IKH.T + K @ K.T
+    return inject_state(x, K @ rw), 0.5 * (Pn + Pn.T), gamma
+
+
 # Camera.T_BC0 of config/rvio_euroc.yaml:55-62 (row-major)
 _T_BC0 = [0.0148655429818, -0.999880929698, 0.00414029679422, -0.0216401454975,
           0.999557249008, 0.0149672133247, 0.025715529948, -0.064676986768,

@@ -106,19 +106,40 @@ LP_HD inline size_t lit_diag_end(int ldh, bool stamps) {
 #define LP_IMUP_WAVES (LP_IMUP_T / 64)
 #define LP_IMUP_WAVE_BYTES (16 * 64 * 8)
 #define LP_IMUP_LDS_BYTES (LP_IMUP_WAVES * LP_IMUP_WAVE_BYTES)
+// aux_update_kernel<MB> (aux_update.hip): one workgroup of eight waves per instance.  MB: the row count its register arrays are unrolled for;
+// the T product deals G = ceil(d / 64) row groups x aux_splits(G) column ranges over the waves (G <= 4 at d <= 24 + 6 (RVIO_MAX_LEN - 1)).
+// LDS: H~ (d x MB) | T (d x (MB + 1)) | U | S, L (MB x (MB + 1) each) | 1 / d, v~ (MB each) | xi, dx (d each) | 8, where U holds the partial
+// sums of T (splits x d rows), then those of S, then K and D (2 d rows)
+#define LP_AUX_T 512
+#define LP_AUX_MAX_ROWS 16       // RVIO_AUX_MAX_ROWS
+LP_HD inline int aux_mb(int m) { return m <= 4 ? 4 : 16; }
+LP_HD inline int aux_splits(int G) { return G <= 2 ? 4 : 2; }
+LP_HD inline size_t aux_u_doubles(int d, int MB) {
+    const int S = aux_splits((d + 63) >> 6);
+    return (size_t)(S > 2 ? S : 2) * d * (MB + 1);
+}
+LP_HD inline size_t aux_lds_doubles(int d, int MB) {
+    return (size_t)d * MB + (size_t)d * (MB + 1) + aux_u_doubles(d, MB) + 2 * (size_t)MB * (MB + 1) + 2 * MB + 2 * (size_t)d + 8;
+}
+// the largest footprint over the clone counts 0 .. nmax a handle passes through (not the last one's: the column ranges go from 4 to 2 at d = 129)
+LP_HD inline size_t aux_lds_max_doubles(int nmax, int MB) {
+    size_t w = 0;
+    for (int n = 0; n <= nmax; ++n) { const size_t a = aux_lds_doubles(24 + 6 * n, MB); if (a > w) w = a; }
+    return w;
+}
 
 // ---------------------------------------------------------------- the kernels create_impl gives a dynamic-LDS limit
 enum LpKernel {
     LPK_FEAT_BUILD16, LPK_FEAT_BUILD4, LPK_GRAM_REDUCE, LPK_BLOCK_SUM, LPK_LIT_BATCH, LPK_GEMM_T_LDS, LPK_GRAM_BATCH4, LPK_GRAM_BATCH6, LPK_FEAT_PROP,
     LPK_BOOKKEEP_B, LPK_RANSAC_BOOK, LPK_SOLVE9_SMALL, LPK_SOLVE6_1, LPK_SOLVE6_2, LPK_SOLVE6_3, LPK_JOSEPH_BATCH, LPK_UG, LPK_UG_LDS, LPK_FINAL_LDS,
-    LPK_JOSEPH_LDS, LPK_IMU_POSE, LPK_COUNT
+    LPK_JOSEPH_LDS, LPK_IMU_POSE, LPK_AUX_UPDATE4, LPK_AUX_UPDATE16, LPK_COUNT
 };
 // (as c++filt prints them, without return type and arguments: how the test finds each kernel's static LDS in the code object's notes)
 static const char* const kLpKernelName[LPK_COUNT] = {
     "feat_build_kernel<16>", "feat_build_kernel<4>", "gram_reduce_kernel", "block_sum_kernel", "lit_batch_kernel", "gemm_T_lds_kernel",
     "gram_reduce_batch_kernel<4>", "gram_reduce_batch_kernel<6>", "feat_prop_kernel", "bookkeep_b_kernel", "ransac_book_kernel", "solve9_small_kernel",
     "solve6_kernel<1, 8, 8>", "solve6_kernel<2, 12, 8>", "solve6_kernel<2, 16, 8>", "joseph_batch_kernel", "ug_kernel", "ug_lds_kernel", "final_lds_kernel",
-    "joseph_lds_kernel", "imu_pose_kernel"
+    "joseph_lds_kernel", "imu_pose_kernel", "aux_update_kernel<4>", "aux_update_kernel<16>"
 };
 
 struct LaunchPlan {
@@ -245,6 +266,8 @@ inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size
     p.attr[LPK_FINAL_LDS] = LP_FNL_BYTES;
     p.attr[LPK_JOSEPH_LDS] = LP_JL_BYTES;
     p.attr[LPK_IMU_POSE] = LP_IMUP_LDS_BYTES;
+    p.attr[LPK_AUX_UPDATE4] = aux_lds_max_doubles(nmax, 4) * sizeof(double);      // (what a launch asks for follows the clone count)
+    p.attr[LPK_AUX_UPDATE16] = aux_lds_max_doubles(nmax, 16) * sizeof(double);
     if (batch > 1 && !p.solve5_variant && !p.solve7_variant) { p.rc = 1; p.why = "batched filter: clone window too long for the unrolled solve kernel (6n <= 126)"; return p; }
     // nothing above may ask for more than a CU has: a configuration that would is refused here, by name, not by a failed hipFuncSetAttribute / launch
     for (int k = 0; k < LPK_COUNT; ++k)
@@ -401,6 +424,12 @@ enum {
 struct LpLaunch { int gx = 0, gy = 1, gz = 1, threads = 0; size_t lds = 0; int kernel = LPF_NONE; };   // gx == 0: not launched
 // imu_pose_kernel on `instances` instances (rvio_hip_predict: one; rvio_hip_predict_dev and the IMU-rate ring: the handle's batch)
 LP_HD inline LpLaunch imu_pose_launch(int instances) { return {(instances + LP_IMUP_WAVES - 1) / LP_IMUP_WAVES, 1, 1, LP_IMUP_T, LP_IMUP_LDS_BYTES, LPK_IMU_POSE}; }
+// aux_update_kernel on a window of n clones, m rows: ONE form at every batch size (a batch handle's instance and a plain handle compute the same
+// bits), the kernel instance by the row count, the dynamic LDS by the window as it is now
+LP_HD inline LpLaunch aux_update_launch(int n, int m, int batch) {
+    const int MB = aux_mb(m);
+    return {1, 1, batch, LP_AUX_T, aux_lds_doubles(24 + 6 * n, MB) * sizeof(double), MB == 4 ? LPK_AUX_UPDATE4 : LPK_AUX_UPDATE16};
+}
 
 enum LpStream {          // the ROLE of a stream in a call; stream_of (rvio_hip.hip) maps it to one of the handle's four
     LPR_FILTER,          //   the filter stream: every launch of a per-stage call that is not forked to the side stream

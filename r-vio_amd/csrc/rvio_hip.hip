@@ -25,6 +25,7 @@
 #include "landmarks.hip"   // Updater::update's landmark cloud (rvio_hip_set_landmarks)
 #include "odom.hip"        // the per-frame odometry record: pose, velocity, covariance (rvio_hip_set_odometry)
 #include "imu_pose.hip"    // IMU-rate odometry: a pose per IMU sample (rvio_hip_predict, rvio_hip_set_imu_odometry)
+#include "aux_update.hip"  // the auxiliary measurement update: wheel odometry, zero velocity, speed over ground (rvio_hip_update_aux)
 #pragma clang fp contract(off)
 #include "frontend_kernels.hip"
 #include "klt3.hip"
@@ -179,6 +180,11 @@ struct rvio_hip {
     rvio_imu_pose* pred_out = nullptr;
     int pred_cap = 0;
     bool has_state = false;    // rvio_hip_set_state* / rvio_hip_initialize* has run (rvio_hip_predict* refuses to extrapolate from nothing)
+    // auxiliary measurement update (aux_update.hip), allocated by the first rvio_hip_update_aux* call, outside the slab: (gamma, applied) of the
+    // last call per instance; the host form's pinned staging [H | v | sigma | active flags], its device copy, and the event behind the H2D copy
+    double* aux_diag = nullptr;
+    double *aux_pin = nullptr, *aux_stage = nullptr;
+    hipEvent_t evAux = nullptr;
     // colour input (rvio_hip_set_image_format): the gray images every stage behind gray_kernel reads instead of the caller's.  Allocated with the
     // first colour format, outside the slab (a mono handle keeps its memory layout), instance stride W * H; four in rotation like d_eq2[] (see
     // build_pyramid_dev for who reads a slot last)
@@ -494,6 +500,8 @@ static const void* lp_kernel_fn(int k) {
         case LPK_FINAL_LDS: return (const void*)final_lds_kernel;
         case LPK_JOSEPH_LDS: return (const void*)joseph_lds_kernel;
         case LPK_IMU_POSE: return (const void*)imu_pose_kernel;
+        case LPK_AUX_UPDATE4: return (const void*)aux_update_kernel<4>;
+        case LPK_AUX_UPDATE16: return (const void*)aux_update_kernel<16>;
     }
     return nullptr;
 }
@@ -639,6 +647,10 @@ void rvio_hip_destroy(rvio_hip* h) {
     if (h->imuo_ring) hipFree(h->imuo_ring);
     if (h->pred_imu) hipFree(h->pred_imu);
     if (h->pred_out) hipFree(h->pred_out);
+    if (h->aux_diag) hipFree(h->aux_diag);
+    if (h->aux_stage) hipFree(h->aux_stage);
+    if (h->aux_pin) hipHostFree(h->aux_pin);
+    if (h->evAux) hipEventDestroy(h->evAux);
     for (int k = 0; k < rvio_hip::kPin; ++k) { if (h->pin[k]) hipHostFree(h->pin[k]); if (h->evPin[k]) hipEventDestroy(h->evPin[k]); if (h->evPin2[k]) hipEventDestroy(h->evPin2[k]); }
     if (h->first_mirror) hipHostFree(h->first_mirror);
     if (h->evA) hipEventDestroy(h->evA);
@@ -1392,6 +1404,89 @@ int rvio_hip_get_imu_odometry(rvio_hip* h, int instance, int64_t first_seq, int 
     if (cnt > c0)
         HIPCHK(h, hipMemcpy2DAsync(out + c0, sizeof(rvio_imu_pose), h->imuo_ring + instance, pitch, sizeof(rvio_imu_pose), (size_t)(cnt - c0), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RVIO_OK;
+}
+
+// ------------------------------------------------------------------ auxiliary measurement update (aux_update.hip)
+static_assert(LP_AUX_MAX_ROWS == RVIO_AUX_MAX_ROWS, "launch_plan.h: the row limit of the auxiliary update");
+// strides in doubles (0: shared).  Asynchronous on the filter stream: in place on x[cur] / P[cur], no toggle
+static int update_aux_dev(rvio_hip* h, int m, int mode, int gate, const double* d_H, size_t H_stride, const double* d_v, size_t v_stride,
+                          const double* d_sigma, size_t sigma_stride, const int32_t* d_active) {
+    if (!h->has_state) { h->err = "rvio_hip_update_aux before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
+    if (h->in_frame) { h->err = "rvio_hip_update_aux between rvio_hip_frame_begin_dev and rvio_hip_frame_end"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->aux_diag) {
+        HIPCHK(h, hipMalloc((void**)&h->aux_diag, sizeof(double) * 2 * (size_t)h->batch));
+        HIPCHK(h, hipMemsetAsync(h->aux_diag, 0, sizeof(double) * 2 * (size_t)h->batch, h->stream));
+    }
+    // a factor of the clone block in flight on the side queue reads the covariance that is about to change; one in the slab belongs to the old one
+    if (h->chol_async) { HIPCHK(h, hipStreamWaitEvent(h->stream, h->evL, 0)); h->chol_async = false; }
+    h->chol_ready = false;
+    const int n = h->n_clones_host;
+    const LpLaunch l = aux_update_launch(n, m, h->batch);
+    const size_t w = sizeof(double);
+    if (l.kernel == LPK_AUX_UPDATE4)
+        hipLaunchKernelGGL(aux_update_kernel<4>, lp_grid(l), lp_block(l), l.lds, h->stream, n, h->dc.dmax, m, mode, gate, h->x[h->cur], h->P[h->cur], h->d_pose, h->meta,
+                           h->slab_bytes, d_H, H_stride * w, d_v, v_stride * w, d_sigma, sigma_stride * w, (const int*)d_active, h->aux_diag);
+    else
+        hipLaunchKernelGGL(aux_update_kernel<16>, lp_grid(l), lp_block(l), l.lds, h->stream, n, h->dc.dmax, m, mode, gate, h->x[h->cur], h->P[h->cur], h->d_pose, h->meta,
+                           h->slab_bytes, d_H, H_stride * w, d_v, v_stride * w, d_sigma, sigma_stride * w, (const int*)d_active, h->aux_diag);
+    HIPCHK(h, hipGetLastError());
+    return RVIO_OK;
+}
+int rvio_hip_update_aux_dev(rvio_hip* h, int m, int mode, int gate, const double* d_H, size_t H_stride, const double* d_v, size_t v_stride,
+                            const double* d_sigma, size_t sigma_stride, const int32_t* d_active) {
+    if (!h || !d_H || !d_v || !d_sigma || m < 1 || m > RVIO_AUX_MAX_ROWS || (mode != RVIO_AUX_RESIDUAL && mode != RVIO_AUX_VALUE) || (gate != 0 && gate != 1))
+        return RVIO_ERR_INVALID;
+    const size_t d = 24 + 6 * (size_t)h->n_clones_host;
+    if ((H_stride && H_stride < (size_t)m * d) || (v_stride && v_stride < (size_t)m) || (sigma_stride && sigma_stride < (size_t)m)) return RVIO_ERR_INVALID;
+    return update_aux_dev(h, m, mode, gate, d_H, H_stride, d_v, v_stride, d_sigma, sigma_stride, d_active);
+}
+// host buffers: checked here, packed into the pinned block once the copy of the previous call has left it, copied and consumed on the filter
+// stream — no wait for the stream itself
+int rvio_hip_update_aux(rvio_hip* h, int instance, const rvio_aux_meas* meas) {
+    if (!h || !meas || !meas->H || !meas->v || !meas->sigma || instance < -1 || instance >= h->batch) return RVIO_ERR_INVALID;
+    const int m = meas->m, n = h->n_clones_host, d = 24 + 6 * n;
+    if (m < 1 || m > RVIO_AUX_MAX_ROWS || (meas->mode != RVIO_AUX_RESIDUAL && meas->mode != RVIO_AUX_VALUE) || (meas->gate != 0 && meas->gate != 1)) return RVIO_ERR_INVALID;
+    for (int r = 0; r < m; ++r) {
+        if (!std::isfinite(meas->v[r]) || !std::isfinite(meas->sigma[r]) || !(meas->sigma[r] > 0)) { h->err = "rvio_hip_update_aux: a residual is not finite or a sigma is not finite and > 0"; return RVIO_ERR_INVALID; }
+        for (int c = 0; c < d; ++c) {
+            const double e = meas->H[(size_t)r * d + c];
+            if (!std::isfinite(e)) { h->err = "rvio_hip_update_aux: H holds a non-finite value"; return RVIO_ERR_INVALID; }
+            const bool rot = c < 3 || (c >= 9 && c < 12) || (c >= 24 && (c - 24) % 6 < 3);
+            if (meas->mode == RVIO_AUX_VALUE && rot && e != 0.0) { h->err = "rvio_hip_update_aux: VALUE mode with a non-zero entry in a rotation column of H (xi is 0 there: linearise and use RESIDUAL mode)"; return RVIO_ERR_INVALID; }
+        }
+    }
+    if (!h->has_state) { h->err = "rvio_hip_update_aux before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
+    if (h->in_frame) { h->err = "rvio_hip_update_aux between rvio_hip_frame_begin_dev and rvio_hip_frame_end"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t nH = (size_t)RVIO_AUX_MAX_ROWS * h->dc.dmax, nd = nH + 2 * RVIO_AUX_MAX_ROWS, bytes = nd * sizeof(double) + sizeof(int32_t) * (size_t)h->batch;
+    if (!h->aux_pin) {
+        HIPCHK(h, hipHostMalloc((void**)&h->aux_pin, bytes, hipHostMallocDefault));
+        HIPCHK(h, hipMalloc((void**)&h->aux_stage, bytes));
+        HIPCHK(h, hipEventCreateWithFlags(&h->evAux, hipEventDisableTiming));
+    } else HIPCHK(h, hipEventSynchronize(h->evAux));
+    std::memcpy(h->aux_pin, meas->H, sizeof(double) * (size_t)m * d);
+    std::memcpy(h->aux_pin + nH, meas->v, sizeof(double) * m);
+    std::memcpy(h->aux_pin + nH + RVIO_AUX_MAX_ROWS, meas->sigma, sizeof(double) * m);
+    int32_t* act = (int32_t*)(h->aux_pin + nd);
+    for (int i = 0; i < h->batch; ++i) act[i] = (instance < 0 || i == instance) ? 1 : 0;
+    HIPCHK(h, hipMemcpyAsync(h->aux_stage, h->aux_pin, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->evAux, h->stream));
+    return update_aux_dev(h, m, meas->mode, meas->gate, h->aux_stage, 0, h->aux_stage + nH, 0, h->aux_stage + nH + RVIO_AUX_MAX_ROWS, 0,
+                          instance < 0 ? (const int32_t*)nullptr : (const int32_t*)(h->aux_stage + nd));
+}
+// (gamma, applied) of the last rvio_hip_update_aux* call; waits for the filter stream only, like rvio_hip_get_pose
+int rvio_hip_get_aux_diag(rvio_hip* h, int instance, double* gamma, int32_t* applied) {
+    if (!h || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
+    if (!h->aux_diag) { h->err = "rvio_hip_get_aux_diag before the first rvio_hip_update_aux"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    double buf[2];
+    HIPCHK(h, hipMemcpyAsync(buf, h->aux_diag + 2 * (size_t)instance, sizeof buf, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    long long ap; std::memcpy(&ap, &buf[1], sizeof ap);
+    if (gamma) *gamma = buf[0];
+    if (applied) *applied = (int32_t)ap;
     return RVIO_OK;
 }
 

@@ -29,6 +29,7 @@ SYMBOLS = [
     "rvio_hip_set_odometry", "rvio_hip_get_odometry", "rvio_hip_get_odometry_all", "rvio_hip_get_pose_at",
     "rvio_calibration_from_config", "rvio_hip_set_calibration_at", "rvio_hip_set_calibrations", "rvio_hip_get_calibration_at", "rvio_hip_initialize_at",
     "rvio_hip_predict", "rvio_hip_predict_dev", "rvio_hip_set_imu_odometry", "rvio_hip_get_imu_odometry",
+    "rvio_hip_update_aux", "rvio_hip_update_aux_dev", "rvio_hip_get_aux_diag",
 ]
 
 _LIB = None
@@ -518,3 +519,22 @@ class RvioHip:
         self._ck(self.L.rvio_hip_get_imu_odometry(self.h, int(instance), C.c_int64(int(first_seq)), cap,
                                                   out.ctypes.data_as(C.POINTER(abi.ImuPose)) if len(out) else None, C.byref(n)), "get_imu_odometry")
         return out[: n.value].copy()
+
+    # ---- auxiliary measurement update (Updater.cc:540-619 with a full-width H)
+    def update_aux(self, H, v, sigma, mode=abi.RVIO_AUX_RESIDUAL, gate=0, instance=-1):
+        """fuse m <= 16 rows (H: m x d in the error-state order of P, R = diag(sigma^2)) into (x, P) in place on the device; mode VALUE: v is the
+        measured value and the device forms v - H xi(x); gate: apply iff gamma < chi2_95(m); instance -1: every instance.  Asynchronous."""
+        ms = abi.make_aux_meas(H, v, sigma, mode, gate)
+        self._ck(self.L.rvio_hip_update_aux(self.h, int(instance), C.byref(ms)), "update_aux")
+
+    def update_aux_dev(self, m, mode, gate, d_H_ptr, H_stride, d_v_ptr, v_stride, d_sigma_ptr, sigma_stride, d_active_ptr=None):
+        """the same on device buffers for every instance in one launch (strides in doubles, 0: shared; d_active: B int32 flags or None)"""
+        self._ck(self.L.rvio_hip_update_aux_dev(self.h, int(m), int(mode), int(gate), C.c_void_p(d_H_ptr), C.c_size_t(int(H_stride)), C.c_void_p(d_v_ptr),
+                                                C.c_size_t(int(v_stride)), C.c_void_p(d_sigma_ptr), C.c_size_t(int(sigma_stride)),
+                                                C.c_void_p(d_active_ptr) if d_active_ptr else None), "update_aux_dev")
+
+    def aux_diag(self, instance=0):
+        """(gamma, applied) of one instance in the last update_aux* call"""
+        g, a = C.c_double(0), C.c_int32(0)
+        self._ck(self.L.rvio_hip_get_aux_diag(self.h, int(instance), C.byref(g), C.byref(a)), "get_aux_diag")
+        return float(g.value), int(a.value)
