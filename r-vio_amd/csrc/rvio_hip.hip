@@ -16,6 +16,7 @@
 
 #include "../../include/rvio_hip.h"
 #include "rvio_dev.h"
+#include "ring_span.h"
 #include "frontend_dev.h"
 #include "filter_kernels.hip"
 #include "filter_kernels2.hip"
@@ -35,6 +36,18 @@
 #include "gray.hip"        // Tracker.cc:182-196 for colour cameras (rvio_hip_set_image_format)
 #include "raw.hip"         // ... and for 16-bit and Bayer cameras: cv_bridge's conversion to MONO8 (rvio_mono.cc:64)
 #pragma clang fp contract(fast)
+
+// A ring of records on the device, laid out as ring_span.h states (ring[(seq - 1) % cap][instance]); the operations on it follow the handle:
+// ring_set_capacity, ring_read
+template <typename T>
+struct DevRing {
+    const char *noun, *setter;   // for the error messages: "odometry", "rvio_hip_set_odometry"
+    T* ring = nullptr;
+    int cap = 0;           // records per instance the ring holds
+    bool on = false;       // the launches that write it run
+    long long seq = 0;     // records written since create / rvio_hip_initialize / the last change of capacity: the newest record's seq
+    T* slot(long long s, int batch) const { return ring + ring_index(s, cap, batch); }   // the `batch` records of seq s
+};
 
 struct rvio_hip {
     rvio_config cfg;
@@ -76,7 +89,8 @@ struct rvio_hip {
     StageSync* stage_sync = nullptr;   // device-side completion counter of the filter chain (aug) and the value it reaches after the launches so far
     StageSync stage_tgt = {};
     double* S9scr = nullptr;     // solve9's slab of tiles in L2 (plan.solve9_nt != 0): 5 NT^2 x 256 doubles (+ the verdict of the Cholesky role)
-    bool chol_ready = false;     // the slab holds L, G of the clone block the next solve will see (written by the role workgroup of the per-feature / propagate launch)
+    bool chol_ready = false;     // the slab holds L, G of the clone block the next solve will see (written by the role workgroup of the per-feature / propagate launch).
+                                 // chol_ready / chol_async: touched by the chol_* functions only, see the rule above them
     float* eig_map = nullptr;    // W x H min-eigenvalue map of rvio_hip_get_corners(eig): allocated on first use
     // staging
     rvio_imu* d_imu = nullptr;
@@ -135,7 +149,10 @@ struct rvio_hip {
     TrackerDev t;
     PyrDev pyr[4];   // four in rotation: pyramid(k) (image stream, run-ahead) may be built while KLT(k-2), KLT(k-1) still match the others
     int pyr_cur = 0;
-    std::vector<void*> allocs;
+    // Everything allocated outside the slab — the slab itself, the on-demand buffers of the features, pinned staging, their events — belongs to
+    // this registry (own_dev / own_pinned / own_event, own_replace, own_release); rvio_hip_destroy walks it, no member is freed by name
+    struct Owned { void* p; int kind; };   // kind: OWN_DEV | OWN_PINNED | OWN_EVENT
+    std::vector<Owned> owned;
     // filter slab: the filter state, the update scratch and the Tracker -> Updater hand-over of ONE instance are carved from one
     // slab; a batch handle (rvio_hip_create_batch) owns `batch` slabs back to back and launches every filter kernel with
     // gridDim.z = batch (rvio_dev.h zoff)
@@ -163,17 +180,11 @@ struct rvio_hip {
     int lm_frame = -1;       // nImageCountAfterInit when the update behind the cloud was enqueued, -1: none since create / initialize
     LmOut lm = {nullptr, nullptr, nullptr, nullptr, 0};
     // odometry ring (odom_kernel behind every augment/compose stage): allocated by rvio_hip_set_odometry, outside the slab (a handle that never
-    // enables it keeps its memory layout and its launches), laid out ring[(seq - 1) % odom_cap][instance]
-    rvio_odom* odom_ring = nullptr;
-    int odom_cap = 0;          // records per instance the ring holds
-    bool odom_on = false;
-    long long odom_seq = 0;    // records written since create / rvio_hip_initialize / the last change of capacity: the newest record's seq
-    // IMU-rate ring (imu_pose_kernel in front of whatever propagates in place): allocated by rvio_hip_set_imu_odometry, outside the slab, laid
-    // out ring[(seq - 1) % imuo_cap][instance]; imuo_seq counts the samples recorded (the m of every propagate while the ring is on)
-    rvio_imu_pose* imuo_ring = nullptr;
-    int imuo_cap = 0;
-    bool imuo_on = false;
-    long long imuo_seq = 0;
+    // enables it keeps its memory layout and its launches)
+    DevRing<rvio_odom> odom{"odometry", "rvio_hip_set_odometry"};
+    // IMU-rate ring (imu_pose_kernel in front of whatever propagates in place): allocated by rvio_hip_set_imu_odometry, outside the slab;
+    // imuo.seq counts the samples recorded (the m of every propagate while the ring is on)
+    DevRing<rvio_imu_pose> imuo{"IMU-rate odometry", "rvio_hip_set_imu_odometry"};
     size_t time_imu_bs = 0;    // instance stride of time_imu (rvio_hip_debug_time_kernel(13))
     // staging of rvio_hip_predict (host in / host out), allocated by its first call, outside the slab: samples in, records out
     rvio_imu* pred_imu = nullptr;
@@ -241,9 +252,72 @@ static unsigned ev_flags() { return (paranoid_bits() & PAR_SYSFENCE) ? hipEventD
         }                                                                                        \
     } while (0)
 
+// a step that returns an RVIO_* code of its own (and has set h->err): pass a failure on
+#define RCCHK(call)                                   \
+    do {                                              \
+        const int rc_ = (call);                       \
+        if (rc_ != RVIO_OK) return rc_;               \
+    } while (0)
+
+// ---------------------------------------------------------------- the registry of what the handle owns outside the slab (rvio_hip::owned).
+// Each allocation writes *p only when it has succeeded, so a set-up of several parts allocates into locals and commits its members last.
+enum { OWN_DEV, OWN_PINNED, OWN_EVENT };
+// a device block; zero: cleared on the filter stream (the caller waits for that stream before another stream uses the block)
+template <typename T>
+static int own_dev(rvio_hip* h, T** p, size_t bytes, bool zero = false) {
+    void* q = nullptr;
+    HIPCHK(h, hipMalloc(&q, bytes));
+    h->owned.push_back({q, OWN_DEV});
+    if (zero) HIPCHK(h, hipMemsetAsync(q, 0, bytes, h->stream));
+    *p = (T*)q;
+    return RVIO_OK;
+}
+template <typename T>
+static int own_pinned(rvio_hip* h, T** p, size_t bytes, unsigned flags = hipHostMallocDefault) {
+    void* q = nullptr;
+    HIPCHK(h, hipHostMalloc(&q, bytes, flags));
+    h->owned.push_back({q, OWN_PINNED});
+    *p = (T*)q;
+    return RVIO_OK;
+}
+static int own_event(rvio_hip* h, hipEvent_t* e, unsigned flags) {
+    hipEvent_t q = nullptr;
+    HIPCHK(h, hipEventCreateWithFlags(&q, flags));
+    h->owned.push_back({(void*)q, OWN_EVENT});
+    *e = q;
+    return RVIO_OK;
+}
+static void own_free(const rvio_hip::Owned& o) {
+    if (o.kind == OWN_DEV) (void)hipFree(o.p);
+    else if (o.kind == OWN_PINNED) (void)hipHostFree(o.p);
+    else (void)hipEventDestroy((hipEvent_t)o.p);
+}
+// frees a block / destroys an event NOW: the caller knows that nothing in flight uses it.  nullptr: nothing to do
+static void own_release(rvio_hip* h, void* p) {
+    for (auto it = h->owned.begin(); it != h->owned.end(); ++it)
+        if (it->p == p) { own_free(*it); h->owned.erase(it); return; }
+}
+// a block of another size in the place of *p: the new one first (a failure leaves *p as it was), then the old one is freed
+template <typename T>
+static int own_replace(rvio_hip* h, T** p, size_t bytes) {
+    T* const old = *p;
+    RCCHK(own_dev(h, p, bytes));
+    own_release(h, old);
+    return RVIO_OK;
+}
+// Registry entries that live as long as one call (the temporaries of the debug hooks): released when the scope ends, on every path out of it
+// — behind a wait for the filter stream, on which the hooks use them
+struct OwnedScope {
+    rvio_hip* h;
+    std::vector<void*> held;
+    explicit OwnedScope(rvio_hip* h_) : h(h_) {}
+    template <typename T> int dev(T** p, size_t bytes) { const int rc = own_dev(h, p, bytes); if (rc == RVIO_OK) held.push_back(*p); return rc; }
+    int event(hipEvent_t* e, unsigned flags) { const int rc = own_event(h, e, flags); if (rc == RVIO_OK) held.push_back(*e); return rc; }
+    ~OwnedScope() { (void)hipStreamSynchronize(h->stream); for (void* p : held) own_release(h, p); }
+};
+
 template <typename T>
 static int dalloc(rvio_hip* h, T** p, size_t n) {
-    void* q = nullptr;
     size_t bytes = n * sizeof(T);
     if (bytes == 0) bytes = 16;
     if (h->slab_mode) {   // bump allocation inside the filter slab (first pass, slab == nullptr: sizes only)
@@ -251,11 +325,7 @@ static int dalloc(rvio_hip* h, T** p, size_t n) {
         h->slab_off += (bytes + 255) & ~(size_t)255;
         return RVIO_OK;
     }
-    HIPCHK(h, hipMalloc(&q, bytes));
-    HIPCHK(h, hipMemsetAsync(q, 0, bytes, h->stream));
-    h->allocs.push_back(q);
-    *p = (T*)q;
-    return RVIO_OK;
+    return own_dev(h, p, bytes, true);
 }
 // entry points that address ONE instance's front end (a batch handle is driven by rvio_hip_frame_batch_dev / _frame_tracks_dev)
 #define FRONT_END_ONLY(h)                                                                                              \
@@ -268,11 +338,7 @@ static int dalloc(rvio_hip* h, T** p, size_t n) {
         if ((h)->stream_d) HIPCHK(h, hipStreamSynchronize((h)->stream_d));                \
         HIPCHK(h, hipStreamSynchronize((h)->stream_t));                                   \
     } while (0)
-#define DALLOC(h, p, n)                               \
-    do {                                              \
-        int rc_ = dalloc((h), &(p), (n));             \
-        if (rc_ != RVIO_OK) return rc_;               \
-    } while (0)
+#define DALLOC(h, p, n) RCCHK(dalloc((h), &(p), (n)))
 
 extern "C" {
 
@@ -562,20 +628,20 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
     // measured: cfg C 3.2 k frames/s instead of 3.9 k — the command processor time-slices beyond four busy queues.
     if (plan.chol_queue) {
         h->stream_l = h->stream_c;
-        HIPCHK(h, hipEventCreateWithFlags(&h->evA, kEvFlags));
-        HIPCHK(h, hipEventCreateWithFlags(&h->evL, kEvFlags));
+        RCCHK(own_event(h, &h->evA, kEvFlags));
+        RCCHK(own_event(h, &h->evL, kEvFlags));
     }
-    HIPCHK(h, hipEventCreateWithFlags(&h->evD0, kEvFlags));
-    HIPCHK(h, hipEventCreateWithFlags(&h->evD1, kEvFlags));
-    for (int b = 0; b < rvio_hip::kIC; ++b) HIPCHK(h, hipEventCreateWithFlags(&h->evC[b], kEvFlags));
+    RCCHK(own_event(h, &h->evD0, kEvFlags));
+    RCCHK(own_event(h, &h->evD1, kEvFlags));
+    for (int b = 0; b < rvio_hip::kIC; ++b) RCCHK(own_event(h, &h->evC[b], kEvFlags));
     for (int b = 0; b < 2; ++b) {
-        HIPCHK(h, hipEventCreateWithFlags(&h->evT[b], kEvFlags));
-        HIPCHK(h, hipEventCreateWithFlags(&h->evT[b + 2], kEvFlags));
-        HIPCHK(h, hipEventCreateWithFlags(&h->evH[b], kEvFlags));
-        HIPCHK(h, hipEventCreateWithFlags(&h->evH[b + 2], kEvFlags));
-        HIPCHK(h, hipEventCreateWithFlags(&h->evF[b], kEvFlags));
-        HIPCHK(h, hipEventCreateWithFlags(&h->evF[b + 2], kEvFlags));
-        HIPCHK(h, hipEventCreateWithFlags(&h->evIn[b], kEvFlags));
+        RCCHK(own_event(h, &h->evT[b], kEvFlags));
+        RCCHK(own_event(h, &h->evT[b + 2], kEvFlags));
+        RCCHK(own_event(h, &h->evH[b], kEvFlags));
+        RCCHK(own_event(h, &h->evH[b + 2], kEvFlags));
+        RCCHK(own_event(h, &h->evF[b], kEvFlags));
+        RCCHK(own_event(h, &h->evF[b + 2], kEvFlags));
+        RCCHK(own_event(h, &h->evIn[b], kEvFlags));
     }
     if (front_end && cfg->enable_equalizer) {   // CLAHE(3.0, 5x5), Tracker.cc:198-202
         h->cl_tx = 5; h->cl_ty = 5;
@@ -593,11 +659,8 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
     if (front_end) { int rc = alloc_frontend_slab(h); if (rc != RVIO_OK) return rc; }
     h->slab_bytes = h->slab_off;
     {
-        void* q = nullptr;
-        HIPCHK(h, hipMalloc(&q, h->slab_bytes * (size_t)batch));
-        HIPCHK(h, hipMemsetAsync(q, 0, h->slab_bytes * (size_t)batch, h->stream));
-        h->allocs.push_back(q);
-        h->slab = (char*)q; h->slab_off = 0;
+        RCCHK(own_dev(h, &h->slab, h->slab_bytes * (size_t)batch, true));
+        h->slab_off = 0;
     }
     { int rc = alloc_filter_slab(h); if (rc != RVIO_OK) return rc; }
     if (front_end) { int rc = alloc_frontend_slab(h); if (rc != RVIO_OK) return rc; }
@@ -607,7 +670,7 @@ static int create_impl(const rvio_config* cfg, int device, int batch, bool front
     t.info = h->d_info;
     t.first_host = nullptr;
     if (front_end) {
-        HIPCHK(h, hipHostMalloc((void**)&h->first_mirror, sizeof(int) * (size_t)batch, hipHostMallocMapped));
+        RCCHK(own_pinned(h, &h->first_mirror, sizeof(int) * (size_t)batch, hipHostMallocMapped));
         for (int i = 0; i < batch; ++i) h->first_mirror[i] = 1;
         void* dp_ = nullptr;
         HIPCHK(h, hipHostGetDevicePointer(&dp_, h->first_mirror, 0));
@@ -642,27 +705,9 @@ void rvio_hip_destroy(rvio_hip* h) {
     if (h->stream_t) hipStreamSynchronize(h->stream_t);
     if (h->stream) hipStreamSynchronize(h->stream);
     if (h->private_queues) g_private_queue_handles.fetch_sub(1);
-    for (void* p : h->allocs) hipFree(p);
-    if (h->odom_ring) hipFree(h->odom_ring);
-    if (h->imuo_ring) hipFree(h->imuo_ring);
-    if (h->pred_imu) hipFree(h->pred_imu);
-    if (h->pred_out) hipFree(h->pred_out);
-    if (h->aux_diag) hipFree(h->aux_diag);
-    if (h->aux_stage) hipFree(h->aux_stage);
-    if (h->aux_pin) hipHostFree(h->aux_pin);
-    if (h->evAux) hipEventDestroy(h->evAux);
-    for (int k = 0; k < rvio_hip::kPin; ++k) { if (h->pin[k]) hipHostFree(h->pin[k]); if (h->evPin[k]) hipEventDestroy(h->evPin[k]); if (h->evPin2[k]) hipEventDestroy(h->evPin2[k]); }
-    if (h->first_mirror) hipHostFree(h->first_mirror);
-    if (h->evA) hipEventDestroy(h->evA);
-    if (h->evL) hipEventDestroy(h->evL);
-    if (h->evD0) hipEventDestroy(h->evD0);
-    if (h->evD1) hipEventDestroy(h->evD1);
+    for (const rvio_hip::Owned& o : h->owned) own_free(o);   // the slab, every event, everything allocated on demand (the streams are idle)
     if (h->stream_d) hipStreamDestroy(h->stream_d);
     if (h->stream_c) hipStreamDestroy(h->stream_c);
-    for (int b = 0; b < rvio_hip::kIC; ++b) if (h->evC[b]) hipEventDestroy(h->evC[b]);
-    for (int b = 0; b < 4; ++b) { if (h->evT[b]) hipEventDestroy(h->evT[b]); if (h->evH[b]) hipEventDestroy(h->evH[b]); }
-    for (int b = 0; b < rvio_hip::kHand; ++b) if (h->evF[b]) hipEventDestroy(h->evF[b]);
-    for (int b = 0; b < 2; ++b) if (h->evIn[b]) hipEventDestroy(h->evIn[b]);
     if (h->stream_t) hipStreamDestroy(h->stream_t);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -691,6 +736,38 @@ int rvio_hip_sync(rvio_hip* h) {
     return RVIO_OK;
 }
 
+// ------------------------------------------------------------------ the cached factor of the clone block
+// solve9 can start from a Cholesky factor of P's clone block that was computed ahead of the solve and lies in the solve9 slab (S9scr):
+//   chol_ready   a role workgroup of a launch already on the filter stream writes it (6n <= 96): stream order puts it in front of the solve
+//   chol_async   it was queued on stream_l behind augment/compose (6n > 96) and evL is recorded behind it: the solve waits for evL
+// THE RULE: whoever writes P's clone block in place (anything but propagate, which leaves that block alone), replaces P, or rewrites the
+// slab calls chol_drop() in front of the write — or the next solve at 6n > 96 starts from the factor of another matrix, silently.  chol_drop
+// says how a factor still in flight on stream_l is awaited, because it READS the covariance that is about to change.
+// No other code touches the two flags.
+static void chol_role(rvio_hip* h, bool writes) { h->chol_ready = writes; }   // the launch just enqueued: its role workgroup writes the factor (false: it has none)
+static void chol_queued(rvio_hip* h) { h->chol_async = true; }                // the factor was just enqueued on stream_l, evL behind it
+//   CHOL_FILTER_WAITS   the writer is enqueued on the filter stream: that stream waits for evL
+//   CHOL_HOST_WAITS     the writer runs on the host's schedule: the host waits for stream_l
+//   CHOL_DRAINED        the caller has drained every stream of the handle
+enum CholAwait { CHOL_FILTER_WAITS, CHOL_HOST_WAITS, CHOL_DRAINED };
+static int chol_drop(rvio_hip* h, CholAwait how) {
+    if (h->chol_async) {
+        if (how == CHOL_FILTER_WAITS) HIPCHK(h, hipStreamWaitEvent(h->stream, h->evL, 0));
+        else if (how == CHOL_HOST_WAITS) HIPCHK(h, hipStreamSynchronize(h->stream_l));
+        h->chol_async = false;
+    }
+    h->chol_ready = false;
+    return RVIO_OK;
+}
+// Take it for the solve: is a factor of the clone block in the slab, or about to be (stream_l: the solve waits for it; a failed wait: the
+// solve factors Pcc itself)?  The solve behind this call consumes it.
+static bool take_chol(rvio_hip* h) {
+    if (h->chol_async && hipStreamWaitEvent(h->stream, h->evL, 0) != hipSuccess) { h->chol_async = false; h->chol_ready = false; }
+    const bool pre = h->chol_ready || h->chol_async;
+    h->chol_ready = false; h->chol_async = false;
+    return pre;
+}
+
 // ------------------------------------------------------------------ state
 static int set_state_range(rvio_hip* h, int lo, int hi, const double* x, int xdim, const double* P, int d) {
     if (!h || !x || !P) return RVIO_ERR_INVALID;
@@ -699,7 +776,7 @@ static int set_state_range(rvio_hip* h, int lo, int hi, const double* x, int xdi
     HIPCHK(h, hipSetDevice(h->device));
     FilterMeta m; std::memset(&m, 0, sizeof m);
     m.n_clones = n; m.img_count = h->img_count;
-    if (h->chol_async) { HIPCHK(h, hipStreamSynchronize(h->stream_l)); h->chol_async = false; }   // (a factor in flight reads the covariance that is about to be replaced)
+    RCCHK(chol_drop(h, CHOL_HOST_WAITS));   // (the covariance is about to be replaced)
     for (int i = lo; i < hi; ++i) {
         const size_t o = (size_t)i * h->slab_bytes;
         double* Pi = (double*)((char*)h->P[h->cur] + o);
@@ -710,7 +787,6 @@ static int set_state_range(rvio_hip* h, int lo, int hi, const double* x, int xdi
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->n_clones_host = n;
-    h->chol_ready = false;   // (the slab's factor belongs to the covariance that was just replaced)
     h->has_state = true;
     return RVIO_OK;
 }
@@ -780,8 +856,8 @@ int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n
     initial_state(h->cfg, w, a, n_imu, x, P);
     h->img_count = 0;
     h->lm_frame = -1;   // no cloud since initialisation (the enable flag stays)
-    h->odom_seq = 0;    // ... and no odometry record: seq restarts at 1 (the getters read nothing beyond odom_seq)
-    h->imuo_seq = 0;    // ... nor an IMU-rate record
+    h->odom.seq = 0;    // ... and no odometry record: seq restarts at 1 (the getters read nothing beyond seq)
+    h->imuo.seq = 0;    // ... nor an IMU-rate record
     // a (re-)initialised filter starts with an empty window: the tracker starts over too (mbIsTheFirstImage, Tracker.cc:88), or its
     // histories would be longer than the window they refer to
     if (h->front_end) {
@@ -833,12 +909,7 @@ static int set_calibration_range(rvio_hip* h, int lo, int hi, const rvio_calibra
         if (!calibration_ok(src + (i - lo))) { h->err = "calibration of instance " + std::to_string(i) + ": a non-finite member, or fx / fy = 0"; return RVIO_ERR_INVALID; }
     { const int rc = drain_all(h); if (rc != RVIO_OK) return rc; }
     const bool fresh = !h->cal;
-    if (fresh) {
-        CamCal* p = nullptr;
-        HIPCHK(h, hipMalloc((void**)&p, sizeof(CamCal) * (size_t)h->batch));
-        h->allocs.push_back(p);
-        h->cal = p;
-    }
+    if (fresh) RCCHK(own_dev(h, &h->cal, sizeof(CamCal) * (size_t)h->batch));
     for (int i = lo; i < hi; ++i) h->cals[(size_t)i] = src[i - lo];
     const int first = fresh ? 0 : lo, last = fresh ? h->batch : hi;
     std::vector<CamCal> dev((size_t)(last - first));
@@ -866,21 +937,21 @@ int rvio_hip_get_calibration_at(rvio_hip* h, int instance, rvio_calibration* c) 
 // that list long.  The kernels take any m (propagate and RANSAC's gyro prior walk the samples in chunks); what is sized is the staging of
 // the HOST-buffer entry points: RVIO_HIP_MAX_IMU samples are allocated up front, a longer batch grows it once (the host waits for the
 // handle's streams, allocates, goes on) instead of being refused.
+// the pinned ring of rvio_hip_frame is laid out for one image size and IMU capacity: when either changes (on a drained handle) its blocks go,
+// and the next rvio_hip_frame allocates them again (the events stay)
+static void drop_pin_ring(rvio_hip* h) {
+    for (int k = 0; k < rvio_hip::kPin; ++k) { own_release(h, h->pin[k]); h->pin[k] = nullptr; }
+}
 static int ensure_imu_capacity(rvio_hip* h, int m) {
     if (m <= h->imu_cap) return RVIO_OK;
     int rc = drain_all(h);   // (an earlier device-side error stays visible through rvio_hip_sync / rvio_hip_get_frame_info)
     if (rc != RVIO_OK) return rc;
     const int cap = std::max(2 * h->imu_cap, (m + 63) & ~63);
-    auto grow = [&](rvio_imu** p) -> int {
-        void* q = nullptr;
-        HIPCHK(h, hipMalloc(&q, sizeof(rvio_imu) * (size_t)cap));
-        h->allocs.push_back(q);      // (the old block stays where it was — a slab member, or a block freed with the handle)
-        *p = (rvio_imu*)q;
-        return RVIO_OK;
-    };
+    // (the old block stays where it was — a slab member, or a block freed with the handle)
+    auto grow = [&](rvio_imu** p) { return own_dev(h, p, sizeof(rvio_imu) * (size_t)cap); };
     if ((rc = grow(&h->d_imu)) != RVIO_OK) return rc;
     for (int k = 0; k <= rvio_hip::kHand; ++k) if (h->hb_imu[k] && (rc = grow(&h->hb_imu[k])) != RVIO_OK) return rc;
-    for (int k = 0; k < rvio_hip::kPin; ++k) if (h->pin[k]) { hipHostFree(h->pin[k]); h->pin[k] = nullptr; }   // rvio_hip_frame lays the ring out again
+    drop_pin_ring(h);   // rvio_hip_frame lays the ring out again
     h->imu_cap = cap;
     return RVIO_OK;
 }
@@ -899,10 +970,10 @@ static void launch_imu_pose(rvio_hip* h, hipStream_t st, int instances, const do
 // The IMU-rate ring's launch: directly in front of whatever propagates in place, on the stream that propagate runs on (it reads the state that
 // propagate is about to overwrite, and the same samples).  img_count: nImageCountAfterInit of the frame that consumes the samples.
 static int imu_ring_record(rvio_hip* h, const rvio_imu* d_imu, int m, size_t imu_bs, hipStream_t st, int img_count) {
-    if (!h->imuo_on || m <= 0) return RVIO_OK;
-    launch_imu_pose(h, st, h->batch, h->x[h->cur], d_imu, imu_bs, m, h->imuo_ring, 0, h->imuo_seq + 1, h->imuo_cap, img_count);
+    if (!h->imuo.on || m <= 0) return RVIO_OK;
+    launch_imu_pose(h, st, h->batch, h->x[h->cur], d_imu, imu_bs, m, h->imuo.ring, 0, h->imuo.seq + 1, h->imuo.cap, img_count);
     HIPCHK(h, hipGetLastError());
-    h->imuo_seq += m;   // (counted once the launch is known to be enqueued: the getter serves nothing beyond imuo_seq)
+    h->imuo.seq += m;   // (counted once the launch is known to be enqueued: the getter serves nothing beyond seq)
     return RVIO_OK;
 }
 // img_count: nImageCountAfterInit of the frame this propagate belongs to, for the IMU-rate ring's records (-1: the handle's current count — every caller
@@ -910,7 +981,7 @@ static int imu_ring_record(rvio_hip* h, const rvio_imu* d_imu, int m, size_t imu
 static int propagate_dev(rvio_hip* h, const rvio_imu* d_imu, int m, size_t imu_bs = 0, hipStream_t st = nullptr, int img_count = -1) {   // imu_bs = 0: every instance integrates the same samples
     if (!st) st = h->stream;
     h->time_imu = d_imu; h->time_m = m; h->time_imu_bs = imu_bs;   // (rvio_hip_debug_time_kernel(8), (13))
-    if (h->imuo_on) { const int rci = imu_ring_record(h, d_imu, m, imu_bs, st, img_count < 0 ? h->img_count : img_count); if (rci != RVIO_OK) return rci; }
+    if (h->imuo.on) { const int rci = imu_ring_record(h, d_imu, m, imu_bs, st, img_count < 0 ? h->img_count : img_count); if (rci != RVIO_OK) return rci; }
     if (h->batch > 8)
         hipLaunchKernelGGL(propagate_kernel3b, dim3(1, 1, h->batch), dim3(256), 0, st, h->dc, h->meta, h->n_clones_host, h->x[h->cur], h->P[h->cur], d_imu, m,
                            h->slab_bytes, imu_bs);
@@ -920,7 +991,7 @@ static int propagate_dev(rvio_hip* h, const rvio_imu* d_imu, int m, size_t imu_b
         const int nc = h->n_clones_host;
         if (h->plan.solve9_nt == 4) hipLaunchKernelGGL(propagate_chol_kernel<2>, dim3(2), dim3(256), 0, st, h->dc, h->meta, nc, h->x[h->cur], h->P[h->cur], d_imu, m, h->S9scr);
         else hipLaunchKernelGGL(propagate_chol_kernel<3>, dim3(2), dim3(256), 0, st, h->dc, h->meta, nc, h->x[h->cur], h->P[h->cur], d_imu, m, h->S9scr);
-        h->chol_ready = true;
+        chol_role(h, true);
     }
     else
     hipLaunchKernelGGL(propagate_kernel3, dim3(1, 1, h->batch), dim3(256), 0, st, h->dc, h->meta, h->n_clones_host, h->x[h->cur], h->P[h->cur], d_imu, m,
@@ -980,7 +1051,7 @@ static void launch_feat_prop(rvio_hip* h, int n, const rvio_imu* d_imu, int m, i
     hipLaunchKernelGGL(feat_prop_kernel, dim3(d.Fu + 1 + (chol ? 1 : 0)), dim3(256), h->plan.fprop_lds, h->stream, d, n, h->x[h->cur], h->P[h->cur],
                        h->t.n_feat, h->t.types, h->t.len, h->t.meas, h->partial, h->nrows, h->acc, h->ndof, h->gamma, h->pfinv, h->tm_global, h->bin,
                        h->meta, d_imu, m, chol ? h->S9scr : (double*)nullptr, h->plan.solve9_nt, rank, world, h->lit_rows, (const CamCal*)h->cal);
-    h->chol_ready = chol;
+    chol_role(h, chol);
 }
 // reduction of the per-feature shares into [S2 | S1]; gram_finish: the last workgroup turns the block into [A|b] in place (rank truncation included), as the
 // batch kernels always do — behind them the literal sweep for the instances whose small stacks need it (literal.h)
@@ -1007,7 +1078,7 @@ static int update_local_dev(rvio_hip* h, int rank, int world, bool combine) {
     const int B = h->batch;
     if (h->fuse_m >= 0) {
         // (the frame count is this frame's: frame_tail_dev / the sharded frame have advanced it)
-        if (h->imuo_on) { const int rci = imu_ring_record(h, h->fuse_imu, h->fuse_m, 0, h->stream, h->img_count); if (rci != RVIO_OK) return rci; }
+        if (h->imuo.on) { const int rci = imu_ring_record(h, h->fuse_imu, h->fuse_m, 0, h->stream, h->img_count); if (rci != RVIO_OK) return rci; }
         launch_feat_prop(h, n, h->fuse_imu, h->fuse_m, rank, world);
         h->fuse_m = -1;
     } else {
@@ -1037,14 +1108,6 @@ static void launch_s9_chol(rvio_hip* h, int NT, int n, double* Pc, hipStream_t s
 static void launch_s9_sweep(rvio_hip* h, int NT, const double* Ab) {
     if (NT == 8) hipLaunchKernelGGL((solve9_sweep_kernel<2, 4>), dim3(1), dim3(1024), 0, h->stream, h->dc, Ab, h->S9scr);
     else hipLaunchKernelGGL((solve9_sweep_kernel<3, 4>), dim3(1), dim3(1024), 0, h->stream, h->dc, Ab, h->S9scr);
-}
-// Is a factor of the clone block in the slab (role workgroup of this update's per-feature / propagate launch), or about to be (stream_l: the solve
-// waits for it; a failed wait: the solve factors Pcc itself)?  The solve behind this call consumes it.
-static bool take_chol(rvio_hip* h) {
-    if (h->chol_async && hipStreamWaitEvent(h->stream, h->evL, 0) != hipSuccess) { h->chol_async = false; h->chol_ready = false; }
-    const bool pre = h->chol_ready || h->chol_async;
-    h->chol_ready = false; h->chol_async = false;
-    return pre;
 }
 
 static void launch_solve(rvio_hip* h, const UpdateForms& f, int n, const double* Ab) {
@@ -1140,9 +1203,7 @@ static int lm_alloc(rvio_hip* h, LmOut* out) {
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_feat = 256, o_pr = o_feat + up(sizeof(int) * Fu), o_pw = o_pr + up(sizeof(double) * 3 * Fu), bs = o_pw + up(sizeof(double) * 3 * Fu);
     char* p = nullptr;
-    HIPCHK(h, hipMalloc((void**)&p, bs * h->batch));
-    h->allocs.push_back(p);
-    HIPCHK(h, hipMemsetAsync(p, 0, bs * h->batch, h->stream));
+    RCCHK(own_dev(h, &p, bs * h->batch, true));
     *out = LmOut{(int*)p, (int*)(p + o_feat), (double*)(p + o_pr), (double*)(p + o_pw), bs};
     return RVIO_OK;
 }
@@ -1275,53 +1336,63 @@ static void launch_odom(rvio_hip* h, rvio_odom* slot, long long seq) {
     hipLaunchKernelGGL(odom_kernel, dim3((h->batch + 3) / 4), dim3(256), 0, h->stream, h->batch, h->dc.dmax, (const double*)h->x[h->cur], (const double*)h->P[h->cur],
                        (const double*)h->d_pose, h->slab_bytes, seq, h->img_count, h->n_clones_host, (unsigned long long*)slot);
 }
-int rvio_hip_set_odometry(rvio_hip* h, int capacity) {
-    if (!h || capacity < 0 || capacity > 65536) return RVIO_ERR_INVALID;
-    if (capacity == 0) { h->odom_on = false; return RVIO_OK; }   // (the launches stop, the ring and its records stay)
-    if (capacity != h->odom_cap) {
-        const size_t bytes = (size_t)capacity * h->batch * sizeof(rvio_odom);
+// The two operations of a DevRing (the odometry ring here, the IMU-rate ring below).  Capacity: 0 switches the launches off and keeps the ring and
+// its records; the capacity it has only switches them on; another one (or the first) is allocated with nothing in flight, and a new ring is empty.
+extern "C++" {
+template <typename T>
+static int ring_set_capacity(rvio_hip* h, DevRing<T>& r, int capacity, int limit) {
+    if (capacity < 0 || capacity > limit) return RVIO_ERR_INVALID;
+    if (capacity == 0) { r.on = false; return RVIO_OK; }
+    if (capacity != r.cap) {
+        const size_t bytes = (size_t)capacity * h->batch * sizeof(T);
         if (bytes > ((size_t)1 << 30)) {
-            h->err = "odometry ring of " + std::to_string(capacity) + " x " + std::to_string(h->batch) + " records = " + std::to_string(bytes) + " bytes exceeds 1 GiB";
+            h->err = std::string(r.noun) + " ring of " + std::to_string(capacity) + " x " + std::to_string(h->batch) + " records = " + std::to_string(bytes) + " bytes exceeds 1 GiB";
             return RVIO_ERR_UNSUPPORTED;
         }
-        // (first enable or another capacity: with nothing in flight; a new ring is empty)
         { const int rc = drain_all(h); if (rc != RVIO_OK) return rc; }
-        rvio_odom* p = nullptr;
-        HIPCHK(h, hipMalloc((void**)&p, bytes));
-        if (h->odom_ring) (void)hipFree(h->odom_ring);
-        h->odom_ring = p; h->odom_cap = capacity; h->odom_seq = 0;
-        HIPCHK(h, hipMemsetAsync(p, 0, bytes, h->stream));
+        RCCHK(own_replace(h, &r.ring, bytes));
+        r.cap = capacity; r.seq = 0;
+        HIPCHK(h, hipMemsetAsync(r.ring, 0, bytes, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    h->odom_on = true;
+    r.on = true;
     return RVIO_OK;
 }
-// the filter stream only, like rvio_hip_get_pose: every record is written on it
-int rvio_hip_get_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_odom* out, int32_t* n) {
-    if (!h || instance < 0 || instance >= h->batch || max_n < 0 || (!out && max_n > 0)) return RVIO_ERR_INVALID;
-    if (!h->odom_ring) { h->err = "the odometry ring was never enabled (rvio_hip_set_odometry)"; return RVIO_ERR_STATE; }
+template <typename T>
+static bool ring_exists(rvio_hip* h, const DevRing<T>& r) {
+    if (!r.ring) h->err = std::string("the ") + r.noun + " ring was never enabled (" + r.setter + ")";
+    return r.ring != nullptr;
+}
+// Up to max_n records of one instance from first_seq on, oldest first (ring_span.h: at most two spans; instance i's records lie batch records
+// apart).  The filter stream only, like rvio_hip_get_pose: every record is written on it, or on a stream it has joined since (the overlapped
+// propagate of rvio_hip_frame_tracks_dev)
+template <typename T>
+static int ring_read(rvio_hip* h, const DevRing<T>& r, int instance, int64_t first_seq, int max_n, T* out, int32_t* n) {
+    if (instance < 0 || instance >= h->batch || max_n < 0 || (!out && max_n > 0)) return RVIO_ERR_INVALID;
+    if (!ring_exists(h, r)) return RVIO_ERR_STATE;
     HIPCHK(h, hipSetDevice(h->device));
-    const long long newest = h->odom_seq, cap = h->odom_cap;
-    const long long lo = std::max<long long>(std::max<long long>(first_seq, newest - cap + 1), 1);
-    const long long cnt = std::max<long long>(0, std::min<long long>(newest - lo + 1, max_n));
-    if (n) *n = (int32_t)cnt;
-    if (cnt == 0) return RVIO_OK;
-    // instance i's records lie batch records apart; the range wraps around the end of the ring at most once
-    const size_t pitch = sizeof(rvio_odom) * h->batch;
-    const long long s0 = (lo - 1) % cap, c0 = std::min(cnt, cap - s0);
-    HIPCHK(h, hipMemcpy2DAsync(out, sizeof(rvio_odom), h->odom_ring + (size_t)s0 * h->batch + instance, pitch, sizeof(rvio_odom), (size_t)c0, hipMemcpyDeviceToHost, h->stream));
-    if (cnt > c0)
-        HIPCHK(h, hipMemcpy2DAsync(out + c0, sizeof(rvio_odom), h->odom_ring + instance, pitch, sizeof(rvio_odom), (size_t)(cnt - c0), hipMemcpyDeviceToHost, h->stream));
+    const RingSpan s = ring_span(r.seq, r.cap, first_seq, max_n);
+    if (n) *n = (int32_t)s.count;
+    if (s.count == 0) return RVIO_OK;
+    const size_t pitch = sizeof(T) * h->batch;
+    HIPCHK(h, hipMemcpy2DAsync(out, sizeof(T), r.ring + (size_t)s.slot0 * h->batch + instance, pitch, sizeof(T), (size_t)s.n0, hipMemcpyDeviceToHost, h->stream));
+    if (s.count > s.n0)
+        HIPCHK(h, hipMemcpy2DAsync(out + s.n0, sizeof(T), r.ring + instance, pitch, sizeof(T), (size_t)(s.count - s.n0), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RVIO_OK;
 }
+}  // extern "C++"
+int rvio_hip_set_odometry(rvio_hip* h, int capacity) { return h ? ring_set_capacity(h, h->odom, capacity, 65536) : RVIO_ERR_INVALID; }
+int rvio_hip_get_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_odom* out, int32_t* n) {
+    return h ? ring_read(h, h->odom, instance, first_seq, max_n, out, n) : RVIO_ERR_INVALID;
+}
 int rvio_hip_get_odometry_all(rvio_hip* h, rvio_odom* out, int64_t* seq) {
     if (!h || !out) return RVIO_ERR_INVALID;
-    if (!h->odom_ring) { h->err = "the odometry ring was never enabled (rvio_hip_set_odometry)"; return RVIO_ERR_STATE; }
+    if (!ring_exists(h, h->odom)) return RVIO_ERR_STATE;
     HIPCHK(h, hipSetDevice(h->device));
-    if (seq) *seq = h->odom_seq;
-    if (h->odom_seq == 0) return RVIO_OK;
-    HIPCHK(h, hipMemcpyAsync(out, h->odom_ring + (size_t)((h->odom_seq - 1) % h->odom_cap) * h->batch, sizeof(rvio_odom) * h->batch, hipMemcpyDeviceToHost, h->stream));
+    if (seq) *seq = h->odom.seq;
+    if (h->odom.seq == 0) return RVIO_OK;
+    HIPCHK(h, hipMemcpyAsync(out, h->odom.slot(h->odom.seq, h->batch), sizeof(rvio_odom) * h->batch, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RVIO_OK;
 }
@@ -1350,11 +1421,11 @@ int rvio_hip_predict(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio
     HIPCHK(h, hipSetDevice(h->device));
     if (m > h->pred_cap) {   // (every earlier call has waited for its copies: nothing reads the old blocks)
         const int cap = std::max(std::max(2 * h->pred_cap, RVIO_HIP_MAX_IMU), (m + 63) & ~63);
-        rvio_imu* pi = nullptr; rvio_imu_pose* po = nullptr;
-        HIPCHK(h, hipMalloc((void**)&pi, sizeof(rvio_imu) * (size_t)cap));
-        if (hipMalloc((void**)&po, sizeof(rvio_imu_pose) * (size_t)cap) != hipSuccess) { (void)hipFree(pi); h->err = "hipMalloc of the predict staging failed"; return RVIO_ERR_NO_DEVICE; }
-        if (h->pred_imu) (void)hipFree(h->pred_imu);
-        if (h->pred_out) (void)hipFree(h->pred_out);
+        rvio_imu* pi = nullptr; rvio_imu_pose* po = nullptr;   // (both or neither: the members change once the pair exists)
+        int rc = own_dev(h, &pi, sizeof(rvio_imu) * (size_t)cap);
+        if (rc == RVIO_OK) rc = own_dev(h, &po, sizeof(rvio_imu_pose) * (size_t)cap);
+        if (rc != RVIO_OK) { own_release(h, pi); return rc; }
+        own_release(h, h->pred_imu); own_release(h, h->pred_out);
         h->pred_imu = pi; h->pred_out = po; h->pred_cap = cap;
     }
     HIPCHK(h, hipMemcpyAsync(h->pred_imu, imu, sizeof(rvio_imu) * (size_t)m, hipMemcpyHostToDevice, h->stream));
@@ -1365,46 +1436,9 @@ int rvio_hip_predict(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio
     return RVIO_OK;
 }
 // the ring: rvio_hip_set_odometry's clauses, one record per IMU sample instead of one per frame
-int rvio_hip_set_imu_odometry(rvio_hip* h, int capacity) {
-    if (!h || capacity < 0 || capacity > 1048576) return RVIO_ERR_INVALID;
-    if (capacity == 0) { h->imuo_on = false; return RVIO_OK; }   // (the launches stop, the ring and its records stay)
-    if (capacity != h->imuo_cap) {
-        const size_t bytes = (size_t)capacity * h->batch * sizeof(rvio_imu_pose);
-        if (bytes > ((size_t)1 << 30)) {
-            h->err = "IMU-rate odometry ring of " + std::to_string(capacity) + " x " + std::to_string(h->batch) + " records = " + std::to_string(bytes) + " bytes exceeds 1 GiB";
-            return RVIO_ERR_UNSUPPORTED;
-        }
-        // (first enable or another capacity: with nothing in flight; a new ring is empty)
-        { const int rc = drain_all(h); if (rc != RVIO_OK) return rc; }
-        HIPCHK(h, hipSetDevice(h->device));
-        rvio_imu_pose* p = nullptr;
-        HIPCHK(h, hipMalloc((void**)&p, bytes));
-        if (h->imuo_ring) (void)hipFree(h->imuo_ring);
-        h->imuo_ring = p; h->imuo_cap = capacity; h->imuo_seq = 0;
-        HIPCHK(h, hipMemsetAsync(p, 0, bytes, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    h->imuo_on = true;
-    return RVIO_OK;
-}
-// the filter stream only: every record is written on it, or on a stream it has joined since (the overlapped propagate of rvio_hip_frame_tracks_dev)
+int rvio_hip_set_imu_odometry(rvio_hip* h, int capacity) { return h ? ring_set_capacity(h, h->imuo, capacity, 1048576) : RVIO_ERR_INVALID; }
 int rvio_hip_get_imu_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_imu_pose* out, int32_t* n) {
-    if (!h || instance < 0 || instance >= h->batch || max_n < 0 || (!out && max_n > 0)) return RVIO_ERR_INVALID;
-    if (!h->imuo_ring) { h->err = "the IMU-rate odometry ring was never enabled (rvio_hip_set_imu_odometry)"; return RVIO_ERR_STATE; }
-    HIPCHK(h, hipSetDevice(h->device));
-    const long long newest = h->imuo_seq, cap = h->imuo_cap;
-    const long long lo = std::max<long long>(std::max<long long>(first_seq, newest - cap + 1), 1);
-    const long long cnt = std::max<long long>(0, std::min<long long>(newest - lo + 1, max_n));
-    if (n) *n = (int32_t)cnt;
-    if (cnt == 0) return RVIO_OK;
-    // instance i's records lie batch records apart; the range wraps around the end of the ring at most once
-    const size_t pitch = sizeof(rvio_imu_pose) * h->batch;
-    const long long s0 = (lo - 1) % cap, c0 = std::min(cnt, cap - s0);
-    HIPCHK(h, hipMemcpy2DAsync(out, sizeof(rvio_imu_pose), h->imuo_ring + (size_t)s0 * h->batch + instance, pitch, sizeof(rvio_imu_pose), (size_t)c0, hipMemcpyDeviceToHost, h->stream));
-    if (cnt > c0)
-        HIPCHK(h, hipMemcpy2DAsync(out + c0, sizeof(rvio_imu_pose), h->imuo_ring + instance, pitch, sizeof(rvio_imu_pose), (size_t)(cnt - c0), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return RVIO_OK;
+    return h ? ring_read(h, h->imuo, instance, first_seq, max_n, out, n) : RVIO_ERR_INVALID;
 }
 
 // ------------------------------------------------------------------ auxiliary measurement update (aux_update.hip)
@@ -1415,13 +1449,8 @@ static int update_aux_dev(rvio_hip* h, int m, int mode, int gate, const double* 
     if (!h->has_state) { h->err = "rvio_hip_update_aux before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
     if (h->in_frame) { h->err = "rvio_hip_update_aux between rvio_hip_frame_begin_dev and rvio_hip_frame_end"; return RVIO_ERR_STATE; }
     HIPCHK(h, hipSetDevice(h->device));
-    if (!h->aux_diag) {
-        HIPCHK(h, hipMalloc((void**)&h->aux_diag, sizeof(double) * 2 * (size_t)h->batch));
-        HIPCHK(h, hipMemsetAsync(h->aux_diag, 0, sizeof(double) * 2 * (size_t)h->batch, h->stream));
-    }
-    // a factor of the clone block in flight on the side queue reads the covariance that is about to change; one in the slab belongs to the old one
-    if (h->chol_async) { HIPCHK(h, hipStreamWaitEvent(h->stream, h->evL, 0)); h->chol_async = false; }
-    h->chol_ready = false;
+    if (!h->aux_diag) RCCHK(own_dev(h, &h->aux_diag, sizeof(double) * 2 * (size_t)h->batch, true));
+    RCCHK(chol_drop(h, CHOL_FILTER_WAITS));   // (the update changes the covariance in place)
     const int n = h->n_clones_host;
     const LpLaunch l = aux_update_launch(n, m, h->batch);
     const size_t w = sizeof(double);
@@ -1461,10 +1490,14 @@ int rvio_hip_update_aux(rvio_hip* h, int instance, const rvio_aux_meas* meas) {
     if (h->in_frame) { h->err = "rvio_hip_update_aux between rvio_hip_frame_begin_dev and rvio_hip_frame_end"; return RVIO_ERR_STATE; }
     HIPCHK(h, hipSetDevice(h->device));
     const size_t nH = (size_t)RVIO_AUX_MAX_ROWS * h->dc.dmax, nd = nH + 2 * RVIO_AUX_MAX_ROWS, bytes = nd * sizeof(double) + sizeof(int32_t) * (size_t)h->batch;
-    if (!h->aux_pin) {
-        HIPCHK(h, hipHostMalloc((void**)&h->aux_pin, bytes, hipHostMallocDefault));
-        HIPCHK(h, hipMalloc((void**)&h->aux_stage, bytes));
-        HIPCHK(h, hipEventCreateWithFlags(&h->evAux, hipEventDisableTiming));
+    if (!h->aux_pin) {   // (all three or none: a failure half-way leaves the members null, and the next call starts over)
+        double *pin = nullptr, *stage = nullptr;
+        hipEvent_t ev = nullptr;
+        int rc = own_pinned(h, &pin, bytes);
+        if (rc == RVIO_OK) rc = own_dev(h, &stage, bytes);
+        if (rc == RVIO_OK) rc = own_event(h, &ev, hipEventDisableTiming);
+        if (rc != RVIO_OK) { own_release(h, pin); own_release(h, stage); return rc; }
+        h->aux_pin = pin; h->aux_stage = stage; h->evAux = ev;
     } else HIPCHK(h, hipEventSynchronize(h->evAux));
     std::memcpy(h->aux_pin, meas->H, sizeof(double) * (size_t)m * d);
     std::memcpy(h->aux_pin + nH, meas->v, sizeof(double) * m);
@@ -1499,12 +1532,12 @@ static int augment_compose_dev(rvio_hip* h, int do_augment) {
     const int cg = 1 + (h->batch >= 128 ? 4 : std::max(1, std::min(64, (d.dmax * d.dmax + 255) / 256)));
     unsigned long long* done = nullptr;
     if (h->batch == 1) { done = &h->stage_sync->aug; h->stage_tgt.aug += (unsigned long long)cg; }
-    if (h->chol_async) { HIPCHK(h, hipStreamWaitEvent(h->stream, h->evL, 0)); h->chol_async = false; }   // (a frame without an update: its factor was never consumed)
+    // the clone block changes (window slide / new clone).  (A factor still in flight here: a frame without an update never consumed it)
+    RCCHK(chol_drop(h, CHOL_FILTER_WAITS));
     hipLaunchKernelGGL(augcomp_kernel2, dim3(cg, 1, h->batch), dim3(256), 0, h->stream, d, h->n_clones_host, do_augment, h->x[c], h->P[c], h->x[o], h->P[o], h->d_pose,
                        h->slab_bytes, done);
     HIPCHK(h, hipGetLastError());
     h->cur = o;
-    h->chol_ready = false;   // the clone block has changed (window slide / new clone)
     if (do_augment && h->n_clones_host < d.nmax) h->n_clones_host++;
     // Long windows (6n > 96, solve in its split form): Pcc = L L^T of the NEXT update is known from here on — propagation leaves the clone block
     // alone — so the factor starts now on a stream of its own and runs beside propagate, the wait for the tracker and the per-feature stage; the
@@ -1514,15 +1547,15 @@ static int augment_compose_dev(rvio_hip* h, int do_augment) {
         HIPCHK(h, hipStreamWaitEvent(h->stream_l, h->evA, 0));
         launch_s9_chol(h, h->plan.solve9_nt, h->n_clones_host, h->P[h->cur], h->stream_l);
         HIPCHK(h, hipEventRecord(h->evL, h->stream_l));
-        h->chol_async = true;
+        chol_queued(h);
     }
     // the odometry record of this frame: behind evA (the run-ahead factor above starts when it did before), on the filter stream (whatever waits
     // for "the filter has finished" through an event waits for the record too; the device-side counter augcomp_kernel2 bumps guards the hand-over
     // tables, which the record does not read).  It reads x / P / pose as augcomp_kernel2 left them; the next writer of either is the next frame's
     // propagate, behind it on this stream.
-    if (h->odom_on) {
-        h->odom_seq++;
-        launch_odom(h, h->odom_ring + (size_t)((h->odom_seq - 1) % h->odom_cap) * h->batch, h->odom_seq);
+    if (h->odom.on) {
+        h->odom.seq++;
+        launch_odom(h, h->odom.slot(h->odom.seq, h->batch), h->odom.seq);
         HIPCHK(h, hipGetLastError());
     }
     return RVIO_OK;
@@ -1729,26 +1762,17 @@ int rvio_hip_set_image_format(rvio_hip* h, int format) {
     const size_t npx = (size_t)h->dc.W * h->dc.H;
     if (format != RVIO_PIX_MONO8 && !h->d_gray[0]) {   // first converting format: the gray buffers of every instance
         uint8_t* p = nullptr;
-        HIPCHK(h, hipMalloc((void**)&p, 4 * npx * (size_t)h->batch));
-        h->allocs.push_back(p);
-        HIPCHK(h, hipMemsetAsync(p, 0, 4 * npx * (size_t)h->batch, h->stream));
+        RCCHK(own_dev(h, &p, 4 * npx * (size_t)h->batch, true));
         for (int k = 0; k < 4; ++k) h->d_gray[k] = p + (size_t)k * npx * h->batch;
     }
     if (npx * ch > h->img_cap) {     // the staging of the host-buffer entry points grows to the interleaved image (the old blocks stay where they were, as in ensure_imu_capacity)
-        auto grow = [&](uint8_t** q) -> int {
-            void* n = nullptr;
-            HIPCHK(h, hipMalloc(&n, npx * ch));
-            h->allocs.push_back(n);
-            *q = (uint8_t*)n;
-            return RVIO_OK;
-        };
+        auto grow = [&](uint8_t** q) { return own_dev(h, q, npx * ch); };
         int rc = grow(&h->d_img);
         for (int k = 0; k < 2 && rc == RVIO_OK; ++k) if (h->hb_img[k]) rc = grow(&h->hb_img[k]);
         if (rc != RVIO_OK) return rc;
         h->img_cap = npx * ch;
     }
-    if (ch != h->pix_ch)             // rvio_hip_frame lays the pinned ring out again (the image slot changes size)
-        for (int k = 0; k < rvio_hip::kPin; ++k) if (h->pin[k]) { hipHostFree(h->pin[k]); h->pin[k] = nullptr; }
+    if (ch != h->pix_ch) drop_pin_ring(h);   // rvio_hip_frame lays the pinned ring out again (the image slot changes size)
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->pix_fmt = format; h->pix_ch = ch;
     h->last.gray_src = nullptr;
@@ -2251,10 +2275,9 @@ int rvio_hip_frame_sharded_dev(rvio_hip* h, const uint8_t* d_img, int stride, co
     if (comm && !ag && !(ag = resolve_allgather(&h->err))) return RVIO_ERR_UNSUPPORTED;
     if (comm && h->gathered_world < world) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        void* q = nullptr;
-        HIPCHK(h, hipMalloc(&q, sizeof(double) * nblk_max * (size_t)world));
-        h->allocs.push_back(q);
-        h->gathered = (double*)q; h->gathered_world = world;
+        // (a larger world: the old block stays, freed with the handle)
+        RCCHK(own_dev(h, &h->gathered, sizeof(double) * nblk_max * (size_t)world));
+        h->gathered_world = world;
     }
     int rc = frame_dev_impl(h, frame_forms(h, d_img, stride, d_cand), d_img, stride, d_imu, m, d_cand, n_cand, false, /*begin_only=*/true, /*defer_propagate=*/true);
     if (rc != RVIO_OK) return rc;
@@ -2297,9 +2320,10 @@ int rvio_hip_frame(rvio_hip* h, const uint8_t* img, int stride, const rvio_imu* 
         const size_t pin_cand = h->pin_imu + ((sizeof(rvio_imu) * (size_t)h->imu_cap + 255) & ~(size_t)255);
         h->pin_bytes = pin_cand + sizeof(float) * 2 * h->dc.F;
         for (int k = 0; k < rvio_hip::kPin; ++k) {
-            HIPCHK(h, hipHostMalloc((void**)&h->pin[k], h->pin_bytes, hipHostMallocDefault));
-            if (!h->evPin[k]) HIPCHK(h, hipEventCreateWithFlags(&h->evPin[k], kEvFlags));     // (the ring is laid out again after ensure_imu_capacity)
-            if (!h->evPin2[k]) HIPCHK(h, hipEventCreateWithFlags(&h->evPin2[k], kEvFlags));
+            int rc = own_pinned(h, &h->pin[k], h->pin_bytes);
+            if (rc == RVIO_OK && !h->evPin[k]) rc = own_event(h, &h->evPin[k], kEvFlags);     // (the ring is laid out again after drop_pin_ring)
+            if (rc == RVIO_OK && !h->evPin2[k]) rc = own_event(h, &h->evPin2[k], kEvFlags);
+            if (rc != RVIO_OK) { drop_pin_ring(h); return rc; }   // (the next call starts over: pin[0] says whether the ring exists)
         }
     }
     const int b = (int)(h->frame_no & 1);
@@ -2378,17 +2402,7 @@ int rvio_hip_get_frame_info(rvio_hip* h, rvio_frame_info* info) {
     if (m.err & 4) { h->err = "a device-side stage counter timed out (filter -> book-keeping): the frame sequence is invalid, re-initialise"; return RVIO_ERR_STATE; }
     return RVIO_OK;
 }
-int rvio_hip_get_pose(rvio_hip* h, double p[3], double q[4]) {
-    if (!h) return RVIO_ERR_INVALID;
-    HIPCHK(h, hipSetDevice(h->device));
-    double buf[8];
-    HIPCHK(h, hipMemcpyAsync(buf, h->d_pose, sizeof buf, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (p) for (int i = 0; i < 3; ++i) p[i] = buf[i];
-    if (q) for (int i = 0; i < 4; ++i) q[i] = buf[3 + i];
-    return RVIO_OK;
-}
-// the same line of one instance of a batch handle: augcomp_kernel2 writes d_pose at the slab stride
+// one instance of a batch handle: augcomp_kernel2 writes d_pose at the slab stride
 int rvio_hip_get_pose_at(rvio_hip* h, int instance, double p[3], double q[4]) {
     if (!h || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
@@ -2399,6 +2413,7 @@ int rvio_hip_get_pose_at(rvio_hip* h, int instance, double p[3], double q[4]) {
     if (q) for (int i = 0; i < 4; ++i) q[i] = buf[3 + i];
     return RVIO_OK;
 }
+int rvio_hip_get_pose(rvio_hip* h, double p[3], double q[4]) { return rvio_hip_get_pose_at(h, 0, p, q); }
 
 }  // extern "C"
 
@@ -2425,7 +2440,7 @@ int rvio_hip_get_corners(rvio_hip* h, int32_t* n, float* xy, float* raw_xy, floa
         // detector saw — level 0 of the current pyramid — by the map-only kernel (same arithmetic); its side effects on the detector's
         // per-frame scratch are undone (the image maximum returns to its rest value)
         const DevCfg& d = h->dc;
-        if (!h->eig_map) { const bool sm = h->slab_mode; h->slab_mode = false; const int rc = dalloc(h, &h->eig_map, (size_t)d.W * d.H); h->slab_mode = sm; if (rc != RVIO_OK) return rc; }
+        if (!h->eig_map) RCCHK(own_dev(h, &h->eig_map, sizeof(float) * d.W * d.H, true));
         DetDev dm = ds_;
         dm.eig = h->eig_map;
         hipLaunchKernelGGL(mineig_kernel, dim3((d.W + DET_TW - 1) / DET_TW, (d.H + DET_TH - 1) / DET_TH, 1), dim3(DET_T), 0, h->stream, h->pyr[h->pyr_cur].img[0], d.W, dm, (size_t)0,
@@ -2449,12 +2464,11 @@ int rvio_hip_debug_pyramid(rvio_hip* h, int level, int32_t* w, int32_t* hgt, uin
     const size_t n = (size_t)p.w[level] * p.h[level];
     if (img) HIPCHK(h, hipMemcpyAsync(img, p.img[level], n, hipMemcpyDeviceToHost, h->stream));
     if (dxy) {   // calcSharrDeriv of that level, computed on demand (the pipeline keeps no derivative image)
+        OwnedScope tmps(h);
         int* tmp = nullptr;
-        HIPCHK(h, hipMalloc((void**)&tmp, n * sizeof(int)));
+        RCCHK(tmps.dev(&tmp, n * sizeof(int)));
         hipLaunchKernelGGL(scharr_debug_kernel, dim3((p.w[level] + 63) / 64, (p.h[level] + 3) / 4), dim3(256), 0, h->stream, p.img[level], p.w[level], p.h[level], tmp);
         HIPCHK(h, hipMemcpyAsync(dxy, tmp, n * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        hipFree(tmp);
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RVIO_OK;
@@ -2474,50 +2488,53 @@ int rvio_hip_debug_tracked(rvio_hip* h, int n, float* xy, float* un_xy) {
 // hot kernel on the operands left behind by the last frame: which = 0 -> solve kernel (W = T^-1 + injection),
 // 1 -> klt_kernel3 on the two resident pyramids, 2 -> feat_build_kernel.  Outputs land in scratch / are idempotent.
 int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us) {
-    if (!h || !avg_us || iters < 1) return RVIO_ERR_INVALID;
+    if (!h || !avg_us || iters < 1 || which < 0 || which > 13) return RVIO_ERR_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
     { const int rcd = drain_all(h); if (rcd != RVIO_OK) return rcd; }   // (every queue of the handle: the run-ahead image chains too)
     const DevCfg& d = h->dc;
     const int n = h->n_clones_host;
-    hipEvent_t e0, e1;
+    // what this handle cannot time, ahead of everything the hook creates
+    const bool front_hook = which == 1 || which == 6 || which == 9 || which == 11;
+    if (front_hook && !h->front_end) { h->err = "this batch handle was created without its front end"; return RVIO_ERR_UNSUPPORTED; }
+    if ((which == 1 || which == 6 || which == 9) && h->batch > 1) return RVIO_ERR_UNSUPPORTED;
+    if ((which == 6 || which == 9) && !h->det_ready) return RVIO_ERR_UNSUPPORTED;
+    if (which == 8 && (h->batch > 1 || !h->plan.fuse_ok || !h->time_imu || n < 1)) return RVIO_ERR_UNSUPPORTED;
+    if (which == 10 && !h->lm.count) return RVIO_ERR_UNSUPPORTED;
+    if (which == 11 && (h->pix_fmt == RVIO_PIX_MONO8 || !h->last.gray_src)) { h->err = "no colour or raw image has been handed over (rvio_hip_set_image_format)"; return RVIO_ERR_UNSUPPORTED; }
+    if (which == 12 && !ring_exists(h, h->odom)) return RVIO_ERR_UNSUPPORTED;
+    if (which == 13) {
+        if (!ring_exists(h, h->imuo)) return RVIO_ERR_UNSUPPORTED;
+        if (!h->time_imu || h->time_m < 1) { h->err = "no frame has propagated an IMU batch yet"; return RVIO_ERR_UNSUPPORTED; }
+    }
+    // the hook's temporaries and its two events: released when this scope ends, whichever return ends it
+    OwnedScope tmps(h);
     double *bx = nullptr, *bP = nullptr;
     if (which == 8) {   // (the fused launch propagates in place: the state is put aside and restored behind the timed launches)
-        if (h->batch > 1 || !h->plan.fuse_ok || !h->time_imu || n < 1) return RVIO_ERR_UNSUPPORTED;
-        HIPCHK(h, hipMalloc(&bx, sizeof(double) * d.xdmax)); HIPCHK(h, hipMalloc(&bP, sizeof(double) * d.dmax * d.dmax));
+        RCCHK(tmps.dev(&bx, sizeof(double) * d.xdmax)); RCCHK(tmps.dev(&bP, sizeof(double) * d.dmax * d.dmax));
         HIPCHK(h, hipMemcpyAsync(bx, h->x[h->cur], sizeof(double) * d.xdmax, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(bP, h->P[h->cur], sizeof(double) * d.dmax * d.dmax, hipMemcpyDeviceToDevice, h->stream));
     }
-    if (which == 11 && (h->pix_fmt == RVIO_PIX_MONO8 || !h->last.gray_src)) { h->err = "no colour or raw image has been handed over (rvio_hip_set_image_format)"; return RVIO_ERR_UNSUPPORTED; }
-    rvio_odom* odt = nullptr;
-    if (which == 12) {   // (into a slot of its own: the ring stays what the frames wrote)
-        if (!h->odom_ring) { h->err = "the odometry ring was never enabled (rvio_hip_set_odometry)"; return RVIO_ERR_UNSUPPORTED; }
-        HIPCHK(h, hipMalloc((void**)&odt, sizeof(rvio_odom) * h->batch));
-    }
-    rvio_imu_pose* ipt = nullptr;
-    if (which == 13) {   // (into a buffer of its own, in the ring's layout: the ring stays what the frames wrote)
-        if (!h->imuo_ring) { h->err = "the IMU-rate odometry ring was never enabled (rvio_hip_set_imu_odometry)"; return RVIO_ERR_UNSUPPORTED; }
-        if (!h->time_imu || h->time_m < 1) { h->err = "no frame has propagated an IMU batch yet"; return RVIO_ERR_UNSUPPORTED; }
-        HIPCHK(h, hipMalloc((void**)&ipt, sizeof(rvio_imu_pose) * (size_t)h->time_m * h->batch));
-    }
+    rvio_odom* odt = nullptr;        // (12: into a slot of its own: the ring stays what the frames wrote)
+    if (which == 12) RCCHK(tmps.dev(&odt, sizeof(rvio_odom) * h->batch));
+    rvio_imu_pose* ipt = nullptr;    // (13: into a buffer of its own, in the ring's layout: the ring stays what the frames wrote)
+    if (which == 13) RCCHK(tmps.dev(&ipt, sizeof(rvio_imu_pose) * (size_t)h->time_m * h->batch));
     LmOut lmt = {nullptr, nullptr, nullptr, nullptr, 0};
     if (which == 10) {   // (into buffers of its own: the getter's cloud stays the last update's)
-        if (!h->lm.count) return RVIO_ERR_UNSUPPORTED;
-        const int rc = lm_alloc(h, &lmt);
-        if (rc != RVIO_OK) return rc;
+        RCCHK(lm_alloc(h, &lmt));
+        tmps.held.push_back(lmt.count);   // (the one allocation behind the four pointers)
     }
     // the forms the frame's update would get at this window (time what the chain sees: the Cholesky factor rides in the per-feature launch / runs on its own
     // queue; the slab holds the factor of the last update): fw for a whole update, fs for one separately timed stage
     const bool pre = h->plan.solve9_nt && (h->plan.solve9_nt <= 6 || h->plan.chol_queue);
     const UpdateForms fw = forms_at(h, n, pre, true), fs = forms_at(h, n, pre, false);
     // ... and the kernel forms a front-end call with the device detector gets on the last image handed over (1, 6, 9, 11)
-    const bool front_hook = which == 1 || which == 6 || which == 9 || which == 11;
-    if (front_hook && !h->front_end) { h->err = "this batch handle was created without its front end"; return RVIO_ERR_UNSUPPORTED; }
     const FrontForms ff = front_hook ? call_forms(h, false, false, h->last.gray_src, h->last.gray_stride, h->last.gray_bs) : FrontForms();
-    HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    RCCHK(tmps.event(&e0, hipEventDefault)); RCCHK(tmps.event(&e1, hipEventDefault));
     HIPCHK(h, hipEventRecord(e0, h->stream));
     for (int it = 0; it < iters; ++it) {
         if (which == 12) {   // odom_kernel as augment_compose_dev launches it, on the composed state the last frame left
-            launch_odom(h, odt, h->odom_seq);
+            launch_odom(h, odt, h->odom.seq);
         } else
         if (which == 13) {   // imu_pose_kernel as the ring launches it: the IMU batch of the last frame (the caller's device buffer must still be alive), the state that frame left
             launch_imu_pose(h, h->stream, h->batch, h->x[h->cur], h->time_imu, h->time_imu_bs, h->time_m, ipt, 0, 1, h->time_m, h->img_count);
@@ -2532,7 +2549,6 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
             // IMU batch of the last frame (the caller's device buffer must still be alive) + at 6n <= 96 the Cholesky role
             launch_feat_prop(h, n, h->time_imu, h->time_m, 0, 1);
         } else if (which == 9) {   // the detector's selection kernel (one workgroup: priority-ordered maximal independent set) on the candidates of the last detector call
-            if (h->batch > 1 || !h->det_ready) return RVIO_ERR_UNSUPPORTED;
             const DetDev q = det_view(h, h->last.det_set, h->last.dslot);
             hipLaunchKernelGGL(greedy_kernel, lp_grid(ff.greedy_l), lp_block(ff.greedy_l), ff.greedy_l.lds, h->stream, q, h->slab_bytes);
         } else
@@ -2543,7 +2559,6 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
             // image back onto the PREVIOUS one from the current feature positions instead — the same displacement magnitudes, reversed, the
             // refilled corners included (they exist in the previous image too).  Outputs land in t.tracked / t.status (scratch between frames).
             // (the form the frames of this handle get: klt_kernel16 once rvio_hip_debug_kernel_forms has switched it to the throughput forms)
-            if (h->batch > 1) return RVIO_ERR_UNSUPPORTED;
             if (ff.klt == LPKL_K16)
                 hipLaunchKernelGGL(klt_kernel16, lp_grid(ff.klt_l), lp_block(ff.klt_l), 0, h->stream, h->pyr[h->pyr_cur], h->pyr[(h->pyr_cur + 3) % 4], d.levels, h->t.n_pts, h->t.feats,
                                    h->t.tracked, h->t.status, (size_t)0);
@@ -2559,31 +2574,25 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
         } else if (which == 7) {   // U, G, P1 + the Joseph form as the handle launches them for a whole update (one instance, 6n <= 60: ONE kernel)
             launch_ug_final(h, fw, n, h->block, h->P[h->cur ^ 1], true, true, false);   // (no solve ran ahead of the timed launch: no dx waits for its roles)
         } else if (which == 6) {   // cornerSubPix on the corners of the last detector call (reads raw_xy, rewrites xy with the same values)
-            if (h->batch > 1 || !h->det_ready) return RVIO_ERR_UNSUPPORTED;
             const DetDev q = det_view(h, h->last.det_set, h->last.dslot);
             const uint8_t* im = h->pyr[h->pyr_cur].img[0];   // level 0 of the current pyramid = the image the detector saw
             launch_subpix(h, ff, q, im, d.W, (size_t)0, 0, h->stream);
         } else if (which == 11) {   // gray_kernel on the last image handed over, in the form the frame launched, into the slot it wrote (the same values again)
             launch_gray(h, ff, h->last.gray_src, h->last.gray_stride, h->last.gray_bs, h->d_gray[h->gray_slot], h->stream);
-        } else return RVIO_ERR_INVALID;
+        }
     }
     HIPCHK(h, hipEventRecord(e1, h->stream));
-    // the timed solves ran on the slab: the next update factors the clone block itself.  (No wait for evL in front of them and none here: drain_all() above
-    // has synchronised stream_c, which IS stream_l, so a factor that was in flight has landed.)
-    if (which == 0) { h->chol_ready = false; h->chol_async = false; }
+    // the timed solves ran on the slab: the next update factors the clone block itself.  (drain_all() above has synchronised stream_c, which IS
+    // stream_l, so a factor that was in flight has landed.)
+    if (which == 0) (void)chol_drop(h, CHOL_DRAINED);
     if (which == 8) {
         HIPCHK(h, hipMemcpyAsync(h->x[h->cur], bx, sizeof(double) * d.xdmax, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->P[h->cur], bP, sizeof(double) * d.dmax * d.dmax, hipMemcpyDeviceToDevice, h->stream));
-        h->chol_ready = false;
+        chol_role(h, false);   // (what the role workgroups of the timed launches left is not kept.  No chol_drop: P is again what it was, a factor from stream_l stays its factor)
     }
     HIPCHK(h, hipEventSynchronize(e1));
     float ms = 0;
     HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    if (bx) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(bx); (void)hipFree(bP); }
-    if (odt) (void)hipFree(odt);   // (the event above has drained the stream)
-    if (ipt) (void)hipFree(ipt);
-    if (lmt.count) { h->allocs.pop_back(); (void)hipFree(lmt.count); }   // (lm_alloc pushed it last; the event above has drained the stream)
     *avg_us = ms * 1e3f / iters;
     HIPCHK(h, hipGetLastError());
     return RVIO_OK;
@@ -2623,7 +2632,7 @@ int rvio_hip_debug_poison(rvio_hip* h, int what) {
         HIPCHK(h, fill(h->Tbuf, sizeof(double) * ldh * ldh)); HIPCHK(h, fill(h->W, sizeof(double) * ldh * ldh));
         if (h->S9scr) {   // the slab holds the Cholesky factor a PRE solve would read (role workgroup / stream_l): it goes with the slab — the next solve factors Pcc itself
             HIPCHK(h, hipMemsetAsync(h->S9scr, 0xff, sizeof(double) * S9_SLAB_DOUBLES(h->plan.solve9_nt), h->stream));
-            h->chol_ready = false; h->chol_async = false;   // (drain_all above has waited for stream_l)
+            (void)chol_drop(h, CHOL_DRAINED);   // (drain_all above has waited for stream_l)
         }
         HIPCHK(h, fill(h->U, sizeof(double) * dm * ldh)); HIPCHK(h, fill(h->G, sizeof(double) * dm * ldh));
         HIPCHK(h, fill(h->Pt1, sizeof(double) * PP));
