@@ -254,13 +254,16 @@ int System::flush_odometry() {
     return 0;
 }
 
-bool System::record_imu_odometry_to(const std::string& path, int ring) {
+bool System::record_imu_odometry_to(const std::string& path, int ring, bool with_cov) {
     if (!h_) return false;
     if (ring < 1) { err_ = "the IMU-rate odometry ring holds at least one record"; return false; }
     auto* f = new std::ofstream(path, std::ofstream::out);
     if (!*f) { delete f; err_ = "cannot write " + path; return false; }
     if (f_io_) (void)flush_imu_odometry();
     if (rvio_hip_set_imu_odometry(h_, ring) != RVIO_OK) { delete f; err_ = rvio_hip_last_error(h_); return false; }
+    if (rvio_hip_set_imu_odometry_cov(h_, with_cov ? 1 : 0) != RVIO_OK) { delete f; err_ = rvio_hip_last_error(h_); return false; }
+    io_cov_ = with_cov;
+    ioc_buf_.assign(with_cov ? (size_t)ring : 0, rvio_imu_cov{});
     delete static_cast<std::ofstream*>(f_io_);
     f_io_ = f;
     io_ring_ = ring;
@@ -285,6 +288,12 @@ int System::flush_imu_odometry() {
     int32_t n = 0;
     if (rvio_hip_get_imu_odometry(h_, 0, io_read_ + 1, io_ring_, io_buf_.data(), &n) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
     auto& f = *static_cast<std::ofstream*>(f_io_);
+    if (io_cov_) {   // the paired records: the same window of the same seq
+        int32_t nc = 0;
+        if (rvio_hip_get_imu_odometry_cov(h_, 0, io_read_ + 1, io_ring_, ioc_buf_.data(), &nc) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+        if (nc != n || (n > 0 && ioc_buf_[0].seq != io_buf_[0].seq)) { err_ = "IMU-rate odometry: the covariance ring does not hold the records of the pose ring"; return -1; }
+        for (int i = 0; i < n; ++i) f << format_imu_odometry_cov(io_buf_[(size_t)i], ioc_buf_[(size_t)i]);
+    } else
     for (int i = 0; i < n; ++i) f << format_imu_odometry(io_buf_[(size_t)i]);
     f.flush();
     // every outstanding sample must have come back: a ring smaller than the samples that arrive between two reads (a read follows the frame that
@@ -471,6 +480,17 @@ std::string format_imu_odometry(const rvio_imu_pose& r) {
     for (double v : r.p) add(v);
     for (double v : r.q) add(v);
     for (double v : r.v) add(v);
+    out += "\n";
+    return out;
+}
+
+std::string format_imu_odometry_cov(const rvio_imu_pose& r, const rvio_imu_cov& c) {
+    char buf[64];
+    std::string out = format_imu_odometry(r);
+    out.pop_back();   // (its newline)
+    auto add = [&](double v) { std::snprintf(buf, sizeof buf, " %.19g", v); out += buf; };
+    for (int i = 0; i < 6; ++i) for (int j = i; j < 6; ++j) add(c.pose_cov[6 * i + j]);
+    for (int i = 0; i < 3; ++i) for (int j = i; j < 3; ++j) add(c.vel_cov[3 * i + j]);
     out += "\n";
     return out;
 }

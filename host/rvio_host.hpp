@@ -113,7 +113,9 @@ public:
     // (flush_imu_odometry, also run by the destructor): no frame is drained for it.  One line per sample, format_imu_odometry.  A read that
     // returns fewer records than are outstanding — the ring was too small for the samples between two reads and has overwritten some — is an
     // error (MonoVIO / flush_imu_odometry return -1, error() names the counts): the file never misses lines silently.
-    bool record_imu_odometry_to(const std::string& path, int ring = 4096);
+    // with_cov: the handle's covariance ring runs beside it (rvio_hip_set_imu_odometry_cov) and every line carries format_imu_odometry_cov's 27
+    // columns behind its 11; without it the file is what it was before the covariance ring existed
+    bool record_imu_odometry_to(const std::string& path, int ring = 4096, bool with_cov = false);
     int flush_imu_odometry();     // 0, or -1 on a library error or on records lost to a ring too small (error())
     // the handle's sticky device-side flags (rvio_frame_info.reserved[0]: 1 singular pivot, 2 a track dropped, 4 a stage counter timed out,
     // 8 a non-positive gate pivot; 0 = none) — waits for everything in flight, so a replay reads it once at its end.  -1: the query failed.
@@ -162,6 +164,8 @@ private:
     int io_ring_ = 0;
     long long io_seq_ = 0, io_read_ = 0;   // IMU samples handed to the filter since initialisation / up to which the ring has been read
     std::vector<rvio_imu_pose> io_buf_;
+    bool io_cov_ = false;         // record_imu_odometry_to(with_cov)
+    std::vector<rvio_imu_cov> ioc_buf_;
     int note_imu_odometry(int m);
 };
 
@@ -183,6 +187,9 @@ std::string format_landmarks(double t, int frame, int n, const int32_t* feat, co
 std::string format_odometry(double t, const rvio_odom& r);
 // one record of the IMU-rate ring: t px py pz qx qy qz qw vx vy vz, %.19g (setprecision(19), like stamped_pose_ests.dat)
 std::string format_imu_odometry(const rvio_imu_pose& r);
+// the same line with the paired covariance record behind it: the 21 entries of pose_cov's upper triangle row by row (c00 c01 ... c05 c11 ... c55, order
+// x y z rotX rotY rotZ), then the 6 of vel_cov's (v00 v01 v02 v11 v12 v22), %.19g
+std::string format_imu_odometry_cov(const rvio_imu_pose& r, const rvio_imu_cov& c);
 std::string format_time_cost(int n_img, double track_ms, double filter_ms);   // one line of time_cost.dat (System.cc:376-378)
 
 }  // namespace rvio

@@ -4,9 +4,10 @@
 // of stamped_pose_ests.dat (System.cc:369-374).
 //
 //   rvio_replay <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--landmarks FILE] [--odometry FILE [--odometry-ring N]]
-//                                        [--imu-odometry FILE [--imu-odometry-ring N]]
+//                                        [--imu-odometry FILE [--imu-odometry-ring N] [--imu-odometry-cov]]
 //                                        --imu-odometry: the pose and velocity behind every IMU sample the filter consumes, read in bulk from the handle's
-//                                        IMU-rate ring of N samples (default 4096; System::record_imu_odometry_to)
+//                                        IMU-rate ring of N samples (default 4096; System::record_imu_odometry_to); --imu-odometry-cov: every
+//                                        line also carries the upper triangles of the sample's pose covariance (21) and velocity covariance (6)
 //                                        --odometry: pose, velocity and pose covariance of every frame, read in bulk from the handle's ring of N
 //                                        records (default 256; System::record_odometry_to); without <poses_out.dat> no frame is drained for its pose
 //                                        --landmarks: Updater::update's landmark cloud behind every updating frame (System::record_landmarks_to)
@@ -147,6 +148,7 @@ struct PassOptions {
     int odometry_ring = 256;
     const char* imu_odometry = nullptr;  // System::record_imu_odometry_to
     int imu_odometry_ring = 4096;
+    bool imu_odometry_cov = false;
     VelocityRows* velocity = nullptr;    // --velocity
 };
 static bool dump_frame(System& sys, const rvio_config& c, FrameDump* d) {
@@ -167,7 +169,7 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
     if (!sys.ok()) { *err = sys.error(); return 1; }
     if (o.landmarks && !sys.record_landmarks_to(o.landmarks)) { *err = sys.error(); return 1; }
     if (o.odometry && !sys.record_odometry_to(o.odometry, o.odometry_ring)) { *err = sys.error(); return 1; }
-    if (o.imu_odometry && !sys.record_imu_odometry_to(o.imu_odometry, o.imu_odometry_ring)) { *err = sys.error(); return 1; }
+    if (o.imu_odometry && !sys.record_imu_odometry_to(o.imu_odometry, o.imu_odometry_ring, o.imu_odometry_cov)) { *err = sys.error(); return 1; }
     size_t ii = 0;
     long n_images = 0, n_frames = 0;
     double t_filter = 0;
@@ -288,7 +290,7 @@ int main(int argc, char** argv) {
     }
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--record-dir DIR] [--record]\n"
-                             "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n"
+                             "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--imu-odometry-cov] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n"
                              "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate]\n", argv[0]);
         return 2;
     }
@@ -296,7 +298,7 @@ int main(int argc, char** argv) {
     int device = 0; long max_frames = -1, stall_seed = -1;
     const char* landmarks = nullptr;
     const char* odometry = nullptr; int odometry_ring = 256;
-    const char* imu_odometry = nullptr; int imu_odometry_ring = 4096;
+    const char* imu_odometry = nullptr; int imu_odometry_ring = 4096; bool imu_odometry_cov = false;
     const char* velocity = nullptr; double velocity_sigma = 0.05; bool velocity_gate = false;
     const char* record_dir = "."; bool force_record = false, sync_every = false, self = false; int noise_wgs = 0;
     for (int i = 3; i < argc; ++i) {
@@ -312,6 +314,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--odometry-ring") && i + 1 < argc) odometry_ring = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--imu-odometry") && i + 1 < argc) imu_odometry = argv[++i];   // one line per IMU sample: pose and velocity (read in bulk from the IMU-rate ring)
         else if (!std::strcmp(argv[i], "--imu-odometry-ring") && i + 1 < argc) imu_odometry_ring = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--imu-odometry-cov")) imu_odometry_cov = true;   // ... and the covariance of each sample's pose and velocity behind it
         else if (!std::strcmp(argv[i], "--selfcheck")) self = true;
         else if (!std::strcmp(argv[i], "--velocity") && i + 1 < argc) velocity = argv[++i];   // `t_ns, vx, vy, vz` rows fused behind the nearest frame (System::velocity)
         else if (!std::strcmp(argv[i], "--velocity-sigma") && i + 1 < argc) velocity_sigma = std::atof(argv[++i]);
@@ -335,7 +338,7 @@ int main(int argc, char** argv) {
     if (self) return selfcheck(s, d, device, max_frames, stall_seed, noise_wgs);
     if (sync_every || stall_seed >= 0 || noise_wgs > 0) {   // the plain replay with one of the two A/B pacings
         std::vector<PoseLine> poses; double ms = 0; int flags = 0;
-        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.velocity = vr;
+        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.imu_odometry_cov = imu_odometry_cov; o.velocity = vr;
         if (run_pass(s, d, device, o, &poses, nullptr, &ms, &flags, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
         if (out_path) { std::ofstream out(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } for (const PoseLine& p : poses) out << format_pose(p); }
         std::fprintf(stderr, "rvio_replay: %zu filtered frames, %.3f ms per MonoVIO call, device flags %d\n", poses.size(), ms, flags);
@@ -347,7 +350,7 @@ int main(int argc, char** argv) {
     if (!sys.record_to(record_dir, force_record)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (landmarks && !sys.record_landmarks_to(landmarks)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (odometry && !sys.record_odometry_to(odometry, odometry_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
-    if (imu_odometry && !sys.record_imu_odometry_to(imu_odometry, imu_odometry_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
+    if (imu_odometry && !sys.record_imu_odometry_to(imu_odometry, imu_odometry_ring, imu_odometry_cov)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     std::ofstream out;
     if (out_path) { out.open(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } }
 

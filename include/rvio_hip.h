@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag) */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov) */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -434,6 +434,46 @@ int rvio_hip_set_imu_odometry(rvio_hip* h, int capacity);
  * RVIO_ERR_STATE: the ring was never enabled; RVIO_ERR_INVALID: instance out of range, max_n < 0, out == NULL with max_n > 0. */
 int rvio_hip_get_imu_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_imu_pose* out, int32_t* n);
 
+/* --- IMU-rate odometry with covariance (added within ABI 6) ------------------- */
+/* The pose_cov / vel_cov an rvio_odom record would carry for the hypothetical frame behind record j of IMU-rate odometry ("an image arrives
+ * right behind sample j and that frame runs no update"), for every sample, by a kernel of its own (csrc/imu_cov.hip); the pose records
+ * stay imu_pose_kernel's.
+ *   1  P11_0 = P[0..23][0..23] of the current covariance.
+ *   2  per sample s: P11 <- Phi_s P11 Phi_s^T + Q_s, Phi_s = I + dt F_s, Q_s = (dt G_s) Sigma G_s^T (PreIntegrator.cc:123-142), F_s and G_s built
+ *      from Rk, Rk^T, vk, gk as they stand IN FRONT of step s — behind step s - 1; at s = 0 QuatToRot(x[10..13]), x[17..19] and the raw
+ *      x[7..9]; gk is re-normalised Rk gR behind every step.  No clone cross-terms: the marginal of the head does not depend on them.
+ *   3  behind step j: P6_j = Vk_j[0..5][:] P11_j Vk_j[0..5][:]^T, Vk_j composition's Jacobian (System.cc:325-365) from (Rk_j, pk_j, pG); its
+ *      top six rows touch columns 0-5 and 9-14 only.
+ *   4  pose_cov_j = (C + C^T) / 2, C = J_j P6_j J_j^T, J_j the 6 x 6 map of rvio_odom.pose_cov at the composed (qjG, pjG = Rk_j (pG - pk_j));
+ *      order (x, y, z, rot X, rot Y, rot Z), exactly symmetric.
+ *   5  vel_cov_j = sym(P11_j)[15..17][15..17] (Vk is the identity there), exactly symmetric. */
+typedef struct rvio_imu_cov {   /* 376 bytes, no padding */
+    int64_t seq;        /* the paired rvio_imu_pose's */
+    int32_t img_count;  /* the paired rvio_imu_pose's */
+    int32_t index;      /* the paired rvio_imu_pose's */
+    double pose_cov[36];   /* row-major 6 x 6 */
+    double vel_cov[9];     /* row-major 3 x 3, of vk_j (IMU frame) */
+} rvio_imu_cov;
+/* rvio_hip_predict's contract plus the covariance records: no side effect on x, P, the frame count, the tracker or any ring; the pose records
+ * are the existing kernel's and out may be NULL (covariances only); m > RVIO_HIP_MAX_IMU grows the staging.  Errors: rvio_hip_predict's, with
+ * cov in place of out as the buffer that must not be NULL. */
+int rvio_hip_predict_cov(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio_imu_pose* out, rvio_imu_cov* cov);
+/* rvio_hip_predict_dev's contract plus d_cov[z * cov_stride + j], cov_stride >= m; d_out may be NULL (out_stride is then ignored). */
+int rvio_hip_predict_cov_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride, int m, rvio_imu_pose* d_out, int out_stride, rvio_imu_cov* d_cov, int cov_stride);
+/* A second ring, paired with the IMU-rate ring: its capacity, its seq, its slot rule ring[(seq - 1) % capacity][instance].  enable = 1: from
+ * now on imu_cov_kernel runs right next to imu_pose_kernel — in front of every launch that propagates in place, on that launch's stream, on
+ * every path the pose ring covers (while the pose ring records: its capacity 0 stops both).  The first enable drains the handle and allocates
+ * the ring outside the filter slab.  enable = 0 stops the launches and keeps the records.  A capacity change through
+ * rvio_hip_set_imu_odometry reallocates and empties both rings, rvio_hip_initialize empties both.  Default off: a handle that never enables
+ * it allocates and launches what it did before.  RVIO_ERR_INVALID: NULL handle, enable outside 0 / 1; RVIO_ERR_STATE: enable = 1 and the
+ * IMU-rate ring was never enabled; RVIO_ERR_UNSUPPORTED (rvio_hip_last_error names the size): capacity x instances x 376 bytes exceeds 1 GiB
+ * (also returned by rvio_hip_set_imu_odometry when a capacity change would take an existing covariance ring beyond that: nothing changes). */
+int rvio_hip_set_imu_odometry_cov(rvio_hip* h, int enable);
+/* rvio_hip_get_imu_odometry's window rule on that ring, restricted to the records with seq >= the first sample recorded since covariance was
+ * last switched on.  Bounds are counted on the host; waits for the filter stream only.  RVIO_ERR_STATE: the covariance ring was never
+ * enabled; RVIO_ERR_INVALID: instance out of range, max_n < 0, out == NULL with max_n > 0. */
+int rvio_hip_get_imu_odometry_cov(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_imu_cov* out, int32_t* n);
+
 /* --- auxiliary measurement update (no reference counterpart) ----------------- */
 /* Fuses what is not a camera track — wheel odometry, a zero-velocity update, a speed-over-ground sensor — on the device: at most
  * RVIO_AUX_MAX_ROWS rows of a measurement the caller has linearised, z = h(x) + noise, with a FULL-WIDTH Jacobian.  The arithmetic of
@@ -559,7 +599,9 @@ int rvio_hip_debug_tracked(rvio_hip* h, int n, float* xy, float* un_xy);
  * 12 = the odometry record kernel on the composed state the last frame left, all instances (into a slot of its own: the ring is left alone;
  * RVIO_ERR_UNSUPPORTED unless the ring was enabled),
  * 13 = the IMU-pose kernel on the state and the IMU batch of the last frame, all instances (a _dev entry point: the caller's IMU buffer must
- * still be alive; into a buffer of its own; RVIO_ERR_UNSUPPORTED unless the IMU-rate ring was enabled and a frame has propagated). */
+ * still be alive; into a buffer of its own; RVIO_ERR_UNSUPPORTED unless the IMU-rate ring was enabled and a frame has propagated),
+ * 14 = the IMU-covariance kernel as the ring launches it, on the same operands, into a buffer of its own (RVIO_ERR_UNSUPPORTED under 13's
+ * conditions, or when the covariance ring is off). */
 int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us);
 /* Test hook against results that depend on LEFT-OVER state (scratch in HBM, LDS contents, stale hand-over entries).  Drains every stream of
  * the handle, then: what & 1 fills the filter's scratch and the spare state / covariance buffer with 0xff bytes (NaN); & 2 rewrites the LDS

@@ -231,6 +231,87 @@ def imu_pose_model(cfg, x, imu):
     return out
 
 
+class ImuCov(C.Structure):
+    """rvio_imu_cov: the covariance behind one IMU sample (rvio_hip_predict_cov*, rvio_hip_get_imu_odometry_cov): 376 bytes, no padding"""
+    _fields_ = [("seq", C.c_int64), ("img_count", C.c_int32), ("index", C.c_int32), ("pose_cov", C.c_double * 36), ("vel_cov", C.c_double * 9)]
+
+
+IMU_COV_DTYPE = np.dtype([("seq", "i8"), ("img_count", "i4"), ("index", "i4"), ("pose_cov", "f8", (6, 6)), ("vel_cov", "f8", (3, 3))])
+assert IMU_COV_DTYPE.itemsize == C.sizeof(ImuCov) == 376
+IMU_COV_COLS = (0, 1, 2, 3, 4, 5, 9, 10, 11, 12, 13, 14)   # the columns of P11 the pose covariance reads
+
+
+def imu_pose_cov_jacobian(qG, pG, qk, pk):
+    """The 6 x 12 map J Vk[0:6][IMU_COV_COLS] from the errors (rot G, pos G, rot k, pos k) of the state in front of composition to the error of
+    the published pose (x, y, z, rot X, rot Y, rot Z): Vk is composition's Jacobian (System.cc:345-355) at (Rk, pkG = Rk (pG - pk)), J the map of
+    odom_pose_jacobian at the composed (qkG, pkG)."""
+    qG, pG, qk, pk = (np.asarray(a, float) for a in (qG, pG, qk, pk))
+    Rk = quat_to_rot(qk)
+    pkG = Rk @ (pG - pk)
+    V = np.zeros((6, 12))
+    V[0:3, 0:3], V[0:3, 6:9] = Rk, np.eye(3)
+    V[3:6, 3:6], V[3:6, 6:9], V[3:6, 9:12] = Rk, _skew(pkG), -Rk
+    return odom_pose_jacobian(quat_mul(qk, qG), pkG) @ V
+
+
+def imu_cov_model(cfg, x, P24, imu):
+    """NumPy model of csrc/imu_cov.hip: the records (abi.IMU_COV_DTYPE; seq = 0, img_count = 0) of the IMU batch `imu` from the state head x[0:26]
+    and the 24 x 24 head of P.  The covariance half of PreIntegrator::propagate's sample loop (PreIntegrator.cc:123-142) beside the state half,
+    then per sample composition's Vk and the odometry record's map.  Calls nothing from the library or the oracle."""
+    x = np.asarray(x, float)
+    P = np.array(np.asarray(P24, float)[:24, :24])
+    qG, pG, gR, vR, bg, ba = x[0:4], x[4:7], x[7:10].copy(), x[17:20].copy(), x[20:23], x[23:26]
+    Rk, vk, gk = quat_to_rot(x[10:14]), vR.copy(), gR.copy()
+    dp, dv, Dt = np.zeros(3), np.zeros(3), 0.0
+    I = np.eye(3)
+    g = float(cfg.gravity)
+    Sig = np.diag(np.repeat([cfg.sigma_g ** 2, cfg.sigma_wg ** 2, cfg.sigma_a ** 2, cfg.sigma_wa ** 2], 3))
+    cols = list(IMU_COV_COLS)
+    out = np.zeros(len(imu), IMU_COV_DTYPE)
+    for j, u in enumerate(imu):
+        dt = float(u["dt"])
+        Dt += dt
+        w, a = u["w"] - bg, u["a"] - ba
+        wx, vx = _skew(w), _skew(vk)
+        F, G = np.zeros((24, 24)), np.zeros((24, 12))
+        F[9:12, 9:12], F[9:12, 18:21] = -wx, -I
+        F[12:15, 9:12], F[12:15, 15:18] = -Rk.T @ vx, Rk.T
+        F[15:18, 6:9], F[15:18, 9:12], F[15:18, 15:18], F[15:18, 18:21], F[15:18, 21:24] = -g * Rk, -g * _skew(gk), -wx, -vx, -I
+        G[9:12, 0:3], G[15:18, 0:3], G[15:18, 6:9], G[18:21, 3:6], G[21:24, 9:12] = -I, -vx, -I, I, I
+        Phi = np.eye(24) + dt * F
+        P = Phi @ P @ Phi.T + (dt * G) @ Sig @ G.T
+        # the state half, as imu_pose_model has it
+        w1 = math.sqrt(float(w @ w))
+        wdt = w1 * dt
+        wx2 = wx @ wx
+        if w1 < cfg.small_angle:
+            dR = I - dt * wx + (dt ** 2 / 2) * wx2
+            f1, f2, f3, f4 = -dt ** 3 / 3, dt ** 4 / 8, -dt ** 2 / 2, dt ** 3 / 6
+        else:
+            c, s = math.cos(wdt), math.sin(wdt)
+            dR = I - (s / w1) * wx + ((1 - c) / w1 ** 2) * wx2
+            f1 = (wdt * c - s) / w1 ** 3
+            f2 = .5 * (wdt * wdt - 2 * c - 2 * wdt * s + 2) / w1 ** 4
+            f3 = (c - 1) / w1 ** 2
+            f4 = (wdt - s) / w1 ** 3
+        Rk = dR @ Rk
+        dp = dp + dv * dt
+        dp = dp + Rk.T @ ((.5 * dt ** 2 * I + f1 * wx + f2 * wx2) @ a)
+        dv = dv + Rk.T @ ((dt * I + f3 * wx + f4 * wx2) @ a)
+        pk = vR * Dt - .5 * g * gR * Dt ** 2 + dp
+        vk = Rk @ (vR - g * gR * Dt + dv)
+        gk = Rk @ gR
+        gk = gk / math.sqrt(float(gk @ gk))
+        # the record behind sample j
+        M = imu_pose_cov_jacobian(qG, pG, rot_to_quat(Rk), pk)
+        Cm = M @ P[np.ix_(cols, cols)] @ M.T
+        r = out[j]
+        r["index"] = j
+        r["pose_cov"] = 0.5 * (Cm + Cm.T)
+        r["vel_cov"] = 0.5 * (P[15:18, 15:18] + P[15:18, 15:18].T)
+    return out
+
+
 # ---- auxiliary measurement update (rvio_hip_update_aux*, csrc/aux_update.hip)
 RVIO_AUX_MAX_ROWS = 16
 RVIO_AUX_RESIDUAL, RVIO_AUX_VALUE = 0, 1

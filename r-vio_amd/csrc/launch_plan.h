@@ -106,6 +106,13 @@ LP_HD inline size_t lit_diag_end(int ldh, bool stamps) {
 #define LP_IMUP_WAVES (LP_IMUP_T / 64)
 #define LP_IMUP_WAVE_BYTES (16 * 64 * 8)
 #define LP_IMUP_LDS_BYTES (LP_IMUP_WAVES * LP_IMUP_WAVE_BYTES)
+// imu_cov_kernel (imu_cov.hip): one wave per instance, one instance per workgroup.  Per sample of a chunk 16 words of the state chain + what the
+// covariance step reads (six 3 x 3 blocks of dt F, dt, the 9 x 9 block of Q: 136 words), overwritten by what the record needs behind the step (the
+// 12 x 12 block and the 3 x 3 velocity block: 153 words); beside them the nine rows of Phi P11 the lanes exchange (9 x 24)
+#define LP_IMUC_T 64
+#define LP_IMUC_CHUNK 32
+#define LP_IMUC_SLOT_WORDS (16 + 153)
+#define LP_IMUC_LDS_BYTES ((LP_IMUC_SLOT_WORDS * LP_IMUC_CHUNK + 216) * 8)
 // aux_update_kernel<MB> (aux_update.hip): one workgroup of eight waves per instance.  MB: the row count its register arrays are unrolled for;
 // the T product deals G = ceil(d / 64) row groups x aux_splits(G) column ranges over the waves (G <= 4 at d <= 24 + 6 (RVIO_MAX_LEN - 1)).
 // LDS: H~ (d x MB) | T (d x (MB + 1)) | U | S, L (MB x (MB + 1) each) | 1 / d, v~ (MB each) | xi, dx (d each) | 8, where U holds the partial
@@ -132,14 +139,14 @@ LP_HD inline size_t aux_lds_max_doubles(int nmax, int MB) {
 enum LpKernel {
     LPK_FEAT_BUILD16, LPK_FEAT_BUILD4, LPK_GRAM_REDUCE, LPK_BLOCK_SUM, LPK_LIT_BATCH, LPK_GEMM_T_LDS, LPK_GRAM_BATCH4, LPK_GRAM_BATCH6, LPK_FEAT_PROP,
     LPK_BOOKKEEP_B, LPK_RANSAC_BOOK, LPK_SOLVE9_SMALL, LPK_SOLVE6_1, LPK_SOLVE6_2, LPK_SOLVE6_3, LPK_JOSEPH_BATCH, LPK_UG, LPK_UG_LDS, LPK_FINAL_LDS,
-    LPK_JOSEPH_LDS, LPK_IMU_POSE, LPK_AUX_UPDATE4, LPK_AUX_UPDATE16, LPK_COUNT
+    LPK_JOSEPH_LDS, LPK_IMU_POSE, LPK_AUX_UPDATE4, LPK_AUX_UPDATE16, LPK_IMU_COV, LPK_COUNT
 };
 // (as c++filt prints them, without return type and arguments: how the test finds each kernel's static LDS in the code object's notes)
 static const char* const kLpKernelName[LPK_COUNT] = {
     "feat_build_kernel<16>", "feat_build_kernel<4>", "gram_reduce_kernel", "block_sum_kernel", "lit_batch_kernel", "gemm_T_lds_kernel",
     "gram_reduce_batch_kernel<4>", "gram_reduce_batch_kernel<6>", "feat_prop_kernel", "bookkeep_b_kernel", "ransac_book_kernel", "solve9_small_kernel",
     "solve6_kernel<1, 8, 8>", "solve6_kernel<2, 12, 8>", "solve6_kernel<2, 16, 8>", "joseph_batch_kernel", "ug_kernel", "ug_lds_kernel", "final_lds_kernel",
-    "joseph_lds_kernel", "imu_pose_kernel", "aux_update_kernel<4>", "aux_update_kernel<16>"
+    "joseph_lds_kernel", "imu_pose_kernel", "aux_update_kernel<4>", "aux_update_kernel<16>", "imu_cov_kernel"
 };
 
 struct LaunchPlan {
@@ -266,6 +273,7 @@ inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size
     p.attr[LPK_FINAL_LDS] = LP_FNL_BYTES;
     p.attr[LPK_JOSEPH_LDS] = LP_JL_BYTES;
     p.attr[LPK_IMU_POSE] = LP_IMUP_LDS_BYTES;
+    p.attr[LPK_IMU_COV] = LP_IMUC_LDS_BYTES;
     p.attr[LPK_AUX_UPDATE4] = aux_lds_max_doubles(nmax, 4) * sizeof(double);      // (what a launch asks for follows the clone count)
     p.attr[LPK_AUX_UPDATE16] = aux_lds_max_doubles(nmax, 16) * sizeof(double);
     if (batch > 1 && !p.solve5_variant && !p.solve7_variant) { p.rc = 1; p.why = "batched filter: clone window too long for the unrolled solve kernel (6n <= 126)"; return p; }
@@ -424,6 +432,8 @@ enum {
 struct LpLaunch { int gx = 0, gy = 1, gz = 1, threads = 0; size_t lds = 0; int kernel = LPF_NONE; };   // gx == 0: not launched
 // imu_pose_kernel on `instances` instances (rvio_hip_predict: one; rvio_hip_predict_dev and the IMU-rate ring: the handle's batch)
 LP_HD inline LpLaunch imu_pose_launch(int instances) { return {(instances + LP_IMUP_WAVES - 1) / LP_IMUP_WAVES, 1, 1, LP_IMUP_T, LP_IMUP_LDS_BYTES, LPK_IMU_POSE}; }
+// imu_cov_kernel on `instances` instances, next to imu_pose_kernel wherever that runs with covariances asked for
+LP_HD inline LpLaunch imu_cov_launch(int instances) { return {instances, 1, 1, LP_IMUC_T, LP_IMUC_LDS_BYTES, LPK_IMU_COV}; }
 // aux_update_kernel on a window of n clones, m rows: ONE form at every batch size (a batch handle's instance and a plain handle compute the same
 // bits), the kernel instance by the row count, the dynamic LDS by the window as it is now
 LP_HD inline LpLaunch aux_update_launch(int n, int m, int batch) {

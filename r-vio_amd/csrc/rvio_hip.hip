@@ -26,6 +26,7 @@
 #include "landmarks.hip"   // Updater::update's landmark cloud (rvio_hip_set_landmarks)
 #include "odom.hip"        // the per-frame odometry record: pose, velocity, covariance (rvio_hip_set_odometry)
 #include "imu_pose.hip"    // IMU-rate odometry: a pose per IMU sample (rvio_hip_predict, rvio_hip_set_imu_odometry)
+#include "imu_cov.hip"     // ... and its covariance: pose_cov / vel_cov per IMU sample (rvio_hip_predict_cov, rvio_hip_set_imu_odometry_cov)
 #include "aux_update.hip"  // the auxiliary measurement update: wheel odometry, zero velocity, speed over ground (rvio_hip_update_aux)
 #pragma clang fp contract(off)
 #include "frontend_kernels.hip"
@@ -185,11 +186,17 @@ struct rvio_hip {
     // IMU-rate ring (imu_pose_kernel in front of whatever propagates in place): allocated by rvio_hip_set_imu_odometry, outside the slab;
     // imuo.seq counts the samples recorded (the m of every propagate while the ring is on)
     DevRing<rvio_imu_pose> imuo{"IMU-rate odometry", "rvio_hip_set_imu_odometry"};
-    size_t time_imu_bs = 0;    // instance stride of time_imu (rvio_hip_debug_time_kernel(13))
+    // its covariance ring (imu_cov_kernel next to imu_pose_kernel): allocated by rvio_hip_set_imu_odometry_cov, outside the slab, with imuo's capacity,
+    // seq and slot rule.  imuc.seq: the newest record written; imuc_first: the first one since covariance was last switched on
+    DevRing<rvio_imu_cov> imuc{"IMU-rate covariance", "rvio_hip_set_imu_odometry_cov"};
+    long long imuc_first = 1;
+    size_t time_imu_bs = 0;    // instance stride of time_imu (rvio_hip_debug_time_kernel(13), (14))
     // staging of rvio_hip_predict (host in / host out), allocated by its first call, outside the slab: samples in, records out
     rvio_imu* pred_imu = nullptr;
     rvio_imu_pose* pred_out = nullptr;
     int pred_cap = 0;
+    rvio_imu_cov* pred_cov = nullptr;   // ... and the covariance records of rvio_hip_predict_cov, allocated by ITS first call
+    int pred_cov_cap = 0;
     bool has_state = false;    // rvio_hip_set_state* / rvio_hip_initialize* has run (rvio_hip_predict* refuses to extrapolate from nothing)
     // auxiliary measurement update (aux_update.hip), allocated by the first rvio_hip_update_aux* call, outside the slab: (gamma, applied) of the
     // last call per instance; the host form's pinned staging [H | v | sigma | active flags], its device copy, and the event behind the H2D copy
@@ -568,6 +575,7 @@ static const void* lp_kernel_fn(int k) {
         case LPK_IMU_POSE: return (const void*)imu_pose_kernel;
         case LPK_AUX_UPDATE4: return (const void*)aux_update_kernel<4>;
         case LPK_AUX_UPDATE16: return (const void*)aux_update_kernel<16>;
+        case LPK_IMU_COV: return (const void*)imu_cov_kernel;
     }
     return nullptr;
 }
@@ -858,6 +866,7 @@ int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n
     h->lm_frame = -1;   // no cloud since initialisation (the enable flag stays)
     h->odom.seq = 0;    // ... and no odometry record: seq restarts at 1 (the getters read nothing beyond seq)
     h->imuo.seq = 0;    // ... nor an IMU-rate record
+    h->imuc.seq = 0; h->imuc_first = 1;   // ... nor its covariance
     // a (re-)initialised filter starts with an empty window: the tracker starts over too (mbIsTheFirstImage, Tracker.cc:88), or its
     // histories would be longer than the window they refer to
     if (h->front_end) {
@@ -967,12 +976,24 @@ static void launch_imu_pose(rvio_hip* h, hipStream_t st, int instances, const do
     hipLaunchKernelGGL(imu_pose_kernel, dim3((unsigned)l.gx), dim3((unsigned)l.threads), l.lds, st, h->dc.small_angle, h->dc.gravity, instances, x, h->slab_bytes, d_imu, imu_bs, m,
                        (unsigned long long*)out, out_stride, seq0, cap, img_count);
 }
+// imu_cov_kernel (imu_cov.hip) beside it: the same operands plus the 24 x 24 head of P, the same addressing of `out`
+static void launch_imu_cov(rvio_hip* h, hipStream_t st, int instances, const double* x, const double* P, const rvio_imu* d_imu, size_t imu_bs, int m, rvio_imu_cov* out,
+                           long long out_stride, long long seq0, int cap, int img_count) {
+    const LpLaunch l = imu_cov_launch(instances);
+    hipLaunchKernelGGL(imu_cov_kernel, dim3((unsigned)l.gx), dim3((unsigned)l.threads), l.lds, st, h->dc.small_angle, h->dc.gravity, h->dc.sg2, h->dc.swg2, h->dc.sa2, h->dc.swa2, instances, x, P,
+                       h->dc.dmax, h->slab_bytes, d_imu, imu_bs, m, (unsigned long long*)out, out_stride, seq0, cap, img_count);
+}
 // The IMU-rate ring's launch: directly in front of whatever propagates in place, on the stream that propagate runs on (it reads the state that
 // propagate is about to overwrite, and the same samples).  img_count: nImageCountAfterInit of the frame that consumes the samples.
 static int imu_ring_record(rvio_hip* h, const rvio_imu* d_imu, int m, size_t imu_bs, hipStream_t st, int img_count) {
     if (!h->imuo.on || m <= 0) return RVIO_OK;
     launch_imu_pose(h, st, h->batch, h->x[h->cur], d_imu, imu_bs, m, h->imuo.ring, 0, h->imuo.seq + 1, h->imuo.cap, img_count);
     HIPCHK(h, hipGetLastError());
+    if (h->imuc.on) {   // the covariance records of the same samples: same seq, same slots
+        launch_imu_cov(h, st, h->batch, h->x[h->cur], h->P[h->cur], d_imu, imu_bs, m, h->imuc.ring, 0, h->imuo.seq + 1, h->imuo.cap, img_count);
+        HIPCHK(h, hipGetLastError());
+        h->imuc.seq = h->imuo.seq + m;
+    }
     h->imuo.seq += m;   // (counted once the launch is known to be enqueued: the getter serves nothing beyond seq)
     return RVIO_OK;
 }
@@ -1412,6 +1433,18 @@ int rvio_hip_predict_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride, int
     HIPCHK(h, hipGetLastError());
     return RVIO_OK;
 }
+// the staging of rvio_hip_predict / rvio_hip_predict_cov holds m samples and m pose records
+static int predict_staging(rvio_hip* h, int m) {
+    if (m <= h->pred_cap) return RVIO_OK;   // (every earlier call has waited for its copies: nothing reads the old blocks)
+    const int cap = std::max(std::max(2 * h->pred_cap, RVIO_HIP_MAX_IMU), (m + 63) & ~63);
+    rvio_imu* pi = nullptr; rvio_imu_pose* po = nullptr;   // (both or neither: the members change once the pair exists)
+    int rc = own_dev(h, &pi, sizeof(rvio_imu) * (size_t)cap);
+    if (rc == RVIO_OK) rc = own_dev(h, &po, sizeof(rvio_imu_pose) * (size_t)cap);
+    if (rc != RVIO_OK) { own_release(h, pi); return rc; }
+    own_release(h, h->pred_imu); own_release(h, h->pred_out);
+    h->pred_imu = pi; h->pred_out = po; h->pred_cap = cap;
+    return RVIO_OK;
+}
 // one instance, host buffers: staged through buffers of its own (the staging of the other host-buffer entry points may still be read by a
 // frame in flight), which grow with m; waits for the filter stream only, like rvio_hip_get_pose
 int rvio_hip_predict(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio_imu_pose* out) {
@@ -1419,15 +1452,7 @@ int rvio_hip_predict(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio
     { const int rc = predict_check(h); if (rc != RVIO_OK) return rc; }
     if (m == 0) return RVIO_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    if (m > h->pred_cap) {   // (every earlier call has waited for its copies: nothing reads the old blocks)
-        const int cap = std::max(std::max(2 * h->pred_cap, RVIO_HIP_MAX_IMU), (m + 63) & ~63);
-        rvio_imu* pi = nullptr; rvio_imu_pose* po = nullptr;   // (both or neither: the members change once the pair exists)
-        int rc = own_dev(h, &pi, sizeof(rvio_imu) * (size_t)cap);
-        if (rc == RVIO_OK) rc = own_dev(h, &po, sizeof(rvio_imu_pose) * (size_t)cap);
-        if (rc != RVIO_OK) { own_release(h, pi); return rc; }
-        own_release(h, h->pred_imu); own_release(h, h->pred_out);
-        h->pred_imu = pi; h->pred_out = po; h->pred_cap = cap;
-    }
+    RCCHK(predict_staging(h, m));
     HIPCHK(h, hipMemcpyAsync(h->pred_imu, imu, sizeof(rvio_imu) * (size_t)m, hipMemcpyHostToDevice, h->stream));
     launch_imu_pose(h, h->stream, 1, (const double*)((const char*)h->x[h->cur] + (size_t)instance * h->slab_bytes), h->pred_imu, 0, m, h->pred_out, m, 0, 0, h->img_count);
     HIPCHK(h, hipGetLastError());
@@ -1435,10 +1460,79 @@ int rvio_hip_predict(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RVIO_OK;
 }
+// the same plus the covariance records (imu_cov.hip); the pose records are the existing kernel's, out / d_out == NULL: covariances only
+int rvio_hip_predict_cov_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride, int m, rvio_imu_pose* d_out, int out_stride, rvio_imu_cov* d_cov, int cov_stride) {
+    if (!h || m < 0 || (m > 0 && (!d_imu || !d_cov)) || imu_stride < 0 || (imu_stride > 0 && imu_stride < m) || (d_out && out_stride < m) || cov_stride < m) return RVIO_ERR_INVALID;
+    { const int rc = predict_check(h); if (rc != RVIO_OK) return rc; }
+    if (m == 0) return RVIO_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t imu_bs = (size_t)imu_stride * sizeof(rvio_imu);
+    if (d_out) launch_imu_pose(h, h->stream, h->batch, h->x[h->cur], d_imu, imu_bs, m, d_out, out_stride, 0, 0, h->img_count);
+    launch_imu_cov(h, h->stream, h->batch, h->x[h->cur], h->P[h->cur], d_imu, imu_bs, m, d_cov, cov_stride, 0, 0, h->img_count);
+    HIPCHK(h, hipGetLastError());
+    return RVIO_OK;
+}
+int rvio_hip_predict_cov(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio_imu_pose* out, rvio_imu_cov* cov) {
+    if (!h || instance < 0 || instance >= h->batch || m < 0 || (m > 0 && (!imu || !cov))) return RVIO_ERR_INVALID;
+    { const int rc = predict_check(h); if (rc != RVIO_OK) return rc; }
+    if (m == 0) return RVIO_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    RCCHK(predict_staging(h, m));
+    if (m > h->pred_cov_cap) {   // (grows with the pair above: every earlier call has waited for its copies)
+        RCCHK(own_replace(h, &h->pred_cov, sizeof(rvio_imu_cov) * (size_t)h->pred_cap));
+        h->pred_cov_cap = h->pred_cap;
+    }
+    const size_t off = (size_t)instance * h->slab_bytes;
+    const double *xi = (const double*)((const char*)h->x[h->cur] + off), *Pi = (const double*)((const char*)h->P[h->cur] + off);
+    HIPCHK(h, hipMemcpyAsync(h->pred_imu, imu, sizeof(rvio_imu) * (size_t)m, hipMemcpyHostToDevice, h->stream));
+    if (out) launch_imu_pose(h, h->stream, 1, xi, h->pred_imu, 0, m, h->pred_out, m, 0, 0, h->img_count);
+    launch_imu_cov(h, h->stream, 1, xi, Pi, h->pred_imu, 0, m, h->pred_cov, m, 0, 0, h->img_count);
+    HIPCHK(h, hipGetLastError());
+    if (out) HIPCHK(h, hipMemcpyAsync(out, h->pred_out, sizeof(rvio_imu_pose) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(cov, h->pred_cov, sizeof(rvio_imu_cov) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RVIO_OK;
+}
+static bool imuc_too_large(rvio_hip* h, int capacity) {
+    const size_t bytes = (size_t)capacity * h->batch * sizeof(rvio_imu_cov);
+    if (bytes <= ((size_t)1 << 30)) return false;
+    h->err = std::string(h->imuc.noun) + " ring of " + std::to_string(capacity) + " x " + std::to_string(h->batch) + " records = " + std::to_string(bytes) + " bytes exceeds 1 GiB";
+    return true;
+}
 // the ring: rvio_hip_set_odometry's clauses, one record per IMU sample instead of one per frame
-int rvio_hip_set_imu_odometry(rvio_hip* h, int capacity) { return h ? ring_set_capacity(h, h->imuo, capacity, 1048576) : RVIO_ERR_INVALID; }
+// (a covariance ring that exists follows every change of capacity: both rings are reallocated and emptied, or neither)
+int rvio_hip_set_imu_odometry(rvio_hip* h, int capacity) {
+    if (!h) return RVIO_ERR_INVALID;
+    const bool both = h->imuc.ring && capacity > 0 && capacity <= 1048576 && capacity != h->imuo.cap;
+    if (both && imuc_too_large(h, capacity)) return RVIO_ERR_UNSUPPORTED;
+    RCCHK(ring_set_capacity(h, h->imuo, capacity, 1048576));
+    if (both) {
+        const bool on = h->imuc.on;
+        RCCHK(ring_set_capacity(h, h->imuc, capacity, 1048576));
+        h->imuc.on = on; h->imuc_first = 1;
+    }
+    return RVIO_OK;
+}
 int rvio_hip_get_imu_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_imu_pose* out, int32_t* n) {
     return h ? ring_read(h, h->imuo, instance, first_seq, max_n, out, n) : RVIO_ERR_INVALID;
+}
+// the covariance ring beside it: the IMU-rate ring's capacity, seq and slots
+int rvio_hip_set_imu_odometry_cov(rvio_hip* h, int enable) {
+    if (!h || (enable != 0 && enable != 1)) return RVIO_ERR_INVALID;
+    if (!enable) { h->imuc.on = false; return RVIO_OK; }
+    if (!ring_exists(h, h->imuo)) return RVIO_ERR_STATE;
+    if (h->imuc.on) return RVIO_OK;
+    if (h->imuc.cap != h->imuo.cap) {
+        if (imuc_too_large(h, h->imuo.cap)) return RVIO_ERR_UNSUPPORTED;
+        RCCHK(ring_set_capacity(h, h->imuc, h->imuo.cap, 1048576));
+    }
+    h->imuc.on = true;
+    h->imuc_first = h->imuo.seq + 1;   // the getter serves what is recorded from here on
+    return RVIO_OK;
+}
+int rvio_hip_get_imu_odometry_cov(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_imu_cov* out, int32_t* n) {
+    if (!h) return RVIO_ERR_INVALID;
+    return ring_read(h, h->imuc, instance, std::max<int64_t>(first_seq, h->imuc_first), max_n, out, n);
 }
 
 // ------------------------------------------------------------------ auxiliary measurement update (aux_update.hip)
@@ -2488,7 +2582,7 @@ int rvio_hip_debug_tracked(rvio_hip* h, int n, float* xy, float* un_xy) {
 // hot kernel on the operands left behind by the last frame: which = 0 -> solve kernel (W = T^-1 + injection),
 // 1 -> klt_kernel3 on the two resident pyramids, 2 -> feat_build_kernel.  Outputs land in scratch / are idempotent.
 int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us) {
-    if (!h || !avg_us || iters < 1 || which < 0 || which > 13) return RVIO_ERR_INVALID;
+    if (!h || !avg_us || iters < 1 || which < 0 || which > 14) return RVIO_ERR_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
     { const int rcd = drain_all(h); if (rcd != RVIO_OK) return rcd; }   // (every queue of the handle: the run-ahead image chains too)
     const DevCfg& d = h->dc;
@@ -2502,8 +2596,9 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
     if (which == 10 && !h->lm.count) return RVIO_ERR_UNSUPPORTED;
     if (which == 11 && (h->pix_fmt == RVIO_PIX_MONO8 || !h->last.gray_src)) { h->err = "no colour or raw image has been handed over (rvio_hip_set_image_format)"; return RVIO_ERR_UNSUPPORTED; }
     if (which == 12 && !ring_exists(h, h->odom)) return RVIO_ERR_UNSUPPORTED;
-    if (which == 13) {
+    if (which == 13 || which == 14) {
         if (!ring_exists(h, h->imuo)) return RVIO_ERR_UNSUPPORTED;
+        if (which == 14 && !h->imuc.on) { h->err = "the IMU-rate covariance ring is off (rvio_hip_set_imu_odometry_cov)"; return RVIO_ERR_UNSUPPORTED; }
         if (!h->time_imu || h->time_m < 1) { h->err = "no frame has propagated an IMU batch yet"; return RVIO_ERR_UNSUPPORTED; }
     }
     // the hook's temporaries and its two events: released when this scope ends, whichever return ends it
@@ -2518,6 +2613,8 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
     if (which == 12) RCCHK(tmps.dev(&odt, sizeof(rvio_odom) * h->batch));
     rvio_imu_pose* ipt = nullptr;    // (13: into a buffer of its own, in the ring's layout: the ring stays what the frames wrote)
     if (which == 13) RCCHK(tmps.dev(&ipt, sizeof(rvio_imu_pose) * (size_t)h->time_m * h->batch));
+    rvio_imu_cov* ict = nullptr;     // (14: likewise)
+    if (which == 14) RCCHK(tmps.dev(&ict, sizeof(rvio_imu_cov) * (size_t)h->time_m * h->batch));
     LmOut lmt = {nullptr, nullptr, nullptr, nullptr, 0};
     if (which == 10) {   // (into buffers of its own: the getter's cloud stays the last update's)
         RCCHK(lm_alloc(h, &lmt));
@@ -2538,6 +2635,9 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
         } else
         if (which == 13) {   // imu_pose_kernel as the ring launches it: the IMU batch of the last frame (the caller's device buffer must still be alive), the state that frame left
             launch_imu_pose(h, h->stream, h->batch, h->x[h->cur], h->time_imu, h->time_imu_bs, h->time_m, ipt, 0, 1, h->time_m, h->img_count);
+        } else
+        if (which == 14) {   // imu_cov_kernel as the ring launches it, on the same operands
+            launch_imu_cov(h, h->stream, h->batch, h->x[h->cur], h->P[h->cur], h->time_imu, h->time_imu_bs, h->time_m, ict, 0, 1, h->time_m, h->img_count);
         } else
         if (which == 10) {
             // landmark_kernel as the update launches it, on the hand-over table, accept flags and (phi, psi, rho) of the last update; the state

@@ -30,6 +30,7 @@ SYMBOLS = [
     "rvio_calibration_from_config", "rvio_hip_set_calibration_at", "rvio_hip_set_calibrations", "rvio_hip_get_calibration_at", "rvio_hip_initialize_at",
     "rvio_hip_predict", "rvio_hip_predict_dev", "rvio_hip_set_imu_odometry", "rvio_hip_get_imu_odometry",
     "rvio_hip_update_aux", "rvio_hip_update_aux_dev", "rvio_hip_get_aux_diag",
+    "rvio_hip_predict_cov", "rvio_hip_predict_cov_dev", "rvio_hip_set_imu_odometry_cov", "rvio_hip_get_imu_odometry_cov",
 ]
 
 _LIB = None
@@ -430,7 +431,7 @@ class RvioHip:
         return xy, un
 
     def time_kernel(self, which, iters=20):
-        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection, 10 the landmark cloud kernel, 11 the gray conversion of the last colour or raw (16-bit, Bayer) image in the form the frame launched, 12 the odometry record kernel, 13 the IMU-pose kernel on the state and IMU batch of the last frame (HIP events, handle stream)"""
+        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection, 10 the landmark cloud kernel, 11 the gray conversion of the last colour or raw (16-bit, Bayer) image in the form the frame launched, 12 the odometry record kernel, 13 the IMU-pose kernel on the state and IMU batch of the last frame, 14 the IMU-covariance kernel on the same operands (HIP events, handle stream)"""
         us = C.c_float(0)
         self._ck(self.L.rvio_hip_debug_time_kernel(self.h, int(which), int(iters), C.byref(us)), "debug_time_kernel")
         return float(us.value)
@@ -518,6 +519,35 @@ class RvioHip:
         n = C.c_int32(0)
         self._ck(self.L.rvio_hip_get_imu_odometry(self.h, int(instance), C.c_int64(int(first_seq)), cap,
                                                   out.ctypes.data_as(C.POINTER(abi.ImuPose)) if len(out) else None, C.byref(n)), "get_imu_odometry")
+        return out[: n.value].copy()
+
+    # ---- IMU-rate odometry with covariance (PreIntegrator.cc:123-142 kept per sample, composed as System.cc:325-365)
+    def predict_cov(self, imu, instance=0, poses=True):
+        """predict plus the covariance record of every sample: (abi.IMU_POSE_DTYPE records or None, abi.IMU_COV_DTYPE records); mutates nothing"""
+        imu = np.ascontiguousarray(imu)
+        out = np.zeros(len(imu), abi.IMU_POSE_DTYPE) if poses else None
+        cov = np.zeros(len(imu), abi.IMU_COV_DTYPE)
+        self._ck(self.L.rvio_hip_predict_cov(self.h, int(instance), imu.ctypes.data_as(C.POINTER(abi.rvio_imu)) if len(imu) else None, len(imu),
+                                             out.ctypes.data_as(C.POINTER(abi.ImuPose)) if poses and len(imu) else None,
+                                             cov.ctypes.data_as(C.POINTER(abi.ImuCov)) if len(cov) else None), "predict_cov")
+        return out, cov
+
+    def predict_cov_dev(self, d_imu_ptr, imu_stride, m, d_out_ptr, out_stride, d_cov_ptr, cov_stride):
+        """the same for every instance, device buffers, asynchronous on the filter stream: d_cov[z * cov_stride + j]; d_out_ptr None / 0: covariances only"""
+        self._ck(self.L.rvio_hip_predict_cov_dev(self.h, C.c_void_p(d_imu_ptr), int(imu_stride), int(m), C.c_void_p(d_out_ptr) if d_out_ptr else None, int(out_stride),
+                                                 C.c_void_p(d_cov_ptr), int(cov_stride)), "predict_cov_dev")
+
+    def set_imu_odometry_cov(self, enable):
+        """keep an rvio_imu_cov record beside every record of the IMU-rate ring from now on (that ring's capacity, seq and slots); 0: off"""
+        self._ck(self.L.rvio_hip_set_imu_odometry_cov(self.h, int(enable)), "set_imu_odometry_cov")
+
+    def get_imu_odometry_cov(self, instance=0, first_seq=1, max_n=None):
+        """covariance records of one instance still in the ring with seq >= first_seq, oldest first (at most max_n): abi.IMU_COV_DTYPE"""
+        cap = getattr(self, "_imuo_cap", 0) if max_n is None else int(max_n)
+        out = np.zeros(max(cap, 0), abi.IMU_COV_DTYPE)
+        n = C.c_int32(0)
+        self._ck(self.L.rvio_hip_get_imu_odometry_cov(self.h, int(instance), C.c_int64(int(first_seq)), cap,
+                                                      out.ctypes.data_as(C.POINTER(abi.ImuCov)) if len(out) else None, C.byref(n)), "get_imu_odometry_cov")
         return out[: n.value].copy()
 
     # ---- auxiliary measurement update (Updater.cc:540-619 with a full-width H)
