@@ -124,6 +124,17 @@ bool parse_settings(const std::string& text, Settings* out, std::string* err) {
     out->cam_time_offset = num("Camera.nTimeOffset", 0.0);
     out->record_outputs = (int)num("INI.RecordOutputs", 0.0);
     out->is_rgb = (int)num("Camera.RGB", 0.0);
+    {   // Standstill.*: optional, never reported as missing; the defaults follow the IMU densities read above
+        auto opt = [&](const char* k, double dflt) { auto it = y.num.find(k); return it != y.num.end() ? it->second : dflt; };
+        rvio_standstill_config& z = out->standstill;
+        rvio_standstill_config_default(&c, &z);
+        out->standstill_enable = (int)opt("Standstill.Enable", 0.0);
+        z.sigma_a = opt("Standstill.SigmaA", z.sigma_a); z.sigma_w = opt("Standstill.SigmaW", z.sigma_w);
+        z.imu_thr = opt("Standstill.ImuThr", z.imu_thr); z.disp_thr_px = opt("Standstill.DispThrPx", z.disp_thr_px);
+        z.min_pairs = (int)opt("Standstill.MinPairs", z.min_pairs);
+        z.sigma_v = opt("Standstill.SigmaV", z.sigma_v); z.sigma_bg = opt("Standstill.SigmaBg", z.sigma_bg);
+        z.bias_rows = (int)opt("Standstill.BiasRows", z.bias_rows); z.gate = (int)opt("Standstill.Gate", z.gate);
+    }
     out->encoding.clear();
     auto e = y.str.find("Camera.Encoding");
     if (e != y.str.end()) {
@@ -165,9 +176,19 @@ System::System(const Settings& s, int device) : s_(s) {
     if (rc != RVIO_OK) {
         err_ = std::string("rvio_hip_create: ") + (h_ ? rvio_hip_last_error(h_) : "invalid configuration") + " (status " + std::to_string(rc) + ")";
         if (h_) { rvio_hip_destroy(h_); h_ = nullptr; }
+        return;
+    }
+    if (s_.standstill_enable) {   // (a handle that is never told keeps the launches it had)
+        if (rvio_hip_set_standstill(h_, &s_.standstill) != RVIO_OK) {
+            err_ = std::string("Standstill.*: ") + rvio_hip_last_error(h_);
+            rvio_hip_destroy(h_); h_ = nullptr;
+            return;
+        }
+        ss_on_ = true;
     }
 }
 System::~System() {
+    if (!ss_path_.empty()) (void)flush_standstill();
     if (f_od_ && h_) (void)flush_odometry();
     if (f_io_ && h_) (void)flush_imu_odometry();
     delete static_cast<std::ofstream*>(f_od_);
@@ -351,6 +372,41 @@ int System::zero_velocity(double sigma, bool gate) {
     return velocity(z, sigma, gate);
 }
 
+// behind a frame: the decision and, where the platform stands still, the zero-velocity update — on the device, nothing waited for unless the
+// records are asked for
+int System::standstill(double t, const rvio_imu* imu, int m) {
+    if (m < 1) return 0;
+    if (rvio_hip_standstill(h_, imu, m, 1) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+    if (!ss_path_.empty()) {
+        rvio_standstill r;
+        if (rvio_hip_get_standstill(h_, 0, &r) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+        ss_recs_.emplace_back(t, r);
+    }
+    return 0;
+}
+bool System::record_standstill_to(const std::string& path) {
+    if (!h_) return false;
+    if (!ss_on_) { err_ = "--standstill needs Standstill.Enable: 1 in the settings"; return false; }
+    std::ofstream f(path, std::ofstream::out);   // (created now: an unwritable path fails here, not after the replay)
+    if (!f) { err_ = "cannot write " + path; return false; }
+    ss_path_ = path;
+    ss_recs_.clear();
+    return true;
+}
+int System::flush_standstill() {
+    if (ss_path_.empty()) return 0;
+    std::ofstream f(ss_path_, std::ofstream::out);
+    if (!f) { err_ = "cannot write " + ss_path_; return -1; }
+    for (const auto& tr : ss_recs_) f << format_standstill(tr.first, tr.second);
+    f.flush();
+    return f ? 0 : -1;
+}
+std::string format_standstill(double t, const rvio_standstill& r) {
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "%.19g %.19g %.19g %d %d %.19g\n", t, r.T, r.disparity, (int)r.n_pairs, (int)r.flags, r.gamma);
+    return buf;
+}
+
 int System::MonoVIO(PoseLine* pose) {
     ImageData image;
     std::vector<ImuData> imus;
@@ -410,6 +466,7 @@ int System::MonoVIO(PoseLine* pose) {
     // the timed body of MonoVIO (System.cc:253-367): track -> propagate -> update -> augment -> compose
     if (!rec_) {
         if (rvio_hip_frame(h_, image.px.data(), row_bytes, pi, m, nullptr, 0) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+        if (ss_on_ && standstill(image.t, pi, m) < 0) return -1;   // (ahead of the pose read-back: the pose line is the updated state's)
         if (pose) {
             pose->t = image.t;
             if (rvio_hip_get_pose(h_, pose->p, pose->q) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
@@ -430,6 +487,7 @@ int System::MonoVIO(PoseLine* pose) {
     if (rvio_hip_propagate(h_, pi, m) != RVIO_OK) return fail();                          // System.cc:263
     if (do_update && rvio_hip_update_tracked(h_) != RVIO_OK) return fail();               // System.cc:266-268
     if (rvio_hip_augment_compose(h_, do_augment) != RVIO_OK) return fail();               // System.cc:279-365
+    if (ss_on_ && standstill(image.t, pi, m) < 0) return -1;
     PoseLine pl;
     pl.t = image.t;
     if (rvio_hip_get_pose(h_, pl.p, pl.q) != RVIO_OK) return fail();                      // (waits for the filter stream)

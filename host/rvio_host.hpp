@@ -52,6 +52,11 @@ struct Settings {
     int record_outputs = 0;       // INI.RecordOutputs
     int is_rgb = 0;               // Camera.RGB (Tracker.cc:64-65): channel order of a 3 / 4-channel image, 1 = RGB(A), 0 = BGR(A)
     std::string encoding;         // Camera.Encoding (optional): sensor_msgs' name of what the camera delivers — the only way to declare a Bayer mosaic
+    // Standstill.* (all optional; no reference counterpart): Standstill.Enable: 1 switches the device-side standstill detector and its zero-velocity
+    // update on (rvio_hip_set_standstill); .SigmaA .SigmaW .ImuThr .DispThrPx .MinPairs .SigmaV .SigmaBg .BiasRows .Gate override the members of
+    // rvio_standstill_config_default, a missing key keeps its default.  Enable: 0 or absent: the host does the calls it did before the keys existed
+    int standstill_enable = 0;
+    rvio_standstill_config standstill;
     std::vector<std::string> missing;   // keys the reference reads (cv::FileStorage would yield 0 for them) that the file does not hold:
                                         // they keep the EuRoC defaults here, and the caller is told (rvio_replay prints them)
 };
@@ -128,6 +133,13 @@ public:
     int update_aux(const rvio_aux_meas& meas);
     int zero_velocity(double sigma, bool gate);
     int velocity(const double v[3], double sigma, bool gate);
+    // Standstill.Enable: 1: MonoVIO calls rvio_hip_standstill(the IMU samples of the frame, apply = 1) behind every frame once the filter is
+    // initialised — the device decides, the host sees nothing.  record_standstill_to: additionally read the record of every frame through
+    // rvio_hip_get_standstill (its wait for the filter stream is the only synchronisation this adds, and only when the file is asked for) into a
+    // host-side vector, written ONCE at the end (flush_standstill, also run by the destructor): one line per frame, format_standstill
+    bool record_standstill_to(const std::string& path);
+    int flush_standstill();       // 0, or -1 when the file cannot be written (error())
+    bool standstill_enabled() const { return ss_on_; }
     // columns of an auxiliary H right now: 24 + 6 clones, the clones counted as the library counts them (one per frame behind the first, up
     // to Tracker.nMaxTrackingLength - 1) — no read-back
     int state_dim() const;
@@ -167,6 +179,10 @@ private:
     bool io_cov_ = false;         // record_imu_odometry_to(with_cov)
     std::vector<rvio_imu_cov> ioc_buf_;
     int note_imu_odometry(int m);
+    bool ss_on_ = false;          // Standstill.Enable and rvio_hip_set_standstill succeeded
+    std::string ss_path_;         // record_standstill_to
+    std::vector<std::pair<double, rvio_standstill>> ss_recs_;
+    int standstill(double t, const rvio_imu* imu, int m);
 };
 
 // 8- or 16-bit PNG (non-interlaced; gray, RGB or RGBA: channels in file order = RGB) or binary PGM / PPM (P5 / P6; maxval 255: 8 bits, 256 ..
@@ -190,6 +206,8 @@ std::string format_imu_odometry(const rvio_imu_pose& r);
 // the same line with the paired covariance record behind it: the 21 entries of pose_cov's upper triangle row by row (c00 c01 ... c05 c11 ... c55, order
 // x y z rotX rotY rotZ), then the 6 of vel_cov's (v00 v01 v02 v11 v12 v22), %.19g
 std::string format_imu_odometry_cov(const rvio_imu_pose& r, const rvio_imu_cov& c);
+// one standstill record: t T disparity n_pairs flags gamma, %.19g
+std::string format_standstill(double t, const rvio_standstill& r);
 std::string format_time_cost(int n_img, double track_ms, double filter_ms);   // one line of time_cost.dat (System.cc:376-378)
 
 }  // namespace rvio

@@ -11,7 +11,10 @@
 //                                        --odometry: pose, velocity and pose covariance of every frame, read in bulk from the handle's ring of N
 //                                        records (default 256; System::record_odometry_to); without <poses_out.dat> no frame is drained for its pose
 //                                        --landmarks: Updater::update's landmark cloud behind every updating frame (System::record_landmarks_to)
-//                                        [--velocity FILE [--velocity-sigma S] [--velocity-gate]]
+//                                        [--velocity FILE [--velocity-sigma S] [--velocity-gate]] [--standstill FILE]
+//                                        --standstill: with Standstill.Enable: 1 in the settings (the device-side standstill detector and its
+//                                        zero-velocity update behind every frame), one line per frame `t T disparity n_pairs flags gamma`, kept on the
+//                                        host and written once at the end
 //                                        --velocity: a CSV of `t_ns, vx, vy, vz` — the velocity in the IMU frame, e.g. from wheel encoders — fused on the
 //                                        device (System::velocity) right behind the frame whose image stamp is nearest to t_ns, within half an image
 //                                        period; at most one row per frame (the last one wins), rows that match no frame are counted and the count is
@@ -51,7 +54,11 @@ static int check_settings(const char* path) {
                 c.qual_lvl, c.block_x, c.block_y, c.enable_equalizer, c.use_sampson, c.inlier_thr, c.ini_thr_angle, c.ini_thr_displ,
                 c.ini_enable_alignment, s.cam_time_offset, s.record_outputs, s.is_rgb);
     for (int i = 0; i < 16; ++i) std::printf("%s%.17g", i ? ", " : "", c.T_bc[i]);
-    std::printf("], \"encoding\": \"%s\"}\n", s.encoding.c_str());
+    const rvio_standstill_config& z = s.standstill;   // Standstill.* (optional keys)
+    std::printf("], \"standstill\": {\"enable\": %d, \"sigma_a\": %.17g, \"sigma_w\": %.17g, \"imu_thr\": %.17g, \"disp_thr_px\": %.17g, \"min_pairs\": %d, "
+                "\"sigma_v\": %.17g, \"sigma_bg\": %.17g, \"bias_rows\": %d, \"gate\": %d}",
+                s.standstill_enable, z.sigma_a, z.sigma_w, z.imu_thr, z.disp_thr_px, (int)z.min_pairs, z.sigma_v, z.sigma_bg, (int)z.bias_rows, (int)z.gate);
+    std::printf(", \"encoding\": \"%s\"}\n", s.encoding.c_str());
     return 0;
 }
 
@@ -291,7 +298,7 @@ int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--record-dir DIR] [--record]\n"
                              "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--imu-odometry-cov] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n"
-                             "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate]\n", argv[0]);
+                             "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate] [--standstill FILE]\n", argv[0]);
         return 2;
     }
     const char* out_path = nullptr;
@@ -300,6 +307,7 @@ int main(int argc, char** argv) {
     const char* odometry = nullptr; int odometry_ring = 256;
     const char* imu_odometry = nullptr; int imu_odometry_ring = 4096; bool imu_odometry_cov = false;
     const char* velocity = nullptr; double velocity_sigma = 0.05; bool velocity_gate = false;
+    const char* standstill = nullptr;
     const char* record_dir = "."; bool force_record = false, sync_every = false, self = false; int noise_wgs = 0;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -319,6 +327,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--velocity") && i + 1 < argc) velocity = argv[++i];   // `t_ns, vx, vy, vz` rows fused behind the nearest frame (System::velocity)
         else if (!std::strcmp(argv[i], "--velocity-sigma") && i + 1 < argc) velocity_sigma = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--velocity-gate")) velocity_gate = true;
+        else if (!std::strcmp(argv[i], "--standstill") && i + 1 < argc) standstill = argv[++i];   // one line per frame: t T disparity n_pairs flags gamma (needs Standstill.Enable: 1)
         else out_path = argv[i];
     }
     Settings s; std::string err;
@@ -351,6 +360,7 @@ int main(int argc, char** argv) {
     if (landmarks && !sys.record_landmarks_to(landmarks)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (odometry && !sys.record_odometry_to(odometry, odometry_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (imu_odometry && !sys.record_imu_odometry_to(imu_odometry, imu_odometry_ring, imu_odometry_cov)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
+    if (standstill && !sys.record_standstill_to(standstill)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     std::ofstream out;
     if (out_path) { out.open(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } }
 
@@ -377,7 +387,7 @@ int main(int argc, char** argv) {
         if (rc == 1) { ++n_frames; if (out.is_open()) out << format_pose(p); }
         if (rc == 1 && apply_velocity(sys, vr, image_k) < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     }
-    if (sys.flush_odometry() < 0 || sys.flush_imu_odometry() < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
+    if (sys.flush_odometry() < 0 || sys.flush_imu_odometry() < 0 || sys.flush_standstill() < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     std::fprintf(stderr, "rvio_replay: %ld images, %ld filtered frames, %.3f ms per MonoVIO call (host wall clock, pose read-back included)\n",
                  n_images, n_frames, n_images ? 1e3 * t_filter / n_images : 0.0);
     if (vr) print_velocity(*vr);

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov) */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov); standstill detection (rvio_standstill_config, rvio_standstill, rvio_standstill_config_default, rvio_hip_set_standstill, rvio_hip_standstill, rvio_hip_standstill_dev, rvio_hip_get_standstill) */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -527,6 +527,68 @@ int rvio_hip_update_aux_dev(rvio_hip* h, int m, int mode, int gate, const double
 /* gamma (as compared: |v~^T S^-1 v~|) and applied (1 applied; 0 gated out, inactive or a bad pivot) of one instance in the LAST call.  Waits
  * for the filter stream only.  RVIO_ERR_STATE before the first rvio_hip_update_aux* call; RVIO_ERR_INVALID: instance out of range. */
 int rvio_hip_get_aux_diag(rvio_hip* h, int instance, double* gamma, int32_t* applied);
+
+/* --- standstill detection and automatic zero-velocity update (no reference counterpart during operation; System.cc:185-250 tests only
+ *     in front of initialisation) ------------------------------------------------ */
+/* Decides ON THE DEVICE, per instance, whether the platform stands still, and — with apply = 1 — hands that decision to the auxiliary update
+ * above as its d_active flags: a zero-velocity update (and optionally a gyro-bias update) of exactly the instances that are static, without the
+ * host seeing the biases, the tracker's points or the decision.  One launch of standstill_kernel (csrc/standstill.hip), one workgroup per
+ * instance, then aux_update_kernel right behind it.
+ * IMU statistic (SHOE / GLRT, Skog et al. 2010; no attitude in it): with bg = x[20..22], ba = x[23..25] of the instance's current state,
+ * G = cfg.gravity and the m samples handed in,
+ *     a^_j = a_j - ba,  w^_j = w_j - bg,  a_ = mean(a^_j),  u = a_ / |a_|
+ *     T = (1/m) sum_j ( |a^_j - G u|^2 / sigma_a^2 + |w^_j|^2 / sigma_w^2 ),     imu_static = (T < imu_thr)
+ *   (|a_| = 0 or a non-finite T: not static).
+ * Image statistic (handles with a front end): over the live points with at least two observations, the mean length in PIXELS of the step
+ *   between the last two observations of the tracking history, (fx dx, fy dy) with the instance's calibration.  It can only veto:
+ *     img_static = (disp_thr_px <= 0) || (n_pairs < min_pairs) || (disparity < disp_thr_px)
+ *   A handle without front end reports n_pairs = 0, disparity = 0, img_static = 1.
+ * is_static = imu_static && img_static.
+ * The update (apply = 1): RVIO_AUX_VALUE, rows 0..2: H = I at the velocity columns 15..17, z = 0, sigma_v; with bias_rows = 1 three more rows,
+ *   H = I at the gyro-bias columns 18..20, z = the mean RAW gyro reading of the batch (at rest w_m = bg + noise), sigma_bg.  Everything
+ *   rvio_hip_update_aux_dev documents holds: in place, pose line rewritten, no ring record, a kept clone-block factor dropped, an instance that
+ *   is not static (or gated out) not written at all.
+ * The defaults of rvio_standstill_config_default are TUNING VALUES, not measurements: sigma_a / sigma_w are the discrete-time form of the
+ *   configured densities (cfg.sigma_a sqrt(imu_rate), cfg.sigma_g sqrt(imu_rate)), under which T has mean ~ 6, imu_thr = 12 is twice that;
+ *   disp_thr_px = 0.5, min_pairs = 20, sigma_v = 0.05, sigma_bg = sigma_w, bias_rows = 0, gate = 1.
+ * NOT done: a static frame still runs its camera update and augments a clone (skipping both would change the frame path); the accelerometer
+ *   rows a_m = ba + R g are not fused (not linear in additive coordinates). */
+typedef struct rvio_standstill_config {   /* 64 bytes, no padding */
+    double sigma_a, sigma_w;      /* detector noise, m/s^2 and rad/s per sample, finite and > 0 */
+    double imu_thr;               /* > 0 */
+    double disp_thr_px;           /* <= 0: image test off */
+    double sigma_v, sigma_bg;     /* the update's standard deviations, finite and > 0 */
+    int32_t min_pairs;            /* >= 1 */
+    int32_t bias_rows;            /* 0 | 1 */
+    int32_t gate;                 /* 0 | 1: the aux update's chi-square gate */
+    int32_t reserved;
+} rvio_standstill_config;
+typedef struct rvio_standstill {          /* 40 bytes, no padding */
+    double T;            /* the IMU statistic, as computed */
+    double disparity;    /* px, 0 with n_pairs == 0 */
+    double gamma;        /* the aux update's, 0 when not applied */
+    int32_t n_pairs;
+    int32_t flags;       /* bit 0 imu_static, 1 img_static, 2 is_static, 3 applied */
+    int32_t m;           /* samples looked at */
+    int32_t img_count;   /* the handle's frame count at the call */
+} rvio_standstill;
+void rvio_standstill_config_default(const rvio_config* cfg, rvio_standstill_config* out);
+/* Switches the feature on with *c (copied), or off with NULL.  Nothing is allocated before the first rvio_hip_standstill* call (then: records,
+ * flags, v, H at 6 x d_max, sigma — outside the filter slab); a handle that never calls this allocates and launches what it did before.
+ * RVIO_ERR_INVALID: NULL handle or a bad member — rvio_hip_last_error names it. */
+int rvio_hip_set_standstill(rvio_hip* h, const rvio_standstill_config* c);
+/* One decision per instance from m IMU samples (host buffer: every instance sees the same batch; _dev: device buffer, instance z reads
+ * d_imu + z * imu_stride, imu_stride = 0: shared, else >= m — the rules of rvio_hip_predict_dev).  apply: 0 = detect only: nothing but the
+ * standstill records changes; 1 = the update above on the static instances.  Asynchronous on rvio_hip_stream, no host wait: the detector is
+ * ordered behind the book-keeping of the last frame and in front of the next one's by stream events (it runs on the stream that runs
+ * book-keeping; the filter stream waits for it in front of the update).  Call it between whole frames or between the stage entry points, on
+ * every rank of a sharded handle alike.  RVIO_ERR_STATE: no state yet, rvio_hip_set_standstill not called (or called with NULL), between
+ * rvio_hip_frame_begin_dev and rvio_hip_frame_end.  RVIO_ERR_INVALID: NULL handle or buffer, m < 1, apply not 0 | 1, a stride too short. */
+int rvio_hip_standstill(rvio_hip* h, const rvio_imu* imu, int m, int apply);
+int rvio_hip_standstill_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride, int m, int apply);
+/* The record of one instance from the LAST rvio_hip_standstill* call; waits for the filter stream only.  RVIO_ERR_STATE before the first such
+ * call; RVIO_ERR_INVALID: NULL argument, instance out of range. */
+int rvio_hip_get_standstill(rvio_hip* h, int instance, rvio_standstill* out);
 
 /* --- feature-sharded updater (no reference counterpart) ------ */
 /* Stage A: per-feature build + gate on the features f with f % world == rank,

@@ -408,6 +408,81 @@ def aux_update_model(x, P, H, v, sigma, mode=RVIO_AUX_RESIDUAL):
     return inject_state(x, K @ rw), 0.5 * (Pn + Pn.T), gamma
 
 
+# ---- standstill detection (rvio_hip_standstill*, csrc/standstill.hip)
+class rvio_standstill_config(C.Structure):
+    """detector and update settings: 64 bytes, no padding"""
+    _fields_ = [("sigma_a", C.c_double), ("sigma_w", C.c_double), ("imu_thr", C.c_double), ("disp_thr_px", C.c_double),
+                ("sigma_v", C.c_double), ("sigma_bg", C.c_double),
+                ("min_pairs", C.c_int32), ("bias_rows", C.c_int32), ("gate", C.c_int32), ("reserved", C.c_int32)]
+
+
+class rvio_standstill(C.Structure):
+    """the record of one instance: 40 bytes, no padding"""
+    _fields_ = [("T", C.c_double), ("disparity", C.c_double), ("gamma", C.c_double),
+                ("n_pairs", C.c_int32), ("flags", C.c_int32), ("m", C.c_int32), ("img_count", C.c_int32)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+assert C.sizeof(rvio_standstill_config) == 64 and C.sizeof(rvio_standstill) == 40
+SS_IMU_STATIC, SS_IMG_STATIC, SS_IS_STATIC, SS_APPLIED = 1, 2, 4, 8
+
+
+def standstill_config_default(cfg, **over):
+    """the tuning values of C rvio_standstill_config_default (NOT measurements): the discrete-time form of the configured densities, twice the
+    mean of T under them, half a pixel, 20 pairs, 5 cm/s"""
+    c = rvio_standstill_config()
+    c.sigma_a = cfg.sigma_a * math.sqrt(cfg.imu_rate)
+    c.sigma_w = cfg.sigma_g * math.sqrt(cfg.imu_rate)
+    c.imu_thr, c.disp_thr_px, c.sigma_v, c.sigma_bg = 12.0, 0.5, 0.05, c.sigma_w
+    c.min_pairs, c.bias_rows, c.gate, c.reserved = 20, 0, 1, 0
+    for k, v in over.items():
+        setattr(c, k, v)
+    return c
+
+
+def standstill_model(x, imu, pairs_prev, pairs_cur, fx, fy, G, cfg):
+    """NumPy float64 model of csrc/standstill.hip: (T, w_mean, disparity, n_pairs, flags without the `applied` bit).
+    x: the state (bg = x[20:23], ba = x[23:26]); imu: abi.IMU_DTYPE records; pairs_prev / pairs_cur: the last two observations of every live
+    point that has two, n x 2 NORMALISED coordinates (None or empty: no front end / no pairs); cfg: rvio_standstill_config"""
+    x = np.asarray(x, float)
+    w = np.asarray(imu["w"], float).reshape(-1, 3) - x[20:23]
+    a = np.asarray(imu["a"], float).reshape(-1, 3) - x[23:26]
+    m = len(w)
+    abar = a.sum(axis=0) / m
+    an = math.sqrt(float(abar @ abar))
+    with np.errstate(all="ignore"):
+        u = abar / an
+        e = a - G * u
+        T = float(((e * e).sum(axis=1) / cfg.sigma_a ** 2 + (w * w).sum(axis=1) / cfg.sigma_w ** 2).sum() / m)
+    w_mean = w.sum(axis=0) / m + x[20:23]
+    imu_static = an > 0 and T < cfg.imu_thr
+    n_pairs, disparity = 0, 0.0
+    if pairs_prev is not None and len(pairs_prev):
+        d = np.asarray(pairs_cur, float).reshape(-1, 2) - np.asarray(pairs_prev, float).reshape(-1, 2)
+        n_pairs = len(d)
+        disparity = float(np.sqrt((fx * d[:, 0]) ** 2 + (fy * d[:, 1]) ** 2).sum() / n_pairs)
+    img_static = (not cfg.disp_thr_px > 0) or n_pairs < cfg.min_pairs or disparity < cfg.disp_thr_px
+    flags = (SS_IMU_STATIC if imu_static else 0) | (SS_IMG_STATIC if img_static else 0) | (SS_IS_STATIC if imu_static and img_static else 0)
+    return T, w_mean, disparity, n_pairs, flags
+
+
+def standstill_measurement(d, w_mean, cfg):
+    """(H, z, sigma) of the standstill update for aux_update_model / rvio_hip_update_aux in VALUE mode: zero velocity at columns 15..17 and, with
+    cfg.bias_rows, the mean raw gyro reading as a measurement of bg at columns 18..20"""
+    rows = 6 if cfg.bias_rows else 3
+    H = np.zeros((rows, d))
+    for r in range(rows):
+        H[r, 15 + r] = 1.0
+    z = np.zeros(rows)
+    sigma = np.full(rows, float(cfg.sigma_v))
+    if cfg.bias_rows:
+        z[3:6] = np.asarray(w_mean, float)
+        sigma[3:6] = float(cfg.sigma_bg)
+    return H, z, sigma
+
+
 # Camera.T_BC0 of config/rvio_euroc.yaml:55-62 (row-major)
 _T_BC0 = [0.0148655429818, -0.999880929698, 0.00414029679422, -0.0216401454975,
           0.999557249008, 0.0149672133247, 0.025715529948, -0.064676986768,

@@ -28,6 +28,7 @@
 #include "imu_pose.hip"    // IMU-rate odometry: a pose per IMU sample (rvio_hip_predict, rvio_hip_set_imu_odometry)
 #include "imu_cov.hip"     // ... and its covariance: pose_cov / vel_cov per IMU sample (rvio_hip_predict_cov, rvio_hip_set_imu_odometry_cov)
 #include "aux_update.hip"  // the auxiliary measurement update: wheel odometry, zero velocity, speed over ground (rvio_hip_update_aux)
+#include "standstill.hip"  // standstill detection in front of it: the zero-velocity update of the instances that do not move (rvio_hip_standstill)
 #pragma clang fp contract(off)
 #include "frontend_kernels.hip"
 #include "klt3.hip"
@@ -203,6 +204,20 @@ struct rvio_hip {
     double* aux_diag = nullptr;
     double *aux_pin = nullptr, *aux_stage = nullptr;
     hipEvent_t evAux = nullptr;
+    // standstill detection (standstill.hip): the configuration of rvio_hip_set_standstill; one block allocated by the first rvio_hip_standstill*
+    // call, outside the slab — records, (gamma, applied) pairs of ITS aux launches, v (6 per instance), the shared H (6 x dmax) and sigma, the
+    // flags — the staging of the host-buffer form, and the two events that order the detector against the filter stream.
+    // book_stream: the stream that ran the last book-keeping (post_klt_dev), where the detector is launched; ss_last: the stream the last detector
+    // ran on while no book-keeping has been enqueued behind it (nullptr otherwise): a book-keeping on ANOTHER stream waits for evSSb first
+    bool ss_on = false;
+    rvio_standstill_config ss_cfg = {};
+    rvio_standstill* ss_rec = nullptr;
+    double *ss_diag = nullptr, *ss_v = nullptr, *ss_H = nullptr, *ss_sigma = nullptr;
+    int* ss_active = nullptr;
+    rvio_imu* ss_imu = nullptr;
+    int ss_imu_cap = 0;
+    hipEvent_t evSSa = nullptr, evSSb = nullptr;
+    hipStream_t book_stream = nullptr, ss_last = nullptr;
     // colour input (rvio_hip_set_image_format): the gray images every stage behind gray_kernel reads instead of the caller's.  Allocated with the
     // first colour format, outside the slab (a mono handle keeps its memory layout), instance stride W * H; four in rotation like d_eq2[] (see
     // build_pyramid_dev for who reads a slot last)
@@ -576,6 +591,7 @@ static const void* lp_kernel_fn(int k) {
         case LPK_AUX_UPDATE4: return (const void*)aux_update_kernel<4>;
         case LPK_AUX_UPDATE16: return (const void*)aux_update_kernel<16>;
         case LPK_IMU_COV: return (const void*)imu_cov_kernel;
+        case LPK_STANDSTILL: return (const void*)standstill_kernel;
     }
     return nullptr;
 }
@@ -1539,21 +1555,24 @@ int rvio_hip_get_imu_odometry_cov(rvio_hip* h, int instance, int64_t first_seq, 
 static_assert(LP_AUX_MAX_ROWS == RVIO_AUX_MAX_ROWS, "launch_plan.h: the row limit of the auxiliary update");
 // strides in doubles (0: shared).  Asynchronous on the filter stream: in place on x[cur] / P[cur], no toggle
 static int update_aux_dev(rvio_hip* h, int m, int mode, int gate, const double* d_H, size_t H_stride, const double* d_v, size_t v_stride,
-                          const double* d_sigma, size_t sigma_stride, const int32_t* d_active) {
+                          const double* d_sigma, size_t sigma_stride, const int32_t* d_active, double* d_diag = nullptr) {   // d_diag: (gamma, applied) go there instead of aux_diag (the standstill update keeps its own)
     if (!h->has_state) { h->err = "rvio_hip_update_aux before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
     if (h->in_frame) { h->err = "rvio_hip_update_aux between rvio_hip_frame_begin_dev and rvio_hip_frame_end"; return RVIO_ERR_STATE; }
     HIPCHK(h, hipSetDevice(h->device));
-    if (!h->aux_diag) RCCHK(own_dev(h, &h->aux_diag, sizeof(double) * 2 * (size_t)h->batch, true));
+    if (!d_diag) {
+        if (!h->aux_diag) RCCHK(own_dev(h, &h->aux_diag, sizeof(double) * 2 * (size_t)h->batch, true));
+        d_diag = h->aux_diag;
+    }
     RCCHK(chol_drop(h, CHOL_FILTER_WAITS));   // (the update changes the covariance in place)
     const int n = h->n_clones_host;
     const LpLaunch l = aux_update_launch(n, m, h->batch);
     const size_t w = sizeof(double);
     if (l.kernel == LPK_AUX_UPDATE4)
         hipLaunchKernelGGL(aux_update_kernel<4>, lp_grid(l), lp_block(l), l.lds, h->stream, n, h->dc.dmax, m, mode, gate, h->x[h->cur], h->P[h->cur], h->d_pose, h->meta,
-                           h->slab_bytes, d_H, H_stride * w, d_v, v_stride * w, d_sigma, sigma_stride * w, (const int*)d_active, h->aux_diag);
+                           h->slab_bytes, d_H, H_stride * w, d_v, v_stride * w, d_sigma, sigma_stride * w, (const int*)d_active, d_diag);
     else
         hipLaunchKernelGGL(aux_update_kernel<16>, lp_grid(l), lp_block(l), l.lds, h->stream, n, h->dc.dmax, m, mode, gate, h->x[h->cur], h->P[h->cur], h->d_pose, h->meta,
-                           h->slab_bytes, d_H, H_stride * w, d_v, v_stride * w, d_sigma, sigma_stride * w, (const int*)d_active, h->aux_diag);
+                           h->slab_bytes, d_H, H_stride * w, d_v, v_stride * w, d_sigma, sigma_stride * w, (const int*)d_active, d_diag);
     HIPCHK(h, hipGetLastError());
     return RVIO_OK;
 }
@@ -1614,6 +1633,121 @@ int rvio_hip_get_aux_diag(rvio_hip* h, int instance, double* gamma, int32_t* app
     long long ap; std::memcpy(&ap, &buf[1], sizeof ap);
     if (gamma) *gamma = buf[0];
     if (applied) *applied = (int32_t)ap;
+    return RVIO_OK;
+}
+
+// ------------------------------------------------------------------ standstill detection (standstill.hip)
+static_assert(sizeof(rvio_standstill_config) == 64 && sizeof(rvio_standstill) == 40, "include/rvio_hip.h: the standstill structs have no padding");
+void rvio_standstill_config_default(const rvio_config* cfg, rvio_standstill_config* out) {
+    if (!cfg || !out) return;
+    std::memset(out, 0, sizeof *out);
+    // tuning values, not measurements: the discrete-time form of the configured densities; T has mean ~ 6 under them
+    out->sigma_a = cfg->sigma_a * std::sqrt(cfg->imu_rate);
+    out->sigma_w = cfg->sigma_g * std::sqrt(cfg->imu_rate);
+    out->imu_thr = 12.0;
+    out->disp_thr_px = 0.5;
+    out->sigma_v = 0.05;
+    out->sigma_bg = out->sigma_w;
+    out->min_pairs = 20; out->bias_rows = 0; out->gate = 1; out->reserved = 0;
+}
+int rvio_hip_set_standstill(rvio_hip* h, const rvio_standstill_config* c) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (!c) { h->ss_on = false; return RVIO_OK; }
+    auto pos = [](double v) { return std::isfinite(v) && v > 0; };
+    const char* bad = nullptr;
+    if (!pos(c->sigma_a)) bad = "sigma_a (finite and > 0)";
+    else if (!pos(c->sigma_w)) bad = "sigma_w (finite and > 0)";
+    else if (!pos(c->imu_thr)) bad = "imu_thr (finite and > 0)";
+    else if (std::isnan(c->disp_thr_px)) bad = "disp_thr_px (a number; <= 0: image test off)";
+    else if (!pos(c->sigma_v)) bad = "sigma_v (finite and > 0)";
+    else if (!pos(c->sigma_bg)) bad = "sigma_bg (finite and > 0)";
+    else if (c->min_pairs < 1) bad = "min_pairs (>= 1)";
+    else if (c->bias_rows != 0 && c->bias_rows != 1) bad = "bias_rows (0 | 1)";
+    else if (c->gate != 0 && c->gate != 1) bad = "gate (0 | 1)";
+    if (bad) { h->err = std::string("rvio_hip_set_standstill: bad member ") + bad; return RVIO_ERR_INVALID; }
+    h->ss_cfg = *c; h->ss_cfg.reserved = 0;
+    h->ss_on = true;
+    return RVIO_OK;
+}
+static int standstill_check(rvio_hip* h) {
+    if (!h->has_state) { h->err = "rvio_hip_standstill before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
+    if (!h->ss_on) { h->err = "rvio_hip_standstill before rvio_hip_set_standstill"; return RVIO_ERR_STATE; }
+    if (h->in_frame) { h->err = "rvio_hip_standstill between rvio_hip_frame_begin_dev and rvio_hip_frame_end"; return RVIO_ERR_STATE; }
+    return RVIO_OK;
+}
+// imu_bs: bytes between the instances' samples (0: shared)
+static int standstill_dev(rvio_hip* h, const rvio_imu* d_imu, size_t imu_bs, int m, int apply) {
+    const size_t B = (size_t)h->batch;
+    if (!h->ss_rec) {   // (one block, both events, or nothing: a failure half-way leaves the members null, and the next call starts over)
+        const size_t n_rec = sizeof(rvio_standstill) * B, n_diag = 16 * B, n_v = 48 * B, n_H = sizeof(double) * 6 * (size_t)h->dc.dmax, n_sg = 48;
+        char* blk = nullptr;
+        hipEvent_t ea = nullptr, eb = nullptr;
+        int rc = own_dev(h, &blk, n_rec + n_diag + n_v + n_H + n_sg + sizeof(int) * B, true);   // (cleared on the filter stream: whoever reads it first is ordered behind that stream below)
+        if (rc == RVIO_OK) rc = own_event(h, &ea, kEvFlags);
+        if (rc == RVIO_OK) rc = own_event(h, &eb, kEvFlags);
+        if (rc != RVIO_OK) { own_release(h, blk); own_release(h, (void*)ea); return rc; }
+        h->ss_rec = (rvio_standstill*)blk; h->ss_diag = (double*)(blk + n_rec); h->ss_v = (double*)(blk + n_rec + n_diag);
+        h->ss_H = (double*)(blk + n_rec + n_diag + n_v); h->ss_sigma = (double*)(blk + n_rec + n_diag + n_v + n_H);
+        h->ss_active = (int*)(blk + n_rec + n_diag + n_v + n_H + n_sg);
+        h->evSSa = ea; h->evSSb = eb;
+    }
+    // The detector reads hist / hist_len / slot / n_pts, which the refill half of the LAST book-keeping wrote and the NEXT one rewrites: it runs on the
+    // stream that ran the last one (stream order on both sides; post_klt_dev covers a next one on another stream), behind the filter stream (bg, ba
+    // of the current state, the IMU staging, the cleared block), and the filter stream goes on behind it.  No host wait.
+    const bool front = h->front_end;
+    const hipStream_t st = (front && h->book_stream) ? h->book_stream : h->stream;
+    if (st != h->stream) {
+        HIPCHK(h, hipEventRecord(h->evSSa, h->stream));
+        HIPCHK(h, hipStreamWaitEvent(st, h->evSSa, 0));
+    }
+    const int n = h->n_clones_host, rows = h->ss_cfg.bias_rows ? 6 : 3;
+    const LpLaunch l = standstill_launch(h->batch);
+    hipLaunchKernelGGL(standstill_kernel, lp_grid(l), lp_block(l), l.lds, st, h->dc, (const CamCal*)h->cal, h->t, front ? 1 : 0, (const double*)h->x[h->cur], h->slab_bytes,
+                       d_imu, imu_bs, m, h->ss_cfg, n, rows, apply, h->img_count, h->ss_rec, h->ss_active, h->ss_v, h->ss_H, h->ss_sigma, h->ss_diag);
+    HIPCHK(h, hipGetLastError());
+    if (front) {
+        HIPCHK(h, hipEventRecord(h->evSSb, st));
+        h->ss_last = st;
+    }
+    if (st != h->stream) HIPCHK(h, hipStreamWaitEvent(h->stream, h->evSSb, 0));
+    if (apply)
+        RCCHK(update_aux_dev(h, rows, RVIO_AUX_VALUE, h->ss_cfg.gate, h->ss_H, 0, h->ss_v, 6, h->ss_sigma, 0, (const int32_t*)h->ss_active, h->ss_diag));
+    if (paranoid_bits() & PAR_DRAIN) return drain_all(h);
+    return RVIO_OK;
+}
+int rvio_hip_standstill_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride, int m, int apply) {
+    if (!h || !d_imu || m < 1 || (apply != 0 && apply != 1) || imu_stride < 0 || (imu_stride > 0 && imu_stride < m)) return RVIO_ERR_INVALID;
+    RCCHK(standstill_check(h));
+    HIPCHK(h, hipSetDevice(h->device));
+    return standstill_dev(h, d_imu, (size_t)imu_stride * sizeof(rvio_imu), m, apply);
+}
+// host buffer: staged through a block of its own (which grows with m), copied on the filter stream — the detector is ordered behind that stream
+int rvio_hip_standstill(rvio_hip* h, const rvio_imu* imu, int m, int apply) {
+    if (!h || !imu || m < 1 || (apply != 0 && apply != 1)) return RVIO_ERR_INVALID;
+    RCCHK(standstill_check(h));
+    HIPCHK(h, hipSetDevice(h->device));
+    if (m > h->ss_imu_cap) {   // (hipFree waits for what still reads the old block)
+        const int cap = std::max(std::max(2 * h->ss_imu_cap, RVIO_HIP_MAX_IMU), (m + 63) & ~63);
+        rvio_imu* p = nullptr;
+        RCCHK(own_dev(h, &p, sizeof(rvio_imu) * (size_t)cap));
+        own_release(h, h->ss_imu);
+        h->ss_imu = p; h->ss_imu_cap = cap;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->ss_imu, imu, sizeof(rvio_imu) * (size_t)m, hipMemcpyHostToDevice, h->stream));
+    return standstill_dev(h, h->ss_imu, 0, m, apply);
+}
+// waits for the filter stream only (that stream waits for the detector wherever it ran)
+int rvio_hip_get_standstill(rvio_hip* h, int instance, rvio_standstill* out) {
+    if (!h || !out || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
+    if (!h->ss_rec) { h->err = "rvio_hip_get_standstill before the first rvio_hip_standstill"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    double dg[2];
+    HIPCHK(h, hipMemcpyAsync(out, h->ss_rec + instance, sizeof *out, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dg, h->ss_diag + 2 * (size_t)instance, sizeof dg, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    long long ap; std::memcpy(&ap, &dg[1], sizeof ap);
+    out->gamma = ap ? dg[0] : 0.0;
+    if (ap) out->flags |= 8;
     return RVIO_OK;
 }
 
@@ -1977,6 +2111,11 @@ static int build_pyramid_dev(rvio_hip* h, const FrontForms& f, const uint8_t* d_
 static int post_klt_dev(rvio_hip* h, const FrontForms& f, const rvio_imu* d_imu, int m, const float* d_cand, int n_cand, const BookWait& bw, BookOut* out) {
     const size_t bs = h->slab_bytes;
     const hipStream_t base = stream_of(h, f.base, f.ic), side = stream_of(h, f.side, f.ic), tail = stream_of(h, f.book, f.ic);
+    // (standstill detection, rvio_hip_standstill*: the detector reads what this book-keeping rewrites.  It ran on the stream of the LAST book-keeping;
+    // if this one runs elsewhere — the call mode changed — its stream waits for the detector.  A handle without the feature never gets here)
+    if (h->ss_last && h->ss_last != tail) HIPCHK(h, hipStreamWaitEvent(tail, h->evSSb, 0));
+    h->ss_last = nullptr;
+    h->book_stream = tail;
     const LpLaunch &lr = f.ransac_l, &la = f.book_a_l, &lb = f.book_b_l;
     const float* xy = h->det_xy2[f.dslot];      // the detector's corner list replaces the caller's
     const int* nout = h->det_nout + f.dslot;

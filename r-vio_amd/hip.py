@@ -31,6 +31,7 @@ SYMBOLS = [
     "rvio_hip_predict", "rvio_hip_predict_dev", "rvio_hip_set_imu_odometry", "rvio_hip_get_imu_odometry",
     "rvio_hip_update_aux", "rvio_hip_update_aux_dev", "rvio_hip_get_aux_diag",
     "rvio_hip_predict_cov", "rvio_hip_predict_cov_dev", "rvio_hip_set_imu_odometry_cov", "rvio_hip_get_imu_odometry_cov",
+    "rvio_standstill_config_default", "rvio_hip_set_standstill", "rvio_hip_standstill", "rvio_hip_standstill_dev", "rvio_hip_get_standstill",
 ]
 
 _LIB = None
@@ -568,3 +569,23 @@ class RvioHip:
         g, a = C.c_double(0), C.c_int32(0)
         self._ck(self.L.rvio_hip_get_aux_diag(self.h, int(instance), C.byref(g), C.byref(a)), "get_aux_diag")
         return float(g.value), int(a.value)
+
+    # ---- standstill detection and the automatic zero-velocity update (csrc/standstill.hip in front of the auxiliary update)
+    def set_standstill(self, c):
+        """switch the feature on with an abi.rvio_standstill_config, off with None"""
+        self._ck(self.L.rvio_hip_set_standstill(self.h, C.byref(c) if c is not None else None), "set_standstill")
+
+    def standstill(self, imu, apply=1):
+        """one decision per instance from the IMU batch (host records, shared by every instance); apply: fuse zero velocity into the static ones.  Asynchronous."""
+        imu = np.ascontiguousarray(imu)
+        self._ck(self.L.rvio_hip_standstill(self.h, imu.ctypes.data_as(C.POINTER(abi.rvio_imu)) if len(imu) else None, len(imu), int(apply)), "standstill")
+
+    def standstill_dev(self, d_imu_ptr, imu_stride, m, apply=1):
+        """the same on a device buffer: instance z reads d_imu + z * imu_stride (0: shared)"""
+        self._ck(self.L.rvio_hip_standstill_dev(self.h, C.c_void_p(d_imu_ptr), int(imu_stride), int(m), int(apply)), "standstill_dev")
+
+    def get_standstill(self, instance=0):
+        """the abi.rvio_standstill record of one instance from the last standstill* call (waits for the filter stream only)"""
+        r = abi.rvio_standstill()
+        self._ck(self.L.rvio_hip_get_standstill(self.h, int(instance), C.byref(r)), "get_standstill")
+        return r
