@@ -372,6 +372,113 @@ int System::zero_velocity(double sigma, bool gate) {
     return velocity(z, sigma, gate);
 }
 
+// ---- absolute fixes (rvio_hip_update_fix)
+int System::update_fix(int kind, const rvio_fix& fix, bool gate) {
+    if (!h_ || !ready_) { err_ = "System::update_fix before the filter is initialised"; return -1; }
+    if (rvio_hip_update_fix(h_, -1, kind, gate ? 1 : 0, &fix) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+    return 0;
+}
+int System::fix_position(const double p[3], const double sigma[3], const double* lever, bool gate) {
+    rvio_fix f{};
+    for (int i = 0; i < 3; ++i) { f.z[i] = p[i]; f.sigma[i] = sigma[i]; f.lever[i] = lever ? lever[i] : 0.0; }
+    return update_fix(RVIO_FIX_POSITION, f, gate);
+}
+int System::fix_attitude(const double q[4], const double sigma[3], bool gate) {
+    rvio_fix f{};
+    for (int i = 0; i < 4; ++i) f.z[3 + i] = q[i];
+    for (int i = 0; i < 3; ++i) f.sigma[3 + i] = sigma[i];
+    return update_fix(RVIO_FIX_ATTITUDE, f, gate);
+}
+int System::fix_pose(const double p[3], const double q[4], const double sigma_p[3], const double sigma_q[3], const double* lever, bool gate) {
+    rvio_fix f{};
+    for (int i = 0; i < 4; ++i) f.z[3 + i] = q[i];
+    for (int i = 0; i < 3; ++i) { f.z[i] = p[i]; f.sigma[i] = sigma_p[i]; f.sigma[3 + i] = sigma_q[i]; f.lever[i] = lever ? lever[i] : 0.0; }
+    return update_fix(RVIO_FIX_POSE, f, gate);
+}
+int System::fix_gravity(const double a[3], const double sigma[3], bool gate) {
+    rvio_fix f{};
+    for (int i = 0; i < 3; ++i) { f.z[i] = a[i]; f.sigma[i] = sigma[i]; }
+    return update_fix(RVIO_FIX_GRAVITY, f, gate);
+}
+void System::queue_fixes(std::vector<FixRow> rows, bool gate) {
+    std::stable_sort(rows.begin(), rows.end(), [](const FixRow& a, const FixRow& b) { return a.t < b.t; });
+    fx_rows_ = std::move(rows); fx_next_ = 0; fx_gate_ = gate;
+}
+// behind the frame stamped t: every queued fix whose stamp that frame has reached, through the typed calls
+int System::apply_fixes(double t) {
+    for (; fx_next_ < fx_rows_.size() && fx_rows_[fx_next_].t <= t; ++fx_next_) {
+        const rvio_fix& f = fx_rows_[fx_next_].fix;
+        int rc = -1;
+        switch (fx_rows_[fx_next_].kind) {
+            case RVIO_FIX_POSITION: rc = fix_position(f.z, f.sigma, f.lever, fx_gate_); break;
+            case RVIO_FIX_ATTITUDE: rc = fix_attitude(f.z + 3, f.sigma + 3, fx_gate_); break;
+            case RVIO_FIX_POSE: rc = fix_pose(f.z, f.z + 3, f.sigma, f.sigma + 3, f.lever, fx_gate_); break;
+            case RVIO_FIX_GRAVITY: rc = fix_gravity(f.z, f.sigma, fx_gate_); break;
+            default: err_ = "System: a queued fix of unknown kind";
+        }
+        if (rc < 0) return -1;
+    }
+    return 0;
+}
+bool parse_fixes(const std::string& text, const std::string& name, std::vector<FixRow>* out, std::string* err) {
+    static const char* const kNames[4] = {"position", "attitude", "pose", "gravity"};
+    out->clear();
+    std::istringstream in(text);
+    std::string line;
+    for (long ln = 1; std::getline(in, line); ++ln) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        const size_t b = line.find_first_not_of(" \t");
+        if (b == std::string::npos || line[b] == '#') continue;
+        auto bad = [&](const std::string& why) { *err = name + ":" + std::to_string(ln) + ": " + why + ": " + line; return false; };
+        std::string flat = line;
+        std::replace(flat.begin(), flat.end(), ',', ' ');
+        std::istringstream ls(flat);
+        std::vector<std::string> tok;
+        for (std::string w; ls >> w;) tok.push_back(w);
+        if (tok.size() < 2) return bad("not `t kind values... sigmas... [lever]`");
+        int kind = -1;
+        for (int k = 0; k < 4; ++k) if (tok[1] == kNames[k] || tok[1] == std::to_string(k)) kind = k;
+        if (kind < 0) return bad("unknown kind '" + tok[1] + "' (position | attitude | pose | gravity or 0 .. 3)");
+        std::vector<double> v;
+        for (size_t i = 0; i < tok.size(); ++i) {
+            if (i == 1) continue;
+            char* end = nullptr;
+            const double x = std::strtod(tok[i].c_str(), &end);
+            if (end == tok[i].c_str() || *end != 0 || !std::isfinite(x)) return bad("'" + tok[i] + "' is not a finite number");
+            v.push_back(x);
+        }
+        // v: t, then the kind's values and sigmas, then (POSITION, POSE) an optional lever
+        const int nz = kind == RVIO_FIX_POSE ? 7 : (kind == RVIO_FIX_ATTITUDE ? 4 : 3), ns = kind == RVIO_FIX_POSE ? 6 : 3;
+        const bool may_lever = kind == RVIO_FIX_POSITION || kind == RVIO_FIX_POSE;
+        const size_t need = 1 + (size_t)nz + ns;
+        if (v.size() != need && !(may_lever && v.size() == need + 3))
+            return bad(std::string(kNames[kind]) + " takes " + std::to_string(nz) + " values and " + std::to_string(ns) + " sigmas" + (may_lever ? " and an optional lever of 3" : "") +
+                       " behind t and the kind, the line holds " + std::to_string(v.size() - 1));
+        FixRow r;
+        r.t = v[0]; r.kind = kind;
+        const int z0 = kind == RVIO_FIX_ATTITUDE ? 3 : 0, s0 = kind == RVIO_FIX_ATTITUDE ? 3 : 0;
+        for (int i = 0; i < nz; ++i) r.fix.z[z0 + i] = v[1 + i];
+        for (int i = 0; i < ns; ++i) {
+            if (!(v[1 + nz + i] > 0)) return bad("a sigma is not > 0");
+            r.fix.sigma[s0 + i] = v[1 + nz + i];
+        }
+        if (v.size() == need + 3) for (int i = 0; i < 3; ++i) r.fix.lever[i] = v[need + i];
+        if (kind == RVIO_FIX_ATTITUDE || kind == RVIO_FIX_POSE) {
+            const double* q = r.fix.z + 3;
+            if (std::fabs(std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]) - 1.0) > 1e-6) return bad("the quaternion is not of unit length (1e-6)");
+        }
+        out->push_back(r);
+    }
+    return true;
+}
+bool read_fixes(const std::string& path, std::vector<FixRow>* out, std::string* err) {
+    std::ifstream f(path);
+    if (!f) { *err = "cannot read " + path; return false; }
+    std::stringstream ss;
+    ss << f.rdbuf();
+    return parse_fixes(ss.str(), path, out, err);
+}
+
 // behind a frame: the decision and, where the platform stands still, the zero-velocity update — on the device, nothing waited for unless the
 // records are asked for
 int System::standstill(double t, const rvio_imu* imu, int m) {
@@ -467,6 +574,7 @@ int System::MonoVIO(PoseLine* pose) {
     if (!rec_) {
         if (rvio_hip_frame(h_, image.px.data(), row_bytes, pi, m, nullptr, 0) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
         if (ss_on_ && standstill(image.t, pi, m) < 0) return -1;   // (ahead of the pose read-back: the pose line is the updated state's)
+        if (fx_next_ < fx_rows_.size() && apply_fixes(image.t) < 0) return -1;   // (likewise)
         if (pose) {
             pose->t = image.t;
             if (rvio_hip_get_pose(h_, pose->p, pose->q) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
@@ -488,6 +596,7 @@ int System::MonoVIO(PoseLine* pose) {
     if (do_update && rvio_hip_update_tracked(h_) != RVIO_OK) return fail();               // System.cc:266-268
     if (rvio_hip_augment_compose(h_, do_augment) != RVIO_OK) return fail();               // System.cc:279-365
     if (ss_on_ && standstill(image.t, pi, m) < 0) return -1;
+    if (fx_next_ < fx_rows_.size() && apply_fixes(image.t) < 0) return -1;
     PoseLine pl;
     pl.t = image.t;
     if (rvio_hip_get_pose(h_, pl.p, pl.q) != RVIO_OK) return fail();                      // (waits for the filter stream)

@@ -83,6 +83,19 @@ private:
 
 struct PoseLine { double t, p[3], q[4]; };   // System.cc:369-374: timestamp pGk(3) qkG(4)
 
+// one line of a --fix file
+struct FixRow { double t = 0; int kind = 0; rvio_fix fix{}; };
+// A fix file is text, one fix per line, blank lines and '#' lines skipped, fields separated by blanks or commas:
+//     t position x y z  sx sy sz  [lx ly lz]
+//     t attitude qx qy qz qw  sx sy sz
+//     t pose     x y z  qx qy qz qw  sx sy sz  srx sry srz  [lx ly lz]
+//     t gravity  ax ay az  sx sy sz
+// t: seconds, on the clock of the image stamps; kind: the word or its number (0 .. 3); sigma: one per axis, rad for the attitude, all > 0; the
+// lever is optional.  A malformed line — an unknown kind, a wrong field count, a field that is no finite number, a sigma <= 0, a quaternion off
+// unit length by more than 1e-6 — is an error that names the line: "<name>:<line number>: <why>: <the line>".
+bool parse_fixes(const std::string& text, const std::string& name, std::vector<FixRow>* out, std::string* err);
+bool read_fixes(const std::string& path, std::vector<FixRow>* out, std::string* err);
+
 class System {
 public:
     System(const Settings& s, int device);
@@ -140,6 +153,20 @@ public:
     bool record_standstill_to(const std::string& path);
     int flush_standstill();       // 0, or -1 when the file cannot be written (error())
     bool standstill_enabled() const { return ss_on_; }
+    // Absolute fixes (rvio_hip_update_fix): a world-frame position (GNSS / RTK, UWB, a motion-capture marker), attitude or pose (motion capture,
+    // a fiducial, a relocalisation result), or the accelerometer at rest, linearised on the device at the state the call finds — no state is
+    // read back.  Positions and quaternions in the frame and convention of the pose line (PoseLine: pGk, qkG JPL xyzw; the world frame is the
+    // first IMU frame, NOT gravity-aligned); sigma: per axis (rad for an attitude); lever: the sensed point in the IMU frame, nullptr = the IMU
+    // itself; gate: the 95 % chi-square test.  0, or -1 with error().
+    int update_fix(int kind, const rvio_fix& fix, bool gate);
+    int fix_position(const double p[3], const double sigma[3], const double* lever, bool gate);
+    int fix_attitude(const double q[4], const double sigma[3], bool gate);
+    int fix_pose(const double p[3], const double q[4], const double sigma_p[3], const double sigma_q[3], const double* lever, bool gate);
+    int fix_gravity(const double a[3], const double sigma[3], bool gate);
+    // fixes with time stamps (rvio_replay --fix): MonoVIO fuses each one behind the first frame whose image stamp is >= its t, ahead of that
+    // frame's pose read-back — AT THAT FRAME'S STATE, not at t: bridging the gap (propagating to the fix's stamp) is not done.  Rows are sorted by t
+    void queue_fixes(std::vector<FixRow> rows, bool gate);
+    long fixes_applied() const { return (long)fx_next_; }
     // columns of an auxiliary H right now: 24 + 6 clones, the clones counted as the library counts them (one per frame behind the first, up
     // to Tracker.nMaxTrackingLength - 1) — no read-back
     int state_dim() const;
@@ -183,6 +210,10 @@ private:
     std::string ss_path_;         // record_standstill_to
     std::vector<std::pair<double, rvio_standstill>> ss_recs_;
     int standstill(double t, const rvio_imu* imu, int m);
+    std::vector<FixRow> fx_rows_; // queue_fixes, sorted by t
+    size_t fx_next_ = 0;          // the first row not yet fused
+    bool fx_gate_ = false;
+    int apply_fixes(double t);
 };
 
 // 8- or 16-bit PNG (non-interlaced; gray, RGB or RGBA: channels in file order = RGB) or binary PGM / PPM (P5 / P6; maxval 255: 8 bits, 256 ..

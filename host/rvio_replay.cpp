@@ -19,7 +19,14 @@
 //                                        device (System::velocity) right behind the frame whose image stamp is nearest to t_ns, within half an image
 //                                        period; at most one row per frame (the last one wins), rows that match no frame are counted and the count is
 //                                        printed.  S: the standard deviation per axis in m/s (default 0.05); --velocity-gate: the 95 % chi-square gate
+//                                        [--fix FILE [--fix-gate]]
+//                                        --fix: absolute fixes, one per line `t kind values... sigmas... [lever]` (rvio_host.hpp parse_fixes: a world-frame
+//                                        position, attitude or pose in the pose file's frame and convention, or the accelerometer at rest), each
+//                                        linearised and fused on the device (System::fix_position / _attitude / _pose / _gravity) behind the first
+//                                        frame whose image stamp is >= t, ahead of that frame's pose line — at THAT frame's state, not at t: the gap is
+//                                        not bridged.  --fix-gate: the 95 % chi-square gate.  A malformed line is an error that names the line
 //   rvio_replay --check-settings <settings.yaml>        print the parsed configuration (no GPU needed)
+//   rvio_replay --check-fix <fixes.txt>                 print the parsed fix file, one JSON object per fix (no GPU needed)
 //   rvio_replay --check-dataset <asl_root>              print what the dataset reader found (no GPU needed)
 //   rvio_replay --check-image <file.png|.pgm>           decode one image and print its size and checksum (no GPU needed)
 #include <dlfcn.h>
@@ -93,6 +100,20 @@ static int check_image(const char* path, bool is_rgb, const char* encoding) {
     return 0;
 }
 
+// ---------------------------------------------------------------- --fix
+static int check_fix(const char* path) {
+    std::vector<FixRow> rows; std::string err;
+    if (!read_fixes(path, &rows, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
+    for (const FixRow& r : rows) {
+        std::printf("{\"t\": %.17g, \"kind\": %d, \"z\": [", r.t, r.kind);
+        for (int i = 0; i < 7; ++i) std::printf("%s%.17g", i ? ", " : "", r.fix.z[i]);
+        std::printf("], \"sigma\": [");
+        for (int i = 0; i < 6; ++i) std::printf("%s%.17g", i ? ", " : "", r.fix.sigma[i]);
+        std::printf("], \"lever\": [%.17g, %.17g, %.17g]}\n", r.fix.lever[0], r.fix.lever[1], r.fix.lever[2]);
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------- --velocity
 struct VelocityRows {
     std::vector<int> has;                 // per image of the dataset: a row was matched to it
@@ -157,6 +178,8 @@ struct PassOptions {
     int imu_odometry_ring = 4096;
     bool imu_odometry_cov = false;
     VelocityRows* velocity = nullptr;    // --velocity
+    const std::vector<FixRow>* fixes = nullptr;   // --fix
+    bool fix_gate = false;
 };
 static bool dump_frame(System& sys, const rvio_config& c, FrameDump* d) {
     rvio_hip* h = sys.handle();
@@ -177,6 +200,7 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
     if (o.landmarks && !sys.record_landmarks_to(o.landmarks)) { *err = sys.error(); return 1; }
     if (o.odometry && !sys.record_odometry_to(o.odometry, o.odometry_ring)) { *err = sys.error(); return 1; }
     if (o.imu_odometry && !sys.record_imu_odometry_to(o.imu_odometry, o.imu_odometry_ring, o.imu_odometry_cov)) { *err = sys.error(); return 1; }
+    if (o.fixes) sys.queue_fixes(*o.fixes, o.fix_gate);
     size_t ii = 0;
     long n_images = 0, n_frames = 0;
     double t_filter = 0;
@@ -287,6 +311,7 @@ static int selfcheck(const Settings& s, const AslDataset& d, int device, long ma
 int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "--check-settings")) return check_settings(argv[2]);
     if (argc >= 3 && !std::strcmp(argv[1], "--check-dataset")) return check_dataset(argv[2]);
+    if (argc >= 3 && !std::strcmp(argv[1], "--check-fix")) return check_fix(argv[2]);
     if (argc >= 3 && !std::strcmp(argv[1], "--check-image")) {   // --check-image FILE [--bgr] [--encoding NAME]
         bool rgb = true; const char* enc = nullptr;
         for (int i = 3; i < argc; ++i) {
@@ -298,7 +323,7 @@ int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--record-dir DIR] [--record]\n"
                              "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--imu-odometry-cov] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n"
-                             "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate] [--standstill FILE]\n", argv[0]);
+                             "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate] [--standstill FILE] [--fix FILE] [--fix-gate]\n", argv[0]);
         return 2;
     }
     const char* out_path = nullptr;
@@ -308,6 +333,7 @@ int main(int argc, char** argv) {
     const char* imu_odometry = nullptr; int imu_odometry_ring = 4096; bool imu_odometry_cov = false;
     const char* velocity = nullptr; double velocity_sigma = 0.05; bool velocity_gate = false;
     const char* standstill = nullptr;
+    const char* fix = nullptr; bool fix_gate = false;
     const char* record_dir = "."; bool force_record = false, sync_every = false, self = false; int noise_wgs = 0;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -328,6 +354,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--velocity-sigma") && i + 1 < argc) velocity_sigma = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--velocity-gate")) velocity_gate = true;
         else if (!std::strcmp(argv[i], "--standstill") && i + 1 < argc) standstill = argv[++i];   // one line per frame: t T disparity n_pairs flags gamma (needs Standstill.Enable: 1)
+        else if (!std::strcmp(argv[i], "--fix") && i + 1 < argc) fix = argv[++i];   // `t kind values... sigmas... [lever]` lines fused behind the first frame at or past t (System::fix_*)
+        else if (!std::strcmp(argv[i], "--fix-gate")) fix_gate = true;
         else out_path = argv[i];
     }
     Settings s; std::string err;
@@ -343,16 +371,21 @@ int main(int argc, char** argv) {
         vrows.sigma = velocity_sigma; vrows.gate = velocity_gate;
         vr = &vrows;
     }
+    std::vector<FixRow> fixes;
+    if (fix) {
+        if (self) { std::fprintf(stderr, "--fix and --selfcheck do not combine\n"); return 1; }
+        if (!read_fixes(fix, &fixes, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
+    }
     print_runtime();
     if (self) return selfcheck(s, d, device, max_frames, stall_seed, noise_wgs);
     if (sync_every || stall_seed >= 0 || noise_wgs > 0) {   // the plain replay with one of the two A/B pacings
         std::vector<PoseLine> poses; double ms = 0; int flags = 0;
-        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.imu_odometry_cov = imu_odometry_cov; o.velocity = vr;
+        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.imu_odometry_cov = imu_odometry_cov; o.velocity = vr; if (fix) { o.fixes = &fixes; o.fix_gate = fix_gate; }
         if (run_pass(s, d, device, o, &poses, nullptr, &ms, &flags, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
         if (out_path) { std::ofstream out(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } for (const PoseLine& p : poses) out << format_pose(p); }
         std::fprintf(stderr, "rvio_replay: %zu filtered frames, %.3f ms per MonoVIO call, device flags %d\n", poses.size(), ms, flags);
         if (vr) print_velocity(*vr);
-        return 0;
+        return 0;   // (the pass has printed nothing about --fix: its System is gone)
     }
     System sys(s, device);
     if (!sys.ok()) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
@@ -361,6 +394,7 @@ int main(int argc, char** argv) {
     if (odometry && !sys.record_odometry_to(odometry, odometry_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (imu_odometry && !sys.record_imu_odometry_to(imu_odometry, imu_odometry_ring, imu_odometry_cov)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (standstill && !sys.record_standstill_to(standstill)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
+    if (fix) sys.queue_fixes(fixes, fix_gate);
     std::ofstream out;
     if (out_path) { out.open(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } }
 
@@ -391,6 +425,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "rvio_replay: %ld images, %ld filtered frames, %.3f ms per MonoVIO call (host wall clock, pose read-back included)\n",
                  n_images, n_frames, n_images ? 1e3 * t_filter / n_images : 0.0);
     if (vr) print_velocity(*vr);
+    if (fix) std::fprintf(stderr, "rvio_replay: fix: %zu rows, %ld applied\n", fixes.size(), sys.fixes_applied());
     // anything only the device saw (0 in every test and bench run): said out loud, the poses above are suspect if it is not 0
     const int flags = sys.device_flags();
     if (flags) std::fprintf(stderr, "rvio_replay: DEVICE-SIDE FLAGS %d (1 singular pivot in the solve, 2 a track the window cannot hold was dropped, "

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov); standstill detection (rvio_standstill_config, rvio_standstill, rvio_standstill_config_default, rvio_hip_set_standstill, rvio_hip_standstill, rvio_hip_standstill_dev, rvio_hip_get_standstill) */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov); standstill detection (rvio_standstill_config, rvio_standstill, rvio_standstill_config_default, rvio_hip_set_standstill, rvio_hip_standstill, rvio_hip_standstill_dev, rvio_hip_get_standstill); absolute fixes (rvio_fix_kind, rvio_fix, rvio_fix_diag, rvio_hip_update_fix, rvio_hip_update_fix_dev, rvio_hip_get_fix, rvio_hip_get_fix_rows) */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -489,6 +489,8 @@ int rvio_hip_get_imu_odometry_cov(rvio_hip* h, int instance, int64_t first_seq, 
  *   measurement of the additive coordinates and the device forms r = z - H xi(x), where xi(x) is x in error-state order with 0 in every rotation
  *   slot: xi[3..8] = x[4..9], xi[12..23] = x[14..25], xi[27+6p .. 29+6p] = x[30+7p .. 32+7p].  Zero velocity: m = 3, H = I at columns 15..17,
  *   z = 0; a velocity in the IMU frame: the same with z = v_meas.  No state is read back to form a residual.
+ *   (Measurements that are NOT linear in these coordinates — a world-frame position, attitude or pose, the accelerometer at rest — are
+ *   linearised on the device by rvio_hip_update_fix below.)
  * gate: 0: always apply; 1: apply iff |gamma| < chi2inv(0.95, m), the table and the comparison of the feature gate (Updater.cc:422).
  * In place: x and P of the current buffer are updated where they lie (no double-buffer toggle); an instance that is gated out, inactive or
  * indefinite is not written at all.  The pose line (rvio_hip_get_pose[_at]) is rewritten from the updated state, (pGk, qkG) =
@@ -552,7 +554,8 @@ int rvio_hip_get_aux_diag(rvio_hip* h, int instance, double* gamma, int32_t* app
  *   configured densities (cfg.sigma_a sqrt(imu_rate), cfg.sigma_g sqrt(imu_rate)), under which T has mean ~ 6, imu_thr = 12 is twice that;
  *   disp_thr_px = 0.5, min_pairs = 20, sigma_v = 0.05, sigma_bg = sigma_w, bias_rows = 0, gate = 1.
  * NOT done: a static frame still runs its camera update and augments a clone (skipping both would change the frame path); the accelerometer
- *   rows a_m = ba + R g are not fused (not linear in additive coordinates). */
+ *   rows a_m = ba + G R_k g are not fused BY THIS CALL.  They exist as RVIO_FIX_GRAVITY (rvio_hip_update_fix below, linearised on the device): a
+ *   caller applies them when rvio_hip_get_standstill says static, or hands rvio_hip_update_fix_dev its own flags. */
 typedef struct rvio_standstill_config {   /* 64 bytes, no padding */
     double sigma_a, sigma_w;      /* detector noise, m/s^2 and rad/s per sample, finite and > 0 */
     double imu_thr;               /* > 0 */
@@ -589,6 +592,61 @@ int rvio_hip_standstill_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride, 
 /* The record of one instance from the LAST rvio_hip_standstill* call; waits for the filter stream only.  RVIO_ERR_STATE before the first such
  * call; RVIO_ERR_INVALID: NULL argument, instance out of range. */
 int rvio_hip_get_standstill(rvio_hip* h, int instance, rvio_standstill* out);
+
+/* --- absolute fixes: world-frame position, attitude, pose; the accelerometer at rest (no reference counterpart) ------------------ */
+/* rvio_hip_update_aux fuses what the caller has linearised; these measurements are not linear in the robocentric state, and linearising them
+ * on the host costs a drain and a state read-back per fix.  Here the linearisation happens where the state is: fix_rows_kernel
+ * (csrc/fix_rows.hip, one wave per instance) writes (H, r, sigma) at the instance's CURRENT state and aux_update_kernel, unchanged, runs right
+ * behind it in RVIO_AUX_RESIDUAL mode with m = 3 (POSE: 6) rows.
+ * Frames and conventions are those of rvio_hip_get_pose: a position is pGk = R(qG)^T (pk - pG), a quaternion is qkG = QuatMul(qk, qG), JPL xyzw,
+ * rotating world vectors into the IMU frame.  THE FILTER'S WORLD FRAME IS THE FIRST IMU FRAME AND IS NOT GRAVITY-ALIGNED — hence no heading-only
+ * kind; aligning an ENU or motion-capture frame to it, and re-expressing a sensor's attitude as the IMU's, is the caller's job.
+ * With R_G = R(x[0:4]), R_k = R(x[10:14]) (an all-zero qk reads as I), R = R_k R_G, l = lever, s = pk - pG + R_k^T l, G = cfg.gravity, g = x[7:10],
+ * the columns of P as rvio_hip_update_aux documents them and R_true ~ (I - [dth x]) R in every rotation slot (all columns not listed are 0):
+ *   POSITION  m = 3  h = R_G^T s                     r = z[0:3] - h
+ *                    cols 0-2: -R_G^T [s x]   3-5: -R_G^T   9-11: -R_G^T R_k^T [l x]   12-14: R_G^T
+ *   ATTITUDE  m = 3  the world-frame rotation error phi of R_wb = R^T;  with E = R(z[3:7])^T R:  r = (E21 - E12, E02 - E20, E10 - E01) / 2
+ *                    cols 0-2: R_G^T   9-11: R^T
+ *   POSE      m = 6  the three position rows, then the three attitude rows
+ *   GRAVITY   m = 3  h = ba + G R_k g (PreIntegrator.cc:107, 175-177 at rest)   r = z[0:3] - h,  z[0:3] = the mean RAW accelerometer reading
+ *                    cols 6-8: G R_k   9-11: G [R_k g x]   21-23: I
+ *             (the state carries g as three coordinates and injection re-normalises it, Updater.cc:566-568: what the gain moves ALONG g is
+ *             dropped there, so the part of a residual along gravity is only taken up as far as the prior hands it to ba)
+ * The fix is fused at the state the call finds, not at a time stamp of its own: bridging the gap to the sensor's stamp is the caller's.  One
+ * update, not iterated.  Everything rvio_hip_update_aux_dev documents holds: in place, `gate` as there, the pose line rewritten, no ring record, a
+ * kept clone-block factor dropped, an inactive or gated-out instance not written at all, error bit 8 on a non-positive pivot. */
+typedef enum { RVIO_FIX_POSITION = 0, RVIO_FIX_ATTITUDE = 1, RVIO_FIX_POSE = 2, RVIO_FIX_GRAVITY = 3 } rvio_fix_kind;
+typedef struct rvio_fix {      /* 128 bytes, no padding */
+    double z[7];      /* [0..2] position (POSITION, POSE) or mean raw accelerometer reading (GRAVITY); [3..6] quaternion (ATTITUDE, POSE) */
+    double sigma[6];  /* [0..2] go with z[0..2], [3..5] (rad) with the quaternion */
+    double lever[3];  /* position of the sensed point in the IMU frame; POSITION and POSE only */
+} rvio_fix;
+typedef struct rvio_fix_diag { /* 72 bytes, no padding */
+    double r[6];         /* the residual as formed on the device, rows m .. 5 are 0 */
+    double gamma;        /* the aux update's |r~^T S^-1 r~| as compared with the gate's table, also when the gate refused it; 0: inactive */
+    int32_t applied;     /* 1: fused; 0: inactive, gated out or a bad pivot */
+    int32_t kind, m;
+    int32_t img_count;   /* the handle's frame count at the call */
+} rvio_fix_diag;
+/* Host record: *fix is checked, staged in a pinned block of the handle's own and consumed on rvio_hip_stream — no wait for the stream.  instance:
+ * 0 .. batch - 1, or -1: every instance gets the same fix.  _dev: device records, instance z reads d_fix + z * fix_stride RECORDS (0: shared);
+ * d_active: NULL or one int32 per instance, 0 = leave this instance alone; the values are not checked, as in rvio_hip_update_aux_dev.  kind and
+ * gate hold for the whole call.  The first call allocates the feature's block outside the filter slab (the rows at 6 x d_max per instance, r,
+ * sigma, the records, the (gamma, applied) pairs of ITS aux launches — a later rvio_hip_update_aux does not overwrite them — and the staging of
+ * the host form); a handle that never calls these allocates and launches what it did before.  Plain, batch and sharded handles; on a sharded
+ * handle every rank calls alike.
+ * RVIO_ERR_STATE: no state yet, between rvio_hip_frame_begin_dev and rvio_hip_frame_end.  RVIO_ERR_INVALID: NULL handle or record, kind, gate or
+ * instance out of range and — host form only — a non-finite entry the kind uses, a used sigma <= 0, | |q| - 1 | > 1e-6 (rvio_hip_last_error). */
+int rvio_hip_update_fix(rvio_hip* h, int instance, int kind, int gate, const rvio_fix* fix);
+int rvio_hip_update_fix_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_stride, const int32_t* d_active);
+/* The record of one instance from the LAST rvio_hip_update_fix* call (an instance that call left alone keeps r of the call that last touched
+ * it, with applied = 0); waits for the filter stream only.  RVIO_ERR_STATE before the first such call; RVIO_ERR_INVALID: NULL argument, instance
+ * out of range. */
+int rvio_hip_get_fix(rvio_hip* h, int instance, rvio_fix_diag* out);
+/* The rows the device formed in that call: *m, *d (= 24 + 6 clones at the call), H (m x d row-major) and sigma (m); H and sigma may be NULL —
+ * ask for m and d first.  Handing them with the record's r to rvio_hip_update_aux (RVIO_AUX_RESIDUAL) at the same state repeats the update bit
+ * for bit.  Waits for the filter stream only.  Errors as rvio_hip_get_fix. */
+int rvio_hip_get_fix_rows(rvio_hip* h, int instance, int32_t* m, int32_t* d, double* H, double* sigma);
 
 /* --- feature-sharded updater (no reference counterpart) ------ */
 /* Stage A: per-feature build + gate on the features f with f % world == rank,

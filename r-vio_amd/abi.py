@@ -483,6 +483,86 @@ def standstill_measurement(d, w_mean, cfg):
     return H, z, sigma
 
 
+# ---- absolute fixes (rvio_hip_update_fix*, csrc/fix_rows.hip in front of the auxiliary update)
+RVIO_FIX_POSITION, RVIO_FIX_ATTITUDE, RVIO_FIX_POSE, RVIO_FIX_GRAVITY = 0, 1, 2, 3
+FIX_KINDS = (RVIO_FIX_POSITION, RVIO_FIX_ATTITUDE, RVIO_FIX_POSE, RVIO_FIX_GRAVITY)
+FIX_ROWS = {RVIO_FIX_POSITION: 3, RVIO_FIX_ATTITUDE: 3, RVIO_FIX_POSE: 6, RVIO_FIX_GRAVITY: 3}
+
+
+class rvio_fix(C.Structure):
+    """one absolute fix: 128 bytes, no padding.  z[0:3]: position (POSITION, POSE) or mean raw accelerometer reading (GRAVITY); z[3:7]: quaternion
+    (ATTITUDE, POSE); sigma[0:3] go with z[0:3], sigma[3:6] (rad) with the quaternion; lever: the sensed point in the IMU frame (POSITION, POSE)"""
+    _fields_ = [("z", C.c_double * 7), ("sigma", C.c_double * 6), ("lever", C.c_double * 3)]
+
+
+class rvio_fix_diag(C.Structure):
+    """the record of one instance from the last fix: 72 bytes, no padding"""
+    _fields_ = [("r", C.c_double * 6), ("gamma", C.c_double), ("applied", C.c_int32), ("kind", C.c_int32), ("m", C.c_int32), ("img_count", C.c_int32)]
+
+
+FIX_DTYPE = np.dtype([("z", "f8", 7), ("sigma", "f8", 6), ("lever", "f8", 3)])
+assert C.sizeof(rvio_fix) == FIX_DTYPE.itemsize == 128 and C.sizeof(rvio_fix_diag) == 72
+
+
+def make_fix(p=None, q=None, sigma_p=0.0, sigma_q=0.0, lever=(0.0, 0.0, 0.0)):
+    """an rvio_fix: p -> z[0:3] (position, or the accelerometer reading), q -> z[3:7]; sigma_p / sigma_q: scalars or 3-vectors"""
+    f = rvio_fix()
+    if p is not None:
+        f.z[0:3] = [float(v) for v in p]
+    if q is not None:
+        f.z[3:7] = [float(v) for v in q]
+    f.sigma[0:3] = [float(v) for v in np.broadcast_to(np.asarray(sigma_p, float), (3,))]
+    f.sigma[3:6] = [float(v) for v in np.broadcast_to(np.asarray(sigma_q, float), (3,))]
+    f.lever[0:3] = [float(v) for v in lever]
+    return f
+
+
+def fix_h(cfg, x, kind, lever=(0.0, 0.0, 0.0)):
+    """The predicted measurement of a fix at the state x, laid out like rvio_fix.z (unused entries 0): [0:3] the world-frame position of the
+    sensed point R_G^T (pk - pG + R_k^T l) (POSITION, POSE) or the accelerometer at rest ba + G R_k g (GRAVITY); [3:7] the quaternion of the
+    pose line QuatMul(qk, qG) (ATTITUDE, POSE).  An all-zero qk reads as the identity."""
+    x, l = np.asarray(x, float), np.asarray(lever, float)
+    RG, Rk = quat_to_rot(x[0:4]), quat_to_rot(x[10:14])
+    z = np.zeros(7)
+    if kind in (RVIO_FIX_POSITION, RVIO_FIX_POSE):
+        z[0:3] = RG.T @ (x[14:17] - x[4:7] + Rk.T @ l)
+    if kind in (RVIO_FIX_ATTITUDE, RVIO_FIX_POSE):
+        z[3:7] = quat_mul(x[10:14] if x[10:14].any() else np.array([0.0, 0.0, 0.0, 1.0]), x[0:4])
+    if kind == RVIO_FIX_GRAVITY:
+        z[0:3] = x[23:26] + cfg.gravity * (Rk @ x[7:10])
+    return z
+
+
+def fix_model(cfg, x, kind, fix):
+    """NumPy float64 model of csrc/fix_rows.hip: (H [m x d], r [m], sigma [m]) of one fix (rvio_fix, or anything with z, sigma, lever)
+    linearised at the state x, in the error-state order of P under R_true ~ (I - [dth x]) R.  The table of include/rvio_hip.h; calls nothing
+    from the library or the oracle."""
+    x = np.asarray(x, float)
+    z, sg, l = (np.array([float(v) for v in a]) for a in (fix.z, fix.sigma, fix.lever))
+    d = 24 + 6 * ((len(x) - 26) // 7)
+    RG, Rk = quat_to_rot(x[0:4]), quat_to_rot(x[10:14])
+    rows_H, rows_r, rows_s = [], [], []
+    if kind in (RVIO_FIX_POSITION, RVIO_FIX_POSE):
+        s = x[14:17] - x[4:7] + Rk.T @ l
+        H = np.zeros((3, d))
+        H[:, 0:3], H[:, 3:6], H[:, 9:12], H[:, 12:15] = -RG.T @ _skew(s), -RG.T, -RG.T @ Rk.T @ _skew(l), RG.T
+        rows_H.append(H), rows_r.append(z[0:3] - RG.T @ s), rows_s.append(sg[0:3])
+    if kind in (RVIO_FIX_ATTITUDE, RVIO_FIX_POSE):
+        R = Rk @ RG
+        E = quat_to_rot(z[3:7]).T @ R
+        H = np.zeros((3, d))
+        H[:, 0:3], H[:, 9:12] = RG.T, R.T
+        rows_H.append(H), rows_r.append(0.5 * np.array([E[2, 1] - E[1, 2], E[0, 2] - E[2, 0], E[1, 0] - E[0, 1]])), rows_s.append(sg[3:6])
+    if kind == RVIO_FIX_GRAVITY:
+        G = float(cfg.gravity)
+        gk = Rk @ x[7:10]
+        H = np.zeros((3, d))
+        H[:, 6:9], H[:, 9:12], H[:, 21:24] = G * Rk, G * _skew(gk), np.eye(3)
+        rows_H.append(H), rows_r.append(z[0:3] - (x[23:26] + G * gk)), rows_s.append(sg[0:3])
+    assert rows_H, "kind"
+    return np.vstack(rows_H), np.concatenate(rows_r), np.concatenate(rows_s)
+
+
 # Camera.T_BC0 of config/rvio_euroc.yaml:55-62 (row-major)
 _T_BC0 = [0.0148655429818, -0.999880929698, 0.00414029679422, -0.0216401454975,
           0.999557249008, 0.0149672133247, 0.025715529948, -0.064676986768,

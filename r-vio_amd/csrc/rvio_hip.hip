@@ -29,6 +29,7 @@
 #include "imu_cov.hip"     // ... and its covariance: pose_cov / vel_cov per IMU sample (rvio_hip_predict_cov, rvio_hip_set_imu_odometry_cov)
 #include "aux_update.hip"  // the auxiliary measurement update: wheel odometry, zero velocity, speed over ground (rvio_hip_update_aux)
 #include "standstill.hip"  // standstill detection in front of it: the zero-velocity update of the instances that do not move (rvio_hip_standstill)
+#include "fix_rows.hip"    // absolute fixes in front of it: position, attitude, pose, gravity rows linearised at the current state (rvio_hip_update_fix)
 #pragma clang fp contract(off)
 #include "frontend_kernels.hip"
 #include "klt3.hip"
@@ -218,6 +219,14 @@ struct rvio_hip {
     int ss_imu_cap = 0;
     hipEvent_t evSSa = nullptr, evSSb = nullptr;
     hipStream_t book_stream = nullptr, ss_last = nullptr;
+    // absolute fixes (fix_rows.hip): one block allocated by the first rvio_hip_update_fix* call, outside the slab — the rows H (6 x dmax per
+    // instance), r and sigma (6 per instance), the records, the (gamma, applied) pairs of ITS aux launches, one staged rvio_fix and the flags of the
+    // host form — with the pinned twin of that staging and the event behind its copy.  fx_kind / fx_m / fx_d: the last call's, for the getters
+    double *fx_H = nullptr, *fx_r = nullptr, *fx_sigma = nullptr, *fx_pair = nullptr;
+    rvio_fix_diag* fx_rec = nullptr;
+    char *fx_stage = nullptr, *fx_pin = nullptr;
+    hipEvent_t evFix = nullptr;
+    int fx_kind = 0, fx_m = 0, fx_d = 0;
     // colour input (rvio_hip_set_image_format): the gray images every stage behind gray_kernel reads instead of the caller's.  Allocated with the
     // first colour format, outside the slab (a mono handle keeps its memory layout), instance stride W * H; four in rotation like d_eq2[] (see
     // build_pyramid_dev for who reads a slot last)
@@ -592,6 +601,7 @@ static const void* lp_kernel_fn(int k) {
         case LPK_AUX_UPDATE16: return (const void*)aux_update_kernel<16>;
         case LPK_IMU_COV: return (const void*)imu_cov_kernel;
         case LPK_STANDSTILL: return (const void*)standstill_kernel;
+        case LPK_FIX: return (const void*)fix_rows_kernel;
     }
     return nullptr;
 }
@@ -1748,6 +1758,104 @@ int rvio_hip_get_standstill(rvio_hip* h, int instance, rvio_standstill* out) {
     long long ap; std::memcpy(&ap, &dg[1], sizeof ap);
     out->gamma = ap ? dg[0] : 0.0;
     if (ap) out->flags |= 8;
+    return RVIO_OK;
+}
+
+// ------------------------------------------------------------------ absolute fixes (fix_rows.hip)
+static_assert(sizeof(rvio_fix) == 128 && sizeof(rvio_fix_diag) == 72, "include/rvio_hip.h: the fix structs have no padding");
+static_assert(LP_FIX_ROWS == 6, "launch_plan.h: the rows of a POSE fix");
+static int fix_check(rvio_hip* h) {
+    if (!h->has_state) { h->err = "rvio_hip_update_fix before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
+    if (h->in_frame) { h->err = "rvio_hip_update_fix between rvio_hip_frame_begin_dev and rvio_hip_frame_end"; return RVIO_ERR_STATE; }
+    return RVIO_OK;
+}
+// bytes of the host form's staging: one record, one flag per instance
+static size_t fix_stage_bytes(const rvio_hip* h) { return sizeof(rvio_fix) + sizeof(int32_t) * (size_t)h->batch; }
+static int fix_alloc(rvio_hip* h) {
+    if (h->fx_H) return RVIO_OK;   // (all or nothing: a failure half-way leaves the members null, and the next call starts over)
+    const size_t B = (size_t)h->batch;
+    const size_t n_H = sizeof(double) * LP_FIX_ROWS * (size_t)h->dc.dmax * B, n_r = 48 * B, n_sg = 48 * B, n_pair = 16 * B, n_rec = sizeof(rvio_fix_diag) * B;
+    char *blk = nullptr, *pin = nullptr;
+    hipEvent_t ev = nullptr;
+    int rc = own_dev(h, &blk, n_H + n_r + n_sg + n_pair + n_rec + fix_stage_bytes(h), true);   // (cleared on the filter stream, where everything that touches it runs)
+    if (rc == RVIO_OK) rc = own_pinned(h, &pin, fix_stage_bytes(h));
+    if (rc == RVIO_OK) rc = own_event(h, &ev, hipEventDisableTiming);
+    if (rc != RVIO_OK) { own_release(h, blk); own_release(h, pin); return rc; }
+    h->fx_H = (double*)blk; h->fx_r = (double*)(blk + n_H); h->fx_sigma = (double*)(blk + n_H + n_r); h->fx_pair = (double*)(blk + n_H + n_r + n_sg);
+    h->fx_rec = (rvio_fix_diag*)(blk + n_H + n_r + n_sg + n_pair); h->fx_stage = blk + n_H + n_r + n_sg + n_pair + n_rec;
+    h->fx_pin = pin; h->evFix = ev;
+    return RVIO_OK;
+}
+// fix_bs: bytes between the instances' records (0: shared).  The kernel reads x of the current buffer, which the filter stream owns: it runs on
+// that stream, no event; the aux launch behind it reads the rows in stream order
+static int update_fix_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_bs, const int32_t* d_active) {
+    const int n = h->n_clones_host, m = kind == RVIO_FIX_POSE ? 6 : 3;
+    const size_t H_stride = (size_t)LP_FIX_ROWS * h->dc.dmax;
+    const LpLaunch l = fix_launch(h->batch);
+    hipLaunchKernelGGL(fix_rows_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, n, kind, h->dc.gravity, (const double*)h->x[h->cur], h->slab_bytes, d_fix, fix_bs,
+                       (const int*)d_active, h->img_count, h->fx_H, H_stride * sizeof(double), h->fx_r, h->fx_sigma, h->fx_rec, h->fx_pair);
+    HIPCHK(h, hipGetLastError());
+    h->fx_kind = kind; h->fx_m = m; h->fx_d = 24 + 6 * n;
+    RCCHK(update_aux_dev(h, m, RVIO_AUX_RESIDUAL, gate, h->fx_H, H_stride, h->fx_r, 6, h->fx_sigma, 6, d_active, h->fx_pair));
+    if (paranoid_bits() & PAR_DRAIN) return drain_all(h);
+    return RVIO_OK;
+}
+int rvio_hip_update_fix_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_stride, const int32_t* d_active) {
+    if (!h || !d_fix || kind < RVIO_FIX_POSITION || kind > RVIO_FIX_GRAVITY || (gate != 0 && gate != 1)) return RVIO_ERR_INVALID;
+    RCCHK(fix_check(h));
+    HIPCHK(h, hipSetDevice(h->device));
+    RCCHK(fix_alloc(h));
+    return update_fix_dev(h, kind, gate, d_fix, fix_stride * sizeof(rvio_fix), d_active);
+}
+// host record: checked here, packed into the pinned block once the copy of the previous call has left it, copied and consumed on the filter stream —
+// no wait for the stream itself
+int rvio_hip_update_fix(rvio_hip* h, int instance, int kind, int gate, const rvio_fix* fix) {
+    if (!h || !fix || kind < RVIO_FIX_POSITION || kind > RVIO_FIX_GRAVITY || (gate != 0 && gate != 1) || instance < -1 || instance >= h->batch) return RVIO_ERR_INVALID;
+    const bool pos = kind == RVIO_FIX_POSITION || kind == RVIO_FIX_POSE, att = kind == RVIO_FIX_ATTITUDE || kind == RVIO_FIX_POSE, vec = pos || kind == RVIO_FIX_GRAVITY;
+    auto fin = [](const double* p, int k) { for (int i = 0; i < k; ++i) if (!std::isfinite(p[i])) return false; return true; };
+    auto positive = [](const double* p, int k) { for (int i = 0; i < k; ++i) if (!(p[i] > 0)) return false; return true; };
+    if ((vec && !(fin(fix->z, 3) && fin(fix->sigma, 3))) || (att && !(fin(fix->z + 3, 4) && fin(fix->sigma + 3, 3))) || (pos && !fin(fix->lever, 3))) {
+        h->err = "rvio_hip_update_fix: an entry of z, sigma or lever that this kind uses is not finite"; return RVIO_ERR_INVALID;
+    }
+    if ((vec && !positive(fix->sigma, 3)) || (att && !positive(fix->sigma + 3, 3))) { h->err = "rvio_hip_update_fix: a sigma that this kind uses is not > 0"; return RVIO_ERR_INVALID; }
+    if (att) {
+        const double* q = fix->z + 3;
+        if (std::fabs(std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]) - 1.0) > 1e-6) { h->err = "rvio_hip_update_fix: the quaternion z[3..6] is not of unit length (1e-6)"; return RVIO_ERR_INVALID; }
+    }
+    RCCHK(fix_check(h));
+    HIPCHK(h, hipSetDevice(h->device));
+    const bool fresh = !h->fx_H;
+    RCCHK(fix_alloc(h));
+    if (!fresh) HIPCHK(h, hipEventSynchronize(h->evFix));
+    std::memcpy(h->fx_pin, fix, sizeof *fix);
+    int32_t* act = (int32_t*)(h->fx_pin + sizeof(rvio_fix));
+    for (int i = 0; i < h->batch; ++i) act[i] = (instance < 0 || i == instance) ? 1 : 0;
+    HIPCHK(h, hipMemcpyAsync(h->fx_stage, h->fx_pin, fix_stage_bytes(h), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->evFix, h->stream));
+    return update_fix_dev(h, kind, gate, (const rvio_fix*)h->fx_stage, 0, instance < 0 ? (const int32_t*)nullptr : (const int32_t*)(h->fx_stage + sizeof(rvio_fix)));
+}
+// waits for the filter stream only
+int rvio_hip_get_fix(rvio_hip* h, int instance, rvio_fix_diag* out) {
+    if (!h || !out || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
+    if (!h->fx_m) { h->err = "rvio_hip_get_fix before the first rvio_hip_update_fix"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    double dg[2];
+    HIPCHK(h, hipMemcpyAsync(out, h->fx_rec + instance, sizeof *out, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dg, h->fx_pair + 2 * (size_t)instance, sizeof dg, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    long long ap; std::memcpy(&ap, &dg[1], sizeof ap);
+    out->gamma = dg[0];   // (as compared, also when the gate refused it: by how much is what a caller wants to know then)
+    out->applied = ap ? 1 : 0;
+    return RVIO_OK;
+}
+int rvio_hip_get_fix_rows(rvio_hip* h, int instance, int32_t* m, int32_t* d, double* H, double* sigma) {
+    if (!h || !m || !d || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
+    if (!h->fx_m) { h->err = "rvio_hip_get_fix_rows before the first rvio_hip_update_fix"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    *m = h->fx_m; *d = h->fx_d;
+    if (H) HIPCHK(h, hipMemcpyAsync(H, h->fx_H + (size_t)instance * LP_FIX_ROWS * h->dc.dmax, sizeof(double) * (size_t)h->fx_m * h->fx_d, hipMemcpyDeviceToHost, h->stream));
+    if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, h->fx_sigma + 6 * (size_t)instance, sizeof(double) * (size_t)h->fx_m, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return RVIO_OK;
 }
 

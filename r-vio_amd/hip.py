@@ -32,6 +32,7 @@ SYMBOLS = [
     "rvio_hip_update_aux", "rvio_hip_update_aux_dev", "rvio_hip_get_aux_diag",
     "rvio_hip_predict_cov", "rvio_hip_predict_cov_dev", "rvio_hip_set_imu_odometry_cov", "rvio_hip_get_imu_odometry_cov",
     "rvio_standstill_config_default", "rvio_hip_set_standstill", "rvio_hip_standstill", "rvio_hip_standstill_dev", "rvio_hip_get_standstill",
+    "rvio_hip_update_fix", "rvio_hip_update_fix_dev", "rvio_hip_get_fix", "rvio_hip_get_fix_rows",
 ]
 
 _LIB = None
@@ -589,3 +590,28 @@ class RvioHip:
         r = abi.rvio_standstill()
         self._ck(self.L.rvio_hip_get_standstill(self.h, int(instance), C.byref(r)), "get_standstill")
         return r
+
+    # ---- absolute fixes: position, attitude, pose, gravity rows linearised on the device (csrc/fix_rows.hip in front of the auxiliary update)
+    def update_fix(self, kind, fix, gate=0, instance=-1):
+        """fuse one abi.rvio_fix (host record) of kind abi.RVIO_FIX_*; instance: 0 .. B - 1, or -1 = every instance.  Asynchronous."""
+        self._ck(self.L.rvio_hip_update_fix(self.h, int(instance), int(kind), int(gate), C.byref(fix) if fix is not None else None), "update_fix")
+
+    def update_fix_dev(self, kind, gate, d_fix_ptr, fix_stride=0, d_active_ptr=None):
+        """the same on device records: instance z reads d_fix + z * fix_stride records (0: shared); d_active: None or one int32 per instance"""
+        self._ck(self.L.rvio_hip_update_fix_dev(self.h, int(kind), int(gate), C.c_void_p(d_fix_ptr), C.c_size_t(int(fix_stride)),
+                                                C.c_void_p(d_active_ptr) if d_active_ptr else None), "update_fix_dev")
+
+    def get_fix(self, instance=0):
+        """the abi.rvio_fix_diag record of one instance from the last update_fix* call (waits for the filter stream only)"""
+        r = abi.rvio_fix_diag()
+        self._ck(self.L.rvio_hip_get_fix(self.h, int(instance), C.byref(r)), "get_fix")
+        return r
+
+    def get_fix_rows(self, instance=0):
+        """(H [m x d], sigma [m]) as the device formed them in the last update_fix* call"""
+        m, d = C.c_int32(0), C.c_int32(0)
+        self._ck(self.L.rvio_hip_get_fix_rows(self.h, int(instance), C.byref(m), C.byref(d), None, None), "get_fix_rows")
+        H, sigma = np.zeros((m.value, d.value)), np.zeros(m.value)
+        dp = C.POINTER(C.c_double)
+        self._ck(self.L.rvio_hip_get_fix_rows(self.h, int(instance), C.byref(m), C.byref(d), H.ctypes.data_as(dp), sigma.ctypes.data_as(dp)), "get_fix_rows")
+        return H, sigma

@@ -1,0 +1,29 @@
+// Host build of csrc/launch_plan.h for tests/test_fix_plan.py: the launch form of the absolute-fix rows (fix_launch) and what the plan does
+// with the kernel's static LDS, as plain C functions.
+#include <cstring>
+#include "../../r-vio_amd/csrc/launch_plan.h"
+
+extern "C" {
+long fp_lds_limit() { return RVIO_LDS_LIMIT; }
+int fp_threads() { return LP_FIX_T; }
+int fp_rows() { return LP_FIX_ROWS; }
+int fp_head_doubles() { return LP_FIX_HEAD; }
+int fp_num_kernels() { return LPK_COUNT; }
+const char* fp_kernel_name(int k) { return (k >= 0 && k < LPK_COUNT) ? kLpKernelName[k] : ""; }
+// out: gx, gy, gz, threads, dynamic LDS bytes, LpKernel
+void fp_launch(int batch, long* out) {
+    const LpLaunch l = fix_launch(batch);
+    out[0] = l.gx; out[1] = l.gy; out[2] = l.gz; out[3] = l.threads; out[4] = (long)l.lds; out[5] = l.kernel;
+}
+// the aux launch that runs behind it: out as above (m = 3 and 6 rows at n clones)
+void fp_aux_launch(int n, int m, int batch, long* out) {
+    const LpLaunch l = aux_update_launch(n, m, batch);
+    out[0] = l.gx; out[1] = l.gy; out[2] = l.gz; out[3] = l.threads; out[4] = (long)l.lds; out[5] = l.kernel;
+}
+// the plan of a handle: its refusal code, and the dynamic-LDS limit create sets for LpKernel k
+int fp_plan(int max_len, int n_features, int batch, const size_t* statics, int k, long* attr) {
+    const LaunchPlan p = launch_plan(max_len, n_features, batch, statics);
+    *attr = (long)p.attr[k];
+    return p.rc;
+}
+}

@@ -1,0 +1,63 @@
+"""The launch form of the absolute-fix rows (csrc/launch_plan.h fix_launch), compiled with g++ from tests/hostemu/fix_plan_emu.cpp and checked
+on the CPU at batch 1 / 8 / 128 / 2048: one wave per instance, no dynamic LDS, and the kernel's static LDS — read from the built library's gfx950
+code object under the name launch_plan.h gives it — the 6 x 24 head of the Jacobian and no more, within the 160 KiB of a CU.  The aux launch behind
+it takes the <4> form at m = 3 (POSITION, ATTITUDE, GRAVITY) and the <16> form at m = 6 (POSE)."""
+import ctypes as C
+import os
+import subprocess
+
+import pytest
+
+from test_aux_plan import static_lds  # noqa: F401  (the fixture that reads the code object's notes)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "hostemu", "fix_plan_emu.cpp")
+LIMIT = 163840
+NAME = "fix_rows_kernel"
+
+
+@pytest.fixture(scope="module")
+def emu(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("fix_plan") / "fix_plan_emu.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unused-variable", SRC, "-o", so])
+    L = C.CDLL(so)
+    L.fp_kernel_name.restype = C.c_char_p
+    L.fp_lds_limit.restype = C.c_long
+    return L
+
+
+def test_constants(emu):
+    assert emu.fp_lds_limit() == LIMIT and emu.fp_threads() == 64 and emu.fp_rows() == 6 and emu.fp_head_doubles() == 144
+
+
+@pytest.mark.parametrize("batch", [1, 8, 128, 2048])
+def test_one_wave_per_instance_within_a_cu(emu, static_lds, batch):
+    names = [emu.fp_kernel_name(k).decode() for k in range(emu.fp_num_kernels())]
+    assert NAME in names and NAME in static_lds, "fix_rows_kernel must be named in kLpKernelName and present in the built library"
+    out = (C.c_long * 6)()
+    emu.fp_launch(batch, out)
+    gx, gy, gz, threads, lds, kern = list(out)
+    assert (gx, gy, gz, threads) == (1, 1, batch, 64)
+    assert names[kern] == NAME and lds == 0
+    st = static_lds[NAME]
+    print("batch %d: static LDS of %s = %d B, dynamic 0" % (batch, NAME, st))
+    # the 6 x 24 head, nothing else
+    assert 8 * emu.fp_head_doubles() <= st <= 2048 and st + lds <= LIMIT
+    # the plan sets no dynamic-LDS limit for it and accepts the stock handle with this static part ...
+    statics = (C.c_size_t * len(names))(*[static_lds[nm] for nm in names])
+    attr = C.c_long(-1)
+    assert emu.fp_plan(11, 200, batch, statics, kern, C.byref(attr)) == 0 and attr.value == 0
+    # ... and refuses, by name of the limit, a build whose kernel would not fit a CU
+    statics[kern] = LIMIT + 8
+    assert emu.fp_plan(11, 200, batch, statics, kern, C.byref(attr)) == 1
+
+
+@pytest.mark.parametrize("batch", [1, 128])
+@pytest.mark.parametrize("n", [0, 10, 31])
+def test_the_update_behind_it_takes_both_aux_forms(emu, n, batch):
+    names = [emu.fp_kernel_name(k).decode() for k in range(emu.fp_num_kernels())]
+    out = (C.c_long * 6)()
+    emu.fp_aux_launch(n, 3, batch, out)
+    assert names[out[5]] == "aux_update_kernel<4>" and out[2] == batch
+    emu.fp_aux_launch(n, 6, batch, out)
+    assert names[out[5]] == "aux_update_kernel<16>" and out[2] == batch
