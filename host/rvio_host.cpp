@@ -400,15 +400,72 @@ int System::fix_gravity(const double a[3], const double sigma[3], bool gate) {
     for (int i = 0; i < 3; ++i) { f.z[i] = a[i]; f.sigma[i] = sigma[i]; }
     return update_fix(RVIO_FIX_GRAVITY, f, gate);
 }
-void System::queue_fixes(std::vector<FixRow> rows, bool gate) {
-    std::stable_sort(rows.begin(), rows.end(), [](const FixRow& a, const FixRow& b) { return a.t < b.t; });
-    fx_rows_ = std::move(rows); fx_next_ = 0; fx_gate_ = gate;
+// ---- past-frame fixes (rvio_hip_update_fix_past): a delayed fix fused at the frame it was taken
+FixAge resolve_fix_age(const std::vector<double>& stamps, double t, bool interpolate) {
+    FixAge r;
+    if (stamps.empty() || !(t < stamps.front())) { r.where = FIX_AGE_NOW; return r; }      // at or past the newest composed image
+    if (t < stamps.back()) { r.where = FIX_AGE_TOO_OLD; return r; }
+    size_t a = 0;
+    while (a + 1 < stamps.size() && !(stamps[a + 1] < t)) ++a;      // the newest a with stamps[a + 1] < t <= stamps[a] (t == the oldest stamp: the last)
+    double lam = 0.0;
+    if (a + 1 < stamps.size() && stamps[a] > stamps[a + 1]) lam = (stamps[a] - t) / (stamps[a] - stamps[a + 1]);
+    r.where = FIX_AGE_PAST;
+    if (interpolate) {
+        if (lam < kFixAgeSnap) lam = 0.0;                          // (on a frame up to rounding of the stamps: that frame)
+        else if (lam > 1.0 - kFixAgeSnap) { ++a; lam = 0.0; }
+        r.age = (int)a; r.frac = lam;
+    } else {
+        r.age = (int)(lam < 0.5 ? a : a + 1); r.frac = 0.0;        // the nearest frame, a tie to the older
+    }
+    return r;
 }
-// behind the frame stamped t: every queued fix whose stamp that frame has reached, through the typed calls
+int System::update_fix_at(double t, int kind, const rvio_fix& fix, bool gate) {
+    if (!h_ || !ready_) { err_ = "System::update_fix_at before the filter is initialised"; return -1; }
+    const FixAge w = resolve_fix_age(std::vector<double>(stamps_.begin(), stamps_.end()), t, kind == RVIO_FIX_POSITION);
+    if (w.where == FIX_AGE_NOW) return update_fix(kind, fix, gate);
+    if (w.where == FIX_AGE_TOO_OLD) { ++fx_dropped_; return 0; }
+    if (rvio_hip_update_fix_past(h_, -1, kind, gate ? 1 : 0, w.age, w.frac, &fix) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+    return 0;
+}
+int System::fix_position_at(double t, const double p[3], const double sigma[3], const double* lever, bool gate) {
+    rvio_fix f{};
+    for (int i = 0; i < 3; ++i) { f.z[i] = p[i]; f.sigma[i] = sigma[i]; f.lever[i] = lever ? lever[i] : 0.0; }
+    return update_fix_at(t, RVIO_FIX_POSITION, f, gate);
+}
+int System::fix_attitude_at(double t, const double q[4], const double sigma[3], bool gate) {
+    rvio_fix f{};
+    for (int i = 0; i < 4; ++i) f.z[3 + i] = q[i];
+    for (int i = 0; i < 3; ++i) f.sigma[3 + i] = sigma[i];
+    return update_fix_at(t, RVIO_FIX_ATTITUDE, f, gate);
+}
+int System::fix_pose_at(double t, const double p[3], const double q[4], const double sigma_p[3], const double sigma_q[3], const double* lever, bool gate) {
+    rvio_fix f{};
+    for (int i = 0; i < 4; ++i) f.z[3 + i] = q[i];
+    for (int i = 0; i < 3; ++i) { f.z[i] = p[i]; f.sigma[i] = sigma_p[i]; f.sigma[3 + i] = sigma_q[i]; f.lever[i] = lever ? lever[i] : 0.0; }
+    return update_fix_at(t, RVIO_FIX_POSE, f, gate);
+}
+// behind a composed frame: its stamp joins the window's, newest first, one per frame the clone window still reaches
+void System::note_stamp(double t) {
+    stamps_.push_front(t);
+    const int d = state_dim();
+    const size_t keep = d >= 24 ? (size_t)(d - 24) / 6 + 1 : 1;
+    while (stamps_.size() > keep) stamps_.pop_back();
+}
+void System::queue_fixes(std::vector<FixRow> rows, bool gate, double latency) {
+    std::stable_sort(rows.begin(), rows.end(), [](const FixRow& a, const FixRow& b) { return a.t < b.t; });
+    fx_rows_ = std::move(rows); fx_next_ = 0; fx_gate_ = gate; fx_latency_ = latency;
+}
+// behind the frame stamped t: every queued fix whose stamp that frame has reached, through the typed calls.  With a latency (>= 0) a fix is
+// available once the frame's stamp has reached its t + latency, and is fused at its own t (the _at calls; GRAVITY has no past form: at the frame)
 int System::apply_fixes(double t) {
-    for (; fx_next_ < fx_rows_.size() && fx_rows_[fx_next_].t <= t; ++fx_next_) {
+    const bool late = fx_latency_ >= 0.0;
+    for (; fx_next_ < fx_rows_.size() && fx_rows_[fx_next_].t + (late ? fx_latency_ : 0.0) <= t; ++fx_next_) {
         const rvio_fix& f = fx_rows_[fx_next_].fix;
         int rc = -1;
+        if (late && fx_rows_[fx_next_].kind != RVIO_FIX_GRAVITY) {
+            if (update_fix_at(fx_rows_[fx_next_].t, fx_rows_[fx_next_].kind, f, fx_gate_) < 0) return -1;
+            continue;
+        }
         switch (fx_rows_[fx_next_].kind) {
             case RVIO_FIX_POSITION: rc = fix_position(f.z, f.sigma, f.lever, fx_gate_); break;
             case RVIO_FIX_ATTITUDE: rc = fix_attitude(f.z + 3, f.sigma + 3, fx_gate_); break;
@@ -547,6 +604,7 @@ int System::MonoVIO(PoseLine* pose) {
                     for (int i = 0; i < 3; ++i) { wm_[i] /= n_imu_; am_[i] /= n_imu_; }
                 if (rvio_hip_initialize(h_, wm_, am_, n_imu_) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
                 ready_ = true;
+                stamps_.clear();
                 break;
             }
         }
@@ -573,6 +631,7 @@ int System::MonoVIO(PoseLine* pose) {
     // the timed body of MonoVIO (System.cc:253-367): track -> propagate -> update -> augment -> compose
     if (!rec_) {
         if (rvio_hip_frame(h_, image.px.data(), row_bytes, pi, m, nullptr, 0) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+        note_stamp(image.t);
         if (ss_on_ && standstill(image.t, pi, m) < 0) return -1;   // (ahead of the pose read-back: the pose line is the updated state's)
         if (fx_next_ < fx_rows_.size() && apply_fixes(image.t) < 0) return -1;   // (likewise)
         if (pose) {
@@ -595,6 +654,7 @@ int System::MonoVIO(PoseLine* pose) {
     if (rvio_hip_propagate(h_, pi, m) != RVIO_OK) return fail();                          // System.cc:263
     if (do_update && rvio_hip_update_tracked(h_) != RVIO_OK) return fail();               // System.cc:266-268
     if (rvio_hip_augment_compose(h_, do_augment) != RVIO_OK) return fail();               // System.cc:279-365
+    note_stamp(image.t);
     if (ss_on_ && standstill(image.t, pi, m) < 0) return -1;
     if (fx_next_ < fx_rows_.size() && apply_fixes(image.t) < 0) return -1;
     PoseLine pl;

@@ -95,6 +95,15 @@ struct FixRow { double t = 0; int kind = 0; rvio_fix fix{}; };
 // unit length by more than 1e-6 — is an error that names the line: "<name>:<line number>: <why>: <the line>".
 bool parse_fixes(const std::string& text, const std::string& name, std::vector<FixRow>* out, std::string* err);
 bool read_fixes(const std::string& path, std::vector<FixRow>* out, std::string* err);
+// Where a fix stamped t falls among the image stamps of the frames the clone window still reaches (newest first, stamps[a] = the frame of age a):
+// FIX_AGE_NOW: at or past the newest composed image (or no frame yet) — fuse at the current state; FIX_AGE_TOO_OLD: older than the oldest frame —
+// drop; FIX_AGE_PAST: (age, frac) for rvio_hip_update_fix_past.  interpolate (POSITION): stamps[age + 1] < t <= stamps[age], frac =
+// (stamps[age] - t) / (stamps[age] - stamps[age + 1]) in [0, 1), snapped onto a frame within kFixAgeSnap of it.  Otherwise (ATTITUDE, POSE: no
+// attitude interpolation) the NEAREST frame, frac = 0 — exact for a fix derived from an image, off by up to half a frame of motion for one that is not.
+enum { FIX_AGE_TOO_OLD = -1, FIX_AGE_PAST = 0, FIX_AGE_NOW = 1 };
+struct FixAge { int where = FIX_AGE_NOW; int age = 0; double frac = 0.0; };
+constexpr double kFixAgeSnap = 1e-6;
+FixAge resolve_fix_age(const std::vector<double>& stamps, double t, bool interpolate);
 
 class System {
 public:
@@ -165,8 +174,20 @@ public:
     int fix_gravity(const double a[3], const double sigma[3], bool gate);
     // fixes with time stamps (rvio_replay --fix): MonoVIO fuses each one behind the first frame whose image stamp is >= its t, ahead of that
     // frame's pose read-back — AT THAT FRAME'S STATE, not at t: bridging the gap (propagating to the fix's stamp) is not done.  Rows are sorted by t
-    void queue_fixes(std::vector<FixRow> rows, bool gate);
+    // latency >= 0 (rvio_replay --fix-latency): a fix becomes available behind the first frame whose stamp is >= its t + latency and is fused AT ITS
+    // OWN t through the _at calls below; < 0: as described above
+    void queue_fixes(std::vector<FixRow> rows, bool gate, double latency = -1.0);
     long fixes_applied() const { return (long)fx_next_; }
+    // Delayed fixes (rvio_hip_update_fix_past): the same measurements with the time t they were taken at, on the clock of the image stamps.  The
+    // System keeps the stamp of every frame the clone window still reaches; t is resolved against them (resolve_fix_age above): a POSITION is
+    // interpolated between the two frames around t, an ATTITUDE or POSE goes to the nearest frame (exact for image-derived fixes, otherwise off by
+    // up to half a frame of motion); a t at or past the newest composed image falls through to the calls above (fused at the current state: the gap
+    // to a stamp newer than the last image is not bridged); a t older than the window is dropped and counted.  0, or -1 with error().
+    int update_fix_at(double t, int kind, const rvio_fix& fix, bool gate);
+    int fix_position_at(double t, const double p[3], const double sigma[3], const double* lever, bool gate);
+    int fix_attitude_at(double t, const double q[4], const double sigma[3], bool gate);
+    int fix_pose_at(double t, const double p[3], const double q[4], const double sigma_p[3], const double sigma_q[3], const double* lever, bool gate);
+    long fixes_dropped() const { return fx_dropped_; }
     // columns of an auxiliary H right now: 24 + 6 clones, the clones counted as the library counts them (one per frame behind the first, up
     // to Tracker.nMaxTrackingLength - 1) — no read-back
     int state_dim() const;
@@ -213,6 +234,10 @@ private:
     std::vector<FixRow> fx_rows_; // queue_fixes, sorted by t
     size_t fx_next_ = 0;          // the first row not yet fused
     bool fx_gate_ = false;
+    double fx_latency_ = -1.0;    // queue_fixes: >= 0 = fuse at the fix's own stamp once t + latency has passed
+    long fx_dropped_ = 0;         // _at calls older than the window
+    std::deque<double> stamps_;   // image stamps of the composed frames the clone window still reaches, newest first
+    void note_stamp(double t);
     int apply_fixes(double t);
 };
 

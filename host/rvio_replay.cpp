@@ -25,8 +25,14 @@
 //                                        linearised and fused on the device (System::fix_position / _attitude / _pose / _gravity) behind the first
 //                                        frame whose image stamp is >= t, ahead of that frame's pose line — at THAT frame's state, not at t: the gap is
 //                                        not bridged.  --fix-gate: the 95 % chi-square gate.  A malformed line is an error that names the line
+//                                        [--fix-latency S]   (with --fix) the fixes arrive S seconds late, as real ones do: a row becomes available behind
+//                                        the first frame whose image stamp is >= t + S and is fused AT ITS OWN t, against the pose the clone window
+//                                        still holds for that time (System::fix_*_at -> rvio_hip_update_fix_past): a position interpolated between
+//                                        the two frames around t, an attitude or pose at the nearest frame; a row older than the window by then is
+//                                        dropped and counted, a gravity row is fused at the frame.  S: a finite number >= 0
 //   rvio_replay --check-settings <settings.yaml>        print the parsed configuration (no GPU needed)
 //   rvio_replay --check-fix <fixes.txt>                 print the parsed fix file, one JSON object per fix (no GPU needed)
+//   rvio_replay --check-fix-age <t0,t1,..> <t> [nearest] where a fix stamped t falls among the window's image stamps, newest first (no GPU needed)
 //   rvio_replay --check-dataset <asl_root>              print what the dataset reader found (no GPU needed)
 //   rvio_replay --check-image <file.png|.pgm>           decode one image and print its size and checksum (no GPU needed)
 #include <dlfcn.h>
@@ -114,6 +120,26 @@ static int check_fix(const char* path) {
     return 0;
 }
 
+// --check-fix-age: resolve_fix_age on stamps given newest first
+static int check_fix_age(const char* list, const char* t_arg, bool nearest) {
+    std::vector<double> stamps;
+    std::string flat = list;
+    for (char& c : flat) if (c == ',') c = ' ';
+    const char* p = flat.c_str();
+    for (char* end = nullptr;; p = end) { const double v = std::strtod(p, &end); if (end == p) break; stamps.push_back(v); }
+    const FixAge w = resolve_fix_age(stamps, std::atof(t_arg), !nearest);
+    std::printf("{\"where\": %d, \"age\": %d, \"frac\": %.17g}\n", w.where, w.age, w.frac);
+    return 0;
+}
+// --fix-latency: seconds, finite and >= 0
+static bool parse_latency(const char* arg, double* out) {
+    char* end = nullptr;
+    const double v = std::strtod(arg, &end);
+    if (end == arg || *end != 0 || !std::isfinite(v) || v < 0) return false;
+    *out = v;
+    return true;
+}
+
 // ---------------------------------------------------------------- --velocity
 struct VelocityRows {
     std::vector<int> has;                 // per image of the dataset: a row was matched to it
@@ -180,6 +206,7 @@ struct PassOptions {
     VelocityRows* velocity = nullptr;    // --velocity
     const std::vector<FixRow>* fixes = nullptr;   // --fix
     bool fix_gate = false;
+    double fix_latency = -1.0;           // --fix-latency (< 0: not given)
 };
 static bool dump_frame(System& sys, const rvio_config& c, FrameDump* d) {
     rvio_hip* h = sys.handle();
@@ -200,7 +227,7 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
     if (o.landmarks && !sys.record_landmarks_to(o.landmarks)) { *err = sys.error(); return 1; }
     if (o.odometry && !sys.record_odometry_to(o.odometry, o.odometry_ring)) { *err = sys.error(); return 1; }
     if (o.imu_odometry && !sys.record_imu_odometry_to(o.imu_odometry, o.imu_odometry_ring, o.imu_odometry_cov)) { *err = sys.error(); return 1; }
-    if (o.fixes) sys.queue_fixes(*o.fixes, o.fix_gate);
+    if (o.fixes) sys.queue_fixes(*o.fixes, o.fix_gate, o.fix_latency);
     size_t ii = 0;
     long n_images = 0, n_frames = 0;
     double t_filter = 0;
@@ -312,6 +339,7 @@ int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "--check-settings")) return check_settings(argv[2]);
     if (argc >= 3 && !std::strcmp(argv[1], "--check-dataset")) return check_dataset(argv[2]);
     if (argc >= 3 && !std::strcmp(argv[1], "--check-fix")) return check_fix(argv[2]);
+    if (argc >= 4 && !std::strcmp(argv[1], "--check-fix-age")) return check_fix_age(argv[2], argv[3], argc >= 5 && !std::strcmp(argv[4], "nearest"));
     if (argc >= 3 && !std::strcmp(argv[1], "--check-image")) {   // --check-image FILE [--bgr] [--encoding NAME]
         bool rgb = true; const char* enc = nullptr;
         for (int i = 3; i < argc; ++i) {
@@ -323,7 +351,7 @@ int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--record-dir DIR] [--record]\n"
                              "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--imu-odometry-cov] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n"
-                             "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate] [--standstill FILE] [--fix FILE] [--fix-gate]\n", argv[0]);
+                             "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate] [--standstill FILE] [--fix FILE] [--fix-gate] [--fix-latency S]\n", argv[0]);
         return 2;
     }
     const char* out_path = nullptr;
@@ -333,7 +361,7 @@ int main(int argc, char** argv) {
     const char* imu_odometry = nullptr; int imu_odometry_ring = 4096; bool imu_odometry_cov = false;
     const char* velocity = nullptr; double velocity_sigma = 0.05; bool velocity_gate = false;
     const char* standstill = nullptr;
-    const char* fix = nullptr; bool fix_gate = false;
+    const char* fix = nullptr; bool fix_gate = false; double fix_latency = -1.0;
     const char* record_dir = "."; bool force_record = false, sync_every = false, self = false; int noise_wgs = 0;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -356,8 +384,13 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--standstill") && i + 1 < argc) standstill = argv[++i];   // one line per frame: t T disparity n_pairs flags gamma (needs Standstill.Enable: 1)
         else if (!std::strcmp(argv[i], "--fix") && i + 1 < argc) fix = argv[++i];   // `t kind values... sigmas... [lever]` lines fused behind the first frame at or past t (System::fix_*)
         else if (!std::strcmp(argv[i], "--fix-gate")) fix_gate = true;
+        else if (!std::strcmp(argv[i], "--fix-latency")) {   // seconds the fixes arrive late: fused at their own stamp (System::fix_*_at)
+            if (i + 1 >= argc || !parse_latency(argv[i + 1], &fix_latency)) { std::fprintf(stderr, "--fix-latency takes seconds, a finite number >= 0\n"); return 1; }
+            ++i;
+        }
         else out_path = argv[i];
     }
+    if (fix_latency >= 0 && !fix) { std::fprintf(stderr, "--fix-latency needs --fix FILE\n"); return 1; }
     Settings s; std::string err;
     if (!read_settings(argv[1], &s, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }   // System.cc:54-58: exit(-1)
     for (const std::string& k : s.missing) std::fprintf(stderr, "settings: %s is missing (upstream would read 0); the EuRoC default is used\n", k.c_str());
@@ -380,7 +413,7 @@ int main(int argc, char** argv) {
     if (self) return selfcheck(s, d, device, max_frames, stall_seed, noise_wgs);
     if (sync_every || stall_seed >= 0 || noise_wgs > 0) {   // the plain replay with one of the two A/B pacings
         std::vector<PoseLine> poses; double ms = 0; int flags = 0;
-        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.imu_odometry_cov = imu_odometry_cov; o.velocity = vr; if (fix) { o.fixes = &fixes; o.fix_gate = fix_gate; }
+        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.imu_odometry_cov = imu_odometry_cov; o.velocity = vr; if (fix) { o.fixes = &fixes; o.fix_gate = fix_gate; o.fix_latency = fix_latency; }
         if (run_pass(s, d, device, o, &poses, nullptr, &ms, &flags, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
         if (out_path) { std::ofstream out(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } for (const PoseLine& p : poses) out << format_pose(p); }
         std::fprintf(stderr, "rvio_replay: %zu filtered frames, %.3f ms per MonoVIO call, device flags %d\n", poses.size(), ms, flags);
@@ -394,7 +427,7 @@ int main(int argc, char** argv) {
     if (odometry && !sys.record_odometry_to(odometry, odometry_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (imu_odometry && !sys.record_imu_odometry_to(imu_odometry, imu_odometry_ring, imu_odometry_cov)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (standstill && !sys.record_standstill_to(standstill)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
-    if (fix) sys.queue_fixes(fixes, fix_gate);
+    if (fix) sys.queue_fixes(fixes, fix_gate, fix_latency);
     std::ofstream out;
     if (out_path) { out.open(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } }
 
@@ -425,7 +458,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "rvio_replay: %ld images, %ld filtered frames, %.3f ms per MonoVIO call (host wall clock, pose read-back included)\n",
                  n_images, n_frames, n_images ? 1e3 * t_filter / n_images : 0.0);
     if (vr) print_velocity(*vr);
-    if (fix) std::fprintf(stderr, "rvio_replay: fix: %zu rows, %ld applied\n", fixes.size(), sys.fixes_applied());
+    if (fix && fix_latency < 0) std::fprintf(stderr, "rvio_replay: fix: %zu rows, %ld applied\n", fixes.size(), sys.fixes_applied());
+    if (fix && fix_latency >= 0) std::fprintf(stderr, "rvio_replay: fix: %zu rows, %ld fused, %ld older than the window and dropped (latency %g s)\n", fixes.size(), sys.fixes_applied() - sys.fixes_dropped(), sys.fixes_dropped(), fix_latency);
     // anything only the device saw (0 in every test and bench run): said out loud, the poses above are suspect if it is not 0
     const int flags = sys.device_flags();
     if (flags) std::fprintf(stderr, "rvio_replay: DEVICE-SIDE FLAGS %d (1 singular pivot in the solve, 2 a track the window cannot hold was dropped, "

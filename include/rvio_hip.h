@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov); standstill detection (rvio_standstill_config, rvio_standstill, rvio_standstill_config_default, rvio_hip_set_standstill, rvio_hip_standstill, rvio_hip_standstill_dev, rvio_hip_get_standstill); absolute fixes (rvio_fix_kind, rvio_fix, rvio_fix_diag, rvio_hip_update_fix, rvio_hip_update_fix_dev, rvio_hip_get_fix, rvio_hip_get_fix_rows) */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov); standstill detection (rvio_standstill_config, rvio_standstill, rvio_standstill_config_default, rvio_hip_set_standstill, rvio_hip_standstill, rvio_hip_standstill_dev, rvio_hip_get_standstill); absolute fixes (rvio_fix_kind, rvio_fix, rvio_fix_diag, rvio_hip_update_fix, rvio_hip_update_fix_dev, rvio_hip_get_fix, rvio_hip_get_fix_rows); past-frame fixes (rvio_hip_update_fix_past, rvio_hip_update_fix_past_dev, rvio_hip_frame_age) */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -647,6 +647,48 @@ int rvio_hip_get_fix(rvio_hip* h, int instance, rvio_fix_diag* out);
  * ask for m and d first.  Handing them with the record's r to rvio_hip_update_aux (RVIO_AUX_RESIDUAL) at the same state repeats the update bit
  * for bit.  Waits for the filter stream only.  Errors as rvio_hip_get_fix. */
 int rvio_hip_get_fix_rows(rvio_hip* h, int instance, int32_t* m, int32_t* d, double* H, double* sigma);
+
+/* --- past-frame fixes: a delayed fix fused at the frame it was taken (no reference counterpart) ----------------------------------- */
+/* Every real source of absolute fixes is late: a relocalisation or fiducial result belongs to an image the filter consumed some frames ago, a
+ * motion-capture pose crosses a network, a GNSS position arrives 50 - 200 ms after its epoch.  rvio_hip_update_fix fuses at the state it finds,
+ * which is wrong by the platform's motion over the latency.  The robocentric window already holds what is needed: clone i (oldest first,
+ * x[26 + 7 i ..]) = (q_i, p_i) is the relative pose between two consecutive image frames, C_i = R(q_i) rotating the older into the newer and p_i
+ * the newer frame's origin in the older, and behind augment / compose the newest clone ends at the state's reference frame {R} — the IMU frame at
+ * the newest image whose rvio_hip_augment_compose has run.  So the world pose of the IMU at any of the last n images is a function of (qG, pG) and
+ * the newest clones (stochastic cloning), and fix_past_kernel (csrc/fix_past.hip, one wave per instance, the chain as an in-wave scan) linearises
+ * the fix against it; aux_update_kernel, unchanged, runs right behind with m = 3 (POSE: 6) rows.
+ * age a = 0 .. n: images back from {R}.  a = 0 is {R} itself, NOT the current IMU pose (qk, pk), which does not enter; behind a whole frame the
+ * two coincide.  With R_G = R(x[0:4]), pG = x[4:7], l = lever:
+ *   A_0 = I, t_0 = 0;   A_m = A_{m-1} C_{n-m},   t_m = t_{m-1} - A_m p_{n-m}   (m = 1 .. a);     u_a = t_a + A_a l,  s_a = u_a - pG
+ *   POSITION  h_a = R_G^T s_a      r = z[0:3] - h_a
+ *             cols 0-2: -R_G^T [s_a x]   3-5: -R_G^T   clone i = n - m (m = 1 .. a): 24+6i..: R_G^T [(u_a - t_{m-1}) x] A_{m-1}   27+6i..: -R_G^T A_m
+ *   ATTITUDE  R(world -> IMU at that image) = A_a^T R_G;  E = R(z[3:7])^T A_a^T R_G,  r = (E21 - E12, E02 - E20, E10 - E01) / 2
+ *             cols 0-2: R_G^T                          clone i = n - m (m = 1 .. a): 24+6i..: -R_G^T A_{m-1}
+ *   POSE      the three position rows, then the three attitude rows
+ * Every column not listed is exactly 0.0: columns 6 - 23 and every clone older than n - a.  RVIO_FIX_GRAVITY has no past form (it reads ba and
+ * R_k g of now).
+ * frac (POSITION only) = lam in [0, 1): the stamp lies lam of the way from the frame of age a towards the OLDER frame of age a + 1;
+ * h = (1 - lam) h_a + lam h_{a+1} and H the same combination of the two row sets; lam > 0 needs a + 1 <= n.  ATTITUDE and POSE take frac = 0.
+ * Host form: age and frac hold for every instance the call touches, and are checked here against the window, which is handle-wide.  _dev form:
+ * d_age one int32 per instance (in a fleet every robot's latency differs), d_frac NULL (0) or one double per instance, d_fix / fix_stride /
+ * d_active as in rvio_hip_update_fix_dev; nothing on the device is checked by the host.  An instance whose age is outside 0 .. n (or a + 1 > n
+ * with lam > 0, lam outside [0, 1), lam > 0 with a kind other than POSITION) is written by neither launch and its record says so: m = 0,
+ * applied = 0, img_count = -1, r = 0.  The kernel keeps an active flag of its own per instance (the caller's AND inside the window) and the
+ * update runs on that.
+ * rvio_hip_get_fix and rvio_hip_get_fix_rows report the last call of either family; rvio_fix_diag.img_count is here the count of the frame the
+ * fix was fused against (the reference frame's count minus the age).  Everything rvio_hip_update_aux_dev documents holds: in place, `gate` as
+ * there, the pose line rewritten, no ring record, a kept clone-block factor dropped, error bit 8 on a non-positive pivot.  The first call
+ * allocates the fix block of rvio_hip_update_fix if need be, plus the flags and the staging of age / frac, outside the filter slab.
+ * RVIO_ERR_STATE as rvio_hip_update_fix.  RVIO_ERR_INVALID: what rvio_hip_update_fix refuses, RVIO_FIX_GRAVITY, NULL d_age and — host form only —
+ * frac outside [0, 1) or not 0 with a kind other than POSITION, an age outside 0 .. n, age + 1 > n with frac > 0 (rvio_hip_last_error).
+ * NOT done: attitude interpolation, time-offset estimation, iterated updates, stamps newer than the last composed image (IMU bridging). */
+int rvio_hip_update_fix_past(rvio_hip* h, int instance, int kind, int gate, int age, double frac, const rvio_fix* fix);
+int rvio_hip_update_fix_past_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_stride, const int32_t* d_age,
+                                 const double* d_frac /* NULL: 0 */, const int32_t* d_active);
+/* The age that the frame counted img_count (as rvio_odom.img_count and rvio_frame_info report it) has NOW: host arithmetic only, nothing is
+ * waited for.  The handle counts a frame in rvio_hip_frame_plan and composes it in rvio_hip_augment_compose; between the two the newest count is
+ * not composed yet.  RVIO_ERR_INVALID: NULL argument, no state, a frame not yet composed, a frame that has left the clone window. */
+int rvio_hip_frame_age(rvio_hip* h, int img_count, int* age);
 
 /* --- feature-sharded updater (no reference counterpart) ------ */
 /* Stage A: per-feature build + gate on the features f with f % world == rank,

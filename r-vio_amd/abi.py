@@ -563,6 +563,80 @@ def fix_model(cfg, x, kind, fix):
     return np.vstack(rows_H), np.concatenate(rows_r), np.concatenate(rows_s)
 
 
+# ---- past-frame fixes (rvio_hip_update_fix_past*, csrc/fix_past.hip in front of the auxiliary update)
+def _fix_past_chain(x, age):
+    """(A_0 .. A_age, t_0 .. t_age): A_m rotates the IMU frame m images back into the reference frame {R}, t_m is that frame's origin in {R}.
+    Clone i = n - m holds the step from the frame m back to the frame m - 1 back: A_m = A_{m-1} C_i, t_m = t_{m-1} - A_m p_i."""
+    n = (len(x) - 26) // 7
+    assert 0 <= age <= n, "age outside the window"
+    A, t = [np.eye(3)], [np.zeros(3)]
+    for m in range(1, age + 1):
+        i = n - m
+        A.append(A[-1] @ quat_to_rot(x[26 + 7 * i: 30 + 7 * i]))
+        t.append(t[-1] - A[-1] @ x[30 + 7 * i: 33 + 7 * i])
+    return A, t
+
+
+def fix_past_h(x, age, lever=(0.0, 0.0, 0.0), frac=0.0):
+    """The predicted measurement of a fix taken `age` images back from the state's reference frame {R} (age 0 = {R} itself, the IMU frame at
+    the newest composed image; the current (qk, pk) does not enter), laid out like rvio_fix.z: [0:3] the world position of the sensed point at
+    that image, R_G^T (t_a + A_a l - pG) — with frac in [0, 1) the point frac of the way towards the frame age + 1 back; [3:7] the quaternion
+    world -> IMU at the frame `age` back, R = A_a^T R_G (never interpolated)."""
+    x, l = np.asarray(x, float), np.broadcast_to(np.asarray(lever, float), (3,))
+    frac = float(frac)
+    assert 0.0 <= frac < 1.0
+    RG = quat_to_rot(x[0:4])
+    A, t = _fix_past_chain(x, age + (1 if frac > 0 else 0))
+    z = np.zeros(7)
+    z[0:3] = RG.T @ (t[age] + A[age] @ l - x[4:7])
+    if frac > 0:
+        z[0:3] = (1 - frac) * z[0:3] + frac * (RG.T @ (t[age + 1] + A[age + 1] @ l - x[4:7]))
+    z[3:7] = rot_to_quat(A[age].T @ RG)
+    return z
+
+
+def _fix_past_rows(x, a, l, A, t, att):
+    """the three position rows (att: attitude rows) at the whole age a"""
+    n = (len(x) - 26) // 7
+    RGt = quat_to_rot(x[0:4]).T
+    H = np.zeros((3, 24 + 6 * n))
+    if att:
+        H[:, 0:3] = RGt
+        for m in range(1, a + 1):
+            H[:, 24 + 6 * (n - m): 27 + 6 * (n - m)] = -RGt @ A[m - 1]
+        return H
+    u = t[a] + A[a] @ l
+    H[:, 0:3], H[:, 3:6] = -RGt @ _skew(u - x[4:7]), -RGt
+    for m in range(1, a + 1):
+        c = 24 + 6 * (n - m)
+        H[:, c: c + 3], H[:, c + 3: c + 6] = RGt @ _skew(u - t[m - 1]) @ A[m - 1], -RGt @ A[m]
+    return H
+
+
+def fix_past_model(x, kind, fix, age, frac=0.0):
+    """NumPy float64 model of csrc/fix_past.hip: (H [m x d], r [m], sigma [m]) of one fix (rvio_fix, or anything with z, sigma, lever) taken
+    `age` images back (POSITION: frac of the way towards age + 1), linearised at the state x in the error-state order of P under
+    R_true ~ (I - [dth x]) R.  The table of include/rvio_hip.h; calls nothing from the library or the oracle."""
+    x, frac = np.asarray(x, float), float(frac)
+    assert kind in (RVIO_FIX_POSITION, RVIO_FIX_ATTITUDE, RVIO_FIX_POSE), "kind"
+    assert 0.0 <= frac < 1.0 and (frac == 0.0 or kind == RVIO_FIX_POSITION)
+    z, sg, l = (np.array([float(v) for v in a]) for a in (fix.z, fix.sigma, fix.lever))
+    RG = quat_to_rot(x[0:4])
+    A, t = _fix_past_chain(x, age + (1 if frac > 0 else 0))
+    rows_H, rows_r, rows_s = [], [], []
+    if kind in (RVIO_FIX_POSITION, RVIO_FIX_POSE):
+        H, h = _fix_past_rows(x, age, l, A, t, False), RG.T @ (t[age] + A[age] @ l - x[4:7])
+        if frac > 0:
+            H = (1 - frac) * H + frac * _fix_past_rows(x, age + 1, l, A, t, False)
+            h = (1 - frac) * h + frac * (RG.T @ (t[age + 1] + A[age + 1] @ l - x[4:7]))
+        rows_H.append(H), rows_r.append(z[0:3] - h), rows_s.append(sg[0:3])
+    if kind in (RVIO_FIX_ATTITUDE, RVIO_FIX_POSE):
+        E = quat_to_rot(z[3:7]).T @ A[age].T @ RG
+        rows_H.append(_fix_past_rows(x, age, l, A, t, True))
+        rows_r.append(0.5 * np.array([E[2, 1] - E[1, 2], E[0, 2] - E[2, 0], E[1, 0] - E[0, 1]])), rows_s.append(sg[3:6])
+    return np.vstack(rows_H), np.concatenate(rows_r), np.concatenate(rows_s)
+
+
 # Camera.T_BC0 of config/rvio_euroc.yaml:55-62 (row-major)
 _T_BC0 = [0.0148655429818, -0.999880929698, 0.00414029679422, -0.0216401454975,
           0.999557249008, 0.0149672133247, 0.025715529948, -0.064676986768,

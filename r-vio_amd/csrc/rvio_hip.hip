@@ -30,6 +30,7 @@
 #include "aux_update.hip"  // the auxiliary measurement update: wheel odometry, zero velocity, speed over ground (rvio_hip_update_aux)
 #include "standstill.hip"  // standstill detection in front of it: the zero-velocity update of the instances that do not move (rvio_hip_standstill)
 #include "fix_rows.hip"    // absolute fixes in front of it: position, attitude, pose, gravity rows linearised at the current state (rvio_hip_update_fix)
+#include "fix_past.hip"    // ... and delayed ones, linearised against the pose the clone window holds for the frame they were taken at (rvio_hip_update_fix_past)
 #pragma clang fp contract(off)
 #include "frontend_kernels.hip"
 #include "klt3.hip"
@@ -78,6 +79,7 @@ struct rvio_hip {
     int cur = 0;
     int img_count = 0;      // host mirror of nImageCountAfterInit (data-independent)
     int n_clones_host = 0;  // host mirror of nCloneStates (data-independent)
+    int composed_count = 0; // img_count of the last frame whose augment / compose has run: the state's reference frame (img_count runs ahead of it between rvio_hip_frame_plan and rvio_hip_augment_compose)
     // update scratch
     double *partial = nullptr, *block = nullptr, *Ab = nullptr, *Tbuf = nullptr, *W = nullptr, *Mg = nullptr, *U = nullptr, *G = nullptr,
            *Pt1 = nullptr, *tm_global = nullptr, *gamma = nullptr, *pfinv = nullptr;
@@ -227,6 +229,11 @@ struct rvio_hip {
     char *fx_stage = nullptr, *fx_pin = nullptr;
     hipEvent_t evFix = nullptr;
     int fx_kind = 0, fx_m = 0, fx_d = 0;
+    // past-frame fixes (fix_past.hip) reuse that block and add one of their own with the first rvio_hip_update_fix_past* call: the kernel's flags
+    // (one int32 per instance) and the staging of the host form (one rvio_fix; frac, age and flag per instance), with its pinned twin and event
+    int32_t* fp_flag = nullptr;
+    char *fp_stage = nullptr, *fp_pin = nullptr;
+    hipEvent_t evFixPast = nullptr;
     // colour input (rvio_hip_set_image_format): the gray images every stage behind gray_kernel reads instead of the caller's.  Allocated with the
     // first colour format, outside the slab (a mono handle keeps its memory layout), instance stride W * H; four in rotation like d_eq2[] (see
     // build_pyramid_dev for who reads a slot last)
@@ -602,6 +609,7 @@ static const void* lp_kernel_fn(int k) {
         case LPK_IMU_COV: return (const void*)imu_cov_kernel;
         case LPK_STANDSTILL: return (const void*)standstill_kernel;
         case LPK_FIX: return (const void*)fix_rows_kernel;
+        case LPK_FIX_PAST: return (const void*)fix_past_kernel;
     }
     return nullptr;
 }
@@ -821,6 +829,7 @@ static int set_state_range(rvio_hip* h, int lo, int hi, const double* x, int xdi
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->n_clones_host = n;
+    h->composed_count = h->img_count;   // (a state handed in is a composed one: its newest clone ends at its reference frame)
     h->has_state = true;
     return RVIO_OK;
 }
@@ -1809,19 +1818,10 @@ int rvio_hip_update_fix_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_f
 }
 // host record: checked here, packed into the pinned block once the copy of the previous call has left it, copied and consumed on the filter stream —
 // no wait for the stream itself
+static int fix_record_check(rvio_hip* h, int kind, const rvio_fix* fix);
 int rvio_hip_update_fix(rvio_hip* h, int instance, int kind, int gate, const rvio_fix* fix) {
     if (!h || !fix || kind < RVIO_FIX_POSITION || kind > RVIO_FIX_GRAVITY || (gate != 0 && gate != 1) || instance < -1 || instance >= h->batch) return RVIO_ERR_INVALID;
-    const bool pos = kind == RVIO_FIX_POSITION || kind == RVIO_FIX_POSE, att = kind == RVIO_FIX_ATTITUDE || kind == RVIO_FIX_POSE, vec = pos || kind == RVIO_FIX_GRAVITY;
-    auto fin = [](const double* p, int k) { for (int i = 0; i < k; ++i) if (!std::isfinite(p[i])) return false; return true; };
-    auto positive = [](const double* p, int k) { for (int i = 0; i < k; ++i) if (!(p[i] > 0)) return false; return true; };
-    if ((vec && !(fin(fix->z, 3) && fin(fix->sigma, 3))) || (att && !(fin(fix->z + 3, 4) && fin(fix->sigma + 3, 3))) || (pos && !fin(fix->lever, 3))) {
-        h->err = "rvio_hip_update_fix: an entry of z, sigma or lever that this kind uses is not finite"; return RVIO_ERR_INVALID;
-    }
-    if ((vec && !positive(fix->sigma, 3)) || (att && !positive(fix->sigma + 3, 3))) { h->err = "rvio_hip_update_fix: a sigma that this kind uses is not > 0"; return RVIO_ERR_INVALID; }
-    if (att) {
-        const double* q = fix->z + 3;
-        if (std::fabs(std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]) - 1.0) > 1e-6) { h->err = "rvio_hip_update_fix: the quaternion z[3..6] is not of unit length (1e-6)"; return RVIO_ERR_INVALID; }
-    }
+    RCCHK(fix_record_check(h, kind, fix));
     RCCHK(fix_check(h));
     HIPCHK(h, hipSetDevice(h->device));
     const bool fresh = !h->fx_H;
@@ -1833,6 +1833,90 @@ int rvio_hip_update_fix(rvio_hip* h, int instance, int kind, int gate, const rvi
     HIPCHK(h, hipMemcpyAsync(h->fx_stage, h->fx_pin, fix_stage_bytes(h), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipEventRecord(h->evFix, h->stream));
     return update_fix_dev(h, kind, gate, (const rvio_fix*)h->fx_stage, 0, instance < 0 ? (const int32_t*)nullptr : (const int32_t*)(h->fx_stage + sizeof(rvio_fix)));
+}
+// what the host forms check of a record: every entry the kind uses is finite, its sigmas > 0, its quaternion of unit length
+static int fix_record_check(rvio_hip* h, int kind, const rvio_fix* fix) {
+    const bool pos = kind == RVIO_FIX_POSITION || kind == RVIO_FIX_POSE, att = kind == RVIO_FIX_ATTITUDE || kind == RVIO_FIX_POSE, vec = pos || kind == RVIO_FIX_GRAVITY;
+    auto fin = [](const double* p, int k) { for (int i = 0; i < k; ++i) if (!std::isfinite(p[i])) return false; return true; };
+    auto positive = [](const double* p, int k) { for (int i = 0; i < k; ++i) if (!(p[i] > 0)) return false; return true; };
+    if ((vec && !(fin(fix->z, 3) && fin(fix->sigma, 3))) || (att && !(fin(fix->z + 3, 4) && fin(fix->sigma + 3, 3))) || (pos && !fin(fix->lever, 3))) {
+        h->err = "rvio_hip_update_fix: an entry of z, sigma or lever that this kind uses is not finite"; return RVIO_ERR_INVALID;
+    }
+    if ((vec && !positive(fix->sigma, 3)) || (att && !positive(fix->sigma + 3, 3))) { h->err = "rvio_hip_update_fix: a sigma that this kind uses is not > 0"; return RVIO_ERR_INVALID; }
+    if (att) {
+        const double* q = fix->z + 3;
+        if (std::fabs(std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]) - 1.0) > 1e-6) { h->err = "rvio_hip_update_fix: the quaternion z[3..6] is not of unit length (1e-6)"; return RVIO_ERR_INVALID; }
+    }
+    return RVIO_OK;
+}
+
+// ---- past-frame fixes (fix_past.hip): the same consumer, the rows linearised against the pose the window holds for an earlier image
+// bytes of the host form's staging: one record; frac, age and flag per instance
+static size_t fix_past_stage_bytes(const rvio_hip* h) { return sizeof(rvio_fix) + (sizeof(double) + 2 * sizeof(int32_t)) * (size_t)h->batch; }
+static int fix_past_alloc(rvio_hip* h) {
+    RCCHK(fix_alloc(h));
+    if (h->fp_flag) return RVIO_OK;
+    if (h->dc.nmax > LP_FIXP_NMAX) { h->err = "rvio_hip_update_fix_past: the clone window is longer than the chain the kernel holds (launch_plan.h LP_FIXP_NMAX)"; return RVIO_ERR_INVALID; }
+    char *blk = nullptr, *pin = nullptr;
+    hipEvent_t ev = nullptr;
+    int rc = own_dev(h, &blk, fix_past_stage_bytes(h) + sizeof(int32_t) * (size_t)h->batch, true);
+    if (rc == RVIO_OK) rc = own_pinned(h, &pin, fix_past_stage_bytes(h));
+    if (rc == RVIO_OK) rc = own_event(h, &ev, hipEventDisableTiming);
+    if (rc != RVIO_OK) { own_release(h, blk); own_release(h, pin); return rc; }
+    h->fp_stage = blk; h->fp_flag = (int32_t*)(blk + fix_past_stage_bytes(h));
+    h->fp_pin = pin; h->evFixPast = ev;
+    return RVIO_OK;
+}
+// fix_bs: bytes between the instances' records (0: shared).  On the filter stream like update_fix_dev; the aux launch gets the kernel's own flags
+static int update_fix_past_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_bs, const int32_t* d_age, const double* d_frac, const int32_t* d_active) {
+    const int n = h->n_clones_host, m = kind == RVIO_FIX_POSE ? 6 : 3;
+    const size_t H_stride = (size_t)LP_FIX_ROWS * h->dc.dmax;
+    const LpLaunch l = fix_past_launch(h->batch);
+    hipLaunchKernelGGL(fix_past_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, n, kind, (const double*)h->x[h->cur], h->slab_bytes, d_fix, fix_bs, (const int*)d_age, d_frac,
+                       (const int*)d_active, h->composed_count, h->fx_H, H_stride * sizeof(double), h->fx_r, h->fx_sigma, h->fx_rec, h->fx_pair, (int*)h->fp_flag);
+    HIPCHK(h, hipGetLastError());
+    h->fx_kind = kind; h->fx_m = m; h->fx_d = 24 + 6 * n;
+    RCCHK(update_aux_dev(h, m, RVIO_AUX_RESIDUAL, gate, h->fx_H, H_stride, h->fx_r, 6, h->fx_sigma, 6, h->fp_flag, h->fx_pair));
+    if (paranoid_bits() & PAR_DRAIN) return drain_all(h);
+    return RVIO_OK;
+}
+int rvio_hip_update_fix_past_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_stride, const int32_t* d_age, const double* d_frac, const int32_t* d_active) {
+    if (!h || !d_fix || !d_age || kind < RVIO_FIX_POSITION || kind > RVIO_FIX_POSE || (gate != 0 && gate != 1)) return RVIO_ERR_INVALID;
+    RCCHK(fix_check(h));
+    HIPCHK(h, hipSetDevice(h->device));
+    RCCHK(fix_past_alloc(h));
+    return update_fix_past_dev(h, kind, gate, d_fix, fix_stride * sizeof(rvio_fix), d_age, d_frac, d_active);
+}
+int rvio_hip_update_fix_past(rvio_hip* h, int instance, int kind, int gate, int age, double frac, const rvio_fix* fix) {
+    if (!h || !fix || kind < RVIO_FIX_POSITION || kind > RVIO_FIX_POSE || (gate != 0 && gate != 1) || instance < -1 || instance >= h->batch) return RVIO_ERR_INVALID;
+    if (!(frac >= 0.0 && frac < 1.0) || (frac != 0.0 && kind != RVIO_FIX_POSITION)) { h->err = "rvio_hip_update_fix_past: frac is outside [0, 1), or not 0 with a kind other than POSITION"; return RVIO_ERR_INVALID; }
+    RCCHK(fix_record_check(h, kind, fix));
+    RCCHK(fix_check(h));
+    if (age < 0 || age + (frac > 0.0 ? 1 : 0) > h->n_clones_host) { h->err = "rvio_hip_update_fix_past: the age (+ 1 with frac > 0) is outside the clone window"; return RVIO_ERR_INVALID; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const bool fresh = !h->fp_flag;
+    RCCHK(fix_past_alloc(h));
+    if (!fresh) HIPCHK(h, hipEventSynchronize(h->evFixPast));
+    const size_t B = (size_t)h->batch, o_frac = sizeof(rvio_fix), o_age = o_frac + sizeof(double) * B, o_act = o_age + sizeof(int32_t) * B;
+    std::memcpy(h->fp_pin, fix, sizeof *fix);
+    double* fr = (double*)(h->fp_pin + o_frac);
+    int32_t *ag = (int32_t*)(h->fp_pin + o_age), *act = (int32_t*)(h->fp_pin + o_act);
+    for (int i = 0; i < h->batch; ++i) { fr[i] = frac; ag[i] = age; act[i] = (instance < 0 || i == instance) ? 1 : 0; }
+    HIPCHK(h, hipMemcpyAsync(h->fp_stage, h->fp_pin, fix_past_stage_bytes(h), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->evFixPast, h->stream));
+    return update_fix_past_dev(h, kind, gate, (const rvio_fix*)h->fp_stage, 0, (const int32_t*)(h->fp_stage + o_age), (const double*)(h->fp_stage + o_frac),
+                               instance < 0 ? (const int32_t*)nullptr : (const int32_t*)(h->fp_stage + o_act));
+}
+// host arithmetic only: the age of the frame counted img_count (as rvio_odom.img_count reports it) in the window as it is now
+int rvio_hip_frame_age(rvio_hip* h, int img_count, int* age) {
+    if (!h || !age) return RVIO_ERR_INVALID;
+    const int a = h->composed_count - img_count;
+    if (!h->has_state || a < 0 || a > h->n_clones_host) {
+        h->err = a < 0 ? "rvio_hip_frame_age: that frame is not composed yet" : "rvio_hip_frame_age: that frame has left the clone window";
+        return RVIO_ERR_INVALID;
+    }
+    *age = a;
+    return RVIO_OK;
 }
 // waits for the filter stream only
 int rvio_hip_get_fix(rvio_hip* h, int instance, rvio_fix_diag* out) {
@@ -1875,6 +1959,7 @@ static int augment_compose_dev(rvio_hip* h, int do_augment) {
     HIPCHK(h, hipGetLastError());
     h->cur = o;
     if (do_augment && h->n_clones_host < d.nmax) h->n_clones_host++;
+    h->composed_count = h->img_count;
     // Long windows (6n > 96, solve in its split form): Pcc = L L^T of the NEXT update is known from here on — propagation leaves the clone block
     // alone — so the factor starts now on a stream of its own and runs beside propagate, the wait for the tracker and the per-feature stage; the
     // solve's first product waits for it (launch_solve).  ~35 us at 6n = 120, ~95 us at 6n = 180 off the filter chain.

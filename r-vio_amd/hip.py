@@ -33,6 +33,7 @@ SYMBOLS = [
     "rvio_hip_predict_cov", "rvio_hip_predict_cov_dev", "rvio_hip_set_imu_odometry_cov", "rvio_hip_get_imu_odometry_cov",
     "rvio_standstill_config_default", "rvio_hip_set_standstill", "rvio_hip_standstill", "rvio_hip_standstill_dev", "rvio_hip_get_standstill",
     "rvio_hip_update_fix", "rvio_hip_update_fix_dev", "rvio_hip_get_fix", "rvio_hip_get_fix_rows",
+    "rvio_hip_update_fix_past", "rvio_hip_update_fix_past_dev", "rvio_hip_frame_age",
 ]
 
 _LIB = None
@@ -615,3 +616,23 @@ class RvioHip:
         dp = C.POINTER(C.c_double)
         self._ck(self.L.rvio_hip_get_fix_rows(self.h, int(instance), C.byref(m), C.byref(d), H.ctypes.data_as(dp), sigma.ctypes.data_as(dp)), "get_fix_rows")
         return H, sigma
+
+
+    # ---- past-frame fixes: a delayed fix linearised against the frame it was taken at (csrc/fix_past.hip in front of the auxiliary update)
+    def update_fix_past(self, kind, fix, age, frac=0.0, gate=0, instance=-1):
+        """fuse one abi.rvio_fix (host record) taken `age` images back from the newest composed frame (POSITION: frac of the way towards
+        age + 1); instance: 0 .. B - 1, or -1 = every instance.  Asynchronous."""
+        self._ck(self.L.rvio_hip_update_fix_past(self.h, int(instance), int(kind), int(gate), int(age), C.c_double(float(frac)),
+                                                 C.byref(fix) if fix is not None else None), "update_fix_past")
+
+    def update_fix_past_dev(self, kind, gate, d_fix_ptr, fix_stride, d_age_ptr, d_frac_ptr=None, d_active_ptr=None):
+        """the same on device records: d_age one int32 per instance, d_frac None (0) or one double per instance"""
+        self._ck(self.L.rvio_hip_update_fix_past_dev(self.h, int(kind), int(gate), C.c_void_p(d_fix_ptr), C.c_size_t(int(fix_stride)), C.c_void_p(d_age_ptr),
+                                                     C.c_void_p(d_frac_ptr) if d_frac_ptr else None, C.c_void_p(d_active_ptr) if d_active_ptr else None),
+                 "update_fix_past_dev")
+
+    def frame_age(self, img_count):
+        """the age the frame counted img_count has now (host arithmetic only); raises when it is not composed yet or has left the window"""
+        a = C.c_int(0)
+        self._ck(self.L.rvio_hip_frame_age(self.h, int(img_count), C.byref(a)), "frame_age")
+        return a.value
