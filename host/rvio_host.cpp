@@ -378,28 +378,30 @@ int System::update_fix(int kind, const rvio_fix& fix, bool gate) {
     if (rvio_hip_update_fix(h_, -1, kind, gate ? 1 : 0, &fix) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
     return 0;
 }
-int System::fix_position(const double p[3], const double sigma[3], const double* lever, bool gate) {
+rvio_fix position_fix(const double p[3], const double sigma[3], const double* lever) {
     rvio_fix f{};
     for (int i = 0; i < 3; ++i) { f.z[i] = p[i]; f.sigma[i] = sigma[i]; f.lever[i] = lever ? lever[i] : 0.0; }
-    return update_fix(RVIO_FIX_POSITION, f, gate);
+    return f;
 }
-int System::fix_attitude(const double q[4], const double sigma[3], bool gate) {
+rvio_fix attitude_fix(const double q[4], const double sigma[3]) {
     rvio_fix f{};
     for (int i = 0; i < 4; ++i) f.z[3 + i] = q[i];
     for (int i = 0; i < 3; ++i) f.sigma[3 + i] = sigma[i];
-    return update_fix(RVIO_FIX_ATTITUDE, f, gate);
+    return f;
 }
-int System::fix_pose(const double p[3], const double q[4], const double sigma_p[3], const double sigma_q[3], const double* lever, bool gate) {
-    rvio_fix f{};
+rvio_fix pose_fix(const double p[3], const double q[4], const double sigma_p[3], const double sigma_q[3], const double* lever) {
+    rvio_fix f = position_fix(p, sigma_p, lever);
     for (int i = 0; i < 4; ++i) f.z[3 + i] = q[i];
-    for (int i = 0; i < 3; ++i) { f.z[i] = p[i]; f.sigma[i] = sigma_p[i]; f.sigma[3 + i] = sigma_q[i]; f.lever[i] = lever ? lever[i] : 0.0; }
-    return update_fix(RVIO_FIX_POSE, f, gate);
+    for (int i = 0; i < 3; ++i) f.sigma[3 + i] = sigma_q[i];
+    return f;
 }
-int System::fix_gravity(const double a[3], const double sigma[3], bool gate) {
-    rvio_fix f{};
-    for (int i = 0; i < 3; ++i) { f.z[i] = a[i]; f.sigma[i] = sigma[i]; }
-    return update_fix(RVIO_FIX_GRAVITY, f, gate);
+rvio_fix gravity_fix(const double a[3], const double sigma[3]) { return position_fix(a, sigma, nullptr); }
+int System::fix_position(const double p[3], const double sigma[3], const double* lever, bool gate) { return update_fix(RVIO_FIX_POSITION, position_fix(p, sigma, lever), gate); }
+int System::fix_attitude(const double q[4], const double sigma[3], bool gate) { return update_fix(RVIO_FIX_ATTITUDE, attitude_fix(q, sigma), gate); }
+int System::fix_pose(const double p[3], const double q[4], const double sigma_p[3], const double sigma_q[3], const double* lever, bool gate) {
+    return update_fix(RVIO_FIX_POSE, pose_fix(p, q, sigma_p, sigma_q, lever), gate);
 }
+int System::fix_gravity(const double a[3], const double sigma[3], bool gate) { return update_fix(RVIO_FIX_GRAVITY, gravity_fix(a, sigma), gate); }
 // ---- past-frame fixes (rvio_hip_update_fix_past): a delayed fix fused at the frame it was taken
 FixAge resolve_fix_age(const std::vector<double>& stamps, double t, bool interpolate) {
     FixAge r;
@@ -427,22 +429,10 @@ int System::update_fix_at(double t, int kind, const rvio_fix& fix, bool gate) {
     if (rvio_hip_update_fix_past(h_, -1, kind, gate ? 1 : 0, w.age, w.frac, &fix) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
     return 0;
 }
-int System::fix_position_at(double t, const double p[3], const double sigma[3], const double* lever, bool gate) {
-    rvio_fix f{};
-    for (int i = 0; i < 3; ++i) { f.z[i] = p[i]; f.sigma[i] = sigma[i]; f.lever[i] = lever ? lever[i] : 0.0; }
-    return update_fix_at(t, RVIO_FIX_POSITION, f, gate);
-}
-int System::fix_attitude_at(double t, const double q[4], const double sigma[3], bool gate) {
-    rvio_fix f{};
-    for (int i = 0; i < 4; ++i) f.z[3 + i] = q[i];
-    for (int i = 0; i < 3; ++i) f.sigma[3 + i] = sigma[i];
-    return update_fix_at(t, RVIO_FIX_ATTITUDE, f, gate);
-}
+int System::fix_position_at(double t, const double p[3], const double sigma[3], const double* lever, bool gate) { return update_fix_at(t, RVIO_FIX_POSITION, position_fix(p, sigma, lever), gate); }
+int System::fix_attitude_at(double t, const double q[4], const double sigma[3], bool gate) { return update_fix_at(t, RVIO_FIX_ATTITUDE, attitude_fix(q, sigma), gate); }
 int System::fix_pose_at(double t, const double p[3], const double q[4], const double sigma_p[3], const double sigma_q[3], const double* lever, bool gate) {
-    rvio_fix f{};
-    for (int i = 0; i < 4; ++i) f.z[3 + i] = q[i];
-    for (int i = 0; i < 3; ++i) { f.z[i] = p[i]; f.sigma[i] = sigma_p[i]; f.sigma[3 + i] = sigma_q[i]; f.lever[i] = lever ? lever[i] : 0.0; }
-    return update_fix_at(t, RVIO_FIX_POSE, f, gate);
+    return update_fix_at(t, RVIO_FIX_POSE, pose_fix(p, q, sigma_p, sigma_q, lever), gate);
 }
 // behind a composed frame: its stamp joins the window's, newest first, one per frame the clone window still reaches
 void System::note_stamp(double t) {
@@ -455,24 +445,17 @@ void System::queue_fixes(std::vector<FixRow> rows, bool gate, double latency) {
     std::stable_sort(rows.begin(), rows.end(), [](const FixRow& a, const FixRow& b) { return a.t < b.t; });
     fx_rows_ = std::move(rows); fx_next_ = 0; fx_gate_ = gate; fx_latency_ = latency;
 }
-// behind the frame stamped t: every queued fix whose stamp that frame has reached, through the typed calls.  With a latency (>= 0) a fix is
-// available once the frame's stamp has reached its t + latency, and is fused at its own t (the _at calls; GRAVITY has no past form: at the frame)
+// behind the frame stamped t: every queued fix whose stamp that frame has reached, its record handed on as parse_fixes left it (the members its
+// kind does not use are 0 there, as in the typed calls' records).  With a latency (>= 0) a fix is available once the frame's stamp has reached
+// its t + latency, and is fused at its own t (update_fix_at; GRAVITY has no past form: at the frame)
 int System::apply_fixes(double t) {
     const bool late = fx_latency_ >= 0.0;
     for (; fx_next_ < fx_rows_.size() && fx_rows_[fx_next_].t + (late ? fx_latency_ : 0.0) <= t; ++fx_next_) {
-        const rvio_fix& f = fx_rows_[fx_next_].fix;
+        const FixRow& r = fx_rows_[fx_next_];
         int rc = -1;
-        if (late && fx_rows_[fx_next_].kind != RVIO_FIX_GRAVITY) {
-            if (update_fix_at(fx_rows_[fx_next_].t, fx_rows_[fx_next_].kind, f, fx_gate_) < 0) return -1;
-            continue;
-        }
-        switch (fx_rows_[fx_next_].kind) {
-            case RVIO_FIX_POSITION: rc = fix_position(f.z, f.sigma, f.lever, fx_gate_); break;
-            case RVIO_FIX_ATTITUDE: rc = fix_attitude(f.z + 3, f.sigma + 3, fx_gate_); break;
-            case RVIO_FIX_POSE: rc = fix_pose(f.z, f.z + 3, f.sigma, f.sigma + 3, f.lever, fx_gate_); break;
-            case RVIO_FIX_GRAVITY: rc = fix_gravity(f.z, f.sigma, fx_gate_); break;
-            default: err_ = "System: a queued fix of unknown kind";
-        }
+        if (late && r.kind != RVIO_FIX_GRAVITY) rc = update_fix_at(r.t, r.kind, r.fix, fx_gate_);
+        else if (r.kind < RVIO_FIX_POSITION || r.kind > RVIO_FIX_GRAVITY) err_ = "System: a queued fix of unknown kind";
+        else rc = update_fix(r.kind, r.fix, fx_gate_);
         if (rc < 0) return -1;
     }
     return 0;

@@ -95,6 +95,11 @@ struct FixRow { double t = 0; int kind = 0; rvio_fix fix{}; };
 // unit length by more than 1e-6 — is an error that names the line: "<name>:<line number>: <why>: <the line>".
 bool parse_fixes(const std::string& text, const std::string& name, std::vector<FixRow>* out, std::string* err);
 bool read_fixes(const std::string& path, std::vector<FixRow>* out, std::string* err);
+// The record of each kind, as parse_fixes fills it too: the members a kind does not use are 0; lever: nullptr for none
+rvio_fix position_fix(const double p[3], const double sigma[3], const double* lever);
+rvio_fix attitude_fix(const double q[4], const double sigma[3]);
+rvio_fix pose_fix(const double p[3], const double q[4], const double sigma_p[3], const double sigma_q[3], const double* lever);
+rvio_fix gravity_fix(const double a[3], const double sigma[3]);
 // Where a fix stamped t falls among the image stamps of the frames the clone window still reaches (newest first, stamps[a] = the frame of age a):
 // FIX_AGE_NOW: at or past the newest composed image (or no frame yet) — fuse at the current state; FIX_AGE_TOO_OLD: older than the oldest frame —
 // drop; FIX_AGE_PAST: (age, frac) for rvio_hip_update_fix_past.  interpolate (POSITION): stamps[age + 1] < t <= stamps[age], frac =

@@ -52,6 +52,9 @@ struct DevRing {
     long long seq = 0;     // records written since create / rvio_hip_initialize / the last change of capacity: the newest record's seq
     T* slot(long long s, int batch) const { return ring + ring_index(s, cap, batch); }   // the `batch` records of seq s
 };
+// The staging of one host-buffer entry point of the measurement updates: a pinned block the call packs, its device twin, and the event behind
+// the H2D copy (the next call packs once that copy has left the pinned block).  Operations: stage_acquire, stage_send
+struct HostStage { char* pin = nullptr; char* dev = nullptr; hipEvent_t ev = nullptr; };
 
 struct rvio_hip {
     rvio_config cfg;
@@ -203,10 +206,8 @@ struct rvio_hip {
     int pred_cov_cap = 0;
     bool has_state = false;    // rvio_hip_set_state* / rvio_hip_initialize* has run (rvio_hip_predict* refuses to extrapolate from nothing)
     // auxiliary measurement update (aux_update.hip), allocated by the first rvio_hip_update_aux* call, outside the slab: (gamma, applied) of the
-    // last call per instance; the host form's pinned staging [H | v | sigma | active flags], its device copy, and the event behind the H2D copy
-    double* aux_diag = nullptr;
-    double *aux_pin = nullptr, *aux_stage = nullptr;
-    hipEvent_t evAux = nullptr;
+    // last call per instance; the host form's staging [H | v | sigma | active flags]
+    struct { double* diag = nullptr; HostStage stage; } aux;
     // standstill detection (standstill.hip): the configuration of rvio_hip_set_standstill; one block allocated by the first rvio_hip_standstill*
     // call, outside the slab — records, (gamma, applied) pairs of ITS aux launches, v (6 per instance), the shared H (6 x dmax) and sigma, the
     // flags — the staging of the host-buffer form, and the two events that order the detector against the filter stream.
@@ -222,18 +223,17 @@ struct rvio_hip {
     hipEvent_t evSSa = nullptr, evSSb = nullptr;
     hipStream_t book_stream = nullptr, ss_last = nullptr;
     // absolute fixes (fix_rows.hip): one block allocated by the first rvio_hip_update_fix* call, outside the slab — the rows H (6 x dmax per
-    // instance), r and sigma (6 per instance), the records, the (gamma, applied) pairs of ITS aux launches, one staged rvio_fix and the flags of the
-    // host form — with the pinned twin of that staging and the event behind its copy.  fx_kind / fx_m / fx_d: the last call's, for the getters
-    double *fx_H = nullptr, *fx_r = nullptr, *fx_sigma = nullptr, *fx_pair = nullptr;
-    rvio_fix_diag* fx_rec = nullptr;
-    char *fx_stage = nullptr, *fx_pin = nullptr;
-    hipEvent_t evFix = nullptr;
-    int fx_kind = 0, fx_m = 0, fx_d = 0;
-    // past-frame fixes (fix_past.hip) reuse that block and add one of their own with the first rvio_hip_update_fix_past* call: the kernel's flags
-    // (one int32 per instance) and the staging of the host form (one rvio_fix; frac, age and flag per instance), with its pinned twin and event
-    int32_t* fp_flag = nullptr;
-    char *fp_stage = nullptr, *fp_pin = nullptr;
-    hipEvent_t evFixPast = nullptr;
+    // instance), r and sigma (6 per instance), the records, the (gamma, applied) pairs of ITS aux launches — and the host form's staging (one
+    // rvio_fix, one flag per instance).  kind / m / d: the last call's, for the getters
+    struct {
+        double *H = nullptr, *r = nullptr, *sigma = nullptr, *pair = nullptr;
+        rvio_fix_diag* rec = nullptr;
+        HostStage stage;
+        int kind = 0, m = 0, d = 0;
+    } fx;
+    // past-frame fixes (fix_past.hip) reuse that block and add, with the first rvio_hip_update_fix_past* call, the kernel's flags (one int32 per
+    // instance) and the host form's staging (one rvio_fix; frac, age and flag per instance)
+    struct { int32_t* flag = nullptr; HostStage stage; } fp;
     // colour input (rvio_hip_set_image_format): the gray images every stage behind gray_kernel reads instead of the caller's.  Allocated with the
     // first colour format, outside the slab (a mono handle keeps its memory layout), instance stride W * H; four in rotation like d_eq2[] (see
     // build_pyramid_dev for who reads a slot last)
@@ -1572,15 +1572,57 @@ int rvio_hip_get_imu_odometry_cov(rvio_hip* h, int instance, int64_t first_seq, 
 
 // ------------------------------------------------------------------ auxiliary measurement update (aux_update.hip)
 static_assert(LP_AUX_MAX_ROWS == RVIO_AUX_MAX_ROWS, "launch_plan.h: the row limit of the auxiliary update");
-// strides in doubles (0: shared).  Asynchronous on the filter stream: in place on x[cur] / P[cur], no toggle
-static int update_aux_dev(rvio_hip* h, int m, int mode, int gate, const double* d_H, size_t H_stride, const double* d_v, size_t v_stride,
-                          const double* d_sigma, size_t sigma_stride, const int32_t* d_active, double* d_diag = nullptr) {   // d_diag: (gamma, applied) go there instead of aux_diag (the standstill update keeps its own)
-    if (!h->has_state) { h->err = "rvio_hip_update_aux before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
-    if (h->in_frame) { h->err = "rvio_hip_update_aux between rvio_hip_frame_begin_dev and rvio_hip_frame_end"; return RVIO_ERR_STATE; }
+// ---- what the measurement updates share (this section, standstill, fixes, past-frame fixes): one way in — entry guard, host staging, active
+// flags — and one way out, the (gamma, applied) pair aux_update_kernel leaves
+// the two state errors of a public call, once per call and in front of anything it enqueues; `entry` names it in the message
+static int meas_guard(rvio_hip* h, const char* entry) {
+    if (!h->has_state) { h->err = std::string(entry) + " before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
+    if (h->in_frame) { h->err = std::string(entry) + " between rvio_hip_frame_begin_dev and rvio_hip_frame_end"; return RVIO_ERR_STATE; }
+    return RVIO_OK;
+}
+// The first use allocates the three parts (all or none: a failure half-way leaves the members null, and the next call starts over); a later
+// one waits until the previous call's copy has left the pinned block.  `bytes` is fixed per handle and entry point
+static int stage_acquire(rvio_hip* h, HostStage& s, size_t bytes) {
+    if (s.pin) { HIPCHK(h, hipEventSynchronize(s.ev)); return RVIO_OK; }
+    HostStage t;
+    int rc = own_pinned(h, &t.pin, bytes);
+    if (rc == RVIO_OK) rc = own_dev(h, &t.dev, bytes);
+    if (rc == RVIO_OK) rc = own_event(h, &t.ev, hipEventDisableTiming);
+    if (rc != RVIO_OK) { own_release(h, t.pin); own_release(h, t.dev); return rc; }
+    s = t;
+    return RVIO_OK;
+}
+// The last int32 per instance of every staged block are the active flags of the host forms' `instance`: one instance, or -1 for all of them.
+// Fills them, then copies the block on the filter stream, where it is consumed — no wait for the stream itself.  *d_active: what the launch
+// gets, the flags' device twin, or with -1 no flags at all
+static int stage_send(rvio_hip* h, const HostStage& s, size_t bytes, int instance, const int32_t** d_active) {
+    const size_t at = bytes - sizeof(int32_t) * (size_t)h->batch;
+    for (int i = 0; i < h->batch; ++i) ((int32_t*)(s.pin + at))[i] = (instance < 0 || i == instance) ? 1 : 0;
+    *d_active = instance < 0 ? nullptr : (const int32_t*)(s.dev + at);
+    HIPCHK(h, hipMemcpyAsync(s.dev, s.pin, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(s.ev, h->stream));
+    return RVIO_OK;
+}
+// (gamma, applied) of one instance as the last aux launch left them at d_pair, behind `rec_bytes` of a record copied from the same stream;
+// waits for the filter stream only, like rvio_hip_get_pose
+static int read_pair(rvio_hip* h, const double* d_pair, int instance, double* gamma, long long* applied, void* rec = nullptr, const void* d_rec = nullptr, size_t rec_bytes = 0) {
     HIPCHK(h, hipSetDevice(h->device));
+    double dg[2];
+    if (rec) HIPCHK(h, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dg, d_pair + 2 * (size_t)instance, sizeof dg, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *gamma = dg[0];
+    std::memcpy(applied, &dg[1], sizeof *applied);
+    return RVIO_OK;
+}
+
+// The bare launch, behind its caller's guard.  Strides in doubles (0: shared).  Asynchronous on the filter stream: in place on x[cur] / P[cur],
+// no toggle.  d_diag: (gamma, applied) go there instead of aux.diag (the standstill and fix updates keep their own)
+static int update_aux_dev(rvio_hip* h, int m, int mode, int gate, const double* d_H, size_t H_stride, const double* d_v, size_t v_stride,
+                          const double* d_sigma, size_t sigma_stride, const int32_t* d_active, double* d_diag = nullptr) {
     if (!d_diag) {
-        if (!h->aux_diag) RCCHK(own_dev(h, &h->aux_diag, sizeof(double) * 2 * (size_t)h->batch, true));
-        d_diag = h->aux_diag;
+        if (!h->aux.diag) RCCHK(own_dev(h, &h->aux.diag, sizeof(double) * 2 * (size_t)h->batch, true));
+        d_diag = h->aux.diag;
     }
     RCCHK(chol_drop(h, CHOL_FILTER_WAITS));   // (the update changes the covariance in place)
     const int n = h->n_clones_host;
@@ -1601,6 +1643,8 @@ int rvio_hip_update_aux_dev(rvio_hip* h, int m, int mode, int gate, const double
         return RVIO_ERR_INVALID;
     const size_t d = 24 + 6 * (size_t)h->n_clones_host;
     if ((H_stride && H_stride < (size_t)m * d) || (v_stride && v_stride < (size_t)m) || (sigma_stride && sigma_stride < (size_t)m)) return RVIO_ERR_INVALID;
+    RCCHK(meas_guard(h, "rvio_hip_update_aux"));
+    HIPCHK(h, hipSetDevice(h->device));
     return update_aux_dev(h, m, mode, gate, d_H, H_stride, d_v, v_stride, d_sigma, sigma_stride, d_active);
 }
 // host buffers: checked here, packed into the pinned block once the copy of the previous call has left it, copied and consumed on the filter
@@ -1618,39 +1662,28 @@ int rvio_hip_update_aux(rvio_hip* h, int instance, const rvio_aux_meas* meas) {
             if (meas->mode == RVIO_AUX_VALUE && rot && e != 0.0) { h->err = "rvio_hip_update_aux: VALUE mode with a non-zero entry in a rotation column of H (xi is 0 there: linearise and use RESIDUAL mode)"; return RVIO_ERR_INVALID; }
         }
     }
-    if (!h->has_state) { h->err = "rvio_hip_update_aux before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
-    if (h->in_frame) { h->err = "rvio_hip_update_aux between rvio_hip_frame_begin_dev and rvio_hip_frame_end"; return RVIO_ERR_STATE; }
+    RCCHK(meas_guard(h, "rvio_hip_update_aux"));
     HIPCHK(h, hipSetDevice(h->device));
+    // [H (MAX_ROWS x dmax) | v | sigma | one flag per instance], offsets in doubles
     const size_t nH = (size_t)RVIO_AUX_MAX_ROWS * h->dc.dmax, nd = nH + 2 * RVIO_AUX_MAX_ROWS, bytes = nd * sizeof(double) + sizeof(int32_t) * (size_t)h->batch;
-    if (!h->aux_pin) {   // (all three or none: a failure half-way leaves the members null, and the next call starts over)
-        double *pin = nullptr, *stage = nullptr;
-        hipEvent_t ev = nullptr;
-        int rc = own_pinned(h, &pin, bytes);
-        if (rc == RVIO_OK) rc = own_dev(h, &stage, bytes);
-        if (rc == RVIO_OK) rc = own_event(h, &ev, hipEventDisableTiming);
-        if (rc != RVIO_OK) { own_release(h, pin); own_release(h, stage); return rc; }
-        h->aux_pin = pin; h->aux_stage = stage; h->evAux = ev;
-    } else HIPCHK(h, hipEventSynchronize(h->evAux));
-    std::memcpy(h->aux_pin, meas->H, sizeof(double) * (size_t)m * d);
-    std::memcpy(h->aux_pin + nH, meas->v, sizeof(double) * m);
-    std::memcpy(h->aux_pin + nH + RVIO_AUX_MAX_ROWS, meas->sigma, sizeof(double) * m);
-    int32_t* act = (int32_t*)(h->aux_pin + nd);
-    for (int i = 0; i < h->batch; ++i) act[i] = (instance < 0 || i == instance) ? 1 : 0;
-    HIPCHK(h, hipMemcpyAsync(h->aux_stage, h->aux_pin, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(h->evAux, h->stream));
-    return update_aux_dev(h, m, meas->mode, meas->gate, h->aux_stage, 0, h->aux_stage + nH, 0, h->aux_stage + nH + RVIO_AUX_MAX_ROWS, 0,
-                          instance < 0 ? (const int32_t*)nullptr : (const int32_t*)(h->aux_stage + nd));
+    HostStage& s = h->aux.stage;
+    RCCHK(stage_acquire(h, s, bytes));
+    double* const pin = (double*)s.pin;
+    const double* const dev = (const double*)s.dev;
+    std::memcpy(pin, meas->H, sizeof(double) * (size_t)m * d);
+    std::memcpy(pin + nH, meas->v, sizeof(double) * m);
+    std::memcpy(pin + nH + RVIO_AUX_MAX_ROWS, meas->sigma, sizeof(double) * m);
+    const int32_t* d_active;
+    RCCHK(stage_send(h, s, bytes, instance, &d_active));
+    return update_aux_dev(h, m, meas->mode, meas->gate, dev, 0, dev + nH, 0, dev + nH + RVIO_AUX_MAX_ROWS, 0, d_active);
 }
-// (gamma, applied) of the last rvio_hip_update_aux* call; waits for the filter stream only, like rvio_hip_get_pose
+// (gamma, applied) of the last rvio_hip_update_aux* call
 int rvio_hip_get_aux_diag(rvio_hip* h, int instance, double* gamma, int32_t* applied) {
     if (!h || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
-    if (!h->aux_diag) { h->err = "rvio_hip_get_aux_diag before the first rvio_hip_update_aux"; return RVIO_ERR_STATE; }
-    HIPCHK(h, hipSetDevice(h->device));
-    double buf[2];
-    HIPCHK(h, hipMemcpyAsync(buf, h->aux_diag + 2 * (size_t)instance, sizeof buf, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    long long ap; std::memcpy(&ap, &buf[1], sizeof ap);
-    if (gamma) *gamma = buf[0];
+    if (!h->aux.diag) { h->err = "rvio_hip_get_aux_diag before the first rvio_hip_update_aux"; return RVIO_ERR_STATE; }
+    double g; long long ap;
+    RCCHK(read_pair(h, h->aux.diag, instance, &g, &ap));
+    if (gamma) *gamma = g;
     if (applied) *applied = (int32_t)ap;
     return RVIO_OK;
 }
@@ -1688,11 +1721,9 @@ int rvio_hip_set_standstill(rvio_hip* h, const rvio_standstill_config* c) {
     h->ss_on = true;
     return RVIO_OK;
 }
-static int standstill_check(rvio_hip* h) {
-    if (!h->has_state) { h->err = "rvio_hip_standstill before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
-    if (!h->ss_on) { h->err = "rvio_hip_standstill before rvio_hip_set_standstill"; return RVIO_ERR_STATE; }
-    if (h->in_frame) { h->err = "rvio_hip_standstill between rvio_hip_frame_begin_dev and rvio_hip_frame_end"; return RVIO_ERR_STATE; }
-    return RVIO_OK;
+static int standstill_check(rvio_hip* h) {   // (a handle without a state reports that first, as it always has)
+    if (h->has_state && !h->ss_on) { h->err = "rvio_hip_standstill before rvio_hip_set_standstill"; return RVIO_ERR_STATE; }
+    return meas_guard(h, "rvio_hip_standstill");
 }
 // imu_bs: bytes between the instances' samples (0: shared)
 static int standstill_dev(rvio_hip* h, const rvio_imu* d_imu, size_t imu_bs, int m, int apply) {
@@ -1759,13 +1790,9 @@ int rvio_hip_standstill(rvio_hip* h, const rvio_imu* imu, int m, int apply) {
 int rvio_hip_get_standstill(rvio_hip* h, int instance, rvio_standstill* out) {
     if (!h || !out || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
     if (!h->ss_rec) { h->err = "rvio_hip_get_standstill before the first rvio_hip_standstill"; return RVIO_ERR_STATE; }
-    HIPCHK(h, hipSetDevice(h->device));
-    double dg[2];
-    HIPCHK(h, hipMemcpyAsync(out, h->ss_rec + instance, sizeof *out, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(dg, h->ss_diag + 2 * (size_t)instance, sizeof dg, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    long long ap; std::memcpy(&ap, &dg[1], sizeof ap);
-    out->gamma = ap ? dg[0] : 0.0;
+    double g; long long ap;
+    RCCHK(read_pair(h, h->ss_diag, instance, &g, &ap, out, h->ss_rec + instance, sizeof *out));
+    out->gamma = ap ? g : 0.0;
     if (ap) out->flags |= 8;
     return RVIO_OK;
 }
@@ -1773,66 +1800,10 @@ int rvio_hip_get_standstill(rvio_hip* h, int instance, rvio_standstill* out) {
 // ------------------------------------------------------------------ absolute fixes (fix_rows.hip)
 static_assert(sizeof(rvio_fix) == 128 && sizeof(rvio_fix_diag) == 72, "include/rvio_hip.h: the fix structs have no padding");
 static_assert(LP_FIX_ROWS == 6, "launch_plan.h: the rows of a POSE fix");
-static int fix_check(rvio_hip* h) {
-    if (!h->has_state) { h->err = "rvio_hip_update_fix before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
-    if (h->in_frame) { h->err = "rvio_hip_update_fix between rvio_hip_frame_begin_dev and rvio_hip_frame_end"; return RVIO_ERR_STATE; }
-    return RVIO_OK;
-}
-// bytes of the host form's staging: one record, one flag per instance
-static size_t fix_stage_bytes(const rvio_hip* h) { return sizeof(rvio_fix) + sizeof(int32_t) * (size_t)h->batch; }
-static int fix_alloc(rvio_hip* h) {
-    if (h->fx_H) return RVIO_OK;   // (all or nothing: a failure half-way leaves the members null, and the next call starts over)
-    const size_t B = (size_t)h->batch;
-    const size_t n_H = sizeof(double) * LP_FIX_ROWS * (size_t)h->dc.dmax * B, n_r = 48 * B, n_sg = 48 * B, n_pair = 16 * B, n_rec = sizeof(rvio_fix_diag) * B;
-    char *blk = nullptr, *pin = nullptr;
-    hipEvent_t ev = nullptr;
-    int rc = own_dev(h, &blk, n_H + n_r + n_sg + n_pair + n_rec + fix_stage_bytes(h), true);   // (cleared on the filter stream, where everything that touches it runs)
-    if (rc == RVIO_OK) rc = own_pinned(h, &pin, fix_stage_bytes(h));
-    if (rc == RVIO_OK) rc = own_event(h, &ev, hipEventDisableTiming);
-    if (rc != RVIO_OK) { own_release(h, blk); own_release(h, pin); return rc; }
-    h->fx_H = (double*)blk; h->fx_r = (double*)(blk + n_H); h->fx_sigma = (double*)(blk + n_H + n_r); h->fx_pair = (double*)(blk + n_H + n_r + n_sg);
-    h->fx_rec = (rvio_fix_diag*)(blk + n_H + n_r + n_sg + n_pair); h->fx_stage = blk + n_H + n_r + n_sg + n_pair + n_rec;
-    h->fx_pin = pin; h->evFix = ev;
-    return RVIO_OK;
-}
-// fix_bs: bytes between the instances' records (0: shared).  The kernel reads x of the current buffer, which the filter stream owns: it runs on
-// that stream, no event; the aux launch behind it reads the rows in stream order
-static int update_fix_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_bs, const int32_t* d_active) {
-    const int n = h->n_clones_host, m = kind == RVIO_FIX_POSE ? 6 : 3;
-    const size_t H_stride = (size_t)LP_FIX_ROWS * h->dc.dmax;
-    const LpLaunch l = fix_launch(h->batch);
-    hipLaunchKernelGGL(fix_rows_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, n, kind, h->dc.gravity, (const double*)h->x[h->cur], h->slab_bytes, d_fix, fix_bs,
-                       (const int*)d_active, h->img_count, h->fx_H, H_stride * sizeof(double), h->fx_r, h->fx_sigma, h->fx_rec, h->fx_pair);
-    HIPCHK(h, hipGetLastError());
-    h->fx_kind = kind; h->fx_m = m; h->fx_d = 24 + 6 * n;
-    RCCHK(update_aux_dev(h, m, RVIO_AUX_RESIDUAL, gate, h->fx_H, H_stride, h->fx_r, 6, h->fx_sigma, 6, d_active, h->fx_pair));
-    if (paranoid_bits() & PAR_DRAIN) return drain_all(h);
-    return RVIO_OK;
-}
-int rvio_hip_update_fix_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_stride, const int32_t* d_active) {
-    if (!h || !d_fix || kind < RVIO_FIX_POSITION || kind > RVIO_FIX_GRAVITY || (gate != 0 && gate != 1)) return RVIO_ERR_INVALID;
-    RCCHK(fix_check(h));
-    HIPCHK(h, hipSetDevice(h->device));
-    RCCHK(fix_alloc(h));
-    return update_fix_dev(h, kind, gate, d_fix, fix_stride * sizeof(rvio_fix), d_active);
-}
-// host record: checked here, packed into the pinned block once the copy of the previous call has left it, copied and consumed on the filter stream —
-// no wait for the stream itself
-static int fix_record_check(rvio_hip* h, int kind, const rvio_fix* fix);
-int rvio_hip_update_fix(rvio_hip* h, int instance, int kind, int gate, const rvio_fix* fix) {
-    if (!h || !fix || kind < RVIO_FIX_POSITION || kind > RVIO_FIX_GRAVITY || (gate != 0 && gate != 1) || instance < -1 || instance >= h->batch) return RVIO_ERR_INVALID;
-    RCCHK(fix_record_check(h, kind, fix));
-    RCCHK(fix_check(h));
-    HIPCHK(h, hipSetDevice(h->device));
-    const bool fresh = !h->fx_H;
-    RCCHK(fix_alloc(h));
-    if (!fresh) HIPCHK(h, hipEventSynchronize(h->evFix));
-    std::memcpy(h->fx_pin, fix, sizeof *fix);
-    int32_t* act = (int32_t*)(h->fx_pin + sizeof(rvio_fix));
-    for (int i = 0; i < h->batch; ++i) act[i] = (instance < 0 || i == instance) ? 1 : 0;
-    HIPCHK(h, hipMemcpyAsync(h->fx_stage, h->fx_pin, fix_stage_bytes(h), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(h->evFix, h->stream));
-    return update_fix_dev(h, kind, gate, (const rvio_fix*)h->fx_stage, 0, instance < 0 ? (const int32_t*)nullptr : (const int32_t*)(h->fx_stage + sizeof(rvio_fix)));
+static const char kFixEntry[] = "rvio_hip_update_fix";   // the state errors of all four entry points name this one
+// what the four entry points check of their arguments (the _dev forms have no instance: -1).  kind_max: GRAVITY, or POSE for a past frame
+static bool fix_args_ok(const rvio_hip* h, const rvio_fix* fix, int kind, int kind_max, int gate, int instance = -1) {
+    return h && fix && kind >= RVIO_FIX_POSITION && kind <= kind_max && (gate == 0 || gate == 1) && instance >= -1 && instance < h->batch;
 }
 // what the host forms check of a record: every entry the kind uses is finite, its sigmas > 0, its quaternion of unit length
 static int fix_record_check(rvio_hip* h, int kind, const rvio_fix* fix) {
@@ -1849,63 +1820,94 @@ static int fix_record_check(rvio_hip* h, int kind, const rvio_fix* fix) {
     }
     return RVIO_OK;
 }
-
-// ---- past-frame fixes (fix_past.hip): the same consumer, the rows linearised against the pose the window holds for an earlier image
-// bytes of the host form's staging: one record; frac, age and flag per instance
-static size_t fix_past_stage_bytes(const rvio_hip* h) { return sizeof(rvio_fix) + (sizeof(double) + 2 * sizeof(int32_t)) * (size_t)h->batch; }
-static int fix_past_alloc(rvio_hip* h) {
-    RCCHK(fix_alloc(h));
-    if (h->fp_flag) return RVIO_OK;
+// behind the guard: the device, and on the first call the result block — rows, r, sigma, pairs, records — and, for a past frame, the kernel's
+// flags (both cleared on the filter stream, where everything that touches them runs)
+static int fix_ready(rvio_hip* h, bool past) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->fx.H) {
+        const size_t B = (size_t)h->batch;
+        const size_t n_H = sizeof(double) * LP_FIX_ROWS * (size_t)h->dc.dmax * B, n_r = 48 * B, n_sg = 48 * B, n_pair = 16 * B, n_rec = sizeof(rvio_fix_diag) * B;
+        char* blk = nullptr;
+        RCCHK(own_dev(h, &blk, n_H + n_r + n_sg + n_pair + n_rec, true));
+        h->fx.H = (double*)blk; h->fx.r = (double*)(blk + n_H); h->fx.sigma = (double*)(blk + n_H + n_r); h->fx.pair = (double*)(blk + n_H + n_r + n_sg);
+        h->fx.rec = (rvio_fix_diag*)(blk + n_H + n_r + n_sg + n_pair);
+    }
+    if (!past || h->fp.flag) return RVIO_OK;
     if (h->dc.nmax > LP_FIXP_NMAX) { h->err = "rvio_hip_update_fix_past: the clone window is longer than the chain the kernel holds (launch_plan.h LP_FIXP_NMAX)"; return RVIO_ERR_INVALID; }
-    char *blk = nullptr, *pin = nullptr;
-    hipEvent_t ev = nullptr;
-    int rc = own_dev(h, &blk, fix_past_stage_bytes(h) + sizeof(int32_t) * (size_t)h->batch, true);
-    if (rc == RVIO_OK) rc = own_pinned(h, &pin, fix_past_stage_bytes(h));
-    if (rc == RVIO_OK) rc = own_event(h, &ev, hipEventDisableTiming);
-    if (rc != RVIO_OK) { own_release(h, blk); own_release(h, pin); return rc; }
-    h->fp_stage = blk; h->fp_flag = (int32_t*)(blk + fix_past_stage_bytes(h));
-    h->fp_pin = pin; h->evFixPast = ev;
-    return RVIO_OK;
+    return own_dev(h, &h->fp.flag, sizeof(int32_t) * (size_t)h->batch, true);
 }
-// fix_bs: bytes between the instances' records (0: shared).  On the filter stream like update_fix_dev; the aux launch gets the kernel's own flags
-static int update_fix_past_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_bs, const int32_t* d_age, const double* d_frac, const int32_t* d_active) {
-    const int n = h->n_clones_host, m = kind == RVIO_FIX_POSE ? 6 : 3;
-    const size_t H_stride = (size_t)LP_FIX_ROWS * h->dc.dmax;
-    const LpLaunch l = fix_past_launch(h->batch);
-    hipLaunchKernelGGL(fix_past_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, n, kind, (const double*)h->x[h->cur], h->slab_bytes, d_fix, fix_bs, (const int*)d_age, d_frac,
-                       (const int*)d_active, h->composed_count, h->fx_H, H_stride * sizeof(double), h->fx_r, h->fx_sigma, h->fx_rec, h->fx_pair, (int*)h->fp_flag);
+static size_t fix_H_stride(const rvio_hip* h) { return (size_t)LP_FIX_ROWS * h->dc.dmax; }   // doubles between the instances' rows
+// What the two producers share behind their own launch: kind, m and d for the getters, the RESIDUAL aux launch on the rows they left — it reads
+// them in stream order and acts where d_flags says — and the drain
+static int fix_consume(rvio_hip* h, int kind, int gate, const int32_t* d_flags) {
     HIPCHK(h, hipGetLastError());
-    h->fx_kind = kind; h->fx_m = m; h->fx_d = 24 + 6 * n;
-    RCCHK(update_aux_dev(h, m, RVIO_AUX_RESIDUAL, gate, h->fx_H, H_stride, h->fx_r, 6, h->fx_sigma, 6, h->fp_flag, h->fx_pair));
+    const int m = kind == RVIO_FIX_POSE ? 6 : 3;
+    h->fx.kind = kind; h->fx.m = m; h->fx.d = 24 + 6 * h->n_clones_host;
+    RCCHK(update_aux_dev(h, m, RVIO_AUX_RESIDUAL, gate, h->fx.H, fix_H_stride(h), h->fx.r, 6, h->fx.sigma, 6, d_flags, h->fx.pair));
     if (paranoid_bits() & PAR_DRAIN) return drain_all(h);
     return RVIO_OK;
 }
+// fix_bs: bytes between the instances' records (0: shared).  The kernel reads x of the current buffer, which the filter stream owns: it runs on
+// that stream, no event
+static int update_fix_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_bs, const int32_t* d_active) {
+    const LpLaunch l = fix_launch(h->batch);
+    hipLaunchKernelGGL(fix_rows_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->n_clones_host, kind, h->dc.gravity, (const double*)h->x[h->cur], h->slab_bytes, d_fix, fix_bs,
+                       (const int*)d_active, h->img_count, h->fx.H, fix_H_stride(h) * sizeof(double), h->fx.r, h->fx.sigma, h->fx.rec, h->fx.pair);
+    return fix_consume(h, kind, gate, d_active);
+}
+int rvio_hip_update_fix_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_stride, const int32_t* d_active) {
+    if (!fix_args_ok(h, d_fix, kind, RVIO_FIX_GRAVITY, gate)) return RVIO_ERR_INVALID;
+    RCCHK(meas_guard(h, kFixEntry));
+    RCCHK(fix_ready(h, false));
+    return update_fix_dev(h, kind, gate, d_fix, fix_stride * sizeof(rvio_fix), d_active);
+}
+// host record: checked here, packed into the pinned block once the copy of the previous call has left it: [one record | one flag per instance]
+int rvio_hip_update_fix(rvio_hip* h, int instance, int kind, int gate, const rvio_fix* fix) {
+    if (!fix_args_ok(h, fix, kind, RVIO_FIX_GRAVITY, gate, instance)) return RVIO_ERR_INVALID;
+    RCCHK(fix_record_check(h, kind, fix));
+    RCCHK(meas_guard(h, kFixEntry));
+    RCCHK(fix_ready(h, false));
+    HostStage& s = h->fx.stage;
+    const size_t bytes = sizeof(rvio_fix) + sizeof(int32_t) * (size_t)h->batch;
+    RCCHK(stage_acquire(h, s, bytes));
+    std::memcpy(s.pin, fix, sizeof *fix);
+    const int32_t* d_active;
+    RCCHK(stage_send(h, s, bytes, instance, &d_active));
+    return update_fix_dev(h, kind, gate, (const rvio_fix*)s.dev, 0, d_active);
+}
+
+// ---- past-frame fixes (fix_past.hip): the same consumer, the rows linearised against the pose the window holds for an earlier image
+// fix_bs: bytes between the instances' records (0: shared).  On the filter stream like update_fix_dev; the aux launch gets the kernel's own flags
+static int update_fix_past_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_bs, const int32_t* d_age, const double* d_frac, const int32_t* d_active) {
+    const LpLaunch l = fix_past_launch(h->batch);
+    hipLaunchKernelGGL(fix_past_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->n_clones_host, kind, (const double*)h->x[h->cur], h->slab_bytes, d_fix, fix_bs, (const int*)d_age, d_frac,
+                       (const int*)d_active, h->composed_count, h->fx.H, fix_H_stride(h) * sizeof(double), h->fx.r, h->fx.sigma, h->fx.rec, h->fx.pair, (int*)h->fp.flag);
+    return fix_consume(h, kind, gate, h->fp.flag);
+}
 int rvio_hip_update_fix_past_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_stride, const int32_t* d_age, const double* d_frac, const int32_t* d_active) {
-    if (!h || !d_fix || !d_age || kind < RVIO_FIX_POSITION || kind > RVIO_FIX_POSE || (gate != 0 && gate != 1)) return RVIO_ERR_INVALID;
-    RCCHK(fix_check(h));
-    HIPCHK(h, hipSetDevice(h->device));
-    RCCHK(fix_past_alloc(h));
+    if (!fix_args_ok(h, d_fix, kind, RVIO_FIX_POSE, gate) || !d_age) return RVIO_ERR_INVALID;
+    RCCHK(meas_guard(h, kFixEntry));
+    RCCHK(fix_ready(h, true));
     return update_fix_past_dev(h, kind, gate, d_fix, fix_stride * sizeof(rvio_fix), d_age, d_frac, d_active);
 }
+// host record, staged like rvio_hip_update_fix's: [one record | frac | age | flag, each per instance]
 int rvio_hip_update_fix_past(rvio_hip* h, int instance, int kind, int gate, int age, double frac, const rvio_fix* fix) {
-    if (!h || !fix || kind < RVIO_FIX_POSITION || kind > RVIO_FIX_POSE || (gate != 0 && gate != 1) || instance < -1 || instance >= h->batch) return RVIO_ERR_INVALID;
+    if (!fix_args_ok(h, fix, kind, RVIO_FIX_POSE, gate, instance)) return RVIO_ERR_INVALID;
     if (!(frac >= 0.0 && frac < 1.0) || (frac != 0.0 && kind != RVIO_FIX_POSITION)) { h->err = "rvio_hip_update_fix_past: frac is outside [0, 1), or not 0 with a kind other than POSITION"; return RVIO_ERR_INVALID; }
     RCCHK(fix_record_check(h, kind, fix));
-    RCCHK(fix_check(h));
+    RCCHK(meas_guard(h, kFixEntry));
     if (age < 0 || age + (frac > 0.0 ? 1 : 0) > h->n_clones_host) { h->err = "rvio_hip_update_fix_past: the age (+ 1 with frac > 0) is outside the clone window"; return RVIO_ERR_INVALID; }
-    HIPCHK(h, hipSetDevice(h->device));
-    const bool fresh = !h->fp_flag;
-    RCCHK(fix_past_alloc(h));
-    if (!fresh) HIPCHK(h, hipEventSynchronize(h->evFixPast));
-    const size_t B = (size_t)h->batch, o_frac = sizeof(rvio_fix), o_age = o_frac + sizeof(double) * B, o_act = o_age + sizeof(int32_t) * B;
-    std::memcpy(h->fp_pin, fix, sizeof *fix);
-    double* fr = (double*)(h->fp_pin + o_frac);
-    int32_t *ag = (int32_t*)(h->fp_pin + o_age), *act = (int32_t*)(h->fp_pin + o_act);
-    for (int i = 0; i < h->batch; ++i) { fr[i] = frac; ag[i] = age; act[i] = (instance < 0 || i == instance) ? 1 : 0; }
-    HIPCHK(h, hipMemcpyAsync(h->fp_stage, h->fp_pin, fix_past_stage_bytes(h), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(h->evFixPast, h->stream));
-    return update_fix_past_dev(h, kind, gate, (const rvio_fix*)h->fp_stage, 0, (const int32_t*)(h->fp_stage + o_age), (const double*)(h->fp_stage + o_frac),
-                               instance < 0 ? (const int32_t*)nullptr : (const int32_t*)(h->fp_stage + o_act));
+    RCCHK(fix_ready(h, true));
+    HostStage& s = h->fp.stage;
+    const size_t B = (size_t)h->batch, o_frac = sizeof(rvio_fix), o_age = o_frac + sizeof(double) * B, bytes = o_age + 2 * sizeof(int32_t) * B;
+    RCCHK(stage_acquire(h, s, bytes));
+    std::memcpy(s.pin, fix, sizeof *fix);
+    double* fr = (double*)(s.pin + o_frac);
+    int32_t* ag = (int32_t*)(s.pin + o_age);
+    for (int i = 0; i < h->batch; ++i) { fr[i] = frac; ag[i] = age; }
+    const int32_t* d_active;
+    RCCHK(stage_send(h, s, bytes, instance, &d_active));
+    return update_fix_past_dev(h, kind, gate, (const rvio_fix*)s.dev, 0, (const int32_t*)(s.dev + o_age), (const double*)(s.dev + o_frac), d_active);
 }
 // host arithmetic only: the age of the frame counted img_count (as rvio_odom.img_count reports it) in the window as it is now
 int rvio_hip_frame_age(rvio_hip* h, int img_count, int* age) {
@@ -1921,24 +1923,20 @@ int rvio_hip_frame_age(rvio_hip* h, int img_count, int* age) {
 // waits for the filter stream only
 int rvio_hip_get_fix(rvio_hip* h, int instance, rvio_fix_diag* out) {
     if (!h || !out || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
-    if (!h->fx_m) { h->err = "rvio_hip_get_fix before the first rvio_hip_update_fix"; return RVIO_ERR_STATE; }
-    HIPCHK(h, hipSetDevice(h->device));
-    double dg[2];
-    HIPCHK(h, hipMemcpyAsync(out, h->fx_rec + instance, sizeof *out, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(dg, h->fx_pair + 2 * (size_t)instance, sizeof dg, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    long long ap; std::memcpy(&ap, &dg[1], sizeof ap);
-    out->gamma = dg[0];   // (as compared, also when the gate refused it: by how much is what a caller wants to know then)
+    if (!h->fx.m) { h->err = "rvio_hip_get_fix before the first rvio_hip_update_fix"; return RVIO_ERR_STATE; }
+    double g; long long ap;
+    RCCHK(read_pair(h, h->fx.pair, instance, &g, &ap, out, h->fx.rec + instance, sizeof *out));
+    out->gamma = g;   // (as compared, also when the gate refused it: by how much is what a caller wants to know then)
     out->applied = ap ? 1 : 0;
     return RVIO_OK;
 }
 int rvio_hip_get_fix_rows(rvio_hip* h, int instance, int32_t* m, int32_t* d, double* H, double* sigma) {
     if (!h || !m || !d || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
-    if (!h->fx_m) { h->err = "rvio_hip_get_fix_rows before the first rvio_hip_update_fix"; return RVIO_ERR_STATE; }
+    if (!h->fx.m) { h->err = "rvio_hip_get_fix_rows before the first rvio_hip_update_fix"; return RVIO_ERR_STATE; }
     HIPCHK(h, hipSetDevice(h->device));
-    *m = h->fx_m; *d = h->fx_d;
-    if (H) HIPCHK(h, hipMemcpyAsync(H, h->fx_H + (size_t)instance * LP_FIX_ROWS * h->dc.dmax, sizeof(double) * (size_t)h->fx_m * h->fx_d, hipMemcpyDeviceToHost, h->stream));
-    if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, h->fx_sigma + 6 * (size_t)instance, sizeof(double) * (size_t)h->fx_m, hipMemcpyDeviceToHost, h->stream));
+    *m = h->fx.m; *d = h->fx.d;
+    if (H) HIPCHK(h, hipMemcpyAsync(H, h->fx.H + (size_t)instance * fix_H_stride(h), sizeof(double) * (size_t)h->fx.m * h->fx.d, hipMemcpyDeviceToHost, h->stream));
+    if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, h->fx.sigma + 6 * (size_t)instance, sizeof(double) * (size_t)h->fx.m, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RVIO_OK;
 }

@@ -4,26 +4,16 @@ the kernel's static LDS — read from the built library's gfx950 code object —
 when it was created, and the T product's deal of row groups x column ranges fits the workgroup's eight waves."""
 import ctypes as C
 import os
-import re
-import shutil
 import subprocess
-import tempfile
 
 import pytest
+
+from code_object import read_static_lds
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "hostemu", "aux_plan_emu.cpp")
 HDR = os.path.join(ROOT, "r-vio_amd", "csrc", "launch_plan.h")
-LIB = os.path.join(ROOT, "r-vio_amd", "librvio_hip.so")
 LIMIT = 163840
-
-
-def _tool(name):
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    for p in (os.path.join(rocm, "llvm", "bin", name), os.path.join(rocm, "lib", "llvm", "bin", name), shutil.which(name) or ""):
-        if p and os.path.exists(p):
-            return p
-    pytest.fail("%s not found (ROCm's LLVM tools are needed to read the built library's code object)" % name)
 
 
 @pytest.fixture(scope="module")
@@ -40,23 +30,7 @@ def emu(tmp_path_factory):
 @pytest.fixture(scope="module")
 def static_lds():
     """{kernel name as c++filt prints it: static LDS in bytes} of the built library's gfx950 code object (as tests/test_launch_plan.py reads it)"""
-    if not os.path.exists(LIB):
-        pytest.fail("r-vio_amd/librvio_hip.so has not been built: run __graft_entry__.build() first")
-    with tempfile.TemporaryDirectory() as t:
-        fat, co = os.path.join(t, "fat.bin"), os.path.join(t, "gfx950.co")
-        subprocess.check_call([_tool("llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", LIB, fat])
-        subprocess.check_call([_tool("clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat, "--output=" + co,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"])
-        notes = subprocess.run([_tool("llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
-    out = {}
-    for blk in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
-        name = re.search(r"\n\s*\.name:\s+(\S+)", blk)
-        lds = re.search(r"\n\s*\.group_segment_fixed_size:\s+(\d+)", blk)
-        assert name and lds, blk[:400]
-        out[name.group(1)] = int(lds.group(1))
-    dem = subprocess.run([shutil.which("c++filt") or _tool("llvm-cxxfilt")], input="\n".join(out), capture_output=True, text=True, check=True).stdout.splitlines()
-    assert len(dem) == len(out)
-    return {re.sub(r"\(.*", "", re.sub(r"^void ", "", d)): v for d, v in zip(dem, out.values())}
+    return read_static_lds()
 
 
 def launch(emu, n, m, batch):

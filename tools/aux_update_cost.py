@@ -16,6 +16,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from _timing import timed  # noqa: E402
 
 
 def main():
@@ -45,17 +46,7 @@ def main():
                 dv = torch.from_numpy(1e-3 * rng.standard_normal(m)).cuda()
                 ds = torch.ones(m, dtype=torch.float64).cuda()
                 torch.cuda.synchronize()
-                h.set_state(x, P)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                for _ in range(a.warmup):
-                    h.update_aux_dev(m, abi.RVIO_AUX_RESIDUAL, 0, dH.data_ptr(), 0, dv.data_ptr(), 0, ds.data_ptr(), 0)
-                h.set_state(x, P)
-                e0.record(st)
-                for _ in range(a.launches):
-                    h.update_aux_dev(m, abi.RVIO_AUX_RESIDUAL, 0, dH.data_ptr(), 0, dv.data_ptr(), 0, ds.data_ptr(), 0)
-                e1.record(st)
-                h.sync()
-                us = 1e3 * e0.elapsed_time(e1) / a.launches
+                us = timed(h, st, x, P, lambda: h.update_aux_dev(m, abi.RVIO_AUX_RESIDUAL, 0, dH.data_ptr(), 0, dv.data_ptr(), 0, ds.data_ptr(), 0), a.warmup, a.launches)
                 gam, applied = h.aux_diag(B - 1)
                 Pn = h.get_state_at(B - 1)[1]
                 print(json.dumps(dict(clones=n, d=d, m=m, batch=B, us_per_launch=round(us, 2), us_per_instance=round(us / B, 3), applied=applied,

@@ -17,6 +17,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from _timing import timed  # noqa: E402
 
 
 def main():
@@ -39,19 +40,6 @@ def main():
             st = torch.cuda.ExternalStream(h.stream())
             d_off = torch.zeros(B, dtype=torch.int32).cuda()
             torch.cuda.synchronize()
-
-            def timed(call):
-                h.set_state(x, P)
-                for _ in range(a.warmup):
-                    call()
-                h.set_state(x, P)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(st)
-                for _ in range(a.launches):
-                    call()
-                e1.record(st)
-                h.sync()
-                return 1e3 * e0.elapsed_time(e1) / a.launches
             for kind, name in ((abi.RVIO_FIX_POSITION, "position_m3"), (abi.RVIO_FIX_POSE, "pose_m6")):
                 # (a wide sigma: 220 updates in a row must leave a covariance the next one can still factor)
                 fix = F.fix_near(cfg, x, kind, F.LEVER, sigma_p=1.0, sigma_q=0.5)
@@ -67,7 +55,7 @@ def main():
                          ("fix_with_update", lambda: h.update_fix_dev(kind, 0, d_fix.data_ptr(), 0, None)))
                 for rep in range(2):          # (twice, alternating: the spread)
                     for case, call in cases:
-                        us = timed(call)
+                        us = timed(h, st, x, P, call, a.warmup, a.launches)
                         applied = int(h.get_fix(B - 1).applied) if case.startswith("fix") else None
                         print(json.dumps(dict(case=case, fix=name, rep=rep, batch=B, clones=n, us_per_call=round(us, 2), us_per_instance=round(us / B, 3),
                                               applied=applied)), flush=True)

@@ -16,6 +16,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from _timing import timed  # noqa: E402
 
 
 def main():
@@ -38,19 +39,6 @@ def main():
         for B in (1, a.batch):
             h = hip.RvioHip(cfg) if B == 1 else hip.RvioHip(cfg, batch=B, front_end=False)
             st = torch.cuda.ExternalStream(h.stream())
-
-            def timed(call):
-                h.set_state(x, P)
-                for _ in range(a.warmup):
-                    call()
-                h.set_state(x, P)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(st)
-                for _ in range(a.launches):
-                    call()
-                e1.record(st)
-                h.sync()
-                return 1e3 * e0.elapsed_time(e1) / a.launches
             # (a wide sigma: 220 updates in a row must leave a covariance the next one can still factor)
             now = F.fix_near(cfg, x, kind, F.LEVER, sigma_p=1.0)
             d_now = torch.from_numpy(np.frombuffer(bytes(now), np.uint8).copy()).cuda()
@@ -65,7 +53,7 @@ def main():
             torch.cuda.synchronize()
             for rep in range(2):          # (twice, alternating: the spread)
                 for case, age, call in cases:
-                    us = timed(call)
+                    us = timed(h, st, x, P, call, a.warmup, a.launches)
                     print(json.dumps(dict(case=case, age=age, rep=rep, batch=B, clones=n, us_per_call=round(us, 2), us_per_instance=round(us / B, 3),
                                           applied=int(h.get_fix(B - 1).applied))), flush=True)
             assert h.frame_info()["device_error"] == 0

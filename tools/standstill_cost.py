@@ -17,6 +17,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from _timing import timed  # noqa: E402
 
 
 def main():
@@ -45,25 +46,12 @@ def main():
         H, z, sigma = abi.standstill_measurement(d, np.zeros(3), c)
         dH, dv, ds = (torch.from_numpy(np.ascontiguousarray(v)).cuda() for v in (H, z, sigma))
         torch.cuda.synchronize()
-
-        def timed(call):
-            h.set_state(x, P)
-            for _ in range(a.warmup):
-                call()
-            h.set_state(x, P)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(st)
-            for _ in range(a.launches):
-                call()
-            e1.record(st)
-            h.sync()
-            return 1e3 * e0.elapsed_time(e1) / a.launches
         cases = (("aux_update_m3", lambda: h.update_aux_dev(3, abi.RVIO_AUX_VALUE, 0, dH.data_ptr(), 0, dv.data_ptr(), 0, ds.data_ptr(), 0)),
                  ("standstill_detect_only", lambda: h.standstill_dev(d_imu.data_ptr(), 0, m, 0)),
                  ("standstill_apply", lambda: h.standstill_dev(d_imu.data_ptr(), 0, m, 1)))
         for rep in range(2):          # (twice, alternating: the spread)
             for name, call in cases:
-                us = timed(call)
+                us = timed(h, st, x, P, call, a.warmup, a.launches)
                 flags = int(h.get_standstill(B - 1).flags) if name.startswith("standstill") else None
                 print(json.dumps(dict(case=name, rep=rep, batch=B, clones=n, imu_samples=m, us_per_call=round(us, 2), us_per_instance=round(us / B, 3),
                                       flags=flags)), flush=True)
