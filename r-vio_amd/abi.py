@@ -187,19 +187,18 @@ def rot_to_quat(R):
     return _quat_norm_pos(q)
 
 
-def imu_pose_model(cfg, x, imu):
-    """NumPy model of csrc/imu_pose.hip: the records (abi.IMU_POSE_DTYPE; seq = 0, img_count = 0) of the IMU batch `imu` (abi.IMU_DTYPE) from
-    the state head x[0:26].  Sample loop of PreIntegrator::propagate (PreIntegrator.cc:97-179) on the states alone, then the pose line
-    (System.cc:339-341) behind every sample.  Calls nothing from the library or the oracle: a third implementation."""
+def imu_preint_steps(cfg, x, imu):
+    """The state half of PreIntegrator::propagate's sample loop (PreIntegrator.cc:97-179; csrc/imu_preint.h on the device) from the state head
+    x[0:26], one step per sample of `imu` (abi.IMU_DTYPE).  Yields (j, u, dt, w, a, front, behind): the bias-free rate and acceleration, and
+    (Rk, pk, vk, gk) in front of and behind step j.  The one statement of the recursion in this module: imu_pose_model and imu_cov_model walk it."""
     x = np.asarray(x, float)
-    qG, pG, gR, vR, bg, ba = x[0:4], x[4:7], x[7:10].copy(), x[17:20].copy(), x[20:23], x[23:26]
-    Rk = quat_to_rot(x[10:14])
-    RG = quat_to_rot(qG)
+    gR, vR, bg, ba = x[7:10].copy(), x[17:20].copy(), x[20:23], x[23:26]
+    Rk, pk, vk, gk = quat_to_rot(x[10:14]), x[14:17].copy(), vR.copy(), gR.copy()
     dp, dv, Dt = np.zeros(3), np.zeros(3), 0.0
     I = np.eye(3)
     g = float(cfg.gravity)
-    out = np.zeros(len(imu), IMU_POSE_DTYPE)
     for j, u in enumerate(imu):
+        front = (Rk, pk, vk, gk)
         dt = float(u["dt"])
         Dt += dt
         w, a = u["w"] - bg, u["a"] - ba
@@ -223,6 +222,20 @@ def imu_pose_model(cfg, x, imu):
         dv = dv + Rk.T @ ((dt * I + f3 * wx + f4 * wx2) @ a)
         pk = vR * Dt - .5 * g * gR * Dt ** 2 + dp
         vk = Rk @ (vR - g * gR * Dt + dv)
+        gk = Rk @ gR
+        gk = gk / math.sqrt(float(gk @ gk))
+        yield j, u, dt, w, a, front, (Rk, pk, vk, gk)
+
+
+def imu_pose_model(cfg, x, imu):
+    """NumPy model of csrc/imu_pose.hip: the records (abi.IMU_POSE_DTYPE; seq = 0, img_count = 0) of the IMU batch `imu` (abi.IMU_DTYPE) from
+    the state head x[0:26].  imu_preint_steps on the states alone, then the pose line (System.cc:339-341) behind every sample.  Calls nothing
+    from the library or the oracle: a third implementation."""
+    x = np.asarray(x, float)
+    qG, pG = x[0:4], x[4:7]
+    RG = quat_to_rot(qG)
+    out = np.zeros(len(imu), IMU_POSE_DTYPE)
+    for j, u, dt, w, a, front, (Rk, pk, vk, gk) in imu_preint_steps(cfg, x, imu):
         r = out[j]
         r["index"], r["t"] = j, u["t"]
         r["p"] = RG.T @ (pk - pG)
@@ -256,22 +269,18 @@ def imu_pose_cov_jacobian(qG, pG, qk, pk):
 
 def imu_cov_model(cfg, x, P24, imu):
     """NumPy model of csrc/imu_cov.hip: the records (abi.IMU_COV_DTYPE; seq = 0, img_count = 0) of the IMU batch `imu` from the state head x[0:26]
-    and the 24 x 24 head of P.  The covariance half of PreIntegrator::propagate's sample loop (PreIntegrator.cc:123-142) beside the state half,
-    then per sample composition's Vk and the odometry record's map.  Calls nothing from the library or the oracle."""
+    and the 24 x 24 head of P.  The covariance half of PreIntegrator::propagate's sample loop (PreIntegrator.cc:123-142) at the state
+    imu_preint_steps has in front of every step, then per sample composition's Vk and the odometry record's map at the state behind it.  Calls
+    nothing from the library or the oracle."""
     x = np.asarray(x, float)
     P = np.array(np.asarray(P24, float)[:24, :24])
-    qG, pG, gR, vR, bg, ba = x[0:4], x[4:7], x[7:10].copy(), x[17:20].copy(), x[20:23], x[23:26]
-    Rk, vk, gk = quat_to_rot(x[10:14]), vR.copy(), gR.copy()
-    dp, dv, Dt = np.zeros(3), np.zeros(3), 0.0
+    qG, pG = x[0:4], x[4:7]
     I = np.eye(3)
     g = float(cfg.gravity)
     Sig = np.diag(np.repeat([cfg.sigma_g ** 2, cfg.sigma_wg ** 2, cfg.sigma_a ** 2, cfg.sigma_wa ** 2], 3))
     cols = list(IMU_COV_COLS)
     out = np.zeros(len(imu), IMU_COV_DTYPE)
-    for j, u in enumerate(imu):
-        dt = float(u["dt"])
-        Dt += dt
-        w, a = u["w"] - bg, u["a"] - ba
+    for j, u, dt, w, a, (Rk, pk, vk, gk), behind in imu_preint_steps(cfg, x, imu):
         wx, vx = _skew(w), _skew(vk)
         F, G = np.zeros((24, 24)), np.zeros((24, 12))
         F[9:12, 9:12], F[9:12, 18:21] = -wx, -I
@@ -280,30 +289,8 @@ def imu_cov_model(cfg, x, P24, imu):
         G[9:12, 0:3], G[15:18, 0:3], G[15:18, 6:9], G[18:21, 3:6], G[21:24, 9:12] = -I, -vx, -I, I, I
         Phi = np.eye(24) + dt * F
         P = Phi @ P @ Phi.T + (dt * G) @ Sig @ G.T
-        # the state half, as imu_pose_model has it
-        w1 = math.sqrt(float(w @ w))
-        wdt = w1 * dt
-        wx2 = wx @ wx
-        if w1 < cfg.small_angle:
-            dR = I - dt * wx + (dt ** 2 / 2) * wx2
-            f1, f2, f3, f4 = -dt ** 3 / 3, dt ** 4 / 8, -dt ** 2 / 2, dt ** 3 / 6
-        else:
-            c, s = math.cos(wdt), math.sin(wdt)
-            dR = I - (s / w1) * wx + ((1 - c) / w1 ** 2) * wx2
-            f1 = (wdt * c - s) / w1 ** 3
-            f2 = .5 * (wdt * wdt - 2 * c - 2 * wdt * s + 2) / w1 ** 4
-            f3 = (c - 1) / w1 ** 2
-            f4 = (wdt - s) / w1 ** 3
-        Rk = dR @ Rk
-        dp = dp + dv * dt
-        dp = dp + Rk.T @ ((.5 * dt ** 2 * I + f1 * wx + f2 * wx2) @ a)
-        dv = dv + Rk.T @ ((dt * I + f3 * wx + f4 * wx2) @ a)
-        pk = vR * Dt - .5 * g * gR * Dt ** 2 + dp
-        vk = Rk @ (vR - g * gR * Dt + dv)
-        gk = Rk @ gR
-        gk = gk / math.sqrt(float(gk @ gk))
         # the record behind sample j
-        M = imu_pose_cov_jacobian(qG, pG, rot_to_quat(Rk), pk)
+        M = imu_pose_cov_jacobian(qG, pG, rot_to_quat(behind[0]), behind[1])
         Cm = M @ P[np.ix_(cols, cols)] @ M.T
         r = out[j]
         r["index"] = j

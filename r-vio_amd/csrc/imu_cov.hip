@@ -14,9 +14,8 @@
 //
 // Geometry (launch_plan.h LP_IMUC_*): one wave per instance, one instance per 64-thread workgroup, no block-wide barrier.  Per chunk of up to
 // LP_IMUC_CHUNK samples the wave runs
-//   A  lane s <-> sample s: trig, dR, the two a-dependent vectors — imu_pose_kernel's phase A
-//   B  the serial STATE chain, every lane redundantly: Rk <- dR Rk, dp, dv, Dt — imu_pose_kernel's phase B.  Step s leaves (Rk, dp, dv, Dt)
-//      behind it in its sample's slot
+//   A  lane s <-> sample s: imu_sample_terms (imu_preint.h) into words 0..15 of the sample's slot
+//   B  the serial STATE chain, every lane redundantly (imu_chain_chunk).  Step s leaves (Rk, dp, dv, Dt) behind it in those words
 //   C  lane s <-> sample s: (Rk, vk, gk) in front of the step (slot s - 1; the chunk's first sample: carried in registers, at s = 0 the raw
 //      x[10..13], x[17..19], x[7..9]) -> the six distinct non-zero 3 x 3 blocks of dt F_s, dt, and the block of Q_s in rows / columns 9..17, into the
 //      slot; (Rk_s, pk_s) behind the step stay in the lane's registers for phase E
@@ -30,31 +29,21 @@
 //      leaves, which is the only kind the handle holds.)
 //   E  lane s <-> record s: Vk and J as 3 x 3 blocks (30 block products; register arrays under compile-time indices only, the rule at the head of
 //      filter_kernels2.hip), C_ij and C_ji formed separately and added in either order — the same two numbers, hence the same bits.
-// LDS per wave: 169 words x LP_IMUC_CHUNK samples, word-major like imu_pose_kernel's (lane-indexed accesses are consecutive 8-byte words, the
-// chains' reads of one sample's words are wave-uniform broadcasts), + the nine rows of T (216).  The phases of one wave are ordered by program
-// order of its LDS operations; the fences keep the compiler from moving them across a phase boundary.
+// LDS per wave: 169 words x LP_IMUC_CHUNK samples — imu_preint.h's 16-word slot at stride LP_IMUC_CHUNK, and this kernel's own words behind
+// it in the same word-major layout —, + the nine rows of T (216).  The phases of one wave are ordered by imu_wave_fence.
+#pragma once
+#include "imu_preint.h"
 #define IMUC_WORDS 47   // sizeof(rvio_imu_cov) / 8
-#define IMUC_SLOT(W, k, s) (W)[(k) * LP_IMUC_CHUNK + (s)]
+#define IMUC_SLOT(W, k, s) (W)[(k) * LP_IMUC_CHUNK + (s)]   // this kernel's words of sample s, k >= IMUC_PHI
 #define IMUC_PHI 16                  // dt F's blocks, row-major 3 x 3 each: A1 = -dt [w x], B1 = -dt Rk^T [v x], B2 = dt Rk^T, C1 = -dt g Rk, C2 = -dt g [gk x], C3 = -dt [v x]
 #define IMUC_DT (IMUC_PHI + 54)
 #define IMUC_Q (IMUC_PHI + 55)       // 9 x 9, row-major: Q rows / columns 9..17
 #define IMUC_OUT IMUC_PHI            // behind the step: 144 words of the 12 x 12 block, row-major, + 9 of the velocity block
 static_assert(IMUC_Q + 81 <= LP_IMUC_SLOT_WORDS && IMUC_OUT + 153 == LP_IMUC_SLOT_WORDS, "launch_plan.h: imu_cov_kernel's slot");
-#define IMUC_FENCE() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
-struct ImucState { m33 R; d3 p, v, g; };
-// the state behind the step whose (Rk, dp, dv, Dt) lie in slot s: pk, vk by imu_pose_kernel's expressions, gk re-normalised (PreIntegrator.cc:177)
-__device__ __forceinline__ ImucState imuc_state(const double* W, int s, d3 vR, d3 gR, double nG) {
-    ImucState o;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) o.R.m[k] = IMUC_SLOT(W, k, s);
-    const d3 dps = mk3(IMUC_SLOT(W, 9, s), IMUC_SLOT(W, 10, s), IMUC_SLOT(W, 11, s));
-    const d3 dvs = mk3(IMUC_SLOT(W, 12, s), IMUC_SLOT(W, 13, s), IMUC_SLOT(W, 14, s));
-    const double Dts = IMUC_SLOT(W, 15, s);
-    o.p = add3(sub3(scl3(Dts, vR), scl3(.5 * nG * Dts * Dts, gR)), dps);
-    o.v = mv33(o.R, add3(sub3(vR, scl3(nG * Dts, gR)), dvs));
-    o.g = unit3(mv33(o.R, gR));
-    return o;
+// the state behind the step whose chain state lies in slot s
+__device__ __forceinline__ ImuState imuc_state(const double* W, int s, d3 vR, d3 gR, double nG) {
+    return imu_state_behind(imu_get_chain<LP_IMUC_CHUNK>(W, s), vR, gR, nG);
 }
 struct ImucPhi { m33 A1, B1, B2, C1, C2, C3; double dt; };
 __device__ __forceinline__ m33 imuc_ld33(const double* W, int base, int s) {
@@ -99,9 +88,8 @@ __device__ __forceinline__ m33 imuc_blk(const double* W, int a, int b, int s) {
 }
 __device__ __forceinline__ m33 imuc_mulT(const m33& A, const m33& B) { return mul33(A, tr33(B)); }   // A B^T
 
-// out: predict (cap == 0): record j of instance z at out[z * out_stride + j], seq 0; ring (cap > 0): record j has seq = seq0 + j and goes to slot
-// (seq - 1) % cap of ring[cap][batch] — imu_pose_kernel's rule, so record and pose record share seq and slot.  x / P / imu: instance 0's;
-// instance z lies z * bs / z * imu_bs bytes behind (imu_bs = 0: one shared batch).
+// out, out_stride, seq0, cap: imu_record's (imu_preint.h).  x / P / imu: instance 0's; instance z lies z * bs / z * imu_bs bytes behind
+// (imu_bs = 0: one shared batch).
 __global__ __launch_bounds__(LP_IMUC_T) void imu_cov_kernel(double small_angle, double nG, double sg2, double swg2, double sa2, double swa2, int batch,
                                                             const double* __restrict__ x, const double* __restrict__ P, int ld, size_t bs,
                                                             const rvio_imu* __restrict__ imu, size_t imu_bs, int m,
@@ -121,10 +109,8 @@ __global__ __launch_bounds__(LP_IMUC_T) void imu_cov_kernel(double small_angle, 
     const m33 I = eye33();
     const m33 RG = q2r(qG);
     // the state chain's registers, and the state in front of the chunk's first step
-    m33 Rk = q2r(ldq(x + 10)), RkT = tr33(Rk);
-    d3 dp = mk3(0, 0, 0), dv = mk3(0, 0, 0);
-    double Dt = 0.0;
-    m33 Rf = Rk;
+    ImuChain c = {q2r(ldq(x + 10)), mk3(0, 0, 0), mk3(0, 0, 0), 0.0};
+    m33 Rf = c.Rk;
     d3 vf = vR, gf = gR;
     // column cc of P11 (the lanes beyond 23 carry column 23 along and store nothing)
     const int cc = min(lane, 23), ci = min(max(cc - 9, 0), 8);
@@ -140,63 +126,18 @@ __global__ __launch_bounds__(LP_IMUC_T) void imu_cov_kernel(double small_angle, 
         d3 w = mk3(0, 0, 0);
         double dt_s = 0.0;
         if (mine) {
-            const rvio_imu u = imu[s0 + lane];
-            w = sub3(mk3(u.w[0], u.w[1], u.w[2]), bg);
-            const d3 a = sub3(mk3(u.a[0], u.a[1], u.a[2]), ba);
-            const double dt = u.dt, w1 = nrm3(w);
-            const bool small = w1 < small_angle;
-            const double wdt = w1 * dt, wdt2 = wdt * wdt;
-            double sw, cw;
-            sincos(wdt, &sw, &cw);
-            const m33 wx = skew33(w), wx2 = mul33(wx, wx);
-            m33 dR; double f1, f2, f3, f4;
-            if (small) {
-                dR = add33(sub33(I, scl33(dt, wx)), scl33(dt * dt / 2, wx2));
-                f1 = -(dt * dt * dt) / 3; f2 = (dt * dt * dt * dt) / 8; f3 = -(dt * dt) / 2; f4 = (dt * dt * dt) / 6;
-            } else {
-                const double w2 = w1 * w1, w3 = w2 * w1, w4 = w2 * w2;
-                dR = add33(sub33(I, scl33(sw / w1, wx)), scl33((1 - cw) / w2, wx2));
-                f1 = (wdt * cw - sw) / w3;
-                f2 = .5 * (wdt2 - 2 * cw - 2 * wdt * sw + 2) / w4;
-                f3 = (cw - 1) / w2;
-                f4 = (wdt - sw) / w3;
-            }
-            const d3 up = mv33(add33(add33(scl33(.5 * dt * dt, I), scl33(f1, wx)), scl33(f2, wx2)), a);
-            const d3 uv = mv33(add33(add33(scl33(dt, I), scl33(f3, wx)), scl33(f4, wx2)), a);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) IMUC_SLOT(W, k, lane) = dR.m[k];
-            IMUC_SLOT(W, 9, lane) = up.x; IMUC_SLOT(W, 10, lane) = up.y; IMUC_SLOT(W, 11, lane) = up.z;
-            IMUC_SLOT(W, 12, lane) = uv.x; IMUC_SLOT(W, 13, lane) = uv.y; IMUC_SLOT(W, 14, lane) = uv.z;
-            IMUC_SLOT(W, 15, lane) = dt;
-            dt_s = dt;
+            const ImuTerms t = imu_sample_terms(imu[s0 + lane], bg, ba, small_angle);
+            imu_put_terms<LP_IMUC_CHUNK>(W, lane, t);
+            w = t.w; dt_s = t.dt;
         }
-        IMUC_FENCE();
+        imu_wave_fence();
         // ---- B
-        for (int s = 0; s < mc; ++s) {
-            m33 dR;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) dR.m[k] = IMUC_SLOT(W, k, s);
-            const d3 up = mk3(IMUC_SLOT(W, 9, s), IMUC_SLOT(W, 10, s), IMUC_SLOT(W, 11, s));
-            const d3 uv = mk3(IMUC_SLOT(W, 12, s), IMUC_SLOT(W, 13, s), IMUC_SLOT(W, 14, s));
-            const double dt = IMUC_SLOT(W, 15, s);
-            Dt += dt;
-            Rk = mul33(dR, Rk); RkT = tr33(Rk);
-            dp = add3(dp, scl3(dt, dv));
-            dp = add3(dp, mv33(RkT, up));
-            dv = add3(dv, mv33(RkT, uv));
-            if (lane == 0) {
-#pragma unroll
-                for (int k = 0; k < 9; ++k) IMUC_SLOT(W, k, s) = Rk.m[k];
-                IMUC_SLOT(W, 9, s) = dp.x; IMUC_SLOT(W, 10, s) = dp.y; IMUC_SLOT(W, 11, s) = dp.z;
-                IMUC_SLOT(W, 12, s) = dv.x; IMUC_SLOT(W, 13, s) = dv.y; IMUC_SLOT(W, 14, s) = dv.z;
-                IMUC_SLOT(W, 15, s) = Dt;
-            }
-        }
-        IMUC_FENCE();
+        imu_chain_chunk<LP_IMUC_CHUNK>(W, mc, lane, c);
+        imu_wave_fence();
         // ---- C
-        const ImucState bh = imuc_state(W, sl, vR, gR, nG);                      // behind this lane's step
-        const ImucState pv = imuc_state(W, sl > 0 ? sl - 1 : 0, vR, gR, nG);     // behind the step before it
-        const ImucState last = imuc_state(W, mc - 1, vR, gR, nG);                // behind the chunk (uniform)
+        const ImuState bh = imuc_state(W, sl, vR, gR, nG);                      // behind this lane's step
+        const ImuState pv = imuc_state(W, sl > 0 ? sl - 1 : 0, vR, gR, nG);     // behind the step before it
+        const ImuState last = imuc_state(W, mc - 1, vR, gR, nG);                // behind the chunk (uniform)
         {
             const bool first = sl == 0;
             m33 Rs;
@@ -222,7 +163,7 @@ __global__ __launch_bounds__(LP_IMUC_T) void imu_cov_kernel(double small_angle, 
             }
         }
         Rf = last.R; vf = last.v; gf = last.g;
-        IMUC_FENCE();
+        imu_wave_fence();
         // ---- D
         for (int s = 0; s < mc; ++s) {
             ImucPhi F;
@@ -236,7 +177,7 @@ __global__ __launch_bounds__(LP_IMUC_T) void imu_cov_kernel(double small_angle, 
 #pragma unroll
                 for (int i = 0; i < 9; ++i) Tl[i * 24 + lane] = Tc[i];
             }
-            IMUC_FENCE();
+            imu_wave_fence();
             // columns 9..17: P11 Phi^T's column is T's row; Phi on it, plus Q's column
             double V[24], T2[9];
 #pragma unroll
@@ -252,7 +193,7 @@ __global__ __launch_bounds__(LP_IMUC_T) void imu_cov_kernel(double small_angle, 
             // the process noise of the biases: G[18][3] = G[21][9] = I
 #pragma unroll
             for (int r = 18; r < 24; ++r) Pc[r] += (cc == r) ? F.dt * (r < 21 ? swg2 : swa2) : 0.0;
-            IMUC_FENCE();   // (the blocks and T's rows are read: the record's words may go over the first, the next step's T over the second)
+            imu_wave_fence();   // (the blocks and T's rows are read: the record's words may go over the first, the next step's T over the second)
             // what the record needs, over the sample's blocks
             const int cb = cc < 6 ? cc : cc - 3;
             if (col && (cc < 6 || (cc >= 9 && cc < 15))) {
@@ -264,7 +205,7 @@ __global__ __launch_bounds__(LP_IMUC_T) void imu_cov_kernel(double small_angle, 
                 for (int i = 0; i < 3; ++i) IMUC_SLOT(W, IMUC_OUT + 144 + i * 3 + (lane - 15), s) = Pc[15 + i];
             }
         }
-        IMUC_FENCE();
+        imu_wave_fence();
         // ---- E
         const int j = s0 + lane;
         if (mine && (cap == 0 || j >= m - cap)) {
@@ -289,6 +230,8 @@ __global__ __launch_bounds__(LP_IMUC_T) void imu_cov_kernel(double small_angle, 
             const m33 X10 = mul33(RT, P00), X11 = mul33(RT, P01);
             const m33 C00 = sub33(imuc_mulT(X00, A), imuc_mulT(X01, RT)), C01 = imuc_mulT(X00, RT);
             const m33 C10 = sub33(imuc_mulT(X10, A), imuc_mulT(X11, RT)), C11 = imuc_mulT(X10, RT);
+            // (imu_record's rule and imu_record_stored's above, written out: through the helpers this kernel allocates 2 to 8 registers more
+            // than the 500 it has, and it has none to spare)
             const long long seq = cap ? seq0 + j : 0;
             const size_t rec = cap ? (size_t)((seq - 1) % cap) * (size_t)batch + (size_t)z : (size_t)z * (size_t)out_stride + (size_t)j;
             unsigned long long* o = out + rec * IMUC_WORDS;
@@ -299,18 +242,18 @@ __global__ __launch_bounds__(LP_IMUC_T) void imu_cov_kernel(double small_angle, 
 #pragma unroll
                 for (int b = 0; b < 3; ++b) {
                     // (a, b) of the four blocks; the mirror entry adds the same two numbers in the other order
-                    o[2 + a * 6 + b] = (unsigned long long)__double_as_longlong(0.5 * (C00.m[3 * a + b] + C00.m[3 * b + a]));
-                    o[2 + a * 6 + 3 + b] = (unsigned long long)__double_as_longlong(0.5 * (C01.m[3 * a + b] + C10.m[3 * b + a]));
-                    o[2 + (3 + a) * 6 + b] = (unsigned long long)__double_as_longlong(0.5 * (C10.m[3 * a + b] + C01.m[3 * b + a]));
-                    o[2 + (3 + a) * 6 + 3 + b] = (unsigned long long)__double_as_longlong(0.5 * (C11.m[3 * a + b] + C11.m[3 * b + a]));
+                    o[2 + a * 6 + b] = imu_word(0.5 * (C00.m[3 * a + b] + C00.m[3 * b + a]));
+                    o[2 + a * 6 + 3 + b] = imu_word(0.5 * (C01.m[3 * a + b] + C10.m[3 * b + a]));
+                    o[2 + (3 + a) * 6 + b] = imu_word(0.5 * (C10.m[3 * a + b] + C01.m[3 * b + a]));
+                    o[2 + (3 + a) * 6 + 3 + b] = imu_word(0.5 * (C11.m[3 * a + b] + C11.m[3 * b + a]));
                 }
 #pragma unroll
             for (int k = 0; k < 9; ++k) {   // sym(P11)[15..17][15..17]
                 const int kt = 3 * (k % 3) + k / 3;
-                o[38 + k] = (unsigned long long)__double_as_longlong(0.5 * (IMUC_SLOT(W, IMUC_OUT + 144 + k, lane) + IMUC_SLOT(W, IMUC_OUT + 144 + kt, lane)));
+                o[38 + k] = imu_word(0.5 * (IMUC_SLOT(W, IMUC_OUT + 144 + k, lane) + IMUC_SLOT(W, IMUC_OUT + 144 + kt, lane)));
             }
         }
         // (the next chunk's phase A rewrites the slots phase E has read: same wave, program order)
-        IMUC_FENCE();
+        imu_wave_fence();
     }
 }

@@ -198,12 +198,8 @@ struct rvio_hip {
     DevRing<rvio_imu_cov> imuc{"IMU-rate covariance", "rvio_hip_set_imu_odometry_cov"};
     long long imuc_first = 1;
     size_t time_imu_bs = 0;    // instance stride of time_imu (rvio_hip_debug_time_kernel(13), (14))
-    // staging of rvio_hip_predict (host in / host out), allocated by its first call, outside the slab: samples in, records out
-    rvio_imu* pred_imu = nullptr;
-    rvio_imu_pose* pred_out = nullptr;
-    int pred_cap = 0;
-    rvio_imu_cov* pred_cov = nullptr;   // ... and the covariance records of rvio_hip_predict_cov, allocated by ITS first call
-    int pred_cov_cap = 0;
+    // staging of rvio_hip_predict / rvio_hip_predict_cov (host in / host out), outside the slab, owned by predict_staging: samples in, records out
+    struct PredStage { rvio_imu* imu = nullptr; rvio_imu_pose* out = nullptr; rvio_imu_cov* cov = nullptr; int cap = 0; } pred;
     bool has_state = false;    // rvio_hip_set_state* / rvio_hip_initialize* has run (rvio_hip_predict* refuses to extrapolate from nothing)
     // auxiliary measurement update (aux_update.hip), allocated by the first rvio_hip_update_aux* call, outside the slab: (gamma, applied) of the
     // last call per instance; the host form's staging [H | v | sigma | active flags]
@@ -1395,16 +1391,21 @@ static void launch_odom(rvio_hip* h, rvio_odom* slot, long long seq) {
 // The two operations of a DevRing (the odometry ring here, the IMU-rate ring below).  Capacity: 0 switches the launches off and keeps the ring and
 // its records; the capacity it has only switches them on; another one (or the first) is allocated with nothing in flight, and a new ring is empty.
 extern "C++" {
+// a ring may take 1 GiB (also asked ahead of ring_set_capacity where two rings change together: both or neither)
+template <typename T>
+static bool ring_too_large(rvio_hip* h, const DevRing<T>& r, int capacity) {
+    const size_t bytes = (size_t)capacity * h->batch * sizeof(T);
+    if (bytes <= ((size_t)1 << 30)) return false;
+    h->err = std::string(r.noun) + " ring of " + std::to_string(capacity) + " x " + std::to_string(h->batch) + " records = " + std::to_string(bytes) + " bytes exceeds 1 GiB";
+    return true;
+}
 template <typename T>
 static int ring_set_capacity(rvio_hip* h, DevRing<T>& r, int capacity, int limit) {
     if (capacity < 0 || capacity > limit) return RVIO_ERR_INVALID;
     if (capacity == 0) { r.on = false; return RVIO_OK; }
     if (capacity != r.cap) {
+        if (ring_too_large(h, r, capacity)) return RVIO_ERR_UNSUPPORTED;
         const size_t bytes = (size_t)capacity * h->batch * sizeof(T);
-        if (bytes > ((size_t)1 << 30)) {
-            h->err = std::string(r.noun) + " ring of " + std::to_string(capacity) + " x " + std::to_string(h->batch) + " records = " + std::to_string(bytes) + " bytes exceeds 1 GiB";
-            return RVIO_ERR_UNSUPPORTED;
-        }
         { const int rc = drain_all(h); if (rc != RVIO_OK) return rc; }
         RCCHK(own_replace(h, &r.ring, bytes));
         r.cap = capacity; r.seq = 0;
@@ -1458,88 +1459,78 @@ static int predict_check(rvio_hip* h) {
     if (!h->has_state) { h->err = "rvio_hip_predict before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
     return RVIO_OK;
 }
-// every instance, asynchronous on the filter stream: behind everything enqueued there, ahead of everything enqueued later
-int rvio_hip_predict_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride, int m, rvio_imu_pose* d_out, int out_stride) {
-    if (!h || m < 0 || (m > 0 && (!d_imu || !d_out)) || imu_stride < 0 || (imu_stride > 0 && imu_stride < m) || out_stride < m) return RVIO_ERR_INVALID;
-    { const int rc = predict_check(h); if (rc != RVIO_OK) return rc; }
-    if (m == 0) return RVIO_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    launch_imu_pose(h, h->stream, h->batch, h->x[h->cur], d_imu, (size_t)imu_stride * sizeof(rvio_imu), m, d_out, out_stride, 0, 0, h->img_count);
-    HIPCHK(h, hipGetLastError());
-    return RVIO_OK;
-}
-// the staging of rvio_hip_predict / rvio_hip_predict_cov holds m samples and m pose records
-static int predict_staging(rvio_hip* h, int m) {
-    if (m <= h->pred_cap) return RVIO_OK;   // (every earlier call has waited for its copies: nothing reads the old blocks)
-    const int cap = std::max(std::max(2 * h->pred_cap, RVIO_HIP_MAX_IMU), (m + 63) & ~63);
-    rvio_imu* pi = nullptr; rvio_imu_pose* po = nullptr;   // (both or neither: the members change once the pair exists)
-    int rc = own_dev(h, &pi, sizeof(rvio_imu) * (size_t)cap);
-    if (rc == RVIO_OK) rc = own_dev(h, &po, sizeof(rvio_imu_pose) * (size_t)cap);
-    if (rc != RVIO_OK) { own_release(h, pi); return rc; }
-    own_release(h, h->pred_imu); own_release(h, h->pred_out);
-    h->pred_imu = pi; h->pred_out = po; h->pred_cap = cap;
-    return RVIO_OK;
-}
-// one instance, host buffers: staged through buffers of its own (the staging of the other host-buffer entry points may still be read by a
-// frame in flight), which grow with m; waits for the filter stream only, like rvio_hip_get_pose
-int rvio_hip_predict(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio_imu_pose* out) {
-    if (!h || instance < 0 || instance >= h->batch || m < 0 || (m > 0 && (!imu || !out))) return RVIO_ERR_INVALID;
-    { const int rc = predict_check(h); if (rc != RVIO_OK) return rc; }
-    if (m == 0) return RVIO_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    RCCHK(predict_staging(h, m));
-    HIPCHK(h, hipMemcpyAsync(h->pred_imu, imu, sizeof(rvio_imu) * (size_t)m, hipMemcpyHostToDevice, h->stream));
-    launch_imu_pose(h, h->stream, 1, (const double*)((const char*)h->x[h->cur] + (size_t)instance * h->slab_bytes), h->pred_imu, 0, m, h->pred_out, m, 0, 0, h->img_count);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, h->pred_out, sizeof(rvio_imu_pose) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return RVIO_OK;
-}
-// the same plus the covariance records (imu_cov.hip); the pose records are the existing kernel's, out / d_out == NULL: covariances only
-int rvio_hip_predict_cov_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride, int m, rvio_imu_pose* d_out, int out_stride, rvio_imu_cov* d_cov, int cov_stride) {
-    if (!h || m < 0 || (m > 0 && (!d_imu || !d_cov)) || imu_stride < 0 || (imu_stride > 0 && imu_stride < m) || (d_out && out_stride < m) || cov_stride < m) return RVIO_ERR_INVALID;
+// The device forms, every instance, asynchronous on the filter stream (behind everything enqueued there, ahead of everything enqueued later):
+// the pose records where d_out, the covariance records (imu_cov.hip) where d_cov
+static int predict_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride, int m, rvio_imu_pose* d_out, int out_stride, rvio_imu_cov* d_cov, int cov_stride) {
     { const int rc = predict_check(h); if (rc != RVIO_OK) return rc; }
     if (m == 0) return RVIO_OK;
     HIPCHK(h, hipSetDevice(h->device));
     const size_t imu_bs = (size_t)imu_stride * sizeof(rvio_imu);
     if (d_out) launch_imu_pose(h, h->stream, h->batch, h->x[h->cur], d_imu, imu_bs, m, d_out, out_stride, 0, 0, h->img_count);
-    launch_imu_cov(h, h->stream, h->batch, h->x[h->cur], h->P[h->cur], d_imu, imu_bs, m, d_cov, cov_stride, 0, 0, h->img_count);
+    if (d_cov) launch_imu_cov(h, h->stream, h->batch, h->x[h->cur], h->P[h->cur], d_imu, imu_bs, m, d_cov, cov_stride, 0, 0, h->img_count);
     HIPCHK(h, hipGetLastError());
     return RVIO_OK;
 }
-int rvio_hip_predict_cov(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio_imu_pose* out, rvio_imu_cov* cov) {
-    if (!h || instance < 0 || instance >= h->batch || m < 0 || (m > 0 && (!imu || !cov))) return RVIO_ERR_INVALID;
+int rvio_hip_predict_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride, int m, rvio_imu_pose* d_out, int out_stride) {
+    if (!h || m < 0 || (m > 0 && (!d_imu || !d_out)) || imu_stride < 0 || (imu_stride > 0 && imu_stride < m) || out_stride < m) return RVIO_ERR_INVALID;
+    return predict_dev(h, d_imu, imu_stride, m, d_out, out_stride, nullptr, 0);
+}
+// d_out == NULL: covariances only
+int rvio_hip_predict_cov_dev(rvio_hip* h, const rvio_imu* d_imu, int imu_stride, int m, rvio_imu_pose* d_out, int out_stride, rvio_imu_cov* d_cov, int cov_stride) {
+    if (!h || m < 0 || (m > 0 && (!d_imu || !d_cov)) || imu_stride < 0 || (imu_stride > 0 && imu_stride < m) || (d_out && out_stride < m) || cov_stride < m) return RVIO_ERR_INVALID;
+    return predict_dev(h, d_imu, imu_stride, m, d_out, out_stride, d_cov, cov_stride);
+}
+// The staging of the host forms: `cap` samples, pose records and — from the first call that asks for covariance on — covariance records.  It is
+// replaced as a whole (all blocks or none; every earlier call has waited for its copies, so nothing reads the old ones)
+static int predict_staging(rvio_hip* h, int m, bool with_cov) {
+    rvio_hip::PredStage& g = h->pred;
+    with_cov = with_cov || g.cov;
+    if (m <= g.cap && (g.cov || !with_cov)) return RVIO_OK;
+    rvio_hip::PredStage n;
+    n.cap = (m <= g.cap) ? g.cap : std::max(std::max(2 * g.cap, RVIO_HIP_MAX_IMU), (m + 63) & ~63);
+    int rc = own_dev(h, &n.imu, sizeof(rvio_imu) * (size_t)n.cap);
+    if (rc == RVIO_OK) rc = own_dev(h, &n.out, sizeof(rvio_imu_pose) * (size_t)n.cap);
+    if (rc == RVIO_OK && with_cov) rc = own_dev(h, &n.cov, sizeof(rvio_imu_cov) * (size_t)n.cap);
+    const rvio_hip::PredStage drop = (rc == RVIO_OK) ? g : n;
+    own_release(h, drop.imu); own_release(h, drop.out); own_release(h, drop.cov);
+    if (rc == RVIO_OK) g = n;
+    return rc;
+}
+// The host forms, one instance: staged through buffers of their own (the staging of the other host-buffer entry points may still be read by a
+// frame in flight), which grow with m; they wait for the filter stream only, like rvio_hip_get_pose.  The pose records where out, the
+// covariance records where cov
+static int predict_host(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio_imu_pose* out, rvio_imu_cov* cov) {
     { const int rc = predict_check(h); if (rc != RVIO_OK) return rc; }
     if (m == 0) return RVIO_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    RCCHK(predict_staging(h, m));
-    if (m > h->pred_cov_cap) {   // (grows with the pair above: every earlier call has waited for its copies)
-        RCCHK(own_replace(h, &h->pred_cov, sizeof(rvio_imu_cov) * (size_t)h->pred_cap));
-        h->pred_cov_cap = h->pred_cap;
-    }
+    RCCHK(predict_staging(h, m, cov != nullptr));
+    const auto& g = h->pred;
     const size_t off = (size_t)instance * h->slab_bytes;
     const double *xi = (const double*)((const char*)h->x[h->cur] + off), *Pi = (const double*)((const char*)h->P[h->cur] + off);
-    HIPCHK(h, hipMemcpyAsync(h->pred_imu, imu, sizeof(rvio_imu) * (size_t)m, hipMemcpyHostToDevice, h->stream));
-    if (out) launch_imu_pose(h, h->stream, 1, xi, h->pred_imu, 0, m, h->pred_out, m, 0, 0, h->img_count);
-    launch_imu_cov(h, h->stream, 1, xi, Pi, h->pred_imu, 0, m, h->pred_cov, m, 0, 0, h->img_count);
+    HIPCHK(h, hipMemcpyAsync(g.imu, imu, sizeof(rvio_imu) * (size_t)m, hipMemcpyHostToDevice, h->stream));
+    if (out) launch_imu_pose(h, h->stream, 1, xi, g.imu, 0, m, g.out, m, 0, 0, h->img_count);
+    if (cov) launch_imu_cov(h, h->stream, 1, xi, Pi, g.imu, 0, m, g.cov, m, 0, 0, h->img_count);
     HIPCHK(h, hipGetLastError());
-    if (out) HIPCHK(h, hipMemcpyAsync(out, h->pred_out, sizeof(rvio_imu_pose) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(cov, h->pred_cov, sizeof(rvio_imu_cov) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
+    if (out) HIPCHK(h, hipMemcpyAsync(out, g.out, sizeof(rvio_imu_pose) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
+    if (cov) HIPCHK(h, hipMemcpyAsync(cov, g.cov, sizeof(rvio_imu_cov) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RVIO_OK;
 }
-static bool imuc_too_large(rvio_hip* h, int capacity) {
-    const size_t bytes = (size_t)capacity * h->batch * sizeof(rvio_imu_cov);
-    if (bytes <= ((size_t)1 << 30)) return false;
-    h->err = std::string(h->imuc.noun) + " ring of " + std::to_string(capacity) + " x " + std::to_string(h->batch) + " records = " + std::to_string(bytes) + " bytes exceeds 1 GiB";
-    return true;
+int rvio_hip_predict(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio_imu_pose* out) {
+    if (!h || instance < 0 || instance >= h->batch || m < 0 || (m > 0 && (!imu || !out))) return RVIO_ERR_INVALID;
+    return predict_host(h, instance, imu, m, out, nullptr);
+}
+// out == NULL: covariances only
+int rvio_hip_predict_cov(rvio_hip* h, int instance, const rvio_imu* imu, int m, rvio_imu_pose* out, rvio_imu_cov* cov) {
+    if (!h || instance < 0 || instance >= h->batch || m < 0 || (m > 0 && (!imu || !cov))) return RVIO_ERR_INVALID;
+    return predict_host(h, instance, imu, m, out, cov);
 }
 // the ring: rvio_hip_set_odometry's clauses, one record per IMU sample instead of one per frame
 // (a covariance ring that exists follows every change of capacity: both rings are reallocated and emptied, or neither)
 int rvio_hip_set_imu_odometry(rvio_hip* h, int capacity) {
     if (!h) return RVIO_ERR_INVALID;
     const bool both = h->imuc.ring && capacity > 0 && capacity <= 1048576 && capacity != h->imuo.cap;
-    if (both && imuc_too_large(h, capacity)) return RVIO_ERR_UNSUPPORTED;
+    if (both && ring_too_large(h, h->imuc, capacity)) return RVIO_ERR_UNSUPPORTED;
     RCCHK(ring_set_capacity(h, h->imuo, capacity, 1048576));
     if (both) {
         const bool on = h->imuc.on;
@@ -1558,7 +1549,7 @@ int rvio_hip_set_imu_odometry_cov(rvio_hip* h, int enable) {
     if (!ring_exists(h, h->imuo)) return RVIO_ERR_STATE;
     if (h->imuc.on) return RVIO_OK;
     if (h->imuc.cap != h->imuo.cap) {
-        if (imuc_too_large(h, h->imuo.cap)) return RVIO_ERR_UNSUPPORTED;
+        if (ring_too_large(h, h->imuc, h->imuo.cap)) return RVIO_ERR_UNSUPPORTED;
         RCCHK(ring_set_capacity(h, h->imuc, h->imuo.cap, 1048576));
     }
     h->imuc.on = true;
