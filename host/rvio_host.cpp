@@ -519,6 +519,106 @@ bool read_fixes(const std::string& path, std::vector<FixRow>* out, std::string* 
     return parse_fixes(ss.str(), path, out, err);
 }
 
+// ---- relative-pose measurements (rvio_hip_update_rel): a delta pose between two frames of the window
+RelSpan resolve_rel_span(const std::vector<double>& stamps, double t_new, double t_old) {
+    RelSpan r;
+    if (stamps.empty()) return r;
+    const FixAge a = resolve_fix_age(stamps, t_new, false), b = resolve_fix_age(stamps, t_old, false);
+    if (a.where == FIX_AGE_TOO_OLD || b.where == FIX_AGE_TOO_OLD) return r;                  // the older stamp (or both) has left the window
+    r.age_new = a.where == FIX_AGE_NOW ? 0 : a.age;                                          // at or past the newest composed image: that image
+    r.age_old = b.where == FIX_AGE_NOW ? 0 : b.age;
+    r.ok = r.age_new < r.age_old;                                                            // (one frame has no delta)
+    return r;
+}
+int System::update_rel_at(double t_new, double t_old, int kind, const rvio_fix& meas, bool gate) {
+    if (!h_ || !ready_) { err_ = "System::update_rel_at before the filter is initialised"; return -1; }
+    if (!(t_old < t_new)) { err_ = "System::update_rel_at: t_old is not before t_new"; return -1; }
+    const RelSpan w = resolve_rel_span(std::vector<double>(stamps_.begin(), stamps_.end()), t_new, t_old);
+    if (!w.ok) { ++rl_dropped_; return 0; }
+    if (rvio_hip_update_rel(h_, -1, kind, gate ? 1 : 0, w.age_new, w.age_old, &meas) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+    return 0;
+}
+int System::rel_position_at(double t_new, double t_old, const double d[3], const double sigma[3], const double* lever, bool gate) {
+    return update_rel_at(t_new, t_old, RVIO_REL_POSITION, position_fix(d, sigma, lever), gate);
+}
+int System::rel_attitude_at(double t_new, double t_old, const double q[4], const double sigma[3], bool gate) {
+    return update_rel_at(t_new, t_old, RVIO_REL_ATTITUDE, attitude_fix(q, sigma), gate);
+}
+int System::rel_pose_at(double t_new, double t_old, const double d[3], const double q[4], const double sigma_p[3], const double sigma_q[3], const double* lever, bool gate) {
+    return update_rel_at(t_new, t_old, RVIO_REL_POSE, pose_fix(d, q, sigma_p, sigma_q, lever), gate);
+}
+void System::queue_rels(std::vector<RelRow> rows, bool gate) {
+    std::stable_sort(rows.begin(), rows.end(), [](const RelRow& a, const RelRow& b) { return a.t_new < b.t_new; });
+    rl_rows_ = std::move(rows); rl_next_ = 0; rl_gate_ = gate;
+}
+// behind the frame stamped t: every queued measurement whose newer stamp that frame has reached
+int System::apply_rels(double t) {
+    for (; rl_next_ < rl_rows_.size() && rl_rows_[rl_next_].t_new <= t; ++rl_next_) {
+        const RelRow& r = rl_rows_[rl_next_];
+        if (update_rel_at(r.t_new, r.t_old, r.kind, r.meas, rl_gate_) < 0) return -1;
+    }
+    return 0;
+}
+bool parse_rels(const std::string& text, const std::string& name, std::vector<RelRow>* out, std::string* err) {
+    static const char* const kNames[3] = {"position", "attitude", "pose"};
+    out->clear();
+    std::istringstream in(text);
+    std::string line;
+    for (long ln = 1; std::getline(in, line); ++ln) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        const size_t b = line.find_first_not_of(" \t");
+        if (b == std::string::npos || line[b] == '#') continue;
+        auto bad = [&](const std::string& why) { *err = name + ":" + std::to_string(ln) + ": " + why + ": " + line; return false; };
+        std::string flat = line;
+        std::replace(flat.begin(), flat.end(), ',', ' ');
+        std::istringstream ls(flat);
+        std::vector<std::string> tok;
+        for (std::string w; ls >> w;) tok.push_back(w);
+        if (tok.size() < 3) return bad("not `t_new t_old kind values... sigmas... [lever]`");
+        int k = -1;
+        for (int i = 0; i < 3; ++i) if (tok[2] == kNames[i] || tok[2] == std::to_string(RVIO_REL_POSITION + i)) k = i;
+        if (k < 0) return bad("unknown kind '" + tok[2] + "' (position | attitude | pose or 16 .. 18)");
+        std::vector<double> v;
+        for (size_t i = 0; i < tok.size(); ++i) {
+            if (i == 2) continue;
+            char* end = nullptr;
+            const double x = std::strtod(tok[i].c_str(), &end);
+            if (end == tok[i].c_str() || *end != 0 || !std::isfinite(x)) return bad("'" + tok[i] + "' is not a finite number");
+            v.push_back(x);
+        }
+        // v: t_new, t_old, then the kind's values and sigmas, then (position, pose) an optional lever
+        const int nz = k == 2 ? 7 : (k == 1 ? 4 : 3), ns = k == 2 ? 6 : 3;
+        const bool may_lever = k != 1;
+        const size_t need = 2 + (size_t)nz + ns;
+        if (v.size() != need && !(may_lever && v.size() == need + 3))
+            return bad(std::string(kNames[k]) + " takes " + std::to_string(nz) + " values and " + std::to_string(ns) + " sigmas" + (may_lever ? " and an optional lever of 3" : "") +
+                       " behind the two stamps and the kind, the line holds " + std::to_string(v.size() - 2));
+        RelRow r;
+        r.t_new = v[0]; r.t_old = v[1]; r.kind = RVIO_REL_POSITION + k;
+        if (!(r.t_old < r.t_new)) return bad("t_old is not before t_new");
+        const int z0 = k == 1 ? 3 : 0;
+        for (int i = 0; i < nz; ++i) r.meas.z[z0 + i] = v[2 + i];
+        for (int i = 0; i < ns; ++i) {
+            if (!(v[2 + nz + i] > 0)) return bad("a sigma is not > 0");
+            r.meas.sigma[z0 + i] = v[2 + nz + i];
+        }
+        if (v.size() == need + 3) for (int i = 0; i < 3; ++i) r.meas.lever[i] = v[need + i];
+        if (k != 0) {
+            const double* q = r.meas.z + 3;
+            if (std::fabs(std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]) - 1.0) > 1e-6) return bad("the quaternion is not of unit length (1e-6)");
+        }
+        out->push_back(r);
+    }
+    return true;
+}
+bool read_rels(const std::string& path, std::vector<RelRow>* out, std::string* err) {
+    std::ifstream f(path);
+    if (!f) { *err = "cannot read " + path; return false; }
+    std::stringstream ss;
+    ss << f.rdbuf();
+    return parse_rels(ss.str(), path, out, err);
+}
+
 // behind a frame: the decision and, where the platform stands still, the zero-velocity update — on the device, nothing waited for unless the
 // records are asked for
 int System::standstill(double t, const rvio_imu* imu, int m) {
@@ -617,6 +717,7 @@ int System::MonoVIO(PoseLine* pose) {
         note_stamp(image.t);
         if (ss_on_ && standstill(image.t, pi, m) < 0) return -1;   // (ahead of the pose read-back: the pose line is the updated state's)
         if (fx_next_ < fx_rows_.size() && apply_fixes(image.t) < 0) return -1;   // (likewise)
+        if (rl_next_ < rl_rows_.size() && apply_rels(image.t) < 0) return -1;    // (likewise)
         if (pose) {
             pose->t = image.t;
             if (rvio_hip_get_pose(h_, pose->p, pose->q) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
@@ -640,6 +741,7 @@ int System::MonoVIO(PoseLine* pose) {
     note_stamp(image.t);
     if (ss_on_ && standstill(image.t, pi, m) < 0) return -1;
     if (fx_next_ < fx_rows_.size() && apply_fixes(image.t) < 0) return -1;
+    if (rl_next_ < rl_rows_.size() && apply_rels(image.t) < 0) return -1;
     PoseLine pl;
     pl.t = image.t;
     if (rvio_hip_get_pose(h_, pl.p, pl.q) != RVIO_OK) return fail();                      // (waits for the filter stream)

@@ -110,6 +110,23 @@ struct FixAge { int where = FIX_AGE_NOW; int age = 0; double frac = 0.0; };
 constexpr double kFixAgeSnap = 1e-6;
 FixAge resolve_fix_age(const std::vector<double>& stamps, double t, bool interpolate);
 
+// one line of a --rel file: a delta pose between the instants t_old < t_new (rvio_hip_update_rel)
+struct RelRow { double t_new = 0, t_old = 0; int kind = 0; rvio_fix meas{}; };
+// A rel file is text like a fix file, one relative-pose measurement per line:
+//     t_new t_old position dx dy dz  sx sy sz  [lx ly lz]
+//     t_new t_old attitude qx qy qz qw  sx sy sz
+//     t_new t_old pose     dx dy dz  qx qy qz qw  sx sy sz  srx sry srz  [lx ly lz]
+// kind: the word or its number (16 .. 18, RVIO_REL_*); d: the displacement of the sensed point from t_old to t_new in the axes of the IMU frame at
+// t_old; q: the quaternion rotating the IMU frame at t_old into the one at t_new (JPL xyzw); sigmas and lever as in a fix file.  A malformed line
+// — also one with t_new <= t_old — is an error that names the line: "<name>:<line number>: <why>: <the line>".
+bool parse_rels(const std::string& text, const std::string& name, std::vector<RelRow>* out, std::string* err);
+bool read_rels(const std::string& path, std::vector<RelRow>* out, std::string* err);
+// Which two frames of the window a pair of stamps means (stamps newest first, as for resolve_fix_age): BOTH go to the NEAREST frame (no
+// interpolation between frames); t_new at or past the newest composed image is that image (age 0).  ok = false — the pair is dropped — when the
+// older stamp has left the window (or the newer one has), when the two resolve to one frame, and when nothing is composed yet
+struct RelSpan { bool ok = false; int age_new = 0, age_old = 0; };
+RelSpan resolve_rel_span(const std::vector<double>& stamps, double t_new, double t_old);
+
 class System {
 public:
     System(const Settings& s, int device);
@@ -193,6 +210,22 @@ public:
     int fix_attitude_at(double t, const double q[4], const double sigma[3], bool gate);
     int fix_pose_at(double t, const double p[3], const double q[4], const double sigma_p[3], const double sigma_q[3], const double* lever, bool gate);
     long fixes_dropped() const { return fx_dropped_; }
+    // Relative-pose measurements (rvio_hip_update_rel): the delta pose of the IMU between the instants t_old < t_new, on the clock of the image
+    // stamps — a wheel-odometry integrator's increment, a scan matcher's or a second visual odometry's result, a loop closure inside the window —
+    // linearised on the device against the clones between the two frames; no state is read back.  Both stamps go to the NEAREST frame the window
+    // still reaches (resolve_rel_span above; t_new at or past the newest composed image is that image): exact for deltas between images, off by
+    // up to half a frame of motion at either end otherwise.  A pair whose older stamp has left the window, or whose stamps resolve to one frame,
+    // is dropped and counted.  d: the displacement of the sensed point from t_old to t_new in the IMU axes at t_old; q: the quaternion rotating
+    // the IMU frame at t_old into the one at t_new; kind: RVIO_REL_*.  0, or -1 with error().
+    int update_rel_at(double t_new, double t_old, int kind, const rvio_fix& meas, bool gate);
+    int rel_position_at(double t_new, double t_old, const double d[3], const double sigma[3], const double* lever, bool gate);
+    int rel_attitude_at(double t_new, double t_old, const double q[4], const double sigma[3], bool gate);
+    int rel_pose_at(double t_new, double t_old, const double d[3], const double q[4], const double sigma_p[3], const double sigma_q[3], const double* lever, bool gate);
+    long rels_dropped() const { return rl_dropped_; }
+    // measurements with time stamps (rvio_replay --rel): MonoVIO fuses each one behind the first frame whose image stamp is >= its t_new, ahead of
+    // that frame's pose read-back.  Rows are sorted by t_new
+    void queue_rels(std::vector<RelRow> rows, bool gate);
+    long rels_applied() const { return (long)rl_next_; }
     // columns of an auxiliary H right now: 24 + 6 clones, the clones counted as the library counts them (one per frame behind the first, up
     // to Tracker.nMaxTrackingLength - 1) — no read-back
     int state_dim() const;
@@ -244,6 +277,11 @@ private:
     std::deque<double> stamps_;   // image stamps of the composed frames the clone window still reaches, newest first
     void note_stamp(double t);
     int apply_fixes(double t);
+    std::vector<RelRow> rl_rows_; // queue_rels, sorted by t_new
+    size_t rl_next_ = 0;          // the first row not yet handed on
+    bool rl_gate_ = false;
+    long rl_dropped_ = 0;         // pairs the window no longer holds, or that fall onto one frame
+    int apply_rels(double t);
 };
 
 // 8- or 16-bit PNG (non-interlaced; gray, RGB or RGBA: channels in file order = RGB) or binary PGM / PPM (P5 / P6; maxval 255: 8 bits, 256 ..

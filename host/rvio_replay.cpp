@@ -30,9 +30,18 @@
 //                                        still holds for that time (System::fix_*_at -> rvio_hip_update_fix_past): a position interpolated between
 //                                        the two frames around t, an attitude or pose at the nearest frame; a row older than the window by then is
 //                                        dropped and counted, a gravity row is fused at the frame.  S: a finite number >= 0
+//                                        [--rel FILE [--rel-gate]]
+//                                        --rel: relative-pose measurements, one per line `t_new t_old kind values... sigmas... [lever]` (rvio_host.hpp
+//                                        parse_rels: the delta pose of the IMU between two instants, as a wheel-odometry integrator, a scan matcher or
+//                                        a loop closure inside the window gives it), each linearised and fused on the device (System::update_rel_at ->
+//                                        rvio_hip_update_rel) behind the first frame whose image stamp is >= t_new, between the two frames of the clone
+//                                        window nearest to its stamps; a row whose older stamp has left the window, or whose stamps fall onto one frame,
+//                                        is dropped and counted.  --rel-gate: the 95 % chi-square gate.  A malformed line is an error that names the line
 //   rvio_replay --check-settings <settings.yaml>        print the parsed configuration (no GPU needed)
 //   rvio_replay --check-fix <fixes.txt>                 print the parsed fix file, one JSON object per fix (no GPU needed)
 //   rvio_replay --check-fix-age <t0,t1,..> <t> [nearest] where a fix stamped t falls among the window's image stamps, newest first (no GPU needed)
+//   rvio_replay --check-rel <rels.txt>                  print the parsed rel file, one JSON object per measurement (no GPU needed)
+//   rvio_replay --check-rel-span <t0,t1,..> <t_new> <t_old>   which two frames of the window a pair of stamps means, stamps newest first (no GPU needed)
 //   rvio_replay --check-dataset <asl_root>              print what the dataset reader found (no GPU needed)
 //   rvio_replay --check-image <file.png|.pgm>           decode one image and print its size and checksum (no GPU needed)
 #include <dlfcn.h>
@@ -131,6 +140,33 @@ static int check_fix_age(const char* list, const char* t_arg, bool nearest) {
     std::printf("{\"where\": %d, \"age\": %d, \"frac\": %.17g}\n", w.where, w.age, w.frac);
     return 0;
 }
+// ---------------------------------------------------------------- --rel
+static int check_rel(const char* path) {
+    std::vector<RelRow> rows; std::string err;
+    if (!read_rels(path, &rows, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
+    for (const RelRow& r : rows) {
+        std::printf("{\"t_new\": %.17g, \"t_old\": %.17g, \"kind\": %d, \"z\": [", r.t_new, r.t_old, r.kind);
+        for (int i = 0; i < 7; ++i) std::printf("%s%.17g", i ? ", " : "", r.meas.z[i]);
+        std::printf("], \"sigma\": [");
+        for (int i = 0; i < 6; ++i) std::printf("%s%.17g", i ? ", " : "", r.meas.sigma[i]);
+        std::printf("], \"lever\": [%.17g, %.17g, %.17g]}\n", r.meas.lever[0], r.meas.lever[1], r.meas.lever[2]);
+    }
+    return 0;
+}
+static std::vector<double> stamp_list(const char* list) {
+    std::vector<double> stamps;
+    std::string flat = list;
+    for (char& c : flat) if (c == ',') c = ' ';
+    const char* p = flat.c_str();
+    for (char* end = nullptr;; p = end) { const double v = std::strtod(p, &end); if (end == p) break; stamps.push_back(v); }
+    return stamps;
+}
+// --check-rel-span: resolve_rel_span on stamps given newest first
+static int check_rel_span(const char* list, const char* t_new, const char* t_old) {
+    const RelSpan w = resolve_rel_span(stamp_list(list), std::atof(t_new), std::atof(t_old));
+    std::printf("{\"ok\": %d, \"age_new\": %d, \"age_old\": %d}\n", w.ok ? 1 : 0, w.age_new, w.age_old);
+    return 0;
+}
 // --fix-latency: seconds, finite and >= 0
 static bool parse_latency(const char* arg, double* out) {
     char* end = nullptr;
@@ -207,6 +243,8 @@ struct PassOptions {
     const std::vector<FixRow>* fixes = nullptr;   // --fix
     bool fix_gate = false;
     double fix_latency = -1.0;           // --fix-latency (< 0: not given)
+    const std::vector<RelRow>* rels = nullptr;    // --rel
+    bool rel_gate = false;
 };
 static bool dump_frame(System& sys, const rvio_config& c, FrameDump* d) {
     rvio_hip* h = sys.handle();
@@ -228,6 +266,7 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
     if (o.odometry && !sys.record_odometry_to(o.odometry, o.odometry_ring)) { *err = sys.error(); return 1; }
     if (o.imu_odometry && !sys.record_imu_odometry_to(o.imu_odometry, o.imu_odometry_ring, o.imu_odometry_cov)) { *err = sys.error(); return 1; }
     if (o.fixes) sys.queue_fixes(*o.fixes, o.fix_gate, o.fix_latency);
+    if (o.rels) sys.queue_rels(*o.rels, o.rel_gate);
     size_t ii = 0;
     long n_images = 0, n_frames = 0;
     double t_filter = 0;
@@ -340,6 +379,8 @@ int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "--check-dataset")) return check_dataset(argv[2]);
     if (argc >= 3 && !std::strcmp(argv[1], "--check-fix")) return check_fix(argv[2]);
     if (argc >= 4 && !std::strcmp(argv[1], "--check-fix-age")) return check_fix_age(argv[2], argv[3], argc >= 5 && !std::strcmp(argv[4], "nearest"));
+    if (argc >= 3 && !std::strcmp(argv[1], "--check-rel")) return check_rel(argv[2]);
+    if (argc >= 5 && !std::strcmp(argv[1], "--check-rel-span")) return check_rel_span(argv[2], argv[3], argv[4]);
     if (argc >= 3 && !std::strcmp(argv[1], "--check-image")) {   // --check-image FILE [--bgr] [--encoding NAME]
         bool rgb = true; const char* enc = nullptr;
         for (int i = 3; i < argc; ++i) {
@@ -351,7 +392,8 @@ int main(int argc, char** argv) {
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--record-dir DIR] [--record]\n"
                              "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--imu-odometry-cov] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n"
-                             "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate] [--standstill FILE] [--fix FILE] [--fix-gate] [--fix-latency S]\n", argv[0]);
+                             "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate] [--standstill FILE] [--fix FILE] [--fix-gate] [--fix-latency S]\n"
+                             "          [--rel FILE] [--rel-gate]\n", argv[0]);
         return 2;
     }
     const char* out_path = nullptr;
@@ -362,6 +404,7 @@ int main(int argc, char** argv) {
     const char* velocity = nullptr; double velocity_sigma = 0.05; bool velocity_gate = false;
     const char* standstill = nullptr;
     const char* fix = nullptr; bool fix_gate = false; double fix_latency = -1.0;
+    const char* rel = nullptr; bool rel_gate = false;
     const char* record_dir = "."; bool force_record = false, sync_every = false, self = false; int noise_wgs = 0;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -388,6 +431,8 @@ int main(int argc, char** argv) {
             if (i + 1 >= argc || !parse_latency(argv[i + 1], &fix_latency)) { std::fprintf(stderr, "--fix-latency takes seconds, a finite number >= 0\n"); return 1; }
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--rel") && i + 1 < argc) rel = argv[++i];   // `t_new t_old kind values... sigmas... [lever]` lines fused behind the first frame at or past t_new (System::update_rel_at)
+        else if (!std::strcmp(argv[i], "--rel-gate")) rel_gate = true;
         else out_path = argv[i];
     }
     if (fix_latency >= 0 && !fix) { std::fprintf(stderr, "--fix-latency needs --fix FILE\n"); return 1; }
@@ -409,11 +454,16 @@ int main(int argc, char** argv) {
         if (self) { std::fprintf(stderr, "--fix and --selfcheck do not combine\n"); return 1; }
         if (!read_fixes(fix, &fixes, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
     }
+    std::vector<RelRow> rels;
+    if (rel) {
+        if (self) { std::fprintf(stderr, "--rel and --selfcheck do not combine\n"); return 1; }
+        if (!read_rels(rel, &rels, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
+    }
     print_runtime();
     if (self) return selfcheck(s, d, device, max_frames, stall_seed, noise_wgs);
     if (sync_every || stall_seed >= 0 || noise_wgs > 0) {   // the plain replay with one of the two A/B pacings
         std::vector<PoseLine> poses; double ms = 0; int flags = 0;
-        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.imu_odometry_cov = imu_odometry_cov; o.velocity = vr; if (fix) { o.fixes = &fixes; o.fix_gate = fix_gate; o.fix_latency = fix_latency; }
+        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.imu_odometry_cov = imu_odometry_cov; o.velocity = vr; if (fix) { o.fixes = &fixes; o.fix_gate = fix_gate; o.fix_latency = fix_latency; } if (rel) { o.rels = &rels; o.rel_gate = rel_gate; }
         if (run_pass(s, d, device, o, &poses, nullptr, &ms, &flags, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
         if (out_path) { std::ofstream out(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } for (const PoseLine& p : poses) out << format_pose(p); }
         std::fprintf(stderr, "rvio_replay: %zu filtered frames, %.3f ms per MonoVIO call, device flags %d\n", poses.size(), ms, flags);
@@ -428,6 +478,7 @@ int main(int argc, char** argv) {
     if (imu_odometry && !sys.record_imu_odometry_to(imu_odometry, imu_odometry_ring, imu_odometry_cov)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (standstill && !sys.record_standstill_to(standstill)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (fix) sys.queue_fixes(fixes, fix_gate, fix_latency);
+    if (rel) sys.queue_rels(rels, rel_gate);
     std::ofstream out;
     if (out_path) { out.open(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } }
 
@@ -460,6 +511,7 @@ int main(int argc, char** argv) {
     if (vr) print_velocity(*vr);
     if (fix && fix_latency < 0) std::fprintf(stderr, "rvio_replay: fix: %zu rows, %ld applied\n", fixes.size(), sys.fixes_applied());
     if (fix && fix_latency >= 0) std::fprintf(stderr, "rvio_replay: fix: %zu rows, %ld fused, %ld older than the window and dropped (latency %g s)\n", fixes.size(), sys.fixes_applied() - sys.fixes_dropped(), sys.fixes_dropped(), fix_latency);
+    if (rel) std::fprintf(stderr, "rvio_replay: rel: %zu rows, %ld fused, %ld outside the window or on one frame and dropped\n", rels.size(), sys.rels_applied() - sys.rels_dropped(), sys.rels_dropped());
     // anything only the device saw (0 in every test and bench run): said out loud, the poses above are suspect if it is not 0
     const int flags = sys.device_flags();
     if (flags) std::fprintf(stderr, "rvio_replay: DEVICE-SIDE FLAGS %d (1 singular pivot in the solve, 2 a track the window cannot hold was dropped, "

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov); standstill detection (rvio_standstill_config, rvio_standstill, rvio_standstill_config_default, rvio_hip_set_standstill, rvio_hip_standstill, rvio_hip_standstill_dev, rvio_hip_get_standstill); absolute fixes (rvio_fix_kind, rvio_fix, rvio_fix_diag, rvio_hip_update_fix, rvio_hip_update_fix_dev, rvio_hip_get_fix, rvio_hip_get_fix_rows); past-frame fixes (rvio_hip_update_fix_past, rvio_hip_update_fix_past_dev, rvio_hip_frame_age) */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov); standstill detection (rvio_standstill_config, rvio_standstill, rvio_standstill_config_default, rvio_hip_set_standstill, rvio_hip_standstill, rvio_hip_standstill_dev, rvio_hip_get_standstill); absolute fixes (rvio_fix_kind, rvio_fix, rvio_fix_diag, rvio_hip_update_fix, rvio_hip_update_fix_dev, rvio_hip_get_fix, rvio_hip_get_fix_rows); past-frame fixes (rvio_hip_update_fix_past, rvio_hip_update_fix_past_dev, rvio_hip_frame_age); relative-pose measurements (rvio_rel_kind, rvio_hip_update_rel, rvio_hip_update_rel_dev) */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -689,6 +689,51 @@ int rvio_hip_update_fix_past_dev(rvio_hip* h, int kind, int gate, const rvio_fix
  * waited for.  The handle counts a frame in rvio_hip_frame_plan and composes it in rvio_hip_augment_compose; between the two the newest count is
  * not composed yet.  RVIO_ERR_INVALID: NULL argument, no state, a frame not yet composed, a frame that has left the clone window. */
 int rvio_hip_frame_age(rvio_hip* h, int img_count, int* age);
+
+/* --- relative-pose measurements: a delta pose between two frames of the clone window (no reference counterpart) ------------------ */
+/* What most other sensors on a robot produce is neither a state entry nor a world-frame fix but a DELTA POSE BETWEEN TWO INSTANTS: a wheel-odometry
+ * integrator, lidar or radar scan matching, a second visual odometry, a loop closure inside the window, the statement "the platform did not move
+ * between these two images".  Two world-frame fixes would inject absolute information the sensor never had, and rvio_hip_update_aux costs a
+ * drain, a state read-back and a host Jacobian per measurement.  The robocentric window suits the measurement unusually well: clone i IS the
+ * relative pose between two consecutive images, so the pose of the frame a images back in the frame b > a images back depends on the clones
+ * n - b .. n - a - 1 only — not on (qG, pG), (qk, pk), velocity, biases or any newer or older clone.  rel_rows_kernel (csrc/rel_rows.hip, one
+ * wave per instance, the chain as an in-wave scan like fix_past_kernel's) linearises the measurement there; aux_update_kernel, unchanged, runs
+ * right behind with m = 3 (POSE: 6) rows.
+ * Ages count images back from the reference frame {R} as in rvio_hip_update_fix_past: age_new = a, age_old = b, 0 <= a < b <= n, k = b - a.  With
+ * C_i = R(q_i), l = lever (the sensed point in the IMU frame, the same at both instants) and i_j = n - a - j:
+ *   B_0 = I, s_0 = 0;   B_j = B_{j-1} C_{i_j},   s_j = s_{j-1} - B_j p_{i_j}   (j = 1 .. k)
+ * B_k rotates frame b into frame a (older into newer, the sense of a clone's q); -B_k^T s_k is the origin of frame a in frame b (newer in older,
+ * the sense of a clone's p).  The record is rvio_fix as it stands:
+ *   REL_POSITION  m = 3  h = B_k^T (l - s_k) - l: the displacement of the sensed point from instant b to instant a, in frame-b axes
+ *                        r = z[0:3] - h;  sigma[0:3] lie along frame-b axes
+ *                        clone i_j (j = 1 .. k): 24+6i..: -B_k^T [(l - s_{j-1}) x] B_{j-1}   27+6i..: B_k^T B_j
+ *   REL_ATTITUDE  m = 3  z[3:7]: the quaternion rotating frame b into frame a;  E = B_k R(z[3:7])^T,  r = (E21 - E12, E02 - E20, E10 - E01) / 2
+ *                        sigma[3:6] (rad) lie along frame-a axes
+ *                        clone i_j (j = 1 .. k): 24+6i..: B_{j-1}                            27+6i..: 0
+ *   REL_POSE      m = 6  the three position rows, then the three attitude rows
+ * Every column not listed is exactly 0.0: all of columns 0 - 23 and every clone outside n - b .. n - a - 1.  For b = a + 1 without a lever the
+ * measurement IS clone n - a - 1: h = p_i, z[3:7] ~ q_i, and the rows are two identity blocks.
+ * Host form: the ages hold for every instance the call touches and are checked here against the window, which is handle-wide; the record is
+ * checked as rvio_hip_update_fix checks it.  _dev form: d_age_new / d_age_old one int32 per instance, d_meas / meas_stride / d_active as in
+ * rvio_hip_update_fix_dev; nothing on the device is checked by the host.  An instance whose ages are not 0 <= a < b <= n is written by neither
+ * launch and its record says so: m = 0, applied = 0, img_count = -1, r = 0.  The kernel keeps an active flag of its own per instance (the
+ * caller's AND inside the window) and the update runs on that.
+ * rvio_hip_get_fix and rvio_hip_get_fix_rows report the last call of any of the three families; rvio_fix_diag.kind = 16 + the fix kind tells
+ * this one apart, and rvio_fix_diag.img_count is the count of the NEWER frame (the reference frame's count minus age_new).  Everything
+ * rvio_hip_update_aux_dev documents holds: in place, `gate` as there, the pose line rewritten, no ring record, a kept clone-block factor dropped,
+ * error bit 8 on a non-positive pivot.  The first call allocates the fix block and the flags of rvio_hip_update_fix_past if need be, plus the
+ * staging of the ages, outside the filter slab; a handle that never calls these allocates and launches what it did before.  Plain, batch and
+ * sharded handles; on a sharded handle every rank calls alike.  rvio_hip_update_fix* and rvio_hip_update_fix_past* refuse these kinds.
+ * RVIO_ERR_STATE as rvio_hip_update_fix.  RVIO_ERR_INVALID: NULL handle or record, a kind outside 16 .. 18, gate or instance out of range, NULL
+ * d_age_new / d_age_old and — host form only — what rvio_hip_update_fix refuses of a record, age_new < 0, age_old > n, age_new >= age_old
+ * (rvio_hip_last_error).
+ * NOT done: interpolation between frames (both stamps are whole frames); the current (qk, pk) as an endpoint (age 0 is {R}); a sensor-to-IMU
+ * rotation (the caller re-expresses a sensor's delta as the IMU's; only the lever arm is handled); correlation between successive overlapping
+ * deltas of one integrator (they are treated as independent); iterated updates; time-offset estimation. */
+typedef enum { RVIO_REL_POSITION = 16, RVIO_REL_ATTITUDE = 17, RVIO_REL_POSE = 18 } rvio_rel_kind;  /* = 16 + the fix kind: rvio_fix_diag.kind tells the families apart */
+int rvio_hip_update_rel(rvio_hip* h, int instance, int kind, int gate, int age_new, int age_old, const rvio_fix* meas);
+int rvio_hip_update_rel_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_meas, size_t meas_stride, const int32_t* d_age_new,
+                            const int32_t* d_age_old, const int32_t* d_active);
 
 /* --- feature-sharded updater (no reference counterpart) ------ */
 /* Stage A: per-feature build + gate on the features f with f % world == rank,

@@ -624,6 +624,67 @@ def fix_past_model(x, kind, fix, age, frac=0.0):
     return np.vstack(rows_H), np.concatenate(rows_r), np.concatenate(rows_s)
 
 
+# ---- relative-pose measurements between two frames of the window (rvio_hip_update_rel*, csrc/rel_rows.hip in front of the auxiliary update)
+RVIO_REL_POSITION, RVIO_REL_ATTITUDE, RVIO_REL_POSE = 16, 17, 18      # = 16 + the fix kind
+REL_KINDS = (RVIO_REL_POSITION, RVIO_REL_ATTITUDE, RVIO_REL_POSE)
+REL_ROWS = {RVIO_REL_POSITION: 3, RVIO_REL_ATTITUDE: 3, RVIO_REL_POSE: 6}
+
+
+def _rel_chain(x, age_new, age_old):
+    """(B_0 .. B_k, s_0 .. s_k), k = age_old - age_new: the local chain from the frame age_new images back.  B_j rotates the frame j images
+    further back into it, s_j is that frame's origin in it.  Clone i_j = n - age_new - j holds the step: B_j = B_{j-1} C_i, s_j = s_{j-1} - B_j p_i.
+    Reads the clones n - age_old .. n - age_new - 1 and nothing else of x."""
+    n = (len(x) - 26) // 7
+    assert 0 <= age_new < age_old <= n, "ages outside the window, or not age_new < age_old"
+    B, s = [np.eye(3)], [np.zeros(3)]
+    for j in range(1, age_old - age_new + 1):
+        i = n - age_new - j
+        B.append(B[-1] @ quat_to_rot(x[26 + 7 * i: 30 + 7 * i]))
+        s.append(s[-1] - B[-1] @ x[30 + 7 * i: 33 + 7 * i])
+    return B, s
+
+
+def rel_h(x, age_new, age_old, lever=(0.0, 0.0, 0.0)):
+    """The predicted measurement of a delta pose between the frames age_old (b) and age_new (a < b) images back from the state's reference frame,
+    laid out like rvio_fix.z: [0:3] the displacement of the sensed point from instant b to instant a in frame-b axes, B_k^T (l - s_k) - l (no
+    lever: the origin of frame a in frame b, the sense of a clone's p); [3:7] the quaternion rotating frame b into frame a, R = B_k (the sense of
+    a clone's q)."""
+    x, l = np.asarray(x, float), np.broadcast_to(np.asarray(lever, float), (3,))
+    B, s = _rel_chain(x, age_new, age_old)
+    z = np.zeros(7)
+    z[0:3] = B[-1].T @ (l - s[-1]) - l
+    z[3:7] = rot_to_quat(B[-1])
+    return z
+
+
+def rel_model(x, kind, meas, age_new, age_old):
+    """NumPy float64 model of csrc/rel_rows.hip: (H [m x d], r [m], sigma [m]) of one relative-pose measurement (rvio_fix, or anything with z,
+    sigma, lever) between the frames age_old and age_new images back, linearised at the state x in the error-state order of P under
+    R_true ~ (I - [dth x]) R.  The table of include/rvio_hip.h; calls nothing from the library or the oracle."""
+    x = np.asarray(x, float)
+    assert kind in REL_KINDS, "kind"
+    z, sg, l = (np.array([float(v) for v in a]) for a in (meas.z, meas.sigma, meas.lever))
+    n = (len(x) - 26) // 7
+    B, s = _rel_chain(x, age_new, age_old)
+    k = age_old - age_new
+    Bk = B[k]
+    rows_H, rows_r, rows_s = [], [], []
+    if kind in (RVIO_REL_POSITION, RVIO_REL_POSE):
+        H = np.zeros((3, 24 + 6 * n))
+        for j in range(1, k + 1):
+            c = 24 + 6 * (n - age_new - j)
+            H[:, c: c + 3], H[:, c + 3: c + 6] = -Bk.T @ _skew(l - s[j - 1]) @ B[j - 1], Bk.T @ B[j]
+        rows_H.append(H), rows_r.append(z[0:3] - (Bk.T @ (l - s[k]) - l)), rows_s.append(sg[0:3])
+    if kind in (RVIO_REL_ATTITUDE, RVIO_REL_POSE):
+        H = np.zeros((3, 24 + 6 * n))
+        for j in range(1, k + 1):
+            c = 24 + 6 * (n - age_new - j)
+            H[:, c: c + 3] = B[j - 1]
+        E = Bk @ quat_to_rot(z[3:7]).T
+        rows_H.append(H), rows_r.append(0.5 * np.array([E[2, 1] - E[1, 2], E[0, 2] - E[2, 0], E[1, 0] - E[0, 1]])), rows_s.append(sg[3:6])
+    return np.vstack(rows_H), np.concatenate(rows_r), np.concatenate(rows_s)
+
+
 # Camera.T_BC0 of config/rvio_euroc.yaml:55-62 (row-major)
 _T_BC0 = [0.0148655429818, -0.999880929698, 0.00414029679422, -0.0216401454975,
           0.999557249008, 0.0149672133247, 0.025715529948, -0.064676986768,

@@ -149,12 +149,14 @@ LP_HD inline size_t aux_lds_max_doubles(int nmax, int MB) {
 #define LP_FIXP_T 64
 #define LP_FIXP_NMAX 32
 #define LP_FIXP_CHAIN ((LP_FIXP_NMAX + 1) * 12)
+// rel_rows_kernel (rel_rows.hip): the same wave, window limit and chain layout (LP_FIXP_T, LP_FIXP_NMAX, LP_FIXP_CHAIN) — the chain runs between two
+// frames of the window instead of from the reference frame back; its rows have no head block, so the chain is all of its static LDS
 
 // ---------------------------------------------------------------- the kernels create_impl gives a dynamic-LDS limit
 enum LpKernel {
     LPK_FEAT_BUILD16, LPK_FEAT_BUILD4, LPK_GRAM_REDUCE, LPK_BLOCK_SUM, LPK_LIT_BATCH, LPK_GEMM_T_LDS, LPK_GRAM_BATCH4, LPK_GRAM_BATCH6, LPK_FEAT_PROP,
     LPK_BOOKKEEP_B, LPK_RANSAC_BOOK, LPK_SOLVE9_SMALL, LPK_SOLVE6_1, LPK_SOLVE6_2, LPK_SOLVE6_3, LPK_JOSEPH_BATCH, LPK_UG, LPK_UG_LDS, LPK_FINAL_LDS,
-    LPK_JOSEPH_LDS, LPK_IMU_POSE, LPK_AUX_UPDATE4, LPK_AUX_UPDATE16, LPK_IMU_COV, LPK_STANDSTILL, LPK_FIX, LPK_FIX_PAST, LPK_COUNT
+    LPK_JOSEPH_LDS, LPK_IMU_POSE, LPK_AUX_UPDATE4, LPK_AUX_UPDATE16, LPK_IMU_COV, LPK_STANDSTILL, LPK_FIX, LPK_FIX_PAST, LPK_REL, LPK_COUNT
 };
 // (as c++filt prints them, without return type and arguments: how the test finds each kernel's static LDS in the code object's notes)
 static const char* const kLpKernelName[LPK_COUNT] = {
@@ -162,7 +164,7 @@ static const char* const kLpKernelName[LPK_COUNT] = {
     "gram_reduce_batch_kernel<4>", "gram_reduce_batch_kernel<6>", "feat_prop_kernel", "bookkeep_b_kernel", "ransac_book_kernel", "solve9_small_kernel",
     "solve6_kernel<1, 8, 8>", "solve6_kernel<2, 12, 8>", "solve6_kernel<2, 16, 8>", "joseph_batch_kernel", "ug_kernel", "ug_lds_kernel", "final_lds_kernel",
     "joseph_lds_kernel", "imu_pose_kernel", "aux_update_kernel<4>", "aux_update_kernel<16>", "imu_cov_kernel", "standstill_kernel",
-    "fix_rows_kernel", "fix_past_kernel"
+    "fix_rows_kernel", "fix_past_kernel", "rel_rows_kernel"
 };
 
 struct LaunchPlan {
@@ -298,6 +300,8 @@ inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size
     if (statics[LPK_FIX] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
     // fix_past_kernel: likewise (p.attr[LPK_FIX_PAST] stays 0)
     if (statics[LPK_FIX_PAST] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
+    // rel_rows_kernel: likewise (p.attr[LPK_REL] stays 0)
+    if (statics[LPK_REL] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
     if (batch > 1 && !p.solve5_variant && !p.solve7_variant) { p.rc = 1; p.why = "batched filter: clone window too long for the unrolled solve kernel (6n <= 126)"; return p; }
     // nothing above may ask for more than a CU has: a configuration that would is refused here, by name, not by a failed hipFuncSetAttribute / launch
     for (int k = 0; k < LPK_COUNT; ++k)
@@ -468,6 +472,8 @@ LP_HD inline LpLaunch standstill_launch(int batch) { return {1, 1, batch, LP_SS_
 LP_HD inline LpLaunch fix_launch(int batch) { return {1, 1, batch, LP_FIX_T, 0, LPK_FIX}; }
 // fix_past_kernel: the same form
 LP_HD inline LpLaunch fix_past_launch(int batch) { return {1, 1, batch, LP_FIXP_T, 0, LPK_FIX_PAST}; }
+// rel_rows_kernel: the same form
+LP_HD inline LpLaunch rel_launch(int batch) { return {1, 1, batch, LP_FIXP_T, 0, LPK_REL}; }
 
 enum LpStream {          // the ROLE of a stream in a call; stream_of (rvio_hip.hip) maps it to one of the handle's four
     LPR_FILTER,          //   the filter stream: every launch of a per-stage call that is not forked to the side stream

@@ -31,6 +31,7 @@
 #include "standstill.hip"  // standstill detection in front of it: the zero-velocity update of the instances that do not move (rvio_hip_standstill)
 #include "fix_rows.hip"    // absolute fixes in front of it: position, attitude, pose, gravity rows linearised at the current state (rvio_hip_update_fix)
 #include "fix_past.hip"    // ... and delayed ones, linearised against the pose the clone window holds for the frame they were taken at (rvio_hip_update_fix_past)
+#include "rel_rows.hip"    // relative poses between two frames of the window, linearised against the clones between them (rvio_hip_update_rel)
 #pragma clang fp contract(off)
 #include "frontend_kernels.hip"
 #include "klt3.hip"
@@ -230,6 +231,9 @@ struct rvio_hip {
     // past-frame fixes (fix_past.hip) reuse that block and add, with the first rvio_hip_update_fix_past* call, the kernel's flags (one int32 per
     // instance) and the host form's staging (one rvio_fix; frac, age and flag per instance)
     struct { int32_t* flag = nullptr; HostStage stage; } fp;
+    // relative-pose measurements (rel_rows.hip) reuse the fix block and the kernel's flags of the past-frame fixes, and add, with the first
+    // rvio_hip_update_rel call, the host form's staging (one rvio_fix; age_new, age_old and flag per instance)
+    struct { HostStage stage; } rl;
     // colour input (rvio_hip_set_image_format): the gray images every stage behind gray_kernel reads instead of the caller's.  Allocated with the
     // first colour format, outside the slab (a mono handle keeps its memory layout), instance stride W * H; four in rotation like d_eq2[] (see
     // build_pyramid_dev for who reads a slot last)
@@ -606,6 +610,7 @@ static const void* lp_kernel_fn(int k) {
         case LPK_STANDSTILL: return (const void*)standstill_kernel;
         case LPK_FIX: return (const void*)fix_rows_kernel;
         case LPK_FIX_PAST: return (const void*)fix_past_kernel;
+        case LPK_REL: return (const void*)rel_rows_kernel;
     }
     return nullptr;
 }
@@ -1828,11 +1833,11 @@ static int fix_ready(rvio_hip* h, bool past) {
     return own_dev(h, &h->fp.flag, sizeof(int32_t) * (size_t)h->batch, true);
 }
 static size_t fix_H_stride(const rvio_hip* h) { return (size_t)LP_FIX_ROWS * h->dc.dmax; }   // doubles between the instances' rows
-// What the two producers share behind their own launch: kind, m and d for the getters, the RESIDUAL aux launch on the rows they left — it reads
+// What the three producers share behind their own launch: kind, m and d for the getters, the RESIDUAL aux launch on the rows they left — it reads
 // them in stream order and acts where d_flags says — and the drain
 static int fix_consume(rvio_hip* h, int kind, int gate, const int32_t* d_flags) {
     HIPCHK(h, hipGetLastError());
-    const int m = kind == RVIO_FIX_POSE ? 6 : 3;
+    const int m = (kind == RVIO_FIX_POSE || kind == RVIO_REL_POSE) ? 6 : 3;
     h->fx.kind = kind; h->fx.m = m; h->fx.d = 24 + 6 * h->n_clones_host;
     RCCHK(update_aux_dev(h, m, RVIO_AUX_RESIDUAL, gate, h->fx.H, fix_H_stride(h), h->fx.r, 6, h->fx.sigma, 6, d_flags, h->fx.pair));
     if (paranoid_bits() & PAR_DRAIN) return drain_all(h);
@@ -1899,6 +1904,44 @@ int rvio_hip_update_fix_past(rvio_hip* h, int instance, int kind, int gate, int 
     const int32_t* d_active;
     RCCHK(stage_send(h, s, bytes, instance, &d_active));
     return update_fix_past_dev(h, kind, gate, (const rvio_fix*)s.dev, 0, (const int32_t*)(s.dev + o_age), (const double*)(s.dev + o_frac), d_active);
+}
+// ---- relative-pose measurements (rel_rows.hip): the same block, flags and consumer, the rows linearised against the clones between two frames
+static_assert(RVIO_REL_POSITION == 16 + RVIO_FIX_POSITION && RVIO_REL_ATTITUDE == 16 + RVIO_FIX_ATTITUDE && RVIO_REL_POSE == 16 + RVIO_FIX_POSE,
+              "include/rvio_hip.h: a relative kind is 16 + the fix kind");
+static bool rel_args_ok(const rvio_hip* h, const rvio_fix* meas, int kind, int gate, int instance = -1) {
+    return h && meas && kind >= RVIO_REL_POSITION && kind <= RVIO_REL_POSE && (gate == 0 || gate == 1) && instance >= -1 && instance < h->batch;
+}
+// meas_bs: bytes between the instances' records (0: shared).  On the filter stream like update_fix_past_dev; the aux launch gets the kernel's own flags
+static int update_rel_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_meas, size_t meas_bs, const int32_t* d_age_new, const int32_t* d_age_old, const int32_t* d_active) {
+    const LpLaunch l = rel_launch(h->batch);
+    hipLaunchKernelGGL(rel_rows_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->n_clones_host, kind, (const double*)h->x[h->cur], h->slab_bytes, d_meas, meas_bs, (const int*)d_age_new,
+                       (const int*)d_age_old, (const int*)d_active, h->composed_count, h->fx.H, fix_H_stride(h) * sizeof(double), h->fx.r, h->fx.sigma, h->fx.rec, h->fx.pair, (int*)h->fp.flag);
+    return fix_consume(h, kind, gate, h->fp.flag);
+}
+int rvio_hip_update_rel_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_meas, size_t meas_stride, const int32_t* d_age_new, const int32_t* d_age_old, const int32_t* d_active) {
+    if (!rel_args_ok(h, d_meas, kind, gate) || !d_age_new || !d_age_old) return RVIO_ERR_INVALID;
+    RCCHK(meas_guard(h, "rvio_hip_update_rel"));
+    RCCHK(fix_ready(h, true));
+    return update_rel_dev(h, kind, gate, d_meas, meas_stride * sizeof(rvio_fix), d_age_new, d_age_old, d_active);
+}
+// host record, staged like rvio_hip_update_fix_past's: [one record | age_new | age_old | flag, each per instance]
+int rvio_hip_update_rel(rvio_hip* h, int instance, int kind, int gate, int age_new, int age_old, const rvio_fix* meas) {
+    if (!rel_args_ok(h, meas, kind, gate, instance)) return RVIO_ERR_INVALID;
+    RCCHK(fix_record_check(h, kind - RVIO_REL_POSITION, meas));
+    RCCHK(meas_guard(h, "rvio_hip_update_rel"));
+    if (age_new < 0 || age_old > h->n_clones_host) { h->err = "rvio_hip_update_rel: age_new < 0 or age_old beyond the clone window"; return RVIO_ERR_INVALID; }
+    if (age_new >= age_old) { h->err = "rvio_hip_update_rel: age_new is not below age_old (the newer frame first; one frame has no delta)"; return RVIO_ERR_INVALID; }
+    RCCHK(fix_ready(h, true));
+    HostStage& s = h->rl.stage;
+    const size_t B = (size_t)h->batch, o_new = sizeof(rvio_fix), o_old = o_new + sizeof(int32_t) * B, bytes = o_old + 2 * sizeof(int32_t) * B;
+    RCCHK(stage_acquire(h, s, bytes));
+    std::memcpy(s.pin, meas, sizeof *meas);
+    int32_t* an = (int32_t*)(s.pin + o_new);
+    int32_t* ao = (int32_t*)(s.pin + o_old);
+    for (int i = 0; i < h->batch; ++i) { an[i] = age_new; ao[i] = age_old; }
+    const int32_t* d_active;
+    RCCHK(stage_send(h, s, bytes, instance, &d_active));
+    return update_rel_dev(h, kind, gate, (const rvio_fix*)s.dev, 0, (const int32_t*)(s.dev + o_new), (const int32_t*)(s.dev + o_old), d_active);
 }
 // host arithmetic only: the age of the frame counted img_count (as rvio_odom.img_count reports it) in the window as it is now
 int rvio_hip_frame_age(rvio_hip* h, int img_count, int* age) {

@@ -34,6 +34,7 @@ SYMBOLS = [
     "rvio_standstill_config_default", "rvio_hip_set_standstill", "rvio_hip_standstill", "rvio_hip_standstill_dev", "rvio_hip_get_standstill",
     "rvio_hip_update_fix", "rvio_hip_update_fix_dev", "rvio_hip_get_fix", "rvio_hip_get_fix_rows",
     "rvio_hip_update_fix_past", "rvio_hip_update_fix_past_dev", "rvio_hip_frame_age",
+    "rvio_hip_update_rel", "rvio_hip_update_rel_dev",
 ]
 
 _LIB = None
@@ -636,3 +637,15 @@ class RvioHip:
         a = C.c_int(0)
         self._ck(self.L.rvio_hip_frame_age(self.h, int(img_count), C.byref(a)), "frame_age")
         return a.value
+
+    # ---- relative-pose measurements between two frames of the window (csrc/rel_rows.hip in front of the auxiliary update)
+    def update_rel(self, kind, meas, age_new, age_old, gate=0, instance=-1):
+        """fuse one abi.rvio_fix (host record) of kind abi.RVIO_REL_*: the delta pose between the frames age_old and age_new < age_old images
+        back from the newest composed frame; instance: 0 .. B - 1, or -1 = every instance.  Asynchronous."""
+        self._ck(self.L.rvio_hip_update_rel(self.h, int(instance), int(kind), int(gate), int(age_new), int(age_old),
+                                            C.byref(meas) if meas is not None else None), "update_rel")
+
+    def update_rel_dev(self, kind, gate, d_meas_ptr, meas_stride, d_age_new_ptr, d_age_old_ptr, d_active_ptr=None):
+        """the same on device records: d_age_new / d_age_old one int32 per instance"""
+        self._ck(self.L.rvio_hip_update_rel_dev(self.h, int(kind), int(gate), C.c_void_p(d_meas_ptr), C.c_size_t(int(meas_stride)), C.c_void_p(d_age_new_ptr),
+                                                C.c_void_p(d_age_old_ptr), C.c_void_p(d_active_ptr) if d_active_ptr else None), "update_rel_dev")
