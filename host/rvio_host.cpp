@@ -619,6 +619,82 @@ bool read_rels(const std::string& path, std::vector<RelRow>* out, std::string* e
     return parse_rels(ss.str(), path, out, err);
 }
 
+// ---- map landmarks (rvio_hip_update_map): pixel observations of known world points at the image they were matched in
+MapAge resolve_map_age(const std::vector<double>& stamps, double t) {
+    MapAge r;
+    if (stamps.empty()) return r;
+    const FixAge a = resolve_fix_age(stamps, t, false);
+    if (a.where == FIX_AGE_TOO_OLD) return r;
+    r.ok = true;
+    r.age = a.where == FIX_AGE_NOW ? 0 : a.age;
+    return r;
+}
+std::vector<std::pair<int, int>> map_calls(int n) {
+    std::vector<std::pair<int, int>> out;
+    for (int first = 0; first < n; first += RVIO_MAP_MAX_POINTS) out.emplace_back(first, std::min(RVIO_MAP_MAX_POINTS, n - first));
+    return out;
+}
+int System::map_points_at(double t, const rvio_map_obs* pts, int n, int units, bool gate_each) {
+    if (!h_ || !ready_) { err_ = "System::map_points_at before the filter is initialised"; return -1; }
+    if (!pts || n < 1) { err_ = "System::map_points_at: no observations"; return -1; }
+    const MapAge w = resolve_map_age(std::vector<double>(stamps_.begin(), stamps_.end()), t);
+    if (!w.ok) { mp_skipped_.push_back(t); return 0; }
+    for (const std::pair<int, int>& c : map_calls(n))
+        if (rvio_hip_update_map(h_, -1, units, 0, gate_each ? 1 : 0, w.age, c.second, pts + c.first) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+    return 0;
+}
+void System::queue_map(std::vector<MapRow> rows, int units, double latency, bool gate_each) {
+    std::stable_sort(rows.begin(), rows.end(), [](const MapRow& a, const MapRow& b) { return a.t < b.t; });
+    mp_rows_ = std::move(rows); mp_next_ = 0; mp_units_ = units; mp_latency_ = latency > 0 ? latency : 0.0; mp_gate_ = gate_each; mp_groups_ = 0; mp_skipped_.clear();
+}
+// behind the frame stamped t: every queued group whose stamp + latency that frame has reached, fused at the group's own stamp
+int System::apply_map(double t) {
+    while (mp_next_ < mp_rows_.size() && mp_rows_[mp_next_].t + mp_latency_ <= t) {
+        const double tg = mp_rows_[mp_next_].t;
+        std::vector<rvio_map_obs> pts;
+        for (; mp_next_ < mp_rows_.size() && mp_rows_[mp_next_].t == tg; ++mp_next_) pts.push_back(mp_rows_[mp_next_].obs);
+        ++mp_groups_;
+        if (map_points_at(tg, pts.data(), (int)pts.size(), mp_units_, mp_gate_) < 0) return -1;
+    }
+    return 0;
+}
+bool parse_map(const std::string& text, const std::string& name, std::vector<MapRow>* out, std::string* err) {
+    out->clear();
+    std::istringstream in(text);
+    std::string line;
+    for (long ln = 1; std::getline(in, line); ++ln) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        const size_t b = line.find_first_not_of(" \t");
+        if (b == std::string::npos || line[b] == '#') continue;
+        auto bad = [&](const std::string& why) { *err = name + ":" + std::to_string(ln) + ": " + why + ": " + line; return false; };
+        std::string flat = line;
+        std::replace(flat.begin(), flat.end(), ',', ' ');
+        std::istringstream ls(flat);
+        std::vector<double> v;
+        for (std::string w; ls >> w;) {
+            char* end = nullptr;
+            const double x = std::strtod(w.c_str(), &end);
+            if (end == w.c_str() || *end != 0 || !std::isfinite(x)) return bad("'" + w + "' is not a finite number");
+            v.push_back(x);
+        }
+        if (v.size() != 7) return bad("not `t x y z u v sigma`, the line holds " + std::to_string(v.size()) + " fields");
+        if (!(v[6] > 0)) return bad("sigma is not > 0");
+        MapRow r;
+        r.t = v[0];
+        for (int i = 0; i < 3; ++i) r.obs.p_w[i] = v[1 + i];
+        r.obs.uv[0] = v[4]; r.obs.uv[1] = v[5]; r.obs.sigma = v[6];
+        out->push_back(r);
+    }
+    return true;
+}
+bool read_map(const std::string& path, std::vector<MapRow>* out, std::string* err) {
+    std::ifstream f(path);
+    if (!f) { *err = "cannot read " + path; return false; }
+    std::stringstream ss;
+    ss << f.rdbuf();
+    return parse_map(ss.str(), path, out, err);
+}
+
 // behind a frame: the decision and, where the platform stands still, the zero-velocity update — on the device, nothing waited for unless the
 // records are asked for
 int System::standstill(double t, const rvio_imu* imu, int m) {
@@ -718,6 +794,7 @@ int System::MonoVIO(PoseLine* pose) {
         if (ss_on_ && standstill(image.t, pi, m) < 0) return -1;   // (ahead of the pose read-back: the pose line is the updated state's)
         if (fx_next_ < fx_rows_.size() && apply_fixes(image.t) < 0) return -1;   // (likewise)
         if (rl_next_ < rl_rows_.size() && apply_rels(image.t) < 0) return -1;    // (likewise)
+        if (mp_next_ < mp_rows_.size() && apply_map(image.t) < 0) return -1;     // (likewise)
         if (pose) {
             pose->t = image.t;
             if (rvio_hip_get_pose(h_, pose->p, pose->q) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
@@ -742,6 +819,7 @@ int System::MonoVIO(PoseLine* pose) {
     if (ss_on_ && standstill(image.t, pi, m) < 0) return -1;
     if (fx_next_ < fx_rows_.size() && apply_fixes(image.t) < 0) return -1;
     if (rl_next_ < rl_rows_.size() && apply_rels(image.t) < 0) return -1;
+    if (mp_next_ < mp_rows_.size() && apply_map(image.t) < 0) return -1;
     PoseLine pl;
     pl.t = image.t;
     if (rvio_hip_get_pose(h_, pl.p, pl.q) != RVIO_OK) return fail();                      // (waits for the filter stream)

@@ -127,6 +127,23 @@ bool read_rels(const std::string& path, std::vector<RelRow>* out, std::string* e
 struct RelSpan { bool ok = false; int age_new = 0, age_old = 0; };
 RelSpan resolve_rel_span(const std::vector<double>& stamps, double t_new, double t_old);
 
+// one line of a --map file: the observation of a known world point in the image stamped t (rvio_hip_update_map)
+struct MapRow { double t = 0; rvio_map_obs obs{}; };
+// A map file is text like a fix file, one observation per line:
+//     t x y z u v sigma
+// t: the stamp of the image the match was made in; x y z: the point in the filter's world frame (anchored at the first IMU frame and, with
+// Initialization.EnableAlignment, turned to be gravity-aligned — the frame of the pose line: aligning a map frame to it is the caller's job); u v: the observation, raw pixels or undistorted normalised coordinates (rvio_replay --map-units); sigma > 0 in the units
+// of u v.  Lines of one stamp form a group, fused together.  A malformed line is an error that names the line.
+bool parse_map(const std::string& text, const std::string& name, std::vector<MapRow>* out, std::string* err);
+bool read_map(const std::string& path, std::vector<MapRow>* out, std::string* err);
+// Which frame of the window a stamp means (stamps newest first, as for resolve_fix_age): the NEAREST frame — exact for a match made in an image,
+// which is what a map observation is; at or past the newest composed image: that image (age 0).  ok = false — the group is skipped — when the
+// stamp is older than the window, and when nothing is composed yet
+struct MapAge { bool ok = false; int age = 0; };
+MapAge resolve_map_age(const std::vector<double>& stamps, double t);
+// (first, count) of the successive calls n points are fused in: RVIO_MAP_MAX_POINTS per call, the rest in the last one
+std::vector<std::pair<int, int>> map_calls(int n);
+
 class System {
 public:
     System(const Settings& s, int device);
@@ -226,6 +243,21 @@ public:
     // that frame's pose read-back.  Rows are sorted by t_new
     void queue_rels(std::vector<RelRow> rows, bool gate);
     long rels_applied() const { return (long)rl_next_; }
+    // Map landmarks (rvio_hip_update_map): n observations of known world points made in the image stamped t, on the clock of the image stamps —
+    // a surveyed marker, a fiducial's corners, 2D-3D matches against a prior map — linearised on the device against the camera pose the window
+    // holds for the NEAREST frame (resolve_map_age above); gate_each: every point behind its own 95 % chi-square gate (no stack gate).  The gate
+    // protects a consistent filter from wrong matches; a filter that has drifted further than its covariance admits refuses correct matches
+    // too, and a caller who trusts the matches (a relocalisation) switches it off.  More
+    // than RVIO_MAP_MAX_POINTS points are fused in successive calls (map_calls): sequential updates of independent measurements are valid.  A
+    // stamp older than the window is skipped and counted (maps_skipped, and the stamps themselves in map_skipped_stamps).  units: RVIO_MAP_*.
+    // 0, or -1 with error().
+    int map_points_at(double t, const rvio_map_obs* pts, int n, int units, bool gate_each = true);
+    long maps_skipped() const { return (long)mp_skipped_.size(); }
+    const std::vector<double>& map_skipped_stamps() const { return mp_skipped_; }
+    // observations with time stamps (rvio_replay --map): MonoVIO fuses each group of one stamp behind the first frame whose image stamp is >= its
+    // t + latency (matches arrive late: latency >= 0 seconds), AT ITS OWN t.  Rows are sorted by t.  gate_each as above (rvio_replay --map-gate)
+    void queue_map(std::vector<MapRow> rows, int units, double latency, bool gate_each);
+    long map_groups_applied() const { return mp_groups_; }
     // columns of an auxiliary H right now: 24 + 6 clones, the clones counted as the library counts them (one per frame behind the first, up
     // to Tracker.nMaxTrackingLength - 1) — no read-back
     int state_dim() const;
@@ -282,6 +314,14 @@ private:
     bool rl_gate_ = false;
     long rl_dropped_ = 0;         // pairs the window no longer holds, or that fall onto one frame
     int apply_rels(double t);
+    std::vector<MapRow> mp_rows_; // queue_map, sorted by t
+    size_t mp_next_ = 0;          // the first row not yet handed on
+    int mp_units_ = RVIO_MAP_NORMALISED;
+    double mp_latency_ = 0.0;
+    bool mp_gate_ = false;
+    long mp_groups_ = 0;          // groups handed to map_points_at
+    std::vector<double> mp_skipped_;   // stamps of the groups the window no longer held
+    int apply_map(double t);
 };
 
 // 8- or 16-bit PNG (non-interlaced; gray, RGB or RGBA: channels in file order = RGB) or binary PGM / PPM (P5 / P6; maxval 255: 8 bits, 256 ..

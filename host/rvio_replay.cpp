@@ -37,11 +37,22 @@
 //                                        rvio_hip_update_rel) behind the first frame whose image stamp is >= t_new, between the two frames of the clone
 //                                        window nearest to its stamps; a row whose older stamp has left the window, or whose stamps fall onto one frame,
 //                                        is dropped and counted.  --rel-gate: the 95 % chi-square gate.  A malformed line is an error that names the line
+//                                        [--map FILE [--map-units px|norm] [--map-latency S] [--map-gate]]
+//                                        --map: observations of known world points, one per line `t x y z u v sigma` (rvio_host.hpp parse_map: the
+//                                        point in the filter's world frame, seen at (u, v) in the image stamped t), grouped by stamp; each group is
+//                                        linearised and fused on the device (System::map_points_at -> rvio_hip_update_map, more than 8 points in
+//                                        successive calls; --map-gate: every point behind its own 95 % chi-square gate, off by default like --fix-gate) behind the first frame whose image stamp is >=
+//                                        t + S (--map-latency, default 0: matches arrive late), at the frame of the window nearest to t.  A stamp
+//                                        older than the window is reported and skipped.  --map-units: px (raw pixels, the default) or norm
+//                                        (undistorted normalised coordinates)
 //   rvio_replay --check-settings <settings.yaml>        print the parsed configuration (no GPU needed)
 //   rvio_replay --check-fix <fixes.txt>                 print the parsed fix file, one JSON object per fix (no GPU needed)
 //   rvio_replay --check-fix-age <t0,t1,..> <t> [nearest] where a fix stamped t falls among the window's image stamps, newest first (no GPU needed)
 //   rvio_replay --check-rel <rels.txt>                  print the parsed rel file, one JSON object per measurement (no GPU needed)
 //   rvio_replay --check-rel-span <t0,t1,..> <t_new> <t_old>   which two frames of the window a pair of stamps means, stamps newest first (no GPU needed)
+//   rvio_replay --check-map <map.txt>                   print the parsed map file, one JSON object per observation (no GPU needed)
+//   rvio_replay --check-map-age <t0,t1,..> <t>          which frame of the window a map stamp means, stamps newest first (no GPU needed)
+//   rvio_replay --check-map-split <n>                   the successive calls n points are fused in (no GPU needed)
 //   rvio_replay --check-dataset <asl_root>              print what the dataset reader found (no GPU needed)
 //   rvio_replay --check-image <file.png|.pgm>           decode one image and print its size and checksum (no GPU needed)
 #include <dlfcn.h>
@@ -161,10 +172,32 @@ static std::vector<double> stamp_list(const char* list) {
     for (char* end = nullptr;; p = end) { const double v = std::strtod(p, &end); if (end == p) break; stamps.push_back(v); }
     return stamps;
 }
+// ---------------------------------------------------------------- --map
+static int check_map(const char* path) {
+    std::vector<MapRow> rows; std::string err;
+    if (!read_map(path, &rows, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
+    for (const MapRow& r : rows)
+        std::printf("{\"t\": %.17g, \"p_w\": [%.17g, %.17g, %.17g], \"uv\": [%.17g, %.17g], \"sigma\": %.17g}\n", r.t, r.obs.p_w[0], r.obs.p_w[1], r.obs.p_w[2],
+                    r.obs.uv[0], r.obs.uv[1], r.obs.sigma);
+    return 0;
+}
+static int check_map_split(const char* n) {
+    std::printf("[");
+    bool first = true;
+    for (const std::pair<int, int>& c : map_calls(std::atoi(n))) { std::printf("%s[%d, %d]", first ? "" : ", ", c.first, c.second); first = false; }
+    std::printf("]\n");
+    return 0;
+}
 // --check-rel-span: resolve_rel_span on stamps given newest first
 static int check_rel_span(const char* list, const char* t_new, const char* t_old) {
     const RelSpan w = resolve_rel_span(stamp_list(list), std::atof(t_new), std::atof(t_old));
     std::printf("{\"ok\": %d, \"age_new\": %d, \"age_old\": %d}\n", w.ok ? 1 : 0, w.age_new, w.age_old);
+    return 0;
+}
+// --check-map-age: resolve_map_age on stamps given newest first
+static int check_map_age(const char* list, const char* t) {
+    const MapAge w = resolve_map_age(stamp_list(list), std::atof(t));
+    std::printf("{\"ok\": %d, \"age\": %d}\n", w.ok ? 1 : 0, w.age);
     return 0;
 }
 // --fix-latency: seconds, finite and >= 0
@@ -245,6 +278,10 @@ struct PassOptions {
     double fix_latency = -1.0;           // --fix-latency (< 0: not given)
     const std::vector<RelRow>* rels = nullptr;    // --rel
     bool rel_gate = false;
+    const std::vector<MapRow>* maps = nullptr;    // --map
+    int map_units = RVIO_MAP_PIXELS;
+    double map_latency = 0.0;
+    bool map_gate = false;
 };
 static bool dump_frame(System& sys, const rvio_config& c, FrameDump* d) {
     rvio_hip* h = sys.handle();
@@ -267,6 +304,7 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
     if (o.imu_odometry && !sys.record_imu_odometry_to(o.imu_odometry, o.imu_odometry_ring, o.imu_odometry_cov)) { *err = sys.error(); return 1; }
     if (o.fixes) sys.queue_fixes(*o.fixes, o.fix_gate, o.fix_latency);
     if (o.rels) sys.queue_rels(*o.rels, o.rel_gate);
+    if (o.maps) sys.queue_map(*o.maps, o.map_units, o.map_latency, o.map_gate);
     size_t ii = 0;
     long n_images = 0, n_frames = 0;
     double t_filter = 0;
@@ -381,6 +419,9 @@ int main(int argc, char** argv) {
     if (argc >= 4 && !std::strcmp(argv[1], "--check-fix-age")) return check_fix_age(argv[2], argv[3], argc >= 5 && !std::strcmp(argv[4], "nearest"));
     if (argc >= 3 && !std::strcmp(argv[1], "--check-rel")) return check_rel(argv[2]);
     if (argc >= 5 && !std::strcmp(argv[1], "--check-rel-span")) return check_rel_span(argv[2], argv[3], argv[4]);
+    if (argc >= 3 && !std::strcmp(argv[1], "--check-map")) return check_map(argv[2]);
+    if (argc >= 4 && !std::strcmp(argv[1], "--check-map-age")) return check_map_age(argv[2], argv[3]);
+    if (argc >= 3 && !std::strcmp(argv[1], "--check-map-split")) return check_map_split(argv[2]);
     if (argc >= 3 && !std::strcmp(argv[1], "--check-image")) {   // --check-image FILE [--bgr] [--encoding NAME]
         bool rgb = true; const char* enc = nullptr;
         for (int i = 3; i < argc; ++i) {
@@ -393,7 +434,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "usage: %s <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--record-dir DIR] [--record]\n"
                              "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--imu-odometry-cov] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n"
                              "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate] [--standstill FILE] [--fix FILE] [--fix-gate] [--fix-latency S]\n"
-                             "          [--rel FILE] [--rel-gate]\n", argv[0]);
+                             "          [--rel FILE] [--rel-gate] [--map FILE] [--map-units px|norm] [--map-latency S] [--map-gate]\n", argv[0]);
         return 2;
     }
     const char* out_path = nullptr;
@@ -405,6 +446,7 @@ int main(int argc, char** argv) {
     const char* standstill = nullptr;
     const char* fix = nullptr; bool fix_gate = false; double fix_latency = -1.0;
     const char* rel = nullptr; bool rel_gate = false;
+    const char* map = nullptr; int map_units = RVIO_MAP_PIXELS; double map_latency = 0.0; bool map_gate = false;
     const char* record_dir = "."; bool force_record = false, sync_every = false, self = false; int noise_wgs = 0;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -433,6 +475,19 @@ int main(int argc, char** argv) {
         }
         else if (!std::strcmp(argv[i], "--rel") && i + 1 < argc) rel = argv[++i];   // `t_new t_old kind values... sigmas... [lever]` lines fused behind the first frame at or past t_new (System::update_rel_at)
         else if (!std::strcmp(argv[i], "--rel-gate")) rel_gate = true;
+        else if (!std::strcmp(argv[i], "--map") && i + 1 < argc) map = argv[++i];   // `t x y z u v sigma` lines, grouped by stamp, fused at the frame nearest to t (System::map_points_at)
+        else if (!std::strcmp(argv[i], "--map-gate")) map_gate = true;
+        else if (!std::strcmp(argv[i], "--map-units") && i + 1 < argc) {
+            ++i;
+            if (!std::strcmp(argv[i], "px")) map_units = RVIO_MAP_PIXELS;
+            else if (!std::strcmp(argv[i], "norm")) map_units = RVIO_MAP_NORMALISED;
+            else { std::fprintf(stderr, "--map-units takes px or norm, not '%s'\n", argv[i]); return 1; }
+        }
+        else if (!std::strcmp(argv[i], "--map-latency") && i + 1 < argc) {
+            char* end = nullptr;
+            map_latency = std::strtod(argv[++i], &end);
+            if (end == argv[i] || *end != 0 || !std::isfinite(map_latency) || map_latency < 0) { std::fprintf(stderr, "--map-latency takes a finite number >= 0, not '%s'\n", argv[i]); return 1; }
+        }
         else out_path = argv[i];
     }
     if (fix_latency >= 0 && !fix) { std::fprintf(stderr, "--fix-latency needs --fix FILE\n"); return 1; }
@@ -459,11 +514,16 @@ int main(int argc, char** argv) {
         if (self) { std::fprintf(stderr, "--rel and --selfcheck do not combine\n"); return 1; }
         if (!read_rels(rel, &rels, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
     }
+    std::vector<MapRow> maps;
+    if (map) {
+        if (self) { std::fprintf(stderr, "--map and --selfcheck do not combine\n"); return 1; }
+        if (!read_map(map, &maps, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
+    }
     print_runtime();
     if (self) return selfcheck(s, d, device, max_frames, stall_seed, noise_wgs);
     if (sync_every || stall_seed >= 0 || noise_wgs > 0) {   // the plain replay with one of the two A/B pacings
         std::vector<PoseLine> poses; double ms = 0; int flags = 0;
-        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.imu_odometry_cov = imu_odometry_cov; o.velocity = vr; if (fix) { o.fixes = &fixes; o.fix_gate = fix_gate; o.fix_latency = fix_latency; } if (rel) { o.rels = &rels; o.rel_gate = rel_gate; }
+        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.imu_odometry_cov = imu_odometry_cov; o.velocity = vr; if (fix) { o.fixes = &fixes; o.fix_gate = fix_gate; o.fix_latency = fix_latency; } if (rel) { o.rels = &rels; o.rel_gate = rel_gate; } if (map) { o.maps = &maps; o.map_units = map_units; o.map_latency = map_latency; o.map_gate = map_gate; }
         if (run_pass(s, d, device, o, &poses, nullptr, &ms, &flags, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
         if (out_path) { std::ofstream out(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } for (const PoseLine& p : poses) out << format_pose(p); }
         std::fprintf(stderr, "rvio_replay: %zu filtered frames, %.3f ms per MonoVIO call, device flags %d\n", poses.size(), ms, flags);
@@ -479,6 +539,7 @@ int main(int argc, char** argv) {
     if (standstill && !sys.record_standstill_to(standstill)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (fix) sys.queue_fixes(fixes, fix_gate, fix_latency);
     if (rel) sys.queue_rels(rels, rel_gate);
+    if (map) sys.queue_map(maps, map_units, map_latency, map_gate);
     std::ofstream out;
     if (out_path) { out.open(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } }
 
@@ -512,6 +573,11 @@ int main(int argc, char** argv) {
     if (fix && fix_latency < 0) std::fprintf(stderr, "rvio_replay: fix: %zu rows, %ld applied\n", fixes.size(), sys.fixes_applied());
     if (fix && fix_latency >= 0) std::fprintf(stderr, "rvio_replay: fix: %zu rows, %ld fused, %ld older than the window and dropped (latency %g s)\n", fixes.size(), sys.fixes_applied() - sys.fixes_dropped(), sys.fixes_dropped(), fix_latency);
     if (rel) std::fprintf(stderr, "rvio_replay: rel: %zu rows, %ld fused, %ld outside the window or on one frame and dropped\n", rels.size(), sys.rels_applied() - sys.rels_dropped(), sys.rels_dropped());
+    if (map) {
+        for (double t : sys.map_skipped_stamps()) std::fprintf(stderr, "rvio_replay: map: the group stamped %.9f is older than the clone window: skipped\n", t);
+        std::fprintf(stderr, "rvio_replay: map: %zu rows, %ld groups, %ld applied, %ld outside the window and skipped\n", maps.size(), sys.map_groups_applied(),
+                     sys.map_groups_applied() - sys.maps_skipped(), sys.maps_skipped());
+    }
     // anything only the device saw (0 in every test and bench run): said out loud, the poses above are suspect if it is not 0
     const int flags = sys.device_flags();
     if (flags) std::fprintf(stderr, "rvio_replay: DEVICE-SIDE FLAGS %d (1 singular pivot in the solve, 2 a track the window cannot hold was dropped, "

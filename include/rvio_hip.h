@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov); standstill detection (rvio_standstill_config, rvio_standstill, rvio_standstill_config_default, rvio_hip_set_standstill, rvio_hip_standstill, rvio_hip_standstill_dev, rvio_hip_get_standstill); absolute fixes (rvio_fix_kind, rvio_fix, rvio_fix_diag, rvio_hip_update_fix, rvio_hip_update_fix_dev, rvio_hip_get_fix, rvio_hip_get_fix_rows); past-frame fixes (rvio_hip_update_fix_past, rvio_hip_update_fix_past_dev, rvio_hip_frame_age); relative-pose measurements (rvio_rel_kind, rvio_hip_update_rel, rvio_hip_update_rel_dev) */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov); standstill detection (rvio_standstill_config, rvio_standstill, rvio_standstill_config_default, rvio_hip_set_standstill, rvio_hip_standstill, rvio_hip_standstill_dev, rvio_hip_get_standstill); absolute fixes (rvio_fix_kind, rvio_fix, rvio_fix_diag, rvio_hip_update_fix, rvio_hip_update_fix_dev, rvio_hip_get_fix, rvio_hip_get_fix_rows); past-frame fixes (rvio_hip_update_fix_past, rvio_hip_update_fix_past_dev, rvio_hip_frame_age); relative-pose measurements (rvio_rel_kind, rvio_hip_update_rel, rvio_hip_update_rel_dev); map landmarks (rvio_map_units, rvio_map_obs, rvio_map_point, rvio_map_diag, rvio_hip_update_map, rvio_hip_update_map_dev, rvio_hip_get_map, rvio_hip_get_map_rows) */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -734,6 +734,73 @@ typedef enum { RVIO_REL_POSITION = 16, RVIO_REL_ATTITUDE = 17, RVIO_REL_POSE = 1
 int rvio_hip_update_rel(rvio_hip* h, int instance, int kind, int gate, int age_new, int age_old, const rvio_fix* meas);
 int rvio_hip_update_rel_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_meas, size_t meas_stride, const int32_t* d_age_new,
                             const int32_t* d_age_old, const int32_t* d_active);
+
+/* --- map landmarks: pixel observations of KNOWN world points (no reference counterpart) ------------------------------------------ */
+/* What a localisation user has is the observation of a known world point in an image: a surveyed marker corner, a fiducial's corners, a 2D-3D
+ * match against a prior map.  Run through PnP on the host and handed over as RVIO_FIX_POSE, every point's information is squeezed through six
+ * numbers with an invented covariance, and one wrong match poisons the whole pose.  The raw measurement is the pixel, and the handle owns what
+ * linearises it: the instance's calibration, the tracker's undistortion and the chain of relative poses rvio_hip_update_fix_past walks, which
+ * gives the camera pose AT THE IMAGE THE MATCH WAS MADE IN (matches always arrive late).  map_rows_kernel (csrc/map_rows.hip, one workgroup of
+ * four waves per instance) forms two rows per point and a chi-square gate PER POINT against P as the call finds it; aux_update_kernel,
+ * unchanged, runs right behind in RVIO_AUX_RESIDUAL mode with m = 2 n_max rows.
+ * Frames and conventions are those of rvio_hip_update_fix_past: clone i holds (q_i, p_i), C_i = R(q_i); the age a = 0 .. n counts images back
+ * from {R};  A_0 = I, t_0 = 0;  A_m = A_{m-1} C_{n-m},  t_m = t_{m-1} - A_m p_{n-m}.  With R_G = R(x[0:4]), pG = x[4:7], the world point
+ * f = p_w and the instance's calibration (Rci, tci):
+ *   w   = R_G f + pG                      the point in {R}
+ *   p_I = A_a^T (w - t_a)                 in the IMU frame at the image `a` back
+ *   p_C = Rci p_I + tci,  depth = p_C.z
+ *   h   = (p_C.x / depth, p_C.y / depth)  normalised image coordinates
+ *   r   = uv_n - h
+ * With J = (1 / depth) [1 0 -h.x; 0 1 -h.y] and M = J Rci A_a^T (2 x 3) the two rows of a point are, under R_true ~ (I - [dth x]) R:
+ *   cols 0-2 : M [(R_G f) x]          cols 3-5 : M
+ *   clone i = n - m (m = 1 .. a):   24+6i.. (rotation): -M [(w - t_{m-1}) x] A_{m-1}     27+6i.. (position): M A_m
+ * Every other column is exactly 0.0: columns 6 - 23 and every clone older than n - a.  (Held to central differences of h through the state
+ * injection in tests/test_map_abi.py.)
+ * units: RVIO_MAP_NORMALISED — uv holds undistorted normalised coordinates and both rows get sigma;  RVIO_MAP_PIXELS — uv holds raw pixels,
+ * which the device casts to float and undistorts under the instance's calibration exactly as it does a tracked feature; the rows get
+ * sigma / |fx| and sigma / |fy|.
+ * Rows of a launch: slot j of an instance owns rows 2j and 2j + 1 of an m = 2 n_max stack (host form: n_max = n_obs).  A slot that is not used —
+ * at or beyond the instance's count, rejected, gated out — has H = 0.0, r = 0.0, sigma = 1.0 in its rows: after whitening they are zero, S has a
+ * unit diagonal there and they move nothing, so the update equals that of the compacted stack.
+ * status of a slot (rvio_map_point): 0 used;  1 gated out;  2 rejected: depth < 0.1 m (csrc/launch_plan.h LP_MAP_MIN_DEPTH — a tuning value,
+ * not a measurement), or a projection, residual or sigma that is not finite (a sigma not > 0 included);  3 empty slot.
+ * gate_each = 1, the per-point gate: gamma_j = r~_j^T (H~_j P H~_j^T + I_2)^-1 r~_j on the whitened rows of slot j, kept iff
+ * |gamma_j| < chi2inv(0.95, 2) — the table entry and the comparison of the feature gate; a non-positive pivot of the 2 x 2 refuses the slot
+ * with status 1.  Every slot is gated independently against P as the call finds it.  With gate_each = 0, gamma_j is computed and reported all
+ * the same.  gate = 1 is the stack gate of rvio_hip_update_aux against chi2inv(0.95, m): it counts the zeroed rows as degrees of freedom, so it
+ * is LOOSER than nominal when slots are empty or refused, and one wrong match refuses the whole stack — prefer gate_each.
+ * The kernel keeps an active flag per instance: the caller's flag AND the age inside 0 .. n AND at least one used slot; the update runs on that.
+ * An instance with flag 0 is written by neither launch and its record says why: m = 0, applied = 0, and img_count = -1 for an age outside the
+ * window (every slot then reads 3), n_used = 0 when every point was refused.  The host form's age holds for every instance the call touches,
+ * like that of rvio_hip_update_fix_past.  _dev form: instance z reads d_obs + z * obs_stride records (0: shared), d_count[z] of them (NULL:
+ * n_max each; clamped to 0 .. n_max) at the age d_age[z]; nothing on the device is checked by the host.
+ * rvio_hip_get_map: the record and, if pts is not NULL, the RVIO_MAP_MAX_POINTS slot records of one instance from the last map call; gamma /
+ * applied are those of the stack update.  rvio_hip_get_map_rows: m, d and (each may be NULL) the m x d rows, r and sigma as the device formed
+ * them.  Both wait for the filter stream only.
+ * Everything rvio_hip_update_aux_dev documents holds: in place, the pose line rewritten, no ring record, a kept clone-block factor dropped,
+ * error bit 8 on a non-positive pivot of S.  The first call allocates the block of these calls outside the filter slab — rows at 16 x d_max per
+ * instance, r, sigma, the records, the (gamma, applied) pairs, flags, staging; it is separate from the fix block: rvio_hip_get_fix* keep
+ * reporting the last fix-family call.  A handle that never calls these allocates and launches what it did before.  Plain, batch and sharded
+ * handles; on a sharded handle every rank calls alike.
+ * RVIO_ERR_STATE as rvio_hip_update_fix.  RVIO_ERR_INVALID: a NULL handle or buffer (a NULL d_age included), n_obs / n_max outside 1 .. 8, units,
+ * gate or gate_each outside their values, an instance out of range, an obs_stride below n_max unless it is 0, a window longer than the chain the
+ * kernel holds and — host form only — a member that is not finite, sigma <= 0, an age outside 0 .. n (rvio_hip_last_error names the cause).
+ * NOT done: iterated updates; estimating the camera-IMU extrinsic or a time offset; points whose world position is itself uncertain (a
+ * per-point 3 x 3 prior); interpolation between frames; more than 8 points per launch (call again: sequential updates of independent
+ * measurements are valid); alignment of a map frame to the filter's world frame — the frame of the pose line: anchored at the first IMU frame and, with
+ * ini_enable_alignment, turned so that its z axis is the accelerometer's direction at rest — which is the caller's job, as for fixes.  Note on
+ * gate_each: the gate is formed against P; a filter whose covariance does not admit its own drift refuses correct matches too (status 1,
+ * n_used = 0), and a caller who trusts the matches — a relocalisation — calls with gate_each = 0. */
+#define RVIO_MAP_MAX_POINTS 8                 /* 2 rows each = RVIO_AUX_MAX_ROWS */
+typedef enum { RVIO_MAP_NORMALISED = 0, RVIO_MAP_PIXELS = 1 } rvio_map_units;
+typedef struct rvio_map_obs { double p_w[3]; double uv[2]; double sigma; } rvio_map_obs;                                                  /* 48 B */
+typedef struct rvio_map_point { double r[2]; double gamma; double depth; int32_t status, reserved; } rvio_map_point;                      /* 40 B */
+typedef struct rvio_map_diag { double gamma; int32_t applied, m, n_used, n_obs, img_count, reserved; } rvio_map_diag;                     /* 32 B */
+int rvio_hip_update_map(rvio_hip* h, int instance, int units, int gate, int gate_each, int age, int n_obs, const rvio_map_obs* obs);
+int rvio_hip_update_map_dev(rvio_hip* h, int units, int gate, int gate_each, int n_max, const rvio_map_obs* d_obs, size_t obs_stride,
+                            const int32_t* d_count, const int32_t* d_age, const int32_t* d_active);
+int rvio_hip_get_map(rvio_hip* h, int instance, rvio_map_diag* out, rvio_map_point* pts);
+int rvio_hip_get_map_rows(rvio_hip* h, int instance, int32_t* m, int32_t* d, double* H, double* r, double* sigma);
 
 /* --- feature-sharded updater (no reference counterpart) ------ */
 /* Stage A: per-feature build + gate on the features f with f % world == rank,

@@ -685,6 +685,113 @@ def rel_model(x, kind, meas, age_new, age_old):
     return np.vstack(rows_H), np.concatenate(rows_r), np.concatenate(rows_s)
 
 
+# ---- map landmarks: pixel observations of known world points (rvio_hip_update_map*, csrc/map_rows.hip in front of the auxiliary update)
+RVIO_MAP_NORMALISED, RVIO_MAP_PIXELS = 0, 1
+RVIO_MAP_MAX_POINTS = 8
+MAP_USED, MAP_GATED, MAP_REJECTED, MAP_EMPTY = 0, 1, 2, 3
+MAP_MIN_DEPTH = 0.1            # LP_MAP_MIN_DEPTH of csrc/launch_plan.h: a tuning value, not a measurement
+MAP_CHI2_95_2 = 5.991465       # chi2inv(0.95, 2) as csrc/chi2_table.inc holds it (6 decimals): the per-point gate
+
+
+class rvio_map_obs(C.Structure):
+    """one observation of a known world point: 48 bytes, no padding.  p_w: the point in the filter's world frame; uv: normalised coordinates or
+    raw pixels (units); sigma: of uv, in its units"""
+    _fields_ = [("p_w", C.c_double * 3), ("uv", C.c_double * 2), ("sigma", C.c_double)]
+
+
+class rvio_map_point(C.Structure):
+    """what became of one slot: 40 bytes, no padding.  status: 0 used, 1 gated out, 2 rejected, 3 empty slot"""
+    _fields_ = [("r", C.c_double * 2), ("gamma", C.c_double), ("depth", C.c_double), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class rvio_map_diag(C.Structure):
+    """the record of one instance from the last map call: 32 bytes, no padding"""
+    _fields_ = [("gamma", C.c_double), ("applied", C.c_int32), ("m", C.c_int32), ("n_used", C.c_int32), ("n_obs", C.c_int32),
+                ("img_count", C.c_int32), ("reserved", C.c_int32)]
+
+
+MAP_OBS_DTYPE = np.dtype([("p_w", "f8", 3), ("uv", "f8", 2), ("sigma", "f8")])
+assert C.sizeof(rvio_map_obs) == MAP_OBS_DTYPE.itemsize == 48 and C.sizeof(rvio_map_point) == 40 and C.sizeof(rvio_map_diag) == 32
+
+
+def make_map_obs(points):
+    """a ctypes array of rvio_map_obs from (p_w, uv, sigma) triples"""
+    arr = (rvio_map_obs * len(points))()
+    for o, (p_w, uv, sigma) in zip(arr, points):
+        o.p_w[0:3] = [float(v) for v in p_w]
+        o.uv[0:2] = [float(v) for v in uv]
+        o.sigma = float(sigma)
+    return arr
+
+
+def _map_cam(cal):
+    """(Rci, tci) of anything with T_bc (rvio_config, rvio_calibration), as csrc/rvio_hip.hip fill_camcal forms them"""
+    T = np.array([float(v) for v in cal.T_bc]).reshape(4, 4)
+    Rci = T[0:3, 0:3].T.copy()
+    return Rci, -(Rci @ T[0:3, 3])
+
+
+def map_h(cal, x, age, p_w):
+    """(H [2 x d], h [2], depth) of one known world point p_w seen by the camera of calibration `cal` at the image `age` back from the state's
+    reference frame {R}: h the predicted normalised image coordinates, H its Jacobian in the error-state order of P under
+    R_true ~ (I - [dth x]) R.  The table of include/rvio_hip.h; calls nothing from the library or the oracle."""
+    x, f = np.asarray(x, float), np.asarray(p_w, float)
+    n = (len(x) - 26) // 7
+    Rci, tci = _map_cam(cal)
+    A, t = _fix_past_chain(x, age)
+    RGf = quat_to_rot(x[0:4]) @ f
+    w = RGf + x[4:7]
+    pC = Rci @ (A[age].T @ (w - t[age])) + tci
+    depth = float(pC[2])
+    with np.errstate(all="ignore"):
+        h = np.array([pC[0] / depth, pC[1] / depth])
+        M = (np.array([[1.0, 0.0, -h[0]], [0.0, 1.0, -h[1]]]) / depth) @ Rci @ A[age].T
+    H = np.zeros((2, 24 + 6 * n))
+    H[:, 0:3], H[:, 3:6] = M @ _skew(RGf), M
+    for m in range(1, age + 1):
+        c = 24 + 6 * (n - m)
+        H[:, c: c + 3], H[:, c + 3: c + 6] = -M @ _skew(w - t[m - 1]) @ A[m - 1], M @ A[m]
+    return H, h, depth
+
+
+def map_model(cal, x, P, obs, age, units, gate_each, uv_n=None):
+    """NumPy float64 model of csrc/map_rows.hip: (H [2 n x d], r [2 n], sigma [2 n], gamma [n], status [n]) of n = len(obs) <= 8 observations
+    (rvio_map_obs, or anything with p_w, uv, sigma) at the image `age` back.  PIXELS: uv_n holds the undistorted normalised coordinates of the
+    float pixels (n x 2, the tracker's undistortion: the model has none of its own) and the rows get sigma / |fx|, sigma / |fy|.  A slot that is
+    rejected (depth < MAP_MIN_DEPTH or a non-finite projection) or, with gate_each, gated out (|gamma_j| >= chi2inv(0.95, 2) against P as it
+    is, or a non-positive pivot) has H = 0, r = 0, sigma = 1 in its two rows."""
+    x, P = np.asarray(x, float), np.asarray(P, float)
+    assert units in (RVIO_MAP_NORMALISED, RVIO_MAP_PIXELS) and 1 <= len(obs) <= RVIO_MAP_MAX_POINTS
+    assert units == RVIO_MAP_NORMALISED or uv_n is not None, "PIXELS: pass the undistorted coordinates"
+    d = P.shape[0]
+    nob = len(obs)
+    H, r, sg = np.zeros((2 * nob, d)), np.zeros(2 * nob), np.ones(2 * nob)
+    gamma, status = np.zeros(nob), np.zeros(nob, int)
+    for j, o in enumerate(obs):
+        Hj, h, depth = map_h(cal, x, age, [float(v) for v in o.p_w])
+        z = np.array([float(v) for v in o.uv]) if units == RVIO_MAP_NORMALISED else np.asarray(uv_n, float).reshape(-1, 2)[j]
+        s = float(o.sigma)
+        sj = np.array([s, s]) if units == RVIO_MAP_NORMALISED else np.array([s / abs(float(cal.fx)), s / abs(float(cal.fy))])
+        rj = z - h
+        if not (np.isfinite(depth) and depth >= MAP_MIN_DEPTH and np.all(np.isfinite(h)) and np.all(np.isfinite(rj)) and np.all(sj > 0) and np.all(np.isfinite(sj))):
+            status[j] = MAP_REJECTED
+            continue
+        Hw, rw = Hj / sj[:, None], rj / sj
+        S = Hw @ P @ Hw.T + np.eye(2)
+        d0 = S[0, 0]
+        l = S[0, 1] / d0 if d0 > 0 else 0.0
+        d1 = S[1, 1] - l * S[0, 1]
+        if not (d0 > 0 and d1 > 0):
+            status[j] = MAP_GATED
+            continue
+        gamma[j] = abs(rw[0] * rw[0] / d0 + (rw[1] - l * rw[0]) ** 2 / d1)
+        if gate_each and not gamma[j] < MAP_CHI2_95_2:
+            status[j] = MAP_GATED
+            continue
+        H[2 * j: 2 * j + 2], r[2 * j: 2 * j + 2], sg[2 * j: 2 * j + 2] = Hj, rj, sj
+    return H, r, sg, gamma, status
+
+
 # Camera.T_BC0 of config/rvio_euroc.yaml:55-62 (row-major)
 _T_BC0 = [0.0148655429818, -0.999880929698, 0.00414029679422, -0.0216401454975,
           0.999557249008, 0.0149672133247, 0.025715529948, -0.064676986768,

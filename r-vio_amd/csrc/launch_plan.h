@@ -151,12 +151,36 @@ LP_HD inline size_t aux_lds_max_doubles(int nmax, int MB) {
 #define LP_FIXP_CHAIN ((LP_FIXP_NMAX + 1) * 12)
 // rel_rows_kernel (rel_rows.hip): the same wave, window limit and chain layout (LP_FIXP_T, LP_FIXP_NMAX, LP_FIXP_CHAIN) — the chain runs between two
 // frames of the window instead of from the reference frame back; its rows have no head block, so the chain is all of its static LDS
+// map_rows_kernel (map_rows.hip): ONE workgroup of four waves per instance.  Every wave forms the chain of fix_past_kernel (LP_FIXP_NMAX,
+// LP_FIXP_CHAIN); the rows of at most LP_MAP_POINTS observed points (two each: LP_MAP_ROWS = the row limit of the auxiliary update) are staged
+// TRANSPOSED in static LDS ([column][row], LP_MAP_HS doubles) for the per-point gate, whose product with P wave g forms for the g-th 64 of the
+// 6 + 6 a <= LP_MAP_NZ columns that are not zero; per slot LP_MAP_SLOT doubles of geometry and LP_MAP_WAVES x 3 partial sums.  No dynamic part.
+// LP_MAP_MIN_DEPTH (m): a point nearer to the camera plane than this, or behind it, is rejected — a tuning value, not a measurement.
+#define LP_MAP_T 256
+#define LP_MAP_WAVES (LP_MAP_T / 64)
+#define LP_MAP_POINTS 8          // RVIO_MAP_MAX_POINTS
+#define LP_MAP_ROWS (2 * LP_MAP_POINTS)
+#define LP_MAP_DMAX (24 + 6 * LP_FIXP_NMAX)
+#define LP_MAP_NZ (6 + 6 * LP_FIXP_NMAX)
+#define LP_MAP_HS (LP_MAP_DMAX * LP_MAP_ROWS)
+#define LP_MAP_SLOT 28           // head 2 x 6 (12) | M (6) | w (3) | r (2) | sigma (2) | depth | gamma | pad
+#define LP_MAP_PART (LP_MAP_WAVES * LP_MAP_POINTS * 3)
+#define LP_MAP_LDS_DOUBLES (LP_FIXP_CHAIN + LP_MAP_HS + LP_MAP_POINTS * LP_MAP_SLOT + LP_MAP_PART)
+#define LP_MAP_MIN_DEPTH 0.1
+static_assert(LP_MAP_ROWS == LP_AUX_MAX_ROWS, "a map call's rows fill one auxiliary update");
+static_assert(LP_MAP_NZ <= 64 * LP_MAP_WAVES, "one lane per non-zero column");
+// doubles between the instances' rows in the block of the map calls, and that block's bytes: rows | r | sigma | (gamma, applied) | records |
+// per-slot records | flags
+LP_HD inline size_t map_H_stride(int dmax) { return (size_t)LP_MAP_ROWS * dmax; }
+LP_HD inline size_t map_block_bytes(int batch, int dmax) {
+    return (size_t)batch * (8 * map_H_stride(dmax) + 8 * LP_MAP_ROWS + 8 * LP_MAP_ROWS + 16 + 32 + 40 * LP_MAP_POINTS + 4);
+}
 
 // ---------------------------------------------------------------- the kernels create_impl gives a dynamic-LDS limit
 enum LpKernel {
     LPK_FEAT_BUILD16, LPK_FEAT_BUILD4, LPK_GRAM_REDUCE, LPK_BLOCK_SUM, LPK_LIT_BATCH, LPK_GEMM_T_LDS, LPK_GRAM_BATCH4, LPK_GRAM_BATCH6, LPK_FEAT_PROP,
     LPK_BOOKKEEP_B, LPK_RANSAC_BOOK, LPK_SOLVE9_SMALL, LPK_SOLVE6_1, LPK_SOLVE6_2, LPK_SOLVE6_3, LPK_JOSEPH_BATCH, LPK_UG, LPK_UG_LDS, LPK_FINAL_LDS,
-    LPK_JOSEPH_LDS, LPK_IMU_POSE, LPK_AUX_UPDATE4, LPK_AUX_UPDATE16, LPK_IMU_COV, LPK_STANDSTILL, LPK_FIX, LPK_FIX_PAST, LPK_REL, LPK_COUNT
+    LPK_JOSEPH_LDS, LPK_IMU_POSE, LPK_AUX_UPDATE4, LPK_AUX_UPDATE16, LPK_IMU_COV, LPK_STANDSTILL, LPK_FIX, LPK_FIX_PAST, LPK_REL, LPK_MAP, LPK_COUNT
 };
 // (as c++filt prints them, without return type and arguments: how the test finds each kernel's static LDS in the code object's notes)
 static const char* const kLpKernelName[LPK_COUNT] = {
@@ -164,7 +188,7 @@ static const char* const kLpKernelName[LPK_COUNT] = {
     "gram_reduce_batch_kernel<4>", "gram_reduce_batch_kernel<6>", "feat_prop_kernel", "bookkeep_b_kernel", "ransac_book_kernel", "solve9_small_kernel",
     "solve6_kernel<1, 8, 8>", "solve6_kernel<2, 12, 8>", "solve6_kernel<2, 16, 8>", "joseph_batch_kernel", "ug_kernel", "ug_lds_kernel", "final_lds_kernel",
     "joseph_lds_kernel", "imu_pose_kernel", "aux_update_kernel<4>", "aux_update_kernel<16>", "imu_cov_kernel", "standstill_kernel",
-    "fix_rows_kernel", "fix_past_kernel", "rel_rows_kernel"
+    "fix_rows_kernel", "fix_past_kernel", "rel_rows_kernel", "map_rows_kernel"
 };
 
 struct LaunchPlan {
@@ -302,6 +326,8 @@ inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size
     if (statics[LPK_FIX_PAST] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
     // rel_rows_kernel: likewise (p.attr[LPK_REL] stays 0)
     if (statics[LPK_REL] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
+    // map_rows_kernel: likewise (p.attr[LPK_MAP] stays 0)
+    if (statics[LPK_MAP] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
     if (batch > 1 && !p.solve5_variant && !p.solve7_variant) { p.rc = 1; p.why = "batched filter: clone window too long for the unrolled solve kernel (6n <= 126)"; return p; }
     // nothing above may ask for more than a CU has: a configuration that would is refused here, by name, not by a failed hipFuncSetAttribute / launch
     for (int k = 0; k < LPK_COUNT; ++k)
@@ -474,6 +500,8 @@ LP_HD inline LpLaunch fix_launch(int batch) { return {1, 1, batch, LP_FIX_T, 0, 
 LP_HD inline LpLaunch fix_past_launch(int batch) { return {1, 1, batch, LP_FIXP_T, 0, LPK_FIX_PAST}; }
 // rel_rows_kernel: the same form
 LP_HD inline LpLaunch rel_launch(int batch) { return {1, 1, batch, LP_FIXP_T, 0, LPK_REL}; }
+// map_rows_kernel: one workgroup of LP_MAP_WAVES waves per instance, static LDS only
+LP_HD inline LpLaunch map_launch(int batch) { return {1, 1, batch, LP_MAP_T, 0, LPK_MAP}; }
 
 enum LpStream {          // the ROLE of a stream in a call; stream_of (rvio_hip.hip) maps it to one of the handle's four
     LPR_FILTER,          //   the filter stream: every launch of a per-stage call that is not forked to the side stream

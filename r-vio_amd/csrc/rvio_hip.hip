@@ -34,6 +34,7 @@
 #include "rel_rows.hip"    // relative poses between two frames of the window, linearised against the clones between them (rvio_hip_update_rel)
 #pragma clang fp contract(off)
 #include "frontend_kernels.hip"
+#include "map_rows.hip"    // map landmarks: pixel observations of known world points at a past image, gated per point against P (rvio_hip_update_map)
 #include "klt3.hip"
 #include "klt16.hip"
 #include "clahe.hip"
@@ -234,6 +235,11 @@ struct rvio_hip {
     // relative-pose measurements (rel_rows.hip) reuse the fix block and the kernel's flags of the past-frame fixes, and add, with the first
     // rvio_hip_update_rel call, the host form's staging (one rvio_fix; age_new, age_old and flag per instance)
     struct { HostStage stage; } rl;
+    // map landmarks (map_rows.hip): a block of their own, allocated with the first rvio_hip_update_map* call — rows (LP_MAP_ROWS x dmax per
+    // instance), r, sigma, the (gamma, applied) pairs, the records, the per-slot records, the kernel's flags — and the host form's staging
+    // (RVIO_MAP_MAX_POINTS records; age and flag per instance).  m, d: the rows of the last call, for the getters
+    struct { double* H = nullptr; double* r = nullptr; double* sigma = nullptr; double* pair = nullptr; rvio_map_diag* rec = nullptr; rvio_map_point* pts = nullptr;
+             int32_t* flag = nullptr; int m = 0, d = 0; HostStage stage; } mp;
     // colour input (rvio_hip_set_image_format): the gray images every stage behind gray_kernel reads instead of the caller's.  Allocated with the
     // first colour format, outside the slab (a mono handle keeps its memory layout), instance stride W * H; four in rotation like d_eq2[] (see
     // build_pyramid_dev for who reads a slot last)
@@ -611,6 +617,7 @@ static const void* lp_kernel_fn(int k) {
         case LPK_FIX: return (const void*)fix_rows_kernel;
         case LPK_FIX_PAST: return (const void*)fix_past_kernel;
         case LPK_REL: return (const void*)rel_rows_kernel;
+        case LPK_MAP: return (const void*)map_rows_kernel;
     }
     return nullptr;
 }
@@ -1971,6 +1978,113 @@ int rvio_hip_get_fix_rows(rvio_hip* h, int instance, int32_t* m, int32_t* d, dou
     *m = h->fx.m; *d = h->fx.d;
     if (H) HIPCHK(h, hipMemcpyAsync(H, h->fx.H + (size_t)instance * fix_H_stride(h), sizeof(double) * (size_t)h->fx.m * h->fx.d, hipMemcpyDeviceToHost, h->stream));
     if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, h->fx.sigma + 6 * (size_t)instance, sizeof(double) * (size_t)h->fx.m, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RVIO_OK;
+}
+
+// ---- map landmarks (map_rows.hip): pixel observations of known world points; a block, flags and getters of their own, the same guard, staging,
+// pair read-back and aux launch
+static_assert(sizeof(rvio_map_obs) == 48 && sizeof(rvio_map_point) == 40 && sizeof(rvio_map_diag) == 32, "include/rvio_hip.h: the map structs have no padding");
+static_assert(LP_MAP_POINTS == RVIO_MAP_MAX_POINTS && LP_MAP_ROWS == RVIO_AUX_MAX_ROWS, "launch_plan.h: the points and rows of a map call");
+static const char kMapEntry[] = "rvio_hip_update_map";
+// what both entry points check of their arguments (the _dev form has no instance: -1): the cause, or nullptr
+static const char* map_args_bad(const rvio_hip* h, const rvio_map_obs* obs, int units, int gate, int gate_each, int n, int instance = -1) {
+    if (!h) return "NULL handle";
+    if (!obs) return "NULL observations";
+    if (units != RVIO_MAP_NORMALISED && units != RVIO_MAP_PIXELS) return "units is neither RVIO_MAP_NORMALISED nor RVIO_MAP_PIXELS";
+    if ((gate != 0 && gate != 1) || (gate_each != 0 && gate_each != 1)) return "gate and gate_each are 0 or 1";
+    if (n < 1 || n > RVIO_MAP_MAX_POINTS) return "the number of observations is outside 1 .. RVIO_MAP_MAX_POINTS";
+    if (instance < -1 || instance >= h->batch) return "instance out of range";
+    return nullptr;
+}
+static int map_refuse(rvio_hip* h, const char* why) {
+    if (h) h->err = std::string(kMapEntry) + ": " + why;
+    return RVIO_ERR_INVALID;
+}
+// behind the guard: the device, and on the first call the block (cleared on the filter stream, where everything that touches it runs)
+static int map_ready(rvio_hip* h) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->mp.H) return RVIO_OK;
+    if (h->dc.nmax > LP_FIXP_NMAX) { h->err = "rvio_hip_update_map: the clone window is longer than the chain the kernel holds (launch_plan.h LP_FIXP_NMAX)"; return RVIO_ERR_INVALID; }
+    const size_t B = (size_t)h->batch;
+    const size_t n_H = sizeof(double) * map_H_stride(h->dc.dmax) * B, n_r = sizeof(double) * LP_MAP_ROWS * B, n_pair = 16 * B, n_rec = sizeof(rvio_map_diag) * B,
+                 n_pts = sizeof(rvio_map_point) * LP_MAP_POINTS * B;
+    char* blk = nullptr;
+    RCCHK(own_dev(h, &blk, map_block_bytes(h->batch, h->dc.dmax), true));
+    h->mp.r = (double*)(blk + n_H); h->mp.sigma = (double*)(blk + n_H + n_r); h->mp.pair = (double*)(blk + n_H + 2 * n_r);
+    h->mp.rec = (rvio_map_diag*)(blk + n_H + 2 * n_r + n_pair); h->mp.pts = (rvio_map_point*)(blk + n_H + 2 * n_r + n_pair + n_rec);
+    h->mp.flag = (int32_t*)(blk + n_H + 2 * n_r + n_pair + n_rec + n_pts);
+    h->mp.H = (double*)blk;
+    return RVIO_OK;
+}
+// obs_bs: bytes between the instances' records (0: shared).  The kernel reads x and P of the current buffer, which the filter stream owns: it
+// runs on that stream, no event; the aux launch gets the kernel's own flags
+static int update_map_dev(rvio_hip* h, int units, int gate, int gate_each, int n_max, const rvio_map_obs* d_obs, size_t obs_bs, const int32_t* d_count,
+                          const int32_t* d_age, const int32_t* d_active) {
+    const LpLaunch l = map_launch(h->batch);
+    const size_t Hs = map_H_stride(h->dc.dmax);
+    hipLaunchKernelGGL(map_rows_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->dc, (const CamCal*)h->cal, h->n_clones_host, h->dc.dmax, units, gate_each, n_max,
+                       (const double*)h->x[h->cur], (const double*)h->P[h->cur], h->slab_bytes, d_obs, obs_bs, (const int*)d_count, (const int*)d_age, (const int*)d_active,
+                       h->composed_count, h->mp.H, Hs * sizeof(double), h->mp.r, h->mp.sigma, h->mp.rec, h->mp.pts, h->mp.pair, (int*)h->mp.flag);
+    HIPCHK(h, hipGetLastError());
+    h->mp.m = 2 * n_max; h->mp.d = 24 + 6 * h->n_clones_host;
+    RCCHK(update_aux_dev(h, 2 * n_max, RVIO_AUX_RESIDUAL, gate, h->mp.H, Hs, h->mp.r, LP_MAP_ROWS, h->mp.sigma, LP_MAP_ROWS, h->mp.flag, h->mp.pair));
+    if (paranoid_bits() & PAR_DRAIN) return drain_all(h);
+    return RVIO_OK;
+}
+int rvio_hip_update_map_dev(rvio_hip* h, int units, int gate, int gate_each, int n_max, const rvio_map_obs* d_obs, size_t obs_stride, const int32_t* d_count,
+                            const int32_t* d_age, const int32_t* d_active) {
+    if (const char* why = map_args_bad(h, d_obs, units, gate, gate_each, n_max)) return map_refuse(h, why);
+    if (!d_age) return map_refuse(h, "NULL d_age");
+    if (obs_stride && obs_stride < (size_t)n_max) return map_refuse(h, "obs_stride is below n_max and not 0");
+    RCCHK(meas_guard(h, kMapEntry));
+    RCCHK(map_ready(h));
+    return update_map_dev(h, units, gate, gate_each, n_max, d_obs, obs_stride * sizeof(rvio_map_obs), d_count, d_age, d_active);
+}
+// host records, staged like rvio_hip_update_fix_past's: [RVIO_MAP_MAX_POINTS records | age | flag, each per instance]
+int rvio_hip_update_map(rvio_hip* h, int instance, int units, int gate, int gate_each, int age, int n_obs, const rvio_map_obs* obs) {
+    if (const char* why = map_args_bad(h, obs, units, gate, gate_each, n_obs, instance)) return map_refuse(h, why);
+    for (int j = 0; j < n_obs; ++j) {
+        const rvio_map_obs& o = obs[j];
+        if (!(std::isfinite(o.p_w[0]) && std::isfinite(o.p_w[1]) && std::isfinite(o.p_w[2]) && std::isfinite(o.uv[0]) && std::isfinite(o.uv[1]) && std::isfinite(o.sigma))) {
+            h->err = "rvio_hip_update_map: a member of an observation is not finite"; return RVIO_ERR_INVALID;
+        }
+        if (!(o.sigma > 0)) { h->err = "rvio_hip_update_map: a sigma is not > 0"; return RVIO_ERR_INVALID; }
+    }
+    RCCHK(meas_guard(h, kMapEntry));
+    if (age < 0 || age > h->n_clones_host) { h->err = "rvio_hip_update_map: the age is outside the clone window"; return RVIO_ERR_INVALID; }
+    RCCHK(map_ready(h));
+    HostStage& s = h->mp.stage;
+    const size_t B = (size_t)h->batch, o_age = sizeof(rvio_map_obs) * RVIO_MAP_MAX_POINTS, bytes = o_age + 2 * sizeof(int32_t) * B;
+    RCCHK(stage_acquire(h, s, bytes));
+    std::memcpy(s.pin, obs, sizeof(rvio_map_obs) * (size_t)n_obs);
+    int32_t* ag = (int32_t*)(s.pin + o_age);
+    for (int i = 0; i < h->batch; ++i) ag[i] = age;
+    const int32_t* d_active;
+    RCCHK(stage_send(h, s, bytes, instance, &d_active));
+    return update_map_dev(h, units, gate, gate_each, n_obs, (const rvio_map_obs*)s.dev, 0, nullptr, (const int32_t*)(s.dev + o_age), d_active);
+}
+// wait for the filter stream only
+int rvio_hip_get_map(rvio_hip* h, int instance, rvio_map_diag* out, rvio_map_point* pts) {
+    if (!h || !out || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
+    if (!h->mp.m) { h->err = "rvio_hip_get_map before the first rvio_hip_update_map"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (pts) HIPCHK(h, hipMemcpyAsync(pts, h->mp.pts + LP_MAP_POINTS * (size_t)instance, sizeof(rvio_map_point) * LP_MAP_POINTS, hipMemcpyDeviceToHost, h->stream));
+    double g; long long ap;
+    RCCHK(read_pair(h, h->mp.pair, instance, &g, &ap, out, h->mp.rec + instance, sizeof *out));
+    out->gamma = g;
+    out->applied = ap ? 1 : 0;
+    return RVIO_OK;
+}
+int rvio_hip_get_map_rows(rvio_hip* h, int instance, int32_t* m, int32_t* d, double* H, double* r, double* sigma) {
+    if (!h || !m || !d || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
+    if (!h->mp.m) { h->err = "rvio_hip_get_map_rows before the first rvio_hip_update_map"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    *m = h->mp.m; *d = h->mp.d;
+    const size_t rows = (size_t)h->mp.m;
+    if (H) HIPCHK(h, hipMemcpyAsync(H, h->mp.H + (size_t)instance * map_H_stride(h->dc.dmax), sizeof(double) * rows * h->mp.d, hipMemcpyDeviceToHost, h->stream));
+    if (r) HIPCHK(h, hipMemcpyAsync(r, h->mp.r + LP_MAP_ROWS * (size_t)instance, sizeof(double) * rows, hipMemcpyDeviceToHost, h->stream));
+    if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, h->mp.sigma + LP_MAP_ROWS * (size_t)instance, sizeof(double) * rows, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RVIO_OK;
 }

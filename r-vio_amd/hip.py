@@ -35,6 +35,7 @@ SYMBOLS = [
     "rvio_hip_update_fix", "rvio_hip_update_fix_dev", "rvio_hip_get_fix", "rvio_hip_get_fix_rows",
     "rvio_hip_update_fix_past", "rvio_hip_update_fix_past_dev", "rvio_hip_frame_age",
     "rvio_hip_update_rel", "rvio_hip_update_rel_dev",
+    "rvio_hip_update_map", "rvio_hip_update_map_dev", "rvio_hip_get_map", "rvio_hip_get_map_rows",
 ]
 
 _LIB = None
@@ -649,3 +650,33 @@ class RvioHip:
         """the same on device records: d_age_new / d_age_old one int32 per instance"""
         self._ck(self.L.rvio_hip_update_rel_dev(self.h, int(kind), int(gate), C.c_void_p(d_meas_ptr), C.c_size_t(int(meas_stride)), C.c_void_p(d_age_new_ptr),
                                                 C.c_void_p(d_age_old_ptr), C.c_void_p(d_active_ptr) if d_active_ptr else None), "update_rel_dev")
+
+    # ---- map landmarks: pixel observations of known world points (csrc/map_rows.hip in front of the auxiliary update)
+    def update_map(self, obs, age, units=abi.RVIO_MAP_NORMALISED, gate=0, gate_each=1, instance=-1):
+        """fuse 1 .. 8 abi.rvio_map_obs (a ctypes array, abi.make_map_obs) made in the image `age` back from the newest composed frame; gate_each:
+        the chi-square gate per point; gate: the stack gate; instance: 0 .. B - 1, or -1 = every instance.  Asynchronous."""
+        self._ck(self.L.rvio_hip_update_map(self.h, int(instance), int(units), int(gate), int(gate_each), int(age), len(obs) if obs is not None else 0,
+                                            obs if obs is not None else None), "update_map")
+
+    def update_map_dev(self, units, gate, gate_each, n_max, d_obs_ptr, obs_stride, d_count_ptr, d_age_ptr, d_active_ptr=None):
+        """the same on device records: instance z reads d_obs + z * obs_stride records (0: shared), d_count[z] of them (None: n_max each) at the
+        age d_age[z]"""
+        self._ck(self.L.rvio_hip_update_map_dev(self.h, int(units), int(gate), int(gate_each), int(n_max), C.c_void_p(d_obs_ptr), C.c_size_t(int(obs_stride)),
+                                                C.c_void_p(d_count_ptr) if d_count_ptr else None, C.c_void_p(d_age_ptr) if d_age_ptr else None,
+                                                C.c_void_p(d_active_ptr) if d_active_ptr else None), "update_map_dev")
+
+    def get_map(self, instance=0):
+        """(abi.rvio_map_diag, [8 abi.rvio_map_point]) of one instance from the last update_map* call (waits for the filter stream only)"""
+        rec, pts = abi.rvio_map_diag(), (abi.rvio_map_point * abi.RVIO_MAP_MAX_POINTS)()
+        self._ck(self.L.rvio_hip_get_map(self.h, int(instance), C.byref(rec), pts), "get_map")
+        return rec, list(pts)
+
+    def get_map_rows(self, instance=0):
+        """(H [m x d], r [m], sigma [m]) as the device formed them in the last update_map* call"""
+        m, d = C.c_int32(0), C.c_int32(0)
+        self._ck(self.L.rvio_hip_get_map_rows(self.h, int(instance), C.byref(m), C.byref(d), None, None, None), "get_map_rows")
+        H, r, sigma = np.zeros((m.value, d.value)), np.zeros(m.value), np.zeros(m.value)
+        dp = C.POINTER(C.c_double)
+        self._ck(self.L.rvio_hip_get_map_rows(self.h, int(instance), C.byref(m), C.byref(d), H.ctypes.data_as(dp), r.ctypes.data_as(dp), sigma.ctypes.data_as(dp)),
+                 "get_map_rows")
+        return H, r, sigma
