@@ -135,6 +135,12 @@ bool parse_settings(const std::string& text, Settings* out, std::string* err) {
         z.sigma_v = opt("Standstill.SigmaV", z.sigma_v); z.sigma_bg = opt("Standstill.SigmaBg", z.sigma_bg);
         z.bias_rows = (int)opt("Standstill.BiasRows", z.bias_rows); z.gate = (int)opt("Standstill.Gate", z.gate);
     }
+    {   // Meas.*: optional, never reported as missing
+        auto it = y.num.find("Meas.Iterations");
+        out->meas_iterations = it != y.num.end() ? (int)it->second : 1;
+        it = y.num.find("Meas.Tolerance");
+        out->meas_tolerance = it != y.num.end() ? it->second : 0.0;
+    }
     out->encoding.clear();
     auto e = y.str.find("Camera.Encoding");
     if (e != y.str.end()) {
@@ -186,6 +192,19 @@ System::System(const Settings& s, int device) : s_(s) {
         }
         ss_on_ = true;
     }
+    if ((s_.meas_iterations != 1 || s_.meas_tolerance != 0.0) && !set_meas_iterations(s_.meas_iterations, s_.meas_tolerance)) {
+        err_ = "Meas.*: " + err_;
+        rvio_hip_destroy(h_); h_ = nullptr;
+    }
+}
+bool System::set_meas_iterations(int max_iters, double tol) {
+    if (!h_) { err_ = "System::set_meas_iterations without a handle"; return false; }
+    if (rvio_hip_set_meas_iterations(h_, max_iters, tol) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return false; }
+    return true;
+}
+bool System::last_meas_iter(rvio_meas_iter* out) {
+    if (!h_ || rvio_hip_get_meas_iter(h_, 0, out) != RVIO_OK) { err_ = h_ ? rvio_hip_last_error(h_) : "System::last_meas_iter without a handle"; return false; }
+    return true;
 }
 System::~System() {
     if (!ss_path_.empty()) (void)flush_standstill();

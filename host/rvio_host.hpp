@@ -57,6 +57,10 @@ struct Settings {
     // rvio_standstill_config_default, a missing key keeps its default.  Enable: 0 or absent: the host does the calls it did before the keys existed
     int standstill_enable = 0;
     rvio_standstill_config standstill;
+    // Meas.Iterations (1 .. RVIO_MEAS_MAX_ITERS) and Meas.Tolerance (>= 0) — optional; no reference counterpart: the fix, past-fix, rel and map
+    // measurements relinearised on the device (rvio_hip_set_meas_iterations).  Absent or 1: the single update, and the calls the host did before
+    int meas_iterations = 1;
+    double meas_tolerance = 0.0;
     std::vector<std::string> missing;   // keys the reference reads (cv::FileStorage would yield 0 for them) that the file does not hold:
                                         // they keep the EuRoC defaults here, and the caller is told (rvio_replay prints them)
 };
@@ -258,6 +262,11 @@ public:
     // t + latency (matches arrive late: latency >= 0 seconds), AT ITS OWN t.  Rows are sorted by t.  gate_each as above (rvio_replay --map-gate)
     void queue_map(std::vector<MapRow> rows, int units, double latency, bool gate_each);
     long map_groups_applied() const { return mp_groups_; }
+    // the iterated update of every fix / past-fix / rel / map measurement from here on (rvio_hip_set_meas_iterations; rvio_replay --meas-iters,
+    // --meas-tol; the settings keys Meas.Iterations, Meas.Tolerance).  false with error() when the library refuses the values
+    bool set_meas_iterations(int max_iters, double tol);
+    // what the last such measurement took (rvio_hip_get_meas_iter of instance 0: waits for the filter stream); false with error() before the first
+    bool last_meas_iter(rvio_meas_iter* out);
     // columns of an auxiliary H right now: 24 + 6 clones, the clones counted as the library counts them (one per frame behind the first, up
     // to Tracker.nMaxTrackingLength - 1) — no read-back
     int state_dim() const;

@@ -91,6 +91,7 @@ static int check_settings(const char* path) {
     std::printf("], \"standstill\": {\"enable\": %d, \"sigma_a\": %.17g, \"sigma_w\": %.17g, \"imu_thr\": %.17g, \"disp_thr_px\": %.17g, \"min_pairs\": %d, "
                 "\"sigma_v\": %.17g, \"sigma_bg\": %.17g, \"bias_rows\": %d, \"gate\": %d}",
                 s.standstill_enable, z.sigma_a, z.sigma_w, z.imu_thr, z.disp_thr_px, (int)z.min_pairs, z.sigma_v, z.sigma_bg, (int)z.bias_rows, (int)z.gate);
+    std::printf(", \"meas\": {\"iterations\": %d, \"tolerance\": %.17g}", s.meas_iterations, s.meas_tolerance);   // Meas.* (optional keys)
     std::printf(", \"encoding\": \"%s\"}\n", s.encoding.c_str());
     return 0;
 }
@@ -434,7 +435,8 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "usage: %s <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--record-dir DIR] [--record]\n"
                              "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--imu-odometry-cov] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n"
                              "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate] [--standstill FILE] [--fix FILE] [--fix-gate] [--fix-latency S]\n"
-                             "          [--rel FILE] [--rel-gate] [--map FILE] [--map-units px|norm] [--map-latency S] [--map-gate]\n", argv[0]);
+                             "          [--rel FILE] [--rel-gate] [--map FILE] [--map-units px|norm] [--map-latency S] [--map-gate]\n"
+                             "          [--meas-iters N] [--meas-tol T]\n", argv[0]);
         return 2;
     }
     const char* out_path = nullptr;
@@ -447,6 +449,7 @@ int main(int argc, char** argv) {
     const char* fix = nullptr; bool fix_gate = false; double fix_latency = -1.0;
     const char* rel = nullptr; bool rel_gate = false;
     const char* map = nullptr; int map_units = RVIO_MAP_PIXELS; double map_latency = 0.0; bool map_gate = false;
+    int meas_iters = 0; double meas_tol = -1.0;   // (0 / -1: not given, the settings' Meas.* hold)
     const char* record_dir = "."; bool force_record = false, sync_every = false, self = false; int noise_wgs = 0;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -477,6 +480,17 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--rel-gate")) rel_gate = true;
         else if (!std::strcmp(argv[i], "--map") && i + 1 < argc) map = argv[++i];   // `t x y z u v sigma` lines, grouped by stamp, fused at the frame nearest to t (System::map_points_at)
         else if (!std::strcmp(argv[i], "--map-gate")) map_gate = true;
+        else if (!std::strcmp(argv[i], "--meas-iters") && i + 1 < argc) {   // the --fix / --rel / --map measurements relinearised N times on the device (rvio_hip_set_meas_iterations)
+            char* end = nullptr;
+            const long v = std::strtol(argv[++i], &end, 10);
+            if (end == argv[i] || *end != 0 || v < 1 || v > RVIO_MEAS_MAX_ITERS) { std::fprintf(stderr, "--meas-iters takes an integer in 1 .. %d, not '%s'\n", RVIO_MEAS_MAX_ITERS, argv[i]); return 1; }
+            meas_iters = (int)v;
+        }
+        else if (!std::strcmp(argv[i], "--meas-tol") && i + 1 < argc) {
+            char* end = nullptr;
+            meas_tol = std::strtod(argv[++i], &end);
+            if (end == argv[i] || *end != 0 || !std::isfinite(meas_tol) || meas_tol < 0) { std::fprintf(stderr, "--meas-tol takes a finite number >= 0, not '%s'\n", argv[i]); return 1; }
+        }
         else if (!std::strcmp(argv[i], "--map-units") && i + 1 < argc) {
             ++i;
             if (!std::strcmp(argv[i], "px")) map_units = RVIO_MAP_PIXELS;
@@ -519,6 +533,8 @@ int main(int argc, char** argv) {
         if (self) { std::fprintf(stderr, "--map and --selfcheck do not combine\n"); return 1; }
         if (!read_map(map, &maps, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
     }
+    if (meas_iters) s.meas_iterations = meas_iters;   // (the command line overrides the settings; System's constructor hands them to the library)
+    if (meas_tol >= 0) s.meas_tolerance = meas_tol;
     print_runtime();
     if (self) return selfcheck(s, d, device, max_frames, stall_seed, noise_wgs);
     if (sync_every || stall_seed >= 0 || noise_wgs > 0) {   // the plain replay with one of the two A/B pacings
@@ -577,6 +593,13 @@ int main(int argc, char** argv) {
         for (double t : sys.map_skipped_stamps()) std::fprintf(stderr, "rvio_replay: map: the group stamped %.9f is older than the clone window: skipped\n", t);
         std::fprintf(stderr, "rvio_replay: map: %zu rows, %ld groups, %ld applied, %ld outside the window and skipped\n", maps.size(), sys.map_groups_applied(),
                      sys.map_groups_applied() - sys.maps_skipped(), sys.maps_skipped());
+    }
+    if ((fix || rel || map) && (s.meas_iterations != 1 || s.meas_tolerance != 0.0)) {
+        rvio_meas_iter it;
+        if (sys.last_meas_iter(&it))
+            std::fprintf(stderr, "rvio_replay: meas-iters: at most %d passes, tolerance %g; the last measurement took %d, last step %.3e, converged %d, gamma of pass 0 %.6g\n",
+                         s.meas_iterations, s.meas_tolerance, (int)it.iterations, it.step, (int)it.converged, it.gamma0);
+        else std::fprintf(stderr, "rvio_replay: meas-iters: no measurement was fused (%s)\n", sys.error().c_str());
     }
     // anything only the device saw (0 in every test and bench run): said out loud, the poses above are suspect if it is not 0
     const int flags = sys.device_flags();

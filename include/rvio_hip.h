@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov); standstill detection (rvio_standstill_config, rvio_standstill, rvio_standstill_config_default, rvio_hip_set_standstill, rvio_hip_standstill, rvio_hip_standstill_dev, rvio_hip_get_standstill); absolute fixes (rvio_fix_kind, rvio_fix, rvio_fix_diag, rvio_hip_update_fix, rvio_hip_update_fix_dev, rvio_hip_get_fix, rvio_hip_get_fix_rows); past-frame fixes (rvio_hip_update_fix_past, rvio_hip_update_fix_past_dev, rvio_hip_frame_age); relative-pose measurements (rvio_rel_kind, rvio_hip_update_rel, rvio_hip_update_rel_dev); map landmarks (rvio_map_units, rvio_map_obs, rvio_map_point, rvio_map_diag, rvio_hip_update_map, rvio_hip_update_map_dev, rvio_hip_get_map, rvio_hip_get_map_rows) */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov); standstill detection (rvio_standstill_config, rvio_standstill, rvio_standstill_config_default, rvio_hip_set_standstill, rvio_hip_standstill, rvio_hip_standstill_dev, rvio_hip_get_standstill); absolute fixes (rvio_fix_kind, rvio_fix, rvio_fix_diag, rvio_hip_update_fix, rvio_hip_update_fix_dev, rvio_hip_get_fix, rvio_hip_get_fix_rows); past-frame fixes (rvio_hip_update_fix_past, rvio_hip_update_fix_past_dev, rvio_hip_frame_age); relative-pose measurements (rvio_rel_kind, rvio_hip_update_rel, rvio_hip_update_rel_dev); map landmarks (rvio_map_units, rvio_map_obs, rvio_map_point, rvio_map_diag, rvio_hip_update_map, rvio_hip_update_map_dev, rvio_hip_get_map, rvio_hip_get_map_rows); iterated measurement updates (rvio_meas_iter, rvio_hip_set_meas_iterations, rvio_hip_get_meas_iterations, rvio_hip_get_meas_iter) */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -613,7 +613,7 @@ int rvio_hip_get_standstill(rvio_hip* h, int instance, rvio_standstill* out);
  *             (the state carries g as three coordinates and injection re-normalises it, Updater.cc:566-568: what the gain moves ALONG g is
  *             dropped there, so the part of a residual along gravity is only taken up as far as the prior hands it to ba)
  * The fix is fused at the state the call finds, not at a time stamp of its own: bridging the gap to the sensor's stamp is the caller's.  One
- * update, not iterated.  Everything rvio_hip_update_aux_dev documents holds: in place, `gate` as there, the pose line rewritten, no ring record, a
+ * update, linearised once (more passes: rvio_hip_set_meas_iterations below).  Everything rvio_hip_update_aux_dev documents holds: in place, `gate` as there, the pose line rewritten, no ring record, a
  * kept clone-block factor dropped, an inactive or gated-out instance not written at all, error bit 8 on a non-positive pivot. */
 typedef enum { RVIO_FIX_POSITION = 0, RVIO_FIX_ATTITUDE = 1, RVIO_FIX_POSE = 2, RVIO_FIX_GRAVITY = 3 } rvio_fix_kind;
 typedef struct rvio_fix {      /* 128 bytes, no padding */
@@ -681,7 +681,7 @@ int rvio_hip_get_fix_rows(rvio_hip* h, int instance, int32_t* m, int32_t* d, dou
  * allocates the fix block of rvio_hip_update_fix if need be, plus the flags and the staging of age / frac, outside the filter slab.
  * RVIO_ERR_STATE as rvio_hip_update_fix.  RVIO_ERR_INVALID: what rvio_hip_update_fix refuses, RVIO_FIX_GRAVITY, NULL d_age and — host form only —
  * frac outside [0, 1) or not 0 with a kind other than POSITION, an age outside 0 .. n, age + 1 > n with frac > 0 (rvio_hip_last_error).
- * NOT done: attitude interpolation, time-offset estimation, iterated updates, stamps newer than the last composed image (IMU bridging). */
+ * NOT done: attitude interpolation, time-offset estimation, stamps newer than the last composed image (IMU bridging). */
 int rvio_hip_update_fix_past(rvio_hip* h, int instance, int kind, int gate, int age, double frac, const rvio_fix* fix);
 int rvio_hip_update_fix_past_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_stride, const int32_t* d_age,
                                  const double* d_frac /* NULL: 0 */, const int32_t* d_active);
@@ -729,7 +729,7 @@ int rvio_hip_frame_age(rvio_hip* h, int img_count, int* age);
  * (rvio_hip_last_error).
  * NOT done: interpolation between frames (both stamps are whole frames); the current (qk, pk) as an endpoint (age 0 is {R}); a sensor-to-IMU
  * rotation (the caller re-expresses a sensor's delta as the IMU's; only the lever arm is handled); correlation between successive overlapping
- * deltas of one integrator (they are treated as independent); iterated updates; time-offset estimation. */
+ * deltas of one integrator (they are treated as independent); time-offset estimation. */
 typedef enum { RVIO_REL_POSITION = 16, RVIO_REL_ATTITUDE = 17, RVIO_REL_POSE = 18 } rvio_rel_kind;  /* = 16 + the fix kind: rvio_fix_diag.kind tells the families apart */
 int rvio_hip_update_rel(rvio_hip* h, int instance, int kind, int gate, int age_new, int age_old, const rvio_fix* meas);
 int rvio_hip_update_rel_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_meas, size_t meas_stride, const int32_t* d_age_new,
@@ -785,7 +785,7 @@ int rvio_hip_update_rel_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_m
  * RVIO_ERR_STATE as rvio_hip_update_fix.  RVIO_ERR_INVALID: a NULL handle or buffer (a NULL d_age included), n_obs / n_max outside 1 .. 8, units,
  * gate or gate_each outside their values, an instance out of range, an obs_stride below n_max unless it is 0, a window longer than the chain the
  * kernel holds and — host form only — a member that is not finite, sigma <= 0, an age outside 0 .. n (rvio_hip_last_error names the cause).
- * NOT done: iterated updates; estimating the camera-IMU extrinsic or a time offset; points whose world position is itself uncertain (a
+ * NOT done: estimating the camera-IMU extrinsic or a time offset; points whose world position is itself uncertain (a
  * per-point 3 x 3 prior); interpolation between frames; more than 8 points per launch (call again: sequential updates of independent
  * measurements are valid); alignment of a map frame to the filter's world frame — the frame of the pose line: anchored at the first IMU frame and, with
  * ini_enable_alignment, turned so that its z axis is the accelerometer's direction at rest — which is the caller's job, as for fixes.  Note on
@@ -801,6 +801,43 @@ int rvio_hip_update_map_dev(rvio_hip* h, int units, int gate, int gate_each, int
                             const int32_t* d_count, const int32_t* d_age, const int32_t* d_active);
 int rvio_hip_get_map(rvio_hip* h, int instance, rvio_map_diag* out, rvio_map_point* pts);
 int rvio_hip_get_map_rows(rvio_hip* h, int instance, int32_t* m, int32_t* d, double* H, double* r, double* sigma);
+
+/* --- iterated measurement updates: relinearise the fix, past-fix, rel and map families (no reference counterpart) ----------------------- */
+/* The four families above are non-linear in the robocentric state, and one linearisation is only good when the prior is close: a
+ * relocalisation after drift is the far-from-prior case.  With max_iters = K > 1 a call of rvio_hip_update_fix / _fix_past / _rel / _map (and
+ * their _dev forms) runs the iterated EKF update, a Gauss-Newton loop whose every pass refers to the PRIOR (x0, P0):
+ *   dx_0 = 0, x_0 = x0
+ *   pass i = 0 .. K - 1:   (H_i, r_i, sigma) = rows at x_i            the family's rows kernel, unchanged
+ *                          v_i = r_i + H_i dx_i                        the residual referred to the prior
+ *                          K_i = P0 H~_i^T (H~_i P0 H~_i^T + I)^-1     whitened rows, the arithmetic of rvio_hip_update_aux
+ *                          dx_{i+1} = K_i v~_i,   step = max |dx_{i+1} - dx_i|
+ *                          x_{i+1} = x0 (+) dx_{i+1}                   the state injection, always from x0, never chained
+ *                          step < tol or i = K - 1:  P+ = the Joseph form with (K_i, H~_i) on P0; the instance is finished
+ * K pairs (rows kernel, aux_iter_kernel — csrc/aux_update.hip, the update kernel with the four differences this needs) are enqueued on the filter
+ * stream in a fixed sequence: no read-back, no host decision.  P is written once, on the final pass, so every pass forms its gain against P0;
+ * x and the pose line are rewritten by every pass.  A per-instance running flag on the device — the caller's flag AND the rows kernel's own at
+ * pass 0, cleared when the instance is finished — is what the kernels of the later passes get as their active flags: a finished instance keeps
+ * the rows, records and state of the last pass that acted on it.
+ * gate (the chi-square stack gate) is evaluated at pass 0 only, where v_0 is the innovation: a refused instance is finished with nothing
+ * written.  A non-positive pivot at any pass sets sticky error bit 8 and leaves (x0, P0): x and the pose line are written back from the
+ * snapshot, P is never touched, applied = 0.  Map calls: the per-point statuses and gammas are those pass 0 decided (a gated slot stays gated;
+ * the per-point gate is formed at pass 0 only); a used slot whose depth falls below the limit at a later linearisation becomes rejected, and
+ * if none is left the instance ends like a non-positive pivot.  gamma / applied of rvio_hip_get_fix / _get_map: pass 0's gamma; applied = 1
+ * iff the last pass that ran wrote the state.
+ * rvio_hip_set_meas_iterations: a handle setting like rvio_hip_set_standstill; max_iters 1 .. RVIO_MEAS_MAX_ITERS, tol >= 0 and finite
+ * (0: always max_iters passes), else RVIO_ERR_INVALID with a message.  A handle that never calls it, or sets max_iters = 1, launches exactly
+ * what it launched before: the plain kernels on the plain path, the same bits.  rvio_hip_update_aux[_dev] (caller-linearised rows) and
+ * rvio_hip_standstill ignore the setting.  The first iterated call allocates the block outside the filter slab: per instance the snapshot
+ * (26 + 7 n_max doubles and the pose line), dx (d_max doubles), the record and the running flag.
+ * rvio_hip_get_meas_iter: passes run, the last step, converged (step < tol) and pass 0's gamma of one instance in the last fix / past-fix /
+ * rel / map call; after a call at max_iters = 1: iterations = 1, step = 0, converged = 0, gamma0 = that call's gamma.  An instance the call
+ * did not act on reads iterations = 0.  Waits for the filter stream only.  RVIO_ERR_STATE before the first such call.
+ * NOT done: iterating the camera update; line search or damping; the Jacobian of the retraction at dx != 0. */
+#define RVIO_MEAS_MAX_ITERS 8
+typedef struct rvio_meas_iter { double step; double gamma0; int32_t iterations, converged; } rvio_meas_iter;                             /* 24 B */
+int rvio_hip_set_meas_iterations(rvio_hip* h, int max_iters, double tol);
+int rvio_hip_get_meas_iterations(rvio_hip* h, int* max_iters, double* tol);
+int rvio_hip_get_meas_iter(rvio_hip* h, int instance, rvio_meas_iter* out);
 
 /* --- feature-sharded updater (no reference counterpart) ------ */
 /* Stage A: per-feature build + gate on the features f with f % world == rank,

@@ -754,12 +754,14 @@ def map_h(cal, x, age, p_w):
     return H, h, depth
 
 
-def map_model(cal, x, P, obs, age, units, gate_each, uv_n=None):
+def map_model(cal, x, P, obs, age, units, gate_each, uv_n=None, hold=None):
     """NumPy float64 model of csrc/map_rows.hip: (H [2 n x d], r [2 n], sigma [2 n], gamma [n], status [n]) of n = len(obs) <= 8 observations
     (rvio_map_obs, or anything with p_w, uv, sigma) at the image `age` back.  PIXELS: uv_n holds the undistorted normalised coordinates of the
     float pixels (n x 2, the tracker's undistortion: the model has none of its own) and the rows get sigma / |fx|, sigma / |fy|.  A slot that is
     rejected (depth < MAP_MIN_DEPTH or a non-finite projection) or, with gate_each, gated out (|gamma_j| >= chi2inv(0.95, 2) against P as it
-    is, or a non-positive pivot) has H = 0, r = 0, sigma = 1 in its two rows."""
+    is, or a non-positive pivot) has H = 0, r = 0, sigma = 1 in its two rows.
+    hold: (gamma of pass 0, status of the pass before) of an iterated update — a later pass: a slot that is not used keeps its status, a used
+    one keeps its gamma and is not gated again (it may still be rejected at the new state, and then stays so)."""
     x, P = np.asarray(x, float), np.asarray(P, float)
     assert units in (RVIO_MAP_NORMALISED, RVIO_MAP_PIXELS) and 1 <= len(obs) <= RVIO_MAP_MAX_POINTS
     assert units == RVIO_MAP_NORMALISED or uv_n is not None, "PIXELS: pass the undistorted coordinates"
@@ -768,6 +770,9 @@ def map_model(cal, x, P, obs, age, units, gate_each, uv_n=None):
     H, r, sg = np.zeros((2 * nob, d)), np.zeros(2 * nob), np.ones(2 * nob)
     gamma, status = np.zeros(nob), np.zeros(nob, int)
     for j, o in enumerate(obs):
+        if hold is not None and hold[1][j] != MAP_USED:
+            gamma[j], status[j] = hold[0][j], hold[1][j]
+            continue
         Hj, h, depth = map_h(cal, x, age, [float(v) for v in o.p_w])
         z = np.array([float(v) for v in o.uv]) if units == RVIO_MAP_NORMALISED else np.asarray(uv_n, float).reshape(-1, 2)[j]
         s = float(o.sigma)
@@ -775,6 +780,10 @@ def map_model(cal, x, P, obs, age, units, gate_each, uv_n=None):
         rj = z - h
         if not (np.isfinite(depth) and depth >= MAP_MIN_DEPTH and np.all(np.isfinite(h)) and np.all(np.isfinite(rj)) and np.all(sj > 0) and np.all(np.isfinite(sj))):
             status[j] = MAP_REJECTED
+            continue
+        if hold is not None:
+            gamma[j] = hold[0][j]
+            H[2 * j: 2 * j + 2], r[2 * j: 2 * j + 2], sg[2 * j: 2 * j + 2] = Hj, rj, sj
             continue
         Hw, rw = Hj / sj[:, None], rj / sj
         S = Hw @ P @ Hw.T + np.eye(2)
@@ -790,6 +799,73 @@ def map_model(cal, x, P, obs, age, units, gate_each, uv_n=None):
             continue
         H[2 * j: 2 * j + 2], r[2 * j: 2 * j + 2], sg[2 * j: 2 * j + 2] = Hj, rj, sj
     return H, r, sg, gamma, status
+
+
+# ---- iterated measurement updates (rvio_hip_set_meas_iterations: the fix, past-fix, rel and map families relinearised on the device)
+RVIO_MEAS_MAX_ITERS = 8
+
+
+class rvio_meas_iter(C.Structure):
+    """what the iterated update made of one instance in the last fix / past-fix / rel / map call: 24 bytes, no padding.  iterations: passes run;
+    step: max |dx_new - dx| of the last one; converged: step < tol; gamma0: pass 0's gamma (the innovation test)"""
+    _fields_ = [("step", C.c_double), ("gamma0", C.c_double), ("iterations", C.c_int32), ("converged", C.c_int32)]
+
+
+assert C.sizeof(rvio_meas_iter) == 24
+
+
+def iter_update_model(x0, P0, lin, max_iters, tol, dtype=float):
+    """NumPy model of the iterated update (the specification in include/rvio_hip.h): a Gauss-Newton / IEKF loop whose every pass refers to the
+    prior (x0, P0).  lin(x, i) -> (H, r, sigma): the family's row model at the state x for pass i.  Returns (x', P', info) with info a dict:
+    iterations, steps (one per pass), converged, gamma0, dx.  The gain of every pass is formed against P0; P' is the Joseph form of the final
+    pass's gain, symmetrised; the state is always injected from x0.  With max_iters = 1 this is aux_update_model.  No gate (the caller compares
+    gamma0).  dtype: np.longdouble runs the linear algebra of the loop in extended precision (the rows and the injection stay float64 — they
+    are the family models'), which gives the rounding floor of the float64 loop."""
+    x0 = np.asarray(x0, float)
+    P = np.asarray(P0, dtype)
+    d = P.shape[0]
+    dx, x = np.zeros(d, dtype), x0.copy()
+    steps, gamma0, conv = [], 0.0, False
+
+    def solve(S, B):   # float64: what aux_update_model calls; else L D L^T by hand (S is symmetric positive definite; numpy.linalg has no longdouble)
+        if dtype is float:
+            return np.linalg.solve(S, B)
+        m = S.shape[0]
+        L, D = np.eye(m, dtype=dtype), np.zeros(m, dtype)
+        for k in range(m):
+            D[k] = S[k, k] - (L[k, :k] ** 2) @ D[:k]
+            for i in range(k + 1, m):
+                L[i, k] = (S[i, k] - (L[i, :k] * L[k, :k]) @ D[:k]) / D[k]
+        Y = np.array(B, dtype, copy=True)
+        for k in range(m):
+            Y[k] = Y[k] - L[k, :k] @ Y[:k]
+        Y = Y / (D[:, None] if Y.ndim == 2 else D)
+        for k in range(m - 1, -1, -1):
+            Y[k] = Y[k] - L[k + 1:, k] @ Y[k + 1:]
+        return Y
+
+    for i in range(int(max_iters)):
+        H, r, sigma = lin(x, i)
+        H, r, sigma = np.atleast_2d(np.asarray(H, dtype)), np.asarray(r, dtype).reshape(-1), np.asarray(sigma, dtype).reshape(-1)
+        m = H.shape[0]
+        Hw = H / sigma[:, None]
+        vw = r / sigma + Hw @ dx
+        T = P @ Hw.T
+        S = Hw @ T + np.eye(m, dtype=dtype)
+        S = (S + S.T) / 2
+        K = solve(S, T.T).T
+        if i == 0:
+            gamma0 = abs(float(vw @ solve(S, vw)))
+        dxn = K @ vw
+        steps.append(float(np.max(np.abs(dxn - dx))))
+        dx = dxn
+        x = inject_state(x0, np.asarray(dx, float))
+        conv = steps[-1] < tol
+        if conv or i == max_iters - 1:
+            IKH = np.eye(d, dtype=dtype) - K @ Hw
+            Pn = IKH @ P @ IKH.T + K @ K.T
+            return x, (Pn + Pn.T) / 2, {"iterations": i + 1, "steps": steps, "converged": bool(conv), "gamma0": gamma0, "dx": dx}
+    raise AssertionError("max_iters >= 1")
 
 
 # Camera.T_BC0 of config/rvio_euroc.yaml:55-62 (row-major)

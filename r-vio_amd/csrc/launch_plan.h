@@ -134,6 +134,18 @@ LP_HD inline size_t aux_lds_max_doubles(int nmax, int MB) {
     for (int n = 0; n <= nmax; ++n) { const size_t a = aux_lds_doubles(24 + 6 * n, MB); if (a > w) w = a; }
     return w;
 }
+// aux_iter_kernel<MB> (aux_update.hip), one pass of the iterated update: the same footprint + the correction of the previous pass (d doubles)
+LP_HD inline size_t aux_iter_lds_doubles(int d, int MB) { return aux_lds_doubles(d, MB) + (size_t)d; }
+LP_HD inline size_t aux_iter_lds_max_doubles(int nmax, int MB) {
+    size_t w = 0;
+    for (int n = 0; n <= nmax; ++n) { const size_t a = aux_iter_lds_doubles(24 + 6 * n, MB); if (a > w) w = a; }
+    return w;
+}
+// the per-instance block of the iterated measurement chain (rvio_hip.hip MeasIter): doubles between the instances' snapshots — the state, then
+// the pose line in the last 7 — and the block's bytes: snapshots | dx | records (rvio_meas_iter, 24 bytes) | running flags
+#define LP_MEAS_MAX_ITERS 8      // RVIO_MEAS_MAX_ITERS
+LP_HD inline size_t meas_iter_x0_stride(int nmax) { return (size_t)26 + 7 * (size_t)nmax + 7; }
+LP_HD inline size_t meas_iter_block_bytes(int batch, int nmax, int dmax) { return (size_t)batch * (8 * meas_iter_x0_stride(nmax) + 8 * (size_t)dmax + 24 + 4); }
 // standstill_kernel (standstill.hip): one workgroup of four waves per instance; the combine of the waves' partial sums goes through static LDS
 // (LP_SS_RED doubles per wave), there is no dynamic part
 #define LP_SS_T 256
@@ -180,7 +192,8 @@ LP_HD inline size_t map_block_bytes(int batch, int dmax) {
 enum LpKernel {
     LPK_FEAT_BUILD16, LPK_FEAT_BUILD4, LPK_GRAM_REDUCE, LPK_BLOCK_SUM, LPK_LIT_BATCH, LPK_GEMM_T_LDS, LPK_GRAM_BATCH4, LPK_GRAM_BATCH6, LPK_FEAT_PROP,
     LPK_BOOKKEEP_B, LPK_RANSAC_BOOK, LPK_SOLVE9_SMALL, LPK_SOLVE6_1, LPK_SOLVE6_2, LPK_SOLVE6_3, LPK_JOSEPH_BATCH, LPK_UG, LPK_UG_LDS, LPK_FINAL_LDS,
-    LPK_JOSEPH_LDS, LPK_IMU_POSE, LPK_AUX_UPDATE4, LPK_AUX_UPDATE16, LPK_IMU_COV, LPK_STANDSTILL, LPK_FIX, LPK_FIX_PAST, LPK_REL, LPK_MAP, LPK_COUNT
+    LPK_JOSEPH_LDS, LPK_IMU_POSE, LPK_AUX_UPDATE4, LPK_AUX_UPDATE16, LPK_IMU_COV, LPK_STANDSTILL, LPK_FIX, LPK_FIX_PAST, LPK_REL, LPK_MAP,
+    LPK_AUX_ITER4, LPK_AUX_ITER16, LPK_COUNT
 };
 // (as c++filt prints them, without return type and arguments: how the test finds each kernel's static LDS in the code object's notes)
 static const char* const kLpKernelName[LPK_COUNT] = {
@@ -188,7 +201,7 @@ static const char* const kLpKernelName[LPK_COUNT] = {
     "gram_reduce_batch_kernel<4>", "gram_reduce_batch_kernel<6>", "feat_prop_kernel", "bookkeep_b_kernel", "ransac_book_kernel", "solve9_small_kernel",
     "solve6_kernel<1, 8, 8>", "solve6_kernel<2, 12, 8>", "solve6_kernel<2, 16, 8>", "joseph_batch_kernel", "ug_kernel", "ug_lds_kernel", "final_lds_kernel",
     "joseph_lds_kernel", "imu_pose_kernel", "aux_update_kernel<4>", "aux_update_kernel<16>", "imu_cov_kernel", "standstill_kernel",
-    "fix_rows_kernel", "fix_past_kernel", "rel_rows_kernel", "map_rows_kernel"
+    "fix_rows_kernel", "fix_past_kernel", "rel_rows_kernel", "map_rows_kernel", "aux_iter_kernel<4>", "aux_iter_kernel<16>"
 };
 
 struct LaunchPlan {
@@ -318,6 +331,8 @@ inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size
     p.attr[LPK_IMU_COV] = LP_IMUC_LDS_BYTES;
     p.attr[LPK_AUX_UPDATE4] = aux_lds_max_doubles(nmax, 4) * sizeof(double);      // (what a launch asks for follows the clone count)
     p.attr[LPK_AUX_UPDATE16] = aux_lds_max_doubles(nmax, 16) * sizeof(double);
+    p.attr[LPK_AUX_ITER4] = aux_iter_lds_max_doubles(nmax, 4) * sizeof(double);
+    p.attr[LPK_AUX_ITER16] = aux_iter_lds_max_doubles(nmax, 16) * sizeof(double);
     // standstill_kernel asks for no dynamic LDS (p.attr[LPK_STANDSTILL] stays 0: no limit to set); its static part alone is held to a CU here
     if (statics[LPK_STANDSTILL] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
     // fix_rows_kernel: the same (static LDS only, p.attr[LPK_FIX] stays 0)
@@ -491,6 +506,11 @@ LP_HD inline LpLaunch imu_cov_launch(int instances) { return {instances, 1, 1, L
 LP_HD inline LpLaunch aux_update_launch(int n, int m, int batch) {
     const int MB = aux_mb(m);
     return {1, 1, batch, LP_AUX_T, aux_lds_doubles(24 + 6 * n, MB) * sizeof(double), MB == 4 ? LPK_AUX_UPDATE4 : LPK_AUX_UPDATE16};
+}
+// aux_iter_kernel: the same grid and form choice, d more doubles of LDS
+LP_HD inline LpLaunch aux_iter_launch(int n, int m, int batch) {
+    const int MB = aux_mb(m);
+    return {1, 1, batch, LP_AUX_T, aux_iter_lds_doubles(24 + 6 * n, MB) * sizeof(double), MB == 4 ? LPK_AUX_ITER4 : LPK_AUX_ITER16};
 }
 // standstill_kernel: one workgroup per instance at every batch size, static LDS only
 LP_HD inline LpLaunch standstill_launch(int batch) { return {1, 1, batch, LP_SS_T, 0, LPK_STANDSTILL}; }

@@ -33,6 +33,11 @@
 // The kernel owns an active flag per instance: the caller's flag AND age inside 0 .. n AND at least one used slot.  aux_update_kernel gets THAT
 // flag.  An instance outside the window: m = 0, applied = 0, n_used = 0, img_count = -1, every slot 3.  An instance the caller flagged inactive
 // gets flag 0 and nothing else.
+//
+// pass: 0 is all of the above.  A later pass of the iterated update (include/rvio_hip.h, rvio_hip_set_meas_iterations) relinearises at the state
+// the pass before left and keeps what pass 0 decided: a slot that was not used then keeps its status and its record untouched; a used slot
+// keeps pass 0's gamma and is not gated again — steps 4 and 5's product with P are skipped — but may still become rejected by its depth at the
+// new state; `active` then holds the chain's running flags.
 #define MAP_USED 0
 #define MAP_GATED 1
 #define MAP_REJECTED 2
@@ -57,7 +62,7 @@ __device__ __forceinline__ int map_col(int e, int c0) { return e < 6 ? e : c0 + 
 __global__ __launch_bounds__(LP_MAP_T) void map_rows_kernel(DevCfg cfg, const CamCal* __restrict__ cal, int n, int ld, int units, int gate_each, int n_max,
                                                            const double* x, const double* P, size_t bs, const rvio_map_obs* obs, size_t obs_bs, const int* count,
                                                            const int* age, const int* active, int ref_count, double* H, size_t H_bs, double* r, double* sigma,
-                                                           rvio_map_diag* rec, rvio_map_point* pts, double* pair, int* flag) {
+                                                           rvio_map_diag* rec, rvio_map_point* pts, double* pair, int* flag, int pass) {
     static_assert(LP_MAP_T == 256 && LP_FIXP_NMAX < 64 && LP_MAP_SLOT >= 27, "four waves per instance, one lane per clone");
     __shared__ double chain[LP_FIXP_CHAIN];
     __shared__ __align__(16) double Hs[LP_MAP_HS];
@@ -122,7 +127,9 @@ __global__ __launch_bounds__(LP_MAP_T) void map_rows_kernel(DevCfg cfg, const Ca
 #pragma unroll
         for (int k = 0; k < LP_MAP_SLOT; ++k) s[k] = 0.0;
         int status = MAP_EMPTY;
-        if (tid < cnt) {
+        const int held = pass > 0 ? pz[tid].status : MAP_USED;   // what pass 0 made of the slot
+        if (tid < cnt && held != MAP_USED) status = held;
+        else if (tid < cnt) {
             const CamCal cam = cam_of(cfg, cal, z);
             const rvio_map_obs* o = obs + tid;
             m33 Rci;
@@ -194,7 +201,7 @@ __global__ __launch_bounds__(LP_MAP_T) void map_rows_kernel(DevCfg cfg, const Ca
     __syncthreads();
 
     // ---- 4  y = H P over the compacted columns, the three sums of every slot's 2 x 2
-    {
+    if (pass == 0) {   // (uniform)
         const int nz = 6 + 6 * a, c0 = 24 + 6 * (n - a);
         const int e = 64 * wv + lane;
         const bool on = e < nz;
@@ -222,7 +229,16 @@ __global__ __launch_bounds__(LP_MAP_T) void map_rows_kernel(DevCfg cfg, const Ca
     __syncthreads();
 
     // ---- 5  thread j: the 2 x 2, its L D L^T, gamma_j, the decision, the slot's record
-    if (tid < LP_MAP_POINTS) {
+    if (pass > 0) {   // the statuses stand; a slot still used reports its new residual and depth beside pass 0's gamma
+        if (tid < LP_MAP_POINTS && pz[tid].status == MAP_USED) {
+            const double* s = slot + tid * LP_MAP_SLOT;
+            const bool used = st[tid] == MAP_USED;
+            rvio_map_point e;
+            e.r[0] = used ? s[MAP_S_R] : 0.0; e.r[1] = used ? s[MAP_S_R + 1] : 0.0;
+            e.gamma = used ? pz[tid].gamma : 0.0; e.depth = s[MAP_S_DEPTH]; e.status = st[tid]; e.reserved = 0;
+            pz[tid] = e;
+        }
+    } else if (tid < LP_MAP_POINTS) {
         double* s = slot + tid * LP_MAP_SLOT;
         int status = st[tid];
         double gam = 0.0;

@@ -240,6 +240,11 @@ struct rvio_hip {
     // (RVIO_MAP_MAX_POINTS records; age and flag per instance).  m, d: the rows of the last call, for the getters
     struct { double* H = nullptr; double* r = nullptr; double* sigma = nullptr; double* pair = nullptr; rvio_map_diag* rec = nullptr; rvio_map_point* pts = nullptr;
              int32_t* flag = nullptr; int m = 0, d = 0; HostStage stage; } mp;
+    // iterated measurement updates (rvio_hip_set_meas_iterations): the setting, and one block allocated by the first iterated call, outside the
+    // slab — per instance the snapshot (launch_plan.h meas_iter_x0_stride doubles), dx (dmax doubles), the record, the running flag.
+    // last_pair: the (gamma, applied) pairs of the last fix / past-fix / rel / map call (nullptr: none yet); last_iterated: it ran the chain
+    struct { int max_iters = 1; double tol = 0.0; double* x0 = nullptr; double* dx = nullptr; rvio_meas_iter* rec = nullptr; int32_t* run = nullptr;
+             const double* last_pair = nullptr; bool last_iterated = false; } mi;
     // colour input (rvio_hip_set_image_format): the gray images every stage behind gray_kernel reads instead of the caller's.  Allocated with the
     // first colour format, outside the slab (a mono handle keeps its memory layout), instance stride W * H; four in rotation like d_eq2[] (see
     // build_pyramid_dev for who reads a slot last)
@@ -618,6 +623,8 @@ static const void* lp_kernel_fn(int k) {
         case LPK_FIX_PAST: return (const void*)fix_past_kernel;
         case LPK_REL: return (const void*)rel_rows_kernel;
         case LPK_MAP: return (const void*)map_rows_kernel;
+        case LPK_AUX_ITER4: return (const void*)aux_iter_kernel<4>;
+        case LPK_AUX_ITER16: return (const void*)aux_iter_kernel<16>;
     }
     return nullptr;
 }
@@ -1691,6 +1698,84 @@ int rvio_hip_get_aux_diag(rvio_hip* h, int instance, double* gamma, int32_t* app
     return RVIO_OK;
 }
 
+// ---- the measurement chain: what the device-linearised families (fixes, past-frame fixes, relative poses, map landmarks) share behind their
+// argument checks — the rows kernel and the aux launch on the rows it left, once (the plain path, as ever) or, with
+// rvio_hip_set_meas_iterations, max_iters times in a fixed sequence on the filter stream (include/rvio_hip.h: the iterated update)
+static_assert(sizeof(rvio_meas_iter) == 24 && LP_MEAS_MAX_ITERS == RVIO_MEAS_MAX_ITERS, "include/rvio_hip.h: the iteration record has no padding");
+// where a family's rows kernel leaves its rows for the aux launch (strides in doubles) and the (gamma, applied) pairs of its calls
+struct MeasRows { const double* H; size_t H_stride; const double* r; size_t r_stride; const double* sigma; size_t sigma_stride; double* pair; };
+static int meas_iter_ready(rvio_hip* h) {
+    if (h->mi.x0) return RVIO_OK;
+    const size_t B = (size_t)h->batch, n_x0 = sizeof(double) * meas_iter_x0_stride(h->dc.nmax) * B, n_dx = sizeof(double) * (size_t)h->dc.dmax * B, n_rec = sizeof(rvio_meas_iter) * B;
+    char* blk = nullptr;
+    RCCHK(own_dev(h, &blk, meas_iter_block_bytes(h->batch, h->dc.nmax, h->dc.dmax), true));
+    h->mi.dx = (double*)(blk + n_x0); h->mi.rec = (rvio_meas_iter*)(blk + n_x0 + n_dx); h->mi.run = (int32_t*)(blk + n_x0 + n_dx + n_rec);
+    h->mi.x0 = (double*)blk;
+    return RVIO_OK;
+}
+// one pass of the iterated update on the rows `rw`; d_flags: what the rows kernel of this pass left (pass 0: where to act at all)
+static int update_aux_iter_dev(rvio_hip* h, int m, int gate, const MeasRows& rw, const int32_t* d_flags, int pass) {
+    const int n = h->n_clones_host;
+    const LpLaunch l = aux_iter_launch(n, m, h->batch);
+    const size_t w = sizeof(double);
+    const AuxIter it = {h->mi.x0, h->mi.dx, h->mi.rec, (int*)h->mi.run, meas_iter_x0_stride(h->dc.nmax), (size_t)h->dc.dmax, pass, h->mi.max_iters - 1, h->mi.tol};
+    if (l.kernel == LPK_AUX_ITER4)
+        hipLaunchKernelGGL(aux_iter_kernel<4>, lp_grid(l), lp_block(l), l.lds, h->stream, n, h->dc.dmax, m, RVIO_AUX_RESIDUAL, gate, h->x[h->cur], h->P[h->cur], h->d_pose, h->meta,
+                           h->slab_bytes, rw.H, rw.H_stride * w, rw.r, rw.r_stride * w, rw.sigma, rw.sigma_stride * w, (const int*)d_flags, rw.pair, it);
+    else
+        hipLaunchKernelGGL(aux_iter_kernel<16>, lp_grid(l), lp_block(l), l.lds, h->stream, n, h->dc.dmax, m, RVIO_AUX_RESIDUAL, gate, h->x[h->cur], h->P[h->cur], h->d_pose, h->meta,
+                           h->slab_bytes, rw.H, rw.H_stride * w, rw.r, rw.r_stride * w, rw.sigma, rw.sigma_stride * w, (const int*)d_flags, rw.pair, it);
+    HIPCHK(h, hipGetLastError());
+    return RVIO_OK;
+}
+// rows(pass, flags) enqueues the family's rows kernel with `flags` as its d_active.  d_own: the flags that kernel writes itself (nullptr: it
+// keeps none, the aux launch gets the caller's).  Passes behind the first get the running flags of the block, which the aux launch of the
+// pass before cleared for every finished instance.  Ends with the drain of RVIO_PARANOID
+extern "C++" template <class Rows>
+static int meas_chain(rvio_hip* h, int m, int gate, const MeasRows& rw, const int32_t* d_active, const int32_t* d_own, Rows&& rows) {
+    const int K = h->mi.max_iters;
+    if (K > 1) RCCHK(meas_iter_ready(h));
+    h->mi.last_pair = rw.pair; h->mi.last_iterated = K > 1;
+    rows(0, d_active);
+    HIPCHK(h, hipGetLastError());
+    if (K == 1) {
+        RCCHK(update_aux_dev(h, m, RVIO_AUX_RESIDUAL, gate, rw.H, rw.H_stride, rw.r, rw.r_stride, rw.sigma, rw.sigma_stride, d_own ? d_own : d_active, rw.pair));
+    } else {
+        RCCHK(chol_drop(h, CHOL_FILTER_WAITS));   // (the final pass changes the covariance in place)
+        RCCHK(update_aux_iter_dev(h, m, gate, rw, d_own ? d_own : d_active, 0));
+        for (int i = 1; i < K; ++i) {
+            rows(i, h->mi.run);
+            HIPCHK(h, hipGetLastError());
+            RCCHK(update_aux_iter_dev(h, m, gate, rw, d_own, i));
+        }
+    }
+    if (paranoid_bits() & PAR_DRAIN) return drain_all(h);
+    return RVIO_OK;
+}
+int rvio_hip_set_meas_iterations(rvio_hip* h, int max_iters, double tol) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (max_iters < 1 || max_iters > RVIO_MEAS_MAX_ITERS) { h->err = "rvio_hip_set_meas_iterations: max_iters is outside 1 .. RVIO_MEAS_MAX_ITERS"; return RVIO_ERR_INVALID; }
+    if (!(std::isfinite(tol) && tol >= 0.0)) { h->err = "rvio_hip_set_meas_iterations: tol is not finite and >= 0"; return RVIO_ERR_INVALID; }
+    h->mi.max_iters = max_iters; h->mi.tol = tol;
+    return RVIO_OK;
+}
+int rvio_hip_get_meas_iterations(rvio_hip* h, int* max_iters, double* tol) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (max_iters) *max_iters = h->mi.max_iters;
+    if (tol) *tol = h->mi.tol;
+    return RVIO_OK;
+}
+// waits for the filter stream only
+int rvio_hip_get_meas_iter(rvio_hip* h, int instance, rvio_meas_iter* out) {
+    if (!h || !out || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
+    if (!h->mi.last_pair) { h->err = "rvio_hip_get_meas_iter before the first fix, past-fix, rel or map call"; return RVIO_ERR_STATE; }
+    double g; long long ap;
+    if (h->mi.last_iterated) return read_pair(h, h->mi.last_pair, instance, &g, &ap, out, h->mi.rec + instance, sizeof *out);
+    RCCHK(read_pair(h, h->mi.last_pair, instance, &g, &ap));
+    out->step = 0.0; out->gamma0 = g; out->iterations = 1; out->converged = 0;
+    return RVIO_OK;
+}
+
 // ------------------------------------------------------------------ standstill detection (standstill.hip)
 static_assert(sizeof(rvio_standstill_config) == 64 && sizeof(rvio_standstill) == 40, "include/rvio_hip.h: the standstill structs have no padding");
 void rvio_standstill_config_default(const rvio_config* cfg, rvio_standstill_config* out) {
@@ -1840,23 +1925,23 @@ static int fix_ready(rvio_hip* h, bool past) {
     return own_dev(h, &h->fp.flag, sizeof(int32_t) * (size_t)h->batch, true);
 }
 static size_t fix_H_stride(const rvio_hip* h) { return (size_t)LP_FIX_ROWS * h->dc.dmax; }   // doubles between the instances' rows
-// What the three producers share behind their own launch: kind, m and d for the getters, the RESIDUAL aux launch on the rows they left — it reads
-// them in stream order and acts where d_flags says — and the drain
-static int fix_consume(rvio_hip* h, int kind, int gate, const int32_t* d_flags) {
-    HIPCHK(h, hipGetLastError());
+// What the three producers share: kind, m and d for the getters, and the measurement chain on the fix block — their rows kernel (`rows`, as
+// meas_chain calls it) and the RESIDUAL aux launch on the rows it left, which reads them in stream order and acts where the flags say
+extern "C++" template <class Rows>
+static int fix_consume(rvio_hip* h, int kind, int gate, const int32_t* d_active, const int32_t* d_own, Rows&& rows) {
     const int m = (kind == RVIO_FIX_POSE || kind == RVIO_REL_POSE) ? 6 : 3;
     h->fx.kind = kind; h->fx.m = m; h->fx.d = 24 + 6 * h->n_clones_host;
-    RCCHK(update_aux_dev(h, m, RVIO_AUX_RESIDUAL, gate, h->fx.H, fix_H_stride(h), h->fx.r, 6, h->fx.sigma, 6, d_flags, h->fx.pair));
-    if (paranoid_bits() & PAR_DRAIN) return drain_all(h);
-    return RVIO_OK;
+    const MeasRows rw = {h->fx.H, fix_H_stride(h), h->fx.r, 6, h->fx.sigma, 6, h->fx.pair};
+    return meas_chain(h, m, gate, rw, d_active, d_own, rows);
 }
 // fix_bs: bytes between the instances' records (0: shared).  The kernel reads x of the current buffer, which the filter stream owns: it runs on
 // that stream, no event
 static int update_fix_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_bs, const int32_t* d_active) {
     const LpLaunch l = fix_launch(h->batch);
-    hipLaunchKernelGGL(fix_rows_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->n_clones_host, kind, h->dc.gravity, (const double*)h->x[h->cur], h->slab_bytes, d_fix, fix_bs,
-                       (const int*)d_active, h->img_count, h->fx.H, fix_H_stride(h) * sizeof(double), h->fx.r, h->fx.sigma, h->fx.rec, h->fx.pair);
-    return fix_consume(h, kind, gate, d_active);
+    return fix_consume(h, kind, gate, d_active, nullptr, [&](int, const int32_t* flags) {
+        hipLaunchKernelGGL(fix_rows_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->n_clones_host, kind, h->dc.gravity, (const double*)h->x[h->cur], h->slab_bytes, d_fix, fix_bs,
+                           (const int*)flags, h->img_count, h->fx.H, fix_H_stride(h) * sizeof(double), h->fx.r, h->fx.sigma, h->fx.rec, h->fx.pair);
+    });
 }
 int rvio_hip_update_fix_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_stride, const int32_t* d_active) {
     if (!fix_args_ok(h, d_fix, kind, RVIO_FIX_GRAVITY, gate)) return RVIO_ERR_INVALID;
@@ -1883,9 +1968,10 @@ int rvio_hip_update_fix(rvio_hip* h, int instance, int kind, int gate, const rvi
 // fix_bs: bytes between the instances' records (0: shared).  On the filter stream like update_fix_dev; the aux launch gets the kernel's own flags
 static int update_fix_past_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_bs, const int32_t* d_age, const double* d_frac, const int32_t* d_active) {
     const LpLaunch l = fix_past_launch(h->batch);
-    hipLaunchKernelGGL(fix_past_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->n_clones_host, kind, (const double*)h->x[h->cur], h->slab_bytes, d_fix, fix_bs, (const int*)d_age, d_frac,
-                       (const int*)d_active, h->composed_count, h->fx.H, fix_H_stride(h) * sizeof(double), h->fx.r, h->fx.sigma, h->fx.rec, h->fx.pair, (int*)h->fp.flag);
-    return fix_consume(h, kind, gate, h->fp.flag);
+    return fix_consume(h, kind, gate, d_active, h->fp.flag, [&](int, const int32_t* flags) {
+        hipLaunchKernelGGL(fix_past_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->n_clones_host, kind, (const double*)h->x[h->cur], h->slab_bytes, d_fix, fix_bs, (const int*)d_age, d_frac,
+                           (const int*)flags, h->composed_count, h->fx.H, fix_H_stride(h) * sizeof(double), h->fx.r, h->fx.sigma, h->fx.rec, h->fx.pair, (int*)h->fp.flag);
+    });
 }
 int rvio_hip_update_fix_past_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_fix, size_t fix_stride, const int32_t* d_age, const double* d_frac, const int32_t* d_active) {
     if (!fix_args_ok(h, d_fix, kind, RVIO_FIX_POSE, gate) || !d_age) return RVIO_ERR_INVALID;
@@ -1921,9 +2007,10 @@ static bool rel_args_ok(const rvio_hip* h, const rvio_fix* meas, int kind, int g
 // meas_bs: bytes between the instances' records (0: shared).  On the filter stream like update_fix_past_dev; the aux launch gets the kernel's own flags
 static int update_rel_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_meas, size_t meas_bs, const int32_t* d_age_new, const int32_t* d_age_old, const int32_t* d_active) {
     const LpLaunch l = rel_launch(h->batch);
-    hipLaunchKernelGGL(rel_rows_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->n_clones_host, kind, (const double*)h->x[h->cur], h->slab_bytes, d_meas, meas_bs, (const int*)d_age_new,
-                       (const int*)d_age_old, (const int*)d_active, h->composed_count, h->fx.H, fix_H_stride(h) * sizeof(double), h->fx.r, h->fx.sigma, h->fx.rec, h->fx.pair, (int*)h->fp.flag);
-    return fix_consume(h, kind, gate, h->fp.flag);
+    return fix_consume(h, kind, gate, d_active, h->fp.flag, [&](int, const int32_t* flags) {
+        hipLaunchKernelGGL(rel_rows_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->n_clones_host, kind, (const double*)h->x[h->cur], h->slab_bytes, d_meas, meas_bs, (const int*)d_age_new,
+                           (const int*)d_age_old, (const int*)flags, h->composed_count, h->fx.H, fix_H_stride(h) * sizeof(double), h->fx.r, h->fx.sigma, h->fx.rec, h->fx.pair, (int*)h->fp.flag);
+    });
 }
 int rvio_hip_update_rel_dev(rvio_hip* h, int kind, int gate, const rvio_fix* d_meas, size_t meas_stride, const int32_t* d_age_new, const int32_t* d_age_old, const int32_t* d_active) {
     if (!rel_args_ok(h, d_meas, kind, gate) || !d_age_new || !d_age_old) return RVIO_ERR_INVALID;
@@ -2023,14 +2110,13 @@ static int update_map_dev(rvio_hip* h, int units, int gate, int gate_each, int n
                           const int32_t* d_age, const int32_t* d_active) {
     const LpLaunch l = map_launch(h->batch);
     const size_t Hs = map_H_stride(h->dc.dmax);
-    hipLaunchKernelGGL(map_rows_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->dc, (const CamCal*)h->cal, h->n_clones_host, h->dc.dmax, units, gate_each, n_max,
-                       (const double*)h->x[h->cur], (const double*)h->P[h->cur], h->slab_bytes, d_obs, obs_bs, (const int*)d_count, (const int*)d_age, (const int*)d_active,
-                       h->composed_count, h->mp.H, Hs * sizeof(double), h->mp.r, h->mp.sigma, h->mp.rec, h->mp.pts, h->mp.pair, (int*)h->mp.flag);
-    HIPCHK(h, hipGetLastError());
     h->mp.m = 2 * n_max; h->mp.d = 24 + 6 * h->n_clones_host;
-    RCCHK(update_aux_dev(h, 2 * n_max, RVIO_AUX_RESIDUAL, gate, h->mp.H, Hs, h->mp.r, LP_MAP_ROWS, h->mp.sigma, LP_MAP_ROWS, h->mp.flag, h->mp.pair));
-    if (paranoid_bits() & PAR_DRAIN) return drain_all(h);
-    return RVIO_OK;
+    const MeasRows rw = {h->mp.H, Hs, h->mp.r, LP_MAP_ROWS, h->mp.sigma, LP_MAP_ROWS, h->mp.pair};
+    return meas_chain(h, 2 * n_max, gate, rw, d_active, h->mp.flag, [&](int pass, const int32_t* flags) {
+        hipLaunchKernelGGL(map_rows_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->dc, (const CamCal*)h->cal, h->n_clones_host, h->dc.dmax, units, gate_each, n_max,
+                           (const double*)h->x[h->cur], (const double*)h->P[h->cur], h->slab_bytes, d_obs, obs_bs, (const int*)d_count, (const int*)d_age, (const int*)flags,
+                           h->composed_count, h->mp.H, Hs * sizeof(double), h->mp.r, h->mp.sigma, h->mp.rec, h->mp.pts, h->mp.pair, (int*)h->mp.flag, pass);
+    });
 }
 int rvio_hip_update_map_dev(rvio_hip* h, int units, int gate, int gate_each, int n_max, const rvio_map_obs* d_obs, size_t obs_stride, const int32_t* d_count,
                             const int32_t* d_age, const int32_t* d_active) {

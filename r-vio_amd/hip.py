@@ -36,6 +36,7 @@ SYMBOLS = [
     "rvio_hip_update_fix_past", "rvio_hip_update_fix_past_dev", "rvio_hip_frame_age",
     "rvio_hip_update_rel", "rvio_hip_update_rel_dev",
     "rvio_hip_update_map", "rvio_hip_update_map_dev", "rvio_hip_get_map", "rvio_hip_get_map_rows",
+    "rvio_hip_set_meas_iterations", "rvio_hip_get_meas_iterations", "rvio_hip_get_meas_iter",
 ]
 
 _LIB = None
@@ -680,3 +681,21 @@ class RvioHip:
         self._ck(self.L.rvio_hip_get_map_rows(self.h, int(instance), C.byref(m), C.byref(d), H.ctypes.data_as(dp), r.ctypes.data_as(dp), sigma.ctypes.data_as(dp)),
                  "get_map_rows")
         return H, r, sigma
+
+    # ---- iterated measurement updates: the fix, past-fix, rel and map calls relinearised max_iters times on the device
+    def set_meas_iterations(self, max_iters, tol=0.0):
+        """a handle setting: 1 .. abi.RVIO_MEAS_MAX_ITERS passes, an instance finished once max |dx_new - dx| < tol (0: always max_iters passes);
+        1 (the default) is the plain update"""
+        self._ck(self.L.rvio_hip_set_meas_iterations(self.h, int(max_iters), C.c_double(float(tol))), "set_meas_iterations")
+
+    def get_meas_iterations(self):
+        """(max_iters, tol) as set"""
+        k, t = C.c_int(0), C.c_double(0)
+        self._ck(self.L.rvio_hip_get_meas_iterations(self.h, C.byref(k), C.byref(t)), "get_meas_iterations")
+        return int(k.value), float(t.value)
+
+    def get_meas_iter(self, instance=0):
+        """the abi.rvio_meas_iter record of one instance from the last fix / past-fix / rel / map call (waits for the filter stream only)"""
+        r = abi.rvio_meas_iter()
+        self._ck(self.L.rvio_hip_get_meas_iter(self.h, int(instance), C.byref(r)), "get_meas_iter")
+        return r
