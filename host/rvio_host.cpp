@@ -209,8 +209,10 @@ bool System::last_meas_iter(rvio_meas_iter* out) {
 System::~System() {
     if (!ss_path_.empty()) (void)flush_standstill();
     if (f_od_ && h_) (void)flush_odometry();
+    if (f_sm_ && h_) (void)flush_smoothed();
     if (f_io_ && h_) (void)flush_imu_odometry();
     delete static_cast<std::ofstream*>(f_od_);
+    delete static_cast<std::ofstream*>(f_sm_);
     delete static_cast<std::ofstream*>(f_io_);
     delete static_cast<std::ofstream*>(f_pose_);
     delete static_cast<std::ofstream*>(f_time_);
@@ -291,6 +293,51 @@ int System::flush_odometry() {
         od_read_ = r.seq;
     }
     f.flush();
+    return 0;
+}
+
+bool System::record_smoothed_to(const std::string& path, int lag, int ring) {
+    if (!h_) return false;
+    if (ring < 1) { err_ = "the smoothed-odometry ring holds at least one record"; return false; }
+    auto* f = new std::ofstream(path, std::ofstream::out);
+    if (!*f) { delete f; err_ = "cannot write " + path; return false; }
+    if (f_sm_) (void)flush_smoothed();
+    if (rvio_hip_set_smoothed_odometry(h_, ring, lag) != RVIO_OK) { delete f; err_ = rvio_hip_last_error(h_); return false; }
+    delete static_cast<std::ofstream*>(f_sm_);
+    f_sm_ = f;
+    sm_ring_ = ring;
+    sm_buf_.assign((size_t)ring, rvio_window_pose{});
+    // (records written from here on are read from here on, like record_odometry_to)
+    int64_t s = 0;
+    sm_read_ = (ready_ && rvio_hip_get_smoothed_odometry_all(h_, sm_buf_.data(), &s) == RVIO_OK) ? (long long)s : 0;
+    sm_new_ = 0;
+    return true;
+}
+
+// behind a frame handed to the filter: its count and stamp join the queue; the ring is read when half of it may be outstanding
+int System::note_smoothed(double t) {
+    sm_t_.emplace_back(n_img_, t);
+    if (++sm_new_ >= std::max(1, sm_ring_ / 2)) return flush_smoothed();
+    return 0;
+}
+
+int System::flush_smoothed() {
+    if (!f_sm_ || sm_new_ == 0) return 0;
+    int32_t n = 0;
+    if (rvio_hip_get_smoothed_odometry(h_, 0, sm_read_ + 1, sm_ring_, sm_buf_.data(), &n) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+    auto& f = *static_cast<std::ofstream*>(f_sm_);
+    for (int i = 0; i < n; ++i) {
+        const rvio_window_pose& r = sm_buf_[(size_t)i];
+        // (the stamps of frames older than the one this record describes belong to records that were never written or were overwritten)
+        while (!sm_t_.empty() && sm_t_.front().first < r.img_count) sm_t_.pop_front();
+        if (!sm_t_.empty() && sm_t_.front().first == r.img_count) {
+            f << format_smoothed(sm_t_.front().second, r);
+            sm_t_.pop_front();
+        }
+        sm_read_ = r.seq;
+    }
+    f.flush();
+    sm_new_ = 0;
     return 0;
 }
 
@@ -783,6 +830,9 @@ int System::MonoVIO(PoseLine* pose) {
                 if (rvio_hip_initialize(h_, wm_, am_, n_imu_) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
                 ready_ = true;
                 stamps_.clear();
+                // (rvio_hip_initialize restarts the handle's frame count and empties the smoothed ring: the stamps, which are matched to records by
+                // that count — n_img_ mirrors it, both count the frames handed to the filter since this point —, start over with it)
+                sm_t_.clear(); sm_read_ = 0; sm_new_ = 0;
                 break;
             }
         }
@@ -820,6 +870,7 @@ int System::MonoVIO(PoseLine* pose) {
         }
         if (f_lm_ && write_landmarks(image.t) < 0) return -1;
         if (f_od_ && note_odometry(image.t) < 0) return -1;
+        if (f_sm_ && note_smoothed(image.t) < 0) return -1;
         if (f_io_ && note_imu_odometry(m) < 0) return -1;
         return 1;
     }
@@ -849,6 +900,7 @@ int System::MonoVIO(PoseLine* pose) {
     ft << format_time_cost(n_img_, t2 - t1, t3 - t2); ft.flush();
     if (f_lm_ && write_landmarks(image.t) < 0) return -1;
     if (f_od_ && note_odometry(image.t) < 0) return -1;
+    if (f_sm_ && note_smoothed(image.t) < 0) return -1;
     if (f_io_ && note_imu_odometry(m) < 0) return -1;
     if (pose) *pose = pl;
     return 1;
@@ -878,6 +930,13 @@ std::string format_odometry(double t, const rvio_odom& r) {
     for (double v : r.pose_cov) add(v);
     out += "\n";
     return out;
+}
+
+std::string format_smoothed(double t, const rvio_window_pose& r) {
+    rvio_odom o{};
+    o.seq = r.seq;
+    std::copy(r.p, r.p + 3, o.p); std::copy(r.q, r.q + 4, o.q); std::copy(r.pose_cov, r.pose_cov + 36, o.pose_cov);
+    return format_odometry(t, o);
 }
 
 std::string format_imu_odometry(const rvio_imu_pose& r) {

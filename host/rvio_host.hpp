@@ -177,6 +177,12 @@ public:
     // destructor): the pipelined frame is no longer drained once per image for its pose.  One line per frame, format_odometry.
     bool record_odometry_to(const std::string& path, int ring = 256);
     int flush_odometry();         // 0, or -1 on a library error (error())
+    // The fixed-lag smoothed trajectory: enables the handle's smoothed-odometry ring (rvio_hip_set_smoothed_odometry, `ring` records, the frame
+    // `lag` images back behind every frame) and keeps the image stamps by frame count on the host: a record's stamp is that of the image it
+    // describes, `lag` frames before the one it was written behind.  Read like the odometry ring (flush_smoothed, also run by the destructor).
+    // One line per record, format_smoothed: the layout of the odometry file.
+    bool record_smoothed_to(const std::string& path, int lag, int ring = 256);
+    int flush_smoothed();         // 0, or -1 on a library error (error())
     // A dense trajectory: one pose per IMU sample (200 Hz against the 20 Hz of stamped_pose_ests.dat), the pose line MonoVIO would write if an
     // image arrived right behind that sample and ran no update.  Enables the handle's IMU-rate ring (rvio_hip_set_imu_odometry, `ring` samples)
     // and reads it with ONE rvio_hip_get_imu_odometry whenever ring / 2 samples are outstanding and once more at the end
@@ -298,6 +304,12 @@ private:
     std::deque<double> od_t_;     // image timestamps of the records not yet written: front() belongs to seq od_read_ + 1
     std::vector<rvio_odom> od_buf_;
     int note_odometry(double t);
+    void* f_sm_ = nullptr;        // std::ofstream* of record_smoothed_to
+    int sm_ring_ = 0, sm_new_ = 0;         // sm_new_: frames handed to the filter since the ring was last read
+    long long sm_read_ = 0;       // seq of the last record written to the file
+    std::deque<std::pair<int, double>> sm_t_;   // (frame count, image stamp) of the frames no record has described yet, oldest first
+    std::vector<rvio_window_pose> sm_buf_;
+    int note_smoothed(double t);
     long long last_seq();
     void* f_io_ = nullptr;        // std::ofstream* of record_imu_odometry_to
     int io_ring_ = 0;
@@ -349,6 +361,8 @@ std::string format_pose(const PoseLine& p);               // one line of stamped
 std::string format_landmarks(double t, int frame, int n, const int32_t* feat, const double* p_world, const double* p_r);
 // one record of the odometry ring: t seq px py pz qx qy qz qw vx vy vz c00 ... c55 (pose_cov row by row), %.19g
 std::string format_odometry(double t, const rvio_odom& r);
+// one record of the smoothed-odometry ring in the same layout; the three velocity columns are 0 (the window holds no velocity of a past frame)
+std::string format_smoothed(double t, const rvio_window_pose& r);
 // one record of the IMU-rate ring: t px py pz qx qy qz qw vx vy vz, %.19g (setprecision(19), like stamped_pose_ests.dat)
 std::string format_imu_odometry(const rvio_imu_pose& r);
 // the same line with the paired covariance record behind it: the 21 entries of pose_cov's upper triangle row by row (c00 c01 ... c05 c11 ... c55, order

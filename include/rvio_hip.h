@@ -690,6 +690,57 @@ int rvio_hip_update_fix_past_dev(rvio_hip* h, int kind, int gate, const rvio_fix
  * not composed yet.  RVIO_ERR_INVALID: NULL argument, no state, a frame not yet composed, a frame that has left the clone window. */
 int rvio_hip_frame_age(rvio_hip* h, int img_count, int* age);
 
+/* --- fixed-lag smoothed trajectory: pose and covariance of every frame of the clone window (no reference counterpart) ------------- */
+/* rvio_hip_get_pose, the odometry ring and the IMU-rate rings publish the FILTER pose of the newest frame: frame k given measurements up to k.
+ * The window holds better: clone i is the relative pose between two consecutive images, and every later camera update, delayed fix,
+ * relative-pose measurement and map observation corrects it.  The world pose of the image `age` frames back, composed from (qG, pG) and the
+ * newest `age` clones AS THEY ARE NOW, is a fixed-lag smoothed estimate, and its covariance follows from P — what a mapper, a loop-closure back
+ * end, anything that stitches point clouds or key frames wants, `age` frames late.  window_pose_kernel (csrc/window_pose.hip, one workgroup per
+ * (instance, age), FP64) forms it on the device; nothing of x or P crosses PCIe.
+ * With the chain (A_m, t_m) of the past-fix table above, lever 0 and frac 0:
+ *   p = R_G^T (t_a - pG)     the world position of the IMU at that image     R(q) = A_a^T R_G     world -> IMU at that image
+ * in the frames and conventions of rvio_hip_get_pose; at age 0 they ARE that pose line (behind a whole frame).  The sign of q: at age 0 the
+ * bits of x[0..3] (what rvio_odom.q carries); at age > 0 RotToQuat's (util/Numerics.h:126-167), normalised with q[3] >= 0.
+ *   pose_cov = (C + C^T) / 2,  C = J P J^T,  J = the three POSITION rows (lever 0, frac 0) over the three ATTITUDE rows of the past-fix table at
+ * age a: row-major 6 x 6 in the order and error convention of rvio_odom.pose_cov (x, y, z, then the world-frame rotation error phi), exactly
+ * symmetric; at a = 0 J is rvio_odom's.
+ * NOT done: cross-covariances between frames of the window; the pose of the frame that has just left the window; time stamps in the record (the
+ * host knows the stamp of every img_count); interpolation between frames. */
+typedef struct rvio_window_pose {   /* 368 bytes, no padding */
+    int64_t seq;          /* smoothed-odometry ring: 1, 2, ... records written; rvio_hip_get_window*: 0 */
+    int32_t img_count;    /* the count of the frame the record describes: the reference frame's count minus age (-1: age outside the window) */
+    int32_t age;          /* images back from the state's reference frame */
+    int32_t n_clones;     /* nCloneStates when the record was formed */
+    int32_t reserved;     /* 0 */
+    double p[3];
+    double q[4];
+    double pose_cov[36];
+} rvio_window_pose;
+/* The records of ages 0 .. min(n_clones, max_n - 1) of one instance, newest frame first, linearised at the state the call finds; *n = how many.
+ * One launch on the filter stream; waits for the filter stream only, like rvio_hip_get_pose.  seq = 0.  The first call allocates its staging
+ * (max_track_len records), outside the filter slab.  RVIO_ERR_STATE: no state yet (rvio_hip_set_state / rvio_hip_initialize);
+ * RVIO_ERR_INVALID: NULL handle, out or n, instance out of range, max_n < 1 (rvio_hip_last_error). */
+int rvio_hip_get_window(rvio_hip* h, int instance, int max_n, rvio_window_pose* out, int32_t* n);
+/* Every instance, ages age_first .. age_first + n_ages - 1, into a device buffer: record (instance, age) lies at
+ * d_out[instance * out_stride + age - age_first].  Asynchronous on the filter stream: nothing is waited for or read back.  An age beyond the
+ * instance's window writes a record with img_count = -1, n_clones set and every other member 0.  RVIO_ERR_STATE: no state yet;
+ * RVIO_ERR_INVALID: NULL handle or d_out, age_first < 0, n_ages outside 1 .. 65535, out_stride < n_ages.  (With a state handed in through
+ * rvio_hip_set_state before any frame the reference frame's count is 0 and img_count = -age: tell such a record from one beyond the window by
+ * its age, which is 0 there.) */
+int rvio_hip_get_window_dev(rvio_hip* h, int age_first, int n_ages, rvio_window_pose* d_out, size_t out_stride);
+/* The smoothed-odometry ring: behind the augmentation / composition stage of every path (and behind the odometry record, on the filter stream)
+ * one record per instance of the frame `lag` images back, into a ring with exactly the capacity, layout, wrap, empty, stop and 1-GiB rules of
+ * rvio_hip_set_odometry (capacity 0 .. 65536; 0 = off, the default: such a handle allocates and launches what it did before these entry points
+ * existed).  lag = 0 .. max_track_len - 1; lag = max_track_len - 1 is the most-smoothed pose still in the window.  A frame is recorded only when
+ * n_clones >= lag behind its stage: until the window has grown to `lag` there is no record and seq does not advance (the host knows the clone
+ * count: nothing is read back to decide).  Another lag empties the ring like another capacity (seq restarts at 1); rvio_hip_initialize empties
+ * it.  RVIO_ERR_INVALID: NULL handle, capacity outside 0 .. 65536, lag outside 0 .. max_track_len - 1 (rvio_hip_last_error);
+ * RVIO_ERR_UNSUPPORTED: capacity x instances x 368 bytes exceeds 1 GiB. */
+int rvio_hip_set_smoothed_odometry(rvio_hip* h, int capacity, int lag);
+/* rvio_hip_get_odometry's and rvio_hip_get_odometry_all's clauses.  RVIO_ERR_STATE: the ring was never enabled. */
+int rvio_hip_get_smoothed_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_window_pose* out, int32_t* n);
+int rvio_hip_get_smoothed_odometry_all(rvio_hip* h, rvio_window_pose* out /* batch records */, int64_t* seq);
+
 /* --- relative-pose measurements: a delta pose between two frames of the clone window (no reference counterpart) ------------------ */
 /* What most other sensors on a robot produce is neither a state entry nor a world-frame fix but a DELTA POSE BETWEEN TWO INSTANTS: a wheel-odometry
  * integrator, lidar or radar scan matching, a second visual odometry, a loop closure inside the window, the statement "the platform did not move

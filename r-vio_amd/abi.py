@@ -624,6 +624,95 @@ def fix_past_model(x, kind, fix, age, frac=0.0):
     return np.vstack(rows_H), np.concatenate(rows_r), np.concatenate(rows_s)
 
 
+# ---- fixed-lag smoothed trajectory (rvio_hip_get_window*, rvio_hip_set_smoothed_odometry, csrc/window_pose.hip)
+class rvio_window_pose(C.Structure):
+    """the pose and covariance of the frame `age` images back from the state's reference frame: 368 bytes, no padding"""
+    _fields_ = [("seq", C.c_int64), ("img_count", C.c_int32), ("age", C.c_int32), ("n_clones", C.c_int32), ("reserved", C.c_int32),
+                ("p", C.c_double * 3), ("q", C.c_double * 4), ("pose_cov", C.c_double * 36)]
+
+
+WINDOW_POSE_DTYPE = np.dtype([("seq", "i8"), ("img_count", "i4"), ("age", "i4"), ("n_clones", "i4"), ("reserved", "i4"),
+                              ("p", "f8", 3), ("q", "f8", 4), ("pose_cov", "f8", (6, 6))])
+assert WINDOW_POSE_DTYPE.itemsize == C.sizeof(rvio_window_pose) == 368
+
+
+def window_pose_jacobian(x, age):
+    """J (6 x d): the three POSITION rows (lever 0, frac 0) over the three ATTITUDE rows of the past-fix table at `age`"""
+    x = np.asarray(x, float)
+    A, t = _fix_past_chain(x, age)
+    l = np.zeros(3)
+    return np.vstack([_fix_past_rows(x, age, l, A, t, False), _fix_past_rows(x, age, l, A, t, True)])
+
+
+def window_pose_model(x, P, age):
+    """NumPy float64 model of csrc/window_pose.hip: (p, q, cov) of the frame `age` images back from the reference frame of the state x —
+    p = R_G^T (t_a - pG), q = RotToQuat(A_a^T R_G) (age 0: x[0:4] as it is), cov = (C + C^T) / 2 with C = J P J^T.  Calls nothing from the
+    library or the oracle."""
+    x, P = np.asarray(x, float), np.asarray(P, float)
+    A, t = _fix_past_chain(x, age)
+    RG = quat_to_rot(x[0:4])
+    p = RG.T @ (t[age] - x[4:7])
+    q = x[0:4].copy() if age == 0 else rot_to_quat(A[age].T @ RG)
+    J = window_pose_jacobian(x, age)
+    Cm = J @ P @ J.T
+    return p, q, 0.5 * (Cm + Cm.T)
+
+
+def window_pose_model_as(x, P, age, dtype=np.longdouble):
+    """The twin of window_pose_model evaluated in `dtype` throughout (np.longdouble: the truth the tests hold the device and the float64 model
+    to): the same chain, rows and products, written out so that no intermediate passes through float64.  Returns (p, q, cov) in `dtype`."""
+    x, P = np.asarray(x, dtype), np.asarray(P, dtype)
+    n = (len(x) - 26) // 7
+    assert 0 <= age <= n, "age outside the window"
+    one, two, half = dtype(1), dtype(2), dtype(1) / dtype(2)
+
+    def skew(w):
+        S = np.zeros((3, 3), dtype)
+        S[0, 1], S[0, 2], S[1, 0], S[1, 2], S[2, 0], S[2, 1] = -w[2], w[1], w[2], -w[0], -w[1], w[0]
+        return S
+
+    def q2r(q):
+        qx = skew(q[:3])
+        return np.eye(3, dtype=dtype) - two * q[3] * qx + two * (qx @ qx)
+
+    def r2q(R):
+        T = R[0, 0] + R[1, 1] + R[2, 2]
+        d = [R[0, 0], R[1, 1], R[2, 2]]
+        q = np.zeros(4, dtype)
+        big = [i for i in range(3) if d[i] > T and all(d[i] > d[j] for j in range(3) if j != i)]
+        if big:
+            i = big[0]
+            j, k = (i + 1) % 3, (i + 2) % 3
+            q[i] = np.sqrt((one + two * d[i] - T) / dtype(4))
+            s = one / (dtype(4) * q[i])
+            q[j], q[k], q[3] = s * (R[i, j] + R[j, i]), s * (R[i, k] + R[k, i]), s * (R[j, k] - R[k, j])
+        else:
+            q[3] = np.sqrt((one + T) / dtype(4))
+            s = one / (dtype(4) * q[3])
+            q[0], q[1], q[2] = s * (R[1, 2] - R[2, 1]), s * (R[2, 0] - R[0, 2]), s * (R[0, 1] - R[1, 0])
+        q = q / np.sqrt(q @ q)
+        return -q if q[3] < 0 else q
+
+    A, t = [np.eye(3, dtype=dtype)], [np.zeros(3, dtype)]
+    for m in range(1, age + 1):
+        i = n - m
+        A.append(A[-1] @ q2r(x[26 + 7 * i: 30 + 7 * i]))
+        t.append(t[-1] - A[-1] @ x[30 + 7 * i: 33 + 7 * i])
+    RG = q2r(x[0:4])
+    RGt = RG.T
+    u = t[age]
+    J = np.zeros((6, 24 + 6 * n), dtype)
+    J[0:3, 0:3], J[0:3, 3:6], J[3:6, 0:3] = -RGt @ skew(u - x[4:7]), -RGt, RGt
+    for m in range(1, age + 1):
+        c = 24 + 6 * (n - m)
+        J[0:3, c: c + 3], J[0:3, c + 3: c + 6] = RGt @ skew(u - t[m - 1]) @ A[m - 1], -RGt @ A[m]
+        J[3:6, c: c + 3] = -RGt @ A[m - 1]
+    Cm = J @ P @ J.T
+    p = RGt @ (u - x[4:7])
+    q = x[0:4].copy() if age == 0 else r2q(A[age].T @ RG)
+    return p, q, half * (Cm + Cm.T)
+
+
 # ---- relative-pose measurements between two frames of the window (rvio_hip_update_rel*, csrc/rel_rows.hip in front of the auxiliary update)
 RVIO_REL_POSITION, RVIO_REL_ATTITUDE, RVIO_REL_POSE = 16, 17, 18      # = 16 + the fix kind
 REL_KINDS = (RVIO_REL_POSITION, RVIO_REL_ATTITUDE, RVIO_REL_POSE)

@@ -32,6 +32,7 @@
 #include "fix_rows.hip"    // absolute fixes in front of it: position, attitude, pose, gravity rows linearised at the current state (rvio_hip_update_fix)
 #include "fix_past.hip"    // ... and delayed ones, linearised against the pose the clone window holds for the frame they were taken at (rvio_hip_update_fix_past)
 #include "rel_rows.hip"    // relative poses between two frames of the window, linearised against the clones between them (rvio_hip_update_rel)
+#include "window_pose.hip" // the fixed-lag smoothed trajectory: pose and covariance of every frame of the window (rvio_hip_get_window, rvio_hip_set_smoothed_odometry)
 #pragma clang fp contract(off)
 #include "frontend_kernels.hip"
 #include "map_rows.hip"    // map landmarks: pixel observations of known world points at a past image, gated per point against P (rvio_hip_update_map)
@@ -192,6 +193,11 @@ struct rvio_hip {
     // odometry ring (odom_kernel behind every augment/compose stage): allocated by rvio_hip_set_odometry, outside the slab (a handle that never
     // enables it keeps its memory layout and its launches)
     DevRing<rvio_odom> odom{"odometry", "rvio_hip_set_odometry"};
+    // smoothed-odometry ring (window_pose_kernel behind odom_kernel's place in every augment/compose stage, the record of age smo_lag): allocated by
+    // rvio_hip_set_smoothed_odometry, outside the slab.  win_buf: the staging of rvio_hip_get_window (nmax + 1 records), allocated by its first call
+    DevRing<rvio_window_pose> smo{"smoothed-odometry", "rvio_hip_set_smoothed_odometry"};
+    int smo_lag = 0;
+    rvio_window_pose* win_buf = nullptr;
     // IMU-rate ring (imu_pose_kernel in front of whatever propagates in place): allocated by rvio_hip_set_imu_odometry, outside the slab;
     // imuo.seq counts the samples recorded (the m of every propagate while the ring is on)
     DevRing<rvio_imu_pose> imuo{"IMU-rate odometry", "rvio_hip_set_imu_odometry"};
@@ -625,6 +631,7 @@ static const void* lp_kernel_fn(int k) {
         case LPK_MAP: return (const void*)map_rows_kernel;
         case LPK_AUX_ITER4: return (const void*)aux_iter_kernel<4>;
         case LPK_AUX_ITER16: return (const void*)aux_iter_kernel<16>;
+        case LPK_WINDOW_POSE: return (const void*)window_pose_kernel;
     }
     return nullptr;
 }
@@ -915,6 +922,7 @@ int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n
     h->img_count = 0;
     h->lm_frame = -1;   // no cloud since initialisation (the enable flag stays)
     h->odom.seq = 0;    // ... and no odometry record: seq restarts at 1 (the getters read nothing beyond seq)
+    h->smo.seq = 0;     // ... nor a smoothed one
     h->imuo.seq = 0;    // ... nor an IMU-rate record
     h->imuc.seq = 0; h->imuc_first = 1;   // ... nor its covariance
     // a (re-)initialised filter starts with an empty window: the tracker starts over too (mbIsTheFirstImage, Tracker.cc:88), or its
@@ -1469,6 +1477,80 @@ int rvio_hip_get_odometry_all(rvio_hip* h, rvio_odom* out, int64_t* seq) {
     if (seq) *seq = h->odom.seq;
     if (h->odom.seq == 0) return RVIO_OK;
     HIPCHK(h, hipMemcpyAsync(out, h->odom.slot(h->odom.seq, h->batch), sizeof(rvio_odom) * h->batch, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RVIO_OK;
+}
+
+// ------------------------------------------------------------------ fixed-lag smoothed trajectory (window_pose.hip)
+static_assert(sizeof(rvio_window_pose) == 8 * LP_WINP_WORDS, "include/rvio_hip.h: rvio_window_pose has no padding");
+static_assert(RVIO_MAX_LEN - 1 <= LP_FIXP_NMAX, "launch_plan.h: the chain window_pose_kernel holds reaches every window a handle accepts");
+// window_pose_kernel on `instances` instances from x / P on (instance z lies slab_bytes behind), ages age_first .. age_first + n_ages - 1, record
+// (z, age) into out[z * out_stride + age - age_first]; the filter stream, which owns x and P
+static void launch_window_pose(rvio_hip* h, int instances, const double* x, const double* P, int age_first, int n_ages, long long seq, rvio_window_pose* out,
+                               size_t out_stride) {
+    const LpLaunch l = window_pose_launch(instances, n_ages);
+    hipLaunchKernelGGL(window_pose_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->n_clones_host, h->dc.dmax, x, P, h->slab_bytes, age_first, h->composed_count,
+                       seq, (unsigned long long*)out, out_stride);
+}
+static int window_check(rvio_hip* h, const char* entry) {
+    if (!h->has_state) { h->err = std::string(entry) + " before the first rvio_hip_set_state / rvio_hip_initialize"; return RVIO_ERR_STATE; }
+    return RVIO_OK;
+}
+int rvio_hip_get_window(rvio_hip* h, int instance, int max_n, rvio_window_pose* out, int32_t* n) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (!out || !n) { h->err = "rvio_hip_get_window: NULL out or n"; return RVIO_ERR_INVALID; }
+    if (instance < 0 || instance >= h->batch) { h->err = "rvio_hip_get_window: instance out of range"; return RVIO_ERR_INVALID; }
+    if (max_n < 1) { h->err = "rvio_hip_get_window: max_n < 1"; return RVIO_ERR_INVALID; }
+    RCCHK(window_check(h, "rvio_hip_get_window"));
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->win_buf) RCCHK(own_dev(h, &h->win_buf, sizeof(rvio_window_pose) * (size_t)(h->dc.nmax + 1)));
+    const int cnt = std::min(h->n_clones_host + 1, max_n);
+    const size_t off = (size_t)instance * h->slab_bytes;
+    launch_window_pose(h, 1, (const double*)((const char*)h->x[h->cur] + off), (const double*)((const char*)h->P[h->cur] + off), 0, cnt, 0, h->win_buf, (size_t)cnt);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out, h->win_buf, sizeof(rvio_window_pose) * (size_t)cnt, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *n = cnt;
+    return RVIO_OK;
+}
+int rvio_hip_get_window_dev(rvio_hip* h, int age_first, int n_ages, rvio_window_pose* d_out, size_t out_stride) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (!d_out) { h->err = "rvio_hip_get_window_dev: NULL d_out"; return RVIO_ERR_INVALID; }
+    if (age_first < 0 || n_ages < 1 || n_ages > 65535) { h->err = "rvio_hip_get_window_dev: age_first < 0 or n_ages outside 1 .. 65535"; return RVIO_ERR_INVALID; }
+    if (out_stride < (size_t)n_ages) { h->err = "rvio_hip_get_window_dev: out_stride is below n_ages"; return RVIO_ERR_INVALID; }
+    RCCHK(window_check(h, "rvio_hip_get_window_dev"));
+    HIPCHK(h, hipSetDevice(h->device));
+    launch_window_pose(h, h->batch, h->x[h->cur], h->P[h->cur], age_first, n_ages, 0, d_out, out_stride);
+    HIPCHK(h, hipGetLastError());
+    return RVIO_OK;
+}
+// the ring: rvio_hip_set_odometry's clauses; another lag empties a ring that stays (nothing in flight writes it: drained first)
+int rvio_hip_set_smoothed_odometry(rvio_hip* h, int capacity, int lag) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (lag < 0 || lag > h->cfg.max_track_len - 1) { h->err = "rvio_hip_set_smoothed_odometry: lag outside 0 .. max_track_len - 1"; return RVIO_ERR_INVALID; }
+    if (capacity < 0 || capacity > 65536) { h->err = "rvio_hip_set_smoothed_odometry: capacity outside 0 .. 65536"; return RVIO_ERR_INVALID; }
+    const bool kept = capacity > 0 && capacity == h->smo.cap;
+    RCCHK(ring_set_capacity(h, h->smo, capacity, 65536));
+    if (capacity == 0) return RVIO_OK;
+    if (kept && lag != h->smo_lag) {
+        { const int rc = drain_all(h); if (rc != RVIO_OK) return rc; }
+        HIPCHK(h, hipMemsetAsync(h->smo.ring, 0, sizeof(rvio_window_pose) * (size_t)h->smo.cap * h->batch, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        h->smo.seq = 0;
+    }
+    h->smo_lag = lag;
+    return RVIO_OK;
+}
+int rvio_hip_get_smoothed_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_window_pose* out, int32_t* n) {
+    return h ? ring_read(h, h->smo, instance, first_seq, max_n, out, n) : RVIO_ERR_INVALID;
+}
+int rvio_hip_get_smoothed_odometry_all(rvio_hip* h, rvio_window_pose* out, int64_t* seq) {
+    if (!h || !out) return RVIO_ERR_INVALID;
+    if (!ring_exists(h, h->smo)) return RVIO_ERR_STATE;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (seq) *seq = h->smo.seq;
+    if (h->smo.seq == 0) return RVIO_OK;
+    HIPCHK(h, hipMemcpyAsync(out, h->smo.slot(h->smo.seq, h->batch), sizeof(rvio_window_pose) * h->batch, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RVIO_OK;
 }
@@ -2209,6 +2291,12 @@ static int augment_compose_dev(rvio_hip* h, int do_augment) {
     if (h->odom.on) {
         h->odom.seq++;
         launch_odom(h, h->odom.slot(h->odom.seq, h->batch), h->odom.seq);
+        HIPCHK(h, hipGetLastError());
+    }
+    // the smoothed record behind it, same stream, same inputs: the frame smo_lag images back, once the window reaches that far
+    if (h->smo.on && h->n_clones_host >= h->smo_lag) {
+        h->smo.seq++;
+        launch_window_pose(h, h->batch, h->x[h->cur], h->P[h->cur], h->smo_lag, 1, h->smo.seq, h->smo.slot(h->smo.seq, h->batch), 1);
         HIPCHK(h, hipGetLastError());
     }
     return RVIO_OK;

@@ -34,6 +34,7 @@ SYMBOLS = [
     "rvio_standstill_config_default", "rvio_hip_set_standstill", "rvio_hip_standstill", "rvio_hip_standstill_dev", "rvio_hip_get_standstill",
     "rvio_hip_update_fix", "rvio_hip_update_fix_dev", "rvio_hip_get_fix", "rvio_hip_get_fix_rows",
     "rvio_hip_update_fix_past", "rvio_hip_update_fix_past_dev", "rvio_hip_frame_age",
+    "rvio_hip_get_window", "rvio_hip_get_window_dev", "rvio_hip_set_smoothed_odometry", "rvio_hip_get_smoothed_odometry", "rvio_hip_get_smoothed_odometry_all",
     "rvio_hip_update_rel", "rvio_hip_update_rel_dev",
     "rvio_hip_update_map", "rvio_hip_update_map_dev", "rvio_hip_get_map", "rvio_hip_get_map_rows",
     "rvio_hip_set_meas_iterations", "rvio_hip_get_meas_iterations", "rvio_hip_get_meas_iter",
@@ -497,6 +498,44 @@ class RvioHip:
         out = np.zeros(self.batch, abi.ODOM_DTYPE)
         seq = C.c_int64(0)
         self._ck(self.L.rvio_hip_get_odometry_all(self.h, out.ctypes.data_as(C.POINTER(abi.rvio_odom)), C.byref(seq)), "get_odometry_all")
+        return int(seq.value), out
+
+    # ---- fixed-lag smoothed trajectory (csrc/window_pose.hip)
+    def get_window(self, instance=0, max_n=None):
+        """pose and covariance of the frames of ages 0 .. min(n_clones, max_n - 1) of one instance, newest first, at the state as it is now
+        (abi.WINDOW_POSE_DTYPE)"""
+        cap = self.nmax + 1 if max_n is None else int(max_n)
+        out = np.zeros(max(cap, 1), abi.WINDOW_POSE_DTYPE)
+        n = C.c_int32(0)
+        self._ck(self.L.rvio_hip_get_window(self.h, int(instance), cap, out.ctypes.data_as(C.POINTER(abi.rvio_window_pose)), C.byref(n)), "get_window")
+        return out[: n.value].copy()
+
+    def get_window_dev(self, age_first, n_ages, d_out_ptr, out_stride):
+        """every instance, ages age_first .. age_first + n_ages - 1, into device records: (instance, age) at d_out[instance * out_stride + age -
+        age_first].  Asynchronous on the filter stream."""
+        self._ck(self.L.rvio_hip_get_window_dev(self.h, int(age_first), int(n_ages), C.c_void_p(d_out_ptr), C.c_size_t(int(out_stride))), "get_window_dev")
+
+    def set_smoothed_odometry(self, capacity, lag):
+        """keep an rvio_window_pose record of the frame `lag` images back behind every augment/compose stage from the next one on, `capacity` per
+        instance on the device; 0: off"""
+        self._ck(self.L.rvio_hip_set_smoothed_odometry(self.h, int(capacity), int(lag)), "set_smoothed_odometry")
+        if capacity:
+            self._smo_cap = int(capacity)
+
+    def smoothed_odometry(self, instance=0, first_seq=1, max_n=None):
+        """records of one instance still in the smoothed ring with seq >= first_seq, oldest first (at most max_n): abi.WINDOW_POSE_DTYPE"""
+        cap = getattr(self, "_smo_cap", 0) if max_n is None else int(max_n)
+        out = np.zeros(max(cap, 0), abi.WINDOW_POSE_DTYPE)
+        n = C.c_int32(0)
+        self._ck(self.L.rvio_hip_get_smoothed_odometry(self.h, int(instance), C.c_int64(int(first_seq)), cap,
+                                                       out.ctypes.data_as(C.POINTER(abi.rvio_window_pose)) if len(out) else None, C.byref(n)), "get_smoothed_odometry")
+        return out[: n.value].copy()
+
+    def smoothed_odometry_all(self):
+        """(seq, the newest smoothed record of every instance); seq = 0 and zeroed records before the first one"""
+        out = np.zeros(self.batch, abi.WINDOW_POSE_DTYPE)
+        seq = C.c_int64(0)
+        self._ck(self.L.rvio_hip_get_smoothed_odometry_all(self.h, out.ctypes.data_as(C.POINTER(abi.rvio_window_pose)), C.byref(seq)), "get_smoothed_odometry_all")
         return int(seq.value), out
 
     # ---- IMU-rate odometry (PreIntegrator.cc:168-176 kept per sample)
