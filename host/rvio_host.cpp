@@ -210,9 +210,11 @@ System::~System() {
     if (!ss_path_.empty()) (void)flush_standstill();
     if (f_od_ && h_) (void)flush_odometry();
     if (f_sm_ && h_) (void)flush_smoothed();
+    if (f_ed_ && h_) (void)flush_edges();
     if (f_io_ && h_) (void)flush_imu_odometry();
     delete static_cast<std::ofstream*>(f_od_);
     delete static_cast<std::ofstream*>(f_sm_);
+    delete static_cast<std::ofstream*>(f_ed_);
     delete static_cast<std::ofstream*>(f_io_);
     delete static_cast<std::ofstream*>(f_pose_);
     delete static_cast<std::ofstream*>(f_time_);
@@ -338,6 +340,51 @@ int System::flush_smoothed() {
     }
     f.flush();
     sm_new_ = 0;
+    return 0;
+}
+
+bool System::record_edges_to(const std::string& path, int age_new, int age_old, int ring) {
+    if (!h_) return false;
+    if (ring < 1) { err_ = "the edge-odometry ring holds at least one record"; return false; }
+    auto* f = new std::ofstream(path, std::ofstream::out);
+    if (!*f) { delete f; err_ = "cannot write " + path; return false; }
+    if (f_ed_) (void)flush_edges();
+    if (rvio_hip_set_edge_odometry(h_, ring, age_new, age_old) != RVIO_OK) { delete f; err_ = rvio_hip_last_error(h_); return false; }
+    delete static_cast<std::ofstream*>(f_ed_);
+    f_ed_ = f;
+    ed_ring_ = ring;
+    ed_buf_.assign((size_t)ring, rvio_window_edge{});
+    // (records written from here on are read from here on, like record_smoothed_to)
+    int64_t s = 0;
+    ed_read_ = (ready_ && rvio_hip_get_edge_odometry_all(h_, ed_buf_.data(), &s) == RVIO_OK) ? (long long)s : 0;
+    ed_new_ = 0;
+    return true;
+}
+
+// behind a frame handed to the filter: its count and stamp join the queue; the ring is read when half of it may be outstanding
+int System::note_edges(double t) {
+    ed_t_.emplace_back(n_img_, t);
+    if (++ed_new_ >= std::max(1, ed_ring_ / 2)) return flush_edges();
+    return 0;
+}
+
+int System::flush_edges() {
+    if (!f_ed_ || ed_new_ == 0) return 0;
+    int32_t n = 0;
+    if (rvio_hip_get_edge_odometry(h_, 0, ed_read_ + 1, ed_ring_, ed_buf_.data(), &n) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+    auto& f = *static_cast<std::ofstream*>(f_ed_);
+    for (int i = 0; i < n; ++i) {
+        const rvio_window_edge& r = ed_buf_[(size_t)i];
+        // (frames older than this record's older end are named by no later record: the ring's ages are fixed and the counts rise)
+        while (!ed_t_.empty() && ed_t_.front().first < r.img_count_old) ed_t_.pop_front();
+        if (!ed_t_.empty() && ed_t_.front().first == r.img_count_old) {
+            for (const auto& ct : ed_t_)
+                if (ct.first == r.img_count_new) { f << format_edge(ct.second, ed_t_.front().second, r); break; }
+        }
+        ed_read_ = r.seq;
+    }
+    f.flush();
+    ed_new_ = 0;
     return 0;
 }
 
@@ -833,6 +880,7 @@ int System::MonoVIO(PoseLine* pose) {
                 // (rvio_hip_initialize restarts the handle's frame count and empties the smoothed ring: the stamps, which are matched to records by
                 // that count — n_img_ mirrors it, both count the frames handed to the filter since this point —, start over with it)
                 sm_t_.clear(); sm_read_ = 0; sm_new_ = 0;
+                ed_t_.clear(); ed_read_ = 0; ed_new_ = 0;   // (the edge ring likewise)
                 break;
             }
         }
@@ -871,6 +919,7 @@ int System::MonoVIO(PoseLine* pose) {
         if (f_lm_ && write_landmarks(image.t) < 0) return -1;
         if (f_od_ && note_odometry(image.t) < 0) return -1;
         if (f_sm_ && note_smoothed(image.t) < 0) return -1;
+        if (f_ed_ && note_edges(image.t) < 0) return -1;
         if (f_io_ && note_imu_odometry(m) < 0) return -1;
         return 1;
     }
@@ -901,6 +950,7 @@ int System::MonoVIO(PoseLine* pose) {
     if (f_lm_ && write_landmarks(image.t) < 0) return -1;
     if (f_od_ && note_odometry(image.t) < 0) return -1;
     if (f_sm_ && note_smoothed(image.t) < 0) return -1;
+    if (f_ed_ && note_edges(image.t) < 0) return -1;
     if (f_io_ && note_imu_odometry(m) < 0) return -1;
     if (pose) *pose = pl;
     return 1;
@@ -937,6 +987,17 @@ std::string format_smoothed(double t, const rvio_window_pose& r) {
     o.seq = r.seq;
     std::copy(r.p, r.p + 3, o.p); std::copy(r.q, r.q + 4, o.q); std::copy(r.pose_cov, r.pose_cov + 36, o.pose_cov);
     return format_odometry(t, o);
+}
+
+std::string format_edge(double t_new, double t_old, const rvio_window_edge& r) {
+    char buf[64];
+    std::string out;
+    auto put = [&](double v, const char* sep) { std::snprintf(buf, sizeof buf, "%.19g%s", v, sep); out += buf; };
+    put(t_new, " "); put(t_old, " ");
+    for (int i = 0; i < 3; ++i) put(r.p[i], " ");
+    for (int i = 0; i < 4; ++i) put(r.q[i], " ");
+    for (int i = 0; i < 36; ++i) put(r.cov[i], i == 35 ? "\n" : " ");
+    return out;
 }
 
 std::string format_imu_odometry(const rvio_imu_pose& r) {

@@ -183,6 +183,12 @@ public:
     // One line per record, format_smoothed: the layout of the odometry file.
     bool record_smoothed_to(const std::string& path, int lag, int ring = 256);
     int flush_smoothed();         // 0, or -1 on a library error (error())
+    // A pose-graph back end's between-factors: enables the handle's edge-odometry ring (rvio_hip_set_edge_odometry, `ring` records, the edge
+    // between the frames age_new < age_old images back behind every frame) and keeps the image stamps by frame count on the host: a record is
+    // written with the stamps of the two images it connects.  Read like the smoothed ring (flush_edges, also run by the destructor).  One line
+    // per record, format_edge.
+    bool record_edges_to(const std::string& path, int age_new, int age_old, int ring = 256);
+    int flush_edges();            // 0, or -1 on a library error (error())
     // A dense trajectory: one pose per IMU sample (200 Hz against the 20 Hz of stamped_pose_ests.dat), the pose line MonoVIO would write if an
     // image arrived right behind that sample and ran no update.  Enables the handle's IMU-rate ring (rvio_hip_set_imu_odometry, `ring` samples)
     // and reads it with ONE rvio_hip_get_imu_odometry whenever ring / 2 samples are outstanding and once more at the end
@@ -310,6 +316,12 @@ private:
     std::deque<std::pair<int, double>> sm_t_;   // (frame count, image stamp) of the frames no record has described yet, oldest first
     std::vector<rvio_window_pose> sm_buf_;
     int note_smoothed(double t);
+    void* f_ed_ = nullptr;        // std::ofstream* of record_edges_to
+    int ed_ring_ = 0, ed_new_ = 0;         // ed_new_: frames handed to the filter since the ring was last read
+    long long ed_read_ = 0;       // seq of the last record written to the file
+    std::deque<std::pair<int, double>> ed_t_;   // (frame count, image stamp) of the frames a coming record may still name, oldest first
+    std::vector<rvio_window_edge> ed_buf_;
+    int note_edges(double t);
     long long last_seq();
     void* f_io_ = nullptr;        // std::ofstream* of record_imu_odometry_to
     int io_ring_ = 0;
@@ -363,6 +375,10 @@ std::string format_landmarks(double t, int frame, int n, const int32_t* feat, co
 std::string format_odometry(double t, const rvio_odom& r);
 // one record of the smoothed-odometry ring in the same layout; the three velocity columns are 0 (the window holds no velocity of a past frame)
 std::string format_smoothed(double t, const rvio_window_pose& r);
+// one record of the edge-odometry ring: t_new t_old px py pz qx qy qz qw c00 ... c55 (cov row by row), %.19g — p the origin of the newer frame
+// in the older, along the older frame's axes; q (JPL, xyzw) rotates the older frame into the newer; cov rows: p, then the rotation error along the
+// newer frame's axes under R_true ~ (I - [dth x]) R(q) (rvio_window_edge of include/rvio_hip.h)
+std::string format_edge(double t_new, double t_old, const rvio_window_edge& r);
 // one record of the IMU-rate ring: t px py pz qx qy qz qw vx vy vz, %.19g (setprecision(19), like stamped_pose_ests.dat)
 std::string format_imu_odometry(const rvio_imu_pose& r);
 // the same line with the paired covariance record behind it: the 21 entries of pose_cov's upper triangle row by row (c00 c01 ... c05 c11 ... c55, order

@@ -15,6 +15,12 @@
 //                                        max_track_len - 1, the most-smoothed pose still in the window) as the clone window holds it behind every frame,
 //                                        read in bulk from the handle's smoothed ring of N records (default 256; System::record_smoothed_to); one line
 //                                        per record in the layout of --odometry, stamped with the image it describes
+//                                        [--edges FILE [--edges-span K] [--edges-ring N]]
+//                                        --edges: a pose-graph back end's between-factors — the relative pose, with its own 6 x 6 covariance, of
+//                                        the two oldest frames of the window that lie K images apart (default 1: the oldest clone, each consecutive
+//                                        edge at its most smoothed, just before it is marginalised) behind every frame, read in bulk from the
+//                                        handle's edge ring of N records (default 256; System::record_edges_to); one line per record, stamped
+//                                        with the two images it connects (format_edge: t_new t_old p q cov)
 //                                        --landmarks: Updater::update's landmark cloud behind every updating frame (System::record_landmarks_to)
 //                                        [--velocity FILE [--velocity-sigma S] [--velocity-gate]] [--standstill FILE]
 //                                        --standstill: with Standstill.Enable: 1 in the settings (the device-side standstill detector and its
@@ -277,6 +283,8 @@ struct PassOptions {
     int odometry_ring = 256;
     const char* smoothed = nullptr;  // System::record_smoothed_to
     int smoothed_lag = -1, smoothed_ring = 256;
+    const char* edges = nullptr;     // System::record_edges_to
+    int edges_span = 1, edges_ring = 256;
     const char* imu_odometry = nullptr;  // System::record_imu_odometry_to
     int imu_odometry_ring = 4096;
     bool imu_odometry_cov = false;
@@ -310,6 +318,7 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
     if (o.landmarks && !sys.record_landmarks_to(o.landmarks)) { *err = sys.error(); return 1; }
     if (o.odometry && !sys.record_odometry_to(o.odometry, o.odometry_ring)) { *err = sys.error(); return 1; }
     if (o.smoothed && !sys.record_smoothed_to(o.smoothed, o.smoothed_lag < 0 ? s.cfg.max_track_len - 1 : o.smoothed_lag, o.smoothed_ring)) { *err = sys.error(); return 1; }
+    if (o.edges && !sys.record_edges_to(o.edges, s.cfg.max_track_len - 1 - o.edges_span, s.cfg.max_track_len - 1, o.edges_ring)) { *err = sys.error(); return 1; }
     if (o.imu_odometry && !sys.record_imu_odometry_to(o.imu_odometry, o.imu_odometry_ring, o.imu_odometry_cov)) { *err = sys.error(); return 1; }
     if (o.fixes) sys.queue_fixes(*o.fixes, o.fix_gate, o.fix_latency);
     if (o.rels) sys.queue_rels(*o.rels, o.rel_gate);
@@ -349,7 +358,7 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
             if (o.dump_at >= 0 && n_frames > o.dump_at) break;
         }
     }
-    if (sys.flush_odometry() < 0 || sys.flush_smoothed() < 0 || sys.flush_imu_odometry() < 0) { *err = sys.error(); return 1; }
+    if (sys.flush_odometry() < 0 || sys.flush_smoothed() < 0 || sys.flush_edges() < 0 || sys.flush_imu_odometry() < 0) { *err = sys.error(); return 1; }
     if (ms_per_call) *ms_per_call = n_images ? 1e3 * t_filter / n_images : 0.0;
     if (flags) *flags = sys.device_flags();
     return 0;
@@ -441,7 +450,7 @@ int main(int argc, char** argv) {
     }
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--record-dir DIR] [--record]\n"
-                             "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--smoothed FILE] [--smoothed-lag L] [--smoothed-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--imu-odometry-cov] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n"
+                             "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--smoothed FILE] [--smoothed-lag L] [--smoothed-ring N] [--edges FILE] [--edges-span K] [--edges-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--imu-odometry-cov] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n"
                              "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate] [--standstill FILE] [--fix FILE] [--fix-gate] [--fix-latency S]\n"
                              "          [--rel FILE] [--rel-gate] [--map FILE] [--map-units px|norm] [--map-latency S] [--map-gate]\n"
                              "          [--meas-iters N] [--meas-tol T]\n", argv[0]);
@@ -452,6 +461,7 @@ int main(int argc, char** argv) {
     const char* landmarks = nullptr;
     const char* odometry = nullptr; int odometry_ring = 256;
     const char* smoothed = nullptr; int smoothed_lag = -1, smoothed_ring = 256;
+    const char* edges = nullptr; int edges_span = 1, edges_ring = 256;
     const char* imu_odometry = nullptr; int imu_odometry_ring = 4096; bool imu_odometry_cov = false;
     const char* velocity = nullptr; double velocity_sigma = 0.05; bool velocity_gate = false;
     const char* standstill = nullptr;
@@ -474,6 +484,9 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--smoothed") && i + 1 < argc) smoothed = argv[++i];     // one line per record: pose and pose covariance of the frame L images back (read in bulk from the smoothed ring)
         else if (!std::strcmp(argv[i], "--smoothed-lag") && i + 1 < argc) smoothed_lag = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--smoothed-ring") && i + 1 < argc) smoothed_ring = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--edges") && i + 1 < argc) edges = argv[++i];           // one line per record: the edge between the two oldest frames K images apart (read in bulk from the edge ring)
+        else if (!std::strcmp(argv[i], "--edges-span") && i + 1 < argc) edges_span = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--edges-ring") && i + 1 < argc) edges_ring = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--imu-odometry") && i + 1 < argc) imu_odometry = argv[++i];   // one line per IMU sample: pose and velocity (read in bulk from the IMU-rate ring)
         else if (!std::strcmp(argv[i], "--imu-odometry-ring") && i + 1 < argc) imu_odometry_ring = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--imu-odometry-cov")) imu_odometry_cov = true;   // ... and the covariance of each sample's pose and velocity behind it
@@ -551,7 +564,7 @@ int main(int argc, char** argv) {
     if (self) return selfcheck(s, d, device, max_frames, stall_seed, noise_wgs);
     if (sync_every || stall_seed >= 0 || noise_wgs > 0) {   // the plain replay with one of the two A/B pacings
         std::vector<PoseLine> poses; double ms = 0; int flags = 0;
-        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.smoothed = smoothed; o.smoothed_lag = smoothed_lag; o.smoothed_ring = smoothed_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.imu_odometry_cov = imu_odometry_cov; o.velocity = vr; if (fix) { o.fixes = &fixes; o.fix_gate = fix_gate; o.fix_latency = fix_latency; } if (rel) { o.rels = &rels; o.rel_gate = rel_gate; } if (map) { o.maps = &maps; o.map_units = map_units; o.map_latency = map_latency; o.map_gate = map_gate; }
+        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.smoothed = smoothed; o.smoothed_lag = smoothed_lag; o.smoothed_ring = smoothed_ring; o.edges = edges; o.edges_span = edges_span; o.edges_ring = edges_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.imu_odometry_cov = imu_odometry_cov; o.velocity = vr; if (fix) { o.fixes = &fixes; o.fix_gate = fix_gate; o.fix_latency = fix_latency; } if (rel) { o.rels = &rels; o.rel_gate = rel_gate; } if (map) { o.maps = &maps; o.map_units = map_units; o.map_latency = map_latency; o.map_gate = map_gate; }
         if (run_pass(s, d, device, o, &poses, nullptr, &ms, &flags, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
         if (out_path) { std::ofstream out(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } for (const PoseLine& p : poses) out << format_pose(p); }
         std::fprintf(stderr, "rvio_replay: %zu filtered frames, %.3f ms per MonoVIO call, device flags %d\n", poses.size(), ms, flags);
@@ -564,6 +577,7 @@ int main(int argc, char** argv) {
     if (landmarks && !sys.record_landmarks_to(landmarks)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (odometry && !sys.record_odometry_to(odometry, odometry_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (smoothed && !sys.record_smoothed_to(smoothed, smoothed_lag < 0 ? s.cfg.max_track_len - 1 : smoothed_lag, smoothed_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
+    if (edges && !sys.record_edges_to(edges, s.cfg.max_track_len - 1 - edges_span, s.cfg.max_track_len - 1, edges_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (imu_odometry && !sys.record_imu_odometry_to(imu_odometry, imu_odometry_ring, imu_odometry_cov)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (standstill && !sys.record_standstill_to(standstill)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (fix) sys.queue_fixes(fixes, fix_gate, fix_latency);
@@ -595,7 +609,7 @@ int main(int argc, char** argv) {
         if (rc == 1) { ++n_frames; if (out.is_open()) out << format_pose(p); }
         if (rc == 1 && apply_velocity(sys, vr, image_k) < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     }
-    if (sys.flush_odometry() < 0 || sys.flush_smoothed() < 0 || sys.flush_imu_odometry() < 0 || sys.flush_standstill() < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
+    if (sys.flush_odometry() < 0 || sys.flush_smoothed() < 0 || sys.flush_edges() < 0 || sys.flush_imu_odometry() < 0 || sys.flush_standstill() < 0) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     std::fprintf(stderr, "rvio_replay: %ld images, %ld filtered frames, %.3f ms per MonoVIO call (host wall clock, pose read-back included)\n",
                  n_images, n_frames, n_images ? 1e3 * t_filter / n_images : 0.0);
     if (vr) print_velocity(*vr);

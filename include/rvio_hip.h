@@ -704,8 +704,9 @@ int rvio_hip_frame_age(rvio_hip* h, int img_count, int* age);
  *   pose_cov = (C + C^T) / 2,  C = J P J^T,  J = the three POSITION rows (lever 0, frac 0) over the three ATTITUDE rows of the past-fix table at
  * age a: row-major 6 x 6 in the order and error convention of rvio_odom.pose_cov (x, y, z, then the world-frame rotation error phi), exactly
  * symmetric; at a = 0 J is rvio_odom's.
- * NOT done: cross-covariances between frames of the window; the pose of the frame that has just left the window; time stamps in the record (the
- * host knows the stamp of every img_count); interpolation between frames. */
+ * NOT done: cross-covariances between frames of the window IN THIS RECORD — rvio_hip_get_window_joint and rvio_hip_get_window_edges below
+ * publish them, as the joint covariance of the poses and as between-factors; the pose of the frame that has just left the window;
+ * time stamps in the record (the host knows the stamp of every img_count); interpolation between frames. */
 typedef struct rvio_window_pose {   /* 368 bytes, no padding */
     int64_t seq;          /* smoothed-odometry ring: 1, 2, ... records written; rvio_hip_get_window*: 0 */
     int32_t img_count;    /* the count of the frame the record describes: the reference frame's count minus age (-1: age outside the window) */
@@ -740,6 +741,71 @@ int rvio_hip_set_smoothed_odometry(rvio_hip* h, int capacity, int lag);
 /* rvio_hip_get_odometry's and rvio_hip_get_odometry_all's clauses.  RVIO_ERR_STATE: the ring was never enabled. */
 int rvio_hip_get_smoothed_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_window_pose* out, int32_t* n);
 int rvio_hip_get_smoothed_odometry_all(rvio_hip* h, rvio_window_pose* out /* batch records */, int64_t* seq);
+
+/* --- pose-graph export: the edge between two frames of the window and the joint covariance of its poses (no reference counterpart) -- */
+/* The records above carry the 6 x 6 MARGINAL covariance of each frame's world pose.  A pose-graph back end is not fed world poses with independent
+ * marginals — the frames of one window are correlated almost perfectly through (qG, pG) — but BETWEEN-FACTORS: the relative pose of two frames
+ * with the covariance of THAT quantity; and when it takes several frames at once it needs their JOINT covariance.  Both are formed on the device
+ * (csrc/window_edge.hip); nothing of x or P crosses PCIe.  rvio_hip_update_rel puts a delta pose INTO the filter; this takes one OUT, in the same
+ * conventions: an edge read here and handed back there (z = (p, q), sigma^2 = the diagonal of cov) means the same thing.
+ * THE EDGE between the frames age_new = a and age_old = b images back, 0 <= a < b <= n_clones, with the chain (B_j, s_j) of the relative-pose table
+ * below (k = b - a, lever 0); it depends on the clones n - b .. n - a - 1 and on nothing else of x, and on their square of P:
+ *   p = -B_k^T s_k      the origin of frame a in frame b, along frame-b axes (the sense of a clone's p)
+ *   R(q) = B_k          rotates frame b into frame a (the sense of a clone's q); RotToQuat's sign (util/Numerics.h:126-167), normalised, q[3] >= 0
+ *   cov = (C + C^T) / 2,  C = H P H^T,  H = the six RVIO_REL_POSE rows of that table at lever 0: row-major 6 x 6, exactly symmetric.  Rows 0-2:
+ * the error of p along frame-b axes (p_true = p + dp).  Rows 3-5: the rotation error along frame-a axes under R_true ~ (I - [dth x]) R(q) —
+ * the order and convention in which rvio_hip_update_rel(RVIO_REL_POSE) takes sigma.  For b = a + 1 the edge IS clone n - b and cov is its
+ * block of P with the two 3-blocks swapped (P holds rotation before position).  Formed directly from the clones of the span: the same covariance
+ * taken from world-pose marginals and cross-covariances would subtract large, nearly equal numbers.
+ * NOT done: the correlation between successive ring edges (they share no clone when their spans do not overlap, but P correlates every pair of
+ * clones; rvio_hip_get_window_joint gives joint information instead); the frame that has already left the window; (qk, pk) as an endpoint;
+ * information-matrix / g2o / GTSAM output (their quaternion order and perturbation side differ: convert on the host from the conventions above);
+ * interpolation between frames. */
+typedef struct rvio_window_edge {   /* 376 bytes, no padding */
+    int64_t seq;            /* edge ring: 1, 2, ... records written; rvio_hip_get_window_edges*: 0 */
+    int32_t img_count_new;  /* the reference frame's count minus age_new (-1: pair outside the window) */
+    int32_t img_count_old;  /* the reference frame's count minus age_old */
+    int32_t age_new, age_old;
+    int32_t n_clones;       /* nCloneStates when the record was formed */
+    int32_t reserved;       /* 0 */
+    double p[3];
+    double q[4];
+    double cov[36];
+} rvio_window_edge;
+/* n_pairs edges of one instance, pair i = (age_new[i], age_old[i]) (host arrays) into out[i], linearised at the state the call finds.  One
+ * launch on the filter stream; waits for the filter stream only.  seq = 0.  1 <= n_pairs <= 528 (every pair of the longest window); the first
+ * call allocates its staging, outside the filter slab.  RVIO_ERR_STATE: no state yet; RVIO_ERR_INVALID: NULL handle or argument, instance out of
+ * range, n_pairs outside 1 .. 528, a pair that is not 0 <= age_new < age_old <= n_clones (rvio_hip_last_error names it; nothing is launched). */
+int rvio_hip_get_window_edges(rvio_hip* h, int instance, int n_pairs, const int32_t* age_new, const int32_t* age_old, rvio_window_edge* out);
+/* Every instance, ONE pair list (device arrays) for all of them: record (instance, pair) lies at d_out[instance * out_stride + pair].
+ * Asynchronous on the filter stream: nothing is waited for, read back or checked on the host.  A pair that is not 0 <= age_new < age_old <=
+ * the instance's n_clones writes a record with img_count_new = -1, n_clones set and every other member 0.  RVIO_ERR_STATE: no state yet;
+ * RVIO_ERR_INVALID: NULL handle or argument, n_pairs outside 1 .. 65535, out_stride < n_pairs. */
+int rvio_hip_get_window_edges_dev(rvio_hip* h, int n_pairs, const int32_t* d_age_new, const int32_t* d_age_old, rvio_window_edge* d_out, size_t out_stride);
+/* The edge-odometry ring: behind the smoothed record's place in every augmentation / composition stage, one record per instance of the pair
+ * (age_new, age_old), into a ring with exactly the rules of rvio_hip_set_smoothed_odometry (capacity 0 .. 65536; 0 = off, the default: such a
+ * handle allocates and launches what it did before these entry points existed).  A frame is recorded only when n_clones >= age_old behind its
+ * stage.  (age_new, age_old) = (max_track_len - 2, max_track_len - 1) records the oldest clone behind every frame — each consecutive edge at
+ * its most smoothed, just before it is marginalised: a back end's odometry chain.  Another pair empties the ring like another capacity (seq
+ * restarts at 1); rvio_hip_initialize empties it.  RVIO_ERR_INVALID: NULL handle, capacity outside 0 .. 65536, a pair that is not
+ * 0 <= age_new < age_old <= max_track_len - 1 (rvio_hip_last_error); RVIO_ERR_UNSUPPORTED: capacity x instances x 376 bytes exceeds 1 GiB. */
+int rvio_hip_set_edge_odometry(rvio_hip* h, int capacity, int age_new, int age_old);
+/* rvio_hip_get_odometry's and rvio_hip_get_odometry_all's clauses.  RVIO_ERR_STATE: the ring was never enabled. */
+int rvio_hip_get_edge_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_window_edge* out, int32_t* n);
+int rvio_hip_get_edge_odometry_all(rvio_hip* h, rvio_window_edge* out /* batch records */, int64_t* seq);
+/* THE JOINT COVARIANCE of the world poses of the ages 0 .. *n - 1, *n = min(n_clones + 1, max_n), frames newest first: with J_a the Jacobian of
+ * rvio_window_pose at age a, block (a, b) of cov is J_a P J_b^T (6 x 6, pose_cov's order and error convention in rows and columns).  cov is
+ * row-major with leading dimension ld >= 6 max_n; only rows and columns below 6 (*n) are written.  The diagonal blocks carry the bits of
+ * rvio_window_pose.pose_cov, poses[a] the bits rvio_hip_get_window gives, and the whole matrix equals its transpose bit for bit.  max_n = m is
+ * the leading 6 m x 6 m block of the full answer.  One launch on the filter stream; waits for that stream only; the first call allocates its
+ * staging (at most 192^2 doubles and the records).  RVIO_ERR_STATE: no state yet; RVIO_ERR_INVALID: NULL handle, poses, cov or n, instance out
+ * of range, max_n < 1, ld < 6 max_n. */
+int rvio_hip_get_window_joint(rvio_hip* h, int instance, int max_n, rvio_window_pose* poses, double* cov, size_t ld, int32_t* n);
+/* Every instance, ages 0 .. n_ages - 1: pose (instance, age) at d_poses[instance * pose_stride + age]; the instance's matrix, row-major with
+ * leading dimension 6 n_ages, at d_cov + instance * cov_stride (doubles).  Asynchronous on the filter stream.  Blocks touching an age beyond an
+ * instance's window are written as 0.0 and that age's pose record has the img_count = -1 form.  RVIO_ERR_STATE: no state yet; RVIO_ERR_INVALID:
+ * NULL handle, d_poses or d_cov, n_ages outside 1 .. 32, pose_stride < n_ages, cov_stride < (6 n_ages)^2. */
+int rvio_hip_get_window_joint_dev(rvio_hip* h, int n_ages, rvio_window_pose* d_poses, size_t pose_stride, double* d_cov, size_t cov_stride);
 
 /* --- relative-pose measurements: a delta pose between two frames of the clone window (no reference counterpart) ------------------ */
 /* What most other sensors on a robot produce is neither a state entry nor a world-frame fix but a DELTA POSE BETWEEN TWO INSTANTS: a wheel-odometry

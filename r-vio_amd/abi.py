@@ -774,6 +774,171 @@ def rel_model(x, kind, meas, age_new, age_old):
     return np.vstack(rows_H), np.concatenate(rows_r), np.concatenate(rows_s)
 
 
+# ---- pose-graph export: window edges and the joint covariance of the window's poses (rvio_hip_get_window_edges*, rvio_hip_set_edge_odometry,
+# rvio_hip_get_window_joint*, csrc/window_edge.hip)
+class rvio_window_edge(C.Structure):
+    """the relative pose of the frames age_new and age_old images back with the covariance of that quantity: 376 bytes, no padding"""
+    _fields_ = [("seq", C.c_int64), ("img_count_new", C.c_int32), ("img_count_old", C.c_int32), ("age_new", C.c_int32), ("age_old", C.c_int32),
+                ("n_clones", C.c_int32), ("reserved", C.c_int32), ("p", C.c_double * 3), ("q", C.c_double * 4), ("cov", C.c_double * 36)]
+
+
+WINDOW_EDGE_DTYPE = np.dtype([("seq", "i8"), ("img_count_new", "i4"), ("img_count_old", "i4"), ("age_new", "i4"), ("age_old", "i4"),
+                              ("n_clones", "i4"), ("reserved", "i4"), ("p", "f8", 3), ("q", "f8", 4), ("cov", "f8", (6, 6))])
+assert WINDOW_EDGE_DTYPE.itemsize == C.sizeof(rvio_window_edge) == 376
+WINDOW_EDGE_MAX_PAIRS = 528
+
+
+class _RelLever0:
+    """a relative-pose measurement that only carries what the rows need: lever 0"""
+    z, sigma, lever = (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0), (0.0,) * 6, (0.0, 0.0, 0.0)
+
+
+def window_edge_jacobian(x, a, b):
+    """H (6 x d): the six RVIO_REL_POSE rows of rel_model between the frames a < b images back, lever 0"""
+    return rel_model(x, RVIO_REL_POSE, _RelLever0, a, b)[0]
+
+
+def window_edge_model(x, P, a, b):
+    """NumPy float64 model of window_edge_kernel: (p, q, cov) of the edge between the frames a < b images back — p, q = rel_h at lever 0,
+    cov = (C + C^T) / 2 with C = H P H^T, H = window_edge_jacobian.  Calls nothing from the library or the oracle."""
+    x, P = np.asarray(x, float), np.asarray(P, float)
+    z = rel_h(x, a, b)
+    H = window_edge_jacobian(x, a, b)
+    Cm = H @ P @ H.T
+    return z[0:3], z[3:7], 0.5 * (Cm + Cm.T)
+
+
+def _ops_as(dtype):
+    """skew, quaternion -> rotation, rotation -> quaternion evaluated in `dtype` (the helpers of window_pose_model_as)"""
+    one, two = dtype(1), dtype(2)
+
+    def skew(w):
+        S = np.zeros((3, 3), dtype)
+        S[0, 1], S[0, 2], S[1, 0], S[1, 2], S[2, 0], S[2, 1] = -w[2], w[1], w[2], -w[0], -w[1], w[0]
+        return S
+
+    def q2r(q):
+        qx = skew(q[:3])
+        return np.eye(3, dtype=dtype) - two * q[3] * qx + two * (qx @ qx)
+
+    def r2q(R):
+        T = R[0, 0] + R[1, 1] + R[2, 2]
+        d = [R[0, 0], R[1, 1], R[2, 2]]
+        q = np.zeros(4, dtype)
+        big = [i for i in range(3) if d[i] > T and all(d[i] > d[j] for j in range(3) if j != i)]
+        if big:
+            i = big[0]
+            j, k = (i + 1) % 3, (i + 2) % 3
+            q[i] = np.sqrt((one + two * d[i] - T) / dtype(4))
+            s = one / (dtype(4) * q[i])
+            q[j], q[k], q[3] = s * (R[i, j] + R[j, i]), s * (R[i, k] + R[k, i]), s * (R[j, k] - R[k, j])
+        else:
+            q[3] = np.sqrt((one + T) / dtype(4))
+            s = one / (dtype(4) * q[3])
+            q[0], q[1], q[2] = s * (R[1, 2] - R[2, 1]), s * (R[2, 0] - R[0, 2]), s * (R[0, 1] - R[1, 0])
+        q = q / np.sqrt(q @ q)
+        return -q if q[3] < 0 else q
+
+    return skew, q2r, r2q
+
+
+def window_edge_model_as(x, P, a, b, dtype=np.longdouble):
+    """The twin of window_edge_model evaluated in `dtype` throughout (np.longdouble: the truth the tests hold the device and the float64 model
+    to): the same chain, rows and products, written out so that no intermediate passes through float64.  Returns (p, q, cov) in `dtype`."""
+    x, P = np.asarray(x, dtype), np.asarray(P, dtype)
+    n = (len(x) - 26) // 7
+    assert 0 <= a < b <= n, "ages outside the window, or not a < b"
+    skew, q2r, r2q = _ops_as(dtype)
+    k = b - a
+    B, s = [np.eye(3, dtype=dtype)], [np.zeros(3, dtype)]
+    for j in range(1, k + 1):
+        i = n - a - j
+        B.append(B[-1] @ q2r(x[26 + 7 * i: 30 + 7 * i]))
+        s.append(s[-1] - B[-1] @ x[30 + 7 * i: 33 + 7 * i])
+    Bkt = B[k].T
+    H = np.zeros((6, 24 + 6 * n), dtype)
+    for j in range(1, k + 1):
+        c = 24 + 6 * (n - a - j)
+        H[0:3, c: c + 3], H[0:3, c + 3: c + 6] = Bkt @ skew(s[j - 1]) @ B[j - 1], Bkt @ B[j]
+        H[3:6, c: c + 3] = B[j - 1]
+    Cm = H @ P @ H.T
+    return -(Bkt @ s[k]), r2q(B[k]), (dtype(1) / dtype(2)) * (Cm + Cm.T)
+
+
+def window_joint_model(x, P, m):
+    """NumPy float64 model of window_joint_kernel: the joint covariance (6 m x 6 m) of the world poses of the ages 0 .. m - 1, newest first —
+    block (a, b) = J_a P J_b^T with J = window_pose_jacobian, the diagonal blocks symmetrised like window_pose_model's — exactly symmetric.
+    Calls nothing from the library or the oracle."""
+    x, P = np.asarray(x, float), np.asarray(P, float)
+    J = [window_pose_jacobian(x, a) for a in range(m)]
+    X = np.zeros((6 * m, 6 * m))
+    for a in range(m):
+        T = P @ J[a].T
+        Cm = J[a] @ P @ J[a].T              # (window_pose_model's order of products: the same bits)
+        X[6 * a: 6 * a + 6, 6 * a: 6 * a + 6] = 0.5 * (Cm + Cm.T)
+        for b in range(a):
+            Xba = J[b] @ T
+            X[6 * b: 6 * b + 6, 6 * a: 6 * a + 6], X[6 * a: 6 * a + 6, 6 * b: 6 * b + 6] = Xba, Xba.T
+    return X
+
+
+def window_pose_jacobian_as(x, age, dtype=np.longdouble):
+    """window_pose_jacobian evaluated in `dtype` throughout (the J of window_pose_model_as)"""
+    x = np.asarray(x, dtype)
+    n = (len(x) - 26) // 7
+    assert 0 <= age <= n, "age outside the window"
+    skew, q2r, _ = _ops_as(dtype)
+    A, t = [np.eye(3, dtype=dtype)], [np.zeros(3, dtype)]
+    for m in range(1, age + 1):
+        i = n - m
+        A.append(A[-1] @ q2r(x[26 + 7 * i: 30 + 7 * i]))
+        t.append(t[-1] - A[-1] @ x[30 + 7 * i: 33 + 7 * i])
+    RGt = q2r(x[0:4]).T
+    u = t[age]
+    J = np.zeros((6, 24 + 6 * n), dtype)
+    J[0:3, 0:3], J[0:3, 3:6], J[3:6, 0:3] = -RGt @ skew(u - x[4:7]), -RGt, RGt
+    for m in range(1, age + 1):
+        c = 24 + 6 * (n - m)
+        J[0:3, c: c + 3], J[0:3, c + 3: c + 6] = RGt @ skew(u - t[m - 1]) @ A[m - 1], -RGt @ A[m]
+        J[3:6, c: c + 3] = -RGt @ A[m - 1]
+    return J
+
+
+def window_joint_model_as(x, P, m, dtype=np.longdouble):
+    """The twin of window_joint_model evaluated in `dtype` throughout: every block J_a P J_b^T, the whole matrix symmetrised"""
+    P = np.asarray(P, dtype)
+    J = np.vstack([window_pose_jacobian_as(x, a, dtype) for a in range(m)])
+    X = J @ P @ J.T
+    return (dtype(1) / dtype(2)) * (X + X.T)
+
+
+def window_edge_from_poses(x, a, b, dtype=float):
+    """G (6 x 12): the first-order map from the world-pose errors of the frames a and b (each in pose_cov's convention: the position error, then
+    the world-frame rotation error phi, frame a's six first) to the error of the edge (a, b) in rvio_window_edge.cov's convention, so that
+    G Joint[{a, b}] G^T = the edge's cov exactly (the chain rule: H = G [J_a; J_b]).  With W_f = R(q_f)^T (IMU at frame f -> world) and
+    p_f the world positions: dp = W_b^T (dp_a - dp_b) + W_b^T [(p_a - p_b) x] phi_b, dth = W_a^T (phi_a - phi_b)."""
+    x = np.asarray(x, dtype)
+    n = (len(x) - 26) // 7
+    skew, q2r, _ = _ops_as(np.dtype(dtype).type)
+    dt = np.dtype(dtype).type
+
+    def pose(age):
+        A, t = np.eye(3, dtype=dt), np.zeros(3, dt)
+        for m in range(1, age + 1):
+            i = n - m
+            A = A @ q2r(x[26 + 7 * i: 30 + 7 * i])
+            t = t - A @ x[30 + 7 * i: 33 + 7 * i]
+        RG = q2r(x[0:4])
+        return RG.T @ (t - x[4:7]), RG.T @ A          # p_f, W_f
+
+    pa, Wa = pose(a)
+    pb, Wb = pose(b)
+    G = np.zeros((6, 12), dt)
+    G[0:3, 0:3], G[0:3, 6:9], G[0:3, 9:12] = Wb.T, -Wb.T, Wb.T @ skew(pa - pb)
+    G[3:6, 3:6], G[3:6, 9:12] = Wa.T, -Wa.T
+    return G
+
+
 # ---- map landmarks: pixel observations of known world points (rvio_hip_update_map*, csrc/map_rows.hip in front of the auxiliary update)
 RVIO_MAP_NORMALISED, RVIO_MAP_PIXELS = 0, 1
 RVIO_MAP_MAX_POINTS = 8

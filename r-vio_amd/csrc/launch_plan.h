@@ -191,6 +191,22 @@ static_assert(LP_MAP_NZ <= 64 * LP_MAP_WAVES, "one lane per non-zero column");
 #define LP_WINP_WORDS 46         // sizeof(rvio_window_pose) / 8
 #define LP_WINP_LDS_DOUBLES (LP_FIXP_CHAIN + 2 * 6 * LP_WINP_NZ + LP_WINP_GROUPS * 36 * 2 + LP_WINP_WORDS)
 static_assert(LP_WINP_GROUPS * 36 <= LP_WINP_T, "one thread per (group, entry of the 6 x 6)");
+// window_edge_kernel (window_edge.hip): ONE workgroup of four waves per (instance, pair), grid (pairs, 1, instances).  Every wave forms the local
+// chain of rel_rows_kernel (LP_FIXP_NMAX, LP_FIXP_CHAIN); the 6 (b - a) <= LP_WEDGE_NZ columns of the six RVIO_REL_POSE rows that are not zero
+// and the product T = P_span H^T lie in static LDS ([entry][6] each), beside the shares of the LP_WEDGE_GROUPS groups of C = H T and the record's
+// words.  No dynamic part.  LP_WEDGE_MAX_PAIRS: every pair of the longest window, the most one rvio_hip_get_window_edges takes.
+#define LP_WEDGE_T 256
+#define LP_WEDGE_NZ (6 * LP_FIXP_NMAX)
+#define LP_WEDGE_GROUPS 7
+#define LP_WEDGE_WORDS 47        // sizeof(rvio_window_edge) / 8
+#define LP_WEDGE_MAX_PAIRS 528   // 33 * 32 / 2
+#define LP_WEDGE_LDS_DOUBLES (LP_FIXP_CHAIN + 2 * 6 * LP_WEDGE_NZ + LP_WEDGE_GROUPS * 36 * 2 + LP_WEDGE_WORDS)
+static_assert(LP_WEDGE_GROUPS * 36 <= LP_WEDGE_T && LP_WEDGE_WORDS <= LP_WEDGE_T, "one thread per (group, entry of the 6 x 6) and per word");
+// window_joint_kernel (window_edge.hip): ONE workgroup of four waves per (instance, age), grid (ages, 1, instances): window_pose_kernel's chain,
+// J_a, T_a = P_nz J_a^T, shares and record, and beside them the staged J_b of the block in hand (b < a) and the shares of X_ba = J_b T_a (one
+// order per entry: the block is not symmetric).  No dynamic part.
+#define LP_WJNT_T LP_WINP_T
+#define LP_WJNT_LDS_DOUBLES (LP_WINP_LDS_DOUBLES + 6 * LP_WINP_NZ + LP_WINP_GROUPS * 36)
 // doubles between the instances' rows in the block of the map calls, and that block's bytes: rows | r | sigma | (gamma, applied) | records |
 // per-slot records | flags
 LP_HD inline size_t map_H_stride(int dmax) { return (size_t)LP_MAP_ROWS * dmax; }
@@ -203,7 +219,7 @@ enum LpKernel {
     LPK_FEAT_BUILD16, LPK_FEAT_BUILD4, LPK_GRAM_REDUCE, LPK_BLOCK_SUM, LPK_LIT_BATCH, LPK_GEMM_T_LDS, LPK_GRAM_BATCH4, LPK_GRAM_BATCH6, LPK_FEAT_PROP,
     LPK_BOOKKEEP_B, LPK_RANSAC_BOOK, LPK_SOLVE9_SMALL, LPK_SOLVE6_1, LPK_SOLVE6_2, LPK_SOLVE6_3, LPK_JOSEPH_BATCH, LPK_UG, LPK_UG_LDS, LPK_FINAL_LDS,
     LPK_JOSEPH_LDS, LPK_IMU_POSE, LPK_AUX_UPDATE4, LPK_AUX_UPDATE16, LPK_IMU_COV, LPK_STANDSTILL, LPK_FIX, LPK_FIX_PAST, LPK_REL, LPK_MAP,
-    LPK_AUX_ITER4, LPK_AUX_ITER16, LPK_WINDOW_POSE, LPK_COUNT
+    LPK_AUX_ITER4, LPK_AUX_ITER16, LPK_WINDOW_EDGE, LPK_WINDOW_JOINT, LPK_WINDOW_POSE, LPK_COUNT
 };
 // (as c++filt prints them, without return type and arguments: how the test finds each kernel's static LDS in the code object's notes)
 static const char* const kLpKernelName[LPK_COUNT] = {
@@ -211,7 +227,8 @@ static const char* const kLpKernelName[LPK_COUNT] = {
     "gram_reduce_batch_kernel<4>", "gram_reduce_batch_kernel<6>", "feat_prop_kernel", "bookkeep_b_kernel", "ransac_book_kernel", "solve9_small_kernel",
     "solve6_kernel<1, 8, 8>", "solve6_kernel<2, 12, 8>", "solve6_kernel<2, 16, 8>", "joseph_batch_kernel", "ug_kernel", "ug_lds_kernel", "final_lds_kernel",
     "joseph_lds_kernel", "imu_pose_kernel", "aux_update_kernel<4>", "aux_update_kernel<16>", "imu_cov_kernel", "standstill_kernel",
-    "fix_rows_kernel", "fix_past_kernel", "rel_rows_kernel", "map_rows_kernel", "aux_iter_kernel<4>", "aux_iter_kernel<16>", "window_pose_kernel"
+    "fix_rows_kernel", "fix_past_kernel", "rel_rows_kernel", "map_rows_kernel", "aux_iter_kernel<4>", "aux_iter_kernel<16>", "window_edge_kernel",
+    "window_joint_kernel", "window_pose_kernel"
 };
 
 struct LaunchPlan {
@@ -353,6 +370,8 @@ inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size
     if (statics[LPK_REL] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
     // map_rows_kernel: likewise (p.attr[LPK_MAP] stays 0)
     if (statics[LPK_MAP] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
+    // window_edge_kernel, window_joint_kernel: likewise (their p.attr stay 0)
+    if (statics[LPK_WINDOW_EDGE] > RVIO_LDS_LIMIT || statics[LPK_WINDOW_JOINT] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
     // window_pose_kernel: likewise (p.attr[LPK_WINDOW_POSE] stays 0)
     if (statics[LPK_WINDOW_POSE] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
     if (batch > 1 && !p.solve5_variant && !p.solve7_variant) { p.rc = 1; p.why = "batched filter: clone window too long for the unrolled solve kernel (6n <= 126)"; return p; }
@@ -536,6 +555,10 @@ LP_HD inline LpLaunch rel_launch(int batch) { return {1, 1, batch, LP_FIXP_T, 0,
 LP_HD inline LpLaunch map_launch(int batch) { return {1, 1, batch, LP_MAP_T, 0, LPK_MAP}; }
 // window_pose_kernel: one workgroup of four waves per (instance, age), static LDS only
 LP_HD inline LpLaunch window_pose_launch(int batch, int n_ages) { return {n_ages, 1, batch, LP_WINP_T, 0, LPK_WINDOW_POSE}; }
+// window_edge_kernel: one workgroup of four waves per (instance, pair), static LDS only
+LP_HD inline LpLaunch window_edge_launch(int batch, int n_pairs) { return {n_pairs, 1, batch, LP_WEDGE_T, 0, LPK_WINDOW_EDGE}; }
+// window_joint_kernel: one workgroup of four waves per (instance, age), static LDS only
+LP_HD inline LpLaunch window_joint_launch(int batch, int n_ages) { return {n_ages, 1, batch, LP_WJNT_T, 0, LPK_WINDOW_JOINT}; }
 
 enum LpStream {          // the ROLE of a stream in a call; stream_of (rvio_hip.hip) maps it to one of the handle's four
     LPR_FILTER,          //   the filter stream: every launch of a per-stage call that is not forked to the side stream

@@ -33,6 +33,7 @@
 #include "fix_past.hip"    // ... and delayed ones, linearised against the pose the clone window holds for the frame they were taken at (rvio_hip_update_fix_past)
 #include "rel_rows.hip"    // relative poses between two frames of the window, linearised against the clones between them (rvio_hip_update_rel)
 #include "window_pose.hip" // the fixed-lag smoothed trajectory: pose and covariance of every frame of the window (rvio_hip_get_window, rvio_hip_set_smoothed_odometry)
+#include "window_edge.hip" // pose-graph export: the edge between two frames of the window and the joint covariance of its poses (rvio_hip_get_window_edges, rvio_hip_get_window_joint)
 #pragma clang fp contract(off)
 #include "frontend_kernels.hip"
 #include "map_rows.hip"    // map landmarks: pixel observations of known world points at a past image, gated per point against P (rvio_hip_update_map)
@@ -198,6 +199,13 @@ struct rvio_hip {
     DevRing<rvio_window_pose> smo{"smoothed-odometry", "rvio_hip_set_smoothed_odometry"};
     int smo_lag = 0;
     rvio_window_pose* win_buf = nullptr;
+    // edge-odometry ring (window_edge_kernel behind the smoothed record's place, the pair (edg_new, edg_old)): allocated by
+    // rvio_hip_set_edge_odometry, outside the slab.  wedge_buf: the staging of rvio_hip_get_window_edges (LP_WEDGE_MAX_PAIRS records, then the two
+    // age lists); wjoint_buf: that of rvio_hip_get_window_joint ((6 (nmax + 1))^2 doubles, then nmax + 1 pose records); each allocated by the first call
+    DevRing<rvio_window_edge> edg{"edge-odometry", "rvio_hip_set_edge_odometry"};
+    int edg_new = 0, edg_old = 1;
+    char* wedge_buf = nullptr;
+    char* wjoint_buf = nullptr;
     // IMU-rate ring (imu_pose_kernel in front of whatever propagates in place): allocated by rvio_hip_set_imu_odometry, outside the slab;
     // imuo.seq counts the samples recorded (the m of every propagate while the ring is on)
     DevRing<rvio_imu_pose> imuo{"IMU-rate odometry", "rvio_hip_set_imu_odometry"};
@@ -632,6 +640,8 @@ static const void* lp_kernel_fn(int k) {
         case LPK_AUX_ITER4: return (const void*)aux_iter_kernel<4>;
         case LPK_AUX_ITER16: return (const void*)aux_iter_kernel<16>;
         case LPK_WINDOW_POSE: return (const void*)window_pose_kernel;
+        case LPK_WINDOW_EDGE: return (const void*)window_edge_kernel;
+        case LPK_WINDOW_JOINT: return (const void*)window_joint_kernel;
     }
     return nullptr;
 }
@@ -923,6 +933,7 @@ int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n
     h->lm_frame = -1;   // no cloud since initialisation (the enable flag stays)
     h->odom.seq = 0;    // ... and no odometry record: seq restarts at 1 (the getters read nothing beyond seq)
     h->smo.seq = 0;     // ... nor a smoothed one
+    h->edg.seq = 0;     // ... nor an edge
     h->imuo.seq = 0;    // ... nor an IMU-rate record
     h->imuc.seq = 0; h->imuc_first = 1;   // ... nor its covariance
     // a (re-)initialised filter starts with an empty window: the tracker starts over too (mbIsTheFirstImage, Tracker.cc:88), or its
@@ -1552,6 +1563,133 @@ int rvio_hip_get_smoothed_odometry_all(rvio_hip* h, rvio_window_pose* out, int64
     if (h->smo.seq == 0) return RVIO_OK;
     HIPCHK(h, hipMemcpyAsync(out, h->smo.slot(h->smo.seq, h->batch), sizeof(rvio_window_pose) * h->batch, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RVIO_OK;
+}
+
+// ------------------------------------------------------------------ pose-graph export: window edges and joint covariance (window_edge.hip)
+static_assert(sizeof(rvio_window_edge) == 8 * LP_WEDGE_WORDS, "include/rvio_hip.h: rvio_window_edge has no padding");
+static_assert(LP_WEDGE_MAX_PAIRS == RVIO_MAX_LEN * (RVIO_MAX_LEN + 1) / 2, "launch_plan.h: every pair of the longest window");
+// window_edge_kernel on `instances` instances from x / P on, the pairs of the device lists (NULL: the one pair (a0, b0)), record (z, pair) into
+// out[z * out_stride + pair]; the filter stream, which owns x and P
+static void launch_window_edge(rvio_hip* h, int instances, const double* x, const double* P, int n_pairs, const int* d_new, const int* d_old, int a0, int b0,
+                               long long seq, rvio_window_edge* out, size_t out_stride) {
+    const LpLaunch l = window_edge_launch(instances, n_pairs);
+    hipLaunchKernelGGL(window_edge_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->n_clones_host, h->dc.dmax, x, P, h->slab_bytes, d_new, d_old, a0, b0,
+                       h->composed_count, seq, (unsigned long long*)out, out_stride);
+}
+int rvio_hip_get_window_edges(rvio_hip* h, int instance, int n_pairs, const int32_t* age_new, const int32_t* age_old, rvio_window_edge* out) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (!age_new || !age_old || !out) { h->err = "rvio_hip_get_window_edges: NULL age_new, age_old or out"; return RVIO_ERR_INVALID; }
+    if (instance < 0 || instance >= h->batch) { h->err = "rvio_hip_get_window_edges: instance out of range"; return RVIO_ERR_INVALID; }
+    if (n_pairs < 1 || n_pairs > LP_WEDGE_MAX_PAIRS) { h->err = "rvio_hip_get_window_edges: n_pairs outside 1 .. 528"; return RVIO_ERR_INVALID; }
+    RCCHK(window_check(h, "rvio_hip_get_window_edges"));
+    for (int i = 0; i < n_pairs; ++i)
+        if (!(age_new[i] >= 0 && age_new[i] < age_old[i] && age_old[i] <= h->n_clones_host)) {
+            h->err = "rvio_hip_get_window_edges: pair " + std::to_string(i) + " (" + std::to_string(age_new[i]) + ", " + std::to_string(age_old[i]) +
+                     ") is not 0 <= age_new < age_old <= n_clones = " + std::to_string(h->n_clones_host);
+            return RVIO_ERR_INVALID;
+        }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t rec_bytes = sizeof(rvio_window_edge) * (size_t)LP_WEDGE_MAX_PAIRS, list_bytes = sizeof(int32_t) * (size_t)LP_WEDGE_MAX_PAIRS;
+    if (!h->wedge_buf) RCCHK(own_dev(h, &h->wedge_buf, rec_bytes + 2 * list_bytes));
+    rvio_window_edge* d_rec = (rvio_window_edge*)h->wedge_buf;
+    int* d_new = (int*)(h->wedge_buf + rec_bytes);
+    int* d_old = (int*)(h->wedge_buf + rec_bytes + list_bytes);
+    HIPCHK(h, hipMemcpyAsync(d_new, age_new, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_old, age_old, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, h->stream));
+    const size_t off = (size_t)instance * h->slab_bytes;
+    launch_window_edge(h, 1, (const double*)((const char*)h->x[h->cur] + off), (const double*)((const char*)h->P[h->cur] + off), n_pairs, d_new, d_old, 0, 0, 0,
+                       d_rec, (size_t)n_pairs);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out, d_rec, sizeof(rvio_window_edge) * (size_t)n_pairs, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RVIO_OK;
+}
+int rvio_hip_get_window_edges_dev(rvio_hip* h, int n_pairs, const int32_t* d_age_new, const int32_t* d_age_old, rvio_window_edge* d_out, size_t out_stride) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (!d_age_new || !d_age_old || !d_out) { h->err = "rvio_hip_get_window_edges_dev: NULL d_age_new, d_age_old or d_out"; return RVIO_ERR_INVALID; }
+    if (n_pairs < 1 || n_pairs > 65535) { h->err = "rvio_hip_get_window_edges_dev: n_pairs outside 1 .. 65535"; return RVIO_ERR_INVALID; }
+    if (out_stride < (size_t)n_pairs) { h->err = "rvio_hip_get_window_edges_dev: out_stride is below n_pairs"; return RVIO_ERR_INVALID; }
+    RCCHK(window_check(h, "rvio_hip_get_window_edges_dev"));
+    HIPCHK(h, hipSetDevice(h->device));
+    launch_window_edge(h, h->batch, h->x[h->cur], h->P[h->cur], n_pairs, d_age_new, d_age_old, 0, 0, 0, d_out, out_stride);
+    HIPCHK(h, hipGetLastError());
+    return RVIO_OK;
+}
+// the ring: rvio_hip_set_smoothed_odometry's clauses; another pair empties a ring that stays
+int rvio_hip_set_edge_odometry(rvio_hip* h, int capacity, int age_new, int age_old) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (!(age_new >= 0 && age_new < age_old && age_old <= h->cfg.max_track_len - 1)) {
+        h->err = "rvio_hip_set_edge_odometry: not 0 <= age_new < age_old <= max_track_len - 1"; return RVIO_ERR_INVALID;
+    }
+    if (capacity < 0 || capacity > 65536) { h->err = "rvio_hip_set_edge_odometry: capacity outside 0 .. 65536"; return RVIO_ERR_INVALID; }
+    const bool kept = capacity > 0 && capacity == h->edg.cap;
+    RCCHK(ring_set_capacity(h, h->edg, capacity, 65536));
+    if (capacity == 0) return RVIO_OK;
+    if (kept && (age_new != h->edg_new || age_old != h->edg_old)) {
+        { const int rc = drain_all(h); if (rc != RVIO_OK) return rc; }
+        HIPCHK(h, hipMemsetAsync(h->edg.ring, 0, sizeof(rvio_window_edge) * (size_t)h->edg.cap * h->batch, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        h->edg.seq = 0;
+    }
+    h->edg_new = age_new; h->edg_old = age_old;
+    return RVIO_OK;
+}
+int rvio_hip_get_edge_odometry(rvio_hip* h, int instance, int64_t first_seq, int max_n, rvio_window_edge* out, int32_t* n) {
+    return h ? ring_read(h, h->edg, instance, first_seq, max_n, out, n) : RVIO_ERR_INVALID;
+}
+int rvio_hip_get_edge_odometry_all(rvio_hip* h, rvio_window_edge* out, int64_t* seq) {
+    if (!h || !out) return RVIO_ERR_INVALID;
+    if (!ring_exists(h, h->edg)) return RVIO_ERR_STATE;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (seq) *seq = h->edg.seq;
+    if (h->edg.seq == 0) return RVIO_OK;
+    HIPCHK(h, hipMemcpyAsync(out, h->edg.slot(h->edg.seq, h->batch), sizeof(rvio_window_edge) * h->batch, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RVIO_OK;
+}
+// window_joint_kernel on `instances` instances from x / P on, ages 0 .. n_ages - 1: pose (z, a) into poses[z * pose_stride + a], instance z's matrix
+// (row-major, leading dimension ldc) cov_stride doubles behind instance 0's
+static void launch_window_joint(rvio_hip* h, int instances, const double* x, const double* P, int n_ages, rvio_window_pose* poses, size_t pose_stride, double* cov,
+                                size_t cov_stride, int ldc) {
+    const LpLaunch l = window_joint_launch(instances, n_ages);
+    hipLaunchKernelGGL(window_joint_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->n_clones_host, h->dc.dmax, x, P, h->slab_bytes, h->composed_count,
+                       (unsigned long long*)poses, pose_stride, cov, cov_stride, ldc);
+}
+int rvio_hip_get_window_joint(rvio_hip* h, int instance, int max_n, rvio_window_pose* poses, double* cov, size_t ld, int32_t* n) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (!poses || !cov || !n) { h->err = "rvio_hip_get_window_joint: NULL poses, cov or n"; return RVIO_ERR_INVALID; }
+    if (instance < 0 || instance >= h->batch) { h->err = "rvio_hip_get_window_joint: instance out of range"; return RVIO_ERR_INVALID; }
+    if (max_n < 1) { h->err = "rvio_hip_get_window_joint: max_n < 1"; return RVIO_ERR_INVALID; }
+    if (ld < 6 * (size_t)max_n) { h->err = "rvio_hip_get_window_joint: ld is below 6 max_n"; return RVIO_ERR_INVALID; }
+    RCCHK(window_check(h, "rvio_hip_get_window_joint"));
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t side = 6 * (size_t)(h->dc.nmax + 1), cov_bytes = sizeof(double) * side * side;
+    if (!h->wjoint_buf) RCCHK(own_dev(h, &h->wjoint_buf, cov_bytes + sizeof(rvio_window_pose) * (size_t)(h->dc.nmax + 1)));
+    double* d_cov = (double*)h->wjoint_buf;
+    rvio_window_pose* d_poses = (rvio_window_pose*)(h->wjoint_buf + cov_bytes);
+    const int cnt = std::min(h->n_clones_host + 1, max_n);
+    const size_t off = (size_t)instance * h->slab_bytes;
+    launch_window_joint(h, 1, (const double*)((const char*)h->x[h->cur] + off), (const double*)((const char*)h->P[h->cur] + off), cnt, d_poses, (size_t)cnt, d_cov,
+                        0, 6 * cnt);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(poses, d_poses, sizeof(rvio_window_pose) * (size_t)cnt, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpy2DAsync(cov, sizeof(double) * ld, d_cov, sizeof(double) * 6 * (size_t)cnt, sizeof(double) * 6 * (size_t)cnt, 6 * (size_t)cnt,
+                               hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *n = cnt;
+    return RVIO_OK;
+}
+int rvio_hip_get_window_joint_dev(rvio_hip* h, int n_ages, rvio_window_pose* d_poses, size_t pose_stride, double* d_cov, size_t cov_stride) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (!d_poses || !d_cov) { h->err = "rvio_hip_get_window_joint_dev: NULL d_poses or d_cov"; return RVIO_ERR_INVALID; }
+    if (n_ages < 1 || n_ages > RVIO_MAX_LEN) { h->err = "rvio_hip_get_window_joint_dev: n_ages outside 1 .. 32"; return RVIO_ERR_INVALID; }
+    if (pose_stride < (size_t)n_ages) { h->err = "rvio_hip_get_window_joint_dev: pose_stride is below n_ages"; return RVIO_ERR_INVALID; }
+    if (cov_stride < 36 * (size_t)n_ages * n_ages) { h->err = "rvio_hip_get_window_joint_dev: cov_stride is below (6 n_ages)^2"; return RVIO_ERR_INVALID; }
+    RCCHK(window_check(h, "rvio_hip_get_window_joint_dev"));
+    HIPCHK(h, hipSetDevice(h->device));
+    launch_window_joint(h, h->batch, h->x[h->cur], h->P[h->cur], n_ages, d_poses, pose_stride, d_cov, cov_stride, 6 * n_ages);
+    HIPCHK(h, hipGetLastError());
     return RVIO_OK;
 }
 
@@ -2297,6 +2435,12 @@ static int augment_compose_dev(rvio_hip* h, int do_augment) {
     if (h->smo.on && h->n_clones_host >= h->smo_lag) {
         h->smo.seq++;
         launch_window_pose(h, h->batch, h->x[h->cur], h->P[h->cur], h->smo_lag, 1, h->smo.seq, h->smo.slot(h->smo.seq, h->batch), 1);
+        HIPCHK(h, hipGetLastError());
+    }
+    // the edge record behind it, likewise: the pair (edg_new, edg_old), once the window reaches the older frame
+    if (h->edg.on && h->n_clones_host >= h->edg_old) {
+        h->edg.seq++;
+        launch_window_edge(h, h->batch, h->x[h->cur], h->P[h->cur], 1, nullptr, nullptr, h->edg_new, h->edg_old, h->edg.seq, h->edg.slot(h->edg.seq, h->batch), 1);
         HIPCHK(h, hipGetLastError());
     }
     return RVIO_OK;

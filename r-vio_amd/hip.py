@@ -35,6 +35,8 @@ SYMBOLS = [
     "rvio_hip_update_fix", "rvio_hip_update_fix_dev", "rvio_hip_get_fix", "rvio_hip_get_fix_rows",
     "rvio_hip_update_fix_past", "rvio_hip_update_fix_past_dev", "rvio_hip_frame_age",
     "rvio_hip_get_window", "rvio_hip_get_window_dev", "rvio_hip_set_smoothed_odometry", "rvio_hip_get_smoothed_odometry", "rvio_hip_get_smoothed_odometry_all",
+    "rvio_hip_get_window_edges", "rvio_hip_get_window_edges_dev", "rvio_hip_set_edge_odometry", "rvio_hip_get_edge_odometry", "rvio_hip_get_edge_odometry_all",
+    "rvio_hip_get_window_joint", "rvio_hip_get_window_joint_dev",
     "rvio_hip_update_rel", "rvio_hip_update_rel_dev",
     "rvio_hip_update_map", "rvio_hip_update_map_dev", "rvio_hip_get_map", "rvio_hip_get_map_rows",
     "rvio_hip_set_meas_iterations", "rvio_hip_get_meas_iterations", "rvio_hip_get_meas_iter",
@@ -537,6 +539,64 @@ class RvioHip:
         seq = C.c_int64(0)
         self._ck(self.L.rvio_hip_get_smoothed_odometry_all(self.h, out.ctypes.data_as(C.POINTER(abi.rvio_window_pose)), C.byref(seq)), "get_smoothed_odometry_all")
         return int(seq.value), out
+
+    # ---- pose-graph export: window edges and the joint covariance of the window's poses (csrc/window_edge.hip)
+    def get_window_edges(self, pairs, instance=0):
+        """the edges (relative pose and its covariance) between the frames (age_new, age_old) of `pairs` of one instance, at the state as it is
+        now (abi.WINDOW_EDGE_DTYPE)"""
+        pr = np.asarray(pairs, np.int32).reshape(-1, 2)
+        a, b = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        out = np.zeros(max(len(pr), 1), abi.WINDOW_EDGE_DTYPE)
+        self._ck(self.L.rvio_hip_get_window_edges(self.h, int(instance), len(pr), a.ctypes.data_as(C.POINTER(C.c_int32)), b.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  out.ctypes.data_as(C.POINTER(abi.rvio_window_edge))), "get_window_edges")
+        return out[: len(pr)].copy()
+
+    def get_window_edges_dev(self, n_pairs, d_age_new_ptr, d_age_old_ptr, d_out_ptr, out_stride):
+        """every instance, one pair list on the device for all of them: (instance, pair) at d_out[instance * out_stride + pair].  Asynchronous on
+        the filter stream."""
+        self._ck(self.L.rvio_hip_get_window_edges_dev(self.h, int(n_pairs), C.c_void_p(d_age_new_ptr), C.c_void_p(d_age_old_ptr), C.c_void_p(d_out_ptr),
+                                                      C.c_size_t(int(out_stride))), "get_window_edges_dev")
+
+    def set_edge_odometry(self, capacity, age_new, age_old):
+        """keep an rvio_window_edge record of the pair (age_new, age_old) behind every augment/compose stage from the next one on, `capacity` per
+        instance on the device; 0: off"""
+        self._ck(self.L.rvio_hip_set_edge_odometry(self.h, int(capacity), int(age_new), int(age_old)), "set_edge_odometry")
+        if capacity:
+            self._edg_cap = int(capacity)
+
+    def edge_odometry(self, instance=0, first_seq=1, max_n=None):
+        """records of one instance still in the edge ring with seq >= first_seq, oldest first (at most max_n): abi.WINDOW_EDGE_DTYPE"""
+        cap = getattr(self, "_edg_cap", 0) if max_n is None else int(max_n)
+        out = np.zeros(max(cap, 0), abi.WINDOW_EDGE_DTYPE)
+        n = C.c_int32(0)
+        self._ck(self.L.rvio_hip_get_edge_odometry(self.h, int(instance), C.c_int64(int(first_seq)), cap,
+                                                   out.ctypes.data_as(C.POINTER(abi.rvio_window_edge)) if len(out) else None, C.byref(n)), "get_edge_odometry")
+        return out[: n.value].copy()
+
+    def edge_odometry_all(self):
+        """(seq, the newest edge record of every instance); seq = 0 and zeroed records before the first one"""
+        out = np.zeros(self.batch, abi.WINDOW_EDGE_DTYPE)
+        seq = C.c_int64(0)
+        self._ck(self.L.rvio_hip_get_edge_odometry_all(self.h, out.ctypes.data_as(C.POINTER(abi.rvio_window_edge)), C.byref(seq)), "get_edge_odometry_all")
+        return int(seq.value), out
+
+    def get_window_joint(self, instance=0, max_n=None):
+        """(poses, cov): the rvio_window_pose records of ages 0 .. m - 1, m = min(n_clones + 1, max_n), newest first, and the joint covariance
+        (6 m x 6 m) of those poses, block (a, b) = J_a P J_b^T"""
+        cap = self.nmax + 1 if max_n is None else int(max_n)
+        poses = np.zeros(max(cap, 1), abi.WINDOW_POSE_DTYPE)
+        cov = np.zeros((6 * max(cap, 1), 6 * max(cap, 1)))
+        n = C.c_int32(0)
+        self._ck(self.L.rvio_hip_get_window_joint(self.h, int(instance), cap, poses.ctypes.data_as(C.POINTER(abi.rvio_window_pose)),
+                                                  cov.ctypes.data_as(C.POINTER(C.c_double)), C.c_size_t(cov.shape[1]), C.byref(n)), "get_window_joint")
+        m = n.value
+        return poses[:m].copy(), cov[: 6 * m, : 6 * m].copy()
+
+    def get_window_joint_dev(self, n_ages, d_poses_ptr, pose_stride, d_cov_ptr, cov_stride):
+        """every instance, ages 0 .. n_ages - 1: pose (instance, age) at d_poses[instance * pose_stride + age], the instance's 6 n_ages x 6 n_ages
+        matrix at d_cov + instance * cov_stride doubles.  Asynchronous on the filter stream."""
+        self._ck(self.L.rvio_hip_get_window_joint_dev(self.h, int(n_ages), C.c_void_p(d_poses_ptr), C.c_size_t(int(pose_stride)), C.c_void_p(d_cov_ptr),
+                                                      C.c_size_t(int(cov_stride))), "get_window_joint_dev")
 
     # ---- IMU-rate odometry (PreIntegrator.cc:168-176 kept per sample)
     def predict(self, imu, instance=0):
