@@ -219,6 +219,7 @@ System::~System() {
     delete static_cast<std::ofstream*>(f_pose_);
     delete static_cast<std::ofstream*>(f_time_);
     delete static_cast<std::ofstream*>(f_lm_);
+    delete static_cast<std::ofstream*>(f_lmc_);
     if (h_) rvio_hip_destroy(h_);
 }
 
@@ -243,6 +244,30 @@ int System::write_landmarks(double t) {
     lm_last_ = frame;
     auto& f = *static_cast<std::ofstream*>(f_lm_);
     f << format_landmarks(t, frame, n, lm_feat_.data(), lm_pw_.data(), lm_pr_.data());
+    f.flush();
+    return 0;
+}
+
+bool System::record_landmark_cov_to(const std::string& path) {
+    if (!h_) return false;
+    auto* f = new std::ofstream(path, std::ofstream::out);
+    if (!*f) { delete f; err_ = "cannot write " + path; return false; }
+    if (rvio_hip_set_landmark_cov(h_, 1) != RVIO_OK) { delete f; err_ = rvio_hip_last_error(h_); return false; }
+    delete static_cast<std::ofstream*>(f_lmc_);
+    f_lmc_ = f;
+    lmc_rec_.assign((size_t)(s_.cfg.n_features + 1) / 2, rvio_landmark_cov());
+    lmc_last_ = -1;
+    return true;
+}
+
+// behind a filtered frame: the records of the frame's cloud, if it had one (the stamp is new)
+int System::write_landmark_cov(double t) {
+    int32_t n = 0, frame = -1;
+    if (rvio_hip_get_landmark_cov(h_, &n, &frame, lmc_rec_.data()) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
+    if (frame < 0 || frame == lmc_last_) return 0;
+    lmc_last_ = frame;
+    auto& f = *static_cast<std::ofstream*>(f_lmc_);
+    f << format_landmark_cov(t, n, lmc_rec_.data());
     f.flush();
     return 0;
 }
@@ -917,6 +942,7 @@ int System::MonoVIO(PoseLine* pose) {
             if (rvio_hip_get_pose(h_, pose->p, pose->q) != RVIO_OK) { err_ = rvio_hip_last_error(h_); return -1; }
         }
         if (f_lm_ && write_landmarks(image.t) < 0) return -1;
+    if (f_lmc_ && write_landmark_cov(image.t) < 0) return -1;
         if (f_od_ && note_odometry(image.t) < 0) return -1;
         if (f_sm_ && note_smoothed(image.t) < 0) return -1;
         if (f_ed_ && note_edges(image.t) < 0) return -1;
@@ -948,6 +974,7 @@ int System::MonoVIO(PoseLine* pose) {
     fp << format_pose(pl); fp.flush();
     ft << format_time_cost(n_img_, t2 - t1, t3 - t2); ft.flush();
     if (f_lm_ && write_landmarks(image.t) < 0) return -1;
+    if (f_lmc_ && write_landmark_cov(image.t) < 0) return -1;
     if (f_od_ && note_odometry(image.t) < 0) return -1;
     if (f_sm_ && note_smoothed(image.t) < 0) return -1;
     if (f_ed_ && note_edges(image.t) < 0) return -1;
@@ -1031,6 +1058,24 @@ std::string format_landmarks(double t, int frame, int n, const int32_t* feat, co
         const double *w = p_world + 3 * i, *r = p_r + 3 * i;
         std::snprintf(buf, sizeof buf, "%.19g %d %d %.19g %.19g %.19g %.19g %.19g %.19g\n", t, frame, (int)feat[i], w[0], w[1], w[2], r[0], r[1], r[2]);
         out += buf;
+    }
+    return out;
+}
+
+std::string format_landmark_cov(double t, int n, const rvio_landmark_cov* rec) {
+    std::string out;
+    char buf[64];
+    for (int i = 0; i < n; ++i) {
+        const rvio_landmark_cov& r = rec[i];
+        std::snprintf(buf, sizeof buf, "%.19g %d %d %d", t, (int)r.feat, (int)r.n_obs, (int)r.status);
+        out += buf;
+        auto add = [&](double v) { std::snprintf(buf, sizeof buf, " %.19g", v); out += buf; };
+        for (int k = 0; k < 3; ++k) add(r.p_w[k]);
+        for (int a = 0; a < 3; ++a) for (int b = a; b < 3; ++b) add(r.cov_w[3 * a + b]);
+        for (int k = 0; k < 3; ++k) add(r.p_r[k]);
+        for (int a = 0; a < 3; ++a) for (int b = a; b < 3; ++b) add(r.cov_r[3 * a + b]);
+        add(r.rho); add(r.rho_sigma);
+        out += "\n";
     }
     return out;
 }

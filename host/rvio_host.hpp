@@ -171,6 +171,10 @@ public:
     // handle (rvio_hip_set_landmarks) and appends the cloud to `path` behind every frame whose update stamp is new — one line per point,
     // format_landmarks.  The settings file has no key for it.
     bool record_landmarks_to(const std::string& path);
+    // The 3 x 3 covariance of every cloud point (rvio_hip_set_landmark_cov; it switches the cloud on if that is off): appends the records of
+    // the cloud to `path` behind every frame whose update stamp is new — one line per point, format_landmark_cov.  The file of
+    // record_landmarks_to keeps its format.  The settings file has no key for it.
+    bool record_landmark_cov_to(const std::string& path);
     // What the reference publishes every frame as nav_msgs::Odometry and appends to its nav_msgs::Path (System.cc:402-434): enables the
     // handle's odometry ring (rvio_hip_set_odometry, `ring` records) and keeps the image timestamps by seq on the host.  The ring is read
     // with ONE rvio_hip_get_odometry whenever ring / 2 frames are outstanding and once more at the end (flush_odometry, also run by the
@@ -304,6 +308,10 @@ private:
     std::vector<int32_t> lm_feat_;
     std::vector<double> lm_pr_, lm_pw_;
     int write_landmarks(double t);
+    void* f_lmc_ = nullptr;       // std::ofstream* of record_landmark_cov_to
+    int lmc_last_ = -1;           // frame stamp of the last records written
+    std::vector<rvio_landmark_cov> lmc_rec_;
+    int write_landmark_cov(double t);
     void* f_od_ = nullptr;        // std::ofstream* of record_odometry_to
     int od_ring_ = 0;
     long long od_seq_ = 0, od_read_ = 0;   // frames handed to the filter since initialisation / records written to the file
@@ -371,6 +379,9 @@ bool read_asl(const std::string& root, AslDataset* out, std::string* err);
 std::string format_pose(const PoseLine& p);               // one line of stamped_pose_ests.dat, setprecision(19)
 // the points of one cloud (rvio_hip_get_landmarks), one line each: t frame feat xw yw zw xr yr zr (world frame, then {Rk} as published), %.19g
 std::string format_landmarks(double t, int frame, int n, const int32_t* feat, const double* p_world, const double* p_r);
+// the records of one cloud (rvio_hip_get_landmark_cov), one line each: t feat n_obs status p_w[3] cov_w (the 6 entries on and above the diagonal,
+// by rows) p_r[3] cov_r (likewise) rho rho_sigma, %.19g (NaN prints as nan)
+std::string format_landmark_cov(double t, int n, const rvio_landmark_cov* rec);
 // one record of the odometry ring: t seq px py pz qx qy qz qw vx vy vz c00 ... c55 (pose_cov row by row), %.19g
 std::string format_odometry(double t, const rvio_odom& r);
 // one record of the smoothed-odometry ring in the same layout; the three velocity columns are 0 (the window holds no velocity of a past frame)

@@ -3,7 +3,7 @@
 // the two ROS callbacks would (every image triggers System::MonoVIO, rvio_mono.cc:78-80); poses are written in the format
 // of stamped_pose_ests.dat (System.cc:369-374).
 //
-//   rvio_replay <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--landmarks FILE] [--odometry FILE [--odometry-ring N]]
+//   rvio_replay <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--landmarks FILE] [--landmark-cov FILE] [--odometry FILE [--odometry-ring N]]
 //                                        [--imu-odometry FILE [--imu-odometry-ring N] [--imu-odometry-cov]]
 //                                        --imu-odometry: the pose and velocity behind every IMU sample the filter consumes, read in bulk from the handle's
 //                                        IMU-rate ring of N samples (default 4096; System::record_imu_odometry_to); --imu-odometry-cov: every
@@ -22,6 +22,9 @@
 //                                        handle's edge ring of N records (default 256; System::record_edges_to); one line per record, stamped
 //                                        with the two images it connects (format_edge: t_new t_old p q cov)
 //                                        --landmarks: Updater::update's landmark cloud behind every updating frame (System::record_landmarks_to)
+//                                        --landmark-cov: the 3 x 3 covariance of every cloud point, one line per point: t feat n_obs status p_w[3]
+//                                          cov_w (6 upper) p_r[3] cov_r (6 upper) rho rho_sigma (System::record_landmark_cov_to); the --landmarks
+//                                          file keeps its format
 //                                        [--velocity FILE [--velocity-sigma S] [--velocity-gate]] [--standstill FILE]
 //                                        --standstill: with Standstill.Enable: 1 in the settings (the device-side standstill detector and its
 //                                        zero-velocity update behind every frame), one line per frame `t T disparity n_pairs flags gamma`, kept on the
@@ -279,6 +282,7 @@ struct PassOptions {
     long dump_at = -1;               // filtered-frame index behind which the streams are drained and the hand-over is read back
     long max_frames = -1;
     const char* landmarks = nullptr; // System::record_landmarks_to
+    const char* landmark_cov = nullptr; // System::record_landmark_cov_to
     const char* odometry = nullptr;  // System::record_odometry_to
     int odometry_ring = 256;
     const char* smoothed = nullptr;  // System::record_smoothed_to
@@ -316,6 +320,7 @@ static int run_pass(const Settings& s, const AslDataset& d, int device, const Pa
     System sys(s, device);
     if (!sys.ok()) { *err = sys.error(); return 1; }
     if (o.landmarks && !sys.record_landmarks_to(o.landmarks)) { *err = sys.error(); return 1; }
+    if (o.landmark_cov && !sys.record_landmark_cov_to(o.landmark_cov)) { *err = sys.error(); return 1; }
     if (o.odometry && !sys.record_odometry_to(o.odometry, o.odometry_ring)) { *err = sys.error(); return 1; }
     if (o.smoothed && !sys.record_smoothed_to(o.smoothed, o.smoothed_lag < 0 ? s.cfg.max_track_len - 1 : o.smoothed_lag, o.smoothed_ring)) { *err = sys.error(); return 1; }
     if (o.edges && !sys.record_edges_to(o.edges, s.cfg.max_track_len - 1 - o.edges_span, s.cfg.max_track_len - 1, o.edges_ring)) { *err = sys.error(); return 1; }
@@ -450,7 +455,7 @@ int main(int argc, char** argv) {
     }
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <settings.yaml> <asl_root> [<poses_out.dat>] [--device N] [--max-frames K] [--record-dir DIR] [--record]\n"
-                             "          [--landmarks FILE] [--odometry FILE] [--odometry-ring N] [--smoothed FILE] [--smoothed-lag L] [--smoothed-ring N] [--edges FILE] [--edges-span K] [--edges-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--imu-odometry-cov] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n"
+                             "          [--landmarks FILE] [--landmark-cov FILE] [--odometry FILE] [--odometry-ring N] [--smoothed FILE] [--smoothed-lag L] [--smoothed-ring N] [--edges FILE] [--edges-span K] [--edges-ring N] [--imu-odometry FILE] [--imu-odometry-ring N] [--imu-odometry-cov] [--sync-every-frame] [--stall-seed S] [--noise WGS] [--selfcheck]\n"
                              "          [--velocity FILE] [--velocity-sigma S] [--velocity-gate] [--standstill FILE] [--fix FILE] [--fix-gate] [--fix-latency S]\n"
                              "          [--rel FILE] [--rel-gate] [--map FILE] [--map-units px|norm] [--map-latency S] [--map-gate]\n"
                              "          [--meas-iters N] [--meas-tol T]\n", argv[0]);
@@ -459,6 +464,7 @@ int main(int argc, char** argv) {
     const char* out_path = nullptr;
     int device = 0; long max_frames = -1, stall_seed = -1;
     const char* landmarks = nullptr;
+    const char* landmark_cov = nullptr;
     const char* odometry = nullptr; int odometry_ring = 256;
     const char* smoothed = nullptr; int smoothed_lag = -1, smoothed_ring = 256;
     const char* edges = nullptr; int edges_span = 1, edges_ring = 256;
@@ -478,6 +484,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--sync-every-frame")) sync_every = true;                   // rvio_hip_sync behind every frame (A/B of the pipelining)
         else if (!std::strcmp(argv[i], "--stall-seed") && i + 1 < argc) stall_seed = std::atol(argv[++i]);   // sleeping kernels on random streams (A/B of the ordering)
         else if (!std::strcmp(argv[i], "--noise") && i + 1 < argc) noise_wgs = std::atoi(argv[++i]);         // a loaded chip beside the replay (A/B of timing inside kernels)
+        else if (!std::strcmp(argv[i], "--landmark-cov") && i + 1 < argc) landmark_cov = argv[++i];   // the covariance records of every cloud, one point per line
         else if (!std::strcmp(argv[i], "--landmarks") && i + 1 < argc) landmarks = argv[++i];   // the landmark cloud of every update, one point per line
         else if (!std::strcmp(argv[i], "--odometry") && i + 1 < argc) odometry = argv[++i];     // one line per frame: pose, velocity, pose covariance (read in bulk from the ring)
         else if (!std::strcmp(argv[i], "--odometry-ring") && i + 1 < argc) odometry_ring = std::atoi(argv[++i]);
@@ -564,7 +571,7 @@ int main(int argc, char** argv) {
     if (self) return selfcheck(s, d, device, max_frames, stall_seed, noise_wgs);
     if (sync_every || stall_seed >= 0 || noise_wgs > 0) {   // the plain replay with one of the two A/B pacings
         std::vector<PoseLine> poses; double ms = 0; int flags = 0;
-        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.odometry = odometry; o.odometry_ring = odometry_ring; o.smoothed = smoothed; o.smoothed_lag = smoothed_lag; o.smoothed_ring = smoothed_ring; o.edges = edges; o.edges_span = edges_span; o.edges_ring = edges_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.imu_odometry_cov = imu_odometry_cov; o.velocity = vr; if (fix) { o.fixes = &fixes; o.fix_gate = fix_gate; o.fix_latency = fix_latency; } if (rel) { o.rels = &rels; o.rel_gate = rel_gate; } if (map) { o.maps = &maps; o.map_units = map_units; o.map_latency = map_latency; o.map_gate = map_gate; }
+        PassOptions o; o.max_frames = max_frames; o.sync_every_frame = sync_every; o.stall_seed = stall_seed; o.noise_wgs = noise_wgs; o.landmarks = landmarks; o.landmark_cov = landmark_cov; o.odometry = odometry; o.odometry_ring = odometry_ring; o.smoothed = smoothed; o.smoothed_lag = smoothed_lag; o.smoothed_ring = smoothed_ring; o.edges = edges; o.edges_span = edges_span; o.edges_ring = edges_ring; o.imu_odometry = imu_odometry; o.imu_odometry_ring = imu_odometry_ring; o.imu_odometry_cov = imu_odometry_cov; o.velocity = vr; if (fix) { o.fixes = &fixes; o.fix_gate = fix_gate; o.fix_latency = fix_latency; } if (rel) { o.rels = &rels; o.rel_gate = rel_gate; } if (map) { o.maps = &maps; o.map_units = map_units; o.map_latency = map_latency; o.map_gate = map_gate; }
         if (run_pass(s, d, device, o, &poses, nullptr, &ms, &flags, &err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
         if (out_path) { std::ofstream out(out_path); if (!out) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; } for (const PoseLine& p : poses) out << format_pose(p); }
         std::fprintf(stderr, "rvio_replay: %zu filtered frames, %.3f ms per MonoVIO call, device flags %d\n", poses.size(), ms, flags);
@@ -575,6 +582,7 @@ int main(int argc, char** argv) {
     if (!sys.ok()) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (!sys.record_to(record_dir, force_record)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (landmarks && !sys.record_landmarks_to(landmarks)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
+    if (landmark_cov && !sys.record_landmark_cov_to(landmark_cov)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (odometry && !sys.record_odometry_to(odometry, odometry_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (smoothed && !sys.record_smoothed_to(smoothed, smoothed_lag < 0 ? s.cfg.max_track_len - 1 : smoothed_lag, smoothed_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }
     if (edges && !sys.record_edges_to(edges, s.cfg.max_track_len - 1 - edges_span, s.cfg.max_track_len - 1, edges_ring)) { std::fprintf(stderr, "%s\n", sys.error().c_str()); return 1; }

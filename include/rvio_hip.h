@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov); standstill detection (rvio_standstill_config, rvio_standstill, rvio_standstill_config_default, rvio_hip_set_standstill, rvio_hip_standstill, rvio_hip_standstill_dev, rvio_hip_get_standstill); absolute fixes (rvio_fix_kind, rvio_fix, rvio_fix_diag, rvio_hip_update_fix, rvio_hip_update_fix_dev, rvio_hip_get_fix, rvio_hip_get_fix_rows); past-frame fixes (rvio_hip_update_fix_past, rvio_hip_update_fix_past_dev, rvio_hip_frame_age); relative-pose measurements (rvio_rel_kind, rvio_hip_update_rel, rvio_hip_update_rel_dev); map landmarks (rvio_map_units, rvio_map_obs, rvio_map_point, rvio_map_diag, rvio_hip_update_map, rvio_hip_update_map_dev, rvio_hip_get_map, rvio_hip_get_map_rows); iterated measurement updates (rvio_meas_iter, rvio_hip_set_meas_iterations, rvio_hip_get_meas_iterations, rvio_hip_get_meas_iter) */
+#define RVIO_HIP_ABI_VERSION 6   /* 3: rvio_hip_frame_sharded_dev, IMU batches of any length, error bits 4 (hard) / 8;  4: the rvio_hip_debug_poison / _stall / _noise / _kernel_forms test hooks are part of the exported surface;  5: the payload of rvio_hip_update_local / _global is the packed wire format of csrc/rvio_dev.h shard_layout;  6: the landmark cloud (rvio_hip_set_landmarks, rvio_hip_get_landmarks, rvio_hip_get_landmarks_at);  added WITHIN 6, purely additive (no struct, no existing prototype changed): rvio_hip_set_image_format, rvio_hip_get_image_format; the odometry ring (rvio_odom, rvio_hip_set_odometry, rvio_hip_get_odometry, rvio_hip_get_odometry_all) and rvio_hip_get_pose_at; per-instance calibration (rvio_calibration, rvio_calibration_from_config, rvio_hip_set_calibration_at, rvio_hip_set_calibrations, rvio_hip_get_calibration_at) and rvio_hip_initialize_at; IMU-rate odometry (rvio_imu_pose, rvio_hip_predict, rvio_hip_predict_dev, rvio_hip_set_imu_odometry, rvio_hip_get_imu_odometry); the auxiliary measurement update (rvio_aux_meas, rvio_aux_mode, rvio_hip_update_aux, rvio_hip_update_aux_dev, rvio_hip_get_aux_diag); the covariance of IMU-rate odometry (rvio_imu_cov, rvio_hip_predict_cov, rvio_hip_predict_cov_dev, rvio_hip_set_imu_odometry_cov, rvio_hip_get_imu_odometry_cov); standstill detection (rvio_standstill_config, rvio_standstill, rvio_standstill_config_default, rvio_hip_set_standstill, rvio_hip_standstill, rvio_hip_standstill_dev, rvio_hip_get_standstill); absolute fixes (rvio_fix_kind, rvio_fix, rvio_fix_diag, rvio_hip_update_fix, rvio_hip_update_fix_dev, rvio_hip_get_fix, rvio_hip_get_fix_rows); past-frame fixes (rvio_hip_update_fix_past, rvio_hip_update_fix_past_dev, rvio_hip_frame_age); relative-pose measurements (rvio_rel_kind, rvio_hip_update_rel, rvio_hip_update_rel_dev); map landmarks (rvio_map_units, rvio_map_obs, rvio_map_point, rvio_map_diag, rvio_hip_update_map, rvio_hip_update_map_dev, rvio_hip_get_map, rvio_hip_get_map_rows); iterated measurement updates (rvio_meas_iter, rvio_hip_set_meas_iterations, rvio_hip_get_meas_iterations, rvio_hip_get_meas_iter); landmark covariance (rvio_landmark_cov, rvio_hip_set_landmark_cov, rvio_hip_get_landmark_cov, rvio_hip_get_landmark_cov_at, rvio_hip_get_landmark_cov_dev) */
 /* IMU samples the staging of the host-buffer entry points is allocated for (0.96 s at 200 Hz).  PreIntegrator::propagate iterates any
  * list (PreIntegrator.cc:96-97), and so does every entry point here: a longer batch (dropped images) is accepted — the staging grows once,
  * at the price of one host synchronisation; the _dev entry points take any m. */
@@ -1009,6 +1009,64 @@ int rvio_hip_set_landmarks(rvio_hip* h, int enable);
 int rvio_hip_get_landmarks(rvio_hip* h, int32_t* n, int32_t* frame, int32_t* feat, double* p_r, double* p_world);
 int rvio_hip_get_landmarks_at(rvio_hip* h, int instance, int32_t* n, int32_t* frame, int32_t* feat, double* p_r, double* p_world);
 
+/* --- landmark covariance ------------------------------------------------------ */
+/* The 3 x 3 uncertainty of every point of the cloud, formed on the device behind the cloud (csrc/landmark_cov.hip).  The reference
+ * publishes none.  One record per cloud point, in the cloud's order; 224 bytes, no padding.
+ *
+ * The quantity.  theta = (phi, psi, rho), the inverse-depth estimate in the track's first camera frame, is not a state: it is the
+ * least-squares solution of ALL L observations of the track given the clones (for a type-'2' track too: the halving of
+ * Updater.cc:271-275 concerns the update, not the triangulation).  With Hf (2L x 3) and Hx (2L x 6 nPh, nPh = L - 1) the raw
+ * measurement Jacobians before the nullspace projection, evaluated at the stored estimate, N = Hf^T Hf, A = N^-1 Hf^T and pixel noise
+ * n ~ sigma^2 I (sigma = max(sigma_px, sigma_py), the normalised sigma the update itself uses), to first order
+ *     dtheta = -A (Hx dx + n).
+ * The published point is p_r = g(theta, x-) = R_k (R_ic e(theta) / rho + t_ic) + t_k.  With Jth = dg/dtheta, Jx = dg/d(clone errors)
+ * and M = Jx - Jth A Hx:
+ *     cov_r = sigma^2 Jth N^-1 Jth^T + M P-_span M^T
+ * where (x-, P-) are the state and covariance the update READ (the prior pair), P-_span the rows / columns of the track's clones.
+ * This is exact to first order for that pair, because n is independent of the prior error.
+ *
+ * Frames.  p_r, cov_r: the frame {R} of the cloud (the IMU frame at the end of the track's relative-pose chain), the bits of
+ * rvio_hip_get_landmarks' p_r.  p_w, cov_w: p_w = R(qG-)^T (p_r - pG-) evaluated WHOLLY at the prior state x- — NOT the cloud's
+ * p_world, which uses the updated (qG, pG) — and cov_w the same formula with M_w = R_G^T [dp_w/dthG, dp_w/dpG | M] over the columns
+ * 0 .. 5 of P- and the span, cross blocks included.  Error convention: that of P (R_true ~ (I - [dth x]) R on every rotation,
+ * positions additive); both covariances are row-major and symmetric bit for bit.
+ *
+ * rho_sigma = sqrt(Cov(theta)_22) of the same formula, Cov(theta) = sigma^2 N^-1 + (A Hx) P-_span (A Hx)^T: the cheap parallax test.
+ * status: 0 ok; 1: N is not positive definite to working precision (a Cholesky pivot at or below 64 * 2^-52 of its diagonal entry,
+ * also a non-positive one) — cov_r, cov_w and rho_sigma are NaN, p_r and p_w are still filled.
+ *
+ * NOT done: the posterior-refined landmark theta - A Hx dx and its covariance with P+; a covariance for the cloud's own mixed
+ * p_world (prior clones, posterior (qG, pG)): it needs Cov(dx+, dx-) = (I - K H) P-, which no buffer holds; cross-covariance between
+ * a landmark and the window poses, or between landmarks; a ring of clouds; time stamps in the record; uncertain map points in
+ * rvio_hip_update_map. */
+typedef struct rvio_landmark_cov {
+    int32_t feat;        /* index in the frame's hand-over list: rvio_hip_get_landmarks' feat */
+    int32_t n_obs;       /* L: the observations of the track */
+    int32_t status;      /* 0 ok, 1 N not positive definite */
+    int32_t reserved;    /* 0 */
+    double rho;          /* the inverse depth in the first camera frame */
+    double rho_sigma;
+    double p_r[3];
+    double p_w[3];
+    double cov_r[9];
+    double cov_w[9];
+} rvio_landmark_cov;
+/* Off by default.  Enabling it enables the cloud if that is off; switching the cloud off switches this off.  The first enable drains
+ * the handle and allocates ceil(n_features/2) records per instance; takes effect from the next update enqueued, on a batch handle for
+ * every instance.  The kernel only reads the filter's buffers: (x, P), the cloud and every ring are bit-identical with and without
+ * it, and a handle that does not enable it launches what it launched before. */
+int rvio_hip_set_landmark_cov(rvio_hip* h, int enable);
+/* The records of the most recent cloud: rvio_hip_get_landmarks' rules — n and frame are the cloud's, rec holds ceil(n_features/2)
+ * entries (may be NULL), rvio_hip_initialize clears (n = 0, frame = -1), RVIO_ERR_STATE if the covariance was never enabled,
+ * RVIO_ERR_INVALID for an instance out of range.  A cloud published while the covariance was switched off has no records: n = 0
+ * under the stamp of the last cloud that has.  Feature-sharded handles: each rank covers its own cloud, as documented there. */
+int rvio_hip_get_landmark_cov(rvio_hip* h, int32_t* n, int32_t* frame, rvio_landmark_cov* rec);
+int rvio_hip_get_landmark_cov_at(rvio_hip* h, int instance, int32_t* n, int32_t* frame, rvio_landmark_cov* rec);
+/* Every instance into the caller's DEVICE buffers, enqueued on the handle's stream, nothing waited for: instance i's records from
+ * d_out[i * out_stride] on (out_stride >= ceil(n_features/2) records), its count into d_count[i] (may be NULL).  Records at and
+ * beyond the count are not meaningful. */
+int rvio_hip_get_landmark_cov_dev(rvio_hip* h, rvio_landmark_cov* d_out, size_t out_stride, int32_t* d_count);
+
 /* pyramid level of the most recent image (u8 w*h, int16 (dx,dy) w*h*2) and the raw KLT output
  * (vFeatsTracked + its undistorted-normalised form) of the last track() call */
 int rvio_hip_debug_pyramid(rvio_hip* h, int level, int32_t* w, int32_t* hgt, uint8_t* img, int16_t* dxy);
@@ -1029,7 +1087,9 @@ int rvio_hip_debug_tracked(rvio_hip* h, int n, float* xy, float* un_xy);
  * 13 = the IMU-pose kernel on the state and the IMU batch of the last frame, all instances (a _dev entry point: the caller's IMU buffer must
  * still be alive; into a buffer of its own; RVIO_ERR_UNSUPPORTED unless the IMU-rate ring was enabled and a frame has propagated),
  * 14 = the IMU-covariance kernel as the ring launches it, on the same operands, into a buffer of its own (RVIO_ERR_UNSUPPORTED under 13's
- * conditions, or when the covariance ring is off). */
+ * conditions, or when the covariance ring is off),
+ * 15 = the landmark-covariance kernel as the update launches it, on the cloud and operands of the last update, all instances (into records
+ * of its own; RVIO_ERR_UNSUPPORTED unless rvio_hip_set_landmark_cov was enabled and a cloud has been published). */
 int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us);
 /* Test hook against results that depend on LEFT-OVER state (scratch in HBM, LDS contents, stale hand-over entries).  Drains every stream of
  * the handle, then: what & 1 fills the filter's scratch and the spare state / covariance buffer with 0xff bytes (NaN); & 2 rewrites the LDS

@@ -939,6 +939,135 @@ def window_edge_from_poses(x, a, b, dtype=float):
     return G
 
 
+# ---- landmark covariance: the 3 x 3 uncertainty of every cloud point (rvio_hip_set_landmark_cov, rvio_hip_get_landmark_cov*, csrc/landmark_cov.hip)
+class rvio_landmark_cov(C.Structure):
+    """one cloud point with its covariance in {R} and in the world frame of the PRIOR state: 224 bytes, no padding"""
+    _fields_ = [("feat", C.c_int32), ("n_obs", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32), ("rho", C.c_double),
+                ("rho_sigma", C.c_double), ("p_r", C.c_double * 3), ("p_w", C.c_double * 3), ("cov_r", C.c_double * 9), ("cov_w", C.c_double * 9)]
+
+
+LANDMARK_COV_DTYPE = np.dtype([("feat", "i4"), ("n_obs", "i4"), ("status", "i4"), ("reserved", "i4"), ("rho", "f8"), ("rho_sigma", "f8"),
+                               ("p_r", "f8", 3), ("p_w", "f8", 3), ("cov_r", "f8", (3, 3)), ("cov_w", "f8", (3, 3))])
+assert LANDMARK_COV_DTYPE.itemsize == C.sizeof(rvio_landmark_cov) == 224
+LANDMARK_COV_OK, LANDMARK_COV_SINGULAR = 0, 1
+LANDMARK_COV_PIVOT_EPS = 64 * 2.0 ** -52      # LP_LMC_PIVOT_EPS of csrc/launch_plan.h: a Cholesky pivot of N at or below this share of its diagonal entry is not positive
+
+
+def landmark_sigma(cfg):
+    """the normalised pixel sigma of the update (Updater.cc:42-44): max(sigma_px, sigma_py) as a float widened to double"""
+    return float(max(np.float32(cfg.sigma_px), np.float32(cfg.sigma_py)))
+
+
+def landmark_cov_model_as(cal, x, P, ftype, L, meas, pf, dtype=np.longdouble, sigma=None, hf_only=False):
+    """The covariance of one cloud point evaluated in `dtype` throughout (np.longdouble: the truth the tests hold the device and the float64
+    model to).  cal: anything with T_bc (rvio_config, rvio_calibration); x, P: the state and covariance the update READ; ftype: '1' / '2' (or
+    their codes); L: the track length, all L observations enter (the halving of Updater.cc:271-275 concerns the update, not the triangulation);
+    pf = (phi, psi, rho): the stored inverse-depth estimate in the first camera frame; meas is accepted for symmetry with oracle.feature_model
+    and not read: the Jacobians are evaluated at pf.  sigma: the normalised pixel sigma (None: landmark_sigma(cal), which needs an rvio_config).
+
+    With the chain X_0 = R_ic e / rho + t_ic, X_{i+1} = R_i (X_i - p_i) over the nPh = L - 1 clones of the track (the IMU-frame point at every
+    image of the track) and RI_i = R_{i-1} .. R_0:
+      Hf_i = Hp_i [R_ci RI_i R_ic Jang | R_ci ((RI_i - I) t_ic + tI_i)],   Hx_i[clone j < i] = rho Hp_i R_ci RI_i RI_{j+1}^T [ [X_{j+1} x] | -R_j ]
+      N = Hf^T Hf,  A = N^-1 Hf^T,  Jth = RI_nPh R_ic [Jang / rho | -e / rho^2],  Jx[clone j] = RI_nPh RI_{j+1}^T [ [X_{j+1} x] | -R_j ]
+      M = Jx - Jth A Hx,   cov_r = sigma^2 Jth N^-1 Jth^T + M P_span M^T
+      p_w = R_G^T (p_r - pG),   M_w = R_G^T [ -[(p_r - pG) x] | -I | M ],   cov_w = sigma^2 (R_G^T Jth) N^-1 (R_G^T Jth)^T + M_w P M_w^T
+      rho_sigma^2 = (sigma^2 N^-1 + (A Hx) P_span (A Hx)^T)_22
+    in the error convention of P (inject_state: R_true ~ (I - [dth x]) R, positions additive).  Returns a dict; status 1 (a Cholesky pivot of N
+    at or below LANDMARK_COV_PIVOT_EPS of its diagonal entry): the covariances and rho_sigma are NaN, the points are filled.  hf_only: stop
+    behind Hf and the points (P is not read; what a Gauss-Newton triangulation needs per step).  Calls nothing from the library or the oracle."""
+    dt = np.dtype(dtype).type
+    x = np.asarray(x, dt)
+    P = None if hf_only else np.asarray(P, dt)
+    n = (len(x) - 26) // 7
+    d = 24 + 6 * n
+    L = int(L)
+    nPh = L - 1
+    one = "1" if ftype in ("1", b"1", ord("1")) else "2"
+    assert ftype in ("1", b"1", ord("1"), "2", b"2", ord("2")) and 1 <= nPh <= n
+    skew, q2r, _ = _ops_as(dt)
+    sig = dt(landmark_sigma(cal) if sigma is None else sigma)
+    T = np.array([dt(v) for v in cal.T_bc]).reshape(4, 4)
+    Ric, tic = T[0:3, 0:3], T[0:3, 3]
+    Rci = Ric.T
+    c0 = n - nPh if one == "1" else 0
+    phi, psi, rho = (dt(v) for v in pf)
+    e = np.array([np.cos(phi) * np.sin(psi), np.sin(phi), np.cos(phi) * np.cos(psi)], dt)
+    Jang = np.array([[-np.sin(phi) * np.sin(psi), np.cos(phi) * np.cos(psi)], [np.cos(phi), dt(0)],
+                     [-np.sin(phi) * np.cos(psi), -np.cos(phi) * np.sin(psi)]], dt)
+    I3 = np.eye(3, dtype=dt)
+    R, X, RI, tI = [], [Ric @ (e / rho) + tic], [I3], [np.zeros(3, dt)]
+    for i in range(nPh):
+        a = 26 + 7 * (c0 + i)
+        Ri = q2r(x[a: a + 4])
+        R.append(Ri)
+        X.append(Ri @ (X[-1] - x[a + 4: a + 7]))
+        tI.append(Ri @ (tI[-1] - x[a + 4: a + 7]))
+        RI.append(Ri @ RI[-1])
+
+    def D(i, j):   # d X_i / d (error of clone j), j < i
+        return (RI[i] @ RI[j + 1].T) @ np.hstack([skew(X[j + 1]), -R[j]])
+
+    Hf, Hx = np.zeros((2 * L, 3), dt), np.zeros((2 * L, 6 * n), dt)
+    for i in range(L):
+        pc = Rci @ (X[i] - tic)                       # the point in camera i (t_ci = -R_ci t_ic)
+        h = rho * pc
+        Hp = np.array([[1 / h[2], dt(0), -h[0] / (h[2] * h[2])], [dt(0), 1 / h[2], -h[1] / (h[2] * h[2])]], dt)
+        tc = Rci @ ((RI[i] - I3) @ tic + tI[i])
+        Hf[2 * i: 2 * i + 2, 0:2] = Hp @ (Rci @ RI[i] @ Ric @ Jang)
+        Hf[2 * i: 2 * i + 2, 2] = Hp @ tc
+        for j in range(0 if hf_only else i):
+            c = 6 * (c0 + j)
+            Hx[2 * i: 2 * i + 2, c: c + 6] = rho * (Hp @ Rci @ D(i, j))
+    if hf_only:
+        RG = q2r(x[0:4])
+        return dict(Hf=Hf, p_r=X[nPh], p_w=RG.T @ (X[nPh] - x[4:7]))
+    N = Hf.T @ Hf
+    # 3 x 3 Cholesky, the pivots held to their diagonal entries
+    Lc, status = np.zeros((3, 3), dt), LANDMARK_COV_OK
+    for k in range(3):
+        piv = N[k, k] - Lc[k, :k] @ Lc[k, :k]
+        if not piv > dt(LANDMARK_COV_PIVOT_EPS) * N[k, k]:
+            status = LANDMARK_COV_SINGULAR
+            break
+        Lc[k, k] = np.sqrt(piv)
+        for i in range(k + 1, 3):
+            Lc[i, k] = (N[i, k] - Lc[i, :k] @ Lc[k, :k]) / Lc[k, k]
+    Jth = RI[nPh] @ Ric @ np.hstack([Jang / rho, (-e / (rho * rho)).reshape(3, 1)])
+    Jx = np.zeros((3, 6 * n), dt)
+    for j in range(nPh):
+        Jx[:, 6 * (c0 + j): 6 * (c0 + j) + 6] = D(nPh, j)
+    RG = q2r(x[0:4])
+    p_r = X[nPh]
+    p_w = RG.T @ (p_r - x[4:7])
+    out = dict(status=status, n_obs=int(L), rho=rho, p_r=p_r, p_w=p_w, Hf=Hf, Hx=Hx, N=N, Jtheta=Jth, Jx=Jx, span=(24 + 6 * c0, 24 + 6 * (c0 + nPh)))
+    nan3 = np.full((3, 3), np.nan, dt)
+    if status != LANDMARK_COV_OK:
+        out.update(cov_r=nan3, cov_w=nan3.copy(), rho_sigma=dt(np.nan), cov_theta=nan3.copy(), M=None, M_w=None)
+        return out
+    Li = np.zeros((3, 3), dt)                          # L^-1 by forward substitution, N^-1 = L^-T L^-1
+    for c in range(3):
+        for r in range(c, 3):
+            Li[r, c] = ((dt(1) if r == c else dt(0)) - Lc[r, c:r] @ Li[c:r, c]) / Lc[r, r]
+    Ninv = Li.T @ Li
+    AHx = Ninv @ (Hf.T @ Hx)
+    M = np.zeros((3, d), dt)
+    M[:, 24:] = Jx - Jth @ AHx
+    Mw = RG.T @ M
+    Mw[:, 0:3], Mw[:, 3:6] = -RG.T @ skew(p_r - x[4:7]), -RG.T
+    half = dt(1) / dt(2)
+    Cr = sig * sig * (Jth @ Ninv @ Jth.T) + M @ P @ M.T
+    Jw = RG.T @ Jth
+    Cw = sig * sig * (Jw @ Ninv @ Jw.T) + Mw @ P @ Mw.T
+    Ct = sig * sig * Ninv + AHx @ P[24:, 24:] @ AHx.T
+    out.update(cov_r=half * (Cr + Cr.T), cov_w=half * (Cw + Cw.T), cov_theta=half * (Ct + Ct.T), rho_sigma=np.sqrt(Ct[2, 2]), M=M, M_w=Mw, A=Ninv @ Hf.T)
+    return out
+
+
+def landmark_cov_model(cal, x, P, ftype, L, meas, pf, sigma=None, hf_only=False):
+    """NumPy float64 model of csrc/landmark_cov.hip with analytic Jacobians: landmark_cov_model_as evaluated in float64 (see there)"""
+    return landmark_cov_model_as(cal, x, P, ftype, L, meas, pf, dtype=np.float64, sigma=sigma, hf_only=hf_only)
+
+
 # ---- map landmarks: pixel observations of known world points (rvio_hip_update_map*, csrc/map_rows.hip in front of the auxiliary update)
 RVIO_MAP_NORMALISED, RVIO_MAP_PIXELS = 0, 1
 RVIO_MAP_MAX_POINTS = 8

@@ -207,6 +207,24 @@ static_assert(LP_WEDGE_GROUPS * 36 <= LP_WEDGE_T && LP_WEDGE_WORDS <= LP_WEDGE_T
 // order per entry: the block is not symmetric).  No dynamic part.
 #define LP_WJNT_T LP_WINP_T
 #define LP_WJNT_LDS_DOUBLES (LP_WINP_LDS_DOUBLES + 6 * LP_WINP_NZ + LP_WINP_GROUPS * 36)
+// landmark_cov_kernel (landmark_cov.hip): ONE workgroup of four waves per (instance, cloud slot), grid (cloud slots, 1, instances).  The track's
+// chain (R_i, p_i, the running rotations, the point and the lever translation at every image: LP_LMC_CHAIN doubles), the 2 x 3 blocks Hf_i and
+// rho Hp_i R_ci of its at most LP_FIXP_NMAX + 1 observations, the 4 x 3 products summed per column, the LP_LMC_ROWS = 7 rows (M over {R}, M over
+// the world frame, the rho row of A Hx) of the 6 + 6 nPh <= LP_LMC_NZ columns that are not zero and the product T = P_nz [rows]^T lie in static
+// LDS, beside the shares of the LP_LMC_GROUPS groups of the LP_LMC_ENTS = 9 + 9 + 1 entries (two orders each) and the record's words.  The
+// 2 L x 6 nPh Jacobian Hx is never stored.  No dynamic part.  LP_LMC_PIVOT_EPS: a Cholesky pivot of N at or below this share of its diagonal
+// entry counts as not positive (status 1): 2 L_max rounding errors of the sum that forms the entry.
+#define LP_LMC_T 256
+#define LP_LMC_LMAX (LP_FIXP_NMAX + 1)
+#define LP_LMC_NZ (6 + 6 * LP_FIXP_NMAX)
+#define LP_LMC_ROWS 7
+#define LP_LMC_GROUPS 13
+#define LP_LMC_ENTS 19
+#define LP_LMC_WORDS 28          // sizeof(rvio_landmark_cov) / 8
+#define LP_LMC_PIVOT_EPS (64 * 2.220446049250313e-16)
+#define LP_LMC_CHAIN (LP_FIXP_NMAX * 12 + LP_LMC_LMAX * 15)
+#define LP_LMC_LDS_DOUBLES (LP_LMC_CHAIN + LP_LMC_LMAX * 24 + 2 * LP_LMC_ROWS * LP_LMC_NZ + LP_LMC_GROUPS * LP_LMC_ENTS * 2 + 96 + LP_LMC_WORDS)
+static_assert(LP_LMC_GROUPS * LP_LMC_ENTS <= LP_LMC_T && LP_LMC_NZ <= LP_LMC_T && LP_LMC_WORDS <= LP_LMC_T, "one thread per (group, entry), per non-zero column and per word");
 // doubles between the instances' rows in the block of the map calls, and that block's bytes: rows | r | sigma | (gamma, applied) | records |
 // per-slot records | flags
 LP_HD inline size_t map_H_stride(int dmax) { return (size_t)LP_MAP_ROWS * dmax; }
@@ -219,7 +237,7 @@ enum LpKernel {
     LPK_FEAT_BUILD16, LPK_FEAT_BUILD4, LPK_GRAM_REDUCE, LPK_BLOCK_SUM, LPK_LIT_BATCH, LPK_GEMM_T_LDS, LPK_GRAM_BATCH4, LPK_GRAM_BATCH6, LPK_FEAT_PROP,
     LPK_BOOKKEEP_B, LPK_RANSAC_BOOK, LPK_SOLVE9_SMALL, LPK_SOLVE6_1, LPK_SOLVE6_2, LPK_SOLVE6_3, LPK_JOSEPH_BATCH, LPK_UG, LPK_UG_LDS, LPK_FINAL_LDS,
     LPK_JOSEPH_LDS, LPK_IMU_POSE, LPK_AUX_UPDATE4, LPK_AUX_UPDATE16, LPK_IMU_COV, LPK_STANDSTILL, LPK_FIX, LPK_FIX_PAST, LPK_REL, LPK_MAP,
-    LPK_AUX_ITER4, LPK_AUX_ITER16, LPK_WINDOW_EDGE, LPK_WINDOW_JOINT, LPK_WINDOW_POSE, LPK_COUNT
+    LPK_AUX_ITER4, LPK_AUX_ITER16, LPK_WINDOW_EDGE, LPK_WINDOW_JOINT, LPK_LANDMARK_COV, LPK_WINDOW_POSE, LPK_COUNT
 };
 // (as c++filt prints them, without return type and arguments: how the test finds each kernel's static LDS in the code object's notes)
 static const char* const kLpKernelName[LPK_COUNT] = {
@@ -228,7 +246,7 @@ static const char* const kLpKernelName[LPK_COUNT] = {
     "solve6_kernel<1, 8, 8>", "solve6_kernel<2, 12, 8>", "solve6_kernel<2, 16, 8>", "joseph_batch_kernel", "ug_kernel", "ug_lds_kernel", "final_lds_kernel",
     "joseph_lds_kernel", "imu_pose_kernel", "aux_update_kernel<4>", "aux_update_kernel<16>", "imu_cov_kernel", "standstill_kernel",
     "fix_rows_kernel", "fix_past_kernel", "rel_rows_kernel", "map_rows_kernel", "aux_iter_kernel<4>", "aux_iter_kernel<16>", "window_edge_kernel",
-    "window_joint_kernel", "window_pose_kernel"
+    "window_joint_kernel", "landmark_cov_kernel", "window_pose_kernel"
 };
 
 struct LaunchPlan {
@@ -372,6 +390,8 @@ inline LaunchPlan launch_plan(int max_len, int n_features, int batch, const size
     if (statics[LPK_MAP] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
     // window_edge_kernel, window_joint_kernel: likewise (their p.attr stay 0)
     if (statics[LPK_WINDOW_EDGE] > RVIO_LDS_LIMIT || statics[LPK_WINDOW_JOINT] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
+    // landmark_cov_kernel: likewise (p.attr[LPK_LANDMARK_COV] stays 0)
+    if (statics[LPK_LANDMARK_COV] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
     // window_pose_kernel: likewise (p.attr[LPK_WINDOW_POSE] stays 0)
     if (statics[LPK_WINDOW_POSE] > RVIO_LDS_LIMIT) { p.rc = 1; p.why = "LDS footprint (static + dynamic) of a kernel exceeds the 160 KiB of a CU"; return p; }
     if (batch > 1 && !p.solve5_variant && !p.solve7_variant) { p.rc = 1; p.why = "batched filter: clone window too long for the unrolled solve kernel (6n <= 126)"; return p; }
@@ -559,6 +579,8 @@ LP_HD inline LpLaunch window_pose_launch(int batch, int n_ages) { return {n_ages
 LP_HD inline LpLaunch window_edge_launch(int batch, int n_pairs) { return {n_pairs, 1, batch, LP_WEDGE_T, 0, LPK_WINDOW_EDGE}; }
 // window_joint_kernel: one workgroup of four waves per (instance, age), static LDS only
 LP_HD inline LpLaunch window_joint_launch(int batch, int n_ages) { return {n_ages, 1, batch, LP_WJNT_T, 0, LPK_WINDOW_JOINT}; }
+// landmark_cov_kernel: one workgroup per (instance, cloud slot); the slots at and beyond the cloud's count return at once
+LP_HD inline LpLaunch landmark_cov_launch(int batch, int slots) { return {slots, 1, batch, LP_LMC_T, 0, LPK_LANDMARK_COV}; }
 
 enum LpStream {          // the ROLE of a stream in a call; stream_of (rvio_hip.hip) maps it to one of the handle's four
     LPR_FILTER,          //   the filter stream: every launch of a per-stage call that is not forked to the side stream

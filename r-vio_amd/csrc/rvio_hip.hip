@@ -24,6 +24,7 @@
 #include "solve7.hip"
 #include "solve9.hip"   // round 5: the solve as blocked SPD factorisations on the matrix cores (one instance; every window up to 6n = 192)
 #include "landmarks.hip"   // Updater::update's landmark cloud (rvio_hip_set_landmarks)
+#include "landmark_cov.hip"   // the 3 x 3 covariance of every cloud point, behind landmark_kernel (rvio_hip_set_landmark_cov)
 #include "odom.hip"        // the per-frame odometry record: pose, velocity, covariance (rvio_hip_set_odometry)
 #include "imu_pose.hip"    // IMU-rate odometry: a pose per IMU sample (rvio_hip_predict, rvio_hip_set_imu_odometry)
 #include "imu_cov.hip"     // ... and its covariance: pose_cov / vel_cov per IMU sample (rvio_hip_predict_cov, rvio_hip_set_imu_odometry_cov)
@@ -191,6 +192,10 @@ struct rvio_hip {
     bool lm_on = false;
     int lm_frame = -1;       // nImageCountAfterInit when the update behind the cloud was enqueued, -1: none since create / initialize
     LmOut lm = {nullptr, nullptr, nullptr, nullptr, 0};
+    // landmark covariance (landmark_cov_kernel behind landmark_kernel): Fu records per instance, allocated on the first rvio_hip_set_landmark_cov(1)
+    bool lmc_on = false;
+    int lmc_frame = -1;      // lm_frame of the last cloud the records describe, -1: none since create / initialize
+    rvio_landmark_cov* lmc = nullptr;
     // odometry ring (odom_kernel behind every augment/compose stage): allocated by rvio_hip_set_odometry, outside the slab (a handle that never
     // enables it keeps its memory layout and its launches)
     DevRing<rvio_odom> odom{"odometry", "rvio_hip_set_odometry"};
@@ -642,6 +647,7 @@ static const void* lp_kernel_fn(int k) {
         case LPK_WINDOW_POSE: return (const void*)window_pose_kernel;
         case LPK_WINDOW_EDGE: return (const void*)window_edge_kernel;
         case LPK_WINDOW_JOINT: return (const void*)window_joint_kernel;
+        case LPK_LANDMARK_COV: return (const void*)landmark_cov_kernel;
     }
     return nullptr;
 }
@@ -931,6 +937,7 @@ int rvio_hip_initialize(rvio_hip* h, const double w[3], const double a[3], int n
     initial_state(h->cfg, w, a, n_imu, x, P);
     h->img_count = 0;
     h->lm_frame = -1;   // no cloud since initialisation (the enable flag stays)
+    h->lmc_frame = -1;
     h->odom.seq = 0;    // ... and no odometry record: seq restarts at 1 (the getters read nothing beyond seq)
     h->smo.seq = 0;     // ... nor a smoothed one
     h->edg.seq = 0;     // ... nor an edge
@@ -1275,6 +1282,15 @@ static void launch_landmarks(rvio_hip* h, int n, const LmOut& out) {
 // grid / workgroup of a front-end launch as front_forms() (launch_plan.h) fixed them
 static dim3 lp_grid(const LpLaunch& l) { return dim3((unsigned)l.gx, (unsigned)l.gy, (unsigned)l.gz); }
 static dim3 lp_block(const LpLaunch& l) { return dim3((unsigned)l.threads); }
+static_assert(sizeof(rvio_landmark_cov) == 8 * LP_LMC_WORDS, "include/rvio_hip.h: rvio_landmark_cov has no padding");
+// landmark_cov_kernel behind landmark_kernel (h->cur already toggled): the cloud `cloud` as that launch left it, the state AND covariance the
+// update read (x[cur ^ 1], P[cur ^ 1]: every update form writes the other buffers; augcomp_kernel2 rewrites these next), Fu records per instance
+static void launch_landmark_cov(rvio_hip* h, int n, const LmOut& cloud, rvio_landmark_cov* rec) {
+    const LpLaunch l = landmark_cov_launch(h->batch, h->dc.Fu);
+    hipLaunchKernelGGL(landmark_cov_kernel, lp_grid(l), lp_block(l), l.lds, h->stream, h->dc, n, h->dc.dmax, (const double*)h->x[h->cur ^ 1], (const double*)h->P[h->cur ^ 1],
+                       (const unsigned char*)h->t.types, (const int*)h->t.len, (const double*)h->pfinv, h->slab_bytes, h->bin, cloud, (const CamCal*)h->cal,
+                       LmcOut{(unsigned long long*)rec, (size_t)h->dc.Fu});
+}
 // cornerSubPix on the detector's raw corners, in the form f names (frame: the instrumented build's stamp)
 static void launch_subpix(rvio_hip* h, const FrontForms& f, const DetDev& q, const uint8_t* img, int stride, size_t src_bs, int frame, hipStream_t st) {
     const size_t bs = h->slab_bytes;
@@ -1328,8 +1344,10 @@ static int update_global_dev(rvio_hip* h, const double* d_blocks, int world, boo
     h->cur ^= 1;
     if (h->lm_on) {   // the cloud: x[cur] is xk1k1 now, x[cur ^ 1] still xk1k (every update form writes the other buffer; augcomp_kernel2 rewrites it next)
         launch_landmarks(h, n, h->lm);
+        if (h->lmc_on) launch_landmark_cov(h, n, h->lm, h->lmc);
         HIPCHK(h, hipGetLastError());
         h->lm_frame = h->img_count;
+        if (h->lmc_on) h->lmc_frame = h->lm_frame;
     }
     return RVIO_OK;
 }
@@ -1391,6 +1409,7 @@ int rvio_hip_set_landmarks(rvio_hip* h, int enable) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     h->lm_on = enable != 0;
+    if (!h->lm_on) h->lmc_on = false;   // (the covariance follows the cloud: without one there is nothing it could describe)
     return RVIO_OK;
 }
 int rvio_hip_get_landmarks_at(rvio_hip* h, int instance, int32_t* n, int32_t* frame, int32_t* feat, double* p_r, double* p_world) {
@@ -1418,6 +1437,59 @@ int rvio_hip_get_landmarks_at(rvio_hip* h, int instance, int32_t* n, int32_t* fr
 }
 int rvio_hip_get_landmarks(rvio_hip* h, int32_t* n, int32_t* frame, int32_t* feat, double* p_r, double* p_world) {
     return rvio_hip_get_landmarks_at(h, 0, n, frame, feat, p_r, p_world);
+}
+
+// ------------------------------------------------------------------ landmark covariance (landmark_cov.hip)
+int rvio_hip_set_landmark_cov(rvio_hip* h, int enable) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (enable) {
+        if (!h->lm_on) RCCHK(rvio_hip_set_landmarks(h, 1));
+        if (!h->lmc) {   // first enable: allocated with nothing in flight, cleared (a record past the cloud's count is never handed out)
+            { const int rc = drain_all(h); if (rc != RVIO_OK) return rc; }
+            RCCHK(own_dev(h, &h->lmc, sizeof(rvio_landmark_cov) * (size_t)h->dc.Fu * h->batch, true));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+    }
+    h->lmc_on = enable != 0;
+    return RVIO_OK;
+}
+int rvio_hip_get_landmark_cov_at(rvio_hip* h, int instance, int32_t* n, int32_t* frame, rvio_landmark_cov* rec) {
+    if (!h || instance < 0 || instance >= h->batch) return RVIO_ERR_INVALID;
+    if (!h->lmc) { h->err = "the landmark covariance was never enabled (rvio_hip_set_landmark_cov)"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    SYNC_FRONT(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    int cnt = 0;
+    // (a cloud published while the covariance was off has no records: n = 0 under the stamp of the last cloud that has)
+    if (h->lmc_frame >= 0 && h->lmc_frame == h->lm_frame) {
+        HIPCHK(h, hipMemcpyAsync(&cnt, (char*)h->lm.count + (size_t)instance * h->lm.bs, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        cnt = std::max(0, std::min(cnt, h->dc.Fu));
+    }
+    if (n) *n = cnt;
+    if (frame) *frame = h->lmc_frame;
+    if (cnt > 0 && rec) {
+        HIPCHK(h, hipMemcpyAsync(rec, h->lmc + (size_t)instance * h->dc.Fu, sizeof(rvio_landmark_cov) * cnt, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return RVIO_OK;
+}
+int rvio_hip_get_landmark_cov(rvio_hip* h, int32_t* n, int32_t* frame, rvio_landmark_cov* rec) {
+    return rvio_hip_get_landmark_cov_at(h, 0, n, frame, rec);
+}
+int rvio_hip_get_landmark_cov_dev(rvio_hip* h, rvio_landmark_cov* d_out, size_t out_stride, int32_t* d_count) {
+    if (!h) return RVIO_ERR_INVALID;
+    if (!d_out) { h->err = "rvio_hip_get_landmark_cov_dev: NULL d_out"; return RVIO_ERR_INVALID; }
+    if (out_stride < (size_t)h->dc.Fu) { h->err = "rvio_hip_get_landmark_cov_dev: out_stride is below the handle's hand-over slots"; return RVIO_ERR_INVALID; }
+    if (!h->lmc) { h->err = "the landmark covariance was never enabled (rvio_hip_set_landmark_cov)"; return RVIO_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t row = sizeof(rvio_landmark_cov) * (size_t)h->dc.Fu;
+    HIPCHK(h, hipMemcpy2DAsync(d_out, sizeof(rvio_landmark_cov) * out_stride, h->lmc, row, row, (size_t)h->batch, hipMemcpyDeviceToDevice, h->stream));
+    if (d_count) {
+        if (h->lmc_frame >= 0 && h->lmc_frame == h->lm_frame) HIPCHK(h, hipMemcpy2DAsync(d_count, sizeof(int32_t), h->lm.count, h->lm.bs, sizeof(int32_t), (size_t)h->batch, hipMemcpyDeviceToDevice, h->stream));
+        else HIPCHK(h, hipMemsetAsync(d_count, 0, sizeof(int32_t) * (size_t)h->batch, h->stream));
+    }
+    return RVIO_OK;
 }
 
 // ------------------------------------------------------------------ odometry ring (System.cc:402-434)
@@ -3378,7 +3450,7 @@ int rvio_hip_debug_tracked(rvio_hip* h, int n, float* xy, float* un_xy) {
 // hot kernel on the operands left behind by the last frame: which = 0 -> solve kernel (W = T^-1 + injection),
 // 1 -> klt_kernel3 on the two resident pyramids, 2 -> feat_build_kernel.  Outputs land in scratch / are idempotent.
 int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us) {
-    if (!h || !avg_us || iters < 1 || which < 0 || which > 14) return RVIO_ERR_INVALID;
+    if (!h || !avg_us || iters < 1 || which < 0 || which > 15) return RVIO_ERR_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
     { const int rcd = drain_all(h); if (rcd != RVIO_OK) return rcd; }   // (every queue of the handle: the run-ahead image chains too)
     const DevCfg& d = h->dc;
@@ -3390,6 +3462,7 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
     if ((which == 6 || which == 9) && !h->det_ready) return RVIO_ERR_UNSUPPORTED;
     if (which == 8 && (h->batch > 1 || !h->plan.fuse_ok || !h->time_imu || n < 1)) return RVIO_ERR_UNSUPPORTED;
     if (which == 10 && !h->lm.count) return RVIO_ERR_UNSUPPORTED;
+    if (which == 15 && (!h->lmc || !h->lm.count || h->lm_frame < 0)) { h->err = "no cloud with covariance has been published (rvio_hip_set_landmark_cov, then an update)"; return RVIO_ERR_UNSUPPORTED; }
     if (which == 11 && (h->pix_fmt == RVIO_PIX_MONO8 || !h->last.gray_src)) { h->err = "no colour or raw image has been handed over (rvio_hip_set_image_format)"; return RVIO_ERR_UNSUPPORTED; }
     if (which == 12 && !ring_exists(h, h->odom)) return RVIO_ERR_UNSUPPORTED;
     if (which == 13 || which == 14) {
@@ -3416,6 +3489,8 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
         RCCHK(lm_alloc(h, &lmt));
         tmps.held.push_back(lmt.count);   // (the one allocation behind the four pointers)
     }
+    rvio_landmark_cov* lct = nullptr;   // (15: into records of its own: the getter's stay the last update's)
+    if (which == 15) RCCHK(tmps.dev(&lct, sizeof(rvio_landmark_cov) * (size_t)h->dc.Fu * h->batch));
     // the forms the frame's update would get at this window (time what the chain sees: the Cholesky factor rides in the per-feature launch / runs on its own
     // queue; the slab holds the factor of the last update): fw for a whole update, fs for one separately timed stage
     const bool pre = h->plan.solve9_nt && (h->plan.solve9_nt <= 6 || h->plan.chol_queue);
@@ -3434,6 +3509,11 @@ int rvio_hip_debug_time_kernel(rvio_hip* h, int which, int iters, float* avg_us)
         } else
         if (which == 14) {   // imu_cov_kernel as the ring launches it, on the same operands
             launch_imu_cov(h, h->stream, h->batch, h->x[h->cur], h->P[h->cur], h->time_imu, h->time_imu_bs, h->time_m, ict, 0, 1, h->time_m, h->img_count);
+        } else
+        if (which == 15) {
+            // landmark_cov_kernel as the update launches it, on the last update's cloud, hand-over table and (phi, psi, rho); the state and covariance
+            // buffers are the ones it reads (behind a whole frame they hold other values — the same arithmetic on the same span)
+            launch_landmark_cov(h, n, h->lm, lct);
         } else
         if (which == 10) {
             // landmark_kernel as the update launches it, on the hand-over table, accept flags and (phi, psi, rho) of the last update; the state

@@ -25,6 +25,7 @@ SYMBOLS = [
     "rvio_hip_create_batch", "rvio_hip_batch_size", "rvio_hip_set_state_at", "rvio_hip_get_state_at", "rvio_hip_frame_tracks_dev",
     "rvio_hip_frame_batch_dev", "rvio_hip_get_tracker_points_at", "rvio_hip_frame_sharded_dev", "rvio_hip_debug_poison", "rvio_hip_debug_stall", "rvio_hip_debug_noise", "rvio_hip_debug_kernel_forms",
     "rvio_hip_set_landmarks", "rvio_hip_get_landmarks", "rvio_hip_get_landmarks_at",
+    "rvio_hip_set_landmark_cov", "rvio_hip_get_landmark_cov", "rvio_hip_get_landmark_cov_at", "rvio_hip_get_landmark_cov_dev",
     "rvio_hip_set_image_format", "rvio_hip_get_image_format",
     "rvio_hip_set_odometry", "rvio_hip_get_odometry", "rvio_hip_get_odometry_all", "rvio_hip_get_pose_at",
     "rvio_calibration_from_config", "rvio_hip_set_calibration_at", "rvio_hip_set_calibrations", "rvio_hip_get_calibration_at", "rvio_hip_initialize_at",
@@ -236,6 +237,26 @@ class RvioHip:
     def landmarks(self):
         return self.landmarks_at(0)
 
+    # ---- landmark covariance (csrc/landmark_cov.hip): the 3 x 3 uncertainty of every cloud point
+    def set_landmark_cov(self, on=True):
+        """form an rvio_landmark_cov record per cloud point behind every update from the next one on (switches the cloud on if it is off)"""
+        self._ck(self.L.rvio_hip_set_landmark_cov(self.h, int(bool(on))), "set_landmark_cov")
+
+    def landmark_cov_at(self, i):
+        """the records of the most recent cloud of instance i: dict(n, frame, rec), rec an array of abi.LANDMARK_COV_DTYPE cut to n"""
+        n, frame = C.c_int32(0), C.c_int32(0)
+        rec = np.zeros(self.Fu, abi.LANDMARK_COV_DTYPE)
+        self._ck(self.L.rvio_hip_get_landmark_cov_at(self.h, int(i), C.byref(n), C.byref(frame), C.c_void_p(rec.ctypes.data)), "get_landmark_cov_at")
+        return dict(n=n.value, frame=frame.value, rec=rec[:n.value].copy())
+
+    def landmark_cov(self):
+        return self.landmark_cov_at(0)
+
+    def landmark_cov_dev(self, d_out_ptr, out_stride, d_count_ptr=None):
+        """every instance's records (and counts) into the caller's device buffers, enqueued on the handle's stream, nothing waited for"""
+        self._ck(self.L.rvio_hip_get_landmark_cov_dev(self.h, C.c_void_p(d_out_ptr), C.c_size_t(out_stride), C.c_void_p(d_count_ptr or 0)),
+                 "get_landmark_cov_dev")
+
     def augment_compose(self, do_augment=True):
         self._ck(self.L.rvio_hip_augment_compose(self.h, int(do_augment)), "augment_compose")
 
@@ -440,7 +461,7 @@ class RvioHip:
         return xy, un
 
     def time_kernel(self, which, iters=20):
-        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection, 10 the landmark cloud kernel, 11 the gray conversion of the last colour or raw (16-bit, Bayer) image in the form the frame launched, 12 the odometry record kernel, 13 the IMU-pose kernel on the state and IMU batch of the last frame, 14 the IMU-covariance kernel on the same operands (HIP events, handle stream)"""
+        """average device time (us) of one hot kernel: 0 solve, 1 KLT, 2 per-feature build, 3 share reduction, 4 U/G/P1, 5 Joseph form, 6 cornerSubPix, 7 U/G/P1 + Joseph form as launched, 8 feat_prop_kernel as the pipelined frame launches it (state restored), 9 the detector's greedy selection, 10 the landmark cloud kernel, 11 the gray conversion of the last colour or raw (16-bit, Bayer) image in the form the frame launched, 12 the odometry record kernel, 13 the IMU-pose kernel on the state and IMU batch of the last frame, 14 the IMU-covariance kernel on the same operands, 15 the landmark-covariance kernel on the last update's cloud and operands (HIP events, handle stream)"""
         us = C.c_float(0)
         self._ck(self.L.rvio_hip_debug_time_kernel(self.h, int(which), int(iters), C.byref(us)), "debug_time_kernel")
         return float(us.value)

@@ -2,7 +2,10 @@
 (device detector, rvio_hip_frame_dev back to back, one drain at the end of a window), the cloud switched off and on in alternation in ONE
 process — windows of 20 and 200 steps, three repeats each — and landmark_kernel alone (rvio_hip_debug_time_kernel(10), HIP events).
 
-  python tools/landmark_cost.py [--cfg B E] [--out FILE]        one JSON line per configuration (also appended to FILE)
+  python tools/landmark_cost.py [--cfg B E] [--out FILE] [--cov]    one JSON line per configuration (also appended to FILE)
+
+--cov: the same alternation one level up — the cloud stays on, the landmark covariance (rvio_hip_set_landmark_cov, csrc/landmark_cov.hip) is
+switched off and on: "off" is then cloud only, "on" cloud + covariance; the kernel timed alone is landmark_cov_kernel (hook 15).
 
 With the cloud on, a getter per frame would synchronise the pipeline: the timed windows read nothing back (the kernel runs behind every
 update all the same); the cloud of the last frame is read once at the end of a window as a check that it is there."""
@@ -18,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(name, windows=(20, 200), repeats=3, warm=40):
+def run(name, windows=(20, 200), repeats=3, warm=40, cov=False):
     import torch
     import bench
     from rvio_amd import abi, hip
@@ -40,13 +43,16 @@ def run(name, windows=(20, 200), repeats=3, warm=40):
 
     frames(warm)
     h.set_landmarks(True)   # (first enable: allocation, outside every timed window)
+    if cov:
+        h.set_landmark_cov(True)
+    switch = h.set_landmark_cov if cov else h.set_landmarks
     frames(4)
     h.sync()
     rates = {}
     for K in windows:
         for rep in range(repeats):
             for on in (False, True):
-                h.set_landmarks(on)
+                switch(on)
                 h.sync()
                 t0 = time.perf_counter()
                 frames(K)
@@ -55,13 +61,17 @@ def run(name, windows=(20, 200), repeats=3, warm=40):
                 if on:
                     lm = h.landmarks()
                     assert lm["frame"] > 0 and lm["n"] > 0, lm
-    h.set_landmarks(True)
+                    assert not cov or h.landmark_cov()["n"] == lm["n"]
+    switch(True)
     frames(2)
     h.sync()
-    us = h.time_kernel(10, 200)
+    us = h.time_kernel(15 if cov else 10, 200)
     info = h.frame_info()
     h.close()
-    out = dict(cfg=name, features=cfg.n_features, window=cfg.max_track_len - 1, landmark_kernel_us=round(us, 3), device_error=info["device_error"])
+    out = dict(cfg=name, features=cfg.n_features, window=cfg.max_track_len - 1, device_error=info["device_error"])
+    out["landmark_cov_kernel_us" if cov else "landmark_kernel_us"] = round(us, 3)
+    if cov:
+        out["off"], out["on"] = "cloud only", "cloud + covariance"
     for K in windows:
         off, on = np.array(rates["%d_off" % K]), np.array(rates["%d_on" % K])
         out["w%d" % K] = dict(off_fps=[round(v, 1) for v in off], on_fps=[round(v, 1) for v in on],
@@ -73,9 +83,10 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg", nargs="+", default=["B", "E"])
     ap.add_argument("--out", default=None)
+    ap.add_argument("--cov", action="store_true", help="the cloud stays on; alternate the landmark covariance instead")
     a = ap.parse_args()
     for name in a.cfg:
-        res = run(name)
+        res = run(name, cov=a.cov)
         line = json.dumps(res)
         print(line, flush=True)
         if a.out:
