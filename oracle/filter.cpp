@@ -110,7 +110,13 @@ struct FeatOut {
 // Updater.cc:109-455 for one feature.  Pcc = Pk1k.block(24,24,6n,6n).
 // probe (tests only): evaluate the measurement model at a GIVEN inverse-depth triple instead of the LM result, and hand out the
 // residual / Jacobians as they are before the nullspace projection (finite-difference pin of U3, tests/test_oracle_pins.py)
-struct FeatProbe { const double* pf = nullptr; Mat* Hx_raw = nullptr; Mat* Hf_raw = nullptr; std::vector<double>* r_raw = nullptr; };
+struct FeatProbe { const double* pf = nullptr; Mat* Hx_raw = nullptr; Mat* Hf_raw = nullptr; std::vector<double>* r_raw = nullptr; struct FeatTrace* trace = nullptr; };
+// trace (tests only): what the LM loop of U2 decided, iteration by iteration (tests/test_feature_update_model.py: the branch census of the
+// hand-built tracks).  step[it]: 1 = the cost did not rise and the step was taken, 0 = rejected (lambda * 10; lastCost is overwritten all the
+// same, Updater.cc:257-262); cost / last_cost: the pair compared in iteration it; dp2: the depth component of a taken step (0 where rejected).
+// exit_iter: the iteration whose break left the loop, -1 when all ten ran.  invalid: 0 = a triple came out, 1 = the angle test in front of the
+// loop (:158), 2 = the angle test behind it, 3 = rho infinite, 4 = rho < 0 (:265-269, tested in this order).
+struct FeatTrace { int n_iter = 0, exit_iter = -1, invalid = 0; int step[10] = {0}; double cost[10] = {0}, last_cost[10] = {0}, dp2[10] = {0}; };
 
 FeatOut feature_rows(const rvio_config* cfg, const Extr& ex, double sig, const double* x, int n_clones,
                      const Mat& Pcc, unsigned char type, const float* meas, int L, const FeatProbe* probe = nullptr) {
@@ -142,7 +148,8 @@ FeatOut feature_rows(const rvio_config* cfg, const Extr& ex, double sig, const d
     double psi = std::atan2((double)fx0, 1.0);
     double rho = 0.;
     out.phi = phi; out.psi = psi; out.rho = rho;
-    if (std::fabs(phi) > .5 * 3.14 || std::fabs(psi) > .5 * 3.14) return out;
+    FeatTrace* const tr = probe ? probe->trace : nullptr;
+    if (std::fabs(phi) > .5 * 3.14 || std::fabs(psi) > .5 * 3.14) { if (tr) tr->invalid = 1; return out; }
 
     V3 ep = v3(std::cos(phi) * std::sin(psi), std::sin(phi), std::cos(phi) * std::cos(psi));
     double Jang[3][2] = {{-std::sin(phi) * std::sin(psi), std::cos(phi) * std::cos(psi)},
@@ -193,6 +200,7 @@ FeatOut feature_rows(const rvio_config* cfg, const Extr& ex, double sig, const d
             float px = (float)(h[0] / h[2]), py = (float)(h[1] / h[2]);
             accumulate(H, meas[2 * (i + 1)] - px, meas[2 * (i + 1) + 1] - py);
         }
+        if (tr) { tr->n_iter = it + 1; tr->cost[it] = cost; tr->last_cost[it] = lastCost; tr->step[it] = cost <= lastCost; }
         if (cost <= lastCost) {  // :235-256
             Mat A(3, 3);
             for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) A(a, b) = HTH[a][b];
@@ -203,13 +211,15 @@ FeatOut feature_rows(const rvio_config* cfg, const Extr& ex, double sig, const d
             Jang[0][0] = -std::sin(phi) * std::sin(psi); Jang[0][1] = std::cos(phi) * std::cos(psi);
             Jang[1][0] = std::cos(phi);                  Jang[1][1] = 0;
             Jang[2][0] = -std::sin(phi) * std::cos(psi); Jang[2][1] = -std::cos(phi) * std::sin(psi);
-            if (std::fabs(lastCost - cost) < 1e-6 && dp[2] < 1e-6) break;
+            if (tr) tr->dp2[it] = dp[2];
+            if (std::fabs(lastCost - cost) < 1e-6 && dp[2] < 1e-6) { if (tr) tr->exit_iter = it; break; }
             lambda *= .1; lastCost = cost;
         } else {  // :257-262 (quirk D.5: lastCost is overwritten on reject too)
             lambda *= 10; lastCost = cost;
         }
     }
     out.phi = phi; out.psi = psi; out.rho = rho;
+    if (tr) tr->invalid = (std::fabs(phi) > .5 * 3.14 || std::fabs(psi) > .5 * 3.14) ? 2 : std::isinf(rho) ? 3 : rho < 0 ? 4 : 0;
     if (std::fabs(phi) > .5 * 3.14 || std::fabs(psi) > .5 * 3.14 || std::isinf(rho) || rho < 0) return out;  // :265-269
 
     if (type == '2') { nTrackLength = (int)std::ceil(.5 * nTrackLength); nTrackPhases = nTrackLength - 1; }  // :271-275
@@ -563,6 +573,23 @@ int orc_feature_model(const rvio_config* cfg, const double* x, int xdim, unsigne
         for (int j = 0; j < 3; ++j) Hf_rowmajor[i * 3 + j] = Hf(i, j);
     }
     return M;
+}
+
+// The LM loop of U2 for one feature, decision by decision (struct FeatTrace above).  ints[0..2] = iterations run, the iteration of the break
+// (-1: none), the validity test that failed (0: none); ints[3..12] = step taken per iteration; dbl = cost[10] | last_cost[10] | dp2[10];
+// pf_out: the triple as it left the loop (also where it is invalid).  Returns 1 when the feature is valid.
+int orc_feature_trace(const rvio_config* cfg, const double* x, int xdim, unsigned char type, const float* meas, int L,
+                      int32_t ints[13], double dbl[30], double pf_out[3]) {
+    const int n = (xdim - 26) / 7;
+    const Extr ex = extrinsics(cfg);
+    Mat Pcc = Mat::identity(6 * n);
+    FeatTrace t;
+    FeatProbe pr; pr.trace = &t;
+    FeatOut fo = feature_rows(cfg, ex, sigma_im(cfg), x, n, Pcc, type, meas, L, &pr);
+    ints[0] = t.n_iter; ints[1] = t.exit_iter; ints[2] = t.invalid;
+    for (int i = 0; i < 10; ++i) { ints[3 + i] = t.step[i]; dbl[i] = t.cost[i]; dbl[10 + i] = t.last_cost[i]; dbl[20 + i] = t.dp2[i]; }
+    if (pf_out) { pf_out[0] = fo.phi; pf_out[1] = fo.psi; pf_out[2] = fo.rho; }
+    return t.invalid == 0;
 }
 
 // The two halves of orc_update, separately (analysis of the rank truncation, tests/test_truncation.py):

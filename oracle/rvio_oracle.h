@@ -55,6 +55,12 @@ void orc_update(const rvio_config* cfg, const double* x, int xdim, const double*
 int orc_feature_model(const rvio_config* cfg, const double* x, int xdim, unsigned char type, const float* meas, int L,
                       const double* pf, double* r_out, double* Hx_rowmajor, double* Hf_rowmajor, double* pf_out);
 
+/* Tests only: the decisions of the LM loop of U2 for one feature (oracle/filter.cpp: struct FeatTrace): ints = {iterations run, iteration
+ * of the break or -1, failed validity test (0 none, 1 angle before the loop, 2 angle behind it, 3 rho infinite, 4 rho < 0), step taken [10]},
+ * dbl = cost[10] | last_cost[10] | dp2[10]; returns 1 when a valid triple came out. */
+int orc_feature_trace(const rvio_config* cfg, const double* x, int xdim, unsigned char type, const float* meas, int L,
+                      int32_t ints[13], double dbl[30], double pf_out[3]);
+
 /* The two halves of orc_update (analysis of the rank truncation Updater.cc:516-529, tests/test_truncation.py):
  * orc_update_stack = U1..U6, returns M and the stacked pair (Hw row-major M x 6n, r) of the accepted features;
  * orc_update_from_stack = U7..U10 on a given pair; row_norms (may be NULL) = norms of the first min(M,12n) rows after the sweep */

@@ -958,6 +958,55 @@ def landmark_sigma(cfg):
     return float(max(np.float32(cfg.sigma_px), np.float32(cfg.sigma_py)))
 
 
+def _feature_rows_as(cal, x, ftype, L, pf, dt, with_hx=True, first_exact=False):
+    """The measurement model of one feature at the triple pf = (phi, psi, rho), every operation in the scalar type `dt`: the relative-pose chain
+    over the nPh = L - 1 clones of the track and the raw rows of all L observations.  Shared by landmark_cov_model_as and
+    feature_update_model_as.  Written in the point scaled by rho, Y_i = rho X_i (Y_0 = R_ic e + rho t_ic, Y_{i+1} = R_i (Y_i - rho p_i)), so
+    that rho = 0 (no parallax) is an ordinary argument:
+      h_i = R_ci (Y_i - rho t_ic)  (the predicted pixel is h_i[:2] / h_i[2]),   Hf_i = Hp_i [R_ci RI_i R_ic Jang | R_ci ((RI_i - I) t_ic + tI_i)],
+      Hx_i[clone j < i] = Hp_i R_ci RI_i RI_{j+1}^T [ [Y_{j+1} x] | -rho R_j ]
+    first_exact: the first observation as Updater.cc:186-206,297-313 take it — h_0 = e and Hf_0 = Hp_0 Jang, without the factor R_ci R_ic, which is
+    the identity only as far as the configured extrinsic rotation is orthonormal (the EuRoC T_bc: to 6e-13).
+    Returns a dict: x (as dt), n, nPh, c0 (the first clone of the track), rho, e, Jang, Ric, tic, R, RI, tI, Y (lists over the chain), h (L x 3), Hf
+    (2L x 3), Hx (2L x 6n; zeros when with_hx is False)."""
+    x = np.asarray(x, dt)
+    n = (len(x) - 26) // 7
+    L = int(L)
+    nPh = L - 1
+    one = "1" if ftype in ("1", b"1", ord("1")) else "2"
+    assert ftype in ("1", b"1", ord("1"), "2", b"2", ord("2")) and 1 <= nPh <= n
+    skew, q2r, _ = _ops_as(dt)
+    T = np.array([dt(v) for v in cal.T_bc]).reshape(4, 4)
+    Ric, tic = T[0:3, 0:3], T[0:3, 3]
+    Rci = Ric.T
+    c0 = n - nPh if one == "1" else 0
+    phi, psi, rho = (dt(v) for v in pf)
+    e = np.array([np.cos(phi) * np.sin(psi), np.sin(phi), np.cos(phi) * np.cos(psi)], dt)
+    Jang = np.array([[-np.sin(phi) * np.sin(psi), np.cos(phi) * np.cos(psi)], [np.cos(phi), dt(0)],
+                     [-np.sin(phi) * np.cos(psi), -np.cos(phi) * np.sin(psi)]], dt)
+    I3 = np.eye(3, dtype=dt)
+    R, Y, RI, tI = [], [Ric @ e + rho * tic], [I3], [np.zeros(3, dt)]
+    for i in range(nPh):
+        a = 26 + 7 * (c0 + i)
+        Ri = q2r(x[a: a + 4])
+        R.append(Ri)
+        Y.append(Ri @ (Y[-1] - rho * x[a + 4: a + 7]))
+        tI.append(Ri @ (tI[-1] - x[a + 4: a + 7]))
+        RI.append(Ri @ RI[-1])
+    h, Hf, Hx = np.zeros((L, 3), dt), np.zeros((2 * L, 3), dt), np.zeros((2 * L, 6 * n), dt)
+    for i in range(L):
+        exact0 = first_exact and i == 0
+        h[i] = e if exact0 else Rci @ (Y[i] - rho * tic)               # rho times the point in camera i (t_ci = -R_ci t_ic)
+        Hp = np.array([[1 / h[i, 2], dt(0), -h[i, 0] / (h[i, 2] * h[i, 2])], [dt(0), 1 / h[i, 2], -h[i, 1] / (h[i, 2] * h[i, 2])]], dt)
+        tc = Rci @ ((RI[i] - I3) @ tic + tI[i])
+        Hf[2 * i: 2 * i + 2, 0:2] = Hp @ Jang if exact0 else Hp @ (Rci @ RI[i] @ Ric @ Jang)
+        Hf[2 * i: 2 * i + 2, 2] = Hp @ tc
+        for j in range(i if with_hx else 0):
+            c = 6 * (c0 + j)
+            Hx[2 * i: 2 * i + 2, c: c + 6] = Hp @ Rci @ ((RI[i] @ RI[j + 1].T) @ np.hstack([skew(Y[j + 1]), -rho * R[j]]))
+    return dict(x=x, n=n, nPh=nPh, c0=c0, rho=rho, e=e, Jang=Jang, Ric=Ric, tic=tic, R=R, RI=RI, tI=tI, Y=Y, h=h, Hf=Hf, Hx=Hx)
+
+
 def landmark_cov_model_as(cal, x, P, ftype, L, meas, pf, dtype=np.longdouble, sigma=None, hf_only=False):
     """The covariance of one cloud point evaluated in `dtype` throughout (np.longdouble: the truth the tests hold the device and the float64
     model to).  cal: anything with T_bc (rvio_config, rvio_calibration); x, P: the state and covariance the update READ; ftype: '1' / '2' (or
@@ -976,48 +1025,18 @@ def landmark_cov_model_as(cal, x, P, ftype, L, meas, pf, dtype=np.longdouble, si
     at or below LANDMARK_COV_PIVOT_EPS of its diagonal entry): the covariances and rho_sigma are NaN, the points are filled.  hf_only: stop
     behind Hf and the points (P is not read; what a Gauss-Newton triangulation needs per step).  Calls nothing from the library or the oracle."""
     dt = np.dtype(dtype).type
-    x = np.asarray(x, dt)
     P = None if hf_only else np.asarray(P, dt)
-    n = (len(x) - 26) // 7
+    c = _feature_rows_as(cal, x, ftype, L, pf, dt, with_hx=not hf_only)
+    x, n, nPh, c0, rho, e, Jang, Ric, R, RI, Hf, Hx = (c[k] for k in ("x", "n", "nPh", "c0", "rho", "e", "Jang", "Ric", "R", "RI", "Hf", "Hx"))
     d = 24 + 6 * n
     L = int(L)
-    nPh = L - 1
-    one = "1" if ftype in ("1", b"1", ord("1")) else "2"
-    assert ftype in ("1", b"1", ord("1"), "2", b"2", ord("2")) and 1 <= nPh <= n
     skew, q2r, _ = _ops_as(dt)
     sig = dt(landmark_sigma(cal) if sigma is None else sigma)
-    T = np.array([dt(v) for v in cal.T_bc]).reshape(4, 4)
-    Ric, tic = T[0:3, 0:3], T[0:3, 3]
-    Rci = Ric.T
-    c0 = n - nPh if one == "1" else 0
-    phi, psi, rho = (dt(v) for v in pf)
-    e = np.array([np.cos(phi) * np.sin(psi), np.sin(phi), np.cos(phi) * np.cos(psi)], dt)
-    Jang = np.array([[-np.sin(phi) * np.sin(psi), np.cos(phi) * np.cos(psi)], [np.cos(phi), dt(0)],
-                     [-np.sin(phi) * np.cos(psi), -np.cos(phi) * np.sin(psi)]], dt)
-    I3 = np.eye(3, dtype=dt)
-    R, X, RI, tI = [], [Ric @ (e / rho) + tic], [I3], [np.zeros(3, dt)]
-    for i in range(nPh):
-        a = 26 + 7 * (c0 + i)
-        Ri = q2r(x[a: a + 4])
-        R.append(Ri)
-        X.append(Ri @ (X[-1] - x[a + 4: a + 7]))
-        tI.append(Ri @ (tI[-1] - x[a + 4: a + 7]))
-        RI.append(Ri @ RI[-1])
+    X = [Y / rho for Y in c["Y"]]                       # the IMU-frame point at every image of the track
 
     def D(i, j):   # d X_i / d (error of clone j), j < i
         return (RI[i] @ RI[j + 1].T) @ np.hstack([skew(X[j + 1]), -R[j]])
 
-    Hf, Hx = np.zeros((2 * L, 3), dt), np.zeros((2 * L, 6 * n), dt)
-    for i in range(L):
-        pc = Rci @ (X[i] - tic)                       # the point in camera i (t_ci = -R_ci t_ic)
-        h = rho * pc
-        Hp = np.array([[1 / h[2], dt(0), -h[0] / (h[2] * h[2])], [dt(0), 1 / h[2], -h[1] / (h[2] * h[2])]], dt)
-        tc = Rci @ ((RI[i] - I3) @ tic + tI[i])
-        Hf[2 * i: 2 * i + 2, 0:2] = Hp @ (Rci @ RI[i] @ Ric @ Jang)
-        Hf[2 * i: 2 * i + 2, 2] = Hp @ tc
-        for j in range(0 if hf_only else i):
-            c = 6 * (c0 + j)
-            Hx[2 * i: 2 * i + 2, c: c + 6] = rho * (Hp @ Rci @ D(i, j))
     if hf_only:
         RG = q2r(x[0:4])
         return dict(Hf=Hf, p_r=X[nPh], p_w=RG.T @ (X[nPh] - x[4:7]))
@@ -1066,6 +1085,85 @@ def landmark_cov_model_as(cal, x, P, ftype, L, meas, pf, dtype=np.longdouble, si
 def landmark_cov_model(cal, x, P, ftype, L, meas, pf, sigma=None, hf_only=False):
     """NumPy float64 model of csrc/landmark_cov.hip with analytic Jacobians: landmark_cov_model_as evaluated in float64 (see there)"""
     return landmark_cov_model_as(cal, x, P, ftype, L, meas, pf, dtype=np.float64, sigma=sigma, hf_only=hf_only)
+
+
+# ---- the per-feature stage of the update (U3 .. U5 of Updater::update and the feature's share of the information block) at a GIVEN triple
+def _nullspace_rows_as(Hf, Hx, r, N, dt, basis):
+    """(Hn, rn): the rows of Q2^T [Hx | r], Q2 an orthonormal basis of the left nullspace of the first N columns of Hf, every operation in dt.
+    basis 'householder': N reflectors; 'givens': the reference's sweep (Updater.cc:370-402: column by column, rows bottom-up, each rotation
+    built from the pair it zeroes).  Both leave the rows N .. M - 1; what is formed from them (gamma, A, b) does not depend on the choice."""
+    M = Hf.shape[0]
+    W = np.hstack([Hf[:, :N], Hx, r.reshape(M, 1)]).astype(dt)
+    if basis == "householder":
+        for k in range(N):
+            v = W[k:, k].copy()
+            nv = np.sqrt(v @ v)
+            if nv == 0:
+                continue
+            v[0] += nv if v[0] >= 0 else -nv
+            W[k:, :] -= np.outer(v, (dt(2) / (v @ v)) * (v @ W[k:, :]))
+    else:
+        assert basis == "givens"
+        for k in range(N):
+            for m in range(M - 1, k, -1):
+                p, q = W[m - 1, k], W[m, k]
+                nn = np.sqrt(p * p + q * q)
+                if nn == 0:
+                    continue
+                c, s = p / nn, q / nn
+                a, b = W[m - 1, :].copy(), W[m, :].copy()
+                W[m - 1, :], W[m, :] = c * a + s * b, c * b - s * a
+    return W[N:, N: N + Hx.shape[1]], W[N:, -1]
+
+
+def feature_update_model_as(cal, x, P, ftype, L, meas, pf, dtype=np.longdouble, sigma=None, basis="householder"):
+    """What the per-feature stage of the update hands on for ONE feature, evaluated in `dtype` throughout at the given triple pf = (phi, psi,
+    rho) — np.longdouble: the truth the tests hold the device's gate and information share to.  All L observations went into pf; the rows are
+    the first Lu = L (type '1') or ceil(L / 2) (type '2', Updater.cc:271-275) of them, the columns start at clone n - (Lu - 1) (type '1') or 0.
+      r      measurement minus predicted pixel; the pixel is rounded to float32 and the difference taken in float32 (Updater.cc:307-308,338-339)
+      N      2 if |Hf[:, 2]| < 1e-4 (no depth column to project out, Updater.cc:372-377), else 3;  ndof = 2 Lu - N
+      Q_f    an orthonormal basis of the span of the first N columns of Hf;  Hn = Q2^T Hx, rn = Q2^T r over its complement
+      gamma  rn^T (Hn Pcc Hn^T + sigma^2 I)^-1 rn  by a Cholesky factorisation written out in dtype (np.linalg would drop to float64)
+      A, b   Hx^T (I - Q_f Q_f^T) Hx  (6n x 6n) and Hx^T (I - Q_f Q_f^T) r  (6n): the feature's share of the information block
+    None of these depends on the basis chosen (`basis`: 'householder' or the reference's 'givens' sweep).  Returns dict(N, ndof, gamma, A, b,
+    S_cond = cond(Hn Pcc Hn^T + sigma^2 I) (a float64 figure), Lu, cols = (cLo, cHi) the feature's non-zero column range, r, rn_norm, hf2 =
+    |Hf[:, 2]|, r_norm = |r| and hx_norms = the column norms of Hx before the projection: the scales of a backward error).  The chain and the
+    raw rows are _feature_rows_as, shared with landmark_cov_model_as; nothing from the library or the oracle."""
+    dt = np.dtype(dtype).type
+    c = _feature_rows_as(cal, x, ftype, L, pf, dt, first_exact=True)
+    n = c["n"]
+    one = "1" if ftype in ("1", b"1", ord("1")) else "2"
+    Lu = int(L) if one == "1" else (int(L) + 1) // 2
+    M = 2 * Lu
+    Hf, Hx = c["Hf"][:M], c["Hx"][:M]
+    z = np.asarray(meas, np.float32)[:Lu]
+    px = np.stack([c["h"][:Lu, 0] / c["h"][:Lu, 2], c["h"][:Lu, 1] / c["h"][:Lu, 2]], axis=1).astype(np.float32)
+    r32 = (z - px).astype(np.float32).reshape(-1)
+    r = r32.astype(dt)
+    hf2 = np.sqrt(Hf[:, 2] @ Hf[:, 2])
+    N = 2 if hf2 < dt(1e-4) else 3
+    Hn, rn = _nullspace_rows_as(Hf, Hx, r, N, dt, basis)
+    ndof = M - N
+    sig = dt(landmark_sigma(cal) if sigma is None else sigma)
+    Pcc = np.asarray(P, dt)[24:, 24:]
+    S = Hn @ Pcc @ Hn.T
+    S = (dt(1) / dt(2)) * (S + S.T) + sig * sig * np.eye(ndof, dtype=dt)
+    Lc = np.zeros((ndof, ndof), dt)
+    for k in range(ndof):
+        Lc[k, k] = np.sqrt(S[k, k] - Lc[k, :k] @ Lc[k, :k])
+        for i in range(k + 1, ndof):
+            Lc[i, k] = (S[i, k] - Lc[i, :k] @ Lc[k, :k]) / Lc[k, k]
+    y = np.zeros(ndof, dt)
+    for k in range(ndof):
+        y[k] = (rn[k] - Lc[k, :k] @ y[:k]) / Lc[k, k]
+    c0 = n - (Lu - 1) if one == "1" else 0
+    return dict(N=N, ndof=ndof, gamma=y @ y, A=Hn.T @ Hn, b=Hn.T @ rn, S_cond=float(np.linalg.cond(S.astype(np.float64))), Lu=Lu,
+                cols=(6 * c0, 6 * (c0 + Lu - 1)), r=r32, rn_norm=np.sqrt(rn @ rn), hf2=hf2, r_norm=np.sqrt(r @ r), hx_norms=np.sqrt(np.sum(Hx * Hx, axis=0)))
+
+
+def feature_update_model(cal, x, P, ftype, L, meas, pf, sigma=None, basis="householder"):
+    """NumPy float64 model of the per-feature stage at a given triple: feature_update_model_as evaluated in float64 (see there)"""
+    return feature_update_model_as(cal, x, P, ftype, L, meas, pf, dtype=np.float64, sigma=sigma, basis=basis)
 
 
 # ---- map landmarks: pixel observations of known world points (rvio_hip_update_map*, csrc/map_rows.hip in front of the auxiliary update)

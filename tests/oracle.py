@@ -115,6 +115,23 @@ def feature_model(cfg, x, ftype, meas, L, pf=None):
     return r[:M].copy(), Hx[:M].copy(), Hf[:M].copy(), pfo
 
 
+INVALID_NAMES = ("", "angle-before", "angle-after", "rho-inf", "rho-negative")
+
+
+def feature_trace(cfg, x, ftype, meas, L):
+    """the decisions of the LM loop of U2 for one feature (oracle/filter.cpp: struct FeatTrace): dict(valid, n_iter, exit_iter (-1: all ten
+    iterations ran), invalid (one of INVALID_NAMES), step [n_iter] (True: taken), cost, last_cost, dp2 [n_iter], pf)"""
+    x = np.ascontiguousarray(x, float)
+    meas = np.ascontiguousarray(meas, np.float32)
+    ints, dbl, pf = np.zeros(13, np.int32), np.zeros(30), np.zeros(3)
+    L_ = lib()
+    L_.orc_feature_trace.restype = C.c_int
+    ok = L_.orc_feature_trace(C.byref(cfg), _p(x, dp), len(x), C.c_ubyte(int(ftype)), _p(meas, fp), int(L), _p(ints, ip), _p(dbl, dp), _p(pf, dp))
+    k = int(ints[0])
+    return dict(valid=bool(ok), n_iter=k, exit_iter=int(ints[1]), invalid=INVALID_NAMES[int(ints[2])], step=ints[3: 3 + k].astype(bool),
+                cost=dbl[:k].copy(), last_cost=dbl[10: 10 + k].copy(), dp2=dbl[20: 20 + k].copy(), pf=pf)
+
+
 def update_stack(cfg, x, P, types, lens, meas):
     """U1..U6: the stacked (Hw [M, 6n], r [M]) of the accepted features and nGoodFeatCount"""
     x = np.ascontiguousarray(x, float)
